@@ -6,6 +6,19 @@ Workload (BASELINE.json metric "SpMV effective GB/s (fp64, 20k x 20k STENCIL5); 
 5-point stencil (400 M unknowns, centre 5 / neighbours -1, b = 1, x0 = 0, tol 1e-6), the
 configuration of reference docs/PROBLEM_SIZE_SCALING_RESULTS.md:40-47, on N row slabs.
 
+Two kinds of run:
+  plain     (the default) only what the headline needs: set-up, W warm-up solves, the K timed solves (they must agree on
+            iterations, verdict and final residual, or the run is UNMEASURED), the outputs if --dump-outputs asks, and the line:
+            metric, value, unit, higher_is_better, dtype, ms_per_step, vs_baseline and a short config.
+  --full    the plain run and, after its timed steps, everything else below: the in-loop SpMV roofline, stream yardsticks,
+            parity against the golden history, agreement of the ranks' histories, stage breakdown, placement / tile records,
+            host throttle counters, and at N = 1 the spmv, compare, scaling_probe and cpu_baseline legs (each still switched off by
+            its --no-* option). Every key of the line that is not listed under `plain` comes from --full.
+  --dump-outputs DIR  after the timed steps, what the last timed solve handed its caller, as float64 .npy files (< 64 MB in all):
+            x_sample.npy (the solution x at x_sample_index.npy: every row up to 2^21 rows, else 2^21 rows drawn with a fixed seed),
+            residual_history.npy (||r_k||, k = 0 .. iterations) and solve_stats.npy (iterations, converged, final residual). The
+            inputs (b = 1, x0 = 0, the generator's matrix) are the same in every run with the same arguments.
+
   step      one complete CG solve (14 iterations to tolerance), the unit the reference times;
             inputs (slab CSR, b, x0) are resident in HBM before the timed region; every step starts
             from the stored x0 and ends with the solution x in HBM (the deferred x update's flush pass
@@ -13,7 +26,7 @@ configuration of reference docs/PROBLEM_SIZE_SCALING_RESULTS.md:40-47, on N row 
   value     CG iterations per second, whole job = K * iterations / (max over ranks of the time
             of K steps, bracketed by barrier + torch.cuda.synchronize() on both sides).
   scaling   strong: the 400 M-unknown problem is fixed, slabs shrink as N grows.
-  roofline  the dominant kernel of the timed region, the solver's STENCIL5 SpMV (row-lds kernel, fused with the
+  roofline  (--full) the dominant kernel of the timed region, the solver's STENCIL5 SpMV (row-lds kernel, fused with the
             p.Ap partials): algorithmic bytes of one launch (8*nnz + 8*cols + 8*rows of the slab,
             SURVEY.md 8d) / its average duration, from HIP events recorded on the solver's stream
             around every in-loop launch of the timed steps. Peak 8 TB/s (MI355X_MICROARCH.md).
@@ -25,11 +38,11 @@ configuration of reference docs/PROBLEM_SIZE_SCALING_RESULTS.md:40-47, on N row 
             launch from profiles/hbm_traffic.json, only while that file's hash of csrc/spmv_kernels.hip matches.
             spmv_standalone: BASELINE's FIRST metric, the `spmv` leg below in brief (median ms, effective GB/s by
             both of the reference's formulas, algorithmic GB/s, frac of peak); placement: what set-up placement did.
-  spmv      (N = 1 only; runs AFTER the CG leg, so that the solver's slab is the first large allocation of the process)
+  spmv      (--full, N = 1 only; runs AFTER the CG leg, so that the solver's slab is the first large allocation of the process)
             the reference's other headline: stencil5-csr operator on its own staging vectors (the ones run_timed's kernel
             works on), x = 1, 5 warm-ups + 10 timed launches, >2 sigma outliers dropped, median -> "effective" GB/s by both
             of the reference's byte formulas (spmv_metrics.cu:85-101 and the published 12*nnz+16*rows).
-  scaling_probe  (N = 1 only; a PROJECTION, never part of `value`; the role processes load the LAB build of the library,
+  scaling_probe  (--full, N = 1 only; a PROJECTION, never part of `value`; the role processes load the LAB build of the library,
             lib/libspmv_amd_lab.so, the only one with stand-in slabs) the real per-rank slabs of a 2 / 4 / 8-GPU
             run of this problem (rows [r*N/P, (r+1)*N/P), 160 KB halos), edge rank and a two-neighbour rank,
             each in a FRESH process of its own (what a rank of a real job is: inside one process the second slab
@@ -41,19 +54,19 @@ configuration of reference docs/PROBLEM_SIZE_SCALING_RESULTS.md:40-47, on N row 
             the reference's :405-413 -> :728-731), median of 5 solves, for the slab and for the full problem alike.
             The latency of an all-reduce BETWEEN devices cannot be measured on one GPU: the efficiency is given for a
             range of latencies.
-  cpu_baseline  (N = 1, rank 0) the serial C oracle (oracle/spmv_oracle.c, 1 core): its CG on the FULL 400 M-unknown
+  cpu_baseline  (--full, N = 1, rank 0) the serial C oracle (oracle/spmv_oracle.c, 1 core): its CG on the FULL 400 M-unknown
             problem when the host's MemAvailable allows (~45 GB, ~33 s on one EPYC core; `history_vs_committed_golden_ok` then
             re-verifies the golden history on the spot), else on a 10 000 x 10 000 sample scaled by rows (`sample` says which);
             `spmv` = its STENCIL5 and CSR SpMV on the same matrix (1 warm-up + 3 runs, median) in the reference's
             effective-GB/s formula and in algorithmic GB/s; `all_cores` = the same loops under OpenMP.
-  compare   (N = 1; after the spmv leg) BASELINE configs 2 and 5 through get_operator with the reference's 5 + 10 / median rule,
+  compare   (--full, N = 1; after the spmv leg) BASELINE configs 2 and 5 through get_operator with the reference's 5 + 10 / median rule,
             each operator checksum-gated (sum y = n^2 + 4n, ||y||^2 exact): 10 000^2 stencil5-csr / cusparse-csr, 15 000^2 ellpack /
             stencil5-ellpack / stencil5-csr / cusparse-csr. FLAT scalars in `roofline` (the driver's record keeps scalars of
             roofline / config only): stencil10k_ms, csr10k_ms, stencil15k_ms, csr15k_ms, ell15k_ms, ell_stencil15k_ms, each
             with its *_frac (algorithmic bytes of the format / median / 8 TB/s), beside spmv20k_median_ms,
             spmv20k_effective_gbs, spmv20k_effective_gbs_published_formula, spmv20k_frac (BASELINE's first metric).
 
-  placement (rank 0's slab) and spmv.output_placement: on this part a SpMV is ~4.5 % faster when the vector it writes lies in another
+  placement (--full; rank 0's slab) and spmv.output_placement: on this part a SpMV is ~4.5 % faster when the vector it writes lies in another
             class of 32 GiB address regions than the data it reads, and only hipMalloc decides the class (profiles/r04_spmv_regions.txt):
             at set-up, outside every timed region, the operator times its kernel on three allocations for y, one 32 GiB region apart, and keeps the fastest;
             the slab does the same for its coefficient stream, which must not share Ap's class (csrc/cg_slab.hip). Addresses only, same bits.
@@ -61,13 +74,13 @@ configuration of reference docs/PROBLEM_SIZE_SCALING_RESULTS.md:40-47, on N row 
   config.loop_shape  which shape the solver's loop took and who decided ("single rank", "pipeline (verified against the plain order
             at creation)", "plain: ..."; include/spmv_amd/api.h): the library compares its overlapped pipeline with the plain order on
             the first slab of every communicator and falls back by itself -- the line then says `degraded`.
-  config.host_throttled_periods_in_timed_steps / _usec_  CPU throttling of this container (cgroup cpu.stat) over the timed steps: a
+  config.host_throttled_periods_in_timed_steps / _usec_  (--full) CPU throttling of this container (cgroup cpu.stat) over the timed steps: a
             stalled host thread idles the GPU (profiles/r06_throttle_probe.txt); zero rules the host out of a slow `value`.
             The timed solves must agree on (iterations, verdict, final residual) or the run is UNMEASURED.
-  parity_vs_golden  every run, every N: the residual history of the timed solves against the committed CPU-oracle
+  parity_vs_golden  (--full) every N: the residual history of the timed solves against the committed CPU-oracle
             history of the same grid (tests/golden/known_answers.json: 3, 81, 512, 2000, 10000, 15000, 20000); above 1e-10
             relative, or on another iteration count, the run is UNMEASURED (exit 3), whatever it timed.
-  breakdown per rank, from ONE extra solve after the timed region with HIP events at the stage boundaries of every
+  breakdown (--full) per rank, from ONE extra solve after the timed region with HIP events at the stage boundaries of every
             iteration and around every halo exchange (no host syncs, overlap intact): interior SpMV, wait for the halo +
             boundary rows, p.Ap sum + all-reduce, r update, r.r sum + all-reduce + scalar step, direction update, gap
             before the next iteration; max / min over the ranks as the reference reports its timers (mgpu :748-800).
@@ -80,11 +93,12 @@ configuration of reference docs/PROBLEM_SIZE_SCALING_RESULTS.md:40-47, on N row 
             SPMV_AMD_BENCH_ALLREDUCE=mailbox swaps the two legs.
 
 Wall time, worst case of every DEFAULT path (the driver's limit for this file is 600 s):
-  N = 1   torch import + library (<= 120 s on a fresh box) + SpMV leg (~5 s) + (W + K + 1) solves of ~0.11 s + stream ceiling
+  plain   torch import + library + slab set-up (~0.4 s at 20 000^2) + (W + K) solves of ~0.11 s: a few seconds besides the solves.
+  N = 1, --full   torch import + library (<= 120 s on a fresh box) + SpMV leg (~5 s) + (W + K + 1) solves of ~0.11 s + stream ceiling
           (~0.2 s) + compare leg (six operator set-ups, ~15 s) + scaling probe (8 role processes one after the other under one
           child, the child ended after --probe-timeout = 240 s; ~30 s when healthy) + CPU baseline (full size: ~70 s of host
           work, no GPU; sample: ~25 s) : < 480 s, ~150 s when healthy.
-  N > 1   the same import + rendezvous (gloo, 120 s limit for the store) + (W + K + 1) solves + nothing else: rank 0 prints
+  N > 1   the same import + rendezvous (gloo, 120 s limit for the store) + (W + K solves, + 1 with --full) + nothing else: rank 0 prints
           the line as soon as the ranks have agreed on the measured leg. Every wait on a peer inside a solve ends after
           SPMV_AMD_WATCHDOG_S = 60 s with a report; gloo collectives give up after 180 s; a self-launched run is ended by
           its parent after --launch-timeout = 420 s, with a line that says so. < 420 s in every case, ~20 s when healthy.
@@ -573,6 +587,30 @@ def parity_vs_golden(n, hist, iterations):
             "fixture": f"tests/golden/known_answers.json cases[{n}:5.0].cg.history (CPU oracle)"}
 
 
+DUMP_SAMPLE_ROWS = 1 << 21  # 16 MB of x and 16 MB of its row indices: below the 64 MB a dump may take
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(out_dir, slab, st, rank):
+    """--dump-outputs: what the last timed solve handed its caller, as float64 .npy files in out_dir (rank 0 writes them; every rank
+    takes part in the gather of x). x has up to 4e8 rows: past DUMP_SAMPLE_ROWS a fixed-seed sample of rows is kept, the same rows
+    for the same grid in every run, and their indices (exact in float64) beside it."""
+    x = slab.gather()  # collective over the slab's communicator; x lands on rank 0
+    if rank != 0:
+        return
+    rows = len(x)
+    if rows <= DUMP_SAMPLE_ROWS:
+        idx = np.arange(rows, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, rows, size=DUMP_SAMPLE_ROWS, dtype=np.int64))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "x_sample.npy"), np.ascontiguousarray(x[idx], dtype=np.float64))
+    np.save(os.path.join(out_dir, "x_sample_index.npy"), idx.astype(np.float64))
+    del x
+    np.save(os.path.join(out_dir, "residual_history.npy"), np.asarray(slab.history(), dtype=np.float64))
+    np.save(os.path.join(out_dir, "solve_stats.npy"), np.array([st.iterations, st.converged, st.residual_norm], dtype=np.float64))
+
+
 class Unmeasured(Exception):
     """A leg cannot produce a number every rank stands behind; the reason is the same text on all ranks."""
 
@@ -705,14 +743,12 @@ def measure_leg(c, allreduce_kind):
         degraded = (degraded + "; " if degraded else "") + loop_shape
         if rank == 0:
             print(f"bench.py: {loop_shape}", file=sys.stderr)
-    placement = slab.placement()  # set-up work, outside the timed region (csrc/cg_slab.hip, place_coefficients)
-    tile_runs = slab.tile_runs()  # ditto: row-lds tiles per XCD and run, the rule's neighbours timed at creation
-    setup_ms = slab.setup_ms()    # wall ms of creation's phases; none of it inside the timed region
 
     def barrier():
         if multi:
             dist.barrier()
 
+    full = args.full
     try:
         for _ in range(args.warmup):
             st = slab.solve()
@@ -722,24 +758,22 @@ def measure_leg(c, allreduce_kind):
             os.kill(os.getpid(), signal.SIGKILL)
         barrier()
         torch.cuda.synchronize()
-        throttle0 = cgroup_throttle_counters()
+        throttle0 = cgroup_throttle_counters() if full else None
         t0 = time.perf_counter()
         # in-loop SpMV launches are event-timed on their own stream inside the solver: every 7th launch, the phase moving on by
         # one with every solve, so the timed steps cover every iteration of the loop (each pair of events costs two barrier
-        # packets next to the launch; csrc/cg_slab.hip, spmv_event_stride)
+        # packets next to the launch; csrc/cg_slab.hip, spmv_event_stride). A plain run does not read them out.
         spmv_each, event_ms, outcomes = [], [], []
         for _ in range(args.steps):
             st = slab.solve()
-            spmv_each.extend(float(v) for v in slab.spmv_launch_ms())
-            event_ms.append(st.time_total_ms)
+            if full:
+                spmv_each.extend(float(v) for v in slab.spmv_launch_ms())
+                event_ms.append(st.time_total_ms)
             outcomes.append((int(st.iterations), int(st.converged), float(st.residual_norm).hex()))
-        spmv_ms, spmv_launches = float(np.sum(spmv_each)), len(spmv_each)
         torch.cuda.synchronize()
         barrier()
         dt = time.perf_counter() - t0
-        throttle1 = cgroup_throttle_counters()
-        host_throttled = None if throttle0 is None or throttle1 is None else {"periods": throttle1[0] - throttle0[0], "usec": throttle1[1] - throttle0[1]}
-        rank_ms = [float(v) for v in gather(c, dt / args.steps * 1e3)]  # every rank's own wall time per step: the spread is load imbalance
+        rank_ms_own = dt / args.steps * 1e3
         if multi:
             t = torch.tensor([dt], dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -748,6 +782,20 @@ def measure_leg(c, allreduce_kind):
         # gate below looks at the LAST solve's history; a solve that ended early would be a fast solve, not a right one)
         if len(set(outcomes)) != 1:
             raise Unmeasured(f"the {args.steps} timed solves disagree on (iterations, converged, final residual): {sorted(set(outcomes))}")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, slab, st, rank)
+        leg = {"allreduce": allreduce, "allreduce_kind": allreduce_kind if comm is not None else "none", "transport": transport, "degraded": degraded,
+               "dt": dt, "ms_per_step": dt / args.steps * 1e3, "iterations": st.iterations, "converged": bool(st.converged),
+               "final_residual": st.residual_norm, "loop_shape": loop_shape}
+        if not full:
+            return leg
+        spmv_ms, spmv_launches = float(np.sum(spmv_each)), len(spmv_each)
+        throttle1 = cgroup_throttle_counters()
+        host_throttled = None if throttle0 is None or throttle1 is None else {"periods": throttle1[0] - throttle0[0], "usec": throttle1[1] - throttle0[1]}
+        rank_ms = [float(v) for v in gather(c, rank_ms_own)]  # every rank's own wall time per step: the spread is load imbalance
+        placement = slab.placement()  # set-up work, outside the timed region (csrc/cg_slab.hip, place_coefficients)
+        tile_runs = slab.tile_runs()  # ditto: row-lds tiles per XCD and run, the rule's neighbours timed at creation
+        setup_ms = slab.setup_ms()    # wall ms of creation's phases; none of it inside the timed region
         hist = slab.history()
         # every rank computes its scalars from the same all-reduced values: the histories must agree bit for bit
         hexes = gather(c, [float(v).hex() for v in hist])
@@ -761,15 +809,12 @@ def measure_leg(c, allreduce_kind):
         # one more solve with stage-boundary events (outside the timed region): where an iteration's time goes on this rank
         st_t, tl = slab.timeline_solve()
         breakdown = gather(c, dict(tl, rank=rank, rows=slab.n_local, timeline_solve_ms=st_t.time_total_ms))
-        leg = {"allreduce": allreduce, "allreduce_kind": allreduce_kind if comm is not None else "none", "transport": transport, "degraded": degraded,
-               "dt": dt, "ms_per_step": dt / args.steps * 1e3, "iterations": st.iterations, "converged": bool(st.converged),
-               "final_residual": st.residual_norm, "history": [float(v) for v in hist], "rank_ms": rank_ms, "parity_vs_golden": parity,
-               "ranks_agree_on_history": True if multi else None, "breakdown": breakdown, "variant": slab.variant(),
-               "local_rows": slab.n_local, "local_nnz": slab.local_nnz, "spmv_ms": spmv_ms, "spmv_launches": spmv_launches,
-               "event_ms_per_solve": float(np.median(event_ms)),
-               "rccl_ranks": comm.transport_ranks() if (comm is not None and transport == "rccl") else 0,
-               "placement": placement, "tile_runs": tile_runs, "setup_ms": setup_ms, "loop_shape": loop_shape,
-               "host_throttled": host_throttled}
+        leg.update({"history": [float(v) for v in hist], "rank_ms": rank_ms, "parity_vs_golden": parity,
+                    "ranks_agree_on_history": True if multi else None, "breakdown": breakdown, "variant": slab.variant(),
+                    "local_rows": slab.n_local, "local_nnz": slab.local_nnz, "spmv_ms": spmv_ms, "spmv_launches": spmv_launches,
+                    "event_ms_per_solve": float(np.median(event_ms)),
+                    "rccl_ranks": comm.transport_ranks() if (comm is not None and transport == "rccl") else 0,
+                    "placement": placement, "tile_runs": tile_runs, "setup_ms": setup_ms, "host_throttled": host_throttled})
     finally:
         slab.destroy()
         if comm is not None:
@@ -847,7 +892,8 @@ def run_leg_children(c, kind, role, extra_env, timeout_s):
                                                                         "GROUP_WORLD_SIZE", "TORCH_NCCL_ASYNC_ERROR_HANDLING")]:
         env.pop(k)
     argv = [sys.executable, os.path.abspath(__file__), "--gpus", str(c.world), "--steps", str(c.args.steps), "--warmup", str(c.args.warmup),
-            "--grid", str(c.args.grid), "--leg-only", kind, "--leg-role", role] + (["--no-ceiling"] if c.args.no_ceiling else [])
+            "--grid", str(c.args.grid), "--leg-only", kind, "--leg-role", role] + (["--no-ceiling"] if c.args.no_ceiling else []) + \
+           (["--full"] if c.args.full else []) + (["--dump-outputs", c.args.dump_outputs] if c.args.dump_outputs and role == "headline" else [])
     rec, rc, err = None, None, ""
     try:
         child = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=timeout_s)
@@ -909,8 +955,9 @@ def other_allreduce_leg(c, kind, timeout_s):
     rec = out["rec"] or {"error": "child leg printed no record"}
     if "leg" in rec:
         leg = rec["leg"]
-        rec = {k: leg[k] for k in ("allreduce", "ms_per_step", "iterations", "rank_ms", "parity_vs_golden", "ranks_agree_on_history", "rccl_ranks")} | {
-            "breakdown": breakdown_summary(leg["breakdown"])}
+        rec = {k: leg[k] for k in ("allreduce", "ms_per_step", "iterations", "rank_ms", "parity_vs_golden", "ranks_agree_on_history", "rccl_ranks") if k in leg}
+        if "breakdown" in leg:  # --full
+            rec["breakdown"] = breakdown_summary(leg["breakdown"])
     if c.multi:
         try:
             c.dist.barrier()
@@ -919,8 +966,35 @@ def other_allreduce_leg(c, kind, timeout_s):
     return rec
 
 
+BASELINE_NOTE = "reference's published CG iters/s on the same problem at the same GPU count, A100-SXM4-80GB (BASELINE.md); no MI355X number is published"
+
+
+def launched_by():
+    return ("bench.py (self-launched ranks)" if os.environ.get("SPMV_AMD_BENCH_SELF_LAUNCHED") == "1" else
+            ("external launcher (RANK/WORLD_SIZE in the environment)" if "RANK" in os.environ else "single process"))
+
+
+def plain_line(args, base, leg, extras, world, n, rows, nnz):
+    """The line of a plain run (rank 0 only): the headline and what the timed solves themselves returned, nothing measured besides."""
+    degraded = extras.get("degraded") or leg["degraded"]
+    value = args.steps * leg["iterations"] / leg["dt"]
+    headline = world in A100_CG_ITERS_PER_S and n == 20000 and degraded is None
+    out = dict(base, value=value, ms_per_step=leg["dt"] / args.steps * 1e3,
+               vs_baseline=value / A100_CG_ITERS_PER_S[world] if headline else None, baseline_note=BASELINE_NOTE,
+               config={"workload": f"CG on the {n}x{n} 5-point stencil ({rows} unknowns, {nnz} nnz), b=1, x0=0, tol 1e-6",
+                       "grid": n, "unknowns": rows, "nnz": nnz, "partition": f"{world} row slab(s)", "transport": leg["transport"],
+                       "loop_shape": leg.get("loop_shape"), "iterations_per_solve": leg["iterations"], "converged": leg["converged"],
+                       "final_residual": leg["final_residual"]},
+               transport=leg["transport"], allreduce=leg["allreduce"], launched_by=launched_by())
+    if degraded:
+        out["degraded"] = degraded
+    if extras.get("first_leg_failure"):
+        out["first_leg_failure"] = extras["first_leg_failure"]
+    return out
+
+
 def build_line(args, base, leg, spmv, extras, world, n, rows, nnz, compare=None):
-    """The benchmark line from a finished leg (rank 0 only; touches neither the GPU nor another rank)."""
+    """The --full benchmark line from a finished leg (rank 0 only; touches neither the GPU nor another rank)."""
     # template argument: <kMode = 1 (SpMV + p.Ap partials)>
     kernel_symbol = {"stencil5/row-lds": "stencil5_rowlds_kernel<1>", "stencil5/row-direct": "stencil5_rowdirect_kernel<true>"}.get(leg["variant"], leg["variant"])
     transport, allreduce, degraded, dt, iterations = leg["transport"], leg["allreduce"], extras.get("degraded") or leg["degraded"], leg["dt"], leg["iterations"]
@@ -1021,7 +1095,7 @@ def build_line(args, base, leg, spmv, extras, world, n, rows, nnz, compare=None)
         headline = world in A100_CG_ITERS_PER_S and n == 20000 and degraded is None
         out = dict(base, value=value, ms_per_step=dt / args.steps * 1e3,
                    vs_baseline=value / A100_CG_ITERS_PER_S[world] if headline else None,
-                   baseline_note="reference's published CG iters/s on the same problem at the same GPU count, A100-SXM4-80GB (BASELINE.md); no MI355X number is published",
+                   baseline_note=BASELINE_NOTE,
                    config={"workload": f"CG on the {n}x{n} 5-point stencil ({rows} unknowns, {nnz} nnz), b=1, x0=0, tol 1e-6",
                            # BASELINE's first metric as scalars (reference formula spmv_metrics.cu:85-101 / the published 12 nnz + 16 rows)
                            "spmv_effective_gbs": None if spmv is None or "effective_gbs" not in spmv else spmv["effective_gbs"],
@@ -1040,8 +1114,7 @@ def build_line(args, base, leg, spmv, extras, world, n, rows, nnz, compare=None)
                            "residual_history": leg["history"]},
                    transport=transport, allreduce=allreduce, ranks_agree_on_history=leg["ranks_agree_on_history"], parity_vs_golden=leg["parity_vs_golden"],
                    rccl_ranks=leg["rccl_ranks"], devices=devices, rank_ms_per_step=leg["rank_ms"], breakdown=breakdown_summary(leg["breakdown"]),
-                   launched_by="bench.py (self-launched ranks)" if os.environ.get("SPMV_AMD_BENCH_SELF_LAUNCHED") == "1" else
-                   ("external launcher (RANK/WORLD_SIZE in the environment)" if "RANK" in os.environ else "single process"),
+                   launched_by=launched_by(),
                    roofline=roofline)
         if leg.get("placement") is not None:
             out["placement"] = leg["placement"]
@@ -1063,6 +1136,11 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--grid", type=int, default=20000, help="n of the n x n stencil (default: the 400M-unknown headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, measure and check everything else too (roofline, stream yardsticks, golden parity, stage "
+                         "breakdown; at N = 1 the spmv, compare, scaling-probe and CPU-baseline legs); a plain run does only the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed solve returned (sampled x, residual history, iterations / verdict / residual) as float64 .npy files into DIR")
     ap.add_argument("--cpu-sample-grid", type=int, default=None,
                     help="grid of a CPU-baseline SAMPLE, scaled by rows (default: the full workload when the host's MemAvailable allows -- ~33 s on one "
                          "core at 20000 -- else 10000)")
@@ -1092,6 +1170,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0 or args.gpus < 1 or args.grid < 2:
         ap.error("--steps >= 1, --warmup >= 0, --gpus >= 1 and --grid >= 2 are required")
+    if args.allreduce_ab and not args.full:
+        ap.error("--allreduce-ab measures a second configuration: it belongs to --full")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
 
     if args.scaling_probe_only is None and args.probe_role is None and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))
@@ -1185,6 +1267,12 @@ def main():
         except Unmeasured as e:
             give_up(str(e))
     transport = leg["transport"]
+
+    if not args.full:
+        # a plain run: the headline line and nothing else
+        if rank == 0:
+            emit(plain_line(args, base, leg, extras, world, n, rows, nnz))
+        leave(0)
 
     spmv = None
     if world == 1 and not multi and not args.no_spmv:

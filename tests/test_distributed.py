@@ -155,12 +155,12 @@ def test_bench_distributed_path_with_one_rank():
     env = dict(os.environ, SPMV_AMD_BENCH_FORCE_DIST="1", SPMV_AMD_FORCE_COLLECTIVES="1", SPMV_AMD_LIB="lab", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--grid", "1024", "--no-cpu-baseline", "--no-spmv"]
+           "--grid", "1024", "--full", "--no-cpu-baseline", "--no-spmv"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout + out.stderr
     dist_line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     plain = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--grid", "1024",
-                            "--no-cpu-baseline", "--no-spmv"], capture_output=True, text=True, timeout=600)
+                            "--full", "--no-cpu-baseline", "--no-spmv"], capture_output=True, text=True, timeout=600)
     assert plain.returncode == 0, plain.stdout + plain.stderr
     plain_line = json.loads([l for l in plain.stdout.splitlines() if l.startswith("{")][-1])
     assert dist_line["config"]["transport"] == "rccl" and dist_line["n_gpus"] == 1
@@ -181,12 +181,12 @@ def test_multi_rank_pipeline_over_rccl_with_the_rank_as_its_own_neighbour(grid):
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--grid", str(grid), "--no-cpu-baseline", "--no-spmv"]
+           "--grid", str(grid), "--full", "--no-cpu-baseline", "--no-spmv"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout + out.stderr
     nb = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     plain = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--grid", str(grid),
-                            "--no-cpu-baseline", "--no-spmv"], capture_output=True, text=True, timeout=600)
+                            "--full", "--no-cpu-baseline", "--no-spmv"], capture_output=True, text=True, timeout=600)
     assert plain.returncode == 0, plain.stdout + plain.stderr
     one = json.loads([l for l in plain.stdout.splitlines() if l.startswith("{")][-1])
     assert nb["config"]["transport"] == "rccl" and nb["config"]["converged"]
@@ -218,7 +218,7 @@ def check_multi_rank_line(line, world, mailbox_must_work=True, with_ab=False):
         assert all(k in r for k in TIMELINE_KEYS) and r["spmv_interior_us"] > 0 and r["iteration_us"] > 0
     assert set(TIMELINE_KEYS) - {"iterations"} <= set(b["max_over_ranks"]) and b["max_over_ranks"]["iteration_us"] >= b["min_over_ranks"]["iteration_us"]
     if not with_ab:
-        assert "allreduce_ab" not in line  # a default run measures north_star's path and nothing else
+        assert "allreduce_ab" not in line  # without --allreduce-ab a run measures north_star's path and nothing else
         return
     ab = line["allreduce_ab"]
     assert ab["headline"] == "rccl" and ab["rccl"] == line["ms_per_step"]
@@ -245,13 +245,13 @@ FORCED_MULTI_ENV = dict(SPMV_AMD_BENCH_FORCE_DIST="1", SPMV_AMD_FORCE_COLLECTIVE
 def test_bench_multi_rank_default_run_is_lean(tmp_path):
     """One GPU, the complete multi-rank pipeline (SPMV_AMD_BENCH_FORCE_DIST + SPMV_AMD_SELF_NEIGHBOUR: RCCL send / recv of the
     halo rows on the side stream, split SpMV launches, ncclAllReduce of both dot products) on the 2000 x 2000 grid, for which a
-    golden history is committed, WITHOUT any option: exactly one process touched the GPU (the rank's leg child: the rank process
+    golden history is committed, with --full and no other option: exactly one process touched the GPU (the rank's leg child: the rank process
     itself is a supervisor that only rendezvouses; no second leg, no probe), ONE line, with parity_vs_golden and the stage
     breakdown and no allreduce_ab, degraded or first_leg_failure."""
     log = tmp_path / "procs.jsonl"
     env = dict(os.environ, SPMV_AMD_BENCH_PROCESS_LOG=str(log), **FORCED_MULTI_ENV)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--grid", "2000",
-                          "--no-cpu-baseline", "--no-spmv"], env=env, capture_output=True, text=True, timeout=600)
+                          "--full", "--no-cpu-baseline", "--no-spmv"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout + out.stderr
     lines = _json_lines(out.stdout)
     assert len(lines) == 1
@@ -274,7 +274,7 @@ def test_bench_restarts_fresh_ranks_without_overlap_after_a_watchdog_exit(tmp_pa
     env = dict(os.environ, SPMV_AMD_BENCH_PROCESS_LOG=str(log), SPMV_AMD_TEST_WEDGE_OVERLAPPED_EXCHANGE="1", SPMV_AMD_WATCHDOG_S="5", **FORCED_MULTI_ENV)
     t0 = time.monotonic()
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--grid", "2000",
-                          "--no-cpu-baseline", "--no-spmv"], env=env, capture_output=True, text=True, timeout=600)
+                          "--full", "--no-cpu-baseline", "--no-spmv"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and time.monotonic() - t0 < 300, out.stdout + out.stderr
     lines = _json_lines(out.stdout)
     assert len(lines) == 1
@@ -299,7 +299,7 @@ def test_bench_restarts_fresh_ranks_without_overlap_after_wrong_numbers(tmp_path
     log = tmp_path / "procs.jsonl"
     env = dict(os.environ, SPMV_AMD_BENCH_PROCESS_LOG=str(log), SPMV_AMD_TEST_WEDGE_OVERLAPPED_EXCHANGE="2", **FORCED_MULTI_ENV)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--grid", "2000",
-                          "--no-cpu-baseline", "--no-spmv"], env=env, capture_output=True, text=True, timeout=600)
+                          "--full", "--no-cpu-baseline", "--no-spmv"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout + out.stderr
     lines = _json_lines(out.stdout)
     assert len(lines) == 1
@@ -319,7 +319,7 @@ def test_bench_multi_rank_line_carries_both_allreduce_legs_when_asked():
     allreduce_ab added."""
     env = dict(os.environ, **FORCED_MULTI_ENV)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--grid", "2000",
-                          "--no-cpu-baseline", "--no-spmv", "--allreduce-ab"], env=env, capture_output=True, text=True, timeout=600)
+                          "--full", "--no-cpu-baseline", "--no-spmv", "--allreduce-ab"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout + out.stderr
     lines = _json_lines(out.stdout)
     assert len(lines) == 2
@@ -336,7 +336,7 @@ def test_bench_headline_survives_a_second_leg_that_is_killed(tmp_path):
     log = tmp_path / "procs.jsonl"
     env = dict(os.environ, SPMV_AMD_BENCH_TEST_KILL_LEG_CHILD="1", SPMV_AMD_BENCH_PROCESS_LOG=str(log), **FORCED_MULTI_ENV)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--grid", "2000",
-                          "--no-cpu-baseline", "--no-spmv", "--allreduce-ab"], env=env, capture_output=True, text=True, timeout=600)
+                          "--full", "--no-cpu-baseline", "--no-spmv", "--allreduce-ab"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout + out.stderr
     lines = _json_lines(out.stdout)
     assert len(lines) == 2 and lines[0]["value"] is not None and lines[0]["parity_vs_golden"]["ok"] and "allreduce_ab" not in lines[0]
@@ -352,7 +352,7 @@ def test_bench_refuses_a_history_that_misses_the_golden(tmp_path):
     golden["cases"]["512:5.0"]["cg"]["history"][3] *= 1.0 + 1e-9
     bad = tmp_path / "known_answers.json"
     bad.write_text(json.dumps(golden))
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--grid", "512", "--no-cpu-baseline", "--no-spmv"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--grid", "512", "--full", "--no-cpu-baseline", "--no-spmv"]
     good = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert good.returncode == 0 and _json_lines(good.stdout)[-1]["parity_vs_golden"]["ok"], good.stdout + good.stderr
     out = subprocess.run(cmd, env=dict(os.environ, SPMV_AMD_BENCH_GOLDEN=str(bad)), capture_output=True, text=True, timeout=600)
@@ -401,7 +401,7 @@ def test_bench_over_rccl_between_devices(world, tmp_path):
     log = tmp_path / "procs.jsonl"
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", SPMV_AMD_BENCH_PROCESS_LOG=str(log))
     env.pop("RANK", None), env.pop("WORLD_SIZE", None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--grid", "2000"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--grid", "2000", "--full"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout + out.stderr
     lines = _json_lines(out.stdout)
@@ -590,7 +590,7 @@ def test_bench_two_ranks_control_flow_on_one_gpu():
     explicitly allowed: the ranks agree (over gloo) to switch, the run completes with the same residual history as one
     rank, and the line is marked degraded and carries no vs_baseline."""
     env = dict(os.environ, SPMV_AMD_BENCH_DEVICE="0", SPMV_AMD_BENCH_ALLOW_STAGED="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--grid", "1024"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--grid", "1024", "--full"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout + out.stderr
     lines = _json_lines(out.stdout)
@@ -601,7 +601,7 @@ def test_bench_two_ranks_control_flow_on_one_gpu():
     assert [d["rank"] for d in two["devices"]] == [0, 1] and all(d["device"] == 0 for d in two["devices"])
     assert "cpu_baseline" not in two and "spmv" not in two  # N = 1 only legs
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--grid", "1024",
-                          "--no-cpu-baseline", "--no-spmv"], capture_output=True, text=True, timeout=600)
+                          "--full", "--no-cpu-baseline", "--no-spmv"], capture_output=True, text=True, timeout=600)
     one = _json_lines(one.stdout)[-1]
     assert two["config"]["iterations_per_solve"] == one["config"]["iterations_per_solve"]
     h2, h1 = np.array(two["config"]["residual_history"]), np.array(one["config"]["residual_history"])

@@ -217,3 +217,101 @@ def test_reference_mpi_main_finds_its_ranks_and_fails_loudly_without_gpus():
     # the library itself has no MPI dependency
     ldd = subprocess.run(["ldd", os.path.join(ROOT, "cuda-spmv-benchmark_amd", "lib", "libspmv_amd.so")], capture_output=True, text=True).stdout
     assert "libmpi" not in ldd
+
+
+def load_bench(name):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_options_plain_full_and_dump():
+    """--full and --dump-outputs exist; the second all-reduce leg is a second configuration and is refused outside --full (argparse
+    stops before torch or the GPU is touched)."""
+    import sys
+    out = run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"])
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs" in out.stdout
+    out = run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--allreduce-ab"])
+    assert out.returncode == 2 and "--full" in out.stderr and not out.stdout
+
+
+def test_bench_dump_keeps_a_fixed_sample_of_a_large_solution(tmp_path):
+    """--dump-outputs on a solution longer than DUMP_SAMPLE_ROWS: float64 files only, below 64 MB in all, the same rows in every
+    run (fixed seed), each sampled value the solution's at the index written beside it; a rank other than 0 writes nothing."""
+    import numpy as np
+    bench = load_bench("bench_module_dump")
+
+    class Slab:
+        def __init__(self, rows):
+            self.rows = rows
+
+        def gather(self):
+            return np.arange(self.rows, dtype=np.float64) * 0.5
+
+        def history(self):
+            return np.array([2.0, 1.0, 0.25])
+
+    class Stats:
+        iterations, converged, residual_norm = 2, 1, 0.25
+
+    rows = 3 * bench.DUMP_SAMPLE_ROWS + 7
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), Slab(rows), Stats, 0)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["residual_history.npy", "solve_stats.npy", "x_sample.npy", "x_sample_index.npy"]
+    a = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert all(v.dtype == np.float64 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    idx = a["x_sample_index.npy"]
+    assert len(idx) == bench.DUMP_SAMPLE_ROWS and idx.min() >= 0 and idx.max() < rows and np.all(np.diff(idx) >= 0)
+    assert np.array_equal(a["x_sample.npy"], idx * 0.5)
+    assert a["solve_stats.npy"].tolist() == [2.0, 1.0, 0.25] and a["residual_history.npy"].tolist() == [2.0, 1.0, 0.25]
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), a[f])
+    bench.dump_outputs(str(tmp_path / "c"), Slab(10), Stats, 1)
+    assert not (tmp_path / "c").exists()
+
+
+PLAIN_LINE_KEYS = {"metric", "unit", "n_gpus", "steps", "warmup", "higher_is_better", "scaling", "dtype", "data", "value", "ms_per_step",
+                   "vs_baseline", "baseline_note", "config", "transport", "allreduce", "launched_by"}
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_what_the_timed_solve_returned(tmp_path, golden, O):
+    """`bench.py --gpus 1 --steps 3 --warmup 1 --grid 512 --dump-outputs DIR`, twice: ONE line holding the headline keys and nothing
+    that --full adds; value and ms_per_step describe the same 3 steps; the dumped x is the oracle's solution, the dumped history the
+    committed golden one, and the second run's files equal the first's bit for bit (same arguments, same inputs)."""
+    import sys
+
+    import numpy as np
+
+    from conftest import hist_err
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"dump{k}"
+        out = run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--grid", "512",
+                   "--dump-outputs", str(d)])
+        assert out.returncode == 0, out.stdout + out.stderr
+        lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        runs.append((lines[0], d))
+    line, d = runs[0]
+    assert set(line) == PLAIN_LINE_KEYS, set(line) ^ PLAIN_LINE_KEYS
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["dtype"] == "f64" and line["higher_is_better"] is True
+    assert line["metric"] == "cg_iterations_per_second" and line["unit"] == "CG iterations/s" and line["vs_baseline"] is None
+    its = line["config"]["iterations_per_solve"]
+    assert abs(line["value"] - its * 1e3 / line["ms_per_step"]) <= 1e-9 * line["value"] and line["config"]["converged"]
+    files = sorted(os.listdir(d))
+    assert files == ["residual_history.npy", "solve_stats.npy", "x_sample.npy", "x_sample_index.npy"]
+    arrays = {f: np.load(d / f) for f in files}
+    assert all(v.dtype == np.float64 for v in arrays.values()) and sum(v.nbytes for v in arrays.values()) <= 64 << 20
+    g = golden["cases"]["512:5.0"]["cg"]
+    assert arrays["solve_stats.npy"].tolist()[:2] == [its, 1.0] and its == g["iterations"]
+    assert hist_err(arrays["residual_history.npy"], g["history"]) < 1e-10
+    assert np.array_equal(arrays["x_sample_index.npy"], np.arange(512 * 512, dtype=np.float64))
+    rp, ci, va = O.stencil5_csr(512)
+    xo, _, _ = O.cg_partitioned(rp, ci, va, 512, np.ones(512 * 512), np.zeros(512 * 512), world=1)
+    assert np.max(np.abs(arrays["x_sample.npy"] - xo)) <= 1e-10 * np.max(np.abs(xo))
+    for f in files:
+        assert np.array_equal(np.load(runs[1][1] / f), arrays[f]), f

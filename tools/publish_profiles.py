@@ -67,7 +67,7 @@ rec = {
     "TCC_HIT_sum": pmc.get("TCC_HIT_sum"), "TCC_MISS_sum": pmc.get("TCC_MISS_sum"), "algorithmic_bytes_per_launch": alg,
     "ratio_to_algorithmic": (fetch + write) / alg,
     "source": f"profiles/{tag}_bench_pmc_FETCH_SIZE.csv, {tag}_bench_pmc_WRITE_SIZE.csv (separate rocprofv3 --pmc passes over "
-              "`python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-scaling-probe --no-spmv --no-ceiling`, averages over the in-loop launches)",
+              "`python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-scaling-probe --no-spmv --no-ceiling`, averages over the in-loop launches)",
     "note": "FETCH_SIZE x 1024 x 2 (gfx950 tallies 128-B fabric requests at 64 B; the factor is confirmed in the same passes by "
             "cg_update_r_kernel, whose FETCH_SIZE x 2 equals its 16 B/row of reads) + WRITE_SIZE x 1024. These are L2-to-fabric "
             "bytes: Infinity-Cache hits are counted. The excess over the algorithmic bytes is x[row-n] / x[row+n] missing the "

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Process-to-process spread of the default benchmark on one box: `runs` consecutive
-`python bench.py --no-cpu-baseline --no-scaling-probe` processes (five runs within +-0.5 %?).
+`python bench.py --full --no-cpu-baseline --no-scaling-probe` processes (five runs within +-0.5 %?).
    python tools/run_spread.py [runs=5] [steps=10] [ENV=VALUE ...: a second setting, alternated with the default]"""
 import json
 import os
@@ -17,7 +17,7 @@ settings = [("default", {})] + ([(" ".join(sys.argv[3:]), other)] if other else 
 res = {name: [] for name, _ in settings}
 for k in range(runs):
     for name, extra in (settings if k % 2 == 0 else settings[::-1]):
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-scaling-probe", "--no-compare", "--steps", steps],
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-scaling-probe", "--no-compare", "--steps", steps],
                              env=dict(os.environ, **extra), capture_output=True, text=True, timeout=600)
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if out.returncode != 0 or not lines:
