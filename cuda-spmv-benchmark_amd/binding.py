@@ -101,6 +101,8 @@ DECLARED_SYMBOLS = [
     "spmv_amd_cg_slab_time_spmv", "spmv_amd_cg_slab_set_timeline", "spmv_amd_operator_placement", "spmv_amd_cg_slab_placement", "spmv_amd_cg_slab_tile_runs", "spmv_amd_cg_slab_setup_ms", "spmv_amd_cg_slab_spmv_launch_ms",  "spmv_amd_cg_release_workspace", "spmv_amd_cg_slab_timeline_names", "spmv_amd_cg_slab_timeline", "spmv_amd_cg_slab_variant", "spmv_amd_cg_slab_destroy", "spmv_amd_version", "spmv_amd_write_stencil5_values",
     "spmv_amd_blas1_axpy", "spmv_amd_blas1_axpby", "spmv_amd_blas1_axpy_dev", "spmv_amd_blas1_update_p_dev", "spmv_amd_blas1_dot",
     "spmv_amd_cg_fused_step",
+    "spmv_amd_spmm_device", "spmv_amd_spmm_variant", "spmv_amd_block_to_device", "spmv_amd_block_to_host",
+    "spmv_amd_cg_solve_device_multi", "spmv_amd_cg_last_history_multi", "spmv_amd_cg_multi_workspace_bytes",
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
 LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option"]
@@ -435,6 +437,23 @@ class Operator:
     def free(self):
         self.op.contents.free()
 
+    def run_spmm(self, Xk):
+        """Y = A X for the k = 1..8 columns of Xk (numpy (k, cols)) through spmv_amd_spmm_device; returns Y (k, rows)."""
+        Xk = np.ascontiguousarray(np.atleast_2d(Xk), dtype=np.float64)
+        k = Xk.shape[0]
+        assert Xk.shape[1] == self.cols
+        dx, dy = DeviceBlock.from_host(Xk), DeviceBlock(k, self.rows)
+        try:
+            rc = _multi_lib().spmv_amd_spmm_device(self.name.encode(), k, dx.ptr, dy.ptr)
+            if rc != 0:
+                raise RuntimeError(f"spmm_device -> {rc}")
+            return dy.to_host()
+        finally:
+            dx.free(), dy.free()
+
+    def spmm_variant(self):
+        return _multi_lib().spmv_amd_spmm_variant(self.name.encode()).decode()
+
 
 def cg_solve(op, host_matrix, b, x0, max_iters=1000, tol=1e-6, device=True, verbose=0, timers=0):
     """cg_solve_device (device=True) or cg_solve through the C-ABI; returns x, history, stats."""
@@ -449,6 +468,74 @@ def cg_solve(op, host_matrix, b, x0, max_iters=1000, tol=1e-6, device=True, verb
     hist = np.zeros(max_iters + 1, dtype=np.float64)
     count = lib().spmv_amd_cg_last_history(hist.ctypes.data, len(hist))
     return x, hist[:count].copy(), st
+
+
+# ---------------------------------------------------------------- several right-hand sides (include/spmv_amd/api.h)
+def _multi_lib():
+    """lib() with the signatures of the multi-RHS entry points set."""
+    L = lib()
+    if not getattr(L, "_multi_sigs", False):
+        L.spmv_amd_spmm_device.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.spmv_amd_spmm_variant.argtypes = [C.c_char_p]
+        L.spmv_amd_spmm_variant.restype = C.c_char_p
+        L.spmv_amd_block_to_device.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.spmv_amd_block_to_host.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.spmv_amd_cg_solve_device_multi.argtypes = [C.POINTER(SpmvOperator), C.POINTER(MatrixData), C.c_int, C.c_void_p, C.c_void_p,
+                                                     C.POINTER(CGConfig), C.POINTER(CGStats)]
+        L.spmv_amd_cg_last_history_multi.argtypes = [C.c_int, C.c_void_p, C.c_int]
+        L.spmv_amd_cg_multi_workspace_bytes.argtypes = []
+        L.spmv_amd_cg_multi_workspace_bytes.restype = C.c_size_t
+        L._multi_sigs = True
+    return L
+
+
+class DeviceBlock:
+    """k vectors of n rows on the device, row-interleaved (element (row, j) at [row * k + j], api.h); host side (k, n)."""
+
+    def __init__(self, k, n):
+        self.k, self.n = int(k), int(n)
+        self.ptr = lib().spmv_amd_device_alloc(self.k * self.n * 8)
+
+    @classmethod
+    def from_host(cls, a):
+        a = np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64)
+        v = cls(a.shape[0], a.shape[1])
+        if _multi_lib().spmv_amd_block_to_device(v.k, v.n, a.ctypes.data, v.ptr) != 0:
+            raise RuntimeError("block_to_device failed")
+        return v
+
+    def to_host(self):
+        out = np.empty((self.k, self.n), dtype=np.float64)
+        lib().spmv_amd_device_synchronize()
+        if _multi_lib().spmv_amd_block_to_host(self.k, self.n, self.ptr, out.ctypes.data) != 0:
+            raise RuntimeError("block_to_host failed")
+        return out
+
+    def free(self):
+        if self.ptr:
+            lib().spmv_amd_device_free(self.ptr)
+            self.ptr = None
+
+
+def cg_solve_multi(op, host_matrix, Bk, X0k, max_iters=1000, tol=1e-6, verbose=0, timers=0):
+    """spmv_amd_cg_solve_device_multi: k independent CG solves sharing the SpMM. Bk, X0k: (k, n).
+    Returns X (k, n), a list of k residual histories and a list of k CGStats."""
+    Bk = np.ascontiguousarray(np.atleast_2d(Bk), dtype=np.float64)
+    X = np.ascontiguousarray(np.atleast_2d(X0k), dtype=np.float64).copy()
+    k = Bk.shape[0]
+    assert X.shape == Bk.shape
+    cfg = CGConfig(max_iters, tol, verbose, timers)
+    stats = (CGStats * k)()
+    L = _multi_lib()
+    rc = L.spmv_amd_cg_solve_device_multi(op.op, host_matrix.ptr, k, Bk.ctypes.data, X.ctypes.data, C.byref(cfg), stats)
+    if rc != 0:
+        raise RuntimeError(f"cg_solve_device_multi -> {rc}")
+    hists = []
+    for j in range(k):
+        h = np.zeros(max_iters + 1, dtype=np.float64)
+        count = L.spmv_amd_cg_last_history_multi(j, h.ctypes.data, len(h))
+        hists.append(h[:count].copy())
+    return X, hists, list(stats)
 
 
 class Comm:

@@ -1,0 +1,583 @@
+// cg_multi.hip -- batched CG: up to 8 independent systems A x_j = b_j solved together, one matrix pass per iteration.
+//
+// Each column is its own CG solve -- own alpha, beta, stopping test, history and iteration count, the algebra of
+// cg_solve_device (reference src/solvers/cg_solver.cu:436-706, oracle_cg's device form). The only thing the columns share is
+// the SpMM (spmm_kernels.hip), which reads the coefficients once for all of them. Not block CG: no shared Krylov space.
+//
+// One iteration, five kinds of launch on the default stream (block vectors interleaved, multi_rhs.hpp):
+//   AP = A P with the per-column p.Ap partials | sum + pAp step (active = !done, alpha = rr_old / pAp) |
+//   R -= alpha AP with the r.r partials | sum + rr step (residual, history, verdict, beta) |
+//   X += alpha P, then P = R + beta P unless the column converged in this iteration
+// then one small blocking read of the k column states (the stopping test; ~10 us against milliseconds of work). A converged
+// column is frozen: every kernel leaves its X, R, P, history and iteration count alone from the next iteration on.
+// Bytes per interior row and iteration, per system: (40 + 80 k) / k.
+// No run-ahead, no direction ring, no status protocol: that machinery (cg_slab.hip) buys microseconds per iteration of a
+// single solve; here an iteration is k times longer.
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <vector>
+
+#include "device_runtime.hpp"
+#include "multi_rhs.hpp"
+
+using namespace spmv_amd;
+
+namespace {
+
+constexpr hipStream_t kStream = nullptr;  // default stream, shared with the operators
+constexpr int kBlock = 256;
+constexpr int kSlice = kBlock * 16;  // partials one workgroup of the first reduction stage sums
+
+typedef double dbl2 __attribute__((ext_vector_type(2)));
+
+template <int K>
+__device__ __forceinline__ void load_row(const double* __restrict__ p, double (&o)[K]) {
+    if constexpr (K % 2 == 0) {  // workspace vectors: hipMalloc'd, rows of 8k bytes
+#pragma unroll
+        for (int i = 0; i < K / 2; ++i) {
+            const dbl2 t = reinterpret_cast<const dbl2*>(p)[i];
+            o[2 * i] = t.x, o[2 * i + 1] = t.y;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < K; ++i) o[i] = p[i];
+    }
+}
+
+template <int K>
+__device__ __forceinline__ void store_row(double* __restrict__ p, const double (&v)[K]) {
+    if constexpr (K % 2 == 0) {
+#pragma unroll
+        for (int i = 0; i < K / 2; ++i) {
+            dbl2 t;
+            t.x = v[2 * i], t.y = v[2 * i + 1];
+            reinterpret_cast<dbl2*>(p)[i] = t;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < K; ++i) p[i] = v[i];
+    }
+}
+
+// One partial per column of the workgroup's 256 rows: wave trees, then the four wave sums in wave order (the shape of the
+// SpMM's partials; independent of k and of the column's slot).
+template <int K>
+__device__ __forceinline__ void block_partials(double (&d)[K], double* __restrict__ partials, long long count, long long blk) {
+    __shared__ double s_wave[kBlock / 64][K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) d[j] += __shfl_down(d[j], off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) s_wave[threadIdx.x >> 6][j] = d[j];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < K) {
+        const int j = (int)threadIdx.x;
+        partials[(long long)j * count + blk] = ((s_wave[0][j] + s_wave[1][j]) + s_wave[2][j]) + s_wave[3][j];
+    }
+}
+
+// The vector kernels walk their workgroup's 256 rows x k columns FLAT (as the row-lds SpMM does, spmm_kernels.hip): unit
+// f = threadIdx.x + 256 i (i < P) is row f / P, columns (f % P) * V ... + V - 1, with V = 2 for even k (16-byte accesses), 1
+// else, P = k / V -- every access of one instruction is one contiguous run. Dot products go through LDS back to thread = row
+// and into block_partials: per column, the same shape whatever k is.
+template <int K>
+struct Flat {
+    static constexpr int V = K % 2 == 0 ? 2 : 1;
+    static constexpr int P = K / V;
+};
+
+// Thread = row again: the k products of the thread's row from LDS (every thread of the workgroup calls it: it has a barrier).
+template <int K>
+__device__ __forceinline__ void products_to_rows(const double* prod, double (&d)[K]) {
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < K; ++q) d[q] = prod[threadIdx.x * K + q];
+}
+
+// R = b - A x0 (R holds b on entry: axpby_kernel(1.0, b, -1.0, Ap), cg_solver.cu:48-54), P = R, partials of r.r.
+template <int K>
+__global__ __launch_bounds__(kBlock) void multi_init_residual_kernel(long long n, const double* __restrict__ AP, double* __restrict__ R,
+                                                                    double* __restrict__ P, double* __restrict__ partials, long long count) {
+    constexpr int V = Flat<K>::V, U = Flat<K>::P;
+    __shared__ double prod[kBlock * K];
+    const long long row0 = (long long)blockIdx.x * kBlock;
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+        const int f = (int)threadIdx.x + kBlock * i;
+        const int t = f / U, col0 = (f - t * U) * V;
+        double r[V] = {};
+        if (row0 + t < n) {
+            const long long at = (row0 + t) * K + col0;
+            double ap[V];
+            load_row<V>(AP + at, ap);
+            load_row<V>(R + at, r);
+#pragma unroll
+            for (int q = 0; q < V; ++q) r[q] = fma(1.0, r[q], -1.0 * ap[q]);
+            store_row<V>(R + at, r);
+            store_row<V>(P + at, r);
+        }
+#pragma unroll
+        for (int q = 0; q < V; ++q) prod[t * K + col0 + q] = r[q] * r[q];
+    }
+    double d[K];
+    products_to_rows<K>(prod, d);
+    block_partials<K>(d, partials, count, blockIdx.x);
+}
+
+// r = fma(-alpha, Ap, r) for the active columns (cg_solver.cu:59-74), partials of r.r.
+template <int K>
+__global__ __launch_bounds__(kBlock) void multi_update_r_kernel(long long n, const MultiColumn* __restrict__ cols, const double* __restrict__ AP,
+                                                               double* __restrict__ R, double* __restrict__ partials, long long count) {
+    constexpr int V = Flat<K>::V, U = Flat<K>::P;
+    __shared__ double prod[kBlock * K];
+    const long long row0 = (long long)blockIdx.x * kBlock;
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+        const int f = (int)threadIdx.x + kBlock * i;
+        const int t = f / U, col0 = (f - t * U) * V;
+        double r[V] = {};
+        if (row0 + t < n) {
+            const long long at = (row0 + t) * K + col0;
+            double ap[V];
+            load_row<V>(AP + at, ap);
+            load_row<V>(R + at, r);
+#pragma unroll
+            for (int q = 0; q < V; ++q)
+                if (cols[col0 + q].active) r[q] = fma(-cols[col0 + q].alpha, ap[q], r[q]);
+            store_row<V>(R + at, r);
+        }
+#pragma unroll
+        for (int q = 0; q < V; ++q) prod[t * K + col0 + q] = r[q] * r[q];
+    }
+    double d[K];
+    products_to_rows<K>(prod, d);
+    block_partials<K>(d, partials, count, blockIdx.x);
+}
+
+// x = fma(alpha, p, x) for the active columns; then p = fma(beta, p, r) (update_p_kernel, cg_solver.cu:90-95) for those that
+// did not converge in this iteration.
+template <int K>
+__global__ __launch_bounds__(kBlock) void multi_update_xp_kernel(long long n, const MultiColumn* __restrict__ cols, const double* __restrict__ R,
+                                                                double* __restrict__ P, double* __restrict__ X) {
+    constexpr int V = Flat<K>::V, U = Flat<K>::P;
+    const long long row0 = (long long)blockIdx.x * kBlock;
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+        const int f = (int)threadIdx.x + kBlock * i;
+        const int t = f / U, col0 = (f - t * U) * V;
+        if (row0 + t >= n) continue;
+        const long long at = (row0 + t) * K + col0;
+        double x[V], p[V], r[V];
+        load_row<V>(X + at, x);
+        load_row<V>(P + at, p);
+        load_row<V>(R + at, r);
+#pragma unroll
+        for (int q = 0; q < V; ++q) {
+            const MultiColumn& c = cols[col0 + q];
+            if (c.active) {
+                x[q] = fma(c.alpha, p[q], x[q]);
+                if (!c.done) p[q] = fma(c.beta, p[q], r[q]);
+            }
+        }
+        store_row<V>(X + at, x);
+        store_row<V>(P + at, p);
+    }
+}
+
+// Fixed-shape sum of 256 values in shared memory (every thread calls it); returns the sum in thread 0.
+__device__ __forceinline__ double block_tree(double v, double* s) {
+    s[threadIdx.x] = v;
+    __syncthreads();
+#pragma unroll
+    for (int w = kBlock / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
+        __syncthreads();
+    }
+    return s[0];
+}
+
+// Stage 1: workgroup (s, j) sums partials[j * count + s * kSlice ...] (each thread its strided share in ascending order, then
+// a fixed tree) into slices[j * slice_count + s].
+__global__ __launch_bounds__(kBlock) void multi_reduce_slices_kernel(const double* __restrict__ partials, long long count, int slice_count,
+                                                                    double* __restrict__ slices) {
+    __shared__ double s[kBlock];
+    const int j = (int)blockIdx.y, sl = (int)blockIdx.x;
+    const double* __restrict__ src = partials + (long long)j * count;
+    const long long lo = (long long)sl * kSlice, hi = lo + kSlice < count ? lo + kSlice : count;
+    double acc = 0.0;
+    for (long long i = lo + threadIdx.x; i < hi; i += kBlock) acc += src[i];
+    const double t = block_tree(acc, s);
+    if (threadIdx.x == 0) slices[(long long)j * slice_count + sl] = t;
+}
+
+// Stage 2 + the scalar step of column j (workgroup j). which: 0 = initial residual, 1 = pAp, 2 = r.r.
+__global__ __launch_bounds__(kBlock) void multi_reduce_step_kernel(const double* __restrict__ slices, int slice_count, int which, double tol,
+                                                                  MultiColumn* __restrict__ cols, double* __restrict__ hist, int hist_cap) {
+    __shared__ double s[kBlock];
+    const int j = (int)blockIdx.x;
+    double acc = 0.0;
+    for (int i = (int)threadIdx.x; i < slice_count; i += kBlock) acc += slices[(long long)j * slice_count + i];
+    const double total = block_tree(acc, s);
+    if (threadIdx.x != 0) return;
+    MultiColumn& c = cols[j];
+    double* h = hist + (long long)j * hist_cap;
+    if (which == 0) {
+        c.rr_old = total;
+        c.b_norm = sqrt(total);
+        c.residual = c.b_norm;
+        c.alpha = c.beta = c.pAp = 0.0;
+        c.active = 0, c.done = 0, c.iterations = 0;
+        h[0] = c.b_norm;
+    } else if (which == 1) {
+        c.active = c.done ? 0 : 1;
+        if (c.active) {
+            c.pAp = total;
+            c.alpha = c.rr_old / total;
+        }
+    } else if (c.active) {
+        const double res = sqrt(total);
+        c.iterations += 1;
+        if (c.iterations < hist_cap) h[c.iterations] = res;
+        c.residual = res;
+        if (res / c.b_norm < tol) {
+            c.done = 1;
+        } else {
+            c.beta = total / c.rr_old;
+            c.rr_old = total;
+        }
+    }
+}
+
+template <int K>
+void launch_vec(int which, long long n, const MultiColumn* cols, double* X, double* R, double* P, const double* AP, double* partials,
+                long long count) {
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
+    if (which == 0) hipLaunchKernelGGL((multi_init_residual_kernel<K>), grid, block, 0, kStream, n, AP, R, P, partials, count);
+    else if (which == 1) hipLaunchKernelGGL((multi_update_r_kernel<K>), grid, block, 0, kStream, n, cols, AP, R, partials, count);
+    else hipLaunchKernelGGL((multi_update_xp_kernel<K>), grid, block, 0, kStream, n, cols, R, P, X);
+}
+
+void launch_vector_step(int k, int which, long long n, const MultiColumn* cols, double* X, double* R, double* P, const double* AP,
+                        double* partials, long long count) {
+    switch (k) {
+        case 1: launch_vec<1>(which, n, cols, X, R, P, AP, partials, count); break;
+        case 2: launch_vec<2>(which, n, cols, X, R, P, AP, partials, count); break;
+        case 3: launch_vec<3>(which, n, cols, X, R, P, AP, partials, count); break;
+        case 4: launch_vec<4>(which, n, cols, X, R, P, AP, partials, count); break;
+        case 5: launch_vec<5>(which, n, cols, X, R, P, AP, partials, count); break;
+        case 6: launch_vec<6>(which, n, cols, X, R, P, AP, partials, count); break;
+        case 7: launch_vec<7>(which, n, cols, X, R, P, AP, partials, count); break;
+        default: launch_vec<8>(which, n, cols, X, R, P, AP, partials, count); break;
+    }
+}
+
+int slices_for(long long count) { return (int)((count + kSlice - 1) / kSlice); }
+
+// ---- workspace: kept between calls (like cg_solve_device's), released with it ----
+struct MultiWorkspace {
+    int n = 0, k = 0, device = -1;
+    double *X = nullptr, *R = nullptr, *P = nullptr, *AP = nullptr;
+    double* partials = nullptr;  // k x max(SpMM partials, vector partials)
+    double* slices = nullptr;    // k x slices of that
+    MultiColumn* cols = nullptr;
+    double* hist = nullptr;      // k x hist_cap
+    int hist_cap = 0;
+    long long partial_cap = 0;
+    void release() {
+        device_release(X);
+        device_release(R);
+        device_release(P);
+        device_release(AP);
+        device_release(partials);
+        device_release(slices);
+        device_release(cols);
+        device_release(hist);
+        n = k = 0, device = -1, hist_cap = 0, partial_cap = 0;
+    }
+};
+MultiWorkspace g_multi;
+std::vector<std::vector<double>> g_multi_history;  // of the last batched solve, per column
+
+bool fail(const char* what) {
+    fprintf(stderr, "[CG-MULTI] %s\n", what);
+    return false;
+}
+
+// Allocates the workspace for (n, k, partial slots) if it is not there already. Sized against hipMemGetInfo first: a request
+// that does not fit is refused with a message, never a crash.
+bool ensure_workspace(int n, int k, int device, long long partial_cap, int hist_cap) {
+    MultiWorkspace& w = g_multi;
+    if (w.X != nullptr && (w.n != n || w.k != k || w.device != device || w.partial_cap < partial_cap)) w.release();
+    if (w.X == nullptr) {
+        const size_t vec = (size_t)n * k * sizeof(double);
+        const size_t need = 4 * vec + (size_t)k * partial_cap * sizeof(double) + (size_t)k * slices_for(partial_cap) * sizeof(double) +
+                            (size_t)k * hist_cap * sizeof(double) + ((size_t)64 << 20);
+        size_t free_b = 0, total_b = 0;
+        HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+        if (need > free_b) {
+            fprintf(stderr, "[CG-MULTI] the workspace for %d systems of %d rows needs %.2f GB, the device has %.2f GB free: refused\n", k, n,
+                    need / 1e9, free_b / 1e9);
+            return false;
+        }
+        w.X = device_try_alloc<double>((size_t)n * k);
+        w.R = device_try_alloc<double>((size_t)n * k);
+        w.P = device_try_alloc<double>((size_t)n * k);
+        w.AP = device_try_alloc<double>((size_t)n * k);
+        w.partials = device_try_alloc<double>((size_t)k * partial_cap);
+        w.slices = device_try_alloc<double>((size_t)k * slices_for(partial_cap));
+        w.cols = device_try_alloc<MultiColumn>((size_t)k);
+        if (!w.X || !w.R || !w.P || !w.AP || !w.partials || !w.slices || !w.cols) {
+            w.release();
+            return fail("the workspace could not be allocated: refused");
+        }
+        w.n = n, w.k = k, w.device = device, w.partial_cap = partial_cap;
+    }
+    if (w.hist_cap < hist_cap) {
+        device_release(w.hist);
+        w.hist_cap = 0;
+        w.hist = device_try_alloc<double>((size_t)k * hist_cap);
+        if (w.hist == nullptr) return fail("the history could not be allocated: refused");
+        w.hist_cap = hist_cap;
+    }
+    return true;
+}
+
+void column_checksums(const double* x, int n, double* sum, double* norm) {
+    double s = 0.0, q = 0.0;
+    for (int i = 0; i < n; i++) {
+        s += x[i];
+        q += x[i] * x[i];
+    }
+    *sum = s;
+    *norm = sqrt(q);
+}
+
+bool check_rhs(int nrhs) {
+    if (nrhs < 1 || nrhs > kMaxRhs) {
+        fprintf(stderr, "[multi-rhs] nrhs = %d: 1 to %d right-hand sides are supported\n", nrhs, kMaxRhs);
+        return false;
+    }
+    return true;
+}
+
+// The operator behind `op`, if it has a multi-RHS path and is initialised. Host state only (no HIP call).
+bool usable_operator(const SpmvOperator* op, MultiOperand* out) {
+    if (op == nullptr) return fail("null operator");
+    *out = multi_operand_of(op);
+    if (!out->has_multi) {
+        fprintf(stderr, "[multi-rhs] operator '%s' has no multi-RHS path (stencil5-csr and cusparse-csr have one)\n",
+                op->name ? op->name : "?");
+        return false;
+    }
+    if (!out->ready) {
+        fprintf(stderr, "[multi-rhs] operator '%s' used before init\n", op->name);
+        return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+namespace spmv_amd {
+void release_cg_multi_workspace_locked() { g_multi.release(); }
+
+size_t cg_multi_workspace_bytes_locked() {
+    const MultiWorkspace& w = g_multi;
+    if (w.X == nullptr) return 0;
+    return (4 * (size_t)w.n * w.k + (size_t)w.k * w.partial_cap + (size_t)w.k * slices_for(w.partial_cap) + (size_t)w.k * w.hist_cap) *
+               sizeof(double) +
+           (size_t)w.k * sizeof(MultiColumn);
+}
+}  // namespace spmv_amd
+
+extern "C" int spmv_amd_spmm_device(const char* mode, int nrhs, const double* d_X, double* d_Y) {
+    if (mode == nullptr || !check_rhs(nrhs)) return 1;
+    if (d_X == nullptr || d_Y == nullptr) return fail("null block vector"), 1;
+    if ((((uintptr_t)d_X | (uintptr_t)d_Y) & 7) != 0) return fail("block vectors must be 8-byte aligned"), 1;
+    SpmvOperator* op = get_operator(mode);
+    if (op == nullptr) {
+        fprintf(stderr, "[multi-rhs] unknown operator '%s'\n", mode);
+        return 1;
+    }
+    MultiOperand o;
+    if (!usable_operator(op, &o)) return 1;
+    launch_spmm(o.plan, nrhs, d_X, d_Y, nullptr, kStream);
+    HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" const char* spmv_amd_spmm_variant(const char* mode) {
+    SpmvOperator* op = get_operator(mode);
+    if (op == nullptr) return "unknown-operator";
+    const MultiOperand o = multi_operand_of(op);
+    if (!o.has_multi) return "none";
+    return o.ready ? o.plan.name : "uninitialised";
+}
+
+namespace {
+int move_block(int nrhs, size_t n, const double* src, double* dst, bool to_device) {
+    if (!check_rhs(nrhs)) return 1;
+    if (src == nullptr || dst == nullptr) return fail("null block vector"), 1;
+    if (n == 0) return 0;
+    double* staging = device_try_alloc<double>(n * nrhs);
+    if (staging == nullptr) return fail("no device memory for the staging copy"), 1;
+    if (to_device) {
+        upload(staging, src, n * nrhs);
+        launch_interleave(nrhs, n, staging, dst, kStream);
+    } else {
+        HIP_CHECK(hipStreamSynchronize(kStream));
+        launch_deinterleave(nrhs, n, src, staging, kStream);
+        HIP_CHECK(hipStreamSynchronize(kStream));
+        download(dst, staging, n * nrhs);
+    }
+    HIP_CHECK(hipStreamSynchronize(kStream));
+    device_release(staging);
+    return 0;
+}
+}  // namespace
+
+extern "C" int spmv_amd_block_to_device(int nrhs, size_t n, const double* host_columns, double* d_X) {
+    return move_block(nrhs, n, host_columns, d_X, true);
+}
+
+extern "C" int spmv_amd_block_to_host(int nrhs, size_t n, const double* d_X, double* host_columns) {
+    return move_block(nrhs, n, d_X, host_columns, false);
+}
+
+extern "C" int spmv_amd_cg_solve_device_multi(SpmvOperator* op, MatrixData* mat, int nrhs, const double* B, double* X,
+                                              const CGConfig* config, CGStats* stats) {
+    // argument checks: all before the first HIP call
+    if (!check_rhs(nrhs)) return 1;
+    if (mat == nullptr || B == nullptr || X == nullptr || config == nullptr || stats == nullptr)
+        return fail("null argument"), 1;
+    MultiOperand o;
+    if (!usable_operator(op, &o)) return 1;
+    if (o.plan.rows != o.plan.cols || mat->rows != o.plan.rows) {
+        fprintf(stderr, "[CG-MULTI] the operator holds a %d x %d matrix, mat->rows = %d: a square system of that size is required\n",
+                o.plan.rows, o.plan.cols, mat->rows);
+        return 1;
+    }
+    if (config->max_iters < 0) return fail("max_iters < 0"), 1;
+    const int n = mat->rows, k = nrhs;
+    const CGConfig cfg = *config;
+
+    CgWorkspaceScope scope;
+    int device = 0;
+    HIP_CHECK(hipGetDevice(&device));
+    const long long vec_count = ((long long)n + kBlock - 1) / kBlock;
+    const long long spmm_count = o.plan.blocks;
+    const long long partial_cap = vec_count > spmm_count ? vec_count : spmm_count;
+    if (!ensure_workspace(n, k, device, partial_cap, cfg.max_iters + 1)) return 1;
+    MultiWorkspace& w = g_multi;
+
+    // B and x0 arrive as k columns one after the other: through AP (free until the first SpMM) into interleaved R and X
+    upload(w.AP, B, (size_t)n * k);
+    launch_interleave(k, (size_t)n, w.AP, w.R, kStream);
+    HIP_CHECK(hipStreamSynchronize(kStream));
+    upload(w.AP, X, (size_t)n * k);
+    launch_interleave(k, (size_t)n, w.AP, w.X, kStream);
+    HIP_CHECK(hipStreamSynchronize(kStream));
+
+    std::vector<MultiColumn> h_cols((size_t)k);
+    const bool detail = cfg.enable_detailed_timers != 0;
+    EventTimer total, part;
+    double t_spmv = 0.0, t_blas = 0.0, t_red = 0.0;
+    auto stage = [&](double* acc, auto&& launch) {
+        if (detail) part.begin(kStream);
+        launch();
+        if (detail) {
+            part.end(kStream);
+            *acc += part.elapsed_ms();
+        }
+    };
+    auto reduce = [&](long long count, int which) {
+        const int sc = slices_for(count);
+        hipLaunchKernelGGL(multi_reduce_slices_kernel, dim3((unsigned)sc, (unsigned)k), dim3(kBlock), 0, kStream, w.partials, count, sc,
+                           w.slices);
+        hipLaunchKernelGGL(multi_reduce_step_kernel, dim3((unsigned)k), dim3(kBlock), 0, kStream, w.slices, sc, which, cfg.tolerance, w.cols,
+                           w.hist, w.hist_cap);
+    };
+    auto read_columns = [&] { download(h_cols.data(), w.cols, (size_t)k); };
+
+    total.begin(kStream);
+    stage(&t_spmv, [&] { launch_spmm(o.plan, k, w.X, w.AP, nullptr, kStream); });
+    stage(&t_blas, [&] { launch_vector_step(k, 0, n, w.cols, w.X, w.R, w.P, w.AP, w.partials, vec_count); });
+    stage(&t_red, [&] { reduce(vec_count, 0); });
+    read_columns();
+    if (cfg.verbose >= 1)
+        for (int j = 0; j < k; ++j) printf("[CG-MULTI %d] Initial residual: %e\n", j, h_cols[j].b_norm);
+    for (int it = 0; it < cfg.max_iters; ++it) {
+        bool any = false;
+        for (int j = 0; j < k; ++j) any = any || !h_cols[j].done;
+        if (!any) break;
+        stage(&t_spmv, [&] { launch_spmm(o.plan, k, w.P, w.AP, w.partials, kStream); });
+        stage(&t_red, [&] { reduce(spmm_count, 1); });
+        stage(&t_blas, [&] { launch_vector_step(k, 1, n, w.cols, w.X, w.R, w.P, w.AP, w.partials, vec_count); });
+        stage(&t_red, [&] { reduce(vec_count, 2); });
+        stage(&t_blas, [&] { launch_vector_step(k, 2, n, w.cols, w.X, w.R, w.P, w.AP, w.partials, vec_count); });
+        read_columns();  // synchronises: the stopping test of every column
+        if (cfg.verbose >= 2)
+            for (int j = 0; j < k; ++j)
+                if (h_cols[j].active)
+                    printf("[CG-MULTI %d] Iter %3d: residual = %e (rel = %e)\n", j, h_cols[j].iterations, h_cols[j].residual,
+                           h_cols[j].residual / h_cols[j].b_norm);
+    }
+    total.end(kStream);
+    const double total_ms = total.elapsed_ms();
+    HIP_CHECK(hipGetLastError());
+
+    // the solution back as k columns one after the other (outside the timed region, as the upload)
+    launch_deinterleave(k, (size_t)n, w.X, w.AP, kStream);
+    HIP_CHECK(hipStreamSynchronize(kStream));
+    download(X, w.AP, (size_t)n * k);
+    // each column's recorded history only (the buffer may be longer: it keeps the largest max_iters seen)
+    g_multi_history.assign((size_t)k, std::vector<double>());
+    for (int j = 0; j < k; ++j) {
+        const MultiColumn& c = h_cols[j];
+        const int count = c.iterations + 1 < w.hist_cap ? c.iterations + 1 : w.hist_cap;
+        g_multi_history[j].resize((size_t)count);
+        download(g_multi_history[j].data(), w.hist + (size_t)j * w.hist_cap, (size_t)count);
+        CGStats& st = stats[j];
+        st.iterations = c.iterations;
+        // not converged: ||r0|| unless verbose >= 2 copied the last residual back (cg_solve_device, reference :535, :601-619)
+        st.residual_norm = c.done ? c.residual : (cfg.verbose >= 2 && c.iterations > 0 ? c.residual : c.b_norm);
+        st.converged = (c.b_norm > 0.0 && st.residual_norm / c.b_norm < cfg.tolerance) ? 1 : 0;
+        st.time_total_ms = total_ms;
+        st.time_spmv_ms = t_spmv;
+        st.time_blas1_ms = t_blas;
+        st.time_reductions_ms = t_red;
+        column_checksums(X + (size_t)j * n, n, &st.solution_sum, &st.solution_norm);
+        if (cfg.verbose >= 1) {
+            printf("[CG-MULTI %d] Converged: %s\n", j, st.converged ? "YES" : "NO");
+            printf("[CG-MULTI %d] Iterations: %d\n", j, st.iterations);
+            printf("[CG-MULTI %d] Final residual: %e\n", j, st.residual_norm);
+        }
+    }
+    if (cfg.verbose >= 1) {
+        printf("[CG-MULTI] %d systems, time breakdown (whole batch):\n", k);
+        printf("     Total:      %.3f ms\n", total_ms);
+        printf("     SpMV:       %.3f ms\n", t_spmv);
+        printf("     BLAS1:      %.3f ms\n", t_blas);
+        printf("     Reductions: %.3f ms\n", t_red);
+    }
+    return 0;
+}
+
+extern "C" size_t spmv_amd_cg_multi_workspace_bytes(void) {
+    CgWorkspaceScope scope;
+    return cg_multi_workspace_bytes_locked();
+}
+
+extern "C" int spmv_amd_cg_last_history_multi(int rhs, double* out, int cap) {
+    if (rhs < 0 || rhs >= (int)g_multi_history.size()) return -1;
+    const std::vector<double>& h = g_multi_history[(size_t)rhs];
+    const int count = (int)h.size();
+    for (int i = 0; i < count && i < cap && out != nullptr; ++i) out[i] = h[i];
+    return count;
+}

@@ -74,6 +74,7 @@
 
 #include "comm.hpp"
 #include "device_runtime.hpp"
+#include "multi_rhs.hpp"
 #include "stencil_geometry.hpp"
 #include "trace_ranges.hpp"
 #include "watchdog.hpp"
@@ -1661,6 +1662,7 @@ std::mutex g_workspace_lock;
 std::atomic<std::thread::id> g_workspace_owner{std::thread::id()};  // read without the lock by release_cg_workspace() on any thread
 bool g_release_pending = false;  // only ever touched by the owner thread (which holds the lock)
 void release_cg_workspace_locked() {
+    spmv_amd::release_cg_multi_workspace_locked();  // the batched solver's (cg_multi.hip) lives and goes with this one
     if (g_workspace == nullptr) return;
     spmv_amd_cg_slab_destroy(g_workspace);
     g_workspace = nullptr;
@@ -1676,6 +1678,20 @@ void release_cg_workspace() {
     }
     std::lock_guard<std::mutex> guard(g_workspace_lock);
     release_cg_workspace_locked();
+}
+
+// The batched solve (cg_multi.hip) under the same lock and the same owner rule as cg_solve_on_operator below.
+CgWorkspaceScope::CgWorkspaceScope() {
+    g_workspace_lock.lock();
+    g_release_pending = false;
+    g_workspace_owner.store(std::this_thread::get_id(), std::memory_order_release);
+}
+
+CgWorkspaceScope::~CgWorkspaceScope() {
+    g_workspace_owner.store(std::thread::id(), std::memory_order_release);
+    if (g_release_pending) release_cg_workspace_locked();
+    g_release_pending = false;
+    g_workspace_lock.unlock();
 }
 
 // The loop of spmv_amd_cg_slab_solve driven through the caller's operator: the same fused kernels, direction ring,

@@ -1,0 +1,78 @@
+// multi_rhs.hpp -- one matrix, up to 8 right-hand sides: SpMM launchers (spmm_kernels.hip) and the batched CG kernels
+// (cg_multi.hip). Every launcher enqueues on the given stream and returns; none synchronises.
+//
+// Block vectors are row-interleaved: element (row, column j) of a block of k columns lives at X[row * k + j]. One lane reads a
+// row's k values as one run of 8k bytes (16-byte loads where k is even and the pointer allows), and the solver streams 4-5
+// arrays in lock step instead of 4-5 k separate vectors (lock-step streams in different 32 GiB classes cost
+// 6.5 %).
+//
+// Column independence: column j of every kernel here is computed by exactly the instructions that compute column 0 of a
+// k = 1 launch -- per-column accumulators, explicit fma(), -ffp-contract=off -- and every dot product of column j is formed
+// over the same row blocks in the same order whatever k is and whatever slot j the column sits in. A column's results
+// therefore depend on that column's data only (tests/test_multi_rhs_gpu.py checks this bit for bit).
+#pragma once
+
+#include "kernels.hpp"
+#include "spmv_amd.h"
+
+namespace spmv_amd {
+
+constexpr int kMaxRhs = 8;
+
+// Which kernel family one multi-RHS product of an operator takes. The stencil kinds follow the operator's single-vector
+// variant (Stencil5Plan::variant), so a forced variant is honoured here too.
+enum class SpmmKind { StencilLds, StencilDirect, StencilGeneric, StencilCsrLoop, Csr };
+
+struct SpmmPlan {
+    SlabCsr m;                 // the operator's whole matrix (single GPU: row_offset 0, no halos)
+    SpmmKind kind = SpmmKind::Csr;
+    int rows = 0, cols = 0;
+    int col_blocks = 0;        // StencilLds / StencilDirect: 256-column blocks per grid row
+    int xcd_run = 1;           // StencilLds: consecutive blocks one XCD takes of every run of 8 * xcd_run
+    long long blocks = 0;      // workgroups of one launch = dot-partial slots per column
+    const char* name = "";     // "spmm/stencil5-row-lds", ...
+};
+SpmmPlan plan_spmm(const SlabCsr& m, Stencil5Variant stencil_variant, bool csr_operator, int rows, int cols);
+
+// Y = A X for k = 1..8 interleaved columns. d_partials (may be null; square matrices): partials[j * plan.blocks + block] =
+// sum over the block's rows of X[row][j] * (A X)[row][j]. X and Y must be 8-byte aligned; 16-byte aligned X and Y with an
+// even k take 16-byte loads / stores.
+void launch_spmm(const SpmmPlan& plan, int k, const double* X, double* Y, double* d_partials, hipStream_t stream);
+
+// (k, n) column blocks <-> interleaved: dst[row * k + j] = src[j * n + row] and back.
+void launch_interleave(int k, size_t n, const double* src_columns, double* dst_interleaved, hipStream_t stream);
+void launch_deinterleave(int k, size_t n, const double* src_interleaved, double* dst_columns, hipStream_t stream);
+
+// The multi-RHS path of one of this library's operators (operators.hip). Host-side state only: no HIP call, so the argument
+// checks of the entry points built on it hold on a machine without a GPU.
+struct MultiOperand {
+    bool has_multi = false;  // "stencil5-csr" (and its alias "stencil5-halo-mgpu") and "cusparse-csr"; not the ELLPACK ones
+    bool ready = false;      // initialised
+    SpmmPlan plan;
+};
+MultiOperand multi_operand_of(const SpmvOperator* op);
+
+// Holds the lock of the CG workspaces (cg_slab.hip) for its lifetime and marks this thread as the one inside a solve: the
+// batched solve obeys the same lock and the same "release asked from inside the solve" rule as cg_solve_device.
+class CgWorkspaceScope {
+public:
+    CgWorkspaceScope();
+    ~CgWorkspaceScope();
+    CgWorkspaceScope(const CgWorkspaceScope&) = delete;
+    CgWorkspaceScope& operator=(const CgWorkspaceScope&) = delete;
+};
+// Frees the batched solver's workspace (cg_multi.hip); the caller holds the workspace lock.
+void release_cg_multi_workspace_locked();
+// Device bytes the batched solver's workspace holds now (0: none); the caller holds the workspace lock.
+size_t cg_multi_workspace_bytes_locked();
+
+// Per-column state of a batched CG solve (device memory, one entry per column).
+struct MultiColumn {
+    double rr_old, pAp, alpha, beta, b_norm, residual;
+    int active;      // the column takes part in the current iteration (set by the pAp step: !done)
+    int done;        // converged: the column is frozen from the next iteration on
+    int iterations;  // iterations this column took part in
+    int pad;
+};
+
+}  // namespace spmv_amd

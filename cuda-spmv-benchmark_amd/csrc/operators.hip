@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "device_runtime.hpp"
+#include "multi_rhs.hpp"
 #include "stencil_geometry.hpp"
 
 using namespace spmv_amd;
@@ -472,6 +473,22 @@ FusedSpmv fused_spmv_of(const SpmvOperator* op) {
         f.launch = ell_fused_launch<&g_ell_stencil>;
     }
     return f;
+}
+
+// The multi-RHS path (multi_rhs.hpp, spmm_kernels.hip): the stencil operator's SpMM follows its single-vector variant; the CSR
+// operator's is the sequential thread-per-row kernel whatever its single-vector variant. The ELLPACK operators have none.
+MultiOperand multi_operand_of(const SpmvOperator* op) {
+    MultiOperand o;
+    if (op == &SPMV_STENCIL5_CSR || op == &SPMV_STENCIL_HALO_MGPU) {
+        o.has_multi = true;
+        o.ready = g_stencil.ready;
+        if (o.ready) o.plan = plan_spmm(g_stencil.A.view, g_stencil.plan.variant, false, g_stencil.rows, g_stencil.cols);
+    } else if (op == &SPMV_CSR) {
+        o.has_multi = true;
+        o.ready = g_csr.ready;
+        if (o.ready) o.plan = plan_spmm(g_csr.A.view, Stencil5Variant::Auto, true, g_csr.rows, g_csr.cols);
+    }
+    return o;
 }
 }  // namespace spmv_amd
 

@@ -242,8 +242,45 @@ int spmv_amd_cg_fused_step(int which, size_t n, const double* scalars, const dou
 int spmv_amd_cg_last_history(double* out, int cap);
 /* cg_solve_device keeps its five vectors and direction ring between calls (the harness solves one system 13 times,
  * reference src/main/cg_solver.cu:154-178). They are released by the free() of any of this library's operators, or here --
- * the call for a caller that drives its own SpmvOperator table through cg_solve_device. Safe to call at any time. */
+ * the call for a caller that drives its own SpmvOperator table through cg_solve_device. Safe to call at any time.
+ * The batched solver's workspace (spmv_amd_cg_solve_device_multi) is released together with this one. */
 void spmv_amd_cg_release_workspace(void);
+
+/* ---- several right-hand sides per matrix pass (csrc/spmm_kernels.hip, csrc/cg_multi.hip) ----
+ * Block vectors on the device are ROW-INTERLEAVED: element (row, column j) of a block of nrhs columns is X[row * nrhs + j]
+ * (one lane reads a row's nrhs values as one run; the solver streams 4-5 arrays instead of 4-5 nrhs). On the host they are
+ * nrhs vectors one after the other (numpy (nrhs, n) in C order); the two helpers below convert. nrhs is 1 to 8.
+ * "stencil5-csr" and "cusparse-csr" have the multi-RHS path ("ellpack" / "stencil5-ellpack" and caller-supplied operator
+ * tables do not). Column j of every result is computed by exactly the arithmetic of the single-vector path on column j
+ * (spmv_kernels.hip:1-10): it depends on column j's data only, not on nrhs nor on the other columns.
+ * Every entry point checks its arguments (nrhs outside 1..8, null pointers, an operator without the path or not initialised)
+ * before any HIP call and returns non-zero with a message on stderr. */
+
+/* Y = A X on an initialised operator, X of `cols` rows, Y of `rows` rows (device pointers, 8-byte aligned; 16-byte aligned
+ * with an even nrhs take 16-byte loads). Default stream, no synchronisation. The coefficients are read once for all columns;
+ * the kernel follows the operator's single-vector variant (spmv_amd_operator_select_variant). */
+int spmv_amd_spmm_device(const char* mode, int nrhs, const double* d_X, double* d_Y);
+/* Which SpMM kernel the operator's multi-RHS path takes (a static string): "spmm/stencil5-row-lds", "spmm/stencil5-row-direct",
+ * "spmm/stencil5-row-generic", "spmm/stencil5-row-generic(csr-loop)", "spmm/csr"; "none", "uninitialised", "unknown-operator". */
+const char* spmv_amd_spmm_variant(const char* mode);
+/* host (nrhs, n) columns <-> device interleaved block of n rows (synchronous; a temporary device copy of the block). */
+int spmv_amd_block_to_device(int nrhs, size_t n, const double* host_columns, double* d_X);
+int spmv_amd_block_to_host(int nrhs, size_t n, const double* d_X, double* host_columns);
+/* nrhs INDEPENDENT CG solves on one operator (not block CG): each column has its own alpha, beta, stopping test, history and
+ * iteration count, with cg_solve_device's stopping rule, statistics and verbose semantics; a converged column is frozen
+ * while the others go on. Only the SpMM is shared. B, X: host, nrhs vectors of length mat->rows one after the other; X in =
+ * x0, out = solution. stats: nrhs entries; time_total_ms is the wall time of the whole batch (the same in every column), the
+ * breakdown is filled with enable_detailed_timers only; the upload of B / x0 and the download of X are outside the timed
+ * region. The workspace (four block vectors) is sized against the device's free memory first: a batch that does not fit is
+ * refused with a message and a non-zero return. It is kept between calls and released with cg_solve_device's (an
+ * operator's free(), spmv_amd_cg_release_workspace()). */
+int spmv_amd_cg_solve_device_multi(SpmvOperator* op, MatrixData* mat, int nrhs, const double* B, double* X,
+                                   const CGConfig* config, CGStats* stats);
+/* Residual history of column `rhs` of the last batched solve, like spmv_amd_cg_last_history; -1 if there is no such column. */
+int spmv_amd_cg_last_history_multi(int rhs, double* out, int cap);
+/* Device bytes the batched solver's workspace holds now: 0 once it is released (operator free(),
+ * spmv_amd_cg_release_workspace()) or before the first batched solve. No HIP call. */
+size_t spmv_amd_cg_multi_workspace_bytes(void);
 
 /* ---- multi-GPU communicator ---- */
 typedef struct SpmvAmdComm SpmvAmdComm;
