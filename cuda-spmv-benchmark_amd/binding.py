@@ -98,7 +98,7 @@ DECLARED_SYMBOLS = [
     "spmv_amd_comm_mailbox_disable", "spmv_amd_comm_mailbox_ready",
     "spmv_amd_cg_slab_create", "spmv_amd_cg_slab_create_stencil5", "spmv_amd_cg_slab_set_vectors", "spmv_amd_cg_slab_solve",
     "spmv_amd_cg_slab_gather", "spmv_amd_cg_slab_loop_shape", "spmv_amd_cg_slab_history", "spmv_amd_cg_slab_spmv", "spmv_amd_cg_slab_info",
-    "spmv_amd_cg_slab_time_spmv", "spmv_amd_cg_slab_set_timeline", "spmv_amd_operator_placement", "spmv_amd_cg_slab_placement", "spmv_amd_cg_slab_tile_runs", "spmv_amd_cg_slab_setup_ms", "spmv_amd_cg_slab_spmv_launch_ms",  "spmv_amd_cg_release_workspace", "spmv_amd_cg_slab_timeline_names", "spmv_amd_cg_slab_timeline", "spmv_amd_cg_slab_variant", "spmv_amd_cg_slab_destroy", "spmv_amd_version", "spmv_amd_write_stencil5_values",
+    "spmv_amd_cg_slab_time_spmv", "spmv_amd_cg_slab_set_timeline", "spmv_amd_operator_placement", "spmv_amd_cg_slab_placement", "spmv_amd_cg_slab_tile_runs", "spmv_amd_cg_slab_setup_ms", "spmv_amd_cg_slab_coefficient_form","spmv_amd_cg_slab_spmv_launch_ms",  "spmv_amd_cg_release_workspace", "spmv_amd_cg_slab_timeline_names", "spmv_amd_cg_slab_timeline", "spmv_amd_cg_slab_variant", "spmv_amd_cg_slab_destroy", "spmv_amd_version", "spmv_amd_write_stencil5_values",
     "spmv_amd_blas1_axpy", "spmv_amd_blas1_axpby", "spmv_amd_blas1_axpy_dev", "spmv_amd_blas1_update_p_dev", "spmv_amd_blas1_dot",
     "spmv_amd_cg_fused_step",
     "spmv_amd_spmm_device", "spmv_amd_spmm_variant", "spmv_amd_block_to_device", "spmv_amd_block_to_host",
@@ -214,6 +214,8 @@ def lib():
     L.spmv_amd_cg_slab_timeline.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.spmv_amd_cg_slab_variant.restype = C.c_char_p
     L.spmv_amd_cg_slab_variant.argtypes = [C.c_void_p]
+    L.spmv_amd_cg_slab_coefficient_form.argtypes = [C.c_void_p]
+    L.spmv_amd_cg_slab_coefficient_form.restype = C.c_int
     L.spmv_amd_cg_slab_loop_shape.restype = C.c_char_p
     L.spmv_amd_cg_slab_loop_shape.argtypes = [C.c_void_p]
     L.load_matrix_market.argtypes = [C.c_char_p, C.POINTER(MatrixData)]
@@ -722,6 +724,10 @@ class CgSlab:
 
     def variant(self):
         return lib().spmv_amd_cg_slab_variant(self.h).decode()
+
+    def coefficient_form(self):
+        """0: the SpMV streams the CSR values; 1: the symmetric [C, E] + S planes (include/spmv_amd/api.h)."""
+        return int(lib().spmv_amd_cg_slab_coefficient_form(self.h))
 
     def loop_shape(self):
         """"single rank" | "pipeline ..." | "plain: <who decided>" (include/spmv_amd/api.h)."""

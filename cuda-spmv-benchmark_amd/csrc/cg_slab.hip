@@ -114,6 +114,15 @@ struct SpmvAmdCgSlab {
     // neighbours inside one allocation share a region except where it crosses a boundary. The SpMV's coefficient stream does
     // not take part (40 B/row against 8 B/row: not in lock step; r04_arena_spmv_mix.txt), so the CSR arrays stay where they are.
     double* vec_arena = nullptr;
+    // Symmetric coefficient form (kernels.hpp, SymPlanes): a slab that owns its matrix, runs row-lds launches only and whose W / N
+    // entries are bit for bit the E entry of row i-1 / the S entry of row i-n keeps [C, E] and S planes (S with one grid row of
+    // halo) in ONE allocation next to its CSR, and its row-lds launches stream those: 24 B/row of coefficients instead of 40.
+    // The CSR stays for the grid's first and last grid row and as the form of every other slab.
+    double* planes_alloc = nullptr;
+    size_t planes_doubles = 0, planes_s_offset = 0;  // the allocation's length; where the S plane's local part starts
+    SymPlanes planes;
+    bool planes_on = false;
+    const SymPlanes* sym() const { return planes_on ? &planes : nullptr; }
     // place_coefficients: {0, candidates timed, SpMV ms before, SpMV ms kept}
     std::vector<double> placement;
     std::vector<double> tile_runs;  // tune_tile_runs: {rule, kept, SpMV ms with the rule, ms kept}; empty = did not run
@@ -271,6 +280,41 @@ void adopt_operator(SpmvAmdCgSlab* s, SpmvOperator* op) {
 void place_coefficients(SpmvAmdCgSlab* s);  // below
 void tune_tile_runs(SpmvAmdCgSlab* s);
 
+SymPlanes plane_view(const SpmvAmdCgSlab* s, const double* base) { return SymPlanes{base, base + s->planes_s_offset}; }
+
+// A slab whose launches can all be row-lds launches (whole grid rows of a grid that takes row-lds) and that owns its matrix:
+// worth reserving the symmetric planes for before the direction ring takes what is free. Whether it keeps them is decided once
+// the structure is verified and the plans are made (settle_planes).
+bool may_take_planes(const SpmvAmdCgSlab* s) {
+    const int n = s->grid;
+    return s->op == nullptr && n >= 2 && n >= s->shape.knobs.rowlds_min_grid && s->n_local > 0 && s->n_local % n == 0 &&
+           s->row_offset % n == 0;
+}
+
+// Fills the reserved planes from the verified CSR and checks them bit for bit (launch_verify_sym_planes); any mismatch, an
+// unverified structure or a launch that is not row-lds frees them again: the slab keeps the CSR form.
+void settle_planes(SpmvAmdCgSlab* s) {
+    if (s->planes_alloc == nullptr) return;
+    bool keep = s->A.view.verified_stencil && s->fuse_init_residual;  // every launch of the slab is a row-lds launch
+    if (keep) {
+        launch_fill_sym_planes(s->A.view, s->planes_alloc, s->planes_alloc + s->planes_s_offset, s->compute);
+        s->planes = plane_view(s, s->planes_alloc);
+        int* d_flag = device_alloc<int>(1);
+        HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(int), s->compute));
+        launch_verify_sym_planes(s->A.view, s->planes, d_flag, s->compute);
+        int h_flag = 1;
+        HIP_CHECK(hipMemcpyAsync(&h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, s->compute));
+        HIP_CHECK(hipStreamSynchronize(s->compute));
+        device_release(d_flag);
+        keep = h_flag == 0;
+    }
+    if (!keep) {
+        device_release(s->planes_alloc);
+        s->planes = SymPlanes{};
+    }
+    s->planes_on = keep;
+}
+
 // Set-up phase clock: wall time since `from`, after everything enqueued so far has finished.
 double setup_phase_ms(std::chrono::steady_clock::time_point& from) {
     HIP_CHECK(hipDeviceSynchronize());
@@ -310,6 +354,7 @@ void make_common(SpmvAmdCgSlab* s) {
     }
     HIP_CHECK(hipEventCreateWithFlags(&s->ev_p_ready, hipEventDisableTiming));
     HIP_CHECK(hipEventCreateWithFlags(&s->ev_halo_done, hipEventDisableTiming));
+    s->shape = current_launch_shape();
     // The local part of every halo-carrying buffer starts on a 4 KiB boundary whatever the halo length, like the
     // plain allocations of r, Ap, x. Measured with the rank as its own neighbour: a halo of 14 142 doubles put
     // every access of the direction buffers across two 128-byte lines (direction update 0.88 ms against 0.71 ms
@@ -346,6 +391,22 @@ void make_common(SpmvAmdCgSlab* s) {
         // say -- so its ring is held to a quarter of what is free now: 16 slots of 3.2 GB at 4e8 rows on an otherwise idle
         // MI355X, fewer on a fuller device, the in-place form when even four do not fit.
         const size_t fixed = 3 * per_slot;  // r, Ap, the first direction buffer
+        if (may_take_planes(s)) {
+            // the symmetric planes before the ring (24 B per row + one grid row: 9.6 GB at 4e8 rows), where a ring of 4 still fits
+            // beside them; [C, E] first, the S plane's local part on a 4 KiB boundary behind its halo row. Optional: a device that
+            // cannot provide them leaves the slab in the CSR form.
+            const size_t ce = (2 * nl + kLeadUnit - 1) / kLeadUnit * kLeadUnit;
+            const size_t halo_lead = ((size_t)s->grid + kLeadUnit - 1) / kLeadUnit * kLeadUnit;
+            const size_t bytes = (ce + halo_lead + nl) * sizeof(double);
+            if (free_b > bytes + keep_free + fixed + 3 * per_slot) {
+                s->planes_alloc = device_try_alloc<double>(ce + halo_lead + nl);
+                if (s->planes_alloc != nullptr) {
+                    s->planes_doubles = ce + halo_lead + nl;
+                    s->planes_s_offset = ce + halo_lead;
+                    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+                }
+            }
+        }
         const size_t budget = s->op != nullptr ? free_b / 4 : (free_b > keep_free + fixed ? free_b - keep_free - fixed : 0);
         while (want > 1 && (size_t)(want - 1) * per_slot > budget) --want;
         if (want < asked && want < 4) want = 1;  // a ring cut short by memory flushes too often to pay
@@ -366,7 +427,6 @@ void make_common(SpmvAmdCgSlab* s) {
         s->d_alpha_ring = device_alloc<double>(kMaxRingSlots);
         HIP_CHECK(hipMemset(s->d_alpha_ring, 0, kMaxRingSlots * sizeof(double)));
     }
-    s->shape = current_launch_shape();
     if (const char* v = getenv("SPMV_AMD_NO_OVERLAP")) s->no_overlap = v[0] == '1';
 #ifdef SPMV_AMD_LAB
     if (const char* v = getenv("SPMV_AMD_TEST_WEDGE_OVERLAPPED_EXCHANGE")) s->test_wedge_overlapped_exchange = atoi(v);
@@ -414,6 +474,7 @@ void make_common(SpmvAmdCgSlab* s) {
         const auto rowlds = [&](const Stencil5Plan& p) { return p.last_row <= p.first_row || p.variant == Stencil5Variant::RowLds; };
         s->fuse_init_residual = s->plan_whole.variant == Stencil5Variant::RowLds && rowlds(s->plan_interior) && rowlds(s->plan_head) && rowlds(s->plan_tail);
     }
+    settle_planes(s);
     s->setup_ms[2] = setup_phase_ms(phase);
     if (s->setup_trials) place_coefficients(s);
     s->setup_ms[3] = setup_phase_ms(phase);
@@ -440,22 +501,29 @@ void place_coefficients(SpmvAmdCgSlab* s) {
     const size_t nl = (size_t)s->n_local;
     if (s->op != nullptr || !wants_coefficient_placement(nl) || s->ring.size() < 4 || s->A.values == nullptr) return;
     hipStream_t q = s->compute;
-    const size_t count = (size_t)s->A.view.nnz_local;
+    // the coefficient stream the loop reads: the symmetric planes where the slab keeps them, else the CSR values
+    const bool planes = s->planes_on;
+    const size_t count = planes ? s->planes_doubles : (size_t)s->A.view.nnz_local;
     const double* early = s->ring[1];
     const double* late = s->ring[s->ring.size() - 3];
     launch_fill(s->ring[1], nl, 1.0, q);
     launch_fill(s->ring[s->ring.size() - 3], nl, 1.0, q);
     HIP_CHECK(hipMemsetAsync(&s->d_s->converged, 0, sizeof(int), q));
     EventTimer timer;
-    double* const original = s->A.values;
+    double* const original = planes ? s->planes_alloc : s->A.values;
+    const auto point_at = [&](double* values) {
+        if (planes) s->planes = plane_view(s, values);
+        else s->A.view.values = values;
+    };
     auto cost = [&](double* values) {
-        s->A.view.values = values;
+        point_at(values);
         double total = 0.0;
         for (const double* x : {early, late}) {
             float ms[3];
             for (int i = 0; i < 4; ++i) {
                 timer.begin(q);
-                (void)launch_stencil5_spmv(s->A.view, s->plan_whole, x, s->Ap, 1.0, s->fused_dot ? s->partials_spmv : nullptr, nullptr, false, q);
+                (void)launch_stencil5_spmv(s->A.view, s->plan_whole, x, s->Ap, 1.0, s->fused_dot ? s->partials_spmv : nullptr, nullptr, false, q,
+                                           nullptr, s->sym());
                 timer.end(q);
                 const float t = timer.elapsed_ms();
                 if (i > 0) ms[i - 1] = t;
@@ -463,7 +531,7 @@ void place_coefficients(SpmvAmdCgSlab* s) {
             std::sort(ms, ms + 3);
             total += ms[1];
         }
-        s->A.view.values = original;
+        point_at(original);
         return 0.5 * total;
     };
     int tried = 0;
@@ -476,14 +544,17 @@ void place_coefficients(SpmvAmdCgSlab* s) {
     }, &tried, nullptr, original, /*release_first=*/false);
     after = best == original ? before : cost(best);
     HIP_CHECK(hipStreamSynchronize(q));
+    const bool moved = best != original && after < 0.99 * before;
     if (best != original) {
-        if (after < 0.99 * before) s->A.replace_values(best);  // frees `original` when it is an allocation of its own
-        else device_release(best);
+        if (!moved) device_release(best);
+        else if (planes) device_release(s->planes_alloc), s->planes_alloc = best;
+        else s->A.replace_values(best);  // frees `original` when it is an allocation of its own
     }
     s->A.view.values = s->A.values;
+    if (planes) s->planes = plane_view(s, s->planes_alloc);
     for (double* a : s->ring_alloc) HIP_CHECK(hipMemsetAsync(a, 0, s->slot_doubles * sizeof(double), q));
     HIP_CHECK(hipStreamSynchronize(q));
-    s->placement = {0.0, (double)tried, before, s->A.values == original ? before : after};
+    s->placement = {0.0, (double)tried, before, moved ? after : before};
 }
 
 // Row-lds tiles per XCD and run, by measurement on the slab's own vectors (device_runtime.hpp, tune_rowlds_xcd_run): the four
@@ -496,7 +567,7 @@ void tune_tile_runs(SpmvAmdCgSlab* s) {
     launch_fill(x, nl, 1.0, q);
     HIP_CHECK(hipMemsetAsync(&s->d_s->converged, 0, sizeof(int), q));
     double rec[4] = {0, 0, 0, 0};
-    const int run = tune_rowlds_xcd_run(s->A.view, s->shape, x, s->Ap, s->fused_dot ? s->partials_spmv : nullptr, q, rec);
+    const int run = tune_rowlds_xcd_run(s->A.view, s->shape, x, s->Ap, s->fused_dot ? s->partials_spmv : nullptr, q, rec, s->sym());
     HIP_CHECK(hipMemsetAsync(s->ring_alloc[1], 0, s->slot_doubles * sizeof(double), q));
     HIP_CHECK(hipStreamSynchronize(q));
     if (run <= 0) return;
@@ -542,11 +613,11 @@ int slab_boundary_spmv(SpmvAmdCgSlab* s, const double* in, double* part, const i
     int used = 0;
     if (lo > 0 && hi < s->n_local && lo == A.grid_size && s->n_local - hi == A.grid_size) {
         // a rank with two neighbours: its first and last grid row in one launch
-        used += launch_stencil5_spmv_first_and_last_gridrow(A, s->plan_head, s->plan_tail, in, s->Ap, 1.0, at, skip, stream, init);
+        used += launch_stencil5_spmv_first_and_last_gridrow(A, s->plan_head, s->plan_tail, in, s->Ap, 1.0, at, skip, stream, init, s->sym());
     } else {
-        if (lo > 0) used += launch_stencil5_spmv(A, s->plan_head, in, s->Ap, 1.0, at, skip, false, stream, init);
+        if (lo > 0) used += launch_stencil5_spmv(A, s->plan_head, in, s->Ap, 1.0, at, skip, false, stream, init, s->sym());
         if (hi < s->n_local)
-            used += launch_stencil5_spmv(A, s->plan_tail, in, s->Ap, 1.0, at ? at + used : nullptr, skip, false, stream, init);
+            used += launch_stencil5_spmv(A, s->plan_tail, in, s->Ap, 1.0, at ? at + used : nullptr, skip, false, stream, init, s->sym());
     }
     return part ? used : 0;
 }
@@ -586,7 +657,7 @@ int slab_spmv(SpmvAmdCgSlab* s, bool with_dot, bool overlap, const int* skip,
     } else if (hi <= lo || (lo == 0 && hi == s->n_local) || (part == nullptr && !overlap)) {
         // one launch: a slab without halo rows, or of one or two grid rows, or a plain y = A x with the halos already in place
         if (overlap) HIP_CHECK(hipStreamWaitEvent(s->compute, s->ev_halo_done, 0));
-        used = launch_stencil5_spmv(A, s->plan_whole, in, s->Ap, 1.0, part, skip, s->shape.reverse, s->compute, init);
+        used = launch_stencil5_spmv(A, s->plan_whole, in, s->Ap, 1.0, part, skip, s->shape.reverse, s->compute, init, s->sym());
         if (s->tl_after_interior) HIP_CHECK(hipEventRecord(s->tl_after_interior, s->compute));
     } else {
         // rows whose north and south neighbours are local run under the halo exchange; the first / last grid
@@ -599,7 +670,7 @@ int slab_spmv(SpmvAmdCgSlab* s, bool with_dot, bool overlap, const int* skip,
         // it was started under, and the cross-stream wait leaves the path between the SpMV and its dot product -- measured
         // slower on every stand-in slab: +0.1-0.2 % at 20 000^2, +2.4 % on the P = 8 slab of 10 000^2,
         // profiles/r05_ab_halo_wait_first.txt.)
-        used = launch_stencil5_spmv(A, s->plan_interior, in, s->Ap, 1.0, part, skip, s->shape.reverse, s->compute, init);
+        used = launch_stencil5_spmv(A, s->plan_interior, in, s->Ap, 1.0, part, skip, s->shape.reverse, s->compute, init, s->sym());
         s->spmv_split_at = used;  // the boundary rows' partials follow: they enter the sum as extra values (reduce_device.hpp)
         if (s->tl_after_interior) HIP_CHECK(hipEventRecord(s->tl_after_interior, s->compute));
         // in-loop SpMV: the boundary rows ride in the launch that reduces the partials (one launch instead of three); the
@@ -617,7 +688,7 @@ int slab_spmv(SpmvAmdCgSlab* s, bool with_dot, bool overlap, const int* skip,
         }
         if (fused_tail && launch_stencil5_edges_and_reduce(A, s->plan_interior, lo > 0, hi < s->n_local, in, s->Ap, 1.0, part, &s->d_s->pAp, skip,
                                                            s->scratch(), s->spmv_progress, s->spmv_progress_value, s->reduce_mailbox, s->compute,
-                                                           arrival)) {
+                                                           arrival, s->sym())) {
             return used;
         }
         if (arrival.flag != nullptr) HIP_CHECK(hipStreamWaitEvent(s->compute, s->ev_halo_done, 0));  // the fused launch did not apply
@@ -1545,6 +1616,9 @@ extern "C" void spmv_amd_cg_slab_info(const SpmvAmdCgSlab* s, int* row_offset, i
 
 extern "C" const char* spmv_amd_cg_slab_variant(const SpmvAmdCgSlab* s) { return s->variant_name; }
 
+// The coefficients the slab's SpMV streams: 0 = the CSR values, 1 = the symmetric planes (kernels.hpp, SymPlanes).
+extern "C" int spmv_amd_cg_slab_coefficient_form(const SpmvAmdCgSlab* s) { return s->planes_on ? 1 : 0; }
+
 // What placement at creation did: {0, candidates timed, SpMV ms (mean of an early and a late direction buffer as x) where the
 // coefficients were, ms where they are now}. 0 values = it did not run.
 extern "C" int spmv_amd_cg_slab_placement(const SpmvAmdCgSlab* s, double* out, int cap) {
@@ -1588,6 +1662,7 @@ extern "C" int spmv_amd_cg_slab_set_option(SpmvAmdCgSlab* s, const char* name, l
     else if (strcmp(name, "no_overlap") == 0) s->no_overlap = value != 0 || s->comm->pipeline_verdict < 0;  // a refused pipeline stays refused
     else if (strcmp(name, "stop_at") == 0) s->stop_at = value > 0 ? (int)value : 0;
     else if (strcmp(name, "spmv_event_stride") == 0) s->spmv_event_stride = (int)value;
+    else if (strcmp(name, "csr_coefficients") == 0) s->planes_on = value == 0 && s->planes_alloc != nullptr;  // 1: the CSR form
     else return -1;
     return 0;
 }
@@ -1605,7 +1680,7 @@ extern "C" int spmv_amd_cg_slab_time_spmv(SpmvAmdCgSlab* s, int reps, float* ms_
     for (int i = 0; i < reps; ++i) {
         t.begin(s->compute);
         (void)launch_stencil5_spmv(s->A.view, s->plan_whole, s->p, s->Ap, 1.0, s->fused_dot ? s->partials_spmv : nullptr,
-                                   nullptr, false, s->compute);
+                                   nullptr, false, s->compute, nullptr, s->sym());
         t.end(s->compute);
         ms_each[i] = t.elapsed_ms();
     }
@@ -1623,6 +1698,8 @@ extern "C" void spmv_amd_cg_slab_destroy(SpmvAmdCgSlab* s) {
     device_release(s->b);
     s->x0 = nullptr;
     device_release(s->vec_arena);  // r, Ap and the direction buffers
+    device_release(s->planes_alloc);
+    s->planes_on = false;
     s->r = s->Ap = s->p_alloc = s->p = nullptr;
     s->ring_alloc.clear();
     s->ring.clear();

@@ -40,7 +40,7 @@ LaunchShape current_launch_shape() {
 }
 
 int tune_rowlds_xcd_run(const SlabCsr& m, const LaunchShape& shape, const double* x, double* y, double* d_partials, hipStream_t stream,
-                        double* record) {
+                        double* record, const SymPlanes* planes) {
     if (shape.knobs.rowlds_group > 0 || m.n_local < (16 << 20)) return 0;
     LaunchShape trial = shape;
     const Stencil5Plan base = plan_stencil5(m, 0, m.n_local, Stencil5Variant::Auto, trial);
@@ -60,7 +60,7 @@ int tune_rowlds_xcd_run(const SlabCsr& m, const LaunchShape& shape, const double
         float ms[3];
         for (int i = 0; i < 4; ++i) {
             timer.begin(stream);
-            (void)launch_stencil5_spmv(m, p, x, y, 1.0, d_partials, nullptr, false, stream);
+            (void)launch_stencil5_spmv(m, p, x, y, 1.0, d_partials, nullptr, false, stream, nullptr, planes);
             timer.end(stream);
             const float t = timer.elapsed_ms();
             if (i > 0) ms[i - 1] = t;

@@ -123,8 +123,9 @@ inline T* device_alloc_best_of(size_t count, size_t min_count, Cost&& cost_ms, i
 // apply (not a row-lds slab, fewer than 16 Mi rows, SPMV_AMD_ROWLDS_GROUP forces a value). Set-up work: the mapping of
 // workgroups to tiles is a performance choice only, results and partial slots do not depend on it.
 // record (optional, 4 doubles): {rule, kept, ms with the rule, ms kept}.
+// planes (may be null): the slab's symmetric coefficient form, timed as the loop will run it.
 int tune_rowlds_xcd_run(const SlabCsr& m, const LaunchShape& shape, const double* x, double* y, double* d_partials, hipStream_t stream,
-                        double* record = nullptr);
+                        double* record = nullptr, const SymPlanes* planes = nullptr);
 
 // Pair of events for on-stream timing of one region.
 struct EventTimer {

@@ -90,11 +90,27 @@ struct ResidualOut {
     double* r;
     double* p;
 };
+// The symmetric coefficient form of a solver slab (cg_slab.hip): a 5-point stencil whose W and N entries equal, bit for bit, the
+// E entry of row i-1 and the S entry of row i-n needs only C, E and S per row. ce = [C, E] of local row lr at ce[2 lr], ce[2 lr + 1]
+// (E = 0 in column n-1); s = S of local row lr at s[lr] (0 in the grid's last row), with ONE grid row of halo in front of it:
+// s[lr - n], lr < n, is the slab's own N entry of local row lr (0 in the grid's first row). The row-lds kernel then streams 24 B
+// of coefficients per row instead of 40, with the same fma chains. Row-lds launches only; a null view = the CSR form.
+struct SymPlanes {
+    const double* ce = nullptr;  // 16-byte aligned
+    const double* s = nullptr;
+};
+// Fills the planes from a slab that passed verify_stencil (s: the local part, halo in front).
+void launch_fill_sym_planes(const SlabCsr& m, double* ce, double* s, hipStream_t stream);
+// Sets *d_mismatch (int, zeroed by the caller) if any value the row-lds kernel would take from the planes in grid rows 1 .. n-2
+// (W = E[i-1], N = S[i-n] or the halo row, C, E, S) differs in its 64-bit pattern from the CSR entry it stands for.
+void launch_verify_sym_planes(const SlabCsr& m, const SymPlanes& planes, int* d_mismatch, hipStream_t stream);
+
 // Launch by plan. reverse: walk the tiles from the last to the first (row-lds only; same results).
 // init (may be null): see ResidualOut; y is then not written and may be null.
+// planes (may be null; row-lds plans only): the symmetric coefficient form.
 int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& plan, const double* x, double* y, double alpha,
                          double* d_dot_partials, const int* d_skip_flag, bool reverse, hipStream_t stream,
-                         const ResidualOut* init = nullptr);
+                         const ResidualOut* init = nullptr, const SymPlanes* planes = nullptr);
 // first_row/last_row restrict the launch to local rows [first_row, last_row); used to split
 // interior rows from halo-dependent rows. Returns the number of dot partials written (0 when
 // d_dot_partials is null).
@@ -108,7 +124,7 @@ int launch_stencil5_spmv(const SlabCsr& m, const double* x, double* y, double al
 // `head` / `tail` = the plans of the slab's first / last grid row.
 int launch_stencil5_spmv_first_and_last_gridrow(const SlabCsr& m, const Stencil5Plan& head, const Stencil5Plan& tail, const double* x,
                                                 double* y, double alpha, double* d_dot_partials, const int* d_skip_flag,
-                                                hipStream_t stream, const ResidualOut* init = nullptr);
+                                                hipStream_t stream, const ResidualOut* init = nullptr, const SymPlanes* planes = nullptr);
 
 // ---- CSR SpMV ----
 enum class CsrVariant { Auto, Stream, Adaptive, RowScalar, Wavefront };
@@ -207,7 +223,7 @@ void launch_halo_arrived(unsigned* d_flag, unsigned sequence, hipStream_t stream
 bool launch_stencil5_edges_and_reduce(const SlabCsr& m, const Stencil5Plan& interior, bool first_gridrow, bool last_gridrow, const double* x,
                                       double* y, double alpha, const double* d_interior_partials, double* d_out, const int* d_skip_flag,
                                       const ReduceScratch& scratch, int* host_progress, int progress_value, const PeerMailbox* mailbox,
-                                      hipStream_t stream, const HaloArrival& halo = HaloArrival{});
+                                      hipStream_t stream, const HaloArrival& halo = HaloArrival{}, const SymPlanes* planes = nullptr);
 
 // ---- fused CG steps of the slab solver (all skip their work when s->converged) ----
 // r = b - Ap ; p = r ; partials of r.r

@@ -12,7 +12,8 @@
 // Memory contract: STENCIL5 is HBM-bound at 56 B per interior row (40 B values, 8 B x, 8 B y). Three kernels implement it:
 //   row-lds     (grids of >= 512 columns, slabs made of whole grid rows: the benchmark's path) streams `values` with fully
 //               coalesced nontemporal 8-byte loads through a wave-private LDS strip, keeps x / y at 8 bytes per lane and
-//               deals tiles to the XCDs in runs;
+//               deals tiles to the XCDs in runs; a CG slab whose matrix is bitwise symmetric streams [C, E] + S planes
+//               instead (24 B of coefficients per row, not 40: SymPlanes, kernels.hpp), with the same fma chains;
 //   row-direct  (smaller grids) one thread per row on a 2-D index space, the reference's own shape without its divisions;
 //   row-generic (slabs that are not whole grid rows, unverified or non-stencil matrices) one thread per row, the
 //               reference's kernel as it stands: analytic interior rows where the structure was verified, the CSR loop else.
@@ -172,10 +173,16 @@ constexpr int kLdsTileCols = 128;
 // read with SYSTEM-scope loads: the writer is another agent (a peer GPU's stores over xGMI, or the RCCL receive kernel acting
 // for it), and no cache of this device may answer from a line it held before those rows arrived (2 x grid_size
 // values per iteration, nothing on the clock).
-template <int kMode, bool kFreshHalo = false>
+// kSym (the symmetric coefficient form of a solver slab, kernels.hpp SymPlanes): interior grid rows take C and E from the [C, E]
+// plane (one nontemporal 16-byte load per lane and row: read once per SpMV), S from the S plane and N = S[i - n] from the row
+// one grid row up (plain loads: the S line is re-read as N one grid row later, like x's N / S neighbours), and W = E[i - 1]
+// from the LDS copy of the tile's own E values (`strip`; lane 0 loads the one outside the tile). 24 B/row of coefficients
+// instead of 40. The fma chains are the CSR form's, value for value (the planes were verified bit for bit at creation).
+typedef double dbl2 __attribute__((ext_vector_type(2)));
+template <int kMode, bool kFreshHalo = false, bool kSym = false>
 __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __restrict__ x, double* __restrict__ y, double alpha,
                                             int li, int gi, int j0, int lane, int skip, double* __restrict__ strip,
-                                            double* __restrict__ xrow, const ResidualOut& res, double* dot) {
+                                            double* __restrict__ xrow, const ResidualOut& res, double* dot, const SymPlanes& sp = SymPlanes{}) {
     constexpr bool kDot = kMode == 1;
     constexpr bool kInit = kMode == 2;
     const int n = m.grid_size;
@@ -187,7 +194,22 @@ __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __re
         const long long e = stencil_gridrow_base(gi, n) + 5LL * j0 - 1 - m.nnz_base + lane;
         const double* __restrict__ vals = m.values;
         double c[10];
-        if (j0 == 0 || j0 + kLdsTileCols > n - 1) {
+        dbl2 ce[2];                           // kSym: [C, E] of the lane's two rows
+        double cs[2], cn[2], cw = 0.0;        // kSym: S, N = S[i - n]; lane 0: E[i - 1] of the tile's first row
+        if constexpr (kSym) {
+            const long long r0 = (long long)li * n + j0 + lane;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                ce[h] = dbl2{0.0, 0.0};
+                cs[h] = cn[h] = 0.0;
+                if (j0 + lane + 64 * h < n) {
+                    ce[h] = __builtin_nontemporal_load(reinterpret_cast<const dbl2*>(sp.ce) + r0 + 64 * h);
+                    cs[h] = sp.s[r0 + 64 * h];
+                    cn[h] = sp.s[r0 + 64 * h - n];  // local grid row 0: the halo row in front of the plane
+                }
+            }
+            if (lane == 0 && j0 > 0) cw = sp.ce[2 * (r0 - 1) + 1];
+        } else if (j0 == 0 || j0 + kLdsTileCols > n - 1) {
             // first / last tile of the grid row: part of the run lies outside the row (at the slab's
             // ends: outside the array): clamp the addresses, those strip slots feed no row
             const long long hi = m.nnz_local - 1;
@@ -222,8 +244,14 @@ __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __re
             }
         }
         if (skip != 0) return false;
+        if constexpr (kSym) {
+            strip[1 + lane] = ce[0].y;
+            strip[65 + lane] = ce[1].y;
+            if (lane == 0) strip[0] = cw;
+        } else {
 #pragma unroll
-        for (int k = 0; k < 10; ++k) strip[64 * k + lane] = c[k];
+            for (int k = 0; k < 10; ++k) strip[64 * k + lane] = c[k];
+        }
         xrow[1 + lane] = xc[0];
         xrow[65 + lane] = xc[1];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -235,13 +263,37 @@ __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __re
         xw[1] = xrow[64 + lane];
         if (lane < 63) xe[1] = xrow[66 + lane];
         if (j0 + lane == n - 1) xe[0] = 0.0;
+        double cwv[2] = {0.0, 0.0};  // kSym: W = E[i - 1]
+        if constexpr (kSym) {
+            cwv[0] = strip[lane];
+            cwv[1] = strip[64 + lane];
+        }
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int j = j0 + lane + 64 * h;
             if (j < n) {
                 const double* __restrict__ v = strip + 5 * (lane + 64 * h);
                 double sum;
-                if (j > 0 && j < n - 1) {            // [N,W,C,E,S], evaluated W,C,E,N,S
+                if constexpr (kSym) {
+                    const double vw = cwv[h], vc = ce[h].x, ve = ce[h].y, vn = cn[h], vs = cs[h];
+                    if (j > 0 && j < n - 1) {        // W,C,E,N,S
+                        sum = vw * xw[h];
+                        sum = fma(vc, xc[h], sum);
+                        sum = fma(ve, xe[h], sum);
+                        sum = fma(vn, xn[h], sum);
+                        sum = fma(vs, xs[h], sum);
+                    } else if (j == 0) {             // CSR-loop order: N,C,E,S
+                        sum = fma(vn, xn[h], 0.0);
+                        sum = fma(vc, xc[h], sum);
+                        sum = fma(ve, xe[h], sum);
+                        sum = fma(vs, xs[h], sum);
+                    } else {                         // j == n-1, CSR-loop order: N,W,C,S
+                        sum = fma(vn, xn[h], 0.0);
+                        sum = fma(vw, xw[h], sum);
+                        sum = fma(vc, xc[h], sum);
+                        sum = fma(vs, xs[h], sum);
+                    }
+                } else if (j > 0 && j < n - 1) {     // [N,W,C,E,S], evaluated W,C,E,N,S
                     sum = v[1] * xw[h];
                     sum = fma(v[2], xc[h], sum);
                     sum = fma(v[3], xe[h], sum);
@@ -312,8 +364,8 @@ template <int kMode>
 __global__ __launch_bounds__(64) void stencil5_rowlds_kernel(
     SlabCsr m, const double* __restrict__ x, double* __restrict__ y, double alpha, int gi_lo, int row_step,
     int gfirst, int col_tiles, int total_tiles, int run, int reverse, double* __restrict__ dot_partials,
-    const int* __restrict__ skip_flag, ResidualOut res) {
-    __shared__ double strip[5 * kLdsTileCols];
+    const int* __restrict__ skip_flag, ResidualOut res, SymPlanes sp) {
+    __shared__ double strip[5 * kLdsTileCols];  // the tile's coefficients; the symmetric form: its E values (W of the next row)
     __shared__ double xrow[kLdsTileCols + 2];  // the tile's x values: W / E are read back from here
     const int skip = skip_flag != nullptr ? __builtin_nontemporal_load(skip_flag) : 0;
     const int tile = rowlds_tile_of_block((int)blockIdx.x, run, total_tiles, reverse);
@@ -322,7 +374,13 @@ __global__ __launch_bounds__(64) void stencil5_rowlds_kernel(
     const int col_tile = tile - row_group * col_tiles;
     const int li = gi_lo + row_group * row_step;  // local grid row (row_step > 1: a launch over separate grid rows)
     double dot = 0.0;
-    if (!rowlds_tile<kMode>(m, x, y, alpha, li, gfirst + li, col_tile * kLdsTileCols, (int)threadIdx.x, skip, strip, xrow, res, &dot)) return;
+    // the coefficient form is a launch argument (one uniform branch), not a template argument: the in-loop SpMV keeps the one
+    // kernel symbol, stencil5_rowlds_kernel<1>, that bench.py and profiles/hbm_traffic.json identify it by
+    const bool live = sp.ce != nullptr
+                          ? rowlds_tile<kMode, false, true>(m, x, y, alpha, li, gfirst + li, col_tile * kLdsTileCols, (int)threadIdx.x, skip, strip,
+                                                            xrow, res, &dot, sp)
+                          : rowlds_tile<kMode>(m, x, y, alpha, li, gfirst + li, col_tile * kLdsTileCols, (int)threadIdx.x, skip, strip, xrow, res, &dot);
+    if (!live) return;
     if (kMode != 0 && threadIdx.x == 0) dot_partials[tile] = dot;
 }
 
@@ -340,7 +398,7 @@ __global__ __launch_bounds__(64) void stencil5_rowlds_kernel(
 __global__ __launch_bounds__(kReduceBlock) void stencil5_rowlds_edges_reduce_kernel(
     SlabCsr m, const double* __restrict__ x, double* __restrict__ y, double alpha, int li_first, int li_step, int gfirst,
     int col_tiles, int edge_tiles, int edge_blocks, const double* __restrict__ interior_partials, int interior_count, int slice,
-    int slice_blocks, ReduceStage stage, ReduceTail tail, HaloArrival halo) {
+    int slice_blocks, ReduceStage stage, ReduceTail tail, HaloArrival halo, SymPlanes sp) {
     __shared__ double strip[kWavesPerBlock][5 * kLdsTileCols];
     __shared__ double xrow[kWavesPerBlock][kLdsTileCols + 2];
     __shared__ double s[kReduceBlock];
@@ -375,11 +433,13 @@ __global__ __launch_bounds__(kReduceBlock) void stencil5_rowlds_edges_reduce_ker
                 // caches by their own system-scope loads.
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                live = rowlds_tile<1, true>(m, x, y, alpha, li, gfirst + li, (tile - row_group * col_tiles) * kLdsTileCols, lane, skip, strip[wave],
-                                            xrow[wave], none, &dot);
+                const int j0 = (tile - row_group * col_tiles) * kLdsTileCols;
+                live = sp.ce != nullptr ? rowlds_tile<1, true, true>(m, x, y, alpha, li, gfirst + li, j0, lane, skip, strip[wave], xrow[wave], none, &dot, sp)
+                                        : rowlds_tile<1, true>(m, x, y, alpha, li, gfirst + li, j0, lane, skip, strip[wave], xrow[wave], none, &dot);
             } else {
-                live = rowlds_tile<1>(m, x, y, alpha, li, gfirst + li, (tile - row_group * col_tiles) * kLdsTileCols, lane, skip, strip[wave],
-                                      xrow[wave], none, &dot);
+                const int j0 = (tile - row_group * col_tiles) * kLdsTileCols;
+                live = sp.ce != nullptr ? rowlds_tile<1, false, true>(m, x, y, alpha, li, gfirst + li, j0, lane, skip, strip[wave], xrow[wave], none, &dot, sp)
+                                        : rowlds_tile<1>(m, x, y, alpha, li, gfirst + li, j0, lane, skip, strip[wave], xrow[wave], none, &dot);
             }
             if (live && lane == 0) publish(stage.extra + tile, dot);
         }
@@ -814,6 +874,43 @@ __global__ __launch_bounds__(kBlock) void verify_stencil5_kernel(SlabCsr m, int*
     if (!ok) *mismatch = 1;  // benign race: every writer stores the same value
 }
 
+// Symmetric coefficient planes of a verified stencil slab (kernels.hpp, SymPlanes): C, E (0 in column n-1) and S (0 in the
+// grid's last row) of every local row copied from its CSR entries, and the halo row in front of the S plane: the slab's own
+// N entries of its first grid row (0 in the grid's first row).
+__global__ __launch_bounds__(kBlock) void fill_sym_planes_kernel(SlabCsr m, double* __restrict__ ce, double* __restrict__ s) {
+    const long long lr = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (lr >= m.n_local) return;
+    const int n = m.grid_size;
+    const long long g = (long long)m.row_offset + lr;
+    const int i = (int)(g / n), j = (int)(g - (long long)i * n);
+    const double* __restrict__ v = m.values + m.row_ptr[lr];
+    const int kc = (i > 0 ? 1 : 0) + (j > 0 ? 1 : 0);  // the centre's position in the row: after N and W
+    ce[2 * lr] = v[kc];
+    ce[2 * lr + 1] = j < n - 1 ? v[kc + 1] : 0.0;
+    s[lr] = i < n - 1 ? v[m.row_ptr[lr + 1] - m.row_ptr[lr] - 1] : 0.0;
+    if (lr < n) s[lr - n] = i > 0 ? v[0] : 0.0;
+}
+
+__device__ __forceinline__ bool same_bits(double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b); }
+
+// *mismatch = 1 if a row the row-lds kernel evaluates from the planes (every row of grid rows 1 .. n-2) would take any value
+// whose 64-bit pattern differs from the CSR entry the CSR form multiplies there: W = E[i - 1], N = S[i - n] (or the halo row),
+// C, E, S. Bit patterns, not ==: -0.0 against +0.0 or two NaN payloads keep the CSR form.
+__global__ __launch_bounds__(kBlock) void verify_sym_planes_kernel(SlabCsr m, SymPlanes p, int* __restrict__ mismatch) {
+    const long long lr = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (lr >= m.n_local) return;
+    const int n = m.grid_size;
+    const long long g = (long long)m.row_offset + lr;
+    const int i = (int)(g / n), j = (int)(g - (long long)i * n);
+    if (i == 0 || i == n - 1) return;  // the grid's first and last grid row take the CSR loop in every form
+    const double* __restrict__ v = m.values + m.row_ptr[lr];  // [N, (W), C, (E), S]
+    const int kc = j > 0 ? 2 : 1;
+    bool ok = same_bits(p.s[lr - n], v[0]) && same_bits(p.ce[2 * lr], v[kc]) && same_bits(p.s[lr], v[m.row_ptr[lr + 1] - m.row_ptr[lr] - 1]);
+    if (j > 0) ok = ok && same_bits(p.ce[2 * (lr - 1) + 1], v[1]);
+    if (j < n - 1) ok = ok && same_bits(p.ce[2 * lr + 1], v[kc + 1]);
+    if (!ok) *mismatch = 1;  // benign race: every writer stores the same value
+}
+
 inline unsigned blocks_for(long long items) { return (unsigned)((items + kBlock - 1) / kBlock); }
 
 }  // namespace
@@ -834,6 +931,16 @@ void launch_verify_stencil5_csr(const SlabCsr& m, int* d_mismatch, hipStream_t s
     if (m.n_local == 0) return;
     hipLaunchKernelGGL(verify_stencil5_kernel, dim3(blocks_for(m.n_local)), dim3(kBlock), 0, stream,
                        m, d_mismatch);
+}
+
+void launch_fill_sym_planes(const SlabCsr& m, double* ce, double* s, hipStream_t stream) {
+    if (m.n_local == 0) return;
+    hipLaunchKernelGGL(fill_sym_planes_kernel, dim3(blocks_for(m.n_local)), dim3(kBlock), 0, stream, m, ce, s);
+}
+
+void launch_verify_sym_planes(const SlabCsr& m, const SymPlanes& planes, int* d_mismatch, hipStream_t stream) {
+    if (m.n_local == 0) return;
+    hipLaunchKernelGGL(verify_sym_planes_kernel, dim3(blocks_for(m.n_local)), dim3(kBlock), 0, stream, m, planes, d_mismatch);
 }
 
 // Consecutive row-lds tiles one XCD takes of every run of 8 * run tiles. A run a little longer than one grid row lets an XCD
@@ -898,14 +1005,16 @@ int launch_stencil5_spmv(const SlabCsr& m, const double* x, double* y, double al
 namespace {
 // the row-lds kernel over `tiles` tiles: `row_step` grid rows between consecutive row groups (1: a contiguous range)
 void launch_rowlds(const SlabCsr& m, const Stencil5Plan& p, const double* x, double* y, double alpha, int gi_lo, int row_step,
-                   int tiles, double* d_dot_partials, const int* d_skip_flag, bool reverse, hipStream_t stream, const ResidualOut* init) {
+                   int tiles, double* d_dot_partials, const int* d_skip_flag, bool reverse, hipStream_t stream, const ResidualOut* init,
+                   const SymPlanes* planes) {
     const int span = 8 * p.xcd_run;
     const dim3 grid((unsigned)(((long long)tiles + span - 1) / span * span));
     const int gfirst = m.row_offset / m.grid_size;
     const ResidualOut res = init ? *init : ResidualOut{nullptr, nullptr, nullptr};
+    const SymPlanes sp = planes ? *planes : SymPlanes{};
 #define SPMV_AMD_LAUNCH_ROWLDS(MODE)                                                                                   \
     hipLaunchKernelGGL((stencil5_rowlds_kernel<MODE>), grid, dim3(64), 0, stream, m, x, y, alpha, gi_lo, row_step, gfirst, \
-                       p.row_blocks, tiles, p.xcd_run, reverse ? 1 : 0, d_dot_partials, d_skip_flag, res)
+                       p.row_blocks, tiles, p.xcd_run, reverse ? 1 : 0, d_dot_partials, d_skip_flag, res, sp)
     if (init) SPMV_AMD_LAUNCH_ROWLDS(2);
     else if (d_dot_partials) SPMV_AMD_LAUNCH_ROWLDS(1);
     else SPMV_AMD_LAUNCH_ROWLDS(0);
@@ -915,7 +1024,7 @@ void launch_rowlds(const SlabCsr& m, const Stencil5Plan& p, const double* x, dou
 
 int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& p, const double* x, double* y, double alpha,
                          double* d_dot_partials, const int* d_skip_flag, bool reverse, hipStream_t stream,
-                         const ResidualOut* init) {
+                         const ResidualOut* init, const SymPlanes* planes) {
     if (p.last_row <= p.first_row) return 0;
     if (init != nullptr && (p.variant != Stencil5Variant::RowLds || d_dot_partials == nullptr)) {
         fprintf(stderr, "[spmv] the fused initial residual exists for the row-lds kernel only\n");
@@ -923,7 +1032,7 @@ int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& p, const double* 
     }
     const bool dot = d_dot_partials != nullptr;
     if (p.variant == Stencil5Variant::RowLds) {
-        launch_rowlds(m, p, x, y, alpha, p.gi_lo, 1, p.partials, d_dot_partials, d_skip_flag, reverse, stream, init);
+        launch_rowlds(m, p, x, y, alpha, p.gi_lo, 1, p.partials, d_dot_partials, d_skip_flag, reverse, stream, init, planes);
     } else if (p.variant == Stencil5Variant::RowDirect) {
         const dim3 grid((unsigned)p.partials);
         if (dot)
@@ -952,19 +1061,20 @@ int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& p, const double* 
 
 int launch_stencil5_spmv_first_and_last_gridrow(const SlabCsr& m, const Stencil5Plan& head, const Stencil5Plan& tail, const double* x,
                                                 double* y, double alpha, double* d_dot_partials, const int* d_skip_flag,
-                                                hipStream_t stream, const ResidualOut* init) {
+                                                hipStream_t stream, const ResidualOut* init, const SymPlanes* planes) {
     const int n = m.grid_size;
     const int local_gridrows = n > 0 ? m.n_local / n : 0;
     if (head.variant != Stencil5Variant::RowLds || tail.variant != Stencil5Variant::RowLds || local_gridrows < 2) {
         // two launches over the two row ranges (any variant)
-        int used = launch_stencil5_spmv(m, head, x, y, alpha, d_dot_partials, d_skip_flag, false, stream, init);
-        used += launch_stencil5_spmv(m, tail, x, y, alpha, d_dot_partials ? d_dot_partials + used : nullptr, d_skip_flag, false, stream, init);
+        int used = launch_stencil5_spmv(m, head, x, y, alpha, d_dot_partials, d_skip_flag, false, stream, init, planes);
+        used += launch_stencil5_spmv(m, tail, x, y, alpha, d_dot_partials ? d_dot_partials + used : nullptr, d_skip_flag, false, stream, init,
+                                     planes);
         return used;
     }
     // one launch: row group 0 is local grid row 0, row group 1 is the last local grid row; the partial slots
     // are those of the two separate launches back to back
     const int tiles = 2 * head.row_blocks;
-    launch_rowlds(m, head, x, y, alpha, 0, local_gridrows - 1, tiles, d_dot_partials, d_skip_flag, false, stream, init);
+    launch_rowlds(m, head, x, y, alpha, 0, local_gridrows - 1, tiles, d_dot_partials, d_skip_flag, false, stream, init, planes);
     return d_dot_partials ? tiles : 0;
 }
 
@@ -981,7 +1091,7 @@ void launch_halo_arrived(unsigned* d_flag, unsigned sequence, hipStream_t stream
 bool launch_stencil5_edges_and_reduce(const SlabCsr& m, const Stencil5Plan& interior, bool first_gridrow, bool last_gridrow, const double* x,
                                       double* y, double alpha, const double* d_interior_partials, double* d_out, const int* d_skip_flag,
                                       const ReduceScratch& scratch, int* host_progress, int progress_value, const PeerMailbox* mailbox,
-                                      hipStream_t stream, const HaloArrival& halo) {
+                                      hipStream_t stream, const HaloArrival& halo, const SymPlanes* planes) {
     const int n = m.grid_size;
     if (interior.variant != Stencil5Variant::RowLds || scratch.base == nullptr || (!first_gridrow && !last_gridrow) ||
         interior.partials <= 0 || n <= 0 || m.n_local % n != 0)
@@ -996,7 +1106,8 @@ bool launch_stencil5_edges_and_reduce(const SlabCsr& m, const Stencil5Plan& inte
     const ReduceTail tail{d_out, d_skip_flag, host_progress, progress_value, mailbox, StepArgs{nullptr, 0.0, nullptr, nullptr, 0, nullptr, 0}};
     hipLaunchKernelGGL(stencil5_rowlds_edges_reduce_kernel, dim3((unsigned)(edge_blocks + slice_blocks)), dim3(kReduceBlock), 0, stream, m, x, y,
                        alpha, first_gridrow ? 0 : local_gridrows - 1, local_gridrows - 1, m.row_offset / n, col_tiles, edge_tiles, edge_blocks,
-                       d_interior_partials, interior.partials, slice, slice_blocks, reduce_stage_of(scratch.base), tail, halo);
+                       d_interior_partials, interior.partials, slice, slice_blocks, reduce_stage_of(scratch.base), tail, halo,
+                       planes ? *planes : SymPlanes{});
     return true;
 }
 

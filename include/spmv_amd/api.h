@@ -409,6 +409,11 @@ int spmv_amd_cg_slab_tile_runs(const SpmvAmdCgSlab* s, double* out, int cap);
  * reference builds and uploads before its own, cg_solver_mgpu_partitioned.cu:303-413): {matrix to HBM (upload or generation),
  * streams + vectors, verification + launch plans, coefficient placement trial, tile-run trial}. Returns 5. */
 int spmv_amd_cg_slab_setup_ms(const SpmvAmdCgSlab* s, double* out, int cap);
+/* The coefficients the slab's SpMV streams (csrc/cg_slab.hip): 0 = its CSR values (40 B/row), 1 = the symmetric planes
+ * (24 B/row: C, E and S per row; W and N are the E of row i-1 and the S of row i-n). A slab takes the planes when it owns its
+ * matrix, every launch is a row-lds launch and those W / N entries equal their CSR entries bit for bit (checked at creation);
+ * the results are the CSR form's, bit for bit. */
+int spmv_amd_cg_slab_coefficient_form(const SpmvAmdCgSlab* s);
 /* The timed in-loop SpMV launches of the last solve, one by one (ms, iteration order). Returns their number. */
 int spmv_amd_cg_slab_spmv_launch_ms(const SpmvAmdCgSlab* s, float* out, int cap);
 const char* spmv_amd_cg_slab_timeline_names(void);

@@ -34,7 +34,9 @@ SpmvAmdCgSlab* spmv_amd_cg_slab_create_stencil5_as(int n, int as_rank, int as_wo
  * 2: test hook, every iteration is guessed "far", so each solve learns of its convergence one iteration late) --
  * results are bit-identical under each --, "spmv_event_stride" N (time every N-th in-loop SpMV launch; default 7, phase advancing with every solve; 0 = none),
  * and the one option that is NOT result-neutral, a timing aid for stand-in slabs: "stop_at" K (iteration K counts as the
- * converging one whatever its residual; 0 = off). Returns 0, or -1 for an unknown name. */
+ * converging one whatever its residual; 0 = off), and "csr_coefficients" 0/1 (1 = the SpMV streams the CSR values even where the
+ * slab holds the symmetric planes, spmv_amd_cg_slab_coefficient_form; results are bit-identical). Returns 0, or -1 for an
+ * unknown name. */
 int spmv_amd_cg_slab_set_option(SpmvAmdCgSlab* s, const char* name, long long value);
 
 #ifdef __cplusplus
