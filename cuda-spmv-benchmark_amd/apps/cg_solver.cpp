@@ -1,13 +1,53 @@
 // cg_solver -- counterpart of reference src/main/cg_solver.cu: b = 1, x0 = 0, 3 warm-up solves,
 // then 10 timed solves from x0 = 0 each.
 //   cg_solver <matrix.mtx | --stencil=N> [--mode=<m1,..>] [--host|--device] [--tol=1e-6]
-//             [--maxiter=1000] [--timers] [--json=<file>] [--csv=<file>]
+//             [--maxiter=1000] [--timers] [--json=<file>] [--csv=<file>] [--precond=none|jacobi]
+// --precond runs the preconditioned solver (spmv_amd_pcg_solve_device, device only); its JSON / CSV carry the mode string
+// <operator>+<kind>. Without it the binary takes cg_solve_device / cg_solve as before.
 // (The reference's own main, unmodified, also builds against this library: INTEGRATION.md. Unlike
 // it, this binary restarts every timed solve from x0 = 0 instead of from the warm-up's solution.)
+#include <algorithm>
+#include <cmath>
+
 #include "app_common.hpp"
 
+namespace {
+// num_runs preconditioned solves from x0 = 0 with the harness's statistics rule (csrc/harness.hip): mean and population sigma,
+// runs further than 2 sigma from the mean dropped, then median / min / max of the survivors; the stats of the last run.
+int pcg_runs(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, const double* b, std::vector<double>& x, CGConfig cfg,
+             int num_runs, BenchmarkStats* bs, CGStats* st) {
+    std::vector<double> t;
+    for (int k = 0; k < num_runs; ++k) {
+        std::fill(x.begin(), x.end(), 0.0);
+        if (spmv_amd_pcg_solve_device(op, mat, m, b, x.data(), &cfg, st) != 0) return 1;
+        t.push_back(st->time_total_ms);
+    }
+    double mean = 0.0, q = 0.0;
+    for (double v : t) mean += v;
+    mean /= (double)t.size();
+    for (double v : t) q += (v - mean) * (v - mean);
+    const double sigma = std::sqrt(q / (double)t.size());
+    std::vector<double> keep;
+    for (double v : t)
+        if (sigma == 0.0 || std::fabs(v - mean) <= 2.0 * sigma) keep.push_back(v);
+    std::sort(keep.begin(), keep.end());
+    double km = 0.0, kq = 0.0;
+    for (double v : keep) km += v;
+    km /= (double)keep.size();
+    for (double v : keep) kq += (v - km) * (v - km);
+    bs->mean_ms = km;
+    bs->std_dev_ms = std::sqrt(kq / (double)keep.size());
+    bs->median_ms = keep[keep.size() / 2];
+    bs->min_ms = keep.front();
+    bs->max_ms = keep.back();
+    bs->valid_runs = (int)keep.size();
+    bs->outliers_removed = (int)(t.size() - keep.size());
+    return 0;
+}
+}  // namespace
+
 int main(int argc, char** argv) {
-    const char *matrix = nullptr, *modes_text = "stencil5-csr", *json = nullptr, *csv = nullptr;
+    const char *matrix = nullptr, *modes_text = "stencil5-csr", *json = nullptr, *csv = nullptr, *precond = nullptr;
     int stencil = 0, maxiter = 1000, timers = 0;
     bool device = true;
     double tol = 1e-6;
@@ -18,6 +58,7 @@ int main(int argc, char** argv) {
         else if (const char* v4 = app::value_of(argv[i], "--stencil=")) stencil = atoi(v4);
         else if (const char* v5 = app::value_of(argv[i], "--tol=")) tol = atof(v5);
         else if (const char* v6 = app::value_of(argv[i], "--maxiter=")) maxiter = atoi(v6);
+        else if (const char* v7 = app::value_of(argv[i], "--precond=")) precond = v7;
         else if (!strcmp(argv[i], "--host")) device = false;
         else if (!strcmp(argv[i], "--device")) device = true;
         else if (!strcmp(argv[i], "--timers")) timers = 1;
@@ -25,6 +66,14 @@ int main(int argc, char** argv) {
     }
     if (!matrix && stencil <= 0) {
         fprintf(stderr, "Usage: %s <matrix.mtx | --stencil=N> [--mode=<modes>] [--host|--device] [--tol=] [--maxiter=] [--timers] [--json=] [--csv=]\n", argv[0]);
+        return 1;
+    }
+    if (precond && strcmp(precond, "none") != 0 && strcmp(precond, "jacobi") != 0) {
+        fprintf(stderr, "Error: unknown preconditioner '%s' (none, jacobi)\n", precond);
+        return 1;
+    }
+    if (precond && !device) {
+        fprintf(stderr, "Error: --precond runs the device solver only (no --host)\n");
         return 1;
     }
     const std::vector<std::string> modes = app::split_modes(modes_text);
@@ -57,6 +106,41 @@ int main(int argc, char** argv) {
         }
         CGConfig quiet = {maxiter, tol, 0, 0}, cfg = {maxiter, tol, 0, timers};
         CGStats st;
+        if (precond) {
+            int bad_row = -1;
+            SpmvAmdPrecond* pm = spmv_amd_precond_create(op, precond, &bad_row);
+            if (pm == nullptr) {
+                fprintf(stderr, "Failed to create the '%s' preconditioner (row %d)\n", precond, bad_row);
+                op->free();
+                continue;
+            }
+            const std::string tag = m + "+" + precond;
+            printf("Preconditioner: %s\nWarmup (3 runs)...\n", precond);
+            BenchmarkStats bs;
+            memset(&bs, 0, sizeof bs);
+            bool ok = pcg_runs(op, &mat, pm, b.data(), x, quiet, 3, &bs, &st) == 0;
+            memset(&bs, 0, sizeof bs);
+            if (ok) printf("Running benchmark (10 runs)...\n");
+            ok = ok && pcg_runs(op, &mat, pm, b.data(), x, cfg, 10, &bs, &st) == 0;
+            spmv_amd_precond_destroy(pm);
+            if (!ok) {
+                fprintf(stderr, "benchmark failed\n");
+                op->free();
+                continue;
+            }
+            printf("Completed: %d valid runs, %d outliers removed\n", bs.valid_runs, bs.outliers_removed);
+            printf("\n--- Results for %s ---\nConverged: %s in %d iterations\nTime (median): %.3f ms\n", tag.c_str(),
+                   st.converged ? "YES" : "NO", st.iterations, bs.median_ms);
+            printf("Stats: min=%.3f ms, max=%.3f ms, std=%.3f ms\n", bs.min_ms, bs.max_ms, bs.std_dev_ms);
+            printf("\n=== Output Checksum ===\nSum(x):    %.16e\nNorm2(x):  %.16e\n", st.solution_sum, st.solution_norm);
+            if (json) export_cg_json(app::per_mode_path(json, tag.c_str(), ".json").c_str(), tag.c_str(), &mat, &bs, &st);
+            if (csv) {
+                export_cg_csv(csv, tag.c_str(), &mat, &bs, &st, first_csv);
+                first_csv = false;
+            }
+            op->free();
+            continue;
+        }
         printf("Warmup (3 runs)...\n");
         for (int w = 0; w < 3; ++w) {
             std::fill(x.begin(), x.end(), 0.0);

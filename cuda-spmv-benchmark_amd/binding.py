@@ -103,6 +103,8 @@ DECLARED_SYMBOLS = [
     "spmv_amd_cg_fused_step",
     "spmv_amd_spmm_device", "spmv_amd_spmm_variant", "spmv_amd_block_to_device", "spmv_amd_block_to_host",
     "spmv_amd_cg_solve_device_multi", "spmv_amd_cg_last_history_multi", "spmv_amd_cg_multi_workspace_bytes",
+    "spmv_amd_precond_create", "spmv_amd_precond_create_from_diagonal", "spmv_amd_precond_destroy", "spmv_amd_precond_kind",
+    "spmv_amd_precond_inverse_diagonal", "spmv_amd_pcg_solve_device", "spmv_amd_pcg_last_history", "spmv_amd_pcg_release_workspace",
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
 LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option"]
@@ -538,6 +540,91 @@ def cg_solve_multi(op, host_matrix, Bk, X0k, max_iters=1000, tol=1e-6, verbose=0
         count = L.spmv_amd_cg_last_history_multi(j, h.ctypes.data, len(h))
         hists.append(h[:count].copy())
     return X, hists, list(stats)
+
+
+# ---------------------------------------------------------------- preconditioned CG (include/spmv_amd/api.h)
+def _pcg_lib():
+    """lib() with the signatures of the preconditioned-CG entry points set."""
+    L = lib()
+    if not getattr(L, "_pcg_sigs", False):
+        L.spmv_amd_precond_create.argtypes = [C.POINTER(SpmvOperator), C.c_char_p, C.POINTER(C.c_int)]
+        L.spmv_amd_precond_create.restype = C.c_void_p
+        L.spmv_amd_precond_create_from_diagonal.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.spmv_amd_precond_create_from_diagonal.restype = C.c_void_p
+        L.spmv_amd_precond_destroy.argtypes = [C.c_void_p]
+        L.spmv_amd_precond_destroy.restype = None
+        L.spmv_amd_precond_kind.argtypes = [C.c_void_p]
+        L.spmv_amd_precond_kind.restype = C.c_char_p
+        L.spmv_amd_precond_inverse_diagonal.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.spmv_amd_pcg_solve_device.argtypes = [C.POINTER(SpmvOperator), C.POINTER(MatrixData), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(CGConfig), C.POINTER(CGStats)]
+        L.spmv_amd_pcg_last_history.argtypes = [C.c_void_p, C.c_int]
+        L.spmv_amd_pcg_release_workspace.argtypes = []
+        L.spmv_amd_pcg_release_workspace.restype = None
+        L._pcg_sigs = True
+    return L
+
+
+class Precond:
+    """Owner of an SpmvAmdPrecond handle. Precond(op, kind) or Precond.from_diagonal(d); a refusal raises ValueError with
+    .bad_row (the first offending row, or -1)."""
+
+    def __init__(self, op=None, kind="jacobi", _handle=None, _n=0):
+        if _handle is None:
+            bad = C.c_int(-2)
+            _handle = _pcg_lib().spmv_amd_precond_create(op.op, kind.encode(), C.byref(bad))
+            if not _handle:
+                err = ValueError(f"precond_create({op.name}, {kind}) refused, bad_row = {bad.value}")
+                err.bad_row = bad.value
+                raise err
+            _n = op.rows
+        self.handle = _handle
+        self.n = _n
+
+    @classmethod
+    def from_diagonal(cls, d):
+        d = np.ascontiguousarray(d, dtype=np.float64)
+        dv = DeviceVector.from_host(d)
+        try:
+            bad = C.c_int(-2)
+            h = _pcg_lib().spmv_amd_precond_create_from_diagonal(dv.ptr, len(d), C.byref(bad))
+        finally:
+            dv.free()
+        if not h:
+            err = ValueError(f"precond_create_from_diagonal refused, bad_row = {bad.value}")
+            err.bad_row = bad.value
+            raise err
+        return cls(_handle=h, _n=len(d))
+
+    @property
+    def kind(self):
+        return _pcg_lib().spmv_amd_precond_kind(self.handle).decode()
+
+    def inverse_diagonal(self):
+        out = np.empty(self.n, dtype=np.float64)
+        if _pcg_lib().spmv_amd_precond_inverse_diagonal(self.handle, out.ctypes.data, self.n) != 0:
+            raise RuntimeError("precond_inverse_diagonal refused")
+        return out
+
+    def destroy(self):
+        if self.handle:
+            _pcg_lib().spmv_amd_precond_destroy(self.handle)
+            self.handle = None
+
+
+def pcg_solve_device(op, host_matrix, precond, b, x0, max_iters=1000, tol=1e-6, verbose=0, timers=0):
+    """spmv_amd_pcg_solve_device; returns x, history, stats (raises RuntimeError on a refusal)."""
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    x = np.ascontiguousarray(x0, dtype=np.float64).copy()
+    cfg = CGConfig(max_iters, tol, verbose, timers)
+    st = CGStats()
+    L = _pcg_lib()
+    rc = L.spmv_amd_pcg_solve_device(op.op, host_matrix.ptr, precond.handle, b.ctypes.data, x.ctypes.data, C.byref(cfg), C.byref(st))
+    if rc != 0:
+        raise RuntimeError(f"pcg_solve_device -> {rc}")
+    hist = np.zeros(max_iters + 1, dtype=np.float64)
+    count = L.spmv_amd_pcg_last_history(hist.ctypes.data, len(hist))
+    return x, hist[:count].copy(), st
 
 
 class Comm:

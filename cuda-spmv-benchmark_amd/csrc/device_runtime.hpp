@@ -162,6 +162,26 @@ struct FusedSpmv {
 FusedSpmv fused_spmv_of(const SpmvOperator* op);
 // Frees the vectors cg_solve_device keeps between calls (cg_slab.hip); called by every operator's free().
 void release_cg_workspace();
+// The same for the preconditioned solver (pcg.hip); the caller holds the workspace lock (release_cg_workspace does).
+void release_pcg_workspace_locked();
+
+// The device storage an operator of this library keeps its matrix in, for reading its diagonal (pcg.hip): the CSR of
+// stencil5-csr / cusparse-csr, or the slot-major planes of ellpack / stencil5-ellpack (idx[k * rows + r], -1 = padding).
+// Entries of a row appear in CSR order in both (build_csr_struct's stable sort; ELL slots follow it). owner == nullptr: an
+// operator table this library does not own. generation changes with every init and free() of the operator. Defined in
+// operators.hip; host state only (no HIP call).
+struct DiagonalSource {
+    enum Kind { None, Csr, Ell } kind = None;
+    const void* owner = nullptr;
+    bool ready = false;
+    int rows = 0, cols = 0;
+    unsigned long long generation = 0;
+    SlabCsr csr;
+    const int* idx = nullptr;
+    const double* val = nullptr;
+    int width = 0;
+};
+DiagonalSource diagonal_source_of(const SpmvOperator* op);
 
 // Device-resident CSR of one operator or one slab (owning).
 struct DeviceCsr {

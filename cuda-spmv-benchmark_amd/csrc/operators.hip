@@ -44,6 +44,7 @@ struct CsrBackedOperator {
     double tuning[4] = {0, 0, 0, 0};  // {rule, kept, ms with the rule, ms kept}
     int y_candidates = 1;      // output placement: candidates timed for dY, and what the choice was worth (device_runtime.hpp)
     double y_gain = 1.0;
+    unsigned long long generation = 0;  // bumped by every init and free (drop()): what a preconditioner was made from (pcg.hip)
     void alloc_vectors() {
         dX = device_alloc<double>((size_t)cols);
         dY = nullptr;  // placed by place_output() once the kernel that writes it is known
@@ -101,6 +102,7 @@ struct CsrBackedOperator {
         A.release();
         device_release(dX);
         device_release(dY);
+        ++generation;
         ready = false;
         tuned_run = 0;
         variant_name = "uninitialised";
@@ -265,7 +267,9 @@ struct EllOperator {
     const char* variant_name = "uninitialised";
     int y_candidates = 1;  // output placement (device_runtime.hpp)
     double y_gain = 1.0;
+    unsigned long long generation = 0;  // as CsrBackedOperator's
     void drop() {
+        ++generation;
         device_release(planes_block);
         idx = nullptr;
         val = nullptr;
@@ -489,6 +493,29 @@ MultiOperand multi_operand_of(const SpmvOperator* op) {
         if (o.ready) o.plan = plan_spmm(g_csr.A.view, Stencil5Variant::Auto, true, g_csr.rows, g_csr.cols);
     }
     return o;
+}
+
+// Where a Jacobi preconditioner reads the diagonal (pcg.hip): the operator's own device storage, no copy.
+DiagonalSource diagonal_source_of(const SpmvOperator* op) {
+    DiagonalSource d;
+    const CsrBackedOperator* c = (op == &SPMV_STENCIL5_CSR || op == &SPMV_STENCIL_HALO_MGPU) ? &g_stencil : op == &SPMV_CSR ? &g_csr : nullptr;
+    const EllOperator* e = op == &SPMV_ELLPACK ? &g_ell : op == &SPMV_STENCIL5_ELLPACK ? &g_ell_stencil : nullptr;
+    if (c != nullptr) {
+        d.owner = c;
+        d.kind = DiagonalSource::Csr;
+        d.ready = c->ready;
+        d.rows = c->rows, d.cols = c->cols;
+        d.generation = c->generation;
+        d.csr = c->A.view;
+    } else if (e != nullptr) {
+        d.owner = e;
+        d.kind = DiagonalSource::Ell;
+        d.ready = e->ready;
+        d.rows = e->rows, d.cols = e->cols;
+        d.generation = e->generation;
+        d.idx = e->idx, d.val = e->val, d.width = e->width;
+    }
+    return d;
 }
 }  // namespace spmv_amd
 

@@ -1,0 +1,645 @@
+// pcg.hip -- Jacobi-preconditioned CG over any SpmvOperator.
+//
+// A new entry point with its own loop, built the way cg_multi.hip is: the algebra of cg_solve_device with z = M^-1 r,
+// M = diag(A) ("jacobi") or I ("none"), the same stopping rule (true residual ||r_k|| / ||r_0|| < tol, strict, the
+// converging iteration counted), statistics and timer rule. One iteration:
+//   Ap = A p with the p.Ap partials (the operator's fused launch; else run_device + a dot pass) |
+//   sum + step (alpha = rz / pAp) |
+//   r -= alpha Ap, z = dinv r in registers, partials of r.r and r.z |
+//   both sums + step (history, verdict, beta = rz' / rz) |
+//   x += alpha p, p = dinv r + beta p
+// then one small blocking read of the scalars (the stopping test; microseconds against milliseconds of work). Bytes per
+// interior row and iteration on stencil5-csr: 56 (SpMV) + 32 + 48 = 136 ("jacobi"), 120 ("none"); no direction ring, no
+// deferred x update, no run-ahead (that machinery is the slab loop's, cg_slab.hip).
+// Breakdown: a pAp or r.z' that is zero or not finite stops the loop in that iteration with converged = 0 (no sign test:
+// negative-definite systems solve). Sums have a fixed shape (reduce_device.hpp): a solve is bit-reproducible.
+#include <limits.h>
+#include <math.h>
+#include <string.h>
+
+#include <vector>
+
+#include "device_runtime.hpp"
+#include "multi_rhs.hpp"
+#include "reduce_device.hpp"
+
+using namespace spmv_amd;
+
+enum PrecondKind { kNone = 0, kJacobi = 1 };
+
+struct SpmvAmdPrecond {
+    int kind = kNone;
+    int n = 0;
+    const void* owner = nullptr;  // the operator state the diagonal came from (DiagonalSource::owner); null: a caller's diagonal
+    unsigned long long generation = 0;
+    double* dinv = nullptr;       // device, n values ("jacobi")
+};
+
+namespace {
+
+constexpr hipStream_t kStream = nullptr;  // default stream, shared with the operators
+constexpr int kWave = 64;                 // the streaming kernels: one wavefront per workgroup, one 16-byte pair per lane
+
+typedef double d2 __attribute__((ext_vector_type(2)));
+
+// Device scalars of one preconditioned solve.
+struct PcgScalars {
+    double rz;        // r.z of the current residual
+    double pAp, alpha, beta;
+    double b_norm;    // ||r0||
+    double residual;  // ||r_k||
+    int iterations;
+    int converged;    // stopping test met
+    int breakdown;    // pAp or r.z' zero or not finite: stopped, not converged
+    int skip_update;  // this iteration's pAp broke down: r and x stay as they are
+};
+
+__device__ __forceinline__ bool usable(double v) { return v != 0.0 && isfinite(v); }
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    return v;
+}
+
+__device__ __forceinline__ d2 load_once(const double* __restrict__ base, size_t pair) {
+    return __builtin_nontemporal_load(reinterpret_cast<const d2*>(base) + pair);
+}
+__device__ __forceinline__ void store_once(double* __restrict__ base, size_t pair, d2 v) {
+    __builtin_nontemporal_store(v, reinterpret_cast<d2*>(base) + pair);
+}
+
+unsigned stream_blocks(size_t n) {
+    const size_t want = ((n >> 1) + kWave - 1) / kWave;
+    return (unsigned)(want < 1 ? 1 : want);
+}
+
+// ---- diagonal extraction: d_i = sum of row i's entries in column i, CSR order, from 0.0; dinv_i = 1.0 / d_i ----
+// Validity in the same pass: d_i finite, non-zero and of d_0's sign, else atomicMin(bad_row, i).
+
+__device__ __forceinline__ double csr_diagonal(const SlabCsr& m, int r) {
+    double d = 0.0;
+    for (int j = m.row_ptr[r]; j < m.row_ptr[r + 1]; ++j)
+        if (m.col_idx[j] == r) d += m.values[j];
+    return d;
+}
+__device__ __forceinline__ double ell_diagonal(const int* __restrict__ idx, const double* __restrict__ val, int rows, int width, int r) {
+    double d = 0.0;
+    for (int k = 0; k < width; ++k)
+        if (idx[(long long)k * rows + r] == r) d += val[(long long)k * rows + r];
+    return d;
+}
+
+// src: 0 = CSR, 1 = ELL planes, 2 = a plain array of n values
+__device__ __forceinline__ double diagonal_at(int src, const SlabCsr& m, const int* idx, const double* val, int width, int n, int r) {
+    if (src == 0) return csr_diagonal(m, r);
+    if (src == 1) return ell_diagonal(idx, val, n, width, r);
+    return 0.0 + val[r];
+}
+
+__global__ __launch_bounds__(256) void diagonal_inverse_kernel(int src, SlabCsr m, const int* __restrict__ idx, const double* __restrict__ val,
+                                                               int width, int n, double* __restrict__ dinv, int* __restrict__ bad_row) {
+    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (r >= n) return;
+    const double d0 = diagonal_at(src, m, idx, val, width, n, 0);  // row 0: a few entries, the same cached lines for every lane
+    const double d = r == 0 ? d0 : diagonal_at(src, m, idx, val, width, n, r);
+    if (!usable(d) || (d > 0.0) != (d0 > 0.0)) atomicMin(bad_row, r);
+    dinv[r] = 1.0 / d;
+}
+
+// ---- the loop's streaming kernels (16-byte accesses, one pair per lane; the odd last row by lane 0 of workgroup 0) ----
+
+// r = b - Ap ; z = dinv r ; p = z ; partials of r.r and r.z (at partials[blk], partials[count + blk])
+template <bool kJac>
+__global__ __launch_bounds__(kWave) void pcg_init_kernel(size_t n, const double* __restrict__ b, const double* __restrict__ Ap,
+                                                         const double* __restrict__ dinv, double* __restrict__ r, double* __restrict__ p,
+                                                         double* __restrict__ partials, int count) {
+    const size_t i = (size_t)blockIdx.x * kWave + threadIdx.x;
+    double rr = 0.0, rz = 0.0;
+    if (i < (n >> 1)) {
+        const d2 bv = load_once(b, i), av = load_once(Ap, i);
+        d2 rv, zv;
+        rv.x = fma(1.0, bv.x, -1.0 * av.x);
+        rv.y = fma(1.0, bv.y, -1.0 * av.y);
+        if (kJac) {
+            const d2 dv = load_once(dinv, i);
+            zv.x = dv.x * rv.x, zv.y = dv.y * rv.y;
+        } else {
+            zv = rv;
+        }
+        store_once(r, i, rv);
+        reinterpret_cast<d2*>(p)[i] = zv;  // plain: the first SpMV reads it
+        rr = fma(rv.x, rv.x, rr), rr = fma(rv.y, rv.y, rr);
+        rz = fma(rv.x, zv.x, rz), rz = fma(rv.y, zv.y, rz);
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const double rl = fma(1.0, b[n - 1], -1.0 * Ap[n - 1]);
+        const double zl = kJac ? dinv[n - 1] * rl : rl;
+        r[n - 1] = rl, p[n - 1] = zl;
+        rr = fma(rl, rl, rr), rz = fma(rl, zl, rz);
+    }
+    rr = wave_sum(rr), rz = wave_sum(rz);
+    if (threadIdx.x == 0) partials[blockIdx.x] = rr, partials[count + blockIdx.x] = rz;
+}
+
+// r = fma(-alpha, Ap, r) (unless this iteration's pAp broke down) ; z = dinv r ; partials of r.r and r.z
+template <bool kJac>
+__global__ __launch_bounds__(kWave) void pcg_update_r_kernel(size_t n, const PcgScalars* __restrict__ s, const double* __restrict__ Ap,
+                                                             const double* __restrict__ dinv, double* __restrict__ r,
+                                                             double* __restrict__ partials, int count) {
+    const size_t i = (size_t)blockIdx.x * kWave + threadIdx.x;
+    const bool live = i < (n >> 1);
+    d2 av = {0.0, 0.0}, rv = {0.0, 0.0}, dv = {1.0, 1.0};
+    if (live) {  // the loads before the scalars (cg_update_r_kernel has the why)
+        av = load_once(Ap, i);
+        rv = load_once(r, i);
+        if (kJac) dv = load_once(dinv, i);
+    }
+    const bool update = s->skip_update == 0;
+    const double alpha = s->alpha;
+    double rr = 0.0, rz = 0.0;
+    if (live) {
+        if (update) {
+            rv.x = fma(-alpha, av.x, rv.x);
+            rv.y = fma(-alpha, av.y, rv.y);
+            store_once(r, i, rv);
+        }
+        const double zx = kJac ? dv.x * rv.x : rv.x, zy = kJac ? dv.y * rv.y : rv.y;
+        rr = fma(rv.x, rv.x, rr), rr = fma(rv.y, rv.y, rr);
+        rz = fma(rv.x, zx, rz), rz = fma(rv.y, zy, rz);
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        double rl = r[n - 1];
+        if (update) r[n - 1] = rl = fma(-alpha, Ap[n - 1], rl);
+        const double zl = kJac ? dinv[n - 1] * rl : rl;
+        rr = fma(rl, rl, rr), rz = fma(rl, zl, rz);
+    }
+    rr = wave_sum(rr), rz = wave_sum(rz);
+    if (threadIdx.x == 0) partials[blockIdx.x] = rr, partials[count + blockIdx.x] = rz;
+}
+
+// x = fma(alpha, p, x) ; p = fma(beta, p, dinv r) unless the iteration stopped. Scalars first: nothing is read when the
+// iteration's pAp broke down, and r / dinv are not read in the converging iteration.
+template <bool kJac>
+__global__ __launch_bounds__(kWave) void pcg_update_xp_kernel(size_t n, const PcgScalars* __restrict__ s, const double* __restrict__ r,
+                                                              const double* __restrict__ dinv, double* __restrict__ p, double* __restrict__ x) {
+    if (s->skip_update) return;
+    const bool direction = s->converged == 0 && s->breakdown == 0;
+    const double alpha = s->alpha, beta = s->beta;
+    const size_t i = (size_t)blockIdx.x * kWave + threadIdx.x;
+    if (i < (n >> 1)) {
+        d2 xv = load_once(x, i), pv = load_once(p, i);
+        xv.x = fma(alpha, pv.x, xv.x);
+        xv.y = fma(alpha, pv.y, xv.y);
+        store_once(x, i, xv);
+        if (direction) {
+            d2 zv = load_once(r, i);
+            if (kJac) {
+                const d2 dv = load_once(dinv, i);
+                zv.x = dv.x * zv.x, zv.y = dv.y * zv.y;
+            }
+            pv.x = fma(beta, pv.x, zv.x);
+            pv.y = fma(beta, pv.y, zv.y);
+            reinterpret_cast<d2*>(p)[i] = pv;  // plain: the next SpMV's neighbour loads re-use these lines
+        }
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const double pl = p[n - 1];
+        x[n - 1] = fma(alpha, pl, x[n - 1]);
+        if (direction) p[n - 1] = fma(beta, pl, kJac ? dinv[n - 1] * r[n - 1] : r[n - 1]);
+    }
+}
+
+// p.Ap partials for an operator without a fused launch (after its run_device)
+__global__ __launch_bounds__(kWave) void pcg_dot_kernel(size_t n, const double* __restrict__ a, const double* __restrict__ b,
+                                                        double* __restrict__ partials) {
+    const size_t i = (size_t)blockIdx.x * kWave + threadIdx.x;
+    double acc = 0.0;
+    if (i < (n >> 1)) {
+        const d2 av = load_once(a, i), bv = load_once(b, i);
+        acc = fma(av.x, bv.x, acc), acc = fma(av.y, bv.y, acc);
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) acc = fma(a[n - 1], b[n - 1], acc);
+    acc = wave_sum(acc);
+    if (threadIdx.x == 0) partials[blockIdx.x] = acc;
+}
+
+// ---- reductions: NV sums of `count` partials each (value v at partials[v * count ...]) in ONE launch, then the scalar step ----
+// The shape of reduce_device.hpp extended to two values: slice workgroups publish their slice sums of value 0 into the stage's
+// `sums`, of value 1 into its `extra` slots; the workgroup that draws the last ticket sums both and takes the step. One
+// workgroup (no stage) when there are at most 1024 partials. which: 0 = initial r.r / r.z, 1 = pAp, 2 = r.r / r.z'.
+
+__device__ void pcg_step(PcgScalars* s, int which, const double* total, double tol, double* hist, int hist_cap) {
+    if (which == 0) {
+        s->b_norm = sqrt(total[0]);
+        s->residual = s->b_norm;
+        s->rz = total[1];
+        s->pAp = s->alpha = s->beta = 0.0;
+        s->iterations = s->converged = s->breakdown = s->skip_update = 0;
+        if (hist_cap > 0) hist[0] = s->b_norm;
+    } else if (which == 1) {
+        s->pAp = total[0];
+        if (usable(s->pAp)) {
+            s->alpha = s->rz / s->pAp;
+        } else {
+            s->alpha = 0.0;
+            s->skip_update = 1;
+        }
+    } else {
+        const double res = sqrt(total[0]);
+        s->iterations += 1;
+        s->residual = res;
+        if (s->iterations < hist_cap) hist[s->iterations] = res;
+        if (s->skip_update) {
+            s->breakdown = 1;
+        } else if (res / s->b_norm < tol) {
+            s->converged = 1;
+        } else if (!usable(total[1])) {
+            s->breakdown = 1;
+        } else {
+            s->beta = total[1] / s->rz;
+            s->rz = total[1];
+        }
+    }
+}
+
+template <int NV>
+__global__ __launch_bounds__(kReduceBlock) void pcg_reduce_kernel(const double* __restrict__ partials, int count, int slice, int blocks,
+                                                                  double* stage_base, PcgScalars* s, int which, double tol, double* hist,
+                                                                  int hist_cap) {
+    __shared__ double sh[kReduceBlock];
+    __shared__ int s_last;
+    double total[2] = {0.0, 0.0};
+    if (blocks > 1) {
+        const ReduceStage stage = reduce_stage_of(stage_base);
+        unsigned long long* const slot[2] = {stage.sums, stage.extra};
+        const int lo = (int)blockIdx.x * slice, hi = min(lo + slice, count);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            block_tree(strided_sum(partials + (long long)v * count, lo, hi), sh);
+            if (threadIdx.x == 0) publish(slot[v] + blockIdx.x, sh[0]);
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            const unsigned drawn = __hip_atomic_fetch_add(stage.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            s_last = drawn == (unsigned)(blocks - 1) ? 1 : 0;
+            if (s_last) __hip_atomic_store(stage.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();
+        if (s_last == 0) return;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            double acc = 0.0;
+            for (int i = (int)threadIdx.x; i < blocks; i += kReduceBlock) acc += published(slot[v] + i);
+            block_tree(acc, sh);
+            total[v] = sh[0];
+            __syncthreads();
+        }
+    } else {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            block_tree(strided_sum(partials + (long long)v * count, 0, count), sh);
+            total[v] = sh[0];
+            __syncthreads();
+        }
+    }
+    if (threadIdx.x == 0) pcg_step(s, which, total, tol, hist, hist_cap);
+}
+
+// ---- workspace: kept between calls (like cg_solve_device's), released with it ----
+struct PcgWorkspace {
+    int n = 0, device = -1;
+    double *x = nullptr, *b = nullptr, *r = nullptr, *p = nullptr, *Ap = nullptr;
+    double* partials = nullptr;  // max(the fused SpMV's slots, 2 x streaming workgroups)
+    double* stage = nullptr;     // reduce_scratch_alloc()
+    PcgScalars* s = nullptr;
+    double* hist = nullptr;
+    int hist_cap = 0;
+    long long partial_cap = 0;
+    void release() {
+        device_release(x);
+        device_release(b);
+        device_release(r);
+        device_release(p);
+        device_release(Ap);
+        device_release(partials);
+        device_release(stage);
+        device_release(s);
+        device_release(hist);
+        n = 0, device = -1, hist_cap = 0, partial_cap = 0;
+    }
+};
+PcgWorkspace g_pcg;
+std::vector<double> g_pcg_history;  // of the last preconditioned solve
+
+bool fail(const char* what) {
+    fprintf(stderr, "[PCG] %s\n", what);
+    return false;
+}
+
+bool ensure_workspace(int n, int device, long long partial_cap, int hist_cap) {
+    PcgWorkspace& w = g_pcg;
+    if (w.x != nullptr && (w.n != n || w.device != device || w.partial_cap < partial_cap)) w.release();
+    if (w.x == nullptr) {
+        const size_t need = 5 * (size_t)n * sizeof(double) + (size_t)partial_cap * sizeof(double) + (size_t)hist_cap * sizeof(double) +
+                            ((size_t)64 << 20);
+        size_t free_b = 0, total_b = 0;
+        HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+        if (need > free_b) {
+            fprintf(stderr, "[PCG] the workspace for %d rows needs %.2f GB, the device has %.2f GB free: refused\n", n, need / 1e9,
+                    free_b / 1e9);
+            return false;
+        }
+        w.x = device_try_alloc<double>((size_t)n);
+        w.b = device_try_alloc<double>((size_t)n);
+        w.r = device_try_alloc<double>((size_t)n);
+        w.p = device_try_alloc<double>((size_t)n);
+        w.Ap = device_try_alloc<double>((size_t)n);
+        w.partials = device_try_alloc<double>((size_t)partial_cap);
+        w.s = device_try_alloc<PcgScalars>(1);
+        if (!w.x || !w.b || !w.r || !w.p || !w.Ap || !w.partials || !w.s) {
+            w.release();
+            return fail("the workspace could not be allocated: refused");
+        }
+        w.stage = reduce_scratch_alloc();
+        w.n = n, w.device = device, w.partial_cap = partial_cap;
+    }
+    if (w.hist_cap < hist_cap) {
+        device_release(w.hist);
+        w.hist_cap = 0;
+        w.hist = device_try_alloc<double>((size_t)hist_cap);
+        if (w.hist == nullptr) return fail("the history could not be allocated: refused");
+        w.hist_cap = hist_cap;
+    }
+    return true;
+}
+
+int kind_of(const char* kind) {
+    if (kind == nullptr) return -1;
+    if (!strcmp(kind, "none")) return kNone;
+    if (!strcmp(kind, "jacobi")) return kJacobi;
+    return -1;
+}
+
+// The validity pass over a diagonal source; returns the preconditioner or null (*bad_row set when a row is at fault).
+SpmvAmdPrecond* make_jacobi(int src, const SlabCsr& m, const int* idx, const double* val, int width, int n, int* bad_row) {
+    double* dinv = device_try_alloc<double>((size_t)n);
+    int* d_bad = device_try_alloc<int>(1);
+    if (dinv == nullptr || d_bad == nullptr) {
+        device_release(dinv);
+        device_release(d_bad);
+        fail("no device memory for the inverse diagonal");
+        return nullptr;
+    }
+    const int none = INT_MAX;
+    upload(d_bad, &none, 1);
+    hipLaunchKernelGGL(diagonal_inverse_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, kStream, src, m, idx, val, width, n, dinv, d_bad);
+    HIP_CHECK(hipGetLastError());
+    int bad = none;
+    download(&bad, d_bad, 1);  // synchronises
+    device_release(d_bad);
+    if (bad != none) {
+        device_release(dinv);
+        if (bad_row != nullptr) *bad_row = bad;
+        fprintf(stderr, "[PCG] jacobi: the diagonal entry of row %d is zero, not finite or of the other sign than row 0's: refused\n", bad);
+        return nullptr;
+    }
+    SpmvAmdPrecond* pm = new SpmvAmdPrecond();
+    pm->kind = kJacobi;
+    pm->n = n;
+    pm->dinv = dinv;
+    return pm;
+}
+
+void solution_checksums(const double* x, int n, double* sum, double* norm) {
+    double s = 0.0, q = 0.0;
+    for (int i = 0; i < n; i++) {
+        s += x[i];
+        q += x[i] * x[i];
+    }
+    *sum = s;
+    *norm = sqrt(q);
+}
+
+}  // namespace
+
+namespace spmv_amd {
+void release_pcg_workspace_locked() { g_pcg.release(); }
+}  // namespace spmv_amd
+
+extern "C" SpmvAmdPrecond* spmv_amd_precond_create(SpmvOperator* op, const char* kind, int* bad_row) {
+    if (bad_row != nullptr) *bad_row = -1;
+    const int k = kind_of(kind);
+    if (k < 0) {
+        fprintf(stderr, "[PCG] unknown preconditioner kind '%s' (none, jacobi)\n", kind ? kind : "(null)");
+        return nullptr;
+    }
+    if (op == nullptr) return fail("null operator"), nullptr;
+    const DiagonalSource d = diagonal_source_of(op);
+    if (d.owner == nullptr) {
+        fprintf(stderr, "[PCG] operator '%s' is not one of this library's: pass its diagonal to spmv_amd_precond_create_from_diagonal\n",
+                op->name ? op->name : "?");
+        return nullptr;
+    }
+    if (!d.ready) {
+        fprintf(stderr, "[PCG] operator '%s' used before init\n", op->name);
+        return nullptr;
+    }
+    if (d.rows != d.cols) {
+        fprintf(stderr, "[PCG] operator '%s' holds a %d x %d matrix: a square one is required\n", op->name, d.rows, d.cols);
+        return nullptr;
+    }
+    SpmvAmdPrecond* pm = nullptr;
+    if (k == kNone) {
+        pm = new SpmvAmdPrecond();
+        pm->kind = kNone;
+        pm->n = d.rows;
+    } else {
+        pm = make_jacobi(d.kind == DiagonalSource::Csr ? 0 : 1, d.csr, d.idx, d.val, d.width, d.rows, bad_row);
+        if (pm == nullptr) return nullptr;
+    }
+    pm->owner = d.owner;
+    pm->generation = d.generation;
+    return pm;
+}
+
+extern "C" SpmvAmdPrecond* spmv_amd_precond_create_from_diagonal(const double* d_diag, int n, int* bad_row) {
+    if (bad_row != nullptr) *bad_row = -1;
+    if (d_diag == nullptr) return fail("null diagonal"), nullptr;
+    if (n < 1) return fail("n < 1"), nullptr;
+    return make_jacobi(2, SlabCsr{}, nullptr, d_diag, 0, n, bad_row);
+}
+
+extern "C" void spmv_amd_precond_destroy(SpmvAmdPrecond* m) {
+    if (m == nullptr) return;
+    device_release(m->dinv);
+    delete m;
+}
+
+extern "C" const char* spmv_amd_precond_kind(const SpmvAmdPrecond* m) {
+    if (m == nullptr) return "invalid";
+    return m->kind == kJacobi ? "jacobi" : "none";
+}
+
+extern "C" int spmv_amd_precond_inverse_diagonal(const SpmvAmdPrecond* m, double* out, int n) {
+    if (m == nullptr || out == nullptr) return fail("null argument"), 1;
+    if (m->kind != kJacobi) return fail("kind 'none' has no inverse diagonal"), 1;
+    if (n != m->n) {
+        fprintf(stderr, "[PCG] the preconditioner has %d values, %d asked for\n", m->n, n);
+        return 1;
+    }
+    HIP_CHECK(hipStreamSynchronize(kStream));
+    download(out, m->dinv, (size_t)n);
+    return 0;
+}
+
+extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, const double* b, double* x,
+                                         const CGConfig* config, CGStats* stats) {
+    // argument checks: all before the first HIP call
+    if (op == nullptr || mat == nullptr || m == nullptr || b == nullptr || x == nullptr || config == nullptr || stats == nullptr)
+        return fail("null argument"), 1;
+    if (op->run_device == nullptr) {
+        fprintf(stderr, "[PCG] operator '%s' does not support the device-native interface\n", op->name ? op->name : "?");
+        return 1;
+    }
+    if (config->max_iters < 0) return fail("max_iters < 0"), 1;
+    const DiagonalSource d = diagonal_source_of(op);
+    if (d.owner != nullptr) {
+        if (!d.ready) {
+            fprintf(stderr, "[PCG] operator '%s' used before init\n", op->name);
+            return 1;
+        }
+        if (d.rows != d.cols || mat->rows != d.rows) {
+            fprintf(stderr, "[PCG] the operator holds a %d x %d matrix, mat->rows = %d: a square system of that size is required\n", d.rows,
+                    d.cols, mat->rows);
+            return 1;
+        }
+    }
+    if (mat->rows < 1) return fail("mat->rows < 1"), 1;
+    if (m->n != mat->rows) {
+        fprintf(stderr, "[PCG] the preconditioner is for %d rows, mat->rows = %d\n", m->n, mat->rows);
+        return 1;
+    }
+    if (m->owner != nullptr && m->owner != d.owner) return fail("the preconditioner was made from another operator: refused"), 1;
+    if (m->owner != nullptr && m->generation != d.generation)
+        return fail("the preconditioner was made before the operator was last initialised or freed: refused"), 1;
+    const int n = mat->rows;
+    const CGConfig cfg = *config;
+    const bool jac = m->kind == kJacobi;
+
+    CgWorkspaceScope scope;
+    int device = 0;
+    HIP_CHECK(hipGetDevice(&device));
+    const FusedSpmv f = fused_spmv_of(op);
+    const bool fused = f.launch != nullptr && f.partials > 0;
+    const int vec_count = (int)stream_blocks((size_t)n);
+    const long long partial_cap = 2LL * vec_count > f.partials ? 2LL * vec_count : (long long)f.partials;
+    if (!ensure_workspace(n, device, partial_cap, cfg.max_iters + 1)) return 1;
+    PcgWorkspace& w = g_pcg;
+    upload(w.b, b, (size_t)n);
+    upload(w.x, x, (size_t)n);
+
+    const dim3 grid(stream_blocks((size_t)n)), block(kWave);
+    const bool detail = cfg.enable_detailed_timers != 0;
+    EventTimer total, part;
+    double t_spmv = 0.0, t_blas = 0.0, t_red = 0.0;
+    bool op_failed = false;
+    auto stage = [&](double* acc, auto&& launch) {
+        if (detail) part.begin(kStream);
+        launch();
+        if (detail) {
+            part.end(kStream);
+            *acc += part.elapsed_ms();
+        }
+    };
+    auto reduce = [&](int count, int nv, int which) {
+        int slice = 0, blocks = 0;
+        reduce_geometry(count, &slice, &blocks);
+        if (nv == 1)
+            hipLaunchKernelGGL(pcg_reduce_kernel<1>, dim3((unsigned)blocks), dim3(kReduceBlock), 0, kStream, w.partials, count, slice, blocks,
+                               w.stage, w.s, which, cfg.tolerance, w.hist, w.hist_cap);
+        else
+            hipLaunchKernelGGL(pcg_reduce_kernel<2>, dim3((unsigned)blocks), dim3(kReduceBlock), 0, kStream, w.partials, count, slice, blocks,
+                               w.stage, w.s, which, cfg.tolerance, w.hist, w.hist_cap);
+    };
+    auto run_op = [&](const double* in, double* out) {
+        if (op->run_device(in, out) != 0) {
+            fprintf(stderr, "[PCG] operator '%s': run_device failed\n", op->name);
+            op_failed = true;
+        }
+    };
+    PcgScalars h{};
+
+    total.begin(kStream);
+    stage(&t_spmv, [&] { run_op(w.x, w.Ap); });
+    if (jac)
+        stage(&t_blas, [&] { hipLaunchKernelGGL(pcg_init_kernel<true>, grid, block, 0, kStream, (size_t)n, w.b, w.Ap, m->dinv, w.r, w.p, w.partials, vec_count); });
+    else
+        stage(&t_blas, [&] { hipLaunchKernelGGL(pcg_init_kernel<false>, grid, block, 0, kStream, (size_t)n, w.b, w.Ap, nullptr, w.r, w.p, w.partials, vec_count); });
+    stage(&t_red, [&] { reduce(vec_count, 2, 0); });
+    download(&h, w.s, 1);
+    if (cfg.verbose >= 1) printf("[PCG-DEVICE] Initial residual: %e (preconditioner %s)\n", h.b_norm, jac ? "jacobi" : "none");
+    for (int it = 0; it < cfg.max_iters && !op_failed && !h.converged && !h.breakdown; ++it) {
+        int pap_count = vec_count;
+        stage(&t_spmv, [&] {
+            if (fused) {
+                pap_count = f.launch(w.p, w.Ap, w.partials, nullptr, false, nullptr, kStream);
+            } else {
+                run_op(w.p, w.Ap);
+                hipLaunchKernelGGL(pcg_dot_kernel, grid, block, 0, kStream, (size_t)n, w.p, w.Ap, w.partials);
+            }
+        });
+        if (op_failed) break;
+        stage(&t_red, [&] { reduce(pap_count, 1, 1); });
+        if (jac)
+            stage(&t_blas, [&] { hipLaunchKernelGGL(pcg_update_r_kernel<true>, grid, block, 0, kStream, (size_t)n, w.s, w.Ap, m->dinv, w.r, w.partials, vec_count); });
+        else
+            stage(&t_blas, [&] { hipLaunchKernelGGL(pcg_update_r_kernel<false>, grid, block, 0, kStream, (size_t)n, w.s, w.Ap, nullptr, w.r, w.partials, vec_count); });
+        stage(&t_red, [&] { reduce(vec_count, 2, 2); });
+        if (jac)
+            stage(&t_blas, [&] { hipLaunchKernelGGL(pcg_update_xp_kernel<true>, grid, block, 0, kStream, (size_t)n, w.s, w.r, m->dinv, w.p, w.x); });
+        else
+            stage(&t_blas, [&] { hipLaunchKernelGGL(pcg_update_xp_kernel<false>, grid, block, 0, kStream, (size_t)n, w.s, w.r, nullptr, w.p, w.x); });
+        download(&h, w.s, 1);  // synchronises: the stopping test
+        if (cfg.verbose >= 2)
+            printf("[PCG-DEVICE] Iter %3d: residual = %e (rel = %e)\n", h.iterations, h.residual, h.residual / h.b_norm);
+    }
+    total.end(kStream);
+    const double total_ms = total.elapsed_ms();
+    HIP_CHECK(hipGetLastError());
+    download(x, w.x, (size_t)n);
+    const int count = h.iterations + 1 < w.hist_cap ? h.iterations + 1 : w.hist_cap;
+    g_pcg_history.assign((size_t)count, 0.0);
+    download(g_pcg_history.data(), w.hist, (size_t)count);
+    if (op_failed) return 1;
+
+    stats->iterations = h.iterations;
+    // not converged: ||r0|| unless verbose >= 2 copied the last residual back (cg_solve_device's rule)
+    stats->residual_norm = h.converged ? h.residual : (cfg.verbose >= 2 && h.iterations > 0 ? h.residual : h.b_norm);
+    stats->converged = (h.b_norm > 0.0 && stats->residual_norm / h.b_norm < cfg.tolerance) ? 1 : 0;
+    stats->time_total_ms = total_ms;
+    stats->time_spmv_ms = t_spmv;
+    stats->time_blas1_ms = t_blas;
+    stats->time_reductions_ms = t_red;
+    solution_checksums(x, n, &stats->solution_sum, &stats->solution_norm);
+    if (cfg.verbose >= 1) {
+        if (h.breakdown) printf("[PCG-DEVICE] Breakdown in iteration %d (pAp or r.z zero or not finite)\n", h.iterations);
+        printf("[PCG-DEVICE] Converged: %s\n", stats->converged ? "YES" : "NO");
+        printf("[PCG-DEVICE] Iterations: %d\n", stats->iterations);
+        printf("[PCG-DEVICE] Final residual: %e\n", stats->residual_norm);
+        printf("[PCG-DEVICE] Time breakdown:\n");
+        printf("     Total:      %.3f ms\n", stats->time_total_ms);
+        printf("     SpMV:       %.3f ms\n", stats->time_spmv_ms);
+        printf("     BLAS1:      %.3f ms\n", stats->time_blas1_ms);
+        printf("     Reductions: %.3f ms\n", stats->time_reductions_ms);
+    }
+    return 0;
+}
+
+extern "C" int spmv_amd_pcg_last_history(double* out, int cap) {
+    const int count = (int)g_pcg_history.size();
+    for (int i = 0; i < count && i < cap && out != nullptr; ++i) out[i] = g_pcg_history[(size_t)i];
+    return count;
+}
+
+extern "C" void spmv_amd_pcg_release_workspace(void) { spmv_amd::release_cg_workspace(); }

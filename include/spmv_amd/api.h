@@ -282,6 +282,41 @@ int spmv_amd_cg_last_history_multi(int rhs, double* out, int cap);
  * spmv_amd_cg_release_workspace()) or before the first batched solve. No HIP call. */
 size_t spmv_amd_cg_multi_workspace_bytes(void);
 
+/* ---- preconditioned CG (csrc/pcg.hip) ----
+ * z = M^-1 r with M = diag(A) ("jacobi") or I ("none"); otherwise the algebra, stopping rule (true residual, strict <, the
+ * converging iteration counted), statistics, timer rule and verbose semantics of cg_solve_device (verbose lines tagged
+ * [PCG-DEVICE]). A pAp or r.z that is zero or not finite stops the solve in that iteration with converged = 0 and x finite;
+ * there is no sign test, so negative-definite systems solve. Results are deterministic: the same solve twice gives bit-identical
+ * x and history. Every entry point checks its arguments before any HIP call and returns NULL / non-zero with a message on
+ * stderr. */
+typedef struct SpmvAmdPrecond SpmvAmdPrecond;
+/* A preconditioner for an initialised, square operator of this library ("stencil5-csr", "cusparse-csr", "ellpack",
+ * "stencil5-ellpack"). kind "none" | "jacobi". Jacobi reads the operator's own device storage: d_i = the sum of row i's
+ * entries in column i (CSR order, from 0.0), dinv_i = 1.0 / d_i -- the same bits from every operator for the same matrix.
+ * Every d_i must be finite, non-zero and of d_0's sign. NULL on refusal; *bad_row (may be NULL) = the first offending row,
+ * or -1 when the refusal is not about a row. The preconditioner belongs to the operator's current matrix: after the operator's
+ * free() or next init it is refused by spmv_amd_pcg_solve_device. */
+SpmvAmdPrecond* spmv_amd_precond_create(SpmvOperator* op, const char* kind, int* bad_row);
+/* Jacobi from a caller's device diagonal of n values (the same validity rule): the way in for operators this library does
+ * not own. Usable with any operator of n rows. */
+SpmvAmdPrecond* spmv_amd_precond_create_from_diagonal(const double* d_diag, int n, int* bad_row);
+void spmv_amd_precond_destroy(SpmvAmdPrecond* m);
+/* "none", "jacobi"; "invalid" for NULL. */
+const char* spmv_amd_precond_kind(const SpmvAmdPrecond* m);
+/* Host copy of dinv (n must be the preconditioner's size); non-zero for kind "none". */
+int spmv_amd_precond_inverse_diagonal(const SpmvAmdPrecond* m, double* out, int n);
+/* Preconditioned CG on the device. b, x: host arrays of mat->rows values, x in = x0, out = solution (uploaded before and
+ * downloaded after the timed region). Refused: NULL pointers, an uninitialised or non-square operator, n != mat->rows, a
+ * preconditioner made from another operator or from an earlier init of this one. The workspace (x, b, r, p, Ap) is sized
+ * against the device's free memory first, kept between calls and released with cg_solve_device's (an operator's free(),
+ * spmv_amd_cg_release_workspace(), spmv_amd_pcg_release_workspace()). */
+int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, const double* b, double* x,
+                              const CGConfig* config, CGStats* stats);
+/* ||r_k||, k = 0..iterations, of the last preconditioned solve (spmv_amd_cg_last_history is not touched by one). */
+int spmv_amd_pcg_last_history(double* out, int cap);
+/* Releases the solver workspaces: the same as spmv_amd_cg_release_workspace(). Safe to call at any time. */
+void spmv_amd_pcg_release_workspace(void);
+
 /* ---- multi-GPU communicator ---- */
 typedef struct SpmvAmdComm SpmvAmdComm;
 
