@@ -24,20 +24,13 @@
 
 #include "reduce_device.hpp"
 #include "spmv_amd/hip_check.h"
+#include "stream_device.hpp"
 
 namespace spmv_amd {
 namespace {
 
 constexpr int kBlock = kReduceBlock;  // the reduction kernels (reduce_device.hpp)
 constexpr int kStream = 64;           // the streaming kernels: one wavefront per workgroup
-
-typedef double d2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
 
 // Runs the body for this thread's pair (2i, 2i+1) with 16-byte accesses; the odd tail element is
 // handled by thread 0 of block 0 in each kernel.
@@ -50,14 +43,6 @@ __device__ __forceinline__ double wave_sum(double v) {
 __device__ __forceinline__ void block_partial(double acc, double* __restrict__ partials) {
     acc = wave_sum(acc);
     if (threadIdx.x == 0) partials[blockIdx.x] = acc;
-}
-
-// 16-byte accesses of streams that are read / written once per pass
-__device__ __forceinline__ d2 load_once(const double* __restrict__ base, size_t pair) {
-    return __builtin_nontemporal_load(reinterpret_cast<const d2*>(base) + pair);
-}
-__device__ __forceinline__ void store_once(double* __restrict__ base, size_t pair, d2 v) {
-    __builtin_nontemporal_store(v, reinterpret_cast<d2*>(base) + pair);
 }
 
 __global__ __launch_bounds__(kStream) void fill_kernel(double* __restrict__ d, size_t n, double value) {
@@ -474,12 +459,12 @@ __global__ __launch_bounds__(kStream) void cg_flush_x_kernel(size_t n, const dou
     }
 }
 
-inline unsigned stream_grid(size_t n) {
+}  // namespace
+
+unsigned stream_grid(size_t n) {
     const size_t want = ((n >> 1) + kStream - 1) / kStream;
     return (unsigned)(want < 1 ? 1 : want);
 }
-
-}  // namespace
 
 void launch_fill(double* d, size_t n, double value, hipStream_t stream) {
     if (n == 0) return;
@@ -514,11 +499,15 @@ void launch_update_p_dev(size_t n, const double* r, const double* d_b, double* p
 size_t dot_scratch_doubles(size_t n) { return (size_t)stream_grid(n) + (size_t)reduce_scratch_doubles(); }
 int cg_partial_count(size_t n) { return (int)stream_grid(n); }
 
+void launch_dot_partials(size_t n, const double* x, const double* y, double* partials, hipStream_t stream) {
+    hipLaunchKernelGGL(dot_partials_kernel, dim3(stream_grid(n)), dim3(kStream), 0, stream, n, x, y, partials);
+}
+
 void launch_dot(size_t n, const double* x, const double* y, double* scratch, double* d_result,
                 hipStream_t stream) {
     // scratch = [one partial per block | the reduction's own scratch]
     const unsigned blocks = stream_grid(n);
-    hipLaunchKernelGGL(dot_partials_kernel, dim3(blocks), dim3(kStream), 0, stream, n, x, y, scratch);
+    launch_dot_partials(n, x, y, scratch, stream);
     launch_reduce_partials(scratch, (int)blocks, d_result, nullptr, stream, ReduceScratch{scratch + blocks});
 }
 

@@ -21,23 +21,24 @@
 
 #include "device_runtime.hpp"
 #include "multi_rhs.hpp"
+#include "reduce_device.hpp"
+#include "solve_common.hpp"
+#include "stream_device.hpp"
 
 using namespace spmv_amd;
 
 namespace {
 
 constexpr hipStream_t kStream = nullptr;  // default stream, shared with the operators
-constexpr int kBlock = 256;
+constexpr int kBlock = kReduceBlock;  // 256: the vector kernels' workgroup and the width of block_tree (reduce_device.hpp)
 constexpr int kSlice = kBlock * 16;  // partials one workgroup of the first reduction stage sums
-
-typedef double dbl2 __attribute__((ext_vector_type(2)));
 
 template <int K>
 __device__ __forceinline__ void load_row(const double* __restrict__ p, double (&o)[K]) {
     if constexpr (K % 2 == 0) {  // workspace vectors: hipMalloc'd, rows of 8k bytes
 #pragma unroll
         for (int i = 0; i < K / 2; ++i) {
-            const dbl2 t = reinterpret_cast<const dbl2*>(p)[i];
+            const d2 t = reinterpret_cast<const d2*>(p)[i];
             o[2 * i] = t.x, o[2 * i + 1] = t.y;
         }
     } else {
@@ -51,9 +52,9 @@ __device__ __forceinline__ void store_row(double* __restrict__ p, const double (
     if constexpr (K % 2 == 0) {
 #pragma unroll
         for (int i = 0; i < K / 2; ++i) {
-            dbl2 t;
+            d2 t;
             t.x = v[2 * i], t.y = v[2 * i + 1];
-            reinterpret_cast<dbl2*>(p)[i] = t;
+            reinterpret_cast<d2*>(p)[i] = t;
         }
     } else {
 #pragma unroll
@@ -190,18 +191,6 @@ __global__ __launch_bounds__(kBlock) void multi_update_xp_kernel(long long n, co
     }
 }
 
-// Fixed-shape sum of 256 values in shared memory (every thread calls it); returns the sum in thread 0.
-__device__ __forceinline__ double block_tree(double v, double* s) {
-    s[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int w = kBlock / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-        __syncthreads();
-    }
-    return s[0];
-}
-
 // Stage 1: workgroup (s, j) sums partials[j * count + s * kSlice ...] (each thread its strided share in ascending order, then
 // a fixed tree) into slices[j * slice_count + s].
 __global__ __launch_bounds__(kBlock) void multi_reduce_slices_kernel(const double* __restrict__ partials, long long count, int slice_count,
@@ -212,8 +201,8 @@ __global__ __launch_bounds__(kBlock) void multi_reduce_slices_kernel(const doubl
     const long long lo = (long long)sl * kSlice, hi = lo + kSlice < count ? lo + kSlice : count;
     double acc = 0.0;
     for (long long i = lo + threadIdx.x; i < hi; i += kBlock) acc += src[i];
-    const double t = block_tree(acc, s);
-    if (threadIdx.x == 0) slices[(long long)j * slice_count + sl] = t;
+    block_tree(acc, s);
+    if (threadIdx.x == 0) slices[(long long)j * slice_count + sl] = s[0];
 }
 
 // Stage 2 + the scalar step of column j (workgroup j). which: 0 = initial residual, 1 = pAp, 2 = r.r.
@@ -223,8 +212,9 @@ __global__ __launch_bounds__(kBlock) void multi_reduce_step_kernel(const double*
     const int j = (int)blockIdx.x;
     double acc = 0.0;
     for (int i = (int)threadIdx.x; i < slice_count; i += kBlock) acc += slices[(long long)j * slice_count + i];
-    const double total = block_tree(acc, s);
+    block_tree(acc, s);
     if (threadIdx.x != 0) return;
+    const double total = s[0];
     MultiColumn& c = cols[j];
     double* h = hist + (long long)j * hist_cap;
     if (which == 0) {
@@ -309,8 +299,7 @@ bool fail(const char* what) {
     return false;
 }
 
-// Allocates the workspace for (n, k, partial slots) if it is not there already. Sized against hipMemGetInfo first: a request
-// that does not fit is refused with a message, never a crash.
+// Allocates the workspace for (n, k, partial slots) if it is not there already (sized against the free memory first).
 bool ensure_workspace(int n, int k, int device, long long partial_cap, int hist_cap) {
     MultiWorkspace& w = g_multi;
     if (w.X != nullptr && (w.n != n || w.k != k || w.device != device || w.partial_cap < partial_cap)) w.release();
@@ -318,13 +307,9 @@ bool ensure_workspace(int n, int k, int device, long long partial_cap, int hist_
         const size_t vec = (size_t)n * k * sizeof(double);
         const size_t need = 4 * vec + (size_t)k * partial_cap * sizeof(double) + (size_t)k * slices_for(partial_cap) * sizeof(double) +
                             (size_t)k * hist_cap * sizeof(double) + ((size_t)64 << 20);
-        size_t free_b = 0, total_b = 0;
-        HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-        if (need > free_b) {
-            fprintf(stderr, "[CG-MULTI] the workspace for %d systems of %d rows needs %.2f GB, the device has %.2f GB free: refused\n", k, n,
-                    need / 1e9, free_b / 1e9);
-            return false;
-        }
+        char what[48];
+        snprintf(what, sizeof what, "%d systems of %d rows", k, n);
+        if (!device_has_room(need, "CG-MULTI", what)) return false;
         w.X = device_try_alloc<double>((size_t)n * k);
         w.R = device_try_alloc<double>((size_t)n * k);
         w.P = device_try_alloc<double>((size_t)n * k);
@@ -338,24 +323,8 @@ bool ensure_workspace(int n, int k, int device, long long partial_cap, int hist_
         }
         w.n = n, w.k = k, w.device = device, w.partial_cap = partial_cap;
     }
-    if (w.hist_cap < hist_cap) {
-        device_release(w.hist);
-        w.hist_cap = 0;
-        w.hist = device_try_alloc<double>((size_t)k * hist_cap);
-        if (w.hist == nullptr) return fail("the history could not be allocated: refused");
-        w.hist_cap = hist_cap;
-    }
+    if (!grow_history(w.hist, w.hist_cap, hist_cap, (size_t)k)) return fail("the history could not be allocated: refused");
     return true;
-}
-
-void column_checksums(const double* x, int n, double* sum, double* norm) {
-    double s = 0.0, q = 0.0;
-    for (int i = 0; i < n; i++) {
-        s += x[i];
-        q += x[i] * x[i];
-    }
-    *sum = s;
-    *norm = sqrt(q);
 }
 
 bool check_rhs(int nrhs) {
@@ -485,17 +454,7 @@ extern "C" int spmv_amd_cg_solve_device_multi(SpmvOperator* op, MatrixData* mat,
     HIP_CHECK(hipStreamSynchronize(kStream));
 
     std::vector<MultiColumn> h_cols((size_t)k);
-    const bool detail = cfg.enable_detailed_timers != 0;
-    EventTimer total, part;
-    double t_spmv = 0.0, t_blas = 0.0, t_red = 0.0;
-    auto stage = [&](double* acc, auto&& launch) {
-        if (detail) part.begin(kStream);
-        launch();
-        if (detail) {
-            part.end(kStream);
-            *acc += part.elapsed_ms();
-        }
-    };
+    StageTimers T(cfg.enable_detailed_timers != 0, kStream);
     auto reduce = [&](long long count, int which) {
         const int sc = slices_for(count);
         hipLaunchKernelGGL(multi_reduce_slices_kernel, dim3((unsigned)sc, (unsigned)k), dim3(kBlock), 0, kStream, w.partials, count, sc,
@@ -505,10 +464,10 @@ extern "C" int spmv_amd_cg_solve_device_multi(SpmvOperator* op, MatrixData* mat,
     };
     auto read_columns = [&] { download(h_cols.data(), w.cols, (size_t)k); };
 
-    total.begin(kStream);
-    stage(&t_spmv, [&] { launch_spmm(o.plan, k, w.X, w.AP, nullptr, kStream); });
-    stage(&t_blas, [&] { launch_vector_step(k, 0, n, w.cols, w.X, w.R, w.P, w.AP, w.partials, vec_count); });
-    stage(&t_red, [&] { reduce(vec_count, 0); });
+    T.total.begin(kStream);
+    T.run(&T.t_spmv, [&] { launch_spmm(o.plan, k, w.X, w.AP, nullptr, kStream); });
+    T.run(&T.t_blas, [&] { launch_vector_step(k, 0, n, w.cols, w.X, w.R, w.P, w.AP, w.partials, vec_count); });
+    T.run(&T.t_red, [&] { reduce(vec_count, 0); });
     read_columns();
     if (cfg.verbose >= 1)
         for (int j = 0; j < k; ++j) printf("[CG-MULTI %d] Initial residual: %e\n", j, h_cols[j].b_norm);
@@ -516,11 +475,11 @@ extern "C" int spmv_amd_cg_solve_device_multi(SpmvOperator* op, MatrixData* mat,
         bool any = false;
         for (int j = 0; j < k; ++j) any = any || !h_cols[j].done;
         if (!any) break;
-        stage(&t_spmv, [&] { launch_spmm(o.plan, k, w.P, w.AP, w.partials, kStream); });
-        stage(&t_red, [&] { reduce(spmm_count, 1); });
-        stage(&t_blas, [&] { launch_vector_step(k, 1, n, w.cols, w.X, w.R, w.P, w.AP, w.partials, vec_count); });
-        stage(&t_red, [&] { reduce(vec_count, 2); });
-        stage(&t_blas, [&] { launch_vector_step(k, 2, n, w.cols, w.X, w.R, w.P, w.AP, w.partials, vec_count); });
+        T.run(&T.t_spmv, [&] { launch_spmm(o.plan, k, w.P, w.AP, w.partials, kStream); });
+        T.run(&T.t_red, [&] { reduce(spmm_count, 1); });
+        T.run(&T.t_blas, [&] { launch_vector_step(k, 1, n, w.cols, w.X, w.R, w.P, w.AP, w.partials, vec_count); });
+        T.run(&T.t_red, [&] { reduce(vec_count, 2); });
+        T.run(&T.t_blas, [&] { launch_vector_step(k, 2, n, w.cols, w.X, w.R, w.P, w.AP, w.partials, vec_count); });
         read_columns();  // synchronises: the stopping test of every column
         if (cfg.verbose >= 2)
             for (int j = 0; j < k; ++j)
@@ -528,8 +487,8 @@ extern "C" int spmv_amd_cg_solve_device_multi(SpmvOperator* op, MatrixData* mat,
                     printf("[CG-MULTI %d] Iter %3d: residual = %e (rel = %e)\n", j, h_cols[j].iterations, h_cols[j].residual,
                            h_cols[j].residual / h_cols[j].b_norm);
     }
-    total.end(kStream);
-    const double total_ms = total.elapsed_ms();
+    T.total.end(kStream);
+    const double total_ms = T.total.elapsed_ms();
     HIP_CHECK(hipGetLastError());
 
     // the solution back as k columns one after the other (outside the timed region, as the upload)
@@ -544,15 +503,8 @@ extern "C" int spmv_amd_cg_solve_device_multi(SpmvOperator* op, MatrixData* mat,
         g_multi_history[j].resize((size_t)count);
         download(g_multi_history[j].data(), w.hist + (size_t)j * w.hist_cap, (size_t)count);
         CGStats& st = stats[j];
-        st.iterations = c.iterations;
-        // not converged: ||r0|| unless verbose >= 2 copied the last residual back (cg_solve_device, reference :535, :601-619)
-        st.residual_norm = c.done ? c.residual : (cfg.verbose >= 2 && c.iterations > 0 ? c.residual : c.b_norm);
-        st.converged = (c.b_norm > 0.0 && st.residual_norm / c.b_norm < cfg.tolerance) ? 1 : 0;
-        st.time_total_ms = total_ms;
-        st.time_spmv_ms = t_spmv;
-        st.time_blas1_ms = t_blas;
-        st.time_reductions_ms = t_red;
-        column_checksums(X + (size_t)j * n, n, &st.solution_sum, &st.solution_norm);
+        fill_device_stats(&st, c.iterations, c.done != 0, c.residual, c.b_norm, cfg, total_ms, T.t_spmv, T.t_blas, T.t_red);
+        solution_checksums(X + (size_t)j * n, n, &st.solution_sum, &st.solution_norm);
         if (cfg.verbose >= 1) {
             printf("[CG-MULTI %d] Converged: %s\n", j, st.converged ? "YES" : "NO");
             printf("[CG-MULTI %d] Iterations: %d\n", j, st.iterations);
@@ -562,9 +514,9 @@ extern "C" int spmv_amd_cg_solve_device_multi(SpmvOperator* op, MatrixData* mat,
     if (cfg.verbose >= 1) {
         printf("[CG-MULTI] %d systems, time breakdown (whole batch):\n", k);
         printf("     Total:      %.3f ms\n", total_ms);
-        printf("     SpMV:       %.3f ms\n", t_spmv);
-        printf("     BLAS1:      %.3f ms\n", t_blas);
-        printf("     Reductions: %.3f ms\n", t_red);
+        printf("     SpMV:       %.3f ms\n", T.t_spmv);
+        printf("     BLAS1:      %.3f ms\n", T.t_blas);
+        printf("     Reductions: %.3f ms\n", T.t_red);
     }
     return 0;
 }
@@ -576,8 +528,5 @@ extern "C" size_t spmv_amd_cg_multi_workspace_bytes(void) {
 
 extern "C" int spmv_amd_cg_last_history_multi(int rhs, double* out, int cap) {
     if (rhs < 0 || rhs >= (int)g_multi_history.size()) return -1;
-    const std::vector<double>& h = g_multi_history[(size_t)rhs];
-    const int count = (int)h.size();
-    for (int i = 0; i < count && i < cap && out != nullptr; ++i) out[i] = h[i];
-    return count;
+    return copy_history(g_multi_history[(size_t)rhs], out, cap);
 }

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "device_runtime.hpp"
+#include "solve_common.hpp"
 
 using namespace spmv_amd;
 
@@ -57,16 +58,6 @@ struct Vectors {
     }
 };
 
-void fill_solution_checksums(const double* x, int n, double* sum, double* norm) {
-    double s = 0.0, q = 0.0;
-    for (int i = 0; i < n; i++) {
-        s += x[i];
-        q += x[i] * x[i];
-    }
-    *sum = s;
-    *norm = sqrt(q);
-}
-
 void print_breakdown(const char* tag, const CGStats* st) {
     printf("[%s] Converged: %s\n", tag, st->converged ? "YES" : "NO");
     printf("[%s] Iterations: %d\n", tag, st->iterations);
@@ -99,15 +90,13 @@ int cg_solve(SpmvOperator* spmv_op, MatrixData* mat, const double* b, double* x,
     std::vector<double>& hist = last_cg_history();
     hist.clear();
 
-    EventTimer total, part;
-    double t_spmv = 0.0, t_blas = 0.0, t_red = 0.0;
-    auto host_dot = [&](const double* a, const double* c) {
-        part.begin(kStream);
-        launch_dot((size_t)n, a, c, v.scratch, d_scalar, kStream);
+    StageTimers T(/*detail=*/true, kStream);  // this entry point times every stage, as the reference's does
+    auto host_dot = [&](const double* a, const double* c) {  // the launch AND the blocking 8-byte read are the reduction's time
         double h = 0.0;
-        download(&h, d_scalar, 1);
-        part.end(kStream);
-        t_red += part.elapsed_ms();
+        T.run(&T.t_red, [&] {
+            launch_dot((size_t)n, a, c, v.scratch, d_scalar, kStream);
+            download(&h, d_scalar, 1);
+        });
         return h;
     };
     // The reference's host path hands the direction vector to run_timed as a HOST array: four PCIe transfers of the whole vector
@@ -119,26 +108,20 @@ int cg_solve(SpmvOperator* spmv_op, MatrixData* mat, const double* b, double* x,
     bool op_failed = false;  // run_device returned non-zero: stop, release everything, return 1 (never exit() from a library)
     auto host_spmv = [&](const double* d_in, double* d_out) {
         double kernel_ms = 0.0;
-        part.begin(kStream);
-        if (through_host) {
-            download(h_in, d_in, (size_t)n);
-            spmv_op->run_timed(h_in, h_out, &kernel_ms);
-            upload(d_out, h_out, (size_t)n);
-        } else if (spmv_op->run_device(d_in, d_out) != 0) {
-            fprintf(stderr, "[CG] operator '%s': run_device failed\n", spmv_op->name);
-            op_failed = true;
-        }
-        part.end(kStream);
-        t_spmv += part.elapsed_ms();
+        T.run(&T.t_spmv, [&] {
+            if (through_host) {
+                download(h_in, d_in, (size_t)n);
+                spmv_op->run_timed(h_in, h_out, &kernel_ms);
+                upload(d_out, h_out, (size_t)n);
+            } else if (spmv_op->run_device(d_in, d_out) != 0) {
+                fprintf(stderr, "[CG] operator '%s': run_device failed\n", spmv_op->name);
+                op_failed = true;
+            }
+        });
     };
-    auto timed_blas = [&](auto&& launch) {
-        part.begin(kStream);
-        launch();
-        part.end(kStream);
-        t_blas += part.elapsed_ms();
-    };
+    auto timed_blas = [&](auto&& launch) { T.run(&T.t_blas, launch); };
 
-    total.begin(kStream);
+    T.total.begin(kStream);
     host_spmv(v.x, v.Ap);
     timed_blas([&] { launch_axpby((size_t)n, 1.0, v.b, -1.0, v.Ap, v.r, kStream); });
     HIP_CHECK(hipMemcpyAsync(v.p, v.r, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, kStream));
@@ -170,18 +153,18 @@ int cg_solve(SpmvOperator* spmv_op, MatrixData* mat, const double* b, double* x,
         timed_blas([&] { launch_axpby((size_t)n, 1.0, v.r, beta, v.p, v.p, kStream); });
         rr_old = rr_new;
     }
-    total.end(kStream);
-    const float total_ms = total.elapsed_ms();
+    T.total.end(kStream);
+    const float total_ms = T.total.elapsed_ms();
     download(x, v.x, (size_t)n);
 
     stats->iterations = iter;
     stats->residual_norm = residual_norm;
     stats->time_total_ms = total_ms;
-    stats->time_spmv_ms = t_spmv;
-    stats->time_blas1_ms = t_blas;
-    stats->time_reductions_ms = t_red;
+    stats->time_spmv_ms = T.t_spmv;
+    stats->time_blas1_ms = T.t_blas;
+    stats->time_reductions_ms = T.t_red;
     stats->converged = (residual_norm / b_norm < config.tolerance) ? 1 : 0;
-    fill_solution_checksums(x, n, &stats->solution_sum, &stats->solution_norm);
+    solution_checksums(x, n, &stats->solution_sum, &stats->solution_norm);
     if (config.verbose >= 1 && !op_failed) print_breakdown("CG", stats);
 
     v.release();
@@ -200,7 +183,7 @@ int cg_solve_device(SpmvOperator* spmv_op, MatrixData* mat, const double* b, dou
     }
     // the loop lives in cg_slab.hip (cg_solve_on_operator): the slab solver's fused kernels around this operator
     if (cg_solve_on_operator(spmv_op, mat->rows, b, x, config, stats, &last_cg_history()) != 0) return 1;
-    fill_solution_checksums(x, mat->rows, &stats->solution_sum, &stats->solution_norm);
+    solution_checksums(x, mat->rows, &stats->solution_sum, &stats->solution_norm);
     if (config.verbose >= 1) print_breakdown("CG-DEVICE", stats);
     return 0;
 }
@@ -216,8 +199,5 @@ extern "C" int spmv_amd_cg_solve_device(SpmvOperator* op, MatrixData* mat, const
 }
 
 extern "C" int spmv_amd_cg_last_history(double* out, int cap) {
-    const std::vector<double>& h = last_cg_history();
-    const int count = (int)h.size();
-    for (int i = 0; i < count && i < cap; ++i) out[i] = h[i];
-    return count;
+    return copy_history(last_cg_history(), out, cap);
 }

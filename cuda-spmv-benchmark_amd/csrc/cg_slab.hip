@@ -75,6 +75,7 @@
 #include "comm.hpp"
 #include "device_runtime.hpp"
 #include "multi_rhs.hpp"
+#include "solve_common.hpp"
 #include "stencil_geometry.hpp"
 #include "trace_ranges.hpp"
 #include "watchdog.hpp"
@@ -1589,9 +1590,7 @@ extern "C" int spmv_amd_cg_slab_gather(SpmvAmdCgSlab* s, double* x_full) {
 }
 
 extern "C" int spmv_amd_cg_slab_history(SpmvAmdCgSlab* s, double* out, int cap) {
-    const int count = (int)s->history.size();
-    for (int i = 0; i < count && i < cap; ++i) out[i] = s->history[i];
-    return count;
+    return copy_history(s->history, out, cap);
 }
 
 extern "C" int spmv_amd_cg_slab_spmv(SpmvAmdCgSlab* s, const double* x_full, double* y_local) {
@@ -1815,16 +1814,12 @@ int cg_solve_on_operator(SpmvOperator* op, int n, const double* b, double* x, co
     if (spmv_amd_cg_slab_solve(s, &cfg, &st) != 0) return 1;
     download(x, s->x, (size_t)n);
     *history = s->history;
-    stats->iterations = st.iterations;
-    // not converged: the reference's final_residual_norm is whatever it last copied back -- the residual of the last
-    // iteration under verbose >= 2, else still ||r0|| (:535, :601-619)
+    // ||r0|| and the last residual copied back are the history's ends; the slab's six timers onto the reference's four
     const double r0 = s->history.empty() ? 0.0 : s->history.front();
-    stats->residual_norm = st.converged ? st.residual_norm : (config.verbose >= 2 && !s->history.empty() ? s->history.back() : r0);
-    stats->time_total_ms = st.time_total_ms;
-    stats->time_spmv_ms = st.time_spmv_ms + (config.enable_detailed_timers ? st.time_initial_r_ms : 0.0);
-    stats->time_blas1_ms = st.time_blas1_ms;
-    stats->time_reductions_ms = st.time_reductions_ms + st.time_dot_rs_initial_ms;
-    stats->converged = (r0 > 0.0 && stats->residual_norm / r0 < config.tolerance) ? 1 : 0;
+    const double last = st.converged ? st.residual_norm : (s->history.empty() ? 0.0 : s->history.back());
+    fill_device_stats(stats, st.iterations, st.converged != 0, last, r0, config, st.time_total_ms,
+                      st.time_spmv_ms + (config.enable_detailed_timers ? st.time_initial_r_ms : 0.0), st.time_blas1_ms,
+                      st.time_reductions_ms + st.time_dot_rs_initial_ms);
     return 0;
 }
 
@@ -1897,15 +1892,7 @@ int cg_solve_mgpu_partitioned(SpmvOperator* spmv_op, MatrixData* mat, const doub
     }
 
     spmv_amd_cg_slab_gather(s, x);
-    if (rank == 0) {
-        double sum = 0.0, sq = 0.0;
-        for (int i = 0; i < mat->rows; i++) {
-            sum += x[i];
-            sq += x[i] * x[i];
-        }
-        stats->solution_sum = sum;
-        stats->solution_norm = sqrt(sq);
-    }
+    if (rank == 0) solution_checksums(x, mat->rows, &stats->solution_sum, &stats->solution_norm);
     spmv_amd_cg_slab_destroy(s);
     return 0;
 }

@@ -185,6 +185,10 @@ void launch_update_p_dev(size_t n, const double* r, const double* d_b, double* p
 // result = sum x[i]*y[i], fixed reduction shape (deterministic run to run). scratch must
 // hold dot_scratch_doubles(n) doubles and be zeroed once after allocation (ticket counter).
 size_t dot_scratch_doubles(size_t n);
+// The grid of every streaming kernel (one-wave workgroups, one 16-byte pair per lane) = the partials a reducing one writes.
+unsigned stream_grid(size_t n);
+// The first half of launch_dot alone: partials[block] of x.y, stream_grid(n) of them.
+void launch_dot_partials(size_t n, const double* x, const double* y, double* partials, hipStream_t stream);
 void launch_dot(size_t n, const double* x, const double* y, double* scratch, double* d_result,
                 hipStream_t stream);
 // *d_out = (*d_num) / (*d_den)   (scalar_divide_kernel, cg_solver.cu:414-419)

@@ -457,24 +457,38 @@ SpmvOperator SPMV_STENCIL_HALO_MGPU = {"stencil5-halo-mgpu", stencil_init,
                                        run_timed_generic<stencil_run_device, &g_stencil>,
                                        stencil_run_device, stencil_free};
 
+namespace {
+// Which of this library's operators `op` is: its CSR-backed state, its ELLPACK state, or neither (a table this library does
+// not own). "stencil5-halo-mgpu" is the stencil operator under another name. Host state only (no HIP call).
+struct OwnOperator {
+    CsrBackedOperator* csr = nullptr;
+    EllOperator* ell = nullptr;
+};
+OwnOperator own_operator_of(const SpmvOperator* op) {
+    OwnOperator o;
+    if (op == &SPMV_STENCIL5_CSR || op == &SPMV_STENCIL_HALO_MGPU) o.csr = &g_stencil;
+    else if (op == &SPMV_CSR) o.csr = &g_csr;
+    else if (op == &SPMV_ELLPACK) o.ell = &g_ell;
+    else if (op == &SPMV_STENCIL5_ELLPACK) o.ell = &g_ell_stencil;
+    return o;
+}
+}  // namespace
+
 namespace spmv_amd {
 FusedSpmv fused_spmv_of(const SpmvOperator* op) {
     FusedSpmv f;
+    const OwnOperator o = own_operator_of(op);
     // (the row-generic kernel of small or unverified matrices keeps the plain dot kernel, as in the slab solver)
-    if ((op == &SPMV_STENCIL5_CSR || op == &SPMV_STENCIL_HALO_MGPU) && g_stencil.ready && g_stencil.plan.partials > 0 &&
-        g_stencil.plan.variant != Stencil5Variant::RowGeneric) {
+    if (o.csr == &g_stencil && g_stencil.ready && g_stencil.plan.partials > 0 && g_stencil.plan.variant != Stencil5Variant::RowGeneric) {
         f.partials = g_stencil.plan.partials;
         f.can_init = g_stencil.plan.variant == Stencil5Variant::RowLds;
         f.launch = stencil_fused_launch;
-    } else if (op == &SPMV_CSR && g_csr.ready && g_csr.rows == g_csr.cols) {
+    } else if (o.csr == &g_csr && g_csr.ready && g_csr.rows == g_csr.cols) {
         f.partials = csr_fused_dot_partials(g_csr.A.view, g_csr.csr_variant);
         f.launch = f.partials > 0 ? csr_fused_launch : nullptr;
-    } else if (op == &SPMV_ELLPACK && g_ell.ready && g_ell.rows == g_ell.cols) {
-        f.partials = ell_fused_dot_partials(g_ell.rows);
-        f.launch = ell_fused_launch<&g_ell>;
-    } else if (op == &SPMV_STENCIL5_ELLPACK && g_ell_stencil.ready && g_ell_stencil.rows == g_ell_stencil.cols) {
-        f.partials = ell_fused_dot_partials(g_ell_stencil.rows);
-        f.launch = ell_fused_launch<&g_ell_stencil>;
+    } else if (o.ell != nullptr && o.ell->ready && o.ell->rows == o.ell->cols) {
+        f.partials = ell_fused_dot_partials(o.ell->rows);
+        f.launch = o.ell == &g_ell ? ell_fused_launch<&g_ell> : ell_fused_launch<&g_ell_stencil>;
     }
     return f;
 }
@@ -483,23 +497,21 @@ FusedSpmv fused_spmv_of(const SpmvOperator* op) {
 // operator's is the sequential thread-per-row kernel whatever its single-vector variant. The ELLPACK operators have none.
 MultiOperand multi_operand_of(const SpmvOperator* op) {
     MultiOperand o;
-    if (op == &SPMV_STENCIL5_CSR || op == &SPMV_STENCIL_HALO_MGPU) {
-        o.has_multi = true;
-        o.ready = g_stencil.ready;
-        if (o.ready) o.plan = plan_spmm(g_stencil.A.view, g_stencil.plan.variant, false, g_stencil.rows, g_stencil.cols);
-    } else if (op == &SPMV_CSR) {
-        o.has_multi = true;
-        o.ready = g_csr.ready;
-        if (o.ready) o.plan = plan_spmm(g_csr.A.view, Stencil5Variant::Auto, true, g_csr.rows, g_csr.cols);
-    }
+    const CsrBackedOperator* c = own_operator_of(op).csr;
+    if (c == nullptr) return o;
+    o.has_multi = true;
+    o.ready = c->ready;
+    const bool stencil = c == &g_stencil;
+    if (o.ready) o.plan = plan_spmm(c->A.view, stencil ? g_stencil.plan.variant : Stencil5Variant::Auto, !stencil, c->rows, c->cols);
     return o;
 }
 
 // Where a Jacobi preconditioner reads the diagonal (pcg.hip): the operator's own device storage, no copy.
 DiagonalSource diagonal_source_of(const SpmvOperator* op) {
     DiagonalSource d;
-    const CsrBackedOperator* c = (op == &SPMV_STENCIL5_CSR || op == &SPMV_STENCIL_HALO_MGPU) ? &g_stencil : op == &SPMV_CSR ? &g_csr : nullptr;
-    const EllOperator* e = op == &SPMV_ELLPACK ? &g_ell : op == &SPMV_STENCIL5_ELLPACK ? &g_ell_stencil : nullptr;
+    const OwnOperator o = own_operator_of(op);
+    const CsrBackedOperator* c = o.csr;
+    const EllOperator* e = o.ell;
     if (c != nullptr) {
         d.owner = c;
         d.kind = DiagonalSource::Csr;

@@ -1,8 +1,8 @@
 // pcg.hip -- Jacobi-preconditioned CG over any SpmvOperator.
 //
-// A new entry point with its own loop, built the way cg_multi.hip is: the algebra of cg_solve_device with z = M^-1 r,
-// M = diag(A) ("jacobi") or I ("none"), the same stopping rule (true residual ||r_k|| / ||r_0|| < tol, strict, the
-// converging iteration counted), statistics and timer rule. One iteration:
+// An entry point with its own loop: the algebra of cg_solve_device with z = M^-1 r, M = diag(A) ("jacobi") or I ("none"),
+// the same stopping rule (true residual ||r_k|| / ||r_0|| < tol, strict, the converging iteration counted), statistics and
+// timer rule (solve_common.hpp has those, stream_device.hpp the kernels' small helpers). One iteration:
 //   Ap = A p with the p.Ap partials (the operator's fused launch; else run_device + a dot pass) |
 //   sum + step (alpha = rz / pAp) |
 //   r -= alpha Ap, z = dinv r in registers, partials of r.r and r.z |
@@ -22,6 +22,8 @@
 #include "device_runtime.hpp"
 #include "multi_rhs.hpp"
 #include "reduce_device.hpp"
+#include "solve_common.hpp"
+#include "stream_device.hpp"
 
 using namespace spmv_amd;
 
@@ -40,8 +42,6 @@ namespace {
 constexpr hipStream_t kStream = nullptr;  // default stream, shared with the operators
 constexpr int kWave = 64;                 // the streaming kernels: one wavefront per workgroup, one 16-byte pair per lane
 
-typedef double d2 __attribute__((ext_vector_type(2)));
-
 // Device scalars of one preconditioned solve.
 struct PcgScalars {
     double rz;        // r.z of the current residual
@@ -55,24 +55,6 @@ struct PcgScalars {
 };
 
 __device__ __forceinline__ bool usable(double v) { return v != 0.0 && isfinite(v); }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-
-__device__ __forceinline__ d2 load_once(const double* __restrict__ base, size_t pair) {
-    return __builtin_nontemporal_load(reinterpret_cast<const d2*>(base) + pair);
-}
-__device__ __forceinline__ void store_once(double* __restrict__ base, size_t pair, d2 v) {
-    __builtin_nontemporal_store(v, reinterpret_cast<d2*>(base) + pair);
-}
-
-unsigned stream_blocks(size_t n) {
-    const size_t want = ((n >> 1) + kWave - 1) / kWave;
-    return (unsigned)(want < 1 ? 1 : want);
-}
 
 // ---- diagonal extraction: d_i = sum of row i's entries in column i, CSR order, from 0.0; dinv_i = 1.0 / d_i ----
 // Validity in the same pass: d_i finite, non-zero and of d_0's sign, else atomicMin(bad_row, i).
@@ -210,20 +192,6 @@ __global__ __launch_bounds__(kWave) void pcg_update_xp_kernel(size_t n, const Pc
     }
 }
 
-// p.Ap partials for an operator without a fused launch (after its run_device)
-__global__ __launch_bounds__(kWave) void pcg_dot_kernel(size_t n, const double* __restrict__ a, const double* __restrict__ b,
-                                                        double* __restrict__ partials) {
-    const size_t i = (size_t)blockIdx.x * kWave + threadIdx.x;
-    double acc = 0.0;
-    if (i < (n >> 1)) {
-        const d2 av = load_once(a, i), bv = load_once(b, i);
-        acc = fma(av.x, bv.x, acc), acc = fma(av.y, bv.y, acc);
-    }
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) acc = fma(a[n - 1], b[n - 1], acc);
-    acc = wave_sum(acc);
-    if (threadIdx.x == 0) partials[blockIdx.x] = acc;
-}
-
 // ---- reductions: NV sums of `count` partials each (value v at partials[v * count ...]) in ONE launch, then the scalar step ----
 // The shape of reduce_device.hpp extended to two values: slice workgroups publish their slice sums of value 0 into the stage's
 // `sums`, of value 1 into its `extra` slots; the workgroup that draws the last ticket sums both and takes the step. One
@@ -343,13 +311,9 @@ bool ensure_workspace(int n, int device, long long partial_cap, int hist_cap) {
     if (w.x == nullptr) {
         const size_t need = 5 * (size_t)n * sizeof(double) + (size_t)partial_cap * sizeof(double) + (size_t)hist_cap * sizeof(double) +
                             ((size_t)64 << 20);
-        size_t free_b = 0, total_b = 0;
-        HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-        if (need > free_b) {
-            fprintf(stderr, "[PCG] the workspace for %d rows needs %.2f GB, the device has %.2f GB free: refused\n", n, need / 1e9,
-                    free_b / 1e9);
-            return false;
-        }
+        char what[32];
+        snprintf(what, sizeof what, "%d rows", n);
+        if (!device_has_room(need, "PCG", what)) return false;
         w.x = device_try_alloc<double>((size_t)n);
         w.b = device_try_alloc<double>((size_t)n);
         w.r = device_try_alloc<double>((size_t)n);
@@ -364,13 +328,7 @@ bool ensure_workspace(int n, int device, long long partial_cap, int hist_cap) {
         w.stage = reduce_scratch_alloc();
         w.n = n, w.device = device, w.partial_cap = partial_cap;
     }
-    if (w.hist_cap < hist_cap) {
-        device_release(w.hist);
-        w.hist_cap = 0;
-        w.hist = device_try_alloc<double>((size_t)hist_cap);
-        if (w.hist == nullptr) return fail("the history could not be allocated: refused");
-        w.hist_cap = hist_cap;
-    }
+    if (!grow_history(w.hist, w.hist_cap, hist_cap)) return fail("the history could not be allocated: refused");
     return true;
 }
 
@@ -409,16 +367,6 @@ SpmvAmdPrecond* make_jacobi(int src, const SlabCsr& m, const int* idx, const dou
     pm->n = n;
     pm->dinv = dinv;
     return pm;
-}
-
-void solution_checksums(const double* x, int n, double* sum, double* norm) {
-    double s = 0.0, q = 0.0;
-    for (int i = 0; i < n; i++) {
-        s += x[i];
-        q += x[i] * x[i];
-    }
-    *sum = s;
-    *norm = sqrt(q);
 }
 
 }  // namespace
@@ -532,26 +480,16 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
     HIP_CHECK(hipGetDevice(&device));
     const FusedSpmv f = fused_spmv_of(op);
     const bool fused = f.launch != nullptr && f.partials > 0;
-    const int vec_count = (int)stream_blocks((size_t)n);
+    const int vec_count = (int)stream_grid((size_t)n);
     const long long partial_cap = 2LL * vec_count > f.partials ? 2LL * vec_count : (long long)f.partials;
     if (!ensure_workspace(n, device, partial_cap, cfg.max_iters + 1)) return 1;
     PcgWorkspace& w = g_pcg;
     upload(w.b, b, (size_t)n);
     upload(w.x, x, (size_t)n);
 
-    const dim3 grid(stream_blocks((size_t)n)), block(kWave);
-    const bool detail = cfg.enable_detailed_timers != 0;
-    EventTimer total, part;
-    double t_spmv = 0.0, t_blas = 0.0, t_red = 0.0;
+    const dim3 grid(stream_grid((size_t)n)), block(kWave);
+    StageTimers T(cfg.enable_detailed_timers != 0, kStream);
     bool op_failed = false;
-    auto stage = [&](double* acc, auto&& launch) {
-        if (detail) part.begin(kStream);
-        launch();
-        if (detail) {
-            part.end(kStream);
-            *acc += part.elapsed_ms();
-        }
-    };
     auto reduce = [&](int count, int nv, int which) {
         int slice = 0, blocks = 0;
         reduce_geometry(count, &slice, &blocks);
@@ -570,42 +508,42 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
     };
     PcgScalars h{};
 
-    total.begin(kStream);
-    stage(&t_spmv, [&] { run_op(w.x, w.Ap); });
+    T.total.begin(kStream);
+    T.run(&T.t_spmv, [&] { run_op(w.x, w.Ap); });
     if (jac)
-        stage(&t_blas, [&] { hipLaunchKernelGGL(pcg_init_kernel<true>, grid, block, 0, kStream, (size_t)n, w.b, w.Ap, m->dinv, w.r, w.p, w.partials, vec_count); });
+        T.run(&T.t_blas, [&] { hipLaunchKernelGGL(pcg_init_kernel<true>, grid, block, 0, kStream, (size_t)n, w.b, w.Ap, m->dinv, w.r, w.p, w.partials, vec_count); });
     else
-        stage(&t_blas, [&] { hipLaunchKernelGGL(pcg_init_kernel<false>, grid, block, 0, kStream, (size_t)n, w.b, w.Ap, nullptr, w.r, w.p, w.partials, vec_count); });
-    stage(&t_red, [&] { reduce(vec_count, 2, 0); });
+        T.run(&T.t_blas, [&] { hipLaunchKernelGGL(pcg_init_kernel<false>, grid, block, 0, kStream, (size_t)n, w.b, w.Ap, nullptr, w.r, w.p, w.partials, vec_count); });
+    T.run(&T.t_red, [&] { reduce(vec_count, 2, 0); });
     download(&h, w.s, 1);
     if (cfg.verbose >= 1) printf("[PCG-DEVICE] Initial residual: %e (preconditioner %s)\n", h.b_norm, jac ? "jacobi" : "none");
     for (int it = 0; it < cfg.max_iters && !op_failed && !h.converged && !h.breakdown; ++it) {
         int pap_count = vec_count;
-        stage(&t_spmv, [&] {
+        T.run(&T.t_spmv, [&] {
             if (fused) {
                 pap_count = f.launch(w.p, w.Ap, w.partials, nullptr, false, nullptr, kStream);
             } else {
                 run_op(w.p, w.Ap);
-                hipLaunchKernelGGL(pcg_dot_kernel, grid, block, 0, kStream, (size_t)n, w.p, w.Ap, w.partials);
+                launch_dot_partials((size_t)n, w.p, w.Ap, w.partials, kStream);
             }
         });
         if (op_failed) break;
-        stage(&t_red, [&] { reduce(pap_count, 1, 1); });
+        T.run(&T.t_red, [&] { reduce(pap_count, 1, 1); });
         if (jac)
-            stage(&t_blas, [&] { hipLaunchKernelGGL(pcg_update_r_kernel<true>, grid, block, 0, kStream, (size_t)n, w.s, w.Ap, m->dinv, w.r, w.partials, vec_count); });
+            T.run(&T.t_blas, [&] { hipLaunchKernelGGL(pcg_update_r_kernel<true>, grid, block, 0, kStream, (size_t)n, w.s, w.Ap, m->dinv, w.r, w.partials, vec_count); });
         else
-            stage(&t_blas, [&] { hipLaunchKernelGGL(pcg_update_r_kernel<false>, grid, block, 0, kStream, (size_t)n, w.s, w.Ap, nullptr, w.r, w.partials, vec_count); });
-        stage(&t_red, [&] { reduce(vec_count, 2, 2); });
+            T.run(&T.t_blas, [&] { hipLaunchKernelGGL(pcg_update_r_kernel<false>, grid, block, 0, kStream, (size_t)n, w.s, w.Ap, nullptr, w.r, w.partials, vec_count); });
+        T.run(&T.t_red, [&] { reduce(vec_count, 2, 2); });
         if (jac)
-            stage(&t_blas, [&] { hipLaunchKernelGGL(pcg_update_xp_kernel<true>, grid, block, 0, kStream, (size_t)n, w.s, w.r, m->dinv, w.p, w.x); });
+            T.run(&T.t_blas, [&] { hipLaunchKernelGGL(pcg_update_xp_kernel<true>, grid, block, 0, kStream, (size_t)n, w.s, w.r, m->dinv, w.p, w.x); });
         else
-            stage(&t_blas, [&] { hipLaunchKernelGGL(pcg_update_xp_kernel<false>, grid, block, 0, kStream, (size_t)n, w.s, w.r, nullptr, w.p, w.x); });
+            T.run(&T.t_blas, [&] { hipLaunchKernelGGL(pcg_update_xp_kernel<false>, grid, block, 0, kStream, (size_t)n, w.s, w.r, nullptr, w.p, w.x); });
         download(&h, w.s, 1);  // synchronises: the stopping test
         if (cfg.verbose >= 2)
             printf("[PCG-DEVICE] Iter %3d: residual = %e (rel = %e)\n", h.iterations, h.residual, h.residual / h.b_norm);
     }
-    total.end(kStream);
-    const double total_ms = total.elapsed_ms();
+    T.total.end(kStream);
+    const double total_ms = T.total.elapsed_ms();
     HIP_CHECK(hipGetLastError());
     download(x, w.x, (size_t)n);
     const int count = h.iterations + 1 < w.hist_cap ? h.iterations + 1 : w.hist_cap;
@@ -613,14 +551,7 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
     download(g_pcg_history.data(), w.hist, (size_t)count);
     if (op_failed) return 1;
 
-    stats->iterations = h.iterations;
-    // not converged: ||r0|| unless verbose >= 2 copied the last residual back (cg_solve_device's rule)
-    stats->residual_norm = h.converged ? h.residual : (cfg.verbose >= 2 && h.iterations > 0 ? h.residual : h.b_norm);
-    stats->converged = (h.b_norm > 0.0 && stats->residual_norm / h.b_norm < cfg.tolerance) ? 1 : 0;
-    stats->time_total_ms = total_ms;
-    stats->time_spmv_ms = t_spmv;
-    stats->time_blas1_ms = t_blas;
-    stats->time_reductions_ms = t_red;
+    fill_device_stats(stats, h.iterations, h.converged != 0, h.residual, h.b_norm, cfg, total_ms, T.t_spmv, T.t_blas, T.t_red);
     solution_checksums(x, n, &stats->solution_sum, &stats->solution_norm);
     if (cfg.verbose >= 1) {
         if (h.breakdown) printf("[PCG-DEVICE] Breakdown in iteration %d (pAp or r.z zero or not finite)\n", h.iterations);
@@ -637,9 +568,7 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
 }
 
 extern "C" int spmv_amd_pcg_last_history(double* out, int cap) {
-    const int count = (int)g_pcg_history.size();
-    for (int i = 0; i < count && i < cap && out != nullptr; ++i) out[i] = g_pcg_history[(size_t)i];
-    return count;
+    return copy_history(g_pcg_history, out, cap);
 }
 
 extern "C" void spmv_amd_pcg_release_workspace(void) { spmv_amd::release_cg_workspace(); }

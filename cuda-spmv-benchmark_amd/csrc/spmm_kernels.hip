@@ -28,6 +28,7 @@
 
 #include "multi_rhs.hpp"
 #include "stencil_geometry.hpp"
+#include "stream_device.hpp"
 
 namespace spmv_amd {
 namespace {
@@ -35,14 +36,12 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kTile = 64;  // row-lds: columns per wave
 
-typedef double dbl2 __attribute__((ext_vector_type(2)));
-
 template <int K, bool kVec>
 __device__ __forceinline__ void load_row(const double* __restrict__ p, double (&o)[K]) {
     if constexpr (kVec && K % 2 == 0) {
 #pragma unroll
         for (int i = 0; i < K / 2; ++i) {
-            const dbl2 t = reinterpret_cast<const dbl2*>(p)[i];
+            const d2 t = reinterpret_cast<const d2*>(p)[i];
             o[2 * i] = t.x, o[2 * i + 1] = t.y;
         }
     } else {
@@ -56,9 +55,9 @@ __device__ __forceinline__ void store_row_nt(double* __restrict__ p, const doubl
     if constexpr (kVec && K % 2 == 0) {
 #pragma unroll
         for (int i = 0; i < K / 2; ++i) {
-            dbl2 t;
+            d2 t;
             t.x = v[2 * i], t.y = v[2 * i + 1];
-            __builtin_nontemporal_store(t, reinterpret_cast<dbl2*>(p) + i);
+            __builtin_nontemporal_store(t, reinterpret_cast<d2*>(p) + i);
         }
     } else {
 #pragma unroll

@@ -27,6 +27,7 @@
 
 #include "reduce_device.hpp"
 #include "stencil_geometry.hpp"
+#include "stream_device.hpp"
 
 namespace spmv_amd {
 namespace {
@@ -178,7 +179,6 @@ constexpr int kLdsTileCols = 128;
 // one grid row up (plain loads: the S line is re-read as N one grid row later, like x's N / S neighbours), and W = E[i - 1]
 // from the LDS copy of the tile's own E values (`strip`; lane 0 loads the one outside the tile). 24 B/row of coefficients
 // instead of 40. The fma chains are the CSR form's, value for value (the planes were verified bit for bit at creation).
-typedef double dbl2 __attribute__((ext_vector_type(2)));
 template <int kMode, bool kFreshHalo = false, bool kSym = false>
 __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __restrict__ x, double* __restrict__ y, double alpha,
                                             int li, int gi, int j0, int lane, int skip, double* __restrict__ strip,
@@ -194,16 +194,16 @@ __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __re
         const long long e = stencil_gridrow_base(gi, n) + 5LL * j0 - 1 - m.nnz_base + lane;
         const double* __restrict__ vals = m.values;
         double c[10];
-        dbl2 ce[2];                           // kSym: [C, E] of the lane's two rows
+        d2 ce[2];                             // kSym: [C, E] of the lane's two rows
         double cs[2], cn[2], cw = 0.0;        // kSym: S, N = S[i - n]; lane 0: E[i - 1] of the tile's first row
         if constexpr (kSym) {
             const long long r0 = (long long)li * n + j0 + lane;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                ce[h] = dbl2{0.0, 0.0};
+                ce[h] = d2{0.0, 0.0};
                 cs[h] = cn[h] = 0.0;
                 if (j0 + lane + 64 * h < n) {
-                    ce[h] = __builtin_nontemporal_load(reinterpret_cast<const dbl2*>(sp.ce) + r0 + 64 * h);
+                    ce[h] = __builtin_nontemporal_load(reinterpret_cast<const d2*>(sp.ce) + r0 + 64 * h);
                     cs[h] = sp.s[r0 + 64 * h];
                     cn[h] = sp.s[r0 + 64 * h - n];  // local grid row 0: the halo row in front of the plane
                 }
@@ -343,10 +343,7 @@ __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __re
             }
         }
     }
-    if (kDot || kInit) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) dot_acc += __shfl_down(dot_acc, off);
-    }
+    if (kDot || kInit) dot_acc = wave_sum(dot_acc);
     *dot = dot_acc;  // lane 0 holds the tile's partial
     return true;
 }
@@ -692,8 +689,7 @@ __global__ __launch_bounds__(kBlock) void csr_wavefront_kernel(SlabCsr m, const 
         for (int k = m.row_ptr[row] + lane; k < k1; k += 64)
             sum = fma(m.values[k], x_at(x, (long long)m.col_idx[k] - m.row_offset, lo, hi), sum);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off);
+    sum = wave_sum(sum);
     if (lane == 0 && row < m.n_local) y[row] = alpha * sum;
 }
 
