@@ -74,6 +74,19 @@ class CGStatsMultiGPU(C.Structure):
     ]
 
 
+class PcgScalars(C.Structure):
+    """SpmvAmdPcgScalars (include/spmv_amd/lab.h): the device scalars of one preconditioned solve."""
+    _fields_ = [("rz", C.c_double), ("pAp", C.c_double), ("alpha", C.c_double), ("beta", C.c_double), ("b_norm", C.c_double),
+                ("residual", C.c_double), ("iterations", C.c_int), ("converged", C.c_int), ("breakdown", C.c_int), ("skip_update", C.c_int)]
+
+
+class PcgStageArgs(C.Structure):
+    """SpmvAmdPcgStageArgs (include/spmv_amd/lab.h): device pointers and sizes of one spmv_amd_pcg_stage call."""
+    _fields_ = [("n", C.c_size_t), ("b", C.c_void_p), ("Ap", C.c_void_p), ("dinv", C.c_void_p), ("r", C.c_void_p), ("p", C.c_void_p),
+                ("x", C.c_void_p), ("partials", C.c_void_p), ("count", C.c_int), ("which", C.c_int), ("tol", C.c_double),
+                ("hist", C.c_void_p), ("hist_cap", C.c_int)]
+
+
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
 GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int))
@@ -107,7 +120,7 @@ DECLARED_SYMBOLS = [
     "spmv_amd_precond_inverse_diagonal", "spmv_amd_pcg_solve_device", "spmv_amd_pcg_last_history", "spmv_amd_pcg_release_workspace",
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
-LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option"]
+LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_pcg_stage"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
 DECLARED_CXX_SYMBOLS = [
     "SPMV_CSR", "SPMV_STENCIL5_CSR", "SPMV_STENCIL_HALO_MGPU", "SPMV_ELLPACK", "SPMV_STENCIL5_ELLPACK",
@@ -198,6 +211,8 @@ def lib():
         L.spmv_amd_cg_slab_create_stencil5_as.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.spmv_amd_cg_slab_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
         L.spmv_amd_cg_slab_set_option.restype = C.c_int
+        L.spmv_amd_pcg_stage.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PcgStageArgs), C.POINTER(PcgScalars)]
+        L.spmv_amd_pcg_stage.restype = C.c_int
     L.spmv_amd_cg_slab_create.restype = C.c_void_p
     L.spmv_amd_cg_slab_create.argtypes = [C.POINTER(MatrixData), C.c_void_p]
     L.spmv_amd_cg_slab_create_stencil5.restype = C.c_void_p
@@ -625,6 +640,15 @@ def pcg_solve_device(op, host_matrix, precond, b, x0, max_iters=1000, tol=1e-6, 
     hist = np.zeros(max_iters + 1, dtype=np.float64)
     count = L.spmv_amd_pcg_last_history(hist.ctypes.data, len(hist))
     return x, hist[:count].copy(), st
+
+
+def pcg_stage(stage, kind, args, scalars=None):
+    """spmv_amd_pcg_stage (LAB build only; include/spmv_amd/lab.h): one stage of the preconditioned solver's own kernels on the
+    device data `args` (PcgStageArgs) points to; returns its return code (0, or non-zero for a refusal)."""
+    if not is_lab():
+        raise RuntimeError("the PCG stages exist in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+    return lib().spmv_amd_pcg_stage(stage if stage is None else stage.encode(), kind if kind is None else kind.encode(),
+                                    None if args is None else C.byref(args), None if scalars is None else C.byref(scalars))
 
 
 class Comm:

@@ -15,6 +15,8 @@
 // negative-definite systems solve). Sums have a fixed shape (reduce_device.hpp): a solve is bit-reproducible.
 #include <limits.h>
 #include <math.h>
+#include <stddef.h>
+#include <stdint.h>
 #include <string.h>
 
 #include <vector>
@@ -24,6 +26,9 @@
 #include "reduce_device.hpp"
 #include "solve_common.hpp"
 #include "stream_device.hpp"
+#ifdef SPMV_AMD_LAB
+#include "spmv_amd/lab.h"
+#endif
 
 using namespace spmv_amd;
 
@@ -274,6 +279,48 @@ __global__ __launch_bounds__(kReduceBlock) void pcg_reduce_kernel(const double* 
     if (threadIdx.x == 0) pcg_step(s, which, total, tol, hist, hist_cap);
 }
 
+// ---- the loop's launches, one function each: the solve calls these, and so does the LAB build's spmv_amd_pcg_stage (the
+// kernels on caller data, tests/test_pcg_stages_gpu.py). dinv is not read by the "none" instantiations. ----
+
+void launch_pcg_init(bool jac, size_t n, const double* b, const double* Ap, const double* dinv, double* r, double* p, double* partials) {
+    const dim3 grid(stream_grid(n)), block(kWave);
+    const int count = (int)grid.x;
+    if (jac)
+        hipLaunchKernelGGL(pcg_init_kernel<true>, grid, block, 0, kStream, n, b, Ap, dinv, r, p, partials, count);
+    else
+        hipLaunchKernelGGL(pcg_init_kernel<false>, grid, block, 0, kStream, n, b, Ap, nullptr, r, p, partials, count);
+}
+
+void launch_pcg_update_r(bool jac, size_t n, const PcgScalars* s, const double* Ap, const double* dinv, double* r, double* partials) {
+    const dim3 grid(stream_grid(n)), block(kWave);
+    const int count = (int)grid.x;
+    if (jac)
+        hipLaunchKernelGGL(pcg_update_r_kernel<true>, grid, block, 0, kStream, n, s, Ap, dinv, r, partials, count);
+    else
+        hipLaunchKernelGGL(pcg_update_r_kernel<false>, grid, block, 0, kStream, n, s, Ap, nullptr, r, partials, count);
+}
+
+void launch_pcg_update_xp(bool jac, size_t n, const PcgScalars* s, const double* r, const double* dinv, double* p, double* x) {
+    const dim3 grid(stream_grid(n)), block(kWave);
+    if (jac)
+        hipLaunchKernelGGL(pcg_update_xp_kernel<true>, grid, block, 0, kStream, n, s, r, dinv, p, x);
+    else
+        hipLaunchKernelGGL(pcg_update_xp_kernel<false>, grid, block, 0, kStream, n, s, r, nullptr, p, x);
+}
+
+// nv sums of `count` partials each and the scalar step `which` (0: two sums, 1: one, 2: two)
+void launch_pcg_reduce(const double* partials, int count, int nv, int which, double* stage, PcgScalars* s, double tol, double* hist,
+                       int hist_cap) {
+    int slice = 0, blocks = 0;
+    reduce_geometry(count, &slice, &blocks);
+    if (nv == 1)
+        hipLaunchKernelGGL(pcg_reduce_kernel<1>, dim3((unsigned)blocks), dim3(kReduceBlock), 0, kStream, partials, count, slice, blocks, stage,
+                           s, which, tol, hist, hist_cap);
+    else
+        hipLaunchKernelGGL(pcg_reduce_kernel<2>, dim3((unsigned)blocks), dim3(kReduceBlock), 0, kStream, partials, count, slice, blocks, stage,
+                           s, which, tol, hist, hist_cap);
+}
+
 // ---- workspace: kept between calls (like cg_solve_device's), released with it ----
 struct PcgWorkspace {
     int n = 0, device = -1;
@@ -487,18 +534,10 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
     upload(w.b, b, (size_t)n);
     upload(w.x, x, (size_t)n);
 
-    const dim3 grid(stream_grid((size_t)n)), block(kWave);
     StageTimers T(cfg.enable_detailed_timers != 0, kStream);
     bool op_failed = false;
     auto reduce = [&](int count, int nv, int which) {
-        int slice = 0, blocks = 0;
-        reduce_geometry(count, &slice, &blocks);
-        if (nv == 1)
-            hipLaunchKernelGGL(pcg_reduce_kernel<1>, dim3((unsigned)blocks), dim3(kReduceBlock), 0, kStream, w.partials, count, slice, blocks,
-                               w.stage, w.s, which, cfg.tolerance, w.hist, w.hist_cap);
-        else
-            hipLaunchKernelGGL(pcg_reduce_kernel<2>, dim3((unsigned)blocks), dim3(kReduceBlock), 0, kStream, w.partials, count, slice, blocks,
-                               w.stage, w.s, which, cfg.tolerance, w.hist, w.hist_cap);
+        launch_pcg_reduce(w.partials, count, nv, which, w.stage, w.s, cfg.tolerance, w.hist, w.hist_cap);
     };
     auto run_op = [&](const double* in, double* out) {
         if (op->run_device(in, out) != 0) {
@@ -510,10 +549,7 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
 
     T.total.begin(kStream);
     T.run(&T.t_spmv, [&] { run_op(w.x, w.Ap); });
-    if (jac)
-        T.run(&T.t_blas, [&] { hipLaunchKernelGGL(pcg_init_kernel<true>, grid, block, 0, kStream, (size_t)n, w.b, w.Ap, m->dinv, w.r, w.p, w.partials, vec_count); });
-    else
-        T.run(&T.t_blas, [&] { hipLaunchKernelGGL(pcg_init_kernel<false>, grid, block, 0, kStream, (size_t)n, w.b, w.Ap, nullptr, w.r, w.p, w.partials, vec_count); });
+    T.run(&T.t_blas, [&] { launch_pcg_init(jac, (size_t)n, w.b, w.Ap, m->dinv, w.r, w.p, w.partials); });
     T.run(&T.t_red, [&] { reduce(vec_count, 2, 0); });
     download(&h, w.s, 1);
     if (cfg.verbose >= 1) printf("[PCG-DEVICE] Initial residual: %e (preconditioner %s)\n", h.b_norm, jac ? "jacobi" : "none");
@@ -529,15 +565,9 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
         });
         if (op_failed) break;
         T.run(&T.t_red, [&] { reduce(pap_count, 1, 1); });
-        if (jac)
-            T.run(&T.t_blas, [&] { hipLaunchKernelGGL(pcg_update_r_kernel<true>, grid, block, 0, kStream, (size_t)n, w.s, w.Ap, m->dinv, w.r, w.partials, vec_count); });
-        else
-            T.run(&T.t_blas, [&] { hipLaunchKernelGGL(pcg_update_r_kernel<false>, grid, block, 0, kStream, (size_t)n, w.s, w.Ap, nullptr, w.r, w.partials, vec_count); });
+        T.run(&T.t_blas, [&] { launch_pcg_update_r(jac, (size_t)n, w.s, w.Ap, m->dinv, w.r, w.partials); });
         T.run(&T.t_red, [&] { reduce(vec_count, 2, 2); });
-        if (jac)
-            T.run(&T.t_blas, [&] { hipLaunchKernelGGL(pcg_update_xp_kernel<true>, grid, block, 0, kStream, (size_t)n, w.s, w.r, m->dinv, w.p, w.x); });
-        else
-            T.run(&T.t_blas, [&] { hipLaunchKernelGGL(pcg_update_xp_kernel<false>, grid, block, 0, kStream, (size_t)n, w.s, w.r, nullptr, w.p, w.x); });
+        T.run(&T.t_blas, [&] { launch_pcg_update_xp(jac, (size_t)n, w.s, w.r, m->dinv, w.p, w.x); });
         download(&h, w.s, 1);  // synchronises: the stopping test
         if (cfg.verbose >= 2)
             printf("[PCG-DEVICE] Iter %3d: residual = %e (rel = %e)\n", h.iterations, h.residual, h.residual / h.b_norm);
@@ -572,3 +602,107 @@ extern "C" int spmv_amd_pcg_last_history(double* out, int cap) {
 }
 
 extern "C" void spmv_amd_pcg_release_workspace(void) { spmv_amd::release_cg_workspace(); }
+
+#ifdef SPMV_AMD_LAB
+// ---- the loop's kernels one stage at a time on caller data (include/spmv_amd/lab.h; tests/test_pcg_stages_gpu.py) ----
+static_assert(sizeof(SpmvAmdPcgScalars) == sizeof(PcgScalars) && offsetof(SpmvAmdPcgScalars, b_norm) == offsetof(PcgScalars, b_norm) &&
+                  offsetof(SpmvAmdPcgScalars, iterations) == offsetof(PcgScalars, iterations) &&
+                  offsetof(SpmvAmdPcgScalars, skip_update) == offsetof(PcgScalars, skip_update),
+              "lab.h's scalar record is the device record, field for field");
+
+namespace {
+bool stage_fail(const char* stage, const char* what) {
+    fprintf(stderr, "[PCG] stage '%s': %s: refused\n", stage ? stage : "(null)", what);
+    return false;
+}
+// a vector the streaming kernels read or write in 16-byte pairs
+bool stage_vector(const char* stage, const char* name, const void* p) {
+    char what[64];
+    if (p == nullptr) {
+        snprintf(what, sizeof what, "%s is null", name);
+        return stage_fail(stage, what);
+    }
+    if (((uintptr_t)p & 15) != 0) {
+        snprintf(what, sizeof what, "%s is not 16-byte aligned", name);
+        return stage_fail(stage, what);
+    }
+    return true;
+}
+// an array of doubles read or written one at a time
+bool stage_array(const char* stage, const char* name, const void* p) {
+    char what[64];
+    if (p == nullptr) {
+        snprintf(what, sizeof what, "%s is null", name);
+        return stage_fail(stage, what);
+    }
+    if (((uintptr_t)p & 7) != 0) {
+        snprintf(what, sizeof what, "%s is not 8-byte aligned", name);
+        return stage_fail(stage, what);
+    }
+    return true;
+}
+}  // namespace
+
+extern "C" int spmv_amd_pcg_stage(const char* stage, const char* kind, SpmvAmdPcgStageArgs* a, SpmvAmdPcgScalars* scalars) {
+    // argument checks: all before the first HIP call
+    enum { kInit, kUpdateR, kUpdateXp, kReduce } st;
+    if (stage == nullptr) return stage_fail(stage, "no stage named (init, update_r, update_xp, reduce)"), 1;
+    if (!strcmp(stage, "init")) st = kInit;
+    else if (!strcmp(stage, "update_r")) st = kUpdateR;
+    else if (!strcmp(stage, "update_xp")) st = kUpdateXp;
+    else if (!strcmp(stage, "reduce")) st = kReduce;
+    else return stage_fail(stage, "unknown stage (init, update_r, update_xp, reduce)"), 1;
+    if (a == nullptr) return stage_fail(stage, "null arguments"), 1;
+    bool jac = false;
+    if (st != kReduce) {
+        const int k = kind_of(kind);
+        if (k < 0) return stage_fail(stage, "unknown preconditioner kind (none, jacobi)"), 1;
+        jac = k == kJacobi;
+        if (a->n < 1 || a->n > (size_t)INT_MAX) return stage_fail(stage, "n < 1 or beyond the solver's int rows"), 1;
+        if (jac && !stage_vector(stage, "dinv", a->dinv)) return 1;
+    }
+    if (st != kInit && scalars == nullptr) return stage_fail(stage, "null scalar record"), 1;
+    if (st == kInit) {
+        if (!stage_vector(stage, "b", a->b) || !stage_vector(stage, "Ap", a->Ap) || !stage_vector(stage, "r", a->r) ||
+            !stage_vector(stage, "p", a->p) || !stage_array(stage, "partials", a->partials))
+            return 1;
+    } else if (st == kUpdateR) {
+        if (!stage_vector(stage, "Ap", a->Ap) || !stage_vector(stage, "r", a->r) || !stage_array(stage, "partials", a->partials)) return 1;
+    } else if (st == kUpdateXp) {
+        if (!stage_vector(stage, "r", a->r) || !stage_vector(stage, "p", a->p) || !stage_vector(stage, "x", a->x)) return 1;
+    } else {
+        if (a->count < 1) return stage_fail(stage, "count < 1"), 1;
+        if (a->which < 0 || a->which > 2) return stage_fail(stage, "which is not 0, 1 or 2"), 1;
+        if (a->hist_cap < 0) return stage_fail(stage, "hist_cap < 0"), 1;
+        if (!stage_array(stage, "partials", a->partials)) return 1;
+        if (a->hist_cap > 0 && !stage_array(stage, "hist", a->hist)) return 1;
+    }
+
+    PcgScalars h{};
+    if (scalars != nullptr) memcpy(&h, scalars, sizeof h);
+    PcgScalars* d_s = device_alloc<PcgScalars>(1);
+    upload(d_s, &h, 1);
+    double* stage_buf = nullptr;
+    if (st == kInit) {
+        launch_pcg_init(jac, a->n, a->b, a->Ap, a->dinv, a->r, a->p, a->partials);
+        a->count = (int)stream_grid(a->n);
+    } else if (st == kUpdateR) {
+        launch_pcg_update_r(jac, a->n, d_s, a->Ap, a->dinv, a->r, a->partials);
+        a->count = (int)stream_grid(a->n);
+    } else if (st == kUpdateXp) {
+        launch_pcg_update_xp(jac, a->n, d_s, a->r, a->dinv, a->p, a->x);
+    } else {
+        stage_buf = reduce_scratch_alloc();
+        launch_pcg_reduce(a->partials, a->count, a->which == 1 ? 1 : 2, a->which, stage_buf, d_s, a->tol, a->hist, a->hist_cap);
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    if (st == kReduce) {
+        download(&h, d_s, 1);
+        memcpy(scalars, &h, sizeof h);
+    }
+    device_release(stage_buf);
+    device_release(d_s);
+    return 0;
+}
+#endif  // SPMV_AMD_LAB

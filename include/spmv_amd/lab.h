@@ -39,6 +39,53 @@ SpmvAmdCgSlab* spmv_amd_cg_slab_create_stencil5_as(int n, int as_rank, int as_wo
  * unknown name. */
 int spmv_amd_cg_slab_set_option(SpmvAmdCgSlab* s, const char* name, long long value);
 
+/* The device scalars of one preconditioned solve (csrc/pcg.hip keeps the same record on the device). */
+typedef struct SpmvAmdPcgScalars {
+    double rz;        /* r.z of the current residual */
+    double pAp, alpha, beta;
+    double b_norm;    /* ||r0|| */
+    double residual;  /* ||r_k|| */
+    int iterations;
+    int converged;    /* stopping test met */
+    int breakdown;    /* pAp or r.z' zero or not finite: stopped, not converged */
+    int skip_update;  /* this iteration's pAp broke down: r and x stay as they are */
+} SpmvAmdPcgScalars;
+
+/* Device pointers and sizes of one spmv_amd_pcg_stage call; a stage reads only the fields listed for it. */
+typedef struct SpmvAmdPcgStageArgs {
+    size_t n;            /* rows (init, update_r, update_xp) */
+    const double* b;     /* init */
+    const double* Ap;    /* init, update_r */
+    const double* dinv;  /* kind "jacobi": init, update_r, update_xp; kind "none": not looked at */
+    double* r;           /* init: out; update_r: in and out; update_xp: in */
+    double* p;           /* init: out; update_xp: in and out */
+    double* x;           /* update_xp: in and out */
+    double* partials;    /* init, update_r: out, value v of workgroup g at [v * count + g]; reduce: in, the same layout */
+    int count;           /* init, update_r: out, the workgroups of the launch = partials per value ((n / 2 + 63) / 64, at least 1:
+                            the buffer holds 2 * count doubles); reduce: in */
+    int which;           /* reduce: the scalar step, 0 = initial r.r / r.z, 1 = p.Ap (ONE value), 2 = r.r / r.z' */
+    double tol;          /* reduce, which = 2 */
+    double* hist;        /* reduce: residual history, hist_cap doubles (may be null when hist_cap is 0) */
+    int hist_cap;
+} SpmvAmdPcgStageArgs;
+
+/* The preconditioned solver's own kernels (csrc/pcg.hip), one stage per call on the caller's device data -- the launches
+ * spmv_amd_pcg_solve_device makes, through the functions it makes them with: same kernels, grid, block size, reduction geometry
+ * and stage buffer. The model is spmv_amd_cg_fused_step (api.h); tests/test_pcg_stages_gpu.py holds each stage against the
+ * oracle. Every call synchronises. stage (kind = "jacobi" or "none"; "reduce" does not look at it):
+ *   "init"       r = b - Ap, z = dinv r ("none": z = r), p = z, the partials of r.r (value 0) and r.z (value 1); sets a->count
+ *   "update_r"   r = fma(-alpha, Ap, r) unless scalars->skip_update, z = dinv r in registers, the partials of r.r and r.z;
+ *                sets a->count
+ *   "update_xp"  nothing when scalars->skip_update; else x = fma(alpha, p, x) and, unless scalars->converged or ->breakdown,
+ *                p = fma(beta, p, dinv r) (r and dinv are not read otherwise)
+ *   "reduce"     the sums of a->count partials of one (which = 1) or two values, then the scalar step `which` on *scalars (read
+ *                and written, all ten fields) with a->tol, a->hist and a->hist_cap
+ * Vectors are accessed in 16-byte pairs. Refused before any HIP call, with a sentence on stderr and a non-zero return: an
+ * unknown stage or kind, null arguments, n < 1, count < 1, which outside 0..2, hist_cap < 0, a null pointer the stage needs
+ * (scalars: every stage but "init"), a vector that is not 16-byte aligned, partials or hist that are not 8-byte aligned.
+ * Returns 0 otherwise. */
+int spmv_amd_pcg_stage(const char* stage, const char* kind, SpmvAmdPcgStageArgs* a, SpmvAmdPcgScalars* scalars);
+
 #ifdef __cplusplus
 }
 #endif

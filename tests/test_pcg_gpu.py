@@ -1,7 +1,11 @@
 """Jacobi-preconditioned CG (spmv_amd_pcg_solve_device, csrc/pcg.hip) on the GPU: the value it adds on a matrix whose diagonal
 varies, bit-exact inverse diagonals from all four operators, the golden anchors with kinds none / jacobi, refusals, breakdown,
-coexistence with the other CG entry points, the Matrix Market path and the application's --precond."""
+coexistence with the other CG entry points, the Matrix Market path and the application's --precond; then the solves away from
+x0 = 0: non-zero first guesses on odd, negative-definite and two-stage-reduction systems against the restatement AND the true
+residual in long double, tiny systems, the stopping rules and statistics, the detailed timers, non-finite and zero right-hand
+sides, and the workspace across sizes and operators (tests/test_pcg_stages_gpu.py has the kernels one by one)."""
 import ctypes as C
+import functools
 import json
 import os
 import subprocess
@@ -10,8 +14,9 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import conftest
 from conftest import GOLDEN, ROOT
-from pcg_restatement import diagonal, entries_of, hist_err, pcg, scaled_stencil5
+from pcg_restatement import TABLE, diagonal, entries_of, hist_err, pcg, scaled_stencil5, stencil5, table_system, true_residual_norm
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
@@ -297,3 +302,215 @@ def test_application_precond_flag(B):
     plain = subprocess.run([exe, "--stencil=512"], capture_output=True, text=True, timeout=300)
     assert plain.returncode == 0 and "Preconditioner" not in plain.stdout
     assert f"--- Results for stencil5-csr ---\nConverged: YES in {gold['iterations']} iterations" in plain.stdout
+
+
+# ---------------------------------------------------------------- away from x0 = 0 (pcg_restatement.TABLE; tests/test_pcg_host.py
+# holds every row of it in two roundings of the restatement)
+
+@functools.lru_cache(maxsize=None)
+def _system(name):
+    A, b, x0 = table_system(name)
+    return A, b, x0, entries_of(A)
+
+
+@functools.lru_cache(maxsize=None)
+def _restated(name, kind, tol, max_iters):
+    """The restatement's x, history, iterations, verdict on a table system, and its own g (see _true_residual_gap)."""
+    A, b, x0, e = _system(name)
+    x, h, it, conv = pcg(A, b, x0, 1.0 / diagonal(A) if kind == "jacobi" else None, tol, max_iters)
+    return x, h, it, conv, _true_residual_gap(e, b, x, h)
+
+
+def _true_residual_gap(entries, b, x, h):
+    """g = | ||b - A x|| - h[-1] | / h[-1], the true residual accumulated in long double from the COO entries."""
+    return abs(true_residual_norm(entries, b, x) - h[-1]) / h[-1]
+
+
+def _foreign(B, op):
+    """A caller's own operator table around `op`'s device product (the library does not know its matrix)."""
+    own = B.SpmvOperator()
+    own.name = b"mine"
+    own.run_device = B.RUN_DEVICE_FN(lambda dx, dy: op.op.contents.run_device(dx, dy))
+    return type("Foreign", (), {"op": C.pointer(own), "_keep": own})()
+
+
+@pytest.mark.parametrize("row", range(len(TABLE)), ids=[f"{r[0]}-{r[1]}-{r[2]:g}-{r[3]}" for r in TABLE])
+def test_nonzero_first_guess_against_restatement_and_true_residual(B, row):
+    """x0 = standard_normal on every system of the table: iterations equal to the restatement's, history within 1e-10
+    (conftest.hist_err), x within 1e-10 -- `jacobi` through all four operators, `none` through a fused (stencil5-csr) and an unfused
+    (ellpack) one, the 127^2 system also through a caller's operator table with a caller's diagonal. A converged solve is also
+    held to something that shares no algebra with the restatement: g = | ||b - A x|| - h[-1] | / h[-1] in long double must be
+    at most 100 x the restatement's own g on the same case (floor 1e-12): the factor covers another summation order, a lost x0
+    or a wrong alpha in the x update misses it by ten orders of magnitude. x0 = 0 must give another h[0] (x0 is not ignored on
+    both sides).
+    Largest GPU g / restatement g seen on the MI355X: 6.3 (601^2 unscaled, jacobi, tol 1e-6, cusparse-csr: 1.5e-13 against
+    2.3e-14); 55 of the 60 converged solves lie between 0.05 and 3.5."""
+    name, kind, tol, max_iters, iterations = TABLE[row]
+    A, b, x0, e = _system(name)
+    xo, ho, ito, conv, g_ref = _restated(name, kind, tol, max_iters)
+    assert ito == iterations and conv == (max_iters == 1000)
+    rows, n = A.shape[0], int(round(np.sqrt(A.shape[0])))
+    m = B.HostMatrix(e, rows, rows, n)
+    for mode in OPERATORS if kind == "jacobi" else ("stencil5-csr", "ellpack"):
+        B.lib().spmv_amd_reset_host_matrices()
+        op = B.Operator(mode)
+        assert op.init(m) == 0, mode
+        solvers = [(mode, op, B.Precond(op, kind))]
+        if name == "scaled127" and kind == "jacobi" and mode == "cusparse-csr":
+            solvers.append(("caller's table", _foreign(B, op), B.Precond.from_diagonal(diagonal(A))))
+        for label, who, pc in solvers:
+            x, h, st = B.pcg_solve_device(who, m, pc, b, x0, max_iters=max_iters, tol=tol)
+            case = (name, kind, tol, label)
+            assert st.iterations == ito and st.converged == int(conv) and len(h) == ito + 1, (case, st.iterations)
+            assert conftest.hist_err(h, ho) < TOL and _close(x, xo), (case, conftest.hist_err(h, ho))
+            if conv:
+                g = _true_residual_gap(e, b, x, h)
+                print(f"{case}: g = {g:.3e}, the restatement's {g_ref:.3e}, ratio {g / g_ref:.3f}")
+                assert g <= max(100.0 * g_ref, 1e-12), (case, g, g_ref)
+            _, h0, _ = B.pcg_solve_device(who, m, pc, b, np.zeros(rows), max_iters=0, tol=tol)
+            assert len(h0) == 1 and abs(h0[0] - h[0]) > 1e-3 * h[0], case
+            pc.destroy()
+        op.free()
+
+
+def _dense_entries(B, M):
+    M = np.atleast_2d(np.asarray(M, dtype=np.float64))
+    t = [(i, j, M[i, j]) for i in range(M.shape[0]) for j in range(M.shape[1]) if M[i, j] != 0.0]
+    e = np.zeros(len(t), dtype=B.ENTRY_DTYPE)
+    for k, v in enumerate(t):
+        e[k] = v
+    return e
+
+
+def test_tiny_systems_terminate_exactly(B):
+    """1 x 1 ([[3]], b = 2, x0 = 0.5: one iteration, x = 2/3), 2 x 2 ([[4, 1], [1, 3]], b = (1, 2), x0 = (2, 1): two, x = (1/11,
+    7/11)) and the 3 x 3 grid stencil from a random x0: the last residual is rounding noise, so x, the iteration count and the
+    history through conftest.hist_err (noise against noise is not compared relatively)."""
+    rng = np.random.default_rng(33)
+    cases = [(np.array([[3.0]]), np.array([2.0]), np.array([0.5]), -1, 1, np.array([2.0 / 3.0]), ("cusparse-csr", "ellpack")),
+             (np.array([[4.0, 1.0], [1.0, 3.0]]), np.array([1.0, 2.0]), np.array([2.0, 1.0]), -1, 2, np.array([1.0 / 11.0, 7.0 / 11.0]),
+              ("cusparse-csr", "ellpack")),
+             (stencil5(3).toarray(), rng.standard_normal(9), rng.standard_normal(9), 3, None, None, ("cusparse-csr", "ellpack", "stencil5-csr"))]
+    for M, b, x0, grid, iterations, exact, modes in cases:
+        A = sp.csr_matrix(M)
+        rows = A.shape[0]
+        m = B.HostMatrix(_dense_entries(B, M), rows, rows, grid)
+        for kind in ("none", "jacobi"):
+            xo, ho, ito, conv = pcg(A, b, x0, 1.0 / diagonal(A) if kind == "jacobi" else None)
+            assert conv and (iterations is None or ito == iterations), (rows, kind, ito)
+            if exact is not None:
+                assert _close(xo, exact)
+            for mode in modes:
+                B.lib().spmv_amd_reset_host_matrices()
+                op = B.Operator(mode)
+                assert op.init(m) == 0
+                pc = B.Precond(op, kind)
+                x, h, st = B.pcg_solve_device(op, m, pc, b, x0)
+                case = (rows, kind, mode)
+                assert st.converged == 1 and st.iterations == ito and len(h) == ito + 1, (case, st.iterations)
+                assert _close(x, xo) and conftest.hist_err(h, ho) < TOL, case
+                if exact is not None:
+                    assert _close(x, exact), case
+                pc.destroy()
+                op.free()
+
+
+def _jacobi_127(B, mode="stencil5-csr"):
+    A, b, x0, e = _system("scaled127")
+    B.lib().spmv_amd_reset_host_matrices()
+    m = B.HostMatrix(e, A.shape[0], A.shape[0], 127)
+    op = B.Operator(mode)
+    assert op.init(m) == 0
+    return A, b, x0, m, op, B.Precond(op, "jacobi")
+
+
+def test_stopping_rules_and_statistics(B, capfd):
+    """max_iters = 0 and 5, a full solve after a capped one and a capped one after a full one (the history is the last solve's),
+    residual_norm / converged by the reference's rule (fill_device_stats: ||r0|| unless the device converged or verbose >= 2), and
+    tolerances other than 1e-6 -- on the 127^2 jacobi system of the table."""
+    A, b, x0, m, op, pc = _jacobi_127(B)
+    xo, ho, ito, _, _ = _restated("scaled127", "jacobi", 1e-6, 1000)
+    x, h, st = B.pcg_solve_device(op, m, pc, b, x0, max_iters=0)
+    assert st.iterations == 0 and st.converged == 0 and len(h) == 1 and np.array_equal(x, x0)
+    assert abs(h[0] - ho[0]) <= TOL * ho[0] and st.residual_norm == h[0]
+    x5, h5, st5 = B.pcg_solve_device(op, m, pc, b, x0, max_iters=5)
+    assert st5.iterations == 5 and len(h5) == 6 and st5.converged == 0 and st5.residual_norm == h5[0]
+    xf, hf, stf = B.pcg_solve_device(op, m, pc, b, x0)
+    assert stf.iterations == ito and stf.converged == 1 and len(hf) == ito + 1 and stf.residual_norm == hf[-1]
+    assert np.array_equal(h5, hf[:6])  # bit for bit
+    assert conftest.hist_err(hf, ho) < TOL and _close(xf, xo)
+    x5b, h5b, st5b = B.pcg_solve_device(op, m, pc, b, x0, max_iters=5, verbose=2)
+    capfd.readouterr()  # the per-iteration lines
+    assert len(h5b) == 6 and np.array_equal(h5b, h5) and np.array_equal(x5b, x5)  # not the earlier solve's 19 entries
+    assert st5b.iterations == 5 and st5b.residual_norm == h5b[5] and st5b.converged == 0
+    assert not _close(x5, xo)
+    for tol in (1e-10, 1e-2):
+        xt, ht, it, conv = pcg(A, b, x0, 1.0 / diagonal(A), tol)
+        assert conv and (abs(ht[-1] / ht[0] / tol - 1.0) > 1e-6)
+        x, h, st = B.pcg_solve_device(op, m, pc, b, x0, tol=tol)
+        assert st.iterations == it and st.converged == 1 and len(h) == it + 1, (tol, st.iterations, it)
+        assert conftest.hist_err(h, ht) < TOL and _close(x, xt) and st.residual_norm == h[-1], tol
+        assert h[-1] / h[0] < tol <= h[-2] / h[0]
+    pc.destroy()
+    op.free()
+
+
+def test_detailed_timers_change_no_bit(B):
+    """enable_detailed_timers = 1 (events between the launches): x and history bit-identical to the plain solve, each of the
+    three stage times > 0 and their sum <= the total; the plain solve reports the three as 0."""
+    for mode in ("stencil5-csr", "ellpack"):  # fused p.Ap, and run_device + the dot pass
+        _, b, x0, m, op, pc = _jacobi_127(B, mode)
+        x, h, st = B.pcg_solve_device(op, m, pc, b, x0)
+        xt, ht, stt = B.pcg_solve_device(op, m, pc, b, x0, timers=1)
+        assert np.array_equal(xt, x) and np.array_equal(ht, h) and stt.iterations == st.iterations and stt.converged == 1, mode
+        assert st.time_spmv_ms == 0.0 and st.time_blas1_ms == 0.0 and st.time_reductions_ms == 0.0 and st.time_total_ms > 0.0
+        assert stt.time_spmv_ms > 0.0 and stt.time_blas1_ms > 0.0 and stt.time_reductions_ms > 0.0
+        assert stt.time_spmv_ms + stt.time_blas1_ms + stt.time_reductions_ms <= stt.time_total_ms, mode
+        pc.destroy()
+        op.free()
+
+
+def test_non_finite_and_zero_right_hand_sides(B):
+    """Ordinary values through the ordinary kernels: b with one inf (p.Ap is not finite) and b = 0 with x0 = 0 (p.Ap = 0): the first
+    iteration breaks down -- return 0, converged = 0, iterations = 1, x bit-equal x0 (api.h: "stops the solve in that iteration
+    with converged = 0 and x finite")."""
+    for mode in ("stencil5-csr", "ellpack"):
+        A, b, x0, m, op, _pc = _jacobi_127(B, mode)
+        _pc.destroy()
+        rows = A.shape[0]
+        b_inf = b.copy()
+        b_inf[rows // 2 + 3] = np.inf
+        for kind in ("jacobi", "none"):
+            pc = B.Precond(op, kind)
+            for rhs, start in ((b_inf, x0), (b_inf, np.zeros(rows)), (np.zeros(rows), np.zeros(rows))):
+                x, h, st = B.pcg_solve_device(op, m, pc, rhs, start)
+                case = (mode, kind, float(rhs[rows // 2 + 3]))
+                assert st.iterations == 1 and st.converged == 0 and len(h) == 2, (case, st.iterations, st.converged)
+                assert np.array_equal(x, start) and np.all(np.isfinite(x)), case
+            # the solver is as good as before afterwards
+            x, h, st = B.pcg_solve_device(op, m, pc, b, x0, max_iters=5)
+            assert st.iterations == 5 and np.all(np.isfinite(h)) and np.all(np.isfinite(x)), (mode, kind)
+            pc.destroy()
+        op.free()
+
+
+def test_workspace_across_sizes_and_operators(B):
+    """600^2 on stencil5-csr (fused p.Ap, 2813 partials), 127^2 on ellpack (dot pass) and 600^2 on stencil5-csr again in one
+    process, no free() in between: the workspace is re-made at each change of size, the first and the third solve agree bit for
+    bit, and the one in the middle is the restatement's."""
+    A6, b6, x06, e6 = _system("scaled600")
+    A1, b1, x01, e1 = _system("scaled127")
+    B.lib().spmv_amd_reset_host_matrices()
+    m6, m1 = B.HostMatrix(e6, A6.shape[0], A6.shape[0], 600), B.HostMatrix(e1, A1.shape[0], A1.shape[0], 127)
+    big, small = B.Operator("stencil5-csr"), B.Operator("ellpack")
+    assert big.init(m6) == 0 and small.init(m1) == 0
+    pc6, pc1 = B.Precond(big, "jacobi"), B.Precond(small, "jacobi")
+    first = B.pcg_solve_device(big, m6, pc6, b6, x06)
+    middle = B.pcg_solve_device(small, m1, pc1, b1, x01)
+    third = B.pcg_solve_device(big, m6, pc6, b6, x06)
+    assert np.array_equal(first[0], third[0]) and np.array_equal(first[1], third[1]) and first[2].iterations == third[2].iterations
+    for (x, h, st), name in ((first, "scaled600"), (middle, "scaled127")):
+        xo, ho, ito, _, _ = _restated(name, "jacobi", 1e-6, 1000)
+        assert st.converged == 1 and st.iterations == ito and conftest.hist_err(h, ho) < TOL and _close(x, xo), name
+    pc6.destroy(), pc1.destroy()
+    big.free(), small.free()
