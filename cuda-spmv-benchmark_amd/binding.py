@@ -111,7 +111,7 @@ DECLARED_SYMBOLS = [
     "spmv_amd_comm_mailbox_disable", "spmv_amd_comm_mailbox_ready",
     "spmv_amd_cg_slab_create", "spmv_amd_cg_slab_create_stencil5", "spmv_amd_cg_slab_set_vectors", "spmv_amd_cg_slab_solve",
     "spmv_amd_cg_slab_gather", "spmv_amd_cg_slab_loop_shape", "spmv_amd_cg_slab_history", "spmv_amd_cg_slab_spmv", "spmv_amd_cg_slab_info",
-    "spmv_amd_cg_slab_time_spmv", "spmv_amd_cg_slab_set_timeline", "spmv_amd_operator_placement", "spmv_amd_cg_slab_placement", "spmv_amd_cg_slab_tile_runs", "spmv_amd_cg_slab_setup_ms", "spmv_amd_cg_slab_coefficient_form","spmv_amd_cg_slab_spmv_launch_ms",  "spmv_amd_cg_release_workspace", "spmv_amd_cg_slab_timeline_names", "spmv_amd_cg_slab_timeline", "spmv_amd_cg_slab_variant", "spmv_amd_cg_slab_destroy", "spmv_amd_version", "spmv_amd_write_stencil5_values",
+    "spmv_amd_cg_slab_time_spmv", "spmv_amd_cg_slab_set_timeline", "spmv_amd_operator_placement", "spmv_amd_cg_slab_placement", "spmv_amd_cg_slab_tile_runs", "spmv_amd_cg_slab_setup_ms", "spmv_amd_cg_slab_coefficient_form", "spmv_amd_cg_slab_uniform_tiles", "spmv_amd_cg_slab_spmv_launch_ms",  "spmv_amd_cg_release_workspace", "spmv_amd_cg_slab_timeline_names", "spmv_amd_cg_slab_timeline", "spmv_amd_cg_slab_variant", "spmv_amd_cg_slab_destroy", "spmv_amd_version", "spmv_amd_write_stencil5_values",
     "spmv_amd_blas1_axpy", "spmv_amd_blas1_axpby", "spmv_amd_blas1_axpy_dev", "spmv_amd_blas1_update_p_dev", "spmv_amd_blas1_dot",
     "spmv_amd_cg_fused_step",
     "spmv_amd_spmm_device", "spmv_amd_spmm_variant", "spmv_amd_block_to_device", "spmv_amd_block_to_host",
@@ -120,7 +120,7 @@ DECLARED_SYMBOLS = [
     "spmv_amd_precond_inverse_diagonal", "spmv_amd_pcg_solve_device", "spmv_amd_pcg_last_history", "spmv_amd_pcg_release_workspace",
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
-LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_pcg_stage"]
+LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_pcg_stage"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
 DECLARED_CXX_SYMBOLS = [
     "SPMV_CSR", "SPMV_STENCIL5_CSR", "SPMV_STENCIL_HALO_MGPU", "SPMV_ELLPACK", "SPMV_STENCIL5_ELLPACK",
@@ -211,6 +211,8 @@ def lib():
         L.spmv_amd_cg_slab_create_stencil5_as.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.spmv_amd_cg_slab_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
         L.spmv_amd_cg_slab_set_option.restype = C.c_int
+        L.spmv_amd_cg_slab_tile_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong]
+        L.spmv_amd_cg_slab_tile_classes.restype = C.c_longlong
         L.spmv_amd_pcg_stage.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PcgStageArgs), C.POINTER(PcgScalars)]
         L.spmv_amd_pcg_stage.restype = C.c_int
     L.spmv_amd_cg_slab_create.restype = C.c_void_p
@@ -233,6 +235,8 @@ def lib():
     L.spmv_amd_cg_slab_variant.argtypes = [C.c_void_p]
     L.spmv_amd_cg_slab_coefficient_form.argtypes = [C.c_void_p]
     L.spmv_amd_cg_slab_coefficient_form.restype = C.c_int
+    L.spmv_amd_cg_slab_uniform_tiles.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.spmv_amd_cg_slab_uniform_tiles.restype = C.c_int
     L.spmv_amd_cg_slab_loop_shape.restype = C.c_char_p
     L.spmv_amd_cg_slab_loop_shape.argtypes = [C.c_void_p]
     L.load_matrix_market.argtypes = [C.c_char_p, C.POINTER(MatrixData)]
@@ -839,6 +843,23 @@ class CgSlab:
     def coefficient_form(self):
         """0: the SpMV streams the CSR values; 1: the symmetric [C, E] + S planes (include/spmv_amd/api.h)."""
         return int(lib().spmv_amd_cg_slab_coefficient_form(self.h))
+
+    def uniform_tiles(self):
+        """(uniform, total): the row-lds tiles of the slab's plane-evaluated grid rows that load no coefficient, and all of them."""
+        u, t = C.c_longlong(), C.c_longlong()
+        lib().spmv_amd_cg_slab_uniform_tiles(self.h, C.byref(u), C.byref(t))
+        return int(u.value), int(t.value)
+
+    def tile_classes(self):
+        """The tile class map as creation wrote it (LAB build only): uint8 [local grid rows, tiles per grid row], or None."""
+        if not is_lab():
+            raise RuntimeError("the tile class map is read through the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        count = int(lib().spmv_amd_cg_slab_tile_classes(self.h, None, 0))
+        if count == 0:
+            return None
+        out = np.zeros(count, dtype=np.uint8)
+        lib().spmv_amd_cg_slab_tile_classes(self.h, out.ctypes.data, count)
+        return out
 
     def loop_shape(self):
         """"single rank" | "pipeline ..." | "plain: <who decided>" (include/spmv_amd/api.h)."""

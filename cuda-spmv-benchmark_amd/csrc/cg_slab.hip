@@ -123,6 +123,14 @@ struct SpmvAmdCgSlab {
     size_t planes_doubles = 0, planes_s_offset = 0;  // the allocation's length; where the S plane's local part starts
     SymPlanes planes;
     bool planes_on = false;
+    // Tile classes (kernels.hpp, SymPlanes; classify_tiles): one byte per row-lds tile of the slab, 1 where every coefficient the
+    // tile multiplies equals the slab-wide quintuple bit for bit -- such a tile loads no coefficient. Written once at creation from
+    // the CSR values; nothing can alter the matrix of a slab afterwards. The planes stay allocated (class-0 tiles, A/B options).
+    unsigned char* tile_classes = nullptr;
+    size_t tile_class_count = 0;                  // local grid rows x tiles per grid row
+    long long tiles_uniform = 0, tiles_total = 0; // of the tiles of the grid rows that are evaluated from the planes
+    double quintuple[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // W, C, E, N, S
+    bool stream_everywhere = false;  // LAB option: the kernel ignores the map and streams the planes on every tile
     const SymPlanes* sym() const { return planes_on ? &planes : nullptr; }
     // place_coefficients: {0, candidates timed, SpMV ms before, SpMV ms kept}
     std::vector<double> placement;
@@ -281,7 +289,14 @@ void adopt_operator(SpmvAmdCgSlab* s, SpmvOperator* op) {
 void place_coefficients(SpmvAmdCgSlab* s);  // below
 void tune_tile_runs(SpmvAmdCgSlab* s);
 
-SymPlanes plane_view(const SpmvAmdCgSlab* s, const double* base) { return SymPlanes{base, base + s->planes_s_offset}; }
+SymPlanes plane_view(const SpmvAmdCgSlab* s, const double* base) {
+    SymPlanes v;
+    v.ce = base;
+    v.s = base + s->planes_s_offset;
+    v.cls = s->stream_everywhere ? nullptr : s->tile_classes;
+    v.w = s->quintuple[0], v.c = s->quintuple[1], v.e = s->quintuple[2], v.n = s->quintuple[3], v.s5 = s->quintuple[4];
+    return v;
+}
 
 // A slab whose launches can all be row-lds launches (whole grid rows of a grid that takes row-lds) and that owns its matrix:
 // worth reserving the symmetric planes for before the direction ring takes what is free. Whether it keeps them is decided once
@@ -290,6 +305,41 @@ bool may_take_planes(const SpmvAmdCgSlab* s) {
     const int n = s->grid;
     return s->op == nullptr && n >= 2 && n >= s->shape.knobs.rowlds_min_grid && s->n_local > 0 && s->n_local % n == 0 &&
            s->row_offset % n == 0;
+}
+
+// The tile class map of a slab that keeps the planes. The quintuple is the CSR row of one fully interior grid point near the
+// slab's middle: a bad pick costs speed, never correctness -- every tile is compared against it. A slab without a grid row that is
+// evaluated from the planes (or a grid of fewer than three columns) has no map.
+void classify_tiles(SpmvAmdCgSlab* s) {
+    const int n = s->grid;
+    const int gfirst = s->row_offset / n, rows = s->n_local / n;
+    const int lo = std::max(gfirst, 1), hi = std::min(gfirst + rows, n - 1);  // global grid rows [lo, hi) take the planes
+    if (hi <= lo || n < 3) return;
+    const int col_tiles = rowlds_col_tiles(n);
+    s->tiles_total = (long long)(hi - lo) * col_tiles;
+    const long long lr = (long long)(lo + (hi - lo) / 2 - gfirst) * n + n / 2;
+    int first = 0;
+    HIP_CHECK(hipMemcpy(&first, s->A.view.row_ptr + lr, sizeof(int), hipMemcpyDeviceToHost));
+    double row[5];  // [N, W, C, E, S]
+    HIP_CHECK(hipMemcpy(row, s->A.view.values + first, sizeof(row), hipMemcpyDeviceToHost));
+    const double q[5] = {row[1], row[2], row[3], row[0], row[4]};
+    memcpy(s->quintuple, q, sizeof(q));
+    s->tile_class_count = (size_t)rows * col_tiles;
+    const size_t bytes = s->tile_class_count;
+    s->tile_classes = device_try_alloc<unsigned char>(bytes);
+    if (s->tile_classes == nullptr) {
+        s->tile_class_count = 0;
+        return;
+    }
+    unsigned long long* d_count = device_alloc<unsigned long long>(1);
+    HIP_CHECK(hipMemsetAsync(s->tile_classes, 0, bytes, s->compute));
+    HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s->compute));
+    launch_classify_tiles(s->A.view, q, s->tile_classes, d_count, s->compute);
+    unsigned long long h_count = 0;
+    HIP_CHECK(hipMemcpyAsync(&h_count, d_count, sizeof(h_count), hipMemcpyDeviceToHost, s->compute));
+    HIP_CHECK(hipStreamSynchronize(s->compute));
+    device_release(d_count);
+    s->tiles_uniform = (long long)h_count;
 }
 
 // Fills the reserved planes from the verified CSR and checks them bit for bit (launch_verify_sym_planes); any mismatch, an
@@ -312,6 +362,9 @@ void settle_planes(SpmvAmdCgSlab* s) {
     if (!keep) {
         device_release(s->planes_alloc);
         s->planes = SymPlanes{};
+    } else {
+        classify_tiles(s);
+        s->planes = plane_view(s, s->planes_alloc);
     }
     s->planes_on = keep;
 }
@@ -502,6 +555,10 @@ void place_coefficients(SpmvAmdCgSlab* s) {
     const size_t nl = (size_t)s->n_local;
     if (s->op != nullptr || !wants_coefficient_placement(nl) || s->ring.size() < 4 || s->A.values == nullptr) return;
     hipStream_t q = s->compute;
+    // Every tile that is evaluated from the planes is uniform: the SpMV being timed reads no plane value, so the trial skips its
+    // copies (9.6 GB each at 4e8 rows) -- the candidates are still timed and recorded, and a candidate that is kept receives the
+    // planes then (class-0 paths of the A/B options read them).
+    const bool nothing_streamed = s->planes_on && s->tiles_total > 0 && s->tiles_uniform == s->tiles_total && !s->stream_everywhere;
     // the coefficient stream the loop reads: the symmetric planes where the slab keeps them, else the CSR values
     const bool planes = s->planes_on;
     const size_t count = planes ? s->planes_doubles : (size_t)s->A.view.nnz_local;
@@ -538,7 +595,7 @@ void place_coefficients(SpmvAmdCgSlab* s) {
     int tried = 0;
     double before = 0.0, after = 0.0;
     double* best = device_alloc_best_of<double>(count, 0, [&](double* cand) {
-        if (cand != original) HIP_CHECK(hipMemcpyAsync(cand, original, count * sizeof(double), hipMemcpyDeviceToDevice, q));
+        if (cand != original && !nothing_streamed) HIP_CHECK(hipMemcpyAsync(cand, original, count * sizeof(double), hipMemcpyDeviceToDevice, q));
         const double ms = cost(cand);
         if (cand == original) before = ms;
         return ms;
@@ -546,6 +603,10 @@ void place_coefficients(SpmvAmdCgSlab* s) {
     after = best == original ? before : cost(best);
     HIP_CHECK(hipStreamSynchronize(q));
     const bool moved = best != original && after < 0.99 * before;
+    if (moved && nothing_streamed) {
+        HIP_CHECK(hipMemcpyAsync(best, original, count * sizeof(double), hipMemcpyDeviceToDevice, q));
+        HIP_CHECK(hipStreamSynchronize(q));
+    }
     if (best != original) {
         if (!moved) device_release(best);
         else if (planes) device_release(s->planes_alloc), s->planes_alloc = best;
@@ -1618,6 +1679,16 @@ extern "C" const char* spmv_amd_cg_slab_variant(const SpmvAmdCgSlab* s) { return
 // The coefficients the slab's SpMV streams: 0 = the CSR values, 1 = the symmetric planes (kernels.hpp, SymPlanes).
 extern "C" int spmv_amd_cg_slab_coefficient_form(const SpmvAmdCgSlab* s) { return s->planes_on ? 1 : 0; }
 
+// Tile classes of a slab in the symmetric form (kernels.hpp, SymPlanes): *total = the row-lds tiles of the slab's grid rows that are
+// evaluated from the planes (global grid rows 1 .. n-2), *uniform = how many of them hold the slab-wide quintuple in every
+// coefficient they multiply and therefore load none. Both 0 for a slab that keeps the CSR form. Returns 0.
+extern "C" int spmv_amd_cg_slab_uniform_tiles(const SpmvAmdCgSlab* s, long long* uniform, long long* total) {
+    const bool have = s->planes_alloc != nullptr && s->tile_classes != nullptr;
+    if (uniform) *uniform = have ? s->tiles_uniform : 0;
+    if (total) *total = have ? s->tiles_total : 0;
+    return 0;
+}
+
 // What placement at creation did: {0, candidates timed, SpMV ms (mean of an early and a late direction buffer as x) where the
 // coefficients were, ms where they are now}. 0 values = it did not run.
 extern "C" int spmv_amd_cg_slab_placement(const SpmvAmdCgSlab* s, double* out, int cap) {
@@ -1662,8 +1733,21 @@ extern "C" int spmv_amd_cg_slab_set_option(SpmvAmdCgSlab* s, const char* name, l
     else if (strcmp(name, "stop_at") == 0) s->stop_at = value > 0 ? (int)value : 0;
     else if (strcmp(name, "spmv_event_stride") == 0) s->spmv_event_stride = (int)value;
     else if (strcmp(name, "csr_coefficients") == 0) s->planes_on = value == 0 && s->planes_alloc != nullptr;  // 1: the CSR form
+    else if (strcmp(name, "stream_coefficients") == 0) {  // 1: the planes on every tile, the class map ignored
+        s->stream_everywhere = value != 0;
+        if (s->planes_alloc != nullptr) s->planes = plane_view(s, s->planes_alloc);
+    }
     else return -1;
     return 0;
+}
+
+// (LAB build only.) The tile class map as creation wrote it: one byte per row-lds tile at [local grid row * tiles per grid row +
+// column tile], 1 = uniform. Copies min(count, cap) bytes and returns count (0: the slab has no map).
+extern "C" long long spmv_amd_cg_slab_tile_classes(const SpmvAmdCgSlab* s, unsigned char* out, long long cap) {
+    if (s->tile_classes == nullptr) return 0;
+    const long long count = (long long)s->tile_class_count;
+    if (out != nullptr && cap > 0) HIP_CHECK(hipMemcpy(out, s->tile_classes, (size_t)std::min(count, cap), hipMemcpyDeviceToHost));
+    return count;
 }
 #endif  // SPMV_AMD_LAB
 extern "C" const char* spmv_amd_cg_slab_timeline_names(void) { return kTimelineNames; }
@@ -1698,6 +1782,7 @@ extern "C" void spmv_amd_cg_slab_destroy(SpmvAmdCgSlab* s) {
     s->x0 = nullptr;
     device_release(s->vec_arena);  // r, Ap and the direction buffers
     device_release(s->planes_alloc);
+    device_release(s->tile_classes);
     s->planes_on = false;
     s->r = s->Ap = s->p_alloc = s->p = nullptr;
     s->ring_alloc.clear();

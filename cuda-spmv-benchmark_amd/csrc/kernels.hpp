@@ -95,12 +95,26 @@ struct ResidualOut {
 // (E = 0 in column n-1); s = S of local row lr at s[lr] (0 in the grid's last row), with ONE grid row of halo in front of it:
 // s[lr - n], lr < n, is the slab's own N entry of local row lr (0 in the grid's first row). The row-lds kernel then streams 24 B
 // of coefficients per row instead of 40, with the same fma chains. Row-lds launches only; a null view = the CSR form.
+//
+// Tile classes (a property inside this form): a row-lds tile -- 128 columns of one grid row -- of global grid rows 1 .. n-2 is
+// UNIFORM when every coefficient its fma chains multiply equals, as a 64-bit pattern, the matching member of one slab-wide
+// quintuple (w, c, e, n, s): interior columns W, C, E, N, S; column 0 N, C, E, S; column n-1 N, W, C, S. `cls` holds one byte per
+// tile at [local grid row * col_tiles + col_tile] (1 = uniform, 0 = stream the planes), written once at creation from the CSR
+// values (launch_classify_tiles). A wave on a uniform tile loads no coefficient at all and runs the same fma chains on the
+// quintuple, which travels as launch arguments. cls == nullptr: every tile streams the planes.
 struct SymPlanes {
     const double* ce = nullptr;  // 16-byte aligned
     const double* s = nullptr;
+    const unsigned char* cls = nullptr;
+    double w = 0.0, c = 0.0, e = 0.0, n = 0.0, s5 = 0.0;  // the quintuple (s5: S)
 };
 // Fills the planes from a slab that passed verify_stencil (s: the local part, halo in front).
 void launch_fill_sym_planes(const SlabCsr& m, double* ce, double* s, hipStream_t stream);
+// Writes the tile class map of a verified stencil slab made of whole grid rows (SymPlanes: one byte per tile, local grid rows x
+// ceil(n / 128) of them; the grid's first and last grid row get 0) by comparing the CSR values with `quintuple` = {W, C, E, N, S}
+// bit for bit, and adds the number of uniform tiles to *d_uniform (zeroed by the caller).
+void launch_classify_tiles(const SlabCsr& m, const double quintuple[5], unsigned char* cls, unsigned long long* d_uniform, hipStream_t stream);
+int rowlds_col_tiles(int n);  // row-lds tiles per grid row
 // Sets *d_mismatch (int, zeroed by the caller) if any value the row-lds kernel would take from the planes in grid rows 1 .. n-2
 // (W = E[i-1], N = S[i-n] or the halo row, C, E, S) differs in its 64-bit pattern from the CSR entry it stands for.
 void launch_verify_sym_planes(const SlabCsr& m, const SymPlanes& planes, int* d_mismatch, hipStream_t stream);

@@ -449,6 +449,12 @@ int spmv_amd_cg_slab_setup_ms(const SpmvAmdCgSlab* s, double* out, int cap);
  * matrix, every launch is a row-lds launch and those W / N entries equal their CSR entries bit for bit (checked at creation);
  * the results are the CSR form's, bit for bit. */
 int spmv_amd_cg_slab_coefficient_form(const SpmvAmdCgSlab* s);
+/* Inside form 1: a row-lds tile (128 columns of one grid row) whose coefficients all equal, bit for bit, one slab-wide quintuple
+ * (W, C, E, N, S) -- any constant-coefficient stencil away from perturbed entries -- is evaluated without loading a coefficient;
+ * which tiles those are is decided once at creation against the CSR values (one byte per tile). *total = the tiles of the slab's
+ * grid rows that are evaluated from the planes (global grid rows 1 .. n-2), *uniform = how many of them load no coefficient.
+ * Both 0 for a slab in form 0. Either pointer may be null. Returns 0. Results are the CSR form's, bit for bit. */
+int spmv_amd_cg_slab_uniform_tiles(const SpmvAmdCgSlab* s, long long* uniform, long long* total);
 /* The timed in-loop SpMV launches of the last solve, one by one (ms, iteration order). Returns their number. */
 int spmv_amd_cg_slab_spmv_launch_ms(const SpmvAmdCgSlab* s, float* out, int cap);
 const char* spmv_amd_cg_slab_timeline_names(void);

@@ -35,9 +35,15 @@ SpmvAmdCgSlab* spmv_amd_cg_slab_create_stencil5_as(int n, int as_rank, int as_wo
  * results are bit-identical under each --, "spmv_event_stride" N (time every N-th in-loop SpMV launch; default 7, phase advancing with every solve; 0 = none),
  * and the one option that is NOT result-neutral, a timing aid for stand-in slabs: "stop_at" K (iteration K counts as the
  * converging one whatever its residual; 0 = off), and "csr_coefficients" 0/1 (1 = the SpMV streams the CSR values even where the
- * slab holds the symmetric planes, spmv_amd_cg_slab_coefficient_form; results are bit-identical). Returns 0, or -1 for an
- * unknown name. */
+ * slab holds the symmetric planes, spmv_amd_cg_slab_coefficient_form; results are bit-identical) and "stream_coefficients" 0/1
+ * (1 = the kernel ignores the tile class map and streams the planes on every tile, spmv_amd_cg_slab_uniform_tiles; composes with
+ * "csr_coefficients"; results are bit-identical). Returns 0, or -1 for an unknown name. */
 int spmv_amd_cg_slab_set_option(SpmvAmdCgSlab* s, const char* name, long long value);
+
+/* The tile class map of a slab in the symmetric form as creation wrote it (spmv_amd_cg_slab_uniform_tiles): one byte per row-lds
+ * tile at [local grid row * ceil(n / 128) + column tile], 1 = uniform, 0 = the tile streams the planes (the grid's first and last
+ * grid row, which walk the CSR, hold 0). Copies min(count, cap) bytes to `out` (host) and returns count; 0 = no map. */
+long long spmv_amd_cg_slab_tile_classes(const SpmvAmdCgSlab* s, unsigned char* out, long long cap);
 
 /* The device scalars of one preconditioned solve (csrc/pcg.hip keeps the same record on the device). */
 typedef struct SpmvAmdPcgScalars {
