@@ -118,9 +118,11 @@ DECLARED_SYMBOLS = [
     "spmv_amd_cg_solve_device_multi", "spmv_amd_cg_last_history_multi", "spmv_amd_cg_multi_workspace_bytes",
     "spmv_amd_precond_create", "spmv_amd_precond_create_from_diagonal", "spmv_amd_precond_destroy", "spmv_amd_precond_kind",
     "spmv_amd_precond_inverse_diagonal", "spmv_amd_pcg_solve_device", "spmv_amd_pcg_last_history", "spmv_amd_pcg_release_workspace",
+    "spmv_amd_precond_create_chebyshev", "spmv_amd_precond_chebyshev_info", "spmv_amd_precond_apply_device",
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
-LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_pcg_stage"]
+LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_pcg_stage",
+                    "spmv_amd_pcg_last_step_launches"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
 DECLARED_CXX_SYMBOLS = [
     "SPMV_CSR", "SPMV_STENCIL5_CSR", "SPMV_STENCIL_HALO_MGPU", "SPMV_ELLPACK", "SPMV_STENCIL5_ELLPACK",
@@ -215,6 +217,8 @@ def lib():
         L.spmv_amd_cg_slab_tile_classes.restype = C.c_longlong
         L.spmv_amd_pcg_stage.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PcgStageArgs), C.POINTER(PcgScalars)]
         L.spmv_amd_pcg_stage.restype = C.c_int
+        L.spmv_amd_pcg_last_step_launches.argtypes = []
+        L.spmv_amd_pcg_last_step_launches.restype = C.c_int
     L.spmv_amd_cg_slab_create.restype = C.c_void_p
     L.spmv_amd_cg_slab_create.argtypes = [C.POINTER(MatrixData), C.c_void_p]
     L.spmv_amd_cg_slab_create_stencil5.restype = C.c_void_p
@@ -580,6 +584,11 @@ def _pcg_lib():
         L.spmv_amd_pcg_last_history.argtypes = [C.c_void_p, C.c_int]
         L.spmv_amd_pcg_release_workspace.argtypes = []
         L.spmv_amd_pcg_release_workspace.restype = None
+        L.spmv_amd_precond_create_chebyshev.argtypes = [C.POINTER(SpmvOperator), C.c_int, C.c_double, C.c_double, C.POINTER(C.c_int)]
+        L.spmv_amd_precond_create_chebyshev.restype = C.c_void_p
+        L.spmv_amd_precond_chebyshev_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                      C.c_void_p, C.c_int]
+        L.spmv_amd_precond_apply_device.argtypes = [C.POINTER(SpmvOperator), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         L._pcg_sigs = True
     return L
 
@@ -615,9 +624,36 @@ class Precond:
             raise err
         return cls(_handle=h, _n=len(d))
 
+    @classmethod
+    def chebyshev(cls, op, degree=4, lambda_min=0.0, lambda_max=0.0):
+        """spmv_amd_precond_create_chebyshev; bounds <= 0 ask for the automatic ones."""
+        bad = C.c_int(-2)
+        h = _pcg_lib().spmv_amd_precond_create_chebyshev(op.op, degree, lambda_min, lambda_max, C.byref(bad))
+        if not h:
+            err = ValueError(f"precond_create_chebyshev({op.name}, {degree}, {lambda_min}, {lambda_max}) refused, bad_row = {bad.value}")
+            err.bad_row = bad.value
+            raise err
+        return cls(_handle=h, _n=op.rows)
+
     @property
     def kind(self):
         return _pcg_lib().spmv_amd_precond_kind(self.handle).decode()
+
+    def chebyshev_info(self):
+        """degree, lambda_min, lambda_max and the coefficients [c0, h_1, g_1, ...]; None for another kind."""
+        deg, lo, hi = C.c_int(-1), C.c_double(0.0), C.c_double(0.0)
+        coef = np.zeros(65, dtype=np.float64)
+        count = _pcg_lib().spmv_amd_precond_chebyshev_info(self.handle, C.byref(deg), C.byref(lo), C.byref(hi), coef.ctypes.data, len(coef))
+        if count == 0:
+            return None
+        return deg.value, lo.value, hi.value, coef[:count].copy()
+
+    def apply_device(self, op, r_ptr, z_ptr):
+        """spmv_amd_precond_apply_device on device pointers; returns r.z (raises RuntimeError on a refusal)."""
+        rz = C.c_double(0.0)
+        if _pcg_lib().spmv_amd_precond_apply_device(op.op, self.handle, r_ptr, z_ptr, C.byref(rz)) != 0:
+            raise RuntimeError("precond_apply_device refused")
+        return rz.value
 
     def inverse_diagonal(self):
         out = np.empty(self.n, dtype=np.float64)

@@ -160,6 +160,16 @@ struct FusedSpmv {
                   hipStream_t stream) = nullptr;
 };
 FusedSpmv fused_spmv_of(const SpmvOperator* op);
+// What the Chebyshev preconditioner (pcg.hip) may ask of an operator beyond run_device. stencil5-csr on a
+// row-lds plan runs one whole step inside its SpMV launch (kernels.hpp, ChebStep): fused_step returns the partial slots a last step
+// writes. stencil5-csr on any plan has a SpMV that tests a device flag (spmv_if: nothing is read once *d_skip != 0). Every other
+// operator leaves both null and is driven through run_device followed by the streaming step kernel. Defined in operators.hip.
+struct ChebSpmv {
+    int partials = 0;  // slots a fused last step writes
+    int (*fused_step)(const double* d_z, const ChebStep* step, double* d_partials, const int* d_skip, hipStream_t stream) = nullptr;
+    int (*spmv_if)(const double* d_x, double* d_y, const int* d_skip, hipStream_t stream) = nullptr;
+};
+ChebSpmv cheb_spmv_of(const SpmvOperator* op);
 // Frees the vectors cg_solve_device keeps between calls (cg_slab.hip); called by every operator's free().
 void release_cg_workspace();
 // The same for the preconditioned solver (pcg.hip); the caller holds the workspace lock (release_cg_workspace does).

@@ -114,6 +114,20 @@ void launch_fill_sym_planes(const SlabCsr& m, double* ce, double* s, hipStream_t
 // ceil(n / 128) of them; the grid's first and last grid row get 0) by comparing the CSR values with `quintuple` = {W, C, E, N, S}
 // bit for bit, and adds the number of uniform tiles to *d_uniform (zeroed by the caller).
 void launch_classify_tiles(const SlabCsr& m, const double quintuple[5], unsigned char* cls, unsigned long long* d_uniform, hipStream_t stream);
+// One Chebyshev step fused into a row-lds launch (kMode 3; pcg.hip): with w = A z kept in registers,
+//   t = fma(-1.0, w, r) ; u = dinv * t ; d = fma(g, u, h * d) ; z_out = z + d
+// d is updated in place (its own lane only), z_out is a SECOND vector (neighbouring tiles still read z). last != 0: the launch also
+// writes one partial of r . z_out per wave, in the slot layout of the p.Ap partials. work_count (may be null): incremented once per
+// launch that was not skipped.
+struct ChebStep {
+    const double* r = nullptr;
+    const double* dinv = nullptr;
+    double* d = nullptr;
+    double* z_out = nullptr;
+    double g = 0.0, h = 0.0;
+    int last = 0;
+    int* work_count = nullptr;
+};
 int rowlds_col_tiles(int n);  // row-lds tiles per grid row
 // Sets *d_mismatch (int, zeroed by the caller) if any value the row-lds kernel would take from the planes in grid rows 1 .. n-2
 // (W = E[i-1], N = S[i-n] or the halo row, C, E, S) differs in its 64-bit pattern from the CSR entry it stands for.
@@ -125,6 +139,10 @@ void launch_verify_sym_planes(const SlabCsr& m, const SymPlanes& planes, int* d_
 int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& plan, const double* x, double* y, double alpha,
                          double* d_dot_partials, const int* d_skip_flag, bool reverse, hipStream_t stream,
                          const ResidualOut* init = nullptr, const SymPlanes* planes = nullptr);
+// The fused Chebyshev step over a row-lds plan (ChebStep): z is read as the SpMV's x, A z is not written. Returns the partial slots
+// a last step writes (the plan's), or -1 without launching when the plan is not a row-lds one.
+int launch_stencil5_cheb_step(const SlabCsr& m, const Stencil5Plan& plan, const double* z, const ChebStep& step, double* d_dot_partials,
+                              const int* d_skip_flag, hipStream_t stream);
 // first_row/last_row restrict the launch to local rows [first_row, last_row); used to split
 // interior rows from halo-dependent rows. Returns the number of dot partials written (0 when
 // d_dot_partials is null).

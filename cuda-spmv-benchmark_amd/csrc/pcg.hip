@@ -1,4 +1,4 @@
-// pcg.hip -- Jacobi-preconditioned CG over any SpmvOperator.
+// pcg.hip -- preconditioned CG over any SpmvOperator: Jacobi and a Chebyshev polynomial in D^-1 A (section 14).
 //
 // An entry point with its own loop: the algebra of cg_solve_device with z = M^-1 r, M = diag(A) ("jacobi") or I ("none"),
 // the same stopping rule (true residual ||r_k|| / ||r_0|| < tol, strict, the converging iteration counted), statistics and
@@ -13,6 +13,18 @@
 // deferred x update, no run-ahead (that machinery is the slab loop's, cg_slab.hip).
 // Breakdown: a pAp or r.z' that is zero or not finite stops the loop in that iteration with converged = 0 (no sign test:
 // negative-definite systems solve). Sums have a fixed shape (reduce_device.hpp): a solve is bit-reproducible.
+//
+// Kind "chebyshev" (degree k, interval [lmin, lmax] of D^-1 A; coefficients c0, h_1, g_1, ... from the host recurrence below):
+//   term 0:  u = dinv r ; d = c0 u ; z = d
+//   step j:  w = A z ; t = fma(-1, w, r) ; u = dinv t ; d = fma(g_j, u, h_j d) ; z = z + d
+// Applying it is SpMVs and streaming updates only. Its iteration:
+//   Ap = A p with the p.Ap partials | sum + alpha | r -= alpha Ap with term 0 in registers, partials of r.r |
+//   sum of r.r + verdict (history, stopping test; the verdict also lands in a device flag) |
+//   k steps, each testing that flag before it works: the converging iteration streams nothing |
+//   sum of r.z + beta | x += alpha p, p = z + beta p (the "none" x/p kernel with z where it reads r)
+// On stencil5-csr / row-lds a step is ONE launch (spmv_kernels.hip, kMode 3: A z never leaves the registers, z' goes to a second
+// vector): 144 + 88 k bytes per interior row and iteration. Everywhere else it is the operator's SpMV and one streaming kernel
+// (112 per step). The Jacobi and "none" loops above are untouched by this kind: it has its own loop function.
 #include <limits.h>
 #include <math.h>
 #include <stddef.h>
@@ -32,14 +44,18 @@
 
 using namespace spmv_amd;
 
-enum PrecondKind { kNone = 0, kJacobi = 1 };
+enum PrecondKind { kNone = 0, kJacobi = 1, kChebyshev = 2 };
+constexpr int kChebMaxDegree = 32;
 
 struct SpmvAmdPrecond {
     int kind = kNone;
     int n = 0;
     const void* owner = nullptr;  // the operator state the diagonal came from (DiagonalSource::owner); null: a caller's diagonal
     unsigned long long generation = 0;
-    double* dinv = nullptr;       // device, n values ("jacobi")
+    double* dinv = nullptr;       // device, n values ("jacobi", "chebyshev")
+    int degree = 0;               // "chebyshev": steps = SpMVs per application
+    double lambda_min = 0.0, lambda_max = 0.0;
+    double coef[1 + 2 * kChebMaxDegree] = {0.0};  // c0, h_1, g_1, h_2, g_2, ...
 };
 
 namespace {
@@ -197,10 +213,177 @@ __global__ __launch_bounds__(kWave) void pcg_update_xp_kernel(size_t n, const Pc
     }
 }
 
+// ---- kind "chebyshev": lambda_max, term 0 fused into the r update, the streaming step ----
+
+// max_i sum_j |a_ij| sqrt(|dinv_i| |dinv_j|): Gershgorin's bound on D^-1/2 A D^-1/2, which has the spectrum of D^-1 A and, unlike the
+// plain row sum of D^-1 A, does not move under a symmetric diagonal scaling of A. Row i is summed in storage (CSR) order from 0.0, one
+// rounding per operation. The maximum of non-negative doubles is the maximum of their bit patterns as unsigned integers: a wave tree,
+// then one 64-bit unsigned atomic max per wave -- independent of the order. A NaN row wins and is refused on the host.
+__global__ __launch_bounds__(256) void gershgorin_kernel(int src, SlabCsr m, const int* __restrict__ idx, const double* __restrict__ val,
+                                                         int width, int n, const double* __restrict__ dinv, unsigned long long* __restrict__ out) {
+    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    double sum = 0.0;
+    if (r < n) {
+        const double di = fabs(dinv[r]);
+        if (src == 0) {
+            for (int j = m.row_ptr[r]; j < m.row_ptr[r + 1]; ++j) {
+                const double w = sqrt(di * fabs(dinv[m.col_idx[j]]));
+                sum = sum + fabs(m.values[j]) * w;
+            }
+        } else {
+            for (int k = 0; k < width; ++k) {
+                const int c = idx[(long long)k * n + r];
+                if (c < 0) continue;
+                const double w = sqrt(di * fabs(dinv[c]));
+                sum = sum + fabs(val[(long long)k * n + r]) * w;
+            }
+        }
+    }
+    unsigned long long bits = (unsigned long long)__double_as_longlong(sum);  // sum >= +0.0, or NaN
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long other = (unsigned long long)__shfl_down((long long)bits, off);
+        bits = other > bits ? other : bits;
+    }
+    if ((threadIdx.x & 63) == 0) atomicMax(out, bits);
+}
+
+// The residual of the stage and term 0 of the polynomial from it, in registers. kFrom 0: r = b - Ap (the initial residual, bv = b);
+// 1: r = fma(-alpha, Ap, r) unless this iteration's pAp broke down; 2: r as it is (spmv_amd_precond_apply_device: r is only read).
+// Then u = dinv r ; d = c0 u ; z = d. Partials: r.r at partials[blk] (kFrom 0, 1), and r.z at partials[count + blk] when term 0 is the
+// whole polynomial (last != 0, degree 0).
+template <int kFrom>
+__global__ __launch_bounds__(kWave) void cheb_term0_kernel(size_t n, const PcgScalars* __restrict__ s, const double* __restrict__ bv,
+                                                           const double* __restrict__ Ap, const double* __restrict__ dinv, double c0,
+                                                           double* __restrict__ r, double* __restrict__ d, double* __restrict__ z, int last,
+                                                           double* __restrict__ partials, int count) {
+    const size_t i = (size_t)blockIdx.x * kWave + threadIdx.x;
+    const bool live = i < (n >> 1);
+    d2 av = {0.0, 0.0}, rv = {0.0, 0.0}, dv = {0.0, 0.0};
+    if (live) {  // the loads before the scalars
+        if (kFrom != 2) av = load_once(Ap, i);
+        rv = load_once(kFrom == 0 ? bv : r, i);
+        dv = load_once(dinv, i);
+    }
+    bool update = false;
+    double alpha = 0.0;
+    if (kFrom == 1) update = s->skip_update == 0, alpha = s->alpha;
+    double rr = 0.0, rz = 0.0;
+    if (live) {
+        if (kFrom == 0) {
+            rv.x = fma(1.0, rv.x, -1.0 * av.x);
+            rv.y = fma(1.0, rv.y, -1.0 * av.y);
+            store_once(r, i, rv);
+        } else if (kFrom == 1 && update) {
+            rv.x = fma(-alpha, av.x, rv.x);
+            rv.y = fma(-alpha, av.y, rv.y);
+            store_once(r, i, rv);
+        }
+        d2 dd;
+        dd.x = c0 * (dv.x * rv.x);
+        dd.y = c0 * (dv.y * rv.y);
+        store_once(d, i, dd);
+        reinterpret_cast<d2*>(z)[i] = dd;  // plain: the first step's SpMV reads it
+        rr = fma(rv.x, rv.x, rr), rr = fma(rv.y, rv.y, rr);
+        if (last) rz = fma(rv.x, dd.x, rz), rz = fma(rv.y, dd.y, rz);
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        double rl;
+        if (kFrom == 0) {
+            r[n - 1] = rl = fma(1.0, bv[n - 1], -1.0 * Ap[n - 1]);
+        } else {
+            rl = r[n - 1];
+            if (kFrom == 1 && update) r[n - 1] = rl = fma(-alpha, Ap[n - 1], rl);
+        }
+        const double dl = c0 * (dinv[n - 1] * rl);
+        d[n - 1] = dl, z[n - 1] = dl;
+        rr = fma(rl, rl, rr);
+        if (last) rz = fma(rl, dl, rz);
+    }
+    if (kFrom != 2) {
+        rr = wave_sum(rr);
+        if (threadIdx.x == 0) partials[blockIdx.x] = rr;
+    }
+    if (last) {
+        rz = wave_sum(rz);
+        if (threadIdx.x == 0) partials[count + blockIdx.x] = rz;
+    }
+}
+
+// One step behind a SpMV that wrote w = A z: t = fma(-1, w, r) ; u = dinv t ; d = fma(g, u, h d) ; z = z + d, d and z in place.
+// Nothing is read once *stop != 0 (the iteration's verdict; null: no test). last: the partials of r.z at partials[blk].
+__global__ __launch_bounds__(kWave) void cheb_step_kernel(size_t n, const int* __restrict__ stop, const double* __restrict__ w,
+                                                          const double* __restrict__ r, const double* __restrict__ dinv, double g, double h,
+                                                          double* __restrict__ d, double* __restrict__ z, int last, double* __restrict__ partials,
+                                                          int* __restrict__ work_count) {
+    if (stop != nullptr && *stop != 0) return;
+    const size_t i = (size_t)blockIdx.x * kWave + threadIdx.x;
+    double rz = 0.0;
+    if (i < (n >> 1)) {
+        const d2 wv = load_once(w, i), rv = load_once(r, i), iv = load_once(dinv, i);
+        d2 dd = load_once(d, i), zv = reinterpret_cast<const d2*>(z)[i];
+        dd.x = fma(g, iv.x * fma(-1.0, wv.x, rv.x), h * dd.x);
+        dd.y = fma(g, iv.y * fma(-1.0, wv.y, rv.y), h * dd.y);
+        zv.x = zv.x + dd.x;
+        zv.y = zv.y + dd.y;
+        store_once(d, i, dd);
+        reinterpret_cast<d2*>(z)[i] = zv;  // plain: the next SpMV reads it
+        if (last) rz = fma(rv.x, zv.x, rz), rz = fma(rv.y, zv.y, rz);
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const double rl = r[n - 1];
+        const double dl = fma(g, dinv[n - 1] * fma(-1.0, w[n - 1], rl), h * d[n - 1]);
+        const double zl = z[n - 1] + dl;
+        d[n - 1] = dl, z[n - 1] = zl;
+        if (last) rz = fma(rl, zl, rz);
+    }
+    if (work_count != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *work_count += 1;  // one thread per launch; launches are ordered
+    if (last) {
+        rz = wave_sum(rz);
+        if (threadIdx.x == 0) partials[blockIdx.x] = rz;
+    }
+}
+
+// z = dinv r ("jacobi") or z = r ("none") with the partials of r.z: those kinds through spmv_amd_precond_apply_device.
+template <bool kJac>
+__global__ __launch_bounds__(kWave) void precond_apply_kernel(size_t n, const double* __restrict__ r, const double* __restrict__ dinv,
+                                                              double* __restrict__ z, double* __restrict__ partials) {
+    const size_t i = (size_t)blockIdx.x * kWave + threadIdx.x;
+    double rz = 0.0;
+    if (i < (n >> 1)) {
+        const d2 rv = load_once(r, i);
+        d2 zv = rv;
+        if (kJac) {
+            const d2 dv = load_once(dinv, i);
+            zv.x = dv.x * rv.x, zv.y = dv.y * rv.y;
+        }
+        store_once(z, i, zv);
+        rz = fma(rv.x, zv.x, rz), rz = fma(rv.y, zv.y, rz);
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const double rl = r[n - 1];
+        const double zl = kJac ? dinv[n - 1] * rl : rl;
+        z[n - 1] = zl;
+        rz = fma(rl, zl, rz);
+    }
+    rz = wave_sum(rz);
+    if (threadIdx.x == 0) partials[blockIdx.x] = rz;
+}
+
+// The device record of a Chebyshev solve: the scalars every kind keeps, then what only this kind needs. pcg_step's steps 3 to 5 are
+// handed the record's first member and reach the rest through it.
+struct ChebScalars {
+    PcgScalars s;
+    int stop;        // the iteration's verdict (converged or broken down): the steps' skip flag
+    int steps_done;  // step launches that did work
+};
+
 // ---- reductions: NV sums of `count` partials each (value v at partials[v * count ...]) in ONE launch, then the scalar step ----
 // The shape of reduce_device.hpp extended to two values: slice workgroups publish their slice sums of value 0 into the stage's
 // `sums`, of value 1 into its `extra` slots; the workgroup that draws the last ticket sums both and takes the step. One
 // workgroup (no stage) when there are at most 1024 partials. which: 0 = initial r.r / r.z, 1 = pAp, 2 = r.r / r.z'.
+// Kind "chebyshev" (s is the first member of a ChebScalars): 3 = r.r alone with the verdict, which it also writes to the stop flag;
+// 4 = r.z' alone with beta, unless the verdict stopped the iteration; 5 = r.z of an application on its own (rz = the sum).
 
 __device__ void pcg_step(PcgScalars* s, int which, const double* total, double tol, double* hist, int hist_cap) {
     if (which == 0) {
@@ -218,7 +401,7 @@ __device__ void pcg_step(PcgScalars* s, int which, const double* total, double t
             s->alpha = 0.0;
             s->skip_update = 1;
         }
-    } else {
+    } else if (which == 2) {
         const double res = sqrt(total[0]);
         s->iterations += 1;
         s->residual = res;
@@ -233,6 +416,25 @@ __device__ void pcg_step(PcgScalars* s, int which, const double* total, double t
             s->beta = total[1] / s->rz;
             s->rz = total[1];
         }
+    } else if (which == 3) {
+        const double res = sqrt(total[0]);
+        s->iterations += 1;
+        s->residual = res;
+        if (s->iterations < hist_cap) hist[s->iterations] = res;
+        if (s->skip_update) s->breakdown = 1;
+        else if (res / s->b_norm < tol) s->converged = 1;
+        reinterpret_cast<ChebScalars*>(s)->stop = (s->converged != 0 || s->breakdown != 0) ? 1 : 0;
+    } else if (which == 4) {
+        if (s->converged == 0 && s->breakdown == 0) {
+            if (!usable(total[0])) {
+                s->breakdown = 1;
+            } else {
+                s->beta = total[0] / s->rz;
+                s->rz = total[0];
+            }
+        }
+    } else {
+        s->rz = total[0];
     }
 }
 
@@ -321,6 +523,57 @@ void launch_pcg_reduce(const double* partials, int count, int nv, int which, dou
                            s, which, tol, hist, hist_cap);
 }
 
+// ---- kind "chebyshev": the launches ----
+
+template <int kFrom>
+void launch_cheb_term0(size_t n, const PcgScalars* s, const double* b, const double* Ap, const double* dinv, double c0, double* r, double* d,
+                       double* z, bool last, double* partials) {
+    const dim3 grid(stream_grid(n)), block(kWave);
+    hipLaunchKernelGGL(cheb_term0_kernel<kFrom>, grid, block, 0, kStream, n, s, b, Ap, dinv, c0, r, d, z, last ? 1 : 0, partials, (int)grid.x);
+}
+
+// Steps 1 .. degree of one application on top of term 0 (d, and z in *z_a). z_b: the second z vector of the fused step; w: where the
+// unfused step's SpMV writes A z. Returns the vector that holds z afterwards (z_a or z_b) and sets *rz_count to the r.z partials
+// written at `partials` (degree 0: nothing is launched, term 0 wrote them behind its r.r partials). spmv / blas: how the caller
+// runs (and times) a launch of each class. *failed is set when the operator's run_device refuses.
+template <class RunSpmv, class RunBlas>
+double* cheb_run_steps(SpmvOperator* op, const ChebSpmv& c, const SpmvAmdPrecond* m, size_t n, const double* r, double* d, double* z_a,
+                       double* z_b, double* w, double* partials, const int* stop, int* work_count, int* rz_count, bool* failed,
+                       RunSpmv&& spmv, RunBlas&& blas) {
+    double *z = z_a, *z_next = z_b;
+    for (int k = 1; k <= m->degree && !*failed; ++k) {
+        const double h = m->coef[2 * k - 1], g = m->coef[2 * k];
+        const int last = k == m->degree ? 1 : 0;
+        if (c.fused_step != nullptr) {
+            ChebStep step;
+            step.r = r, step.dinv = m->dinv, step.d = d, step.z_out = z_next, step.g = g, step.h = h, step.last = last;
+            step.work_count = work_count;
+            spmv([&] {
+                const int slots = c.fused_step(z, &step, partials, stop, kStream);
+                if (last) *rz_count = slots;
+            });
+            double* const t = z;
+            z = z_next, z_next = t;
+        } else {
+            spmv([&] {
+                if (c.spmv_if != nullptr) {
+                    (void)c.spmv_if(z, w, stop, kStream);
+                } else if (op->run_device(z, w) != 0) {
+                    fprintf(stderr, "[PCG] operator '%s': run_device failed\n", op->name);
+                    *failed = true;
+                }
+            });
+            if (*failed) break;
+            blas([&] {
+                hipLaunchKernelGGL(cheb_step_kernel, dim3(stream_grid(n)), dim3(kWave), 0, kStream, n, stop, w, r, m->dinv, g, h, d, z, last,
+                                   partials, work_count);
+            });
+            if (last) *rz_count = (int)stream_grid(n);
+        }
+    }
+    return z;
+}
+
 // ---- workspace: kept between calls (like cg_solve_device's), released with it ----
 struct PcgWorkspace {
     int n = 0, device = -1;
@@ -331,7 +584,11 @@ struct PcgWorkspace {
     double* hist = nullptr;
     int hist_cap = 0;
     long long partial_cap = 0;
+    double *cd = nullptr, *cz = nullptr, *cz2 = nullptr;  // kind "chebyshev" only: d, z and the fused step's second z
     void release() {
+        device_release(cd);
+        device_release(cz);
+        device_release(cz2);
         device_release(x);
         device_release(b);
         device_release(r);
@@ -346,6 +603,7 @@ struct PcgWorkspace {
 };
 PcgWorkspace g_pcg;
 std::vector<double> g_pcg_history;  // of the last preconditioned solve
+int g_cheb_step_launches = 0;       // Chebyshev step launches of its loop that did work (the LAB build hands it out)
 
 bool fail(const char* what) {
     fprintf(stderr, "[PCG] %s\n", what);
@@ -367,7 +625,7 @@ bool ensure_workspace(int n, int device, long long partial_cap, int hist_cap) {
         w.p = device_try_alloc<double>((size_t)n);
         w.Ap = device_try_alloc<double>((size_t)n);
         w.partials = device_try_alloc<double>((size_t)partial_cap);
-        w.s = device_try_alloc<PcgScalars>(1);
+        w.s = reinterpret_cast<PcgScalars*>(device_try_alloc<ChebScalars>(1));  // the Chebyshev loop's record begins with the common one
         if (!w.x || !w.b || !w.r || !w.p || !w.Ap || !w.partials || !w.s) {
             w.release();
             return fail("the workspace could not be allocated: refused");
@@ -376,6 +634,25 @@ bool ensure_workspace(int n, int device, long long partial_cap, int hist_cap) {
         w.n = n, w.device = device, w.partial_cap = partial_cap;
     }
     if (!grow_history(w.hist, w.hist_cap, hist_cap)) return fail("the history could not be allocated: refused");
+    return true;
+}
+
+// d, z, z' of the Chebyshev loop, next to a workspace ensure_workspace() has made; sized against free memory like the rest
+bool ensure_cheb_workspace(int n) {
+    PcgWorkspace& w = g_pcg;
+    if (w.cd != nullptr) return true;
+    char what[48];
+    snprintf(what, sizeof what, "%d rows (chebyshev)", n);
+    if (!device_has_room(3 * (size_t)n * sizeof(double) + ((size_t)64 << 20), "PCG", what)) return false;
+    w.cd = device_try_alloc<double>((size_t)n);
+    w.cz = device_try_alloc<double>((size_t)n);
+    w.cz2 = device_try_alloc<double>((size_t)n);
+    if (!w.cd || !w.cz || !w.cz2) {
+        device_release(w.cd);
+        device_release(w.cz);
+        device_release(w.cz2);
+        return fail("the Chebyshev vectors could not be allocated: refused");
+    }
     return true;
 }
 
@@ -465,6 +742,178 @@ extern "C" SpmvAmdPrecond* spmv_amd_precond_create_from_diagonal(const double* d
     return make_jacobi(2, SlabCsr{}, nullptr, d_diag, 0, n, bad_row);
 }
 
+namespace {
+// The coefficients of the degree-k Chebyshev polynomial on [lmin, lmax], in the order and with the operations api.h states (the file is
+// compiled with -ffp-contract=off: one rounding per operation).
+void chebyshev_coefficients(int degree, double lmin, double lmax, double* coef) {
+    const double theta = 0.5 * (lmax + lmin);
+    const double delta = 0.5 * (lmax - lmin);
+    const double sigma = theta / delta;
+    coef[0] = 1.0 / theta;
+    double rho = 1.0 / sigma;
+    for (int k = 1; k <= degree; ++k) {
+        const double rho_next = 1.0 / (2.0 * sigma - rho);
+        coef[2 * k - 1] = rho_next * rho;
+        coef[2 * k] = 2.0 * rho_next / delta;
+        rho = rho_next;
+    }
+}
+
+// What every entry point that takes (op, m) checks of the pair before any HIP call; *d: the operator's storage view.
+bool precond_matches(const SpmvOperator* op, const SpmvAmdPrecond* m, DiagonalSource* d) {
+    *d = diagonal_source_of(op);
+    if (m->owner == nullptr) return true;  // made from a caller's diagonal: no operator to belong to
+    if (m->owner != d->owner) return fail("the preconditioner was made from another operator: refused");
+    if (m->generation != d->generation)
+        return fail("the preconditioner was made before the operator was last initialised or freed: refused");
+    if (!d->ready) {
+        fprintf(stderr, "[PCG] operator '%s' used before init\n", op->name);
+        return false;
+    }
+    return true;
+}
+}  // namespace
+
+extern "C" SpmvAmdPrecond* spmv_amd_precond_create_chebyshev(SpmvOperator* op, int degree, double lambda_min, double lambda_max, int* bad_row) {
+    // argument checks: all before the first HIP call
+    if (bad_row != nullptr) *bad_row = -1;
+    if (op == nullptr) return fail("null operator"), nullptr;
+    if (degree < 0 || degree > kChebMaxDegree) {
+        fprintf(stderr, "[PCG] chebyshev: degree %d is outside 0..%d: refused\n", degree, kChebMaxDegree);
+        return nullptr;
+    }
+    if (!isfinite(lambda_min) || !isfinite(lambda_max)) return fail("chebyshev: a bound that is not finite: refused"), nullptr;
+    if (lambda_min > 0.0 && lambda_max > 0.0 && !(lambda_min < lambda_max)) return fail("chebyshev: lambda_min >= lambda_max: refused"), nullptr;
+    const DiagonalSource d = diagonal_source_of(op);
+    if (d.owner == nullptr) {
+        fprintf(stderr, "[PCG] chebyshev: operator '%s' is not one of this library's: refused\n", op->name ? op->name : "?");
+        return nullptr;
+    }
+    if (!d.ready) {
+        fprintf(stderr, "[PCG] operator '%s' used before init\n", op->name);
+        return nullptr;
+    }
+    if (d.rows != d.cols) {
+        fprintf(stderr, "[PCG] operator '%s' holds a %d x %d matrix: a square one is required\n", op->name, d.rows, d.cols);
+        return nullptr;
+    }
+    const int src = d.kind == DiagonalSource::Csr ? 0 : 1;
+    SpmvAmdPrecond* pm = make_jacobi(src, d.csr, d.idx, d.val, d.width, d.rows, bad_row);
+    if (pm == nullptr) return nullptr;
+    pm->kind = kChebyshev;
+    pm->degree = degree;
+    pm->owner = d.owner;
+    pm->generation = d.generation;
+    double lmax = lambda_max;
+    if (!(lmax > 0.0)) {
+        unsigned long long* d_bits = device_alloc<unsigned long long>(1);
+        const unsigned long long zero = 0;
+        upload(d_bits, &zero, 1);
+        hipLaunchKernelGGL(gershgorin_kernel, dim3((unsigned)((d.rows + 255) / 256)), dim3(256), 0, kStream, src, d.csr, d.idx, d.val, d.width,
+                           d.rows, pm->dinv, d_bits);
+        HIP_CHECK(hipGetLastError());
+        unsigned long long bits = 0;
+        download(&bits, d_bits, 1);  // synchronises
+        device_release(d_bits);
+        memcpy(&lmax, &bits, sizeof lmax);
+    }
+    const double lmin = lambda_min > 0.0 ? lambda_min : lmax / 30.0;
+    if (!isfinite(lmax) || !isfinite(lmin) || !(lmin > 0.0) || !(lmin < lmax)) {
+        fprintf(stderr, "[PCG] chebyshev: the interval [%g, %g] is not 0 < lambda_min < lambda_max, both finite: refused\n", lmin, lmax);
+        spmv_amd_precond_destroy(pm);
+        return nullptr;
+    }
+    pm->lambda_min = lmin, pm->lambda_max = lmax;
+    chebyshev_coefficients(degree, lmin, lmax, pm->coef);
+    return pm;
+}
+
+extern "C" int spmv_amd_precond_chebyshev_info(const SpmvAmdPrecond* m, int* degree, double* lambda_min, double* lambda_max,
+                                               double* coefficients, int cap) {
+    if (m == nullptr || m->kind != kChebyshev) return 0;
+    if (degree != nullptr) *degree = m->degree;
+    if (lambda_min != nullptr) *lambda_min = m->lambda_min;
+    if (lambda_max != nullptr) *lambda_max = m->lambda_max;
+    const int count = 1 + 2 * m->degree;
+    for (int i = 0; i < count && i < cap && coefficients != nullptr; ++i) coefficients[i] = m->coef[i];
+    return count;
+}
+
+extern "C" int spmv_amd_precond_apply_device(SpmvOperator* op, const SpmvAmdPrecond* m, const double* d_r, double* d_z, double* rz) {
+    // argument checks: all before the first HIP call
+    if (op == nullptr || m == nullptr || d_r == nullptr || d_z == nullptr) return fail("null argument"), 1;
+    if ((((uintptr_t)d_r) & 15) != 0 || (((uintptr_t)d_z) & 15) != 0) return fail("apply: a vector is not 16-byte aligned: refused"), 1;
+    const size_t n = (size_t)m->n;
+    {
+        const uintptr_t a = (uintptr_t)d_r, b = (uintptr_t)d_z, bytes = n * sizeof(double);
+        if (a < b + bytes && b < a + bytes) return fail("apply: d_z overlaps d_r: refused"), 1;
+    }
+    DiagonalSource d;
+    if (!precond_matches(op, m, &d)) return 1;
+    const bool cheb = m->kind == kChebyshev;
+    if (cheb && (op->run_device == nullptr || d.owner == nullptr || d.rows != m->n || d.cols != m->n))
+        return fail("apply: the operator is not the initialised square one the preconditioner was made from: refused"), 1;
+
+    CgWorkspaceScope scope;
+    const int vec_count = (int)stream_grid(n);
+    const ChebSpmv c = cheb ? cheb_spmv_of(op) : ChebSpmv{};
+    const long long slots = 2LL * vec_count > c.partials ? 2LL * vec_count : (long long)c.partials;
+    double* partials = device_try_alloc<double>((size_t)slots);
+    ChebScalars* cs = device_try_alloc<ChebScalars>(1);
+    double* stage = reduce_scratch_alloc();
+    double *cd = nullptr, *cz2 = nullptr, *cw = nullptr;
+    const bool fused = cheb && c.fused_step != nullptr;
+    bool ok = partials != nullptr && cs != nullptr;
+    if (ok && cheb) {
+        cd = device_try_alloc<double>(n);
+        if (m->degree > 0) (fused ? cz2 : cw) = device_try_alloc<double>(n);
+        ok = cd != nullptr && (m->degree == 0 || cz2 != nullptr || cw != nullptr);
+    }
+    int rc = 0;
+    if (!ok) {
+        rc = 1;
+        fail("apply: the work vectors could not be allocated: refused");
+    } else {
+        HIP_CHECK(hipMemsetAsync(cs, 0, sizeof(ChebScalars), kStream));
+        int rz_count = vec_count;
+        const double* rz_partials = partials;
+        bool failed = false;
+        if (!cheb) {
+            const dim3 grid((unsigned)vec_count), block(kWave);
+            if (m->kind == kJacobi) hipLaunchKernelGGL(precond_apply_kernel<true>, grid, block, 0, kStream, n, d_r, m->dinv, d_z, partials);
+            else hipLaunchKernelGGL(precond_apply_kernel<false>, grid, block, 0, kStream, n, d_r, nullptr, d_z, partials);
+        } else {
+            // the fused step alternates between two z vectors: start where an application of this degree ends in d_z
+            double* const z0 = fused && (m->degree & 1) ? cz2 : d_z;
+            double* const z1 = z0 == d_z ? cz2 : d_z;
+            launch_cheb_term0<2>(n, &cs->s, nullptr, nullptr, m->dinv, m->coef[0], const_cast<double*>(d_r), cd, z0, m->degree == 0, partials);
+            rz_partials = partials + vec_count;
+            const auto now = [](auto&& launch) { launch(); };
+            int steps_count = 0;
+            double* const z_end = cheb_run_steps(op, c, m, n, d_r, cd, z0, z1, cw, partials, nullptr, nullptr, &steps_count, &failed, now, now);
+            if (m->degree > 0) rz_partials = partials, rz_count = steps_count;
+            if (!failed && z_end != d_z) failed = true, fail("apply: internal error, the result is not in d_z");
+        }
+        if (failed) {
+            rc = 1;
+        } else {
+            launch_pcg_reduce(rz_partials, rz_count, 1, 5, stage, &cs->s, 0.0, nullptr, 0);
+            HIP_CHECK(hipGetLastError());
+            PcgScalars h{};
+            download(&h, &cs->s, 1);  // synchronises
+            if (rz != nullptr) *rz = h.rz;
+        }
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+    device_release(partials);
+    device_release(cs);
+    device_release(stage);
+    device_release(cd);
+    device_release(cz2);
+    device_release(cw);
+    return rc;
+}
+
 extern "C" void spmv_amd_precond_destroy(SpmvAmdPrecond* m) {
     if (m == nullptr) return;
     device_release(m->dinv);
@@ -473,12 +922,12 @@ extern "C" void spmv_amd_precond_destroy(SpmvAmdPrecond* m) {
 
 extern "C" const char* spmv_amd_precond_kind(const SpmvAmdPrecond* m) {
     if (m == nullptr) return "invalid";
-    return m->kind == kJacobi ? "jacobi" : "none";
+    return m->kind == kChebyshev ? "chebyshev" : m->kind == kJacobi ? "jacobi" : "none";
 }
 
 extern "C" int spmv_amd_precond_inverse_diagonal(const SpmvAmdPrecond* m, double* out, int n) {
     if (m == nullptr || out == nullptr) return fail("null argument"), 1;
-    if (m->kind != kJacobi) return fail("kind 'none' has no inverse diagonal"), 1;
+    if (m->kind == kNone) return fail("kind 'none' has no inverse diagonal"), 1;
     if (n != m->n) {
         fprintf(stderr, "[PCG] the preconditioner has %d values, %d asked for\n", m->n, n);
         return 1;
@@ -521,6 +970,7 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
     const int n = mat->rows;
     const CGConfig cfg = *config;
     const bool jac = m->kind == kJacobi;
+    const bool cheb = m->kind == kChebyshev;
 
     CgWorkspaceScope scope;
     int device = 0;
@@ -528,17 +978,22 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
     const FusedSpmv f = fused_spmv_of(op);
     const bool fused = f.launch != nullptr && f.partials > 0;
     const int vec_count = (int)stream_grid((size_t)n);
-    const long long partial_cap = 2LL * vec_count > f.partials ? 2LL * vec_count : (long long)f.partials;
+    const ChebSpmv c = cheb ? cheb_spmv_of(op) : ChebSpmv{};
+    long long partial_cap = 2LL * vec_count > f.partials ? 2LL * vec_count : (long long)f.partials;
+    if (c.partials > partial_cap) partial_cap = c.partials;
     if (!ensure_workspace(n, device, partial_cap, cfg.max_iters + 1)) return 1;
+    if (cheb && !ensure_cheb_workspace(n)) return 1;
     PcgWorkspace& w = g_pcg;
+    ChebScalars* const cs = reinterpret_cast<ChebScalars*>(w.s);
     upload(w.b, b, (size_t)n);
     upload(w.x, x, (size_t)n);
 
     StageTimers T(cfg.enable_detailed_timers != 0, kStream);
     bool op_failed = false;
-    auto reduce = [&](int count, int nv, int which) {
-        launch_pcg_reduce(w.partials, count, nv, which, w.stage, w.s, cfg.tolerance, w.hist, w.hist_cap);
+    auto reduce_at = [&](const double* partials, int count, int nv, int which) {
+        launch_pcg_reduce(partials, count, nv, which, w.stage, w.s, cfg.tolerance, w.hist, w.hist_cap);
     };
+    auto reduce = [&](int count, int nv, int which) { reduce_at(w.partials, count, nv, which); };
     auto run_op = [&](const double* in, double* out) {
         if (op->run_device(in, out) != 0) {
             fprintf(stderr, "[PCG] operator '%s': run_device failed\n", op->name);
@@ -548,11 +1003,31 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
     PcgScalars h{};
 
     T.total.begin(kStream);
-    T.run(&T.t_spmv, [&] { run_op(w.x, w.Ap); });
-    T.run(&T.t_blas, [&] { launch_pcg_init(jac, (size_t)n, w.b, w.Ap, m->dinv, w.r, w.p, w.partials); });
-    T.run(&T.t_red, [&] { reduce(vec_count, 2, 0); });
+    // kind "chebyshev": one application behind term 0 (the steps' SpMVs count as SpMV time); returns where z is and reduces r.z
+    const auto as_spmv = [&](auto&& launch) { T.run(&T.t_spmv, launch); };
+    const auto as_blas = [&](auto&& launch) { T.run(&T.t_blas, launch); };
+    auto cheb_steps_and_rz = [&](const int* stop, int* work_count, int which) -> double* {
+        int rz_count = vec_count;
+        double* const z = cheb_run_steps(op, c, m, (size_t)n, w.r, w.cd, w.cz, w.cz2, w.Ap, w.partials, stop, work_count, &rz_count, &op_failed,
+                                         as_spmv, as_blas);
+        if (!op_failed) T.run(&T.t_red, [&] { reduce_at(m->degree == 0 ? w.partials + vec_count : w.partials, rz_count, 1, which); });
+        return z;
+    };
+    if (cheb) {
+        HIP_CHECK(hipMemsetAsync(cs, 0, sizeof(ChebScalars), kStream));
+        T.run(&T.t_spmv, [&] { run_op(w.x, w.Ap); });
+        T.run(&T.t_blas, [&] { launch_cheb_term0<0>((size_t)n, w.s, w.b, w.Ap, m->dinv, m->coef[0], w.r, w.cd, w.cz, m->degree == 0, w.partials); });
+        T.run(&T.t_red, [&] { reduce(vec_count, 1, 0); });
+        const double* const z0 = cheb_steps_and_rz(nullptr, nullptr, 5);
+        if (!op_failed) HIP_CHECK(hipMemcpyAsync(w.p, z0, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, kStream));
+    } else {
+        T.run(&T.t_spmv, [&] { run_op(w.x, w.Ap); });
+        T.run(&T.t_blas, [&] { launch_pcg_init(jac, (size_t)n, w.b, w.Ap, m->dinv, w.r, w.p, w.partials); });
+        T.run(&T.t_red, [&] { reduce(vec_count, 2, 0); });
+    }
     download(&h, w.s, 1);
-    if (cfg.verbose >= 1) printf("[PCG-DEVICE] Initial residual: %e (preconditioner %s)\n", h.b_norm, jac ? "jacobi" : "none");
+    if (cfg.verbose >= 1)
+        printf("[PCG-DEVICE] Initial residual: %e (preconditioner %s)\n", h.b_norm, spmv_amd_precond_kind(m));
     for (int it = 0; it < cfg.max_iters && !op_failed && !h.converged && !h.breakdown; ++it) {
         int pap_count = vec_count;
         T.run(&T.t_spmv, [&] {
@@ -565,9 +1040,19 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
         });
         if (op_failed) break;
         T.run(&T.t_red, [&] { reduce(pap_count, 1, 1); });
-        T.run(&T.t_blas, [&] { launch_pcg_update_r(jac, (size_t)n, w.s, w.Ap, m->dinv, w.r, w.partials); });
-        T.run(&T.t_red, [&] { reduce(vec_count, 2, 2); });
-        T.run(&T.t_blas, [&] { launch_pcg_update_xp(jac, (size_t)n, w.s, w.r, m->dinv, w.p, w.x); });
+        if (cheb) {
+            T.run(&T.t_blas, [&] {
+                launch_cheb_term0<1>((size_t)n, w.s, nullptr, w.Ap, m->dinv, m->coef[0], w.r, w.cd, w.cz, m->degree == 0, w.partials);
+            });
+            T.run(&T.t_red, [&] { reduce(vec_count, 1, 3); });  // r.r and the verdict: the steps below test it on the device
+            const double* const z = cheb_steps_and_rz(&cs->stop, &cs->steps_done, 4);
+            if (op_failed) break;
+            T.run(&T.t_blas, [&] { launch_pcg_update_xp(false, (size_t)n, w.s, z, nullptr, w.p, w.x); });
+        } else {
+            T.run(&T.t_blas, [&] { launch_pcg_update_r(jac, (size_t)n, w.s, w.Ap, m->dinv, w.r, w.partials); });
+            T.run(&T.t_red, [&] { reduce(vec_count, 2, 2); });
+            T.run(&T.t_blas, [&] { launch_pcg_update_xp(jac, (size_t)n, w.s, w.r, m->dinv, w.p, w.x); });
+        }
         download(&h, w.s, 1);  // synchronises: the stopping test
         if (cfg.verbose >= 2)
             printf("[PCG-DEVICE] Iter %3d: residual = %e (rel = %e)\n", h.iterations, h.residual, h.residual / h.b_norm);
@@ -579,6 +1064,8 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
     const int count = h.iterations + 1 < w.hist_cap ? h.iterations + 1 : w.hist_cap;
     g_pcg_history.assign((size_t)count, 0.0);
     download(g_pcg_history.data(), w.hist, (size_t)count);
+    g_cheb_step_launches = 0;
+    if (cheb) download(&g_cheb_step_launches, &cs->steps_done, 1);
     if (op_failed) return 1;
 
     fill_device_stats(stats, h.iterations, h.converged != 0, h.residual, h.b_norm, cfg, total_ms, T.t_spmv, T.t_blas, T.t_red);
@@ -604,6 +1091,8 @@ extern "C" int spmv_amd_pcg_last_history(double* out, int cap) {
 extern "C" void spmv_amd_pcg_release_workspace(void) { spmv_amd::release_cg_workspace(); }
 
 #ifdef SPMV_AMD_LAB
+extern "C" int spmv_amd_pcg_last_step_launches(void) { return g_cheb_step_launches; }
+
 // ---- the loop's kernels one stage at a time on caller data (include/spmv_amd/lab.h; tests/test_pcg_stages_gpu.py) ----
 static_assert(sizeof(SpmvAmdPcgScalars) == sizeof(PcgScalars) && offsetof(SpmvAmdPcgScalars, b_norm) == offsetof(PcgScalars, b_norm) &&
                   offsetof(SpmvAmdPcgScalars, iterations) == offsetof(PcgScalars, iterations) &&

@@ -166,6 +166,11 @@ constexpr int kLdsTileCols = 128;
 // kMode 2 (first SpMV of a solve, x = the initial guess): y is NOT stored; instead r = b - A x (one fma, the
 // reference's axpy_kernel(-1, Ap, b), mgpu :475), p = r, and one partial of r.r per wave -- the initial residual
 // without writing A x0 out and reading it back (16 B/row less, once per solve).
+// kMode 3 (one step of the Chebyshev preconditioner, x = z; kernels.hpp ChebStep): y is NOT stored; the row's sum stays in registers
+// and runs t = fma(-1, sum, r), u = dinv t, d = fma(g, u, h d), z_out = z + d. r, dinv and d are read once (nontemporal, requested
+// with the tile's x loads), d is written back in place, z_out -- another vector than x: neighbouring tiles still read x -- with a
+// plain store, because the next step reads it as x. The last step of an application also leaves one partial of r . z_out per wave.
+// 88 B per interior row (40 coefficients; z, r, dinv, d in; d, z_out out) against 56 + 56 for a SpMV followed by a streaming pass.
 //
 // One tile = local grid row li (global gi), columns [j0, j0 + 128), evaluated by one wave on its private LDS (`strip`:
 // 640 doubles, `xrow`: 130). Returns false if the launch was enqueued past convergence (`skip`: the flag's value,
@@ -188,9 +193,10 @@ template <int kMode, bool kFreshHalo = false, bool kSym = false>
 __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __restrict__ x, double* __restrict__ y, double alpha,
                                             int li, int gi, int j0, int lane, int skip, double* __restrict__ strip,
                                             double* __restrict__ xrow, const ResidualOut& res, double* dot, const SymPlanes& sp = SymPlanes{},
-                                            int tile_class = 0) {
+                                            int tile_class = 0, const ChebStep& step = ChebStep{}) {
     constexpr bool kDot = kMode == 1;
     constexpr bool kInit = kMode == 2;
+    constexpr bool kCheb = kMode == 3;
     const int n = m.grid_size;
     double dot_acc = 0.0;
     if (gi > 0 && gi < n - 1) {
@@ -219,6 +225,7 @@ __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __re
             for (int k = 0; k < 10; ++k) c[k] = __builtin_nontemporal_load(vals + e + 64 * k);
         }
         double xc[2], xw[2], xe[2], xn[2], xs[2], bv[2];
+        double cr[2] = {0.0, 0.0}, cdv[2] = {0.0, 0.0}, cd[2] = {0.0, 0.0};  // kCheb: r, dinv and d of the lane's two rows
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int j = j0 + lane + 64 * h;
@@ -233,6 +240,11 @@ __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __re
                     xn[h] = xl[-n], xs[h] = xl[n];
                 }
                 if (kInit) bv[h] = __builtin_nontemporal_load(res.b + ((long long)li * n + j));
+                if constexpr (kCheb) {  // streams read once per step, requested with the x loads (before the skip flag is tested)
+                    cr[h] = __builtin_nontemporal_load(step.r + ((long long)li * n + j));
+                    cdv[h] = __builtin_nontemporal_load(step.dinv + ((long long)li * n + j));
+                    cd[h] = __builtin_nontemporal_load(step.d + ((long long)li * n + j));
+                }
                 // only the tile's two outer neighbours come from memory; the rest from the LDS copy below
                 if (h == 0 && lane == 0 && j > 0) xw[0] = xl[-1];
                 if (h == 1 && lane == 63 && j < n - 1) xe[1] = xl[1];
@@ -314,7 +326,16 @@ __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __re
                         sum = fma(v[3], xs[h], sum);
                     }
                     if (kDot) dot_acc = fma(xc[h], sum, dot_acc);
-                    if (kInit) {
+                    if constexpr (kCheb) {
+                        const long long lr = (long long)li * n + j;
+                        const double t = fma(-1.0, sum, cr[h]);
+                        const double u = cdv[h] * t;
+                        const double dn = fma(step.g, u, step.h * cd[h]);
+                        const double zn = xc[h] + dn;
+                        __builtin_nontemporal_store(dn, step.d + lr);
+                        step.z_out[lr] = zn;  // plain: the next step's neighbour loads re-use these lines
+                        if (step.last) dot_acc = fma(cr[h], zn, dot_acc);
+                    } else if (kInit) {
                         const long long lr = (long long)li * n + j;
                         const double rv = fma(-1.0, alpha * sum, bv[h]);
                         __builtin_nontemporal_store(rv, res.r + lr);
@@ -362,7 +383,16 @@ __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __re
                 const long long lr = (long long)li * n + j;
                 const double sum = row_reference<false>(m, x, (int)lr, gi, j);
                 if (kDot) dot_acc = fma(x[lr], sum, dot_acc);
-                if (kInit) {
+                if constexpr (kCheb) {
+                    const double rl = step.r[lr];
+                    const double t = fma(-1.0, sum, rl);
+                    const double u = step.dinv[lr] * t;
+                    const double dn = fma(step.g, u, step.h * step.d[lr]);
+                    const double zn = x[lr] + dn;
+                    step.d[lr] = dn;
+                    step.z_out[lr] = zn;
+                    if (step.last) dot_acc = fma(rl, zn, dot_acc);
+                } else if (kInit) {
                     const double rv = fma(-1.0, alpha * sum, res.b[lr]);
                     res.r[lr] = rv;
                     res.p[lr] = rv;
@@ -373,7 +403,7 @@ __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __re
             }
         }
     }
-    if (kDot || kInit) dot_acc = wave_sum(dot_acc);
+    if (kDot || kInit || kCheb) dot_acc = wave_sum(dot_acc);
     *dot = dot_acc;  // lane 0 holds the tile's partial
     return true;
 }
@@ -401,7 +431,7 @@ template <int kMode>
 __global__ __launch_bounds__(64) void stencil5_rowlds_kernel(
     SlabCsr m, const double* __restrict__ x, double* __restrict__ y, double alpha, int gi_lo, int row_step,
     int gfirst, int col_tiles, int total_tiles, int run, int reverse, double* __restrict__ dot_partials,
-    const int* __restrict__ skip_flag, ResidualOut res, SymPlanes sp) {
+    const int* __restrict__ skip_flag, ResidualOut res, SymPlanes sp, ChebStep step) {
     __shared__ double strip[5 * kLdsTileCols];  // the tile's coefficients; the symmetric form: its E values (W of the next row)
     __shared__ double xrow[kLdsTileCols + 2];  // the tile's x values: W / E are read back from here
     const int skip = skip_flag != nullptr ? __builtin_nontemporal_load(skip_flag) : 0;
@@ -414,6 +444,15 @@ __global__ __launch_bounds__(64) void stencil5_rowlds_kernel(
     double dot = 0.0;
     // the coefficient form is a launch argument (one uniform branch), not a template argument: the in-loop SpMV keeps the one
     // kernel symbol, stencil5_rowlds_kernel<1>, that bench.py and profiles/hbm_traffic.json identify it by
+    if constexpr (kMode == 3) {  // the CSR coefficients only: the symmetric planes belong to the slab solver
+        if (!rowlds_tile<3>(m, x, y, alpha, li, gfirst + li, col_tile * kLdsTileCols, (int)threadIdx.x, skip, strip, xrow, res, &dot, sp, 0, step))
+            return;
+        if (threadIdx.x == 0) {
+            if (step.last) dot_partials[tile] = dot;
+            if (tile == 0 && step.work_count != nullptr) *step.work_count += 1;  // one thread per launch; launches are ordered
+        }
+        return;
+    }
     const bool live = sp.ce != nullptr
                           ? rowlds_tile<kMode, false, true>(m, x, y, alpha, li, gfirst + li, col_tile * kLdsTileCols, (int)threadIdx.x, skip, strip,
                                                             xrow, res, &dot, sp, uniform)
@@ -1085,7 +1124,7 @@ namespace {
 // the row-lds kernel over `tiles` tiles: `row_step` grid rows between consecutive row groups (1: a contiguous range)
 void launch_rowlds(const SlabCsr& m, const Stencil5Plan& p, const double* x, double* y, double alpha, int gi_lo, int row_step,
                    int tiles, double* d_dot_partials, const int* d_skip_flag, bool reverse, hipStream_t stream, const ResidualOut* init,
-                   const SymPlanes* planes) {
+                   const SymPlanes* planes, const ChebStep* step = nullptr) {
     const int span = 8 * p.xcd_run;
     const dim3 grid((unsigned)(((long long)tiles + span - 1) / span * span));
     const int gfirst = m.row_offset / m.grid_size;
@@ -1093,8 +1132,10 @@ void launch_rowlds(const SlabCsr& m, const Stencil5Plan& p, const double* x, dou
     const SymPlanes sp = planes ? *planes : SymPlanes{};
 #define SPMV_AMD_LAUNCH_ROWLDS(MODE)                                                                                   \
     hipLaunchKernelGGL((stencil5_rowlds_kernel<MODE>), grid, dim3(64), 0, stream, m, x, y, alpha, gi_lo, row_step, gfirst, \
-                       p.row_blocks, tiles, p.xcd_run, reverse ? 1 : 0, d_dot_partials, d_skip_flag, res, sp)
-    if (init) SPMV_AMD_LAUNCH_ROWLDS(2);
+                       p.row_blocks, tiles, p.xcd_run, reverse ? 1 : 0, d_dot_partials, d_skip_flag, res, sp, cs)
+    const ChebStep cs = step ? *step : ChebStep{};
+    if (step) SPMV_AMD_LAUNCH_ROWLDS(3);
+    else if (init) SPMV_AMD_LAUNCH_ROWLDS(2);
     else if (d_dot_partials) SPMV_AMD_LAUNCH_ROWLDS(1);
     else SPMV_AMD_LAUNCH_ROWLDS(0);
 #undef SPMV_AMD_LAUNCH_ROWLDS
@@ -1136,6 +1177,13 @@ int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& p, const double* 
 #undef SPMV_AMD_LAUNCH_ROWS
     }
     return dot ? p.partials : 0;
+}
+
+int launch_stencil5_cheb_step(const SlabCsr& m, const Stencil5Plan& p, const double* z, const ChebStep& step, double* d_dot_partials,
+                              const int* d_skip_flag, hipStream_t stream) {
+    if (p.variant != Stencil5Variant::RowLds || p.last_row <= p.first_row) return -1;
+    launch_rowlds(m, p, z, nullptr, 1.0, p.gi_lo, 1, p.partials, d_dot_partials, d_skip_flag, false, stream, nullptr, nullptr, &step);
+    return p.partials;
 }
 
 int launch_stencil5_spmv_first_and_last_gridrow(const SlabCsr& m, const Stencil5Plan& head, const Stencil5Plan& tail, const double* x,

@@ -300,6 +300,28 @@ SpmvAmdPrecond* spmv_amd_precond_create(SpmvOperator* op, const char* kind, int*
 /* Jacobi from a caller's device diagonal of n values (the same validity rule): the way in for operators this library does
  * not own. Usable with any operator of n rows. */
 SpmvAmdPrecond* spmv_amd_precond_create_from_diagonal(const double* d_diag, int n, int* bad_row);
+/* Kind "chebyshev" (DESIGN.md section 14): z = M^-1 r is the degree-`degree` Chebyshev polynomial in B = D^-1 A on [lambda_min,
+ * lambda_max], applied with SpMVs and streaming updates only; degree 0 is Jacobi scaled by c0. The operator must be one of this
+ * library's (there is no from-diagonal form); dinv = 1 / d under Jacobi's validity rule (*bad_row as there). degree: 0..32 = steps =
+ * SpMVs per application. lambda_max > 0: used as given; otherwise the symmetric Gershgorin bound max_i sum_j |a_ij| sqrt(|dinv_i|
+ * |dinv_j|), row i summed in storage order from 0.0 (a bound on D^-1/2 A D^-1/2, invariant under symmetric diagonal scaling).
+ * lambda_min > 0: used as given; otherwise lambda_max / 30.0. Refused (NULL) unless 0 < lambda_min < lambda_max, both finite; a NaN or
+ * infinite argument, a degree out of range, a null or uninitialised operator are refused before any HIP call.
+ * Coefficients, host fp64, one rounding per operation, in this order: theta = 0.5 (lmax + lmin); delta = 0.5 (lmax - lmin);
+ * sigma = theta / delta; c0 = 1.0 / theta; rho = 1.0 / sigma; for k = 1..degree: rho' = 1.0 / (2.0 sigma - rho); h_k = rho' rho;
+ * g_k = 2.0 rho' / delta; rho = rho'.
+ * Application, element-wise:  term 0: u = dinv r; d = c0 u; z = d.   step k: w = A z (the operator's own bits); t = fma(-1.0, w, r);
+ * u = dinv t; d = fma(g_k, u, h_k d); z = z + d.
+ * With lambda_max a true upper bound M^-1 A has its spectrum in (0, 2): PCG stays valid; negative-definite matrices work as under
+ * Jacobi. On a well-conditioned matrix the polynomial costs more than it saves (DESIGN.md section 14 has the numbers). */
+SpmvAmdPrecond* spmv_amd_precond_create_chebyshev(SpmvOperator* op, int degree, double lambda_min, double lambda_max, int* bad_row);
+/* degree, interval, and up to cap coefficients in the order c0, h_1, g_1, h_2, g_2, ...; returns how many exist (1 + 2*degree);
+ * 0 for another kind (nothing is written). Any out pointer may be NULL. */
+int spmv_amd_precond_chebyshev_info(const SpmvAmdPrecond* m, int* degree, double* lambda_min, double* lambda_max, double* coefficients, int cap);
+/* z = M^-1 r on device vectors of n rows (16-byte aligned), any kind (none: copy, jacobi: dinv*r). d_z must not overlap d_r, which is
+ * only read. rz (may be NULL): r.z summed by the solver's own fixed-shape reduction. The pair (op, m) is checked as by
+ * spmv_amd_pcg_solve_device, before any HIP call. Work vectors live for the call only. Synchronises. Returns 0, non-zero for a refusal. */
+int spmv_amd_precond_apply_device(SpmvOperator* op, const SpmvAmdPrecond* m, const double* d_r, double* d_z, double* rz);
 void spmv_amd_precond_destroy(SpmvAmdPrecond* m);
 /* "none", "jacobi"; "invalid" for NULL. */
 const char* spmv_amd_precond_kind(const SpmvAmdPrecond* m);
@@ -307,8 +329,8 @@ const char* spmv_amd_precond_kind(const SpmvAmdPrecond* m);
 int spmv_amd_precond_inverse_diagonal(const SpmvAmdPrecond* m, double* out, int n);
 /* Preconditioned CG on the device. b, x: host arrays of mat->rows values, x in = x0, out = solution (uploaded before and
  * downloaded after the timed region). Refused: NULL pointers, an uninitialised or non-square operator, n != mat->rows, a
- * preconditioner made from another operator or from an earlier init of this one. The workspace (x, b, r, p, Ap) is sized
- * against the device's free memory first, kept between calls and released with cg_solve_device's (an operator's free(),
+ * preconditioner made from another operator or from an earlier init of this one. The workspace (x, b, r, p, Ap; kind
+ * "chebyshev": d, z and a second z as well) is sized against the device's free memory first, kept between calls and released with cg_solve_device's (an operator's free(),
  * spmv_amd_cg_release_workspace(), spmv_amd_pcg_release_workspace()). */
 int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, const double* b, double* x,
                               const CGConfig* config, CGStats* stats);

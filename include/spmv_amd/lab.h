@@ -92,6 +92,11 @@ typedef struct SpmvAmdPcgStageArgs {
  * Returns 0 otherwise. */
 int spmv_amd_pcg_stage(const char* stage, const char* kind, SpmvAmdPcgStageArgs* a, SpmvAmdPcgScalars* scalars);
 
+/* Kind "chebyshev": how many step launches of the last solve's LOOP did work, i.e. were not stopped by the iteration's verdict (the
+ * application behind the initial residual is not counted). Every iteration but the converging one runs `degree` of them:
+ * degree * (iterations - 1) for a solve that converged. 0 after a solve of another kind. */
+int spmv_amd_pcg_last_step_launches(void);
+
 #ifdef __cplusplus
 }
 #endif
