@@ -87,6 +87,19 @@ class PcgStageArgs(C.Structure):
                 ("hist", C.c_void_p), ("hist_cap", C.c_int)]
 
 
+class MultiColumn(C.Structure):
+    """SpmvAmdMultiColumn (include/spmv_amd/lab.h): the per-column state of a batched CG solve."""
+    _fields_ = [("rr_old", C.c_double), ("pAp", C.c_double), ("alpha", C.c_double), ("beta", C.c_double), ("b_norm", C.c_double),
+                ("residual", C.c_double), ("active", C.c_int), ("done", C.c_int), ("iterations", C.c_int), ("pad", C.c_int)]
+
+
+class CgMultiStageArgs(C.Structure):
+    """SpmvAmdCgMultiStageArgs (include/spmv_amd/lab.h): device pointers and sizes of one spmv_amd_cg_multi_stage call."""
+    _fields_ = [("mode", C.c_char_p), ("n", C.c_size_t), ("X", C.c_void_p), ("R", C.c_void_p), ("P", C.c_void_p), ("AP", C.c_void_p),
+                ("cols", C.c_void_p), ("partials", C.c_void_p), ("count", C.c_longlong), ("which", C.c_int), ("tol", C.c_double),
+                ("hist", C.c_void_p), ("hist_cap", C.c_int), ("xcd_run", C.c_int)]
+
+
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
 GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int))
@@ -122,7 +135,7 @@ DECLARED_SYMBOLS = [
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
 LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_pcg_stage",
-                    "spmv_amd_pcg_last_step_launches"]
+                    "spmv_amd_pcg_last_step_launches", "spmv_amd_cg_multi_stage"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
 DECLARED_CXX_SYMBOLS = [
     "SPMV_CSR", "SPMV_STENCIL5_CSR", "SPMV_STENCIL_HALO_MGPU", "SPMV_ELLPACK", "SPMV_STENCIL5_ELLPACK",
@@ -219,6 +232,8 @@ def lib():
         L.spmv_amd_pcg_stage.restype = C.c_int
         L.spmv_amd_pcg_last_step_launches.argtypes = []
         L.spmv_amd_pcg_last_step_launches.restype = C.c_int
+        L.spmv_amd_cg_multi_stage.argtypes = [C.c_char_p, C.c_int, C.POINTER(CgMultiStageArgs)]
+        L.spmv_amd_cg_multi_stage.restype = C.c_int
     L.spmv_amd_cg_slab_create.restype = C.c_void_p
     L.spmv_amd_cg_slab_create.argtypes = [C.POINTER(MatrixData), C.c_void_p]
     L.spmv_amd_cg_slab_create_stencil5.restype = C.c_void_p
@@ -563,6 +578,14 @@ def cg_solve_multi(op, host_matrix, Bk, X0k, max_iters=1000, tol=1e-6, verbose=0
         count = L.spmv_amd_cg_last_history_multi(j, h.ctypes.data, len(h))
         hists.append(h[:count].copy())
     return X, hists, list(stats)
+
+
+def cg_multi_stage(stage, k, args):
+    """spmv_amd_cg_multi_stage (LAB build only; include/spmv_amd/lab.h): one stage of the batched solver's own kernels on the
+    device data `args` (CgMultiStageArgs) points to; returns its return code (0, or non-zero for a refusal)."""
+    if not is_lab():
+        raise RuntimeError("the batched-CG stages exist in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+    return lib().spmv_amd_cg_multi_stage(stage if stage is None else stage.encode(), int(k), None if args is None else C.byref(args))
 
 
 # ---------------------------------------------------------------- preconditioned CG (include/spmv_amd/api.h)

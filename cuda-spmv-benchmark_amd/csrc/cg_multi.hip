@@ -13,7 +13,9 @@
 // Bytes per interior row and iteration, per system: (40 + 80 k) / k.
 // No run-ahead, no direction ring, no status protocol: that machinery (cg_slab.hip) buys microseconds per iteration of a
 // single solve; here an iteration is k times longer.
+#include <limits.h>
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -24,6 +26,8 @@
 #include "reduce_device.hpp"
 #include "solve_common.hpp"
 #include "stream_device.hpp"
+
+#include "spmv_amd/lab.h"
 
 using namespace spmv_amd;
 
@@ -269,6 +273,15 @@ void launch_vector_step(int k, int which, long long n, const MultiColumn* cols, 
 
 int slices_for(long long count) { return (int)((count + kSlice - 1) / kSlice); }
 
+// The two reduction launches behind every dot product: k x slices_for(count) slice sums, then per column their sum and the
+// scalar step `which`. slices: k x slices_for(count) doubles.
+void launch_reduce(int k, const double* partials, long long count, double* slices, int which, double tol, MultiColumn* cols, double* hist,
+                   int hist_cap) {
+    const int sc = slices_for(count);
+    hipLaunchKernelGGL(multi_reduce_slices_kernel, dim3((unsigned)sc, (unsigned)k), dim3(kBlock), 0, kStream, partials, count, sc, slices);
+    hipLaunchKernelGGL(multi_reduce_step_kernel, dim3((unsigned)k), dim3(kBlock), 0, kStream, slices, sc, which, tol, cols, hist, hist_cap);
+}
+
 // ---- workspace: kept between calls (like cg_solve_device's), released with it ----
 struct MultiWorkspace {
     int n = 0, k = 0, device = -1;
@@ -456,11 +469,7 @@ extern "C" int spmv_amd_cg_solve_device_multi(SpmvOperator* op, MatrixData* mat,
     std::vector<MultiColumn> h_cols((size_t)k);
     StageTimers T(cfg.enable_detailed_timers != 0, kStream);
     auto reduce = [&](long long count, int which) {
-        const int sc = slices_for(count);
-        hipLaunchKernelGGL(multi_reduce_slices_kernel, dim3((unsigned)sc, (unsigned)k), dim3(kBlock), 0, kStream, w.partials, count, sc,
-                           w.slices);
-        hipLaunchKernelGGL(multi_reduce_step_kernel, dim3((unsigned)k), dim3(kBlock), 0, kStream, w.slices, sc, which, cfg.tolerance, w.cols,
-                           w.hist, w.hist_cap);
+        launch_reduce(k, w.partials, count, w.slices, which, cfg.tolerance, w.cols, w.hist, w.hist_cap);
     };
     auto read_columns = [&] { download(h_cols.data(), w.cols, (size_t)k); };
 
@@ -530,3 +539,92 @@ extern "C" int spmv_amd_cg_last_history_multi(int rhs, double* out, int cap) {
     if (rhs < 0 || rhs >= (int)g_multi_history.size()) return -1;
     return copy_history(g_multi_history[(size_t)rhs], out, cap);
 }
+
+#ifdef SPMV_AMD_LAB
+// ---- the loop's kernels one stage at a time on caller data (include/spmv_amd/lab.h; tests/test_multi_rhs_stages_gpu.py) ----
+static_assert(sizeof(SpmvAmdMultiColumn) == sizeof(MultiColumn) && offsetof(SpmvAmdMultiColumn, rr_old) == offsetof(MultiColumn, rr_old) &&
+                  offsetof(SpmvAmdMultiColumn, pAp) == offsetof(MultiColumn, pAp) && offsetof(SpmvAmdMultiColumn, alpha) == offsetof(MultiColumn, alpha) &&
+                  offsetof(SpmvAmdMultiColumn, beta) == offsetof(MultiColumn, beta) && offsetof(SpmvAmdMultiColumn, b_norm) == offsetof(MultiColumn, b_norm) &&
+                  offsetof(SpmvAmdMultiColumn, residual) == offsetof(MultiColumn, residual) &&
+                  offsetof(SpmvAmdMultiColumn, active) == offsetof(MultiColumn, active) && offsetof(SpmvAmdMultiColumn, done) == offsetof(MultiColumn, done) &&
+                  offsetof(SpmvAmdMultiColumn, iterations) == offsetof(MultiColumn, iterations),
+              "lab.h's column record is the device record, field for field");
+
+namespace {
+bool stage_fail(const char* stage, const char* what) {
+    fprintf(stderr, "[CG-MULTI] stage '%s': %s: refused\n", stage ? stage : "(null)", what);
+    return false;
+}
+// a pointer the stage needs, aligned to `align` bytes (16: a block vector the vector kernels access in 16-byte pairs)
+bool stage_pointer(const char* stage, const char* name, const void* p, int align) {
+    char what[64];
+    if (p == nullptr) {
+        snprintf(what, sizeof what, "%s is null", name);
+        return stage_fail(stage, what);
+    }
+    if (((uintptr_t)p & (uintptr_t)(align - 1)) != 0) {
+        snprintf(what, sizeof what, "%s is not %d-byte aligned", name, align);
+        return stage_fail(stage, what);
+    }
+    return true;
+}
+}  // namespace
+
+extern "C" int spmv_amd_cg_multi_stage(const char* stage, int k, SpmvAmdCgMultiStageArgs* a) {
+    // argument checks: all before the first HIP call
+    enum { kSpmm, kInit, kUpdateR, kUpdateXp, kReduce } st;
+    if (stage == nullptr) return stage_fail(stage, "no stage named (spmm, init, update_r, update_xp, reduce)"), 1;
+    if (!strcmp(stage, "spmm")) st = kSpmm;
+    else if (!strcmp(stage, "init")) st = kInit;
+    else if (!strcmp(stage, "update_r")) st = kUpdateR;
+    else if (!strcmp(stage, "update_xp")) st = kUpdateXp;
+    else if (!strcmp(stage, "reduce")) st = kReduce;
+    else return stage_fail(stage, "unknown stage (spmm, init, update_r, update_xp, reduce)"), 1;
+    if (k < 1 || k > kMaxRhs) return stage_fail(stage, "k is not 1 to 8"), 1;
+    if (a == nullptr) return stage_fail(stage, "null arguments"), 1;
+    MultiOperand o;
+    if (st == kSpmm) {
+        if (!stage_pointer(stage, "X", a->X, 8) || !stage_pointer(stage, "AP", a->AP, 8)) return 1;
+        if (a->partials != nullptr && !stage_pointer(stage, "partials", a->partials, 8)) return 1;
+        if (a->xcd_run < 0) return stage_fail(stage, "xcd_run < 0"), 1;
+        if (a->mode == nullptr) return stage_fail(stage, "no operator named"), 1;
+        SpmvOperator* op = get_operator(a->mode);
+        if (op == nullptr) return stage_fail(stage, "unknown operator"), 1;
+        if (!usable_operator(op, &o)) return stage_fail(stage, "the operator has no usable multi-RHS path"), 1;
+    } else if (st == kReduce) {
+        if (a->count < 1) return stage_fail(stage, "count < 1"), 1;
+        if (a->which < 0 || a->which > 2) return stage_fail(stage, "which is not 0, 1 or 2"), 1;
+        if (a->hist_cap < 0) return stage_fail(stage, "hist_cap < 0"), 1;
+        if (a->which == 0 && a->hist_cap < 1) return stage_fail(stage, "hist_cap < 1 for step 0, which writes the first entry"), 1;
+        if (!stage_pointer(stage, "partials", a->partials, 8) || !stage_pointer(stage, "cols", a->cols, 8)) return 1;
+        if (a->hist_cap > 0 && !stage_pointer(stage, "hist", a->hist, 8)) return 1;
+    } else {
+        if (a->n < 1 || a->n > (size_t)INT_MAX) return stage_fail(stage, "n < 1 or beyond the solver's int rows"), 1;
+        if (st != kInit && !stage_pointer(stage, "cols", a->cols, 8)) return 1;
+        if (st != kUpdateXp && (!stage_pointer(stage, "AP", a->AP, 16) || !stage_pointer(stage, "partials", a->partials, 8))) return 1;
+        if (!stage_pointer(stage, "R", a->R, 16)) return 1;
+        if (st != kUpdateR && !stage_pointer(stage, "P", a->P, 16)) return 1;
+        if (st == kUpdateXp && !stage_pointer(stage, "X", a->X, 16)) return 1;
+    }
+
+    MultiColumn* cols = reinterpret_cast<MultiColumn*>(a->cols);
+    double* slices = nullptr;
+    if (st == kSpmm) {
+        SpmmPlan plan = o.plan;
+        if (a->xcd_run > 0) plan.xcd_run = a->xcd_run;
+        launch_spmm(plan, k, a->X, a->AP, a->partials, kStream);
+        a->count = plan.blocks;
+    } else if (st == kReduce) {
+        slices = device_alloc<double>((size_t)k * slices_for(a->count));
+        launch_reduce(k, a->partials, a->count, slices, a->which, a->tol, cols, a->hist, a->hist_cap);
+    } else {
+        const long long n = (long long)a->n, count = (n + kBlock - 1) / kBlock;
+        launch_vector_step(k, st == kInit ? 0 : st == kUpdateR ? 1 : 2, n, cols, a->X, a->R, a->P, a->AP, a->partials, count);
+        a->count = count;
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    device_release(slices);
+    return 0;
+}
+#endif  // SPMV_AMD_LAB

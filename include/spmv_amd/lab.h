@@ -97,6 +97,61 @@ int spmv_amd_pcg_stage(const char* stage, const char* kind, SpmvAmdPcgStageArgs*
  * degree * (iterations - 1) for a solve that converged. 0 after a solve of another kind. */
 int spmv_amd_pcg_last_step_launches(void);
 
+/* Per-column state of a batched CG solve (csrc/multi_rhs.hpp keeps the same record on the device, one per column). */
+typedef struct SpmvAmdMultiColumn {
+    double rr_old;    /* r.r of the last iteration that did not converge */
+    double pAp, alpha, beta;
+    double b_norm;    /* ||r0|| */
+    double residual;  /* ||r_k|| */
+    int active;       /* the column takes part in the current iteration (the pAp step sets it: !done) */
+    int done;         /* converged: frozen from the next iteration on */
+    int iterations;
+    int pad;
+} SpmvAmdMultiColumn;
+
+/* Device pointers and sizes of one spmv_amd_cg_multi_stage call; a stage reads only the fields listed for it. Block vectors
+ * are row-interleaved, k columns: element (row, column j) at [row * k + j] (api.h, spmv_amd_spmm_device). */
+typedef struct SpmvAmdCgMultiStageArgs {
+    const char* mode;          /* spmm: the operator's name ("stencil5-csr", "cusparse-csr"), initialised */
+    size_t n;                  /* init, update_r, update_xp: rows */
+    double* X;                 /* spmm: in; update_xp: in and out */
+    double* R;                 /* init: in (b) and out; update_r: in and out; update_xp: in */
+    double* P;                 /* init: out; update_xp: in and out */
+    double* AP;                /* spmm: out (A X); init, update_r: in */
+    SpmvAmdMultiColumn* cols;  /* update_r, update_xp: in; reduce: in and out -- k records, DEVICE memory */
+    double* partials;          /* spmm (may be null: no dot products), init, update_r: out, column j's partial of workgroup g at
+                                  [j * count + g]; reduce: in, the same layout */
+    long long count;           /* spmm, init, update_r: out, the workgroups of the launch = partials per column (the buffer holds
+                                  k * count doubles: the operator's SpMM blocks, (n + 255) / 256 for the vector stages); reduce: in */
+    int which;                 /* reduce: the scalar step, 0 = initial r.r, 1 = p.Ap, 2 = r.r */
+    double tol;                /* reduce, which = 2 */
+    double* hist;              /* reduce: k histories of hist_cap doubles, column j's at [j * hist_cap] (may be null when
+                                  hist_cap is 0) */
+    int hist_cap;
+    int xcd_run;               /* spmm: > 0 replaces the plan's XCD run length for this launch (row-lds looks at it, no other
+                                  kind); 0 = the plan's own */
+} SpmvAmdCgMultiStageArgs;
+
+/* The batched solver's own kernels (csrc/spmm_kernels.hip, csrc/cg_multi.hip), one stage per call on the caller's device data
+ * -- the launches spmv_amd_cg_solve_device_multi makes, through the functions it makes them with, for k = 1..8 columns. The
+ * model is spmv_amd_pcg_stage; tests/test_multi_rhs_stages_gpu.py holds each stage against the oracle. Every call
+ * synchronises. stage:
+ *   "spmm"       AP = A X on the operator `mode`; with partials, the per-column partials of x.(A x); sets a->count to the
+ *                plan's workgroups
+ *   "init"       R = R - AP (R holds b on entry), P = R, the partials of r.r; sets a->count
+ *   "update_r"   r_j = fma(-alpha_j, Ap_j, r_j) for the columns with cols[j].active, the partials of r.r of every column;
+ *                sets a->count
+ *   "update_xp"  for the columns with cols[j].active: x_j = fma(alpha_j, p_j, x_j) and, unless cols[j].done,
+ *                p_j = fma(beta_j, p_j, r_j)
+ *   "reduce"     the sums of a->count partials of each column, then the scalar step `which` on cols[j] with a->tol, a->hist and
+ *                a->hist_cap (step 0 writes hist[j * hist_cap] unconditionally: it needs hist_cap >= 1, as the solve's
+ *                max_iters + 1 is)
+ * Refused before any HIP call, with a sentence on stderr and a non-zero return: an unknown stage, k outside 1..8, null
+ * arguments, a null pointer the stage needs, n < 1, count < 1, which outside 0..2, hist_cap < 0 (< 1 for step 0), a block vector
+ * of a vector stage that is not 16-byte aligned, one of "spmm" that is not 8-byte aligned, partials, cols or hist that are not
+ * 8-byte aligned, xcd_run < 0, an operator that is unknown, not initialised or without a multi-RHS path. Returns 0 otherwise. */
+int spmv_amd_cg_multi_stage(const char* stage, int k, SpmvAmdCgMultiStageArgs* a);
+
 #ifdef __cplusplus
 }
 #endif

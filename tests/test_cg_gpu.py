@@ -766,6 +766,8 @@ def test_the_product_library_has_no_hooks(B, monkeypatch):
         assert not hasattr(B.lib(), name), name
     with pytest.raises(RuntimeError):
         B.CgSlab.stencil5_as(640, 0, 2, None)
+    with pytest.raises(RuntimeError):
+        B.cg_multi_stage("reduce", 1, B.CgMultiStageArgs())
     monkeypatch.setenv("SPMV_AMD_SELF_NEIGHBOUR", "1")
     monkeypatch.setenv("SPMV_AMD_FORCE_COLLECTIVES", "1")
     monkeypatch.setenv("SPMV_AMD_TEST_WEDGE_OVERLAPPED_EXCHANGE", "2")

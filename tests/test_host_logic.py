@@ -212,6 +212,7 @@ def test_hooks_live_in_the_lab_build_only(B):
     lab_h = open(os.path.join(ROOT, "include", "spmv_amd", "lab.h")).read()
     for name in B.LAB_ONLY_SYMBOLS:
         assert name not in api and name in lab_h
+    assert {"spmv_amd_pcg_stage", "spmv_amd_cg_multi_stage"} <= set(B.LAB_ONLY_SYMBOLS)  # the per-kernel stage hooks of the solvers
     blob, lab_blob = open(B.LIB_PATH, "rb").read(), open(B.LAB_LIB_PATH, "rb").read()
     for word in (b"SPMV_AMD_TEST_WEDGE_OVERLAPPED_EXCHANGE", b"SPMV_AMD_SELF_NEIGHBOUR", b"SPMV_AMD_FORCE_COLLECTIVES", b"SPMV_AMD_PLACEMENT_FAIL_AFTER",
                  b"stop_at", b"spmv_event_stride", b"lead_rows"):

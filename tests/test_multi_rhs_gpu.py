@@ -13,7 +13,7 @@ from conftest import GOLDEN, hist_err
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-10
-KS = [1, 2, 3, 4, 8]
+KS = list(range(1, 9))  # every instantiation of the kernel templates
 
 
 def random_stencil(O, n, seed):
@@ -72,7 +72,7 @@ def test_spmm_structured_non_stencil_matrices(B, O, fresh_host_matrices, fixture
         assert op.init(m) == 0
         if mode == "stencil5-csr":
             assert op.spmm_variant() == "spmm/stencil5-row-generic(csr-loop)"
-        for k in (1, 3, 8):
+        for k in KS:
             Y = op.run_spmm(X[:k])
             for j in range(k):
                 assert np.array_equal(Y[j], want[j]), (mode, k, j)
@@ -162,12 +162,15 @@ def stats_tuple(s):
     return (s.iterations, s.residual_norm, s.converged, s.solution_sum, s.solution_norm)
 
 
-def test_cg_multi_columns_are_independent_bit_for_bit(B, O, fresh_host_matrices):
-    n = 200
+@pytest.mark.parametrize("n, mode", [(200, "stencil5-csr"), (512, "stencil5-csr"), (200, "cusparse-csr")])
+def test_cg_multi_columns_are_independent_bit_for_bit(B, O, fresh_host_matrices, n, mode):
+    """n = 200 takes row-direct, n = 512 row-lds, cusparse-csr the flat-row kernel: each has its own dot-partial geometry."""
     N = n * n
     m = B.HostMatrix(O.stencil5_coo(n), N, N, n)
-    op = B.Operator("stencil5-csr")
+    op = B.Operator(mode)
     assert op.init(m) == 0
+    assert op.spmm_variant() == {(200, "stencil5-csr"): "spmm/stencil5-row-direct", (512, "stencil5-csr"): "spmm/stencil5-row-lds",
+                                 (200, "cusparse-csr"): "spmm/csr"}[(n, mode)]
     rng = np.random.default_rng(11)
     base = rng.standard_normal(N)
     Bk = np.stack([base, np.ones(N), eigenmode(n), rng.standard_normal(N), 2.0 * base, np.ones(N) + 0.01 * np.sin(np.arange(N)),
@@ -179,8 +182,8 @@ def test_cg_multi_columns_are_independent_bit_for_bit(B, O, fresh_host_matrices)
     for slot, j in enumerate(perm):
         assert np.array_equal(Xp[slot], X[j]) and np.array_equal(hp[slot], hists[j]), (slot, j)
         assert stats_tuple(sp[slot]) == stats_tuple(stats[j])
-    # the same column alone, in pairs, in fours, in eights
-    for k in (1, 2, 4, 8):
+    # the same column alone, in pairs, in threes, ... in eights
+    for k in KS:
         cols = [(3 + i) % 8 for i in range(k)]
         Xk, hk, sk = B.cg_solve_multi(op, m, Bk[cols], np.zeros((k, N)))
         for slot, j in enumerate(cols):
@@ -189,6 +192,41 @@ def test_cg_multi_columns_are_independent_bit_for_bit(B, O, fresh_host_matrices)
     # b and 2b: scaling by 2 is exact, so the histories and solutions are exactly doubled
     assert np.array_equal(hists[4], 2.0 * hists[0]) and np.array_equal(X[4], 2.0 * X[0])
     assert stats[4].iterations == stats[0].iterations
+    op.free()
+
+
+@pytest.mark.parametrize("n", [130, 512])
+def test_cg_multi_a_bad_column_leaves_its_neighbours_alone(B, O, fresh_host_matrices, n):
+    """One column whose right-hand side is zero (0 / 0 in the first alpha) or holds one NaN, in slot 0, slot 1 or the last slot of
+    a batch of 2, 5 or 6 (pairs of columns share 16-byte loads and stores where k is even): every healthy column's x, history and
+    statistics are bit for bit those of the batch without the bad column; the bad column never meets the stopping test, as in
+    the oracle: max_iters iterations, not converged, a history of max_iters + 1 entries. The call returns 0."""
+    N = n * n
+    iters = 8
+    m = B.HostMatrix(O.stencil5_coo(n), N, N, n)
+    rp, ci, va = O.stencil5_csr(n)
+    op = B.Operator("stencil5-csr")
+    assert op.init(m) == 0
+    rng = np.random.default_rng(17)
+    healthy = np.stack([rng.standard_normal(N), eigenmode(n), np.ones(N), rng.uniform(0, 1, N), np.ones(N) + 0.01 * np.sin(np.arange(N))])
+    one_nan = rng.standard_normal(N)
+    one_nan[N // 2 + 1] = np.nan
+    for what, bad in (("zero", np.zeros(N)), ("nan", one_nan)):
+        _, ho, ro = O.cg(rp, ci, va, n, bad, np.zeros(N), max_iters=iters)
+        assert ro.iterations == iters and not ro.converged and len(ho) == iters + 1
+        for k in (2, 5, 6):
+            Xh, hh, sh = B.cg_solve_multi(op, m, healthy[:k - 1], np.zeros((k - 1, N)), max_iters=iters)  # raises unless it returns 0
+            assert k == 2 or sh[1].converged == 1  # the eigenmode: a frozen column next to the bad one
+            for slot in sorted({0, 1, k - 1}):
+                Bk = np.insert(healthy[:k - 1], slot, bad, axis=0)
+                X, hists, stats = B.cg_solve_multi(op, m, Bk, np.zeros((k, N)), max_iters=iters)
+                assert stats[slot].iterations == ro.iterations and stats[slot].converged == ro.converged, (what, k, slot)
+                assert len(hists[slot]) == len(ho), (what, k, slot)
+                others = [s for s in range(k) if s != slot]
+                for j, s in enumerate(others):
+                    assert np.array_equal(X[s], Xh[j]) and np.array_equal(hists[s], hh[j]), (what, k, slot, s)
+                    assert stats_tuple(stats[s]) == stats_tuple(sh[j]), (what, k, slot, s)
+                    assert np.all(np.isfinite(X[s])) and np.all(np.isfinite(hists[s])), (what, k, slot, s)
     op.free()
 
 
@@ -262,7 +300,7 @@ def test_spmm_on_8_byte_aligned_block_vectors(B, O, fresh_host_matrices, mode):
     L = B._multi_lib()
     for forced in (("row-lds", "row-direct", "row-generic") if mode == "stencil5-csr" else (None,)):
         op.select_variant(forced)
-        for k in (2, 3, 4, 8):
+        for k in KS:
             inter = np.ascontiguousarray(X[:k].T).ravel()  # interleaved: [row * k + j]
             dx = B.DeviceVector.from_host(np.concatenate([[0.0], inter]))
             dy = B.DeviceVector(rows * k + 2, fill=-7.0)
