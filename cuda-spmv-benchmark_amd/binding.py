@@ -134,7 +134,7 @@ DECLARED_SYMBOLS = [
     "spmv_amd_precond_create_chebyshev", "spmv_amd_precond_chebyshev_info", "spmv_amd_precond_apply_device",
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
-LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_pcg_stage",
+LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_cg_slab_block_map", "spmv_amd_pcg_stage",
                     "spmv_amd_pcg_last_step_launches", "spmv_amd_cg_multi_stage"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
 DECLARED_CXX_SYMBOLS = [
@@ -228,6 +228,8 @@ def lib():
         L.spmv_amd_cg_slab_set_option.restype = C.c_int
         L.spmv_amd_cg_slab_tile_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong]
         L.spmv_amd_cg_slab_tile_classes.restype = C.c_longlong
+        L.spmv_amd_cg_slab_block_map.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
+        L.spmv_amd_cg_slab_block_map.restype = C.c_longlong
         L.spmv_amd_pcg_stage.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PcgStageArgs), C.POINTER(PcgScalars)]
         L.spmv_amd_pcg_stage.restype = C.c_int
         L.spmv_amd_pcg_last_step_launches.argtypes = []
@@ -919,6 +921,22 @@ class CgSlab:
         out = np.zeros(count, dtype=np.uint8)
         lib().spmv_amd_cg_slab_tile_classes(self.h, out.ctypes.data, count)
         return out
+
+    def block_map(self, which):
+        """The block map of a launch range of the in-loop SpMV (LAB build only): which = 0 the whole slab, 1 the rows that need no
+        halo. uint8, one byte per block tile (row blocks x tiles per grid row, flat), 1 = the fast path; None = the range has no map."""
+        if not is_lab():
+            raise RuntimeError("the block maps are read through the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        count = int(lib().spmv_amd_cg_slab_block_map(self.h, int(which), None, 0))
+        if count == 0:
+            return None
+        out = np.zeros(count, dtype=np.uint8)
+        lib().spmv_amd_cg_slab_block_map(self.h, int(which), out.ctypes.data, count)
+        return out
+
+    def set_block_rows(self, rows):
+        """Grid rows per block tile of the in-loop SpMV (LAB build only): 0 = the one-row kernel, 4 or 8. Rebuilds the block maps."""
+        self.set_option("block_rows", rows)
 
     def loop_shape(self):
         """"single rank" | "pipeline ..." | "plain: <who decided>" (include/spmv_amd/api.h)."""

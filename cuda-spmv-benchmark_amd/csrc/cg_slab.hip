@@ -131,6 +131,11 @@ struct SpmvAmdCgSlab {
     long long tiles_uniform = 0, tiles_total = 0; // of the tiles of the grid rows that are evaluated from the planes
     double quintuple[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // W, C, E, N, S
     bool stream_everywhere = false;  // LAB option: the kernel ignores the map and streams the planes on every tile
+    // Block maps (kernels.hpp, Stencil5Plan::block_map; build_block_maps): the in-loop SpMV evaluates block tiles of
+    // knobs.rowlds_block_rows grid rows, and each launch range -- the whole slab, the rows that need no halo -- has a map of its own,
+    // derived from tile_classes: the ranges start at different grid rows, so their blocks hold different rows.
+    unsigned char *block_map_whole = nullptr, *block_map_interior = nullptr;
+    bool spmv_with_dot = false;  // LAB option: spmv_amd_cg_slab_spmv runs the in-loop form (dot partials wanted)
     const SymPlanes* sym() const { return planes_on ? &planes : nullptr; }
     // place_coefficients: {0, candidates timed, SpMV ms before, SpMV ms kept}
     std::vector<double> placement;
@@ -342,6 +347,32 @@ void classify_tiles(SpmvAmdCgSlab* s) {
     s->tiles_uniform = (long long)h_count;
 }
 
+// Points the whole-slab and interior plans at their block maps (plans are re-made when the tile runs are tuned).
+void attach_block_maps(SpmvAmdCgSlab* s) {
+    s->plan_whole.block_map = s->block_map_whole;
+    s->plan_interior.block_map = s->block_map_interior;
+}
+
+// The block maps of the two launch ranges the in-loop SpMV takes, from the class map, for the plans' block_rows. A slab without a
+// class map, or with block_rows 0, has none: its launches are the one-row kernel's.
+void build_block_maps(SpmvAmdCgSlab* s) {
+    HIP_CHECK(hipStreamSynchronize(s->compute));
+    device_release(s->block_map_whole);
+    device_release(s->block_map_interior);
+    if (s->tile_classes != nullptr) {
+        const auto map_of = [&](const Stencil5Plan& p) -> unsigned char* {
+            const int blocks = rowlds_block_tiles(p);
+            unsigned char* map = blocks > 0 ? device_try_alloc<unsigned char>((size_t)blocks) : nullptr;
+            if (map != nullptr) launch_block_map(s->tile_classes, p, map, s->compute);
+            return map;
+        };
+        s->block_map_whole = map_of(s->plan_whole);
+        s->block_map_interior = map_of(s->plan_interior);
+        HIP_CHECK(hipStreamSynchronize(s->compute));
+    }
+    attach_block_maps(s);
+}
+
 // Fills the reserved planes from the verified CSR and checks them bit for bit (launch_verify_sym_planes); any mismatch, an
 // unverified structure or a launch that is not row-lds frees them again: the slab keeps the CSR form.
 void settle_planes(SpmvAmdCgSlab* s) {
@@ -365,6 +396,7 @@ void settle_planes(SpmvAmdCgSlab* s) {
     } else {
         classify_tiles(s);
         s->planes = plane_view(s, s->planes_alloc);
+        build_block_maps(s);
     }
     s->planes_on = keep;
 }
@@ -629,7 +661,8 @@ void tune_tile_runs(SpmvAmdCgSlab* s) {
     launch_fill(x, nl, 1.0, q);
     HIP_CHECK(hipMemsetAsync(&s->d_s->converged, 0, sizeof(int), q));
     double rec[4] = {0, 0, 0, 0};
-    const int run = tune_rowlds_xcd_run(s->A.view, s->shape, x, s->Ap, s->fused_dot ? s->partials_spmv : nullptr, q, rec, s->sym());
+    const int run = tune_rowlds_xcd_run(s->A.view, s->shape, x, s->Ap, s->fused_dot ? s->partials_spmv : nullptr, q, rec, s->sym(),
+                                        s->plan_whole.block_map);
     HIP_CHECK(hipMemsetAsync(s->ring_alloc[1], 0, s->slot_doubles * sizeof(double), q));
     HIP_CHECK(hipStreamSynchronize(q));
     if (run <= 0) return;
@@ -640,6 +673,7 @@ void tune_tile_runs(SpmvAmdCgSlab* s) {
     s->plan_interior = plan(lo, hi);
     s->plan_head = plan(0, lo);
     s->plan_tail = plan(hi, s->n_local);
+    attach_block_maps(s);  // the maps do not depend on the run length
     s->tile_runs.assign(rec, rec + 4);
 }
 
@@ -1660,7 +1694,7 @@ extern "C" int spmv_amd_cg_slab_spmv(SpmvAmdCgSlab* s, const double* x_full, dou
         upload(s->p - s->halo, x_full + s->row_offset - s->halo, (size_t)s->halo);
     if (s->has_next && s->row_offset + s->n_local + s->halo <= s->n)
         upload(s->p + s->n_local, x_full + s->row_offset + s->n_local, (size_t)s->halo);
-    slab_spmv(s, /*with_dot=*/false, /*overlap=*/false, nullptr);
+    slab_spmv(s, /*with_dot=*/s->spmv_with_dot, /*overlap=*/false, nullptr);
     HIP_CHECK(hipStreamSynchronize(s->compute));
     HIP_CHECK(hipGetLastError());
     download(y_local, s->Ap, (size_t)s->n_local);
@@ -1737,8 +1771,27 @@ extern "C" int spmv_amd_cg_slab_set_option(SpmvAmdCgSlab* s, const char* name, l
         s->stream_everywhere = value != 0;
         if (s->planes_alloc != nullptr) s->planes = plane_view(s, s->planes_alloc);
     }
+    else if (strcmp(name, "block_rows") == 0) {  // grid rows per block tile of the in-loop SpMV: 0 (the one-row kernel), 4 or 8
+        if (value != 0 && value != 4 && value != 8) return -1;
+        s->shape.knobs.rowlds_block_rows = (int)value;
+        for (Stencil5Plan* p : {&s->plan_whole, &s->plan_interior, &s->plan_head, &s->plan_tail})
+            if (p->variant == Stencil5Variant::RowLds) p->block_rows = (int)value;
+        build_block_maps(s);
+    }
+    else if (strcmp(name, "spmv_with_dot") == 0) s->spmv_with_dot = value != 0;  // spmv() in its in-loop form: p.Ap partials and their sum too
     else return -1;
     return 0;
+}
+
+// (LAB build only.) The block map of a launch range as the in-loop SpMV reads it (kernels.hpp, Stencil5Plan): which = 0 the whole
+// slab, 1 the rows that need no halo. One byte per block tile at [row block * tiles per grid row + column tile], 1 = fast path.
+// Copies min(count, cap) bytes and returns count (0: the range has no map).
+extern "C" long long spmv_amd_cg_slab_block_map(const SpmvAmdCgSlab* s, int which, unsigned char* out, long long cap) {
+    const Stencil5Plan& p = which == 0 ? s->plan_whole : s->plan_interior;
+    if (p.block_map == nullptr) return 0;
+    const long long count = rowlds_block_tiles(p);
+    if (out != nullptr && cap > 0) HIP_CHECK(hipMemcpy(out, p.block_map, (size_t)std::min(count, cap), hipMemcpyDeviceToHost));
+    return count;
 }
 
 // (LAB build only.) The tile class map as creation wrote it: one byte per row-lds tile at [local grid row * tiles per grid row +
@@ -1783,6 +1836,8 @@ extern "C" void spmv_amd_cg_slab_destroy(SpmvAmdCgSlab* s) {
     device_release(s->vec_arena);  // r, Ap and the direction buffers
     device_release(s->planes_alloc);
     device_release(s->tile_classes);
+    device_release(s->block_map_whole);
+    device_release(s->block_map_interior);
     s->planes_on = false;
     s->r = s->Ap = s->p_alloc = s->p = nullptr;
     s->ring_alloc.clear();

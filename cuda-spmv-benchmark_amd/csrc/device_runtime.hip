@@ -36,11 +36,13 @@ LaunchShape current_launch_shape() {
     shape.knobs.rowlds_min_grid = env_int("SPMV_AMD_ROWLDS_MIN_GRID", shape.knobs.rowlds_min_grid);
     shape.knobs.rowlds_group = env_int("SPMV_AMD_ROWLDS_GROUP", shape.knobs.rowlds_group);
     if (shape.knobs.rowlds_group < 0 || shape.knobs.rowlds_group > 64) shape.knobs.rowlds_group = 0;
+    const int block_rows = env_int("SPMV_AMD_ROWLDS_BLOCK_ROWS", shape.knobs.rowlds_block_rows);
+    if (block_rows == 0 || block_rows == 4 || block_rows == 8) shape.knobs.rowlds_block_rows = block_rows;
     return shape;
 }
 
 int tune_rowlds_xcd_run(const SlabCsr& m, const LaunchShape& shape, const double* x, double* y, double* d_partials, hipStream_t stream,
-                        double* record, const SymPlanes* planes) {
+                        double* record, const SymPlanes* planes, const unsigned char* block_map) {
     if (shape.knobs.rowlds_group > 0 || m.n_local < (16 << 20)) return 0;
     LaunchShape trial = shape;
     const Stencil5Plan base = plan_stencil5(m, 0, m.n_local, Stencil5Variant::Auto, trial);
@@ -56,7 +58,8 @@ int tune_rowlds_xcd_run(const SlabCsr& m, const LaunchShape& shape, const double
         for (int j = 0; j < k; ++j) seen = seen || cand[j] == g;
         if (seen) continue;
         trial.knobs.rowlds_group = g;
-        const Stencil5Plan p = plan_stencil5(m, 0, m.n_local, Stencil5Variant::RowLds, trial);
+        Stencil5Plan p = plan_stencil5(m, 0, m.n_local, Stencil5Variant::RowLds, trial);
+        p.block_map = block_map;
         float ms[3];
         for (int i = 0; i < 4; ++i) {
             timer.begin(stream);

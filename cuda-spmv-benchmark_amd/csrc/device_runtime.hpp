@@ -124,8 +124,10 @@ inline T* device_alloc_best_of(size_t count, size_t min_count, Cost&& cost_ms, i
 // workgroups to tiles is a performance choice only, results and partial slots do not depend on it.
 // record (optional, 4 doubles): {rule, kept, ms with the rule, ms kept}.
 // planes (may be null): the slab's symmetric coefficient form, timed as the loop will run it.
+// block_map (may be null): the whole slab's block map (kernels.hpp, Stencil5Plan): the trial launches then take block tiles, as the
+// loop's will, and the run length counts block tiles.
 int tune_rowlds_xcd_run(const SlabCsr& m, const LaunchShape& shape, const double* x, double* y, double* d_partials, hipStream_t stream,
-                        double* record = nullptr, const SymPlanes* planes = nullptr);
+                        double* record = nullptr, const SymPlanes* planes = nullptr, const unsigned char* block_map = nullptr);
 
 // Pair of events for on-stream timing of one region.
 struct EventTimer {

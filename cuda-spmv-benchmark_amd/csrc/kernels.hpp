@@ -34,6 +34,9 @@ struct SlabCsr {
 struct Tunables {
     int rowlds_min_grid = 512;    // SPMV_AMD_ROWLDS_MIN_GRID: smallest grid that takes row-lds automatically (tests force it down)
     int rowlds_group = 0;         // SPMV_AMD_ROWLDS_GROUP: consecutive row-lds tiles per XCD; 0 = derived from the grid (xcd_run_group())
+    // SPMV_AMD_ROWLDS_BLOCK_ROWS: grid rows per wave of a solver slab's in-loop SpMV (block tiles): 0 (the one-row kernel), 4 or 8.
+    // 20 000^2 on MI355X, one process, alternated: 1.636 ms / 1.064 / 1.086 (profiles/r13_block_rows_ab.txt)
+    int rowlds_block_rows = 4;
 };
 
 // How many consecutive logical blocks (each `block_columns` grid columns wide) one XCD takes of every run of
@@ -76,7 +79,12 @@ struct Stencil5Plan {
     int first_row = 0, last_row = 0;
     int gi_lo = 0, gi_hi = 0;  // row-direct / row-lds: the local grid rows of the range
     int row_blocks = 0;        // row-generic: workgroups of the launch; row-direct / row-lds: workgroups per grid row
-    int xcd_run = 0;           // row-lds: consecutive tiles one XCD takes of every run of 8 * xcd_run
+    int xcd_run = 0;           // row-lds: consecutive tiles (block tiles, where the launch takes them) one XCD takes of every run of 8 * xcd_run
+    // row-lds: grid rows per block tile of the in-loop SpMV (0, 4 or 8; Tunables) and the range's block map -- one byte per block
+    // tile, 1 = all its tiles uniform and all its rows present (launch_block_map; device memory of the plan's owner). Without a
+    // map the launch is the one-row kernel's.
+    int block_rows = 0;
+    const unsigned char* block_map = nullptr;
     int partials = 0;          // dot-partial slots one launch writes (a fixed function of the slab and the range)
     const char* name = "";     // "stencil5/row-lds", ...
 };
@@ -129,6 +137,10 @@ struct ChebStep {
     int* work_count = nullptr;
 };
 int rowlds_col_tiles(int n);  // row-lds tiles per grid row
+// Block tiles of a row-lds plan -- 128 columns x plan.block_rows grid rows, the last block of the range may be short -- (0: none)
+// and its block map, written from the slab's class map (`cls`: SymPlanes): out[row block * tiles per grid row + column tile].
+int rowlds_block_tiles(const Stencil5Plan& plan);
+void launch_block_map(const unsigned char* cls, const Stencil5Plan& plan, unsigned char* out, hipStream_t stream);
 // Sets *d_mismatch (int, zeroed by the caller) if any value the row-lds kernel would take from the planes in grid rows 1 .. n-2
 // (W = E[i-1], N = S[i-n] or the halo row, C, E, S) differs in its 64-bit pattern from the CSR entry it stands for.
 void launch_verify_sym_planes(const SlabCsr& m, const SymPlanes& planes, int* d_mismatch, hipStream_t stream);
@@ -136,6 +148,8 @@ void launch_verify_sym_planes(const SlabCsr& m, const SymPlanes& planes, int* d_
 // Launch by plan. reverse: walk the tiles from the last to the first (row-lds only; same results).
 // init (may be null): see ResidualOut; y is then not written and may be null.
 // planes (may be null; row-lds plans only): the symmetric coefficient form.
+// A row-lds plan with a block map (Stencil5Plan) takes block tiles -- stencil5_rowlds_block_kernel, the same rows and partial slots --
+// when the launch wants dot partials, has no `init` and `planes` carries a class map; every other launch is the one-row kernel's.
 int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& plan, const double* x, double* y, double alpha,
                          double* d_dot_partials, const int* d_skip_flag, bool reverse, hipStream_t stream,
                          const ResidualOut* init = nullptr, const SymPlanes* planes = nullptr);

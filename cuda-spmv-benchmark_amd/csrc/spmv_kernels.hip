@@ -462,6 +462,145 @@ __global__ __launch_bounds__(64) void stencil5_rowlds_kernel(
 }
 
 // ---------------------------------------------------------------------------------
+// The in-loop SpMV of a solver slab over BLOCK TILES: one wave evaluates 128 columns of kRows consecutive local grid rows
+// [li0, li0 + kRows). On a uniform tile the one-row kernel moves 16 B/row of unique data (x in, y out) but requests every x value
+// three times (centre, north, south) from workgroups that mostly sit on different XCDs; a block tile reads its kRows + 2 rows of
+// x once each, 8 (kRows + 2) / kRows + 8 B/row. No rotation and no software pipeline: every load of the block is issued before
+// the first value is used, so a wave has 6-10 KB in flight.
+// block_map (one byte per block tile of THIS launch range, launch_block_map): 1 = the block holds kRows grid rows and every one
+// of its tiles is uniform (kernels.hpp, SymPlanes) -- the fast path: the fma chains of rowlds_tile<1, false, true> on a uniform
+// tile, W / E from an LDS copy of each row. 0 = the block calls rowlds_tile once per grid row it holds, with that row's own class.
+// Either way one partial of x . (A x) per 128 x 1 tile in the one-row kernel's slot, (li - gi_lo) * col_tiles + col_tile: the
+// reduction's shape and every bit of the sum stay what they were.
+// ---------------------------------------------------------------------------------
+template <int kRows>
+__global__ __launch_bounds__(64) void stencil5_rowlds_block_kernel(
+    SlabCsr m, const double* __restrict__ x, double* __restrict__ y, double alpha, int gi_lo, int gi_hi, int gfirst, int col_tiles,
+    int total_blocks, int run, int reverse, double* __restrict__ dot_partials, const int* __restrict__ skip_flag,
+    const unsigned char* __restrict__ block_map, SymPlanes sp) {
+    constexpr int kRowDoubles = kLdsTileCols + 2;
+    constexpr int kFastDoubles = kRows * kRowDoubles, kOneRowDoubles = 5 * kLdsTileCols + kRowDoubles;
+    // fast path: one x row copy per grid row of the block; the other path: rowlds_tile's strip and x row
+    __shared__ double lds[kFastDoubles > kOneRowDoubles ? kFastDoubles : kOneRowDoubles];
+    const int skip = skip_flag != nullptr ? __builtin_nontemporal_load(skip_flag) : 0;
+    const int block = rowlds_tile_of_block((int)blockIdx.x, run, total_blocks, reverse);
+    if (block < 0) return;
+    const int row_block = block / col_tiles;
+    const int col_tile = block - row_block * col_tiles;
+    const int li0 = gi_lo + row_block * kRows;
+    const int j0 = col_tile * kLdsTileCols, lane = (int)threadIdx.x;
+    const int n = m.grid_size;
+    const int fast = (int)block_map[block];  // a vector load, requested in front of the x loads and tested behind them (rowlds_tile_class)
+    // local grid rows of x that exist: the slab's own and the halo rows around it (SlabCsr). A fast block reads only such rows (its
+    // rows are global grid rows 1 .. n-2); the loads are issued before the map byte is known, so every block must stay inside.
+    const int row_lo = -(m.halo_before / n), row_hi = (m.n_local + m.halo_after) / n;
+    double xv[kRows + 2][2];  // rows li0 - 1 .. li0 + kRows, the lane's two columns
+    double xo[kRows];         // lane 0: the W neighbour left of the tile; lane 63: the E neighbour right of it
+#pragma unroll
+    for (int r = 0; r < kRows + 2; ++r) {
+        const int li = li0 - 1 + r;
+        xv[r][0] = xv[r][1] = 0.0;
+        if (li >= row_lo && li < row_hi) {
+            const double* __restrict__ xr = x + ((long long)li * n + j0);
+            if (j0 + lane < n) xv[r][0] = xr[lane];
+            if (j0 + lane + 64 < n) xv[r][1] = xr[lane + 64];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+        const int li = li0 + r;
+        xo[r] = 0.0;
+        if (li < row_hi) {
+            const double* __restrict__ xr = x + ((long long)li * n + j0);
+            if (lane == 0 && j0 > 0) xo[r] = xr[-1];
+            if (lane == 63 && j0 + kLdsTileCols < n) xo[r] = xr[kLdsTileCols];
+        }
+    }
+    if (__builtin_amdgcn_readfirstlane(fast) != 0) {
+        if (skip != 0) return;
+#pragma unroll
+        for (int r = 0; r < kRows; ++r) {
+            lds[r * kRowDoubles + 1 + lane] = xv[r + 1][0];
+            lds[r * kRowDoubles + 65 + lane] = xv[r + 1][1];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int r = 0; r < kRows; ++r) {
+            const double* __restrict__ xrow = lds + r * kRowDoubles;
+            const int li = li0 + r;
+            // columns beyond n hold 0 in xv, exactly what an absent neighbour contributes
+            double xw[2], xe[2];
+            xw[0] = lane > 0 ? xrow[lane] : xo[r];
+            xe[0] = xrow[2 + lane];
+            xw[1] = xrow[64 + lane];
+            xe[1] = lane < 63 ? xrow[66 + lane] : xo[r];
+            if (j0 + lane == n - 1) xe[0] = 0.0;
+            double dot = 0.0;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int j = j0 + lane + 64 * h;
+                if (j < n) {
+                    const double xc = xv[r + 1][h], xn = xv[r][h], xs = xv[r + 2][h];
+                    double sum;
+                    if (j > 0 && j < n - 1) {  // W,C,E,N,S
+                        sum = sp.w * xw[h];
+                        sum = fma(sp.c, xc, sum);
+                        sum = fma(sp.e, xe[h], sum);
+                        sum = fma(sp.n, xn, sum);
+                        sum = fma(sp.s5, xs, sum);
+                    } else if (j == 0) {       // CSR-loop order: N,C,E,S
+                        sum = fma(sp.n, xn, 0.0);
+                        sum = fma(sp.c, xc, sum);
+                        sum = fma(sp.e, xe[h], sum);
+                        sum = fma(sp.s5, xs, sum);
+                    } else {                   // j == n-1, CSR-loop order: N,W,C,S
+                        sum = fma(sp.n, xn, 0.0);
+                        sum = fma(sp.w, xw[h], sum);
+                        sum = fma(sp.c, xc, sum);
+                        sum = fma(sp.s5, xs, sum);
+                    }
+                    dot = fma(xc, sum, dot);
+                    __builtin_nontemporal_store(alpha * sum, y + ((long long)li * n + j));
+                }
+            }
+            dot = wave_sum(dot);
+            if (lane == 0) dot_partials[(li - gi_lo) * col_tiles + col_tile] = dot;
+        }
+    } else {
+        double* __restrict__ strip = lds;
+        double* __restrict__ xrow = lds + 5 * kLdsTileCols;
+        const ResidualOut none{nullptr, nullptr, nullptr};
+        const int held = gi_hi - li0 < kRows ? gi_hi - li0 : kRows;
+#pragma unroll 1
+        for (int r = 0; r < held; ++r) {
+            const int li = li0 + r;
+            const int uniform = rowlds_tile_class(sp, li, col_tiles, col_tile);
+            double dot = 0.0;
+            if (!rowlds_tile<1, false, true>(m, x, y, alpha, li, gfirst + li, j0, lane, skip, strip, xrow, none, &dot, sp, uniform)) return;
+            if (lane == 0) dot_partials[(li - gi_lo) * col_tiles + col_tile] = dot;
+            // the next row rewrites the LDS this row's lanes have just read
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+    }
+}
+
+// The block map of one launch range [gi_lo, gi_hi) (stencil5_rowlds_block_kernel): one thread per block tile.
+__global__ __launch_bounds__(kBlock) void block_map_kernel(const unsigned char* __restrict__ cls, int col_tiles, int gi_lo, int gi_hi,
+                                                           int block_rows, int total_blocks, unsigned char* __restrict__ out) {
+    const int block = (int)(blockIdx.x * (unsigned)kBlock + threadIdx.x);
+    if (block >= total_blocks) return;
+    const int row_block = block / col_tiles, col_tile = block - row_block * col_tiles;
+    const int li0 = gi_lo + row_block * block_rows;
+    bool fast = li0 + block_rows <= gi_hi;
+    for (int r = 0; fast && r < block_rows; ++r) fast = cls[(long long)(li0 + r) * col_tiles + col_tile] == 1;
+    out[block] = fast ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------
 // The boundary rows of a solver slab AND the reduction of the whole SpMV's p.Ap partials in ONE launch (round 5).
 // A rank with neighbours computes the rows that read halo values -- its first and / or last grid row -- once the halo has
 // landed, behind the interior rows' launch; rounds 2-4 then reduced the partials with two more launches. On the P = 8 slab of
@@ -1102,6 +1241,7 @@ Stencil5Plan plan_stencil5(const SlabCsr& m, int first_row, int last_row, Stenci
             p.xcd_run = knobs.rowlds_group > 0 ? knobs.rowlds_group : rowlds_xcd_run_rule(n);
             if (p.xcd_run < 1 || p.xcd_run > 64) p.xcd_run = 4;
             p.name = "stencil5/row-lds";
+            p.block_rows = knobs.rowlds_block_rows == 4 || knobs.rowlds_block_rows == 8 ? knobs.rowlds_block_rows : 0;
         }
         p.partials = p.row_blocks * (p.gi_hi - p.gi_lo);  // < 2^31 for any int32 CSR
     }
@@ -1140,7 +1280,34 @@ void launch_rowlds(const SlabCsr& m, const Stencil5Plan& p, const double* x, dou
     else SPMV_AMD_LAUNCH_ROWLDS(0);
 #undef SPMV_AMD_LAUNCH_ROWLDS
 }
+
+// the block kernel over the plan's block tiles (the in-loop SpMV of a solver slab; launch_stencil5_spmv decides)
+void launch_rowlds_block(const SlabCsr& m, const Stencil5Plan& p, const double* x, double* y, double alpha, double* d_dot_partials,
+                         const int* d_skip_flag, bool reverse, hipStream_t stream, const SymPlanes& sp) {
+    const int blocks = rowlds_block_tiles(p);
+    const int span = 8 * p.xcd_run;
+    const dim3 grid((unsigned)(((long long)blocks + span - 1) / span * span));
+    const int gfirst = m.row_offset / m.grid_size;
+#define SPMV_AMD_LAUNCH_ROWLDS_BLOCK(ROWS)                                                                                      \
+    hipLaunchKernelGGL((stencil5_rowlds_block_kernel<ROWS>), grid, dim3(64), 0, stream, m, x, y, alpha, p.gi_lo, p.gi_hi, gfirst, \
+                       p.row_blocks, blocks, p.xcd_run, reverse ? 1 : 0, d_dot_partials, d_skip_flag, p.block_map, sp)
+    if (p.block_rows == 4) SPMV_AMD_LAUNCH_ROWLDS_BLOCK(4);
+    else SPMV_AMD_LAUNCH_ROWLDS_BLOCK(8);
+#undef SPMV_AMD_LAUNCH_ROWLDS_BLOCK
+}
 }  // namespace
+
+int rowlds_block_tiles(const Stencil5Plan& p) {
+    if (p.variant != Stencil5Variant::RowLds || p.block_rows <= 0 || p.gi_hi <= p.gi_lo) return 0;
+    return (p.gi_hi - p.gi_lo + p.block_rows - 1) / p.block_rows * p.row_blocks;
+}
+
+void launch_block_map(const unsigned char* cls, const Stencil5Plan& p, unsigned char* out, hipStream_t stream) {
+    const int blocks = rowlds_block_tiles(p);
+    if (blocks <= 0) return;
+    hipLaunchKernelGGL(block_map_kernel, dim3(blocks_for(blocks)), dim3(kBlock), 0, stream, cls, p.row_blocks, p.gi_lo, p.gi_hi, p.block_rows,
+                       blocks, out);
+}
 
 int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& p, const double* x, double* y, double alpha,
                          double* d_dot_partials, const int* d_skip_flag, bool reverse, hipStream_t stream,
@@ -1151,7 +1318,11 @@ int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& p, const double* 
         exit(EXIT_FAILURE);
     }
     const bool dot = d_dot_partials != nullptr;
-    if (p.variant == Stencil5Variant::RowLds) {
+    if (p.variant == Stencil5Variant::RowLds && p.block_rows > 0 && p.block_map != nullptr && dot && init == nullptr && planes != nullptr &&
+        planes->ce != nullptr && planes->cls != nullptr) {
+        // the in-loop SpMV of a slab with a class map: block tiles (the same rows, the same partial slots)
+        launch_rowlds_block(m, p, x, y, alpha, d_dot_partials, d_skip_flag, reverse, stream, *planes);
+    } else if (p.variant == Stencil5Variant::RowLds) {
         launch_rowlds(m, p, x, y, alpha, p.gi_lo, 1, p.partials, d_dot_partials, d_skip_flag, reverse, stream, init, planes);
     } else if (p.variant == Stencil5Variant::RowDirect) {
         const dim3 grid((unsigned)p.partials);

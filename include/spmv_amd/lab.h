@@ -37,13 +37,22 @@ SpmvAmdCgSlab* spmv_amd_cg_slab_create_stencil5_as(int n, int as_rank, int as_wo
  * converging one whatever its residual; 0 = off), and "csr_coefficients" 0/1 (1 = the SpMV streams the CSR values even where the
  * slab holds the symmetric planes, spmv_amd_cg_slab_coefficient_form; results are bit-identical) and "stream_coefficients" 0/1
  * (1 = the kernel ignores the tile class map and streams the planes on every tile, spmv_amd_cg_slab_uniform_tiles; composes with
- * "csr_coefficients"; results are bit-identical). Returns 0, or -1 for an unknown name. */
+ * "csr_coefficients"; results are bit-identical), "block_rows" 0 / 4 / 8 (grid rows per block tile of the in-loop SpMV, the
+ * product's SPMV_AMD_ROWLDS_BLOCK_ROWS; 0 = the one-row kernel; the block maps are rebuilt; results are bit-identical) and
+ * "spmv_with_dot" 0/1 (1 = spmv_amd_cg_slab_spmv runs the SpMV in its in-loop form, p.Ap partials and their sum included, so that
+ * it takes the kernel the loop takes). Returns 0, or -1 for an unknown name or value. */
 int spmv_amd_cg_slab_set_option(SpmvAmdCgSlab* s, const char* name, long long value);
 
 /* The tile class map of a slab in the symmetric form as creation wrote it (spmv_amd_cg_slab_uniform_tiles): one byte per row-lds
  * tile at [local grid row * ceil(n / 128) + column tile], 1 = uniform, 0 = the tile streams the planes (the grid's first and last
  * grid row, which walk the CSR, hold 0). Copies min(count, cap) bytes to `out` (host) and returns count; 0 = no map. */
 long long spmv_amd_cg_slab_tile_classes(const SpmvAmdCgSlab* s, unsigned char* out, long long cap);
+
+/* The block map of one launch range of the in-loop SpMV (which = 0: the whole slab; 1: the rows that need no halo): one byte per
+ * block tile -- 128 columns x block_rows grid rows counted from the range's first grid row -- at [row block * ceil(n / 128) +
+ * column tile], 1 = every tile of the block is uniform and the block holds block_rows rows (the fast path), 0 = the block is
+ * evaluated row by row. Copies min(count, cap) bytes to `out` (host) and returns count; 0 = the range has no map. */
+long long spmv_amd_cg_slab_block_map(const SpmvAmdCgSlab* s, int which, unsigned char* out, long long cap);
 
 /* The device scalars of one preconditioned solve (csrc/pcg.hip keeps the same record on the device). */
 typedef struct SpmvAmdPcgScalars {
