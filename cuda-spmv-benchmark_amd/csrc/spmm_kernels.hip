@@ -1,11 +1,9 @@
 // spmm_kernels.hip -- one sparse matrix times k = 1..8 vectors (SpMM) on gfx950, for the "stencil5-csr" and "cusparse-csr"
 // operators. Block vectors are row-interleaved, X[row * k + j] (multi_rhs.hpp).
 //
-// Arithmetic contract: that of spmv_kernels.hip:1-10, for every column. Each column has its own accumulator, every
-// multiply-add is an explicit fma() and the file is compiled with -ffp-contract=off, so column j of Y is, bit for bit, the
-// single-vector product of column j:
-//   interior stencil rows : t = vW*xW ; fma(vC,xC,t) ; fma(vE,xE,t) ; fma(vN,xN,t) ; fma(vS,xS,t)
-//   every other row       : sum = 0 ; sum = fma(v[k], x[col[k]], sum) for ascending k
+// Arithmetic contract: that of stencil_row_device.hpp, for every column. Each column has its own accumulator and goes through
+// the same fma chains (interior rows: the scalar helper, called per column), and the file is compiled with -ffp-contract=off, so
+// column j of Y is, bit for bit, the single-vector product of column j
 // (the CSR operator's own "csr/stream", "csr/row-scalar" and the oracle's order; "csr/adaptive" and "csr/wavefront" sum long
 // rows as a tree and are not matched: the SpMM keeps the sequential, bit-reproducible form for every matrix).
 //
@@ -28,6 +26,7 @@
 
 #include "multi_rhs.hpp"
 #include "stencil_geometry.hpp"
+#include "stencil_row_device.hpp"
 #include "stream_device.hpp"
 
 namespace spmv_amd {
@@ -93,19 +92,13 @@ __device__ __forceinline__ void csr_row(const SlabCsr& m, const double* __restri
     csr_row_part<K, K, kVec>(m, X, row, 0, sum);
 }
 
-// Interior row, coefficients v = [N,W,C,E,S], evaluated W,C,E,N,S (spmv_kernels.hip:6).
+// Interior row, coefficients v = [N,W,C,E,S], every column.
 template <int K>
 __device__ __forceinline__ void interior_row(double v0, double v1, double v2, double v3, double v4, const double (&xn)[K],
                                              const double (&xw)[K], const double (&xc)[K], const double (&xe)[K],
                                              const double (&xs)[K], double (&sum)[K]) {
 #pragma unroll
-    for (int j = 0; j < K; ++j) {
-        double s = v1 * xw[j];
-        s = fma(v2, xc[j], s);
-        s = fma(v3, xe[j], s);
-        s = fma(v0, xn[j], s);
-        sum[j] = fma(v4, xs[j], s);
-    }
+    for (int j = 0; j < K; ++j) sum[j] = stencil5_interior(v1, xw[j], v2, xc[j], v3, xe[j], v0, xn[j], v4, xs[j]);
 }
 
 // One partial per column of the workgroup's rows: wave trees, then the four wave sums in wave order.
@@ -150,9 +143,7 @@ __global__ __launch_bounds__(kBlock) void spmm_stencil5_rowlds_kernel(SlabCsr m,
     constexpr int P = K / V;
     __shared__ double strip[kBlock / 64][5 * kTile];
     __shared__ double prod[kDot ? kBlock / 64 : 1][kDot ? kTile * K : 1];
-    const long long span = 8LL * run;
-    const long long b = blockIdx.x;
-    const long long blk = (b / span) * span + (b & 7) * run + ((b >> 3) % run);  // XCD runs (spmv_kernels.hip, logical_block)
+    const long long blk = xcd_run_tile<long long>(blockIdx.x, run);
     if (blk >= total) return;
     const int n = m.grid_size;
     const int gi = (int)(blk / col_blocks);
@@ -179,9 +170,7 @@ __global__ __launch_bounds__(kBlock) void spmm_stencil5_rowlds_kernel(SlabCsr m,
         }
 #pragma unroll
         for (int k = 0; k < 5; ++k) st[kTile * k + lane] = c[k];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
     if (j0 < n) {
 #pragma unroll
@@ -206,7 +195,10 @@ __global__ __launch_bounds__(kBlock) void spmm_stencil5_rowlds_kernel(SlabCsr m,
                     const double* v = st + 5 * t;
                     if (j > 0 && j < n - 1) {
                         interior_row<V>(v[0], v[1], v[2], v[3], v[4], xn, xw, xc, xe, xs, sum);
-                    } else if (j == 0) {  // [N,C,E,S] at strip positions 1..4, CSR-loop order
+                    }
+                    // The two column chains (stencil5_first_column / stencil5_last_column of stencil_row_device.hpp) stay written out in this
+                    // kernel: profiles/r14_stencil_helpers_isa_identity.txt, class C site 1, says why.
+                    else if (j == 0) {  // [N,C,E,S] at strip positions 1..4, CSR-loop order
 #pragma unroll
                         for (int q = 0; q < V; ++q) {
                             double s = fma(v[1], xn[q], 0.0);
@@ -238,9 +230,7 @@ __global__ __launch_bounds__(kBlock) void spmm_stencil5_rowlds_kernel(SlabCsr m,
     if (kDot) {
         double d[K];
         if (j0 < n) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
 #pragma unroll
             for (int q = 0; q < K; ++q) d[q] = prod[wave][lane * K + q];
         } else {
@@ -335,8 +325,7 @@ template <int K, bool kDot, bool kVec>
 void launch_kind(const SpmmPlan& p, const double* X, double* Y, double* partials, hipStream_t stream) {
     switch (p.kind) {
         case SpmmKind::StencilLds: {
-            const long long span = 8LL * p.xcd_run;
-            const dim3 grid((unsigned)((p.blocks + span - 1) / span * span));
+            const dim3 grid((unsigned)xcd_padded_grid(p.blocks, p.xcd_run));
             hipLaunchKernelGGL((spmm_stencil5_rowlds_kernel<K, kDot, kVec>), grid, dim3(kBlock), 0, stream, p.m, X, Y, p.col_blocks, p.xcd_run,
                                p.blocks, partials);
             break;

@@ -1,13 +1,7 @@
 // spmv_kernels.hip -- hand-written gfx950 kernels for the three SpMV operators.
 //
-// Arithmetic contract (numerical-semantics checklist): every
-// multiply-add below is an explicit fma() and the file is compiled with
-// -ffp-contract=off, so the order and fusing of operations is exactly
-//   interior stencil rows : t = vW*xW ; fma(vC,xC,t) ; fma(vE,xE,t) ; fma(vN,xN,t) ; fma(vS,xS,t)
-//                           (reference src/spmv/spmv_stencil_csr_direct.cu:105-109 under nvcc -fmad)
-//   every other row       : sum = 0 ; sum = fma(v[k], x[col[k]], sum) for ascending k
-//                           (reference :116-119 ; cg_solver_mgpu_partitioned.cu:49-52)
-// which is what oracle/spmv_oracle.c evaluates on the CPU.
+// Arithmetic contract: stencil_row_device.hpp states it and holds the stencil rows' fma chains, which the kernels below call.
+// Rows that are not stencil rows take sum = 0 ; sum = fma(v[k], x[col[k]], sum) for ascending k, written out where it is used.
 //
 // Memory contract: STENCIL5 is HBM-bound at 56 B per interior row (40 B values, 8 B x, 8 B y). Three kernels implement it:
 //   row-lds     (grids of >= 512 columns, slabs made of whole grid rows: the benchmark's path) streams `values` with fully
@@ -29,6 +23,7 @@
 
 #include "reduce_device.hpp"
 #include "stencil_geometry.hpp"
+#include "stencil_row_device.hpp"
 #include "stream_device.hpp"
 
 namespace spmv_amd {
@@ -36,15 +31,12 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = 4;
-// Workgroups are dealt round-robin to the eight XCDs. logical_block() re-labels them so that each XCD works on
-// `group` CONSECUTIVE logical blocks of every run of 8 * group (the row-lds finding, DESIGN.md section 3: with the
-// same kernel body, which XCD touches which addresses is worth ~5 %). The launcher pads the grid to a multiple of
-// 8 * group; blocks relabelled past `total` return. group <= 1: identity.
+// The logical block of this workgroup in XCD runs of `group` (xcd_run_tile, stencil_row_device.hpp); blocks relabelled past
+// `total` return (-1). group <= 1: dispatch order.
 __device__ __forceinline__ long long logical_block(int group, long long total) {
     const long long b = blockIdx.x;
     if (group <= 1) return b;
-    const long long span = 8LL * group;
-    const long long t = (b / span) * span + (b & 7) * group + ((b >> 3) % group);
+    const long long t = xcd_run_tile<long long>(b, group);
     return t < total ? t : -1;
 }
 
@@ -65,12 +57,7 @@ __device__ __forceinline__ double row_reference(const SlabCsr& m, const double* 
         const long long o = stencil_row_start(i, j, n) - m.nnz_base;
         const double* __restrict__ v = m.values + o;
         const double* __restrict__ xl = x + local_row;
-        double sum = v[1] * xl[-1];
-        sum = fma(v[2], xl[0], sum);
-        sum = fma(v[3], xl[1], sum);
-        sum = fma(v[0], xl[-n], sum);
-        sum = fma(v[4], xl[n], sum);
-        return sum;
+        return stencil5_interior(v[1], xl[-1], v[2], xl[0], v[3], xl[1], v[0], xl[-n], v[4], xl[n]);  // [N,W,C,E,S]
     }
     const int lo = -m.halo_before, hi = m.n_local + m.halo_after;
     const int k0 = m.row_ptr[local_row], k1 = m.row_ptr[local_row + 1];
@@ -110,11 +97,7 @@ __global__ __launch_bounds__(kBlock) void stencil5_rowdirect_kernel(
         if (j > 0 && j < n - 1 && gi > 0 && gi < n - 1) {
             const double* __restrict__ v = m.values + (stencil_gridrow_base(gi, n) + 5LL * j - 1 - m.nnz_base);
             const double v0 = v[0], v1 = v[1], v2 = v[2], v3 = v[3], v4 = v[4];
-            sum = v1 * xl[-1];
-            sum = fma(v2, xl[0], sum);
-            sum = fma(v3, xl[1], sum);
-            sum = fma(v0, xl[-n], sum);
-            sum = fma(v4, xl[n], sum);
+            sum = stencil5_interior(v1, xl[-1], v2, xl[0], v3, xl[1], v0, xl[-n], v4, xl[n]);
         } else {
             sum = row_reference<false>(m, x, (int)lr, gi, j);
         }
@@ -267,15 +250,8 @@ __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __re
             }
             xrow[1 + lane] = xc[0];
             xrow[65 + lane] = xc[1];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            // columns beyond n hold 0 in xc, exactly what an absent neighbour contributes
-            if (lane > 0) xw[0] = xrow[lane];
-            xe[0] = xrow[2 + lane];
-            xw[1] = xrow[64 + lane];
-            if (lane < 63) xe[1] = xrow[66 + lane];
-            if (j0 + lane == n - 1) xe[0] = 0.0;
+            wave_lds_sync();
+            tile_west_east(xrow, lane, j0, n, xw[0], xe[1], xw, xe);
             double cwv[2] = {0.0, 0.0};  // kSym: W = E[i - 1]
             if constexpr (kSym && !kUniform) {
                 cwv[0] = strip[lane];
@@ -291,24 +267,11 @@ __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __re
                         // a uniform tile: the quintuple, bit for bit what every row of the tile holds (checked against the CSR at creation)
                         const double vw = kUniform ? sp.w : cwv[h], vc = kUniform ? sp.c : ce[h].x, ve = kUniform ? sp.e : ce[h].y,
                                      vn = kUniform ? sp.n : cn[h], vs = kUniform ? sp.s5 : cs[h];
-                        if (j > 0 && j < n - 1) {        // W,C,E,N,S
-                            sum = vw * xw[h];
-                            sum = fma(vc, xc[h], sum);
-                            sum = fma(ve, xe[h], sum);
-                            sum = fma(vn, xn[h], sum);
-                            sum = fma(vs, xs[h], sum);
-                        } else if (j == 0) {             // CSR-loop order: N,C,E,S
-                            sum = fma(vn, xn[h], 0.0);
-                            sum = fma(vc, xc[h], sum);
-                            sum = fma(ve, xe[h], sum);
-                            sum = fma(vs, xs[h], sum);
-                        } else {                         // j == n-1, CSR-loop order: N,W,C,S
-                            sum = fma(vn, xn[h], 0.0);
-                            sum = fma(vw, xw[h], sum);
-                            sum = fma(vc, xc[h], sum);
-                            sum = fma(vs, xs[h], sum);
-                        }
-                    } else if (j > 0 && j < n - 1) {     // [N,W,C,E,S], evaluated W,C,E,N,S
+                        sum = stencil5_row(j, n, vw, xw[h], vc, xc[h], ve, xe[h], vn, xn[h], vs, xs[h]);
+                    }
+                    // The CSR strip form: its three chains (stencil_row_device.hpp's, on other strip slots per case) stay written out here;
+                    // profiles/r14_stencil_helpers_isa_identity.txt, class C site 2, says why.
+                    else if (j > 0 && j < n - 1) {       // [N,W,C,E,S], evaluated W,C,E,N,S
                         sum = v[1] * xw[h];
                         sum = fma(v[2], xc[h], sum);
                         sum = fma(v[3], xe[h], sum);
@@ -418,11 +381,9 @@ __device__ __forceinline__ int rowlds_tile_class(const SymPlanes& sp, int li, in
     return sp.cls != nullptr ? (int)sp.cls[li * col_tiles + col_tile] : 0;
 }
 
-// Tile of workgroup b: each XCD takes `run` consecutive tiles of every run of 8 * run (workgroups are dealt round-robin to
-// the eight XCDs); the launcher pads the grid to a multiple of 8 * run, tiles past `total` do not exist (-1).
+// Tile of workgroup b in XCD runs of `run` tiles (xcd_run_tile, stencil_row_device.hpp); tiles past `total` do not exist (-1).
 __device__ __forceinline__ int rowlds_tile_of_block(int b, int run, int total, int reverse) {
-    const int span = 8 * run;
-    int tile = (b / span) * span + (b & 7) * run + ((b >> 3) % run);
+    const int tile = xcd_run_tile<int>(b, run);
     if (tile >= total) return -1;
     return reverse ? total - 1 - tile : tile;  // same tiles, same partial slots, walked from the end
 }
@@ -523,44 +484,19 @@ __global__ __launch_bounds__(64) void stencil5_rowlds_block_kernel(
             lds[r * kRowDoubles + 1 + lane] = xv[r + 1][0];
             lds[r * kRowDoubles + 65 + lane] = xv[r + 1][1];
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
 #pragma unroll
         for (int r = 0; r < kRows; ++r) {
-            const double* __restrict__ xrow = lds + r * kRowDoubles;
             const int li = li0 + r;
-            // columns beyond n hold 0 in xv, exactly what an absent neighbour contributes
             double xw[2], xe[2];
-            xw[0] = lane > 0 ? xrow[lane] : xo[r];
-            xe[0] = xrow[2 + lane];
-            xw[1] = xrow[64 + lane];
-            xe[1] = lane < 63 ? xrow[66 + lane] : xo[r];
-            if (j0 + lane == n - 1) xe[0] = 0.0;
+            tile_west_east(lds + r * kRowDoubles, lane, j0, n, xo[r], xo[r], xw, xe);
             double dot = 0.0;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int j = j0 + lane + 64 * h;
                 if (j < n) {
                     const double xc = xv[r + 1][h], xn = xv[r][h], xs = xv[r + 2][h];
-                    double sum;
-                    if (j > 0 && j < n - 1) {  // W,C,E,N,S
-                        sum = sp.w * xw[h];
-                        sum = fma(sp.c, xc, sum);
-                        sum = fma(sp.e, xe[h], sum);
-                        sum = fma(sp.n, xn, sum);
-                        sum = fma(sp.s5, xs, sum);
-                    } else if (j == 0) {       // CSR-loop order: N,C,E,S
-                        sum = fma(sp.n, xn, 0.0);
-                        sum = fma(sp.c, xc, sum);
-                        sum = fma(sp.e, xe[h], sum);
-                        sum = fma(sp.s5, xs, sum);
-                    } else {                   // j == n-1, CSR-loop order: N,W,C,S
-                        sum = fma(sp.n, xn, 0.0);
-                        sum = fma(sp.w, xw[h], sum);
-                        sum = fma(sp.c, xc, sum);
-                        sum = fma(sp.s5, xs, sum);
-                    }
+                    const double sum = stencil5_row(j, n, sp.w, xw[h], sp.c, xc, sp.e, xe[h], sp.n, xn, sp.s5, xs);
                     dot = fma(xc, sum, dot);
                     __builtin_nontemporal_store(alpha * sum, y + ((long long)li * n + j));
                 }
@@ -580,10 +516,7 @@ __global__ __launch_bounds__(64) void stencil5_rowlds_block_kernel(
             double dot = 0.0;
             if (!rowlds_tile<1, false, true>(m, x, y, alpha, li, gfirst + li, j0, lane, skip, strip, xrow, none, &dot, sp, uniform)) return;
             if (lane == 0) dot_partials[(li - gi_lo) * col_tiles + col_tile] = dot;
-            // the next row rewrites the LDS this row's lanes have just read
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();  // the next row rewrites the LDS this row's lanes have just read
         }
     }
 }
@@ -1029,6 +962,7 @@ __global__ __launch_bounds__(kEllBlock) void ell_stencil5_kernel(int rows, int w
                          v3 = kNt ? __builtin_nontemporal_load(v + 3 * R) : v[3 * R],
                          v4 = kNt ? __builtin_nontemporal_load(v + 4 * R) : v[4 * R];
             const double xc = x[r];
+            // stencil5_interior (stencil_row_device.hpp) written out: profiles/r14_stencil_helpers_isa_identity.txt, class C site 5, says why
             sum = v1 * x[r - 1];
             sum = fma(v2, xc, sum);
             sum = fma(v3, x[r + 1], sum);
@@ -1265,8 +1199,7 @@ namespace {
 void launch_rowlds(const SlabCsr& m, const Stencil5Plan& p, const double* x, double* y, double alpha, int gi_lo, int row_step,
                    int tiles, double* d_dot_partials, const int* d_skip_flag, bool reverse, hipStream_t stream, const ResidualOut* init,
                    const SymPlanes* planes, const ChebStep* step = nullptr) {
-    const int span = 8 * p.xcd_run;
-    const dim3 grid((unsigned)(((long long)tiles + span - 1) / span * span));
+    const dim3 grid((unsigned)xcd_padded_grid(tiles, p.xcd_run));
     const int gfirst = m.row_offset / m.grid_size;
     const ResidualOut res = init ? *init : ResidualOut{nullptr, nullptr, nullptr};
     const SymPlanes sp = planes ? *planes : SymPlanes{};
@@ -1285,8 +1218,7 @@ void launch_rowlds(const SlabCsr& m, const Stencil5Plan& p, const double* x, dou
 void launch_rowlds_block(const SlabCsr& m, const Stencil5Plan& p, const double* x, double* y, double alpha, double* d_dot_partials,
                          const int* d_skip_flag, bool reverse, hipStream_t stream, const SymPlanes& sp) {
     const int blocks = rowlds_block_tiles(p);
-    const int span = 8 * p.xcd_run;
-    const dim3 grid((unsigned)(((long long)blocks + span - 1) / span * span));
+    const dim3 grid((unsigned)xcd_padded_grid(blocks, p.xcd_run));
     const int gfirst = m.row_offset / m.grid_size;
 #define SPMV_AMD_LAUNCH_ROWLDS_BLOCK(ROWS)                                                                                      \
     hipLaunchKernelGGL((stencil5_rowlds_block_kernel<ROWS>), grid, dim3(64), 0, stream, m, x, y, alpha, p.gi_lo, p.gi_hi, gfirst, \
@@ -1503,9 +1435,9 @@ void launch_ell_spmv(int rows, int width, const int* idx, const double* val, con
     // each XCD takes `run` consecutive 256-row blocks of every run of 8 * run (15 000^2: 2.95-3.03 ms in dispatch
     // order, 2.86 ms with runs of 9; 10 000^2: 1.35 -> 1.30 ms; profiles/r02_xcd_group.txt)
     const int run = grid_hint > 0 ? xcd_run_group(grid_hint, kEllBlock, 7) + 1 : 8;
-    const long long span = 8LL * run, blocks = ell_fused_dot_partials(rows);
-    hipLaunchKernelGGL((ell_spmv_kernel<kEllBlock, true>), dim3((unsigned)((blocks + span - 1) / span * span)), dim3(kEllBlock), 0, stream, rows,
-                       width, idx, val, x, y, alpha, beta, run, (int)blocks, d_dot_partials);
+    const int blocks = ell_fused_dot_partials(rows);
+    hipLaunchKernelGGL((ell_spmv_kernel<kEllBlock, true>), dim3((unsigned)xcd_padded_grid(blocks, run)), dim3(kEllBlock), 0, stream, rows,
+                       width, idx, val, x, y, alpha, beta, run, blocks, d_dot_partials);
 }
 
 void launch_ell_stencil5_spmv(int rows, int width, int grid_size, const int* idx,
@@ -1518,9 +1450,9 @@ void launch_ell_stencil5_spmv(int rows, int width, int grid_size, const int* idx
     }
     // 15 000^2: 2.27-2.29 ms in dispatch order, 2.01 ms with runs of 8 blocks per XCD; 20 000^2: 4.01 -> 3.6-3.7 ms
     const int run = xcd_run_group(grid_size, kEllBlock, 8);
-    const long long span = 8LL * run, blocks = ell_fused_dot_partials(rows);
-    hipLaunchKernelGGL((ell_stencil5_kernel<kEllBlock, true>), dim3((unsigned)((blocks + span - 1) / span * span)), dim3(kEllBlock), 0, stream,
-                       rows, width, grid_size, idx, val, x, y, alpha, beta, run, (int)blocks, d_dot_partials);
+    const int blocks = ell_fused_dot_partials(rows);
+    hipLaunchKernelGGL((ell_stencil5_kernel<kEllBlock, true>), dim3((unsigned)xcd_padded_grid(blocks, run)), dim3(kEllBlock), 0, stream, rows,
+                       width, grid_size, idx, val, x, y, alpha, beta, run, blocks, d_dot_partials);
 }
 
 }  // namespace spmv_amd

@@ -252,7 +252,7 @@ void spmv_amd_cg_release_workspace(void);
  * nrhs vectors one after the other (numpy (nrhs, n) in C order); the two helpers below convert. nrhs is 1 to 8.
  * "stencil5-csr" and "cusparse-csr" have the multi-RHS path ("ellpack" / "stencil5-ellpack" and caller-supplied operator
  * tables do not). Column j of every result is computed by exactly the arithmetic of the single-vector path on column j
- * (spmv_kernels.hip:1-10): it depends on column j's data only, not on nrhs nor on the other columns.
+ * (csrc/stencil_row_device.hpp): it depends on column j's data only, not on nrhs nor on the other columns.
  * Every entry point checks its arguments (nrhs outside 1..8, null pointers, an operator without the path or not initialised)
  * before any HIP call and returns non-zero with a message on stderr. */
 

@@ -123,6 +123,41 @@ def test_trace_gaps_finds_the_last_solve_by_every_anchor(tmp_path):
     assert out.returncode == 0 and "solve -2 of the trace: 15 kernels" in out.stdout, out.stdout + out.stderr
 
 
+def test_compare_device_asm_tells_the_three_classes_apart(tmp_path):
+    """tools/compare_device_asm.py (per-kernel comparison of two device assembly files, profiles/*_isa_identity.txt) on three
+    hand-written kernel sections, one per class: the same text under another function ordinal and other comments; the same
+    instructions on other registers; one instruction more. CPU only."""
+    import subprocess
+    import sys
+    from conftest import ROOT
+
+    def kernel(name, ordinal, body, vgprs=8, note=""):
+        return (f'\t.section\t.text.{name},"axG",@progbits,{name},comdat\n\t.globl\t{name}\n{name}:\n; %bb.0: {note}\n' + body.replace("LBB", f".LBB{ordinal}_") +
+                f'\ts_endpgm\n.Lfunc_end{ordinal}:\n\t.section\t.rodata,"a",@progbits\n\t.amdhsa_kernel {name}\n\t\t.amdhsa_next_free_vgpr {vgprs}\n'
+                f'\t\t.amdhsa_next_free_sgpr 16\n\t.end_amdhsa_kernel\n\t.section\t.text.{name},"axG",@progbits,{name},comdat\n\t.set {name}.num_vgpr, {vgprs}\n'
+                f'\t.section\t.AMDGPU.csdata,"",@progbits\n; Kernel info:\n; NumVgprs: {vgprs} {note}\n')
+
+    body = "\tv_fma_f64 v[2:3], v[4:5], v[6:7], v[2:3]\n\ts_cbranch_execz LBB1\n\tglobal_store_dwordx2 v[0:1], v[2:3], off ; store\nLBB1:\n"
+    renamed = body.replace("v[2:3]", "v[10:11]").replace("v[4:5]", "v[2:3]")
+    longer = body.replace("\ts_cbranch", "\ts_waitcnt vmcnt(0)\n\ts_cbranch")
+    head = '\t.text\n\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"\n'
+    tail = '\t.text\n\t.amdgpu_metadata\n---\namdhsa.kernels: []\n...\n\t.end_amdgpu_metadata\n'
+    first, second = tmp_path / "parent.s", tmp_path / "head.s"
+    first.write_text(head + '\t.file\t"parent.hip"\n' + kernel("k_same", 0, body) + kernel("k_regs", 1, body) + kernel("k_longer", 2, body) + kernel("k_budget", 3, body) + tail)
+    second.write_text(head + '\t.file\t"head.hip"\n' + kernel("k_new", 0, body) + kernel("k_same", 1, body, note="another comment") + kernel("k_regs", 2, renamed) +
+                      kernel("k_longer", 3, longer) + kernel("k_budget", 4, renamed, vgprs=12) + tail)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "compare_device_asm.py"), str(first), str(second)], capture_output=True, text=True, timeout=60)
+    lines = {l.split()[3] if l.split()[0] in ("identical", "registers-only", "different") else l.split()[2]: l for l in out.stdout.splitlines()}
+    assert out.returncode == 1 and set(lines) == {"k_same", "k_regs", "k_longer", "k_budget", "k_new"}, out.stdout + out.stderr
+    assert lines["k_same"].split()[:3] == ["identical", "17", "17"], lines["k_same"]
+    assert lines["k_regs"].split()[:3] == ["registers-only", "17", "17"], lines["k_regs"]
+    assert lines["k_longer"].split()[:3] == ["different", "17", "18"] and lines["k_longer"].endswith(".amdhsa block same"), lines["k_longer"]
+    assert lines["k_budget"].split()[0] == "different" and lines["k_budget"].endswith(".amdhsa block DIFFERS"), lines["k_budget"]  # a register rename that needs more registers
+    assert lines["k_new"].split()[0] == "only-in-second", lines["k_new"]
+    same = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "compare_device_asm.py"), str(first), str(first)], capture_output=True, text=True, timeout=60)
+    assert same.returncode == 0 and all(l.startswith("identical") for l in same.stdout.splitlines()) and len(same.stdout.splitlines()) == 4
+
+
 def test_bench_parity_gate_logic_on_the_cpu(golden):
     """bench.py's parity_vs_golden: the committed history passes; one residual off by 1e-9, a missing residual or another
     iteration count does not; a grid without a committed history is reported as such (and does not block a run)."""
