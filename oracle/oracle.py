@@ -193,6 +193,15 @@ def update_p(r, beta, p):
     return p
 
 
+def fma(a, b, c):
+    """fma(a[i], b[i], c[i]) element by element: ONE rounding each (numpy's a * b + c rounds twice)."""
+    a, b, c = np.broadcast_arrays(_f64(a), _f64(b), _f64(c))
+    a, b, c = _f64(a).ravel(), _f64(b).ravel(), _f64(c).ravel()
+    out = np.empty_like(a)
+    lib().oracle_fma(len(a), _dp(a), _dp(b), _dp(c), _dp(out))
+    return out
+
+
 def dot_host(x, y):
     x, y = _f64(x), _f64(y)
     return lib().oracle_dot_host(len(x), _dp(x), _dp(y))

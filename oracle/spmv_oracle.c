@@ -266,6 +266,12 @@ void oracle_update_p(int n, const double* r, double beta, double* p) {
     for (int i = 0; i < n; i++) p[i] = fma(beta, p[i], r[i]);
 }
 
+/* out[i] = fma(a[i], b[i], c[i]): one fused operation per element, three vectors (the accumulation step of the device's dot
+ * products, restated in tests/reduction_restatement.py; numpy's a*b + c rounds twice) */
+void oracle_fma(int n, const double* a, const double* b, const double* c, double* out) {
+    for (int i = 0; i < n; i++) out[i] = fma(a[i], b[i], c[i]);
+}
+
 /* ------------------------------------------------------------------ */
 /* dot products (cg_solver.cu:110-149, 384-409)                        */
 /* ------------------------------------------------------------------ */

@@ -103,6 +103,7 @@ void oracle_axpy(int n, double alpha, const double* x, double* y);
 void oracle_axpby(int n, double alpha, const double* x, double beta, const double* y, double* z);
 void oracle_axpy_sub(int n, double alpha, const double* x, double* y);
 void oracle_update_p(int n, const double* r, double beta, double* p);
+void oracle_fma(int n, const double* a, const double* b, const double* c, double* out);
 
 /* dot_kernel + sum_block_results (cg_solver.cu:110-149): 256-wide tree per block,
  * then a left-to-right host sum over the blocks. */

@@ -13,6 +13,7 @@ import pytest
 
 import matrices as M
 import multi_rhs_restatement as R
+from bitwise import same_bits
 from test_multi_rhs_gpu import random_stencil
 from test_pcg_stages_gpu import GUARD, SENTINEL, SUM_TOL, Guarded
 
@@ -51,14 +52,6 @@ class Shifted(Guarded):
         host = self.dev.to_host()
         assert np.all(host[:self.lead] == SENTINEL) and np.all(host[self.lead + self.n:] == SENTINEL), "written outside the array"
         return host[self.lead:self.lead + self.n].copy()
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same_bits(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 def interleave(columns):
