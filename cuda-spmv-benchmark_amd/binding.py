@@ -134,7 +134,8 @@ DECLARED_SYMBOLS = [
     "spmv_amd_precond_create_chebyshev", "spmv_amd_precond_chebyshev_info", "spmv_amd_precond_apply_device",
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
-LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_cg_slab_block_map", "spmv_amd_pcg_stage",
+LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_cg_slab_block_map", "spmv_amd_cg_slab_slow_blocks",
+                    "spmv_amd_cg_slab_direction_spmv", "spmv_amd_cg_slab_spmv_dot", "spmv_amd_pcg_stage",
                     "spmv_amd_pcg_last_step_launches", "spmv_amd_cg_multi_stage"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
 DECLARED_CXX_SYMBOLS = [
@@ -230,6 +231,13 @@ def lib():
         L.spmv_amd_cg_slab_tile_classes.restype = C.c_longlong
         L.spmv_amd_cg_slab_block_map.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
         L.spmv_amd_cg_slab_block_map.restype = C.c_longlong
+        L.spmv_amd_cg_slab_slow_blocks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
+        L.spmv_amd_cg_slab_slow_blocks.restype = C.c_longlong
+        L.spmv_amd_cg_slab_direction_spmv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                      C.POINTER(C.c_double), C.c_void_p, C.c_int]
+        L.spmv_amd_cg_slab_direction_spmv.restype = C.c_int
+        L.spmv_amd_cg_slab_spmv_dot.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_int]
+        L.spmv_amd_cg_slab_spmv_dot.restype = C.c_int
         L.spmv_amd_pcg_stage.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PcgStageArgs), C.POINTER(PcgScalars)]
         L.spmv_amd_pcg_stage.restype = C.c_int
         L.spmv_amd_pcg_last_step_launches.argtypes = []
@@ -934,12 +942,50 @@ class CgSlab:
         lib().spmv_amd_cg_slab_block_map(self.h, int(which), out.ctypes.data, count)
         return out
 
+    def slow_blocks(self, which):
+        """The slow blocks of a launch range (LAB build only; which as in block_map): int32 indices of the block tiles whose map byte
+        is 0, ascending, as the launch behind the direction update inside the block SpMV reads them (empty: none)."""
+        if not is_lab():
+            raise RuntimeError("the slow-block lists are read through the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        count = int(lib().spmv_amd_cg_slab_slow_blocks(self.h, int(which), None, 0))
+        out = np.zeros(max(count, 0), dtype=np.int32)
+        if count > 0:
+            lib().spmv_amd_cg_slab_slow_blocks(self.h, int(which), out.ctypes.data, count)
+        return out
+
+    def spmv_dot(self):
+        """(partials, pAp) the last spmv() in its in-loop form (set_option("spmv_with_dot", 1)) left beside y (LAB build only)."""
+        if not is_lab():
+            raise RuntimeError("the in-loop SpMV's sum is read through the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        pAp = C.c_double(0.0)
+        count = lib().spmv_amd_cg_slab_spmv_dot(self.h, C.byref(pAp), None, 0)
+        partials = np.empty(count, dtype=np.float64)
+        lib().spmv_amd_cg_slab_spmv_dot(self.h, C.byref(pAp), partials.ctypes.data, count)
+        return partials, pAp.value
+
+    def direction_spmv(self, r, p_in, beta, iteration_matches=1, converged=0):
+        """spmv_amd_cg_slab_direction_spmv (LAB build only; include/spmv_amd/lab.h): the direction update inside the block SpMV, the
+        launch over the slow blocks and the reduction, once, on r and p_in (n_local doubles each). Returns (p_out, Ap, partials, pAp);
+        what a launch did not write is NaN."""
+        if not is_lab():
+            raise RuntimeError("the fused launch alone runs in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        p_in = np.ascontiguousarray(p_in, dtype=np.float64)
+        p_out, Ap = np.empty_like(r), np.empty_like(r)
+        partials = np.empty(len(r), dtype=np.float64)  # more than any plan writes (one per 128 x 1 tile)
+        pAp = C.c_double(0.0)
+        used = lib().spmv_amd_cg_slab_direction_spmv(self.h, r.ctypes.data, p_in.ctypes.data, float(beta), int(iteration_matches), int(converged),
+                                                     p_out.ctypes.data, Ap.ctypes.data, C.byref(pAp), partials.ctypes.data, len(partials))
+        if used < 0:
+            raise RuntimeError("this slab cannot take the direction update inside the block SpMV (no block map, neighbours, or ring 1)")
+        return p_out, Ap, partials[:used], pAp.value
+
     def set_block_rows(self, rows):
         """Grid rows per block tile of the in-loop SpMV (LAB build only): 0 = the one-row kernel, 4 or 8. Rebuilds the block maps."""
         self.set_option("block_rows", rows)
 
     def loop_shape(self):
-        """"single rank" | "pipeline ..." | "plain: <who decided>" (include/spmv_amd/api.h)."""
+        """"single rank[: direction update inside the block SpMV]" | "pipeline ..." | "plain: <who decided>" (include/spmv_amd/api.h)."""
         return lib().spmv_amd_cg_slab_loop_shape(self.h).decode()
 
     def timeline_solve(self, max_iters=1000, tol=1e-6):

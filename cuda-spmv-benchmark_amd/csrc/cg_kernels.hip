@@ -22,6 +22,7 @@
 
 #include <stdlib.h>
 
+#include "direction_device.hpp"
 #include "reduce_device.hpp"
 #include "spmv_amd/hip_check.h"
 #include "stream_device.hpp"
@@ -231,13 +232,7 @@ __global__ __launch_bounds__(kStream) void cg_update_r_kernel(size_t n, const Cg
     if (threadIdx.x == 0) partials[block] = acc;
 }
 
-// The direction update p' = r + beta p exists in two roundings upstream: the multi-GPU solver's axpby_kernel
-// evaluates 1.0*r + beta*p, i.e. fma(1.0, r, beta*p) with beta*p rounded first (cg_solver_mgpu_partitioned.cu:136-140,
-// :682), the single-GPU device solver's update_p_kernel evaluates r + beta*p as one fma(beta, p, r)
-// (cg_solver.cu:90-95). fma_form selects the second; each solver keeps its own reference's arithmetic.
-__device__ __forceinline__ double direction(double r, double beta, double p, int fma_form) {
-    return fma_form ? fma(beta, p, r) : fma(1.0, r, beta * p);
-}
+// The direction update p' = r + beta p in its two roundings: direction(), direction_device.hpp.
 
 // x += alpha*p of iteration `iteration` and, unless that iteration converged, p = 1.0*r + beta*p, in
 // one pass over p (the reference reads p twice: axpy_kernel(alpha, p, x) :598 and axpby_kernel :682).

@@ -68,6 +68,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <limits>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -135,6 +136,13 @@ struct SpmvAmdCgSlab {
     // knobs.rowlds_block_rows grid rows, and each launch range -- the whole slab, the rows that need no halo -- has a map of its own,
     // derived from tile_classes: the ranges start at different grid rows, so their blocks hold different rows.
     unsigned char *block_map_whole = nullptr, *block_map_interior = nullptr;
+    // The blocks of each range whose map byte is 0, in ascending order (device memory; the counts stay on the host): the launch that
+    // follows the direction update inside the block SpMV evaluates exactly these (kernels.hpp, DirectionSpmv).
+    int *slow_list_whole = nullptr, *slow_list_interior = nullptr;
+    int slow_count_whole = 0, slow_count_interior = 0;
+    // SPMV_AMD_FUSED_DIRECTION (0 / 1, read at creation): the direction update inside the block SpMV where the slab is eligible
+    // (LoopShape::fused_direction). LAB build, set_option("fused_direction", 2): on regardless of the slow blocks' share.
+    int fused_direction = 1;
     bool spmv_with_dot = false;  // LAB option: spmv_amd_cg_slab_spmv runs the in-loop form (dot partials wanted)
     const SymPlanes* sym() const { return planes_on ? &planes : nullptr; }
     // place_coefficients: {0, candidates timed, SpMV ms before, SpMV ms kept}
@@ -266,6 +274,10 @@ struct SpmvAmdCgSlab {
 namespace {
 // marks per iteration on the compute stream: iteration start | interior SpMV enqueued-and-done | boundary rows |
 // p.Ap sum (+ all-reduce) | r update | r.r sum (+ all-reduce) + scalar step | direction update
+// (LoopShape::fused_direction: the direction update rides in the next iteration's SpMV launch, so spmv_interior_us of iterations
+// >= 1 is that launch -- direction update, SpMV and the launch over the slow blocks -- and direction_update_us holds no launch: it
+// reports what lies between its two marks, the event records themselves (a few us; and a window flush where the ring is shorter
+// than the solve), so that the stages still add up to the iteration; direction_updates is counted as before)
 constexpr int kTimelineMarks = 7;
 const char* const kTimelineNames =
     "iterations,solve_ms,initial_residual_us,spmv_interior_us,halo_wait_and_boundary_rows_us,reduce_pAp_and_allreduce_us,"
@@ -359,6 +371,9 @@ void build_block_maps(SpmvAmdCgSlab* s) {
     HIP_CHECK(hipStreamSynchronize(s->compute));
     device_release(s->block_map_whole);
     device_release(s->block_map_interior);
+    device_release(s->slow_list_whole);
+    device_release(s->slow_list_interior);
+    s->slow_count_whole = s->slow_count_interior = 0;
     if (s->tile_classes != nullptr) {
         const auto map_of = [&](const Stencil5Plan& p) -> unsigned char* {
             const int blocks = rowlds_block_tiles(p);
@@ -369,6 +384,27 @@ void build_block_maps(SpmvAmdCgSlab* s) {
         s->block_map_whole = map_of(s->plan_whole);
         s->block_map_interior = map_of(s->plan_interior);
         HIP_CHECK(hipStreamSynchronize(s->compute));
+        // the slow blocks of a range, listed once (a map is one byte per block tile: 0.8 MB at 20 000^2)
+        const auto list_of = [&](const Stencil5Plan& p, const unsigned char* map, int* count) -> int* {
+            *count = 0;
+            if (map == nullptr) return nullptr;
+            std::vector<unsigned char> h((size_t)rowlds_block_tiles(p));
+            HIP_CHECK(hipMemcpy(h.data(), map, h.size(), hipMemcpyDeviceToHost));
+            std::vector<int> slow;
+            for (size_t b = 0; b < h.size(); ++b)
+                if (h[b] == 0) slow.push_back((int)b);
+            if (slow.empty()) return nullptr;
+            int* list = device_try_alloc<int>(slow.size());
+            if (list == nullptr) {
+                *count = -1;  // no list: the range keeps the two-launch form
+                return nullptr;
+            }
+            HIP_CHECK(hipMemcpy(list, slow.data(), slow.size() * sizeof(int), hipMemcpyHostToDevice));
+            *count = (int)slow.size();
+            return list;
+        };
+        s->slow_list_whole = list_of(s->plan_whole, s->block_map_whole, &s->slow_count_whole);
+        s->slow_list_interior = list_of(s->plan_interior, s->block_map_interior, &s->slow_count_interior);
     }
     attach_block_maps(s);
 }
@@ -514,6 +550,7 @@ void make_common(SpmvAmdCgSlab* s) {
         HIP_CHECK(hipMemset(s->d_alpha_ring, 0, kMaxRingSlots * sizeof(double)));
     }
     if (const char* v = getenv("SPMV_AMD_NO_OVERLAP")) s->no_overlap = v[0] == '1';
+    if (const char* v = getenv("SPMV_AMD_FUSED_DIRECTION")) s->fused_direction = v[0] == '1' ? 1 : 0;
 #ifdef SPMV_AMD_LAB
     if (const char* v = getenv("SPMV_AMD_TEST_WEDGE_OVERLAPPED_EXCHANGE")) s->test_wedge_overlapped_exchange = atoi(v);
 #endif
@@ -801,6 +838,30 @@ int slab_spmv(SpmvAmdCgSlab* s, bool with_dot, bool overlap, const int* skip,
     return used;
 }
 
+// Can the whole-slab launch take the direction update inside the block SpMV (kernels.hpp, DirectionSpmv)? The plan runs the block
+// kernel on the class map, and the slow blocks are listed. cap: they are at most 1 / 16 of the range's blocks -- each of them costs a
+// second pass over its rows, so a matrix with few uniform tiles keeps the two launches.
+bool direction_spmv_available(const SpmvAmdCgSlab* s, bool cap) {
+    const Stencil5Plan& p = s->plan_whole;
+    const SymPlanes* sp = s->sym();
+    if (s->op != nullptr || !s->fused_dot || sp == nullptr || sp->ce == nullptr || sp->cls == nullptr) return false;
+    if (p.variant != Stencil5Variant::RowLds || p.block_rows <= 0 || p.block_map == nullptr || s->slow_count_whole < 0) return false;
+    return !cap || 16LL * s->slow_count_whole <= rowlds_block_tiles(p);
+}
+
+// p_out = r + beta p_in, Ap = A p_out, the partials of p_out . Ap and their sum: the direction update of iteration `iteration`
+// (1-based, as the kernels count) and the SpMV of the next one in one launch (+ one over the slow blocks), on a slab without
+// neighbours. spmv_done as in slab_spmv.
+int slab_direction_spmv(SpmvAmdCgSlab* s, const double* p_in, double* p_out, int iteration, hipEvent_t spmv_done = nullptr) {
+    s->spmv_split_at = -1;
+    const DirectionSpmv d{s->d_s, iteration, s->device_form, s->r, p_in, p_out, s->slow_list_whole, s->slow_count_whole};
+    const int used = launch_stencil5_direction_spmv(s->A.view, s->plan_whole, d, s->Ap, 1.0, s->partials_spmv, s->shape.reverse, s->compute, *s->sym());
+    if (s->tl_after_interior) HIP_CHECK(hipEventRecord(s->tl_after_interior, s->compute));
+    if (spmv_done) HIP_CHECK(hipEventRecord(spmv_done, s->compute));
+    reduce_spmv_partials(s, used, &s->d_s->pAp, &s->d_s->converged, s->spmv_progress, s->spmv_progress_value, s->reduce_mailbox);
+    return used;
+}
+
 const char* query_name(hipError_t e) {
     return e == hipSuccess ? "idle (all work done)" : e == hipErrorNotReady ? "busy (work pending)" : hipGetErrorString(e);
 }
@@ -905,6 +966,10 @@ struct LoopShape {
     // flag releases the exchange. false = PLAIN: everything on the compute stream, the exchange behind the whole direction update.
     bool pipeline = false;
     bool late = false;       // direction update as lead piece + rest (late bulk)
+    // The direction update of iteration k rides in the SpMV launch of iteration k + 1 (slab_direction_spmv): a slab without
+    // neighbours that owns its matrix, the direction ring, no detailed timers, a whole-slab plan on the block kernel whose slow
+    // blocks are at most 1 / 16 of its blocks. The direction stage then enqueues no vector launch and late bulk has nothing to split.
+    bool fused_direction = false;
     int slots = 1;           // direction ring length; 1 = the in-place x / p update
     EdgeRows edges{0, 0, 0}; // pipeline: [0, count_a) and [second, second + count_b)
     size_t bulk_lo = 0, bulk_hi = 0;  // the rows of the direction update that are not edge rows
@@ -922,7 +987,9 @@ LoopShape loop_shape(const SpmvAmdCgSlab* s, const CGConfigMultiGPU* config) {
     L.detail = config->enable_detailed_timers != 0;
     L.slots = s->ring_slots;
     // (ring mode only: with the in-place form the x update of the converging iteration rides in that very launch)
-    L.late = s->late_bulk && !L.detail && L.slots > 1;
+    L.fused_direction = s->fused_direction != 0 && !L.multi && s->op == nullptr && L.slots > 1 && !L.detail &&
+                        direction_spmv_available(s, /*cap=*/s->fused_direction != 2);
+    L.late = s->late_bulk && !L.detail && L.slots > 1 && !L.fused_direction;
     // Early halo (round 3): the two edge ranges are rounded OUTWARDS to 4 KiB (512 doubles), so that the launch over the rest
     // starts on a 4 KiB boundary like every whole-vector launch does: with the ranges cut exactly at the grid row, the rest of a
     // 15 000-column slab started 64 bytes off a 128-byte line and its direction update ran 20-30 % slower (485 vs 386 us at
@@ -1052,9 +1119,13 @@ SpmvAmdCgSlab* create_from_matrix(MatrixData* mat, SpmvAmdComm* comm, bool setup
 
 extern "C" SpmvAmdCgSlab* spmv_amd_cg_slab_create(MatrixData* mat, SpmvAmdComm* comm) { return create_from_matrix(mat, comm, true); }
 
-// Which shape this slab's loop takes and who decided: "single rank", "pipeline", "plain: <why>". A static string.
+// Which shape this slab's loop takes and who decided: "single rank" (": direction update inside the block SpMV" where
+// LoopShape::fused_direction holds with detailed timers off), "pipeline", "plain: <why>". A static string.
 extern "C" const char* spmv_amd_cg_slab_loop_shape(const SpmvAmdCgSlab* s) {
-    if (!s->comm->exchanges_halos()) return "single rank";
+    if (!s->comm->exchanges_halos()) {
+        const CGConfigMultiGPU any = {1, 0.0, 0, 0};
+        return loop_shape(s, &any).fused_direction ? "single rank: direction update inside the block SpMV" : "single rank";
+    }
     if (!s->no_overlap) {
         const CGConfigMultiGPU any = {1, 0.0, 0, 0};
         if (!loop_shape(s, &any).pipeline) return "plain: the in-place form (ring 1) or a slab too thin to split";
@@ -1143,6 +1214,7 @@ struct SolveRun {
     int tl_exchanges = 0;       // halo exchanges marked on the side stream (exchange j precedes the SpMV of iteration j)
     bool halo_in_flight = false;
     bool step_in_direction = false;  // this iteration's scalar step rides in the direction update's launch
+    const double* direction_from = nullptr;  // fused_direction: p of the iteration just stepped, which the next SpMV launch reads r + beta p from
     // Status records: the record of iteration j (1-based) of this solve carries sequence0 + j. records_read = the latest
     // iteration whose record the host has seen; the host runs at most ONE iteration ahead of it (read_status).
     int sequence0 = 0, records_read = 0;
@@ -1318,14 +1390,20 @@ void SolveRun::stage_spmv() {
     s->spmv_progress = &s->h_poll->progress;
     s->spmv_progress_value = 4 * (s->poll_sequence + 1) + 1;
     mark(enqueued, 0);
+    // fused_direction: the launch of iterations >= 1 writes this iteration's direction (s->p, the slot the direction stage chose)
+    // from the previous one on its way; `enqueued` is the number of the iteration that direction belongs to, as the kernels count
+    const auto spmv = [&](hipEvent_t spmv_done) {
+        if (L.fused_direction && enqueued > 0) return slab_direction_spmv(s, direction_from, s->p, enqueued, spmv_done);
+        return slab_spmv(s, true, halo_in_flight, skip, nullptr, spmv_done);
+    };
     if (timeline) {
         // [1] is recorded inside slab_spmv behind the interior launch, [2] behind the boundary rows; the reduction of the
         // partials is issued by slab_spmv too, so [3] follows directly
         s->tl_after_interior = tl_event(s->tl_compute, mark_index(enqueued, 1));
-        slab_spmv(s, true, halo_in_flight, skip, nullptr, tl_event(s->tl_compute, mark_index(enqueued, 2)));
+        spmv(tl_event(s->tl_compute, mark_index(enqueued, 2)));
         s->tl_after_interior = nullptr;
     } else if (L.detail) {
-        timed(&stats->time_spmv_ms, nullptr, [&] { slab_spmv(s, true, halo_in_flight, skip); });
+        timed(&stats->time_spmv_ms, nullptr, [&] { spmv(nullptr); });
     } else if (s->spmv_event_stride > 0 && (enqueued + s->spmv_event_phase) % s->spmv_event_stride == 0) {
         while (s->spmv_ev.size() < 2 * (size_t)(sampled + 1)) {
             hipEvent_t e;
@@ -1333,11 +1411,11 @@ void SolveRun::stage_spmv() {
             s->spmv_ev.push_back(e);
         }
         HIP_CHECK(hipEventRecord(s->spmv_ev[2 * sampled], s->compute));
-        slab_spmv(s, true, halo_in_flight, skip, nullptr, s->spmv_ev[2 * sampled + 1]);
+        spmv(s->spmv_ev[2 * sampled + 1]);
         sampled_iteration.push_back(enqueued);
         ++sampled;
     } else {
-        slab_spmv(s, true, halo_in_flight, skip);
+        spmv(nullptr);
     }
     s->spmv_progress = nullptr;
 }
@@ -1478,7 +1556,8 @@ void SolveRun::stage_direction_and_halo() {
             }
             trace.push("BLAS_AXPBY");
         };
-        if (L.pipeline) pieces(fused, plain);
+        if (L.fused_direction) direction_from = p_in;  // no launch here: the next SpMV's launch evaluates r + beta p_in into p_next itself
+        else if (L.pipeline) pieces(fused, plain);
         else pieces(plain, plain);
         s->p = p_next;
     }
@@ -1778,6 +1857,10 @@ extern "C" int spmv_amd_cg_slab_set_option(SpmvAmdCgSlab* s, const char* name, l
             if (p->variant == Stencil5Variant::RowLds) p->block_rows = (int)value;
         build_block_maps(s);
     }
+    else if (strcmp(name, "fused_direction") == 0) {  // 0: the direction update as a launch of its own, 1: inside the block SpMV where eligible, 2: ... whatever the slow blocks' share
+        if (value < 0 || value > 2) return -1;
+        s->fused_direction = (int)value;
+    }
     else if (strcmp(name, "spmv_with_dot") == 0) s->spmv_with_dot = value != 0;  // spmv() in its in-loop form: p.Ap partials and their sum too
     else return -1;
     return 0;
@@ -1792,6 +1875,63 @@ extern "C" long long spmv_amd_cg_slab_block_map(const SpmvAmdCgSlab* s, int whic
     const long long count = rowlds_block_tiles(p);
     if (out != nullptr && cap > 0) HIP_CHECK(hipMemcpy(out, p.block_map, (size_t)std::min(count, cap), hipMemcpyDeviceToHost));
     return count;
+}
+
+// (LAB build only.) The slow blocks of a launch range (which: as above): the indices of the block tiles whose map byte is 0, ascending,
+// as the launch behind the direction update inside the block SpMV reads them. Copies min(count, cap) ints and returns count.
+extern "C" long long spmv_amd_cg_slab_slow_blocks(const SpmvAmdCgSlab* s, int which, int* out, long long cap) {
+    const int* list = which == 0 ? s->slow_list_whole : s->slow_list_interior;
+    const long long count = which == 0 ? s->slow_count_whole : s->slow_count_interior;
+    if (count <= 0) return count;
+    if (out != nullptr && cap > 0) HIP_CHECK(hipMemcpy(out, list, (size_t)std::min(count, cap) * sizeof(int), hipMemcpyDeviceToHost));
+    return count;
+}
+
+// (LAB build only.) What the last spmv_amd_cg_slab_spmv in its in-loop form ("spmv_with_dot" 1) left beside y: *pAp = the reduced
+// sum x . (A x) as the loop's scalar step would read it, and the whole-slab plan's partials (min(count, cap) doubles; returns count).
+extern "C" int spmv_amd_cg_slab_spmv_dot(const SpmvAmdCgSlab* s, double* pAp, double* partials, int cap) {
+    HIP_CHECK(hipStreamSynchronize(s->compute));
+    HIP_CHECK(hipMemcpy(pAp, &s->d_s->pAp, sizeof(double), hipMemcpyDeviceToHost));
+    const int count = s->plan_whole.partials;
+    if (partials != nullptr && cap > 0) HIP_CHECK(hipMemcpy(partials, s->partials_spmv, (size_t)std::min(count, cap) * sizeof(double), hipMemcpyDeviceToHost));
+    return count;
+}
+
+// (LAB build only.) The direction update inside the block SpMV, once, on the caller's vectors (host, n_local doubles each): the fused
+// launch, the launch over the slow blocks and the reduction, as an iteration >= 1 of the fused loop shape enqueues them, with
+// s->beta = beta. iteration_matches = 0: the launches are given another iteration number than the scalars hold; converged != 0: the
+// scalars say the solve converged -- either way they must return on the scalars. p_out, Ap (n_local doubles) and partials (cap
+// doubles; returns how many the launches write) are filled with NaN beforehand; *pAp = the reduced sum (NaN where it was not
+// written). Returns the partial count, or -1 where the slab cannot take the launch (direction_spmv_available, ring 1).
+extern "C" int spmv_amd_cg_slab_direction_spmv(SpmvAmdCgSlab* s, const double* r, const double* p_in, double beta, int iteration_matches,
+                                               int converged, double* p_out, double* Ap, double* pAp, double* partials, int cap) {
+    if (s->ring.size() < 2 || s->comm->exchanges_halos() || !direction_spmv_available(s, /*cap=*/false)) return -1;
+    const size_t nl = (size_t)s->n_local;
+    const int iteration = 3;
+    CgScalars sc;
+    memset(&sc, 0, sizeof sc);
+    sc.beta = beta;
+    sc.iterations = iteration;
+    sc.converged = converged != 0 ? 1 : 0;
+    sc.pAp = std::numeric_limits<double>::quiet_NaN();
+    HIP_CHECK(hipMemcpy(s->d_s, &sc, sizeof sc, hipMemcpyHostToDevice));
+    upload(s->r, r, nl);
+    upload(s->ring[0], p_in, nl);
+    HIP_CHECK(hipMemsetAsync(s->ring[1], 0xFF, nl * sizeof(double), s->compute));
+    HIP_CHECK(hipMemsetAsync(s->Ap, 0xFF, nl * sizeof(double), s->compute));
+    HIP_CHECK(hipMemsetAsync(s->partials_spmv, 0xFF, (size_t)s->plan_whole.partials * sizeof(double), s->compute));
+    s->shape.reverse = false;
+    s->reduce_mailbox = nullptr;
+    const int used = slab_direction_spmv(s, s->ring[0], s->ring[1], iteration_matches != 0 ? iteration : iteration + 1);
+    HIP_CHECK(hipStreamSynchronize(s->compute));
+    HIP_CHECK(hipGetLastError());
+    download(p_out, s->ring[1], nl);
+    download(Ap, s->Ap, nl);
+    if (partials != nullptr && cap > 0) download(partials, s->partials_spmv, (size_t)std::min(used, cap));
+    HIP_CHECK(hipMemcpy(&sc, s->d_s, sizeof sc, hipMemcpyDeviceToHost));
+    *pAp = sc.pAp;
+    s->p = s->ring[0];
+    return used;
 }
 
 // (LAB build only.) The tile class map as creation wrote it: one byte per row-lds tile at [local grid row * tiles per grid row +
@@ -1813,10 +1953,25 @@ extern "C" int spmv_amd_cg_slab_timeline(const SpmvAmdCgSlab* s, double* out, in
 extern "C" int spmv_amd_cg_slab_time_spmv(SpmvAmdCgSlab* s, int reps, float* ms_each) {
     HIP_CHECK(hipMemsetAsync(&s->d_s->converged, 0, sizeof(int), s->compute));
     EventTimer t;
+    // a slab whose loop takes the direction update inside the block SpMV: that launch (+ the one over the slow blocks) is its SpMV stage
+    const CGConfigMultiGPU any = {1, 0.0, 0, 0};
+    const bool fused = loop_shape(s, &any).fused_direction;
+    if (fused) {
+        CgScalars sc;
+        memset(&sc, 0, sizeof sc);
+        sc.beta = 0.5, sc.iterations = 1;
+        HIP_CHECK(hipMemcpyAsync(s->d_s, &sc, sizeof sc, hipMemcpyHostToDevice, s->compute));
+        HIP_CHECK(hipStreamSynchronize(s->compute));
+    }
     for (int i = 0; i < reps; ++i) {
         t.begin(s->compute);
-        (void)launch_stencil5_spmv(s->A.view, s->plan_whole, s->p, s->Ap, 1.0, s->fused_dot ? s->partials_spmv : nullptr,
-                                   nullptr, false, s->compute, nullptr, s->sym());
+        if (fused) {
+            const DirectionSpmv d{s->d_s, 1, s->device_form, s->r, s->ring[0], s->ring[1], s->slow_list_whole, s->slow_count_whole};
+            (void)launch_stencil5_direction_spmv(s->A.view, s->plan_whole, d, s->Ap, 1.0, s->partials_spmv, false, s->compute, *s->sym());
+        } else {
+            (void)launch_stencil5_spmv(s->A.view, s->plan_whole, s->p, s->Ap, 1.0, s->fused_dot ? s->partials_spmv : nullptr,
+                                       nullptr, false, s->compute, nullptr, s->sym());
+        }
         t.end(s->compute);
         ms_each[i] = t.elapsed_ms();
     }
@@ -1838,6 +1993,8 @@ extern "C" void spmv_amd_cg_slab_destroy(SpmvAmdCgSlab* s) {
     device_release(s->tile_classes);
     device_release(s->block_map_whole);
     device_release(s->block_map_interior);
+    device_release(s->slow_list_whole);
+    device_release(s->slow_list_interior);
     s->planes_on = false;
     s->r = s->Ap = s->p_alloc = s->p = nullptr;
     s->ring_alloc.clear();

@@ -35,7 +35,9 @@ struct Tunables {
     int rowlds_min_grid = 512;    // SPMV_AMD_ROWLDS_MIN_GRID: smallest grid that takes row-lds automatically (tests force it down)
     int rowlds_group = 0;         // SPMV_AMD_ROWLDS_GROUP: consecutive row-lds tiles per XCD; 0 = derived from the grid (xcd_run_group())
     // SPMV_AMD_ROWLDS_BLOCK_ROWS: grid rows per wave of a solver slab's in-loop SpMV (block tiles): 0 (the one-row kernel), 4 or 8.
-    // 20 000^2 on MI355X, one process, alternated: 1.636 ms / 1.064 / 1.086 (profiles/r13_block_rows_ab.txt)
+    // 20 000^2 on MI355X, one process, alternated: 1.636 ms / 1.064 / 1.086 (profiles/r13_block_rows_ab.txt). With the direction
+    // update inside the SpMV (DirectionSpmv) 8 makes that launch 2 % shorter and the whole solve no faster: 4 stays
+    // (profiles/r15_fused_direction_ab.txt, section 5).
     int rowlds_block_rows = 4;
 };
 
@@ -153,6 +155,24 @@ void launch_verify_sym_planes(const SlabCsr& m, const SymPlanes& planes, int* d_
 int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& plan, const double* x, double* y, double alpha,
                          double* d_dot_partials, const int* d_skip_flag, bool reverse, hipStream_t stream,
                          const ResidualOut* init = nullptr, const SymPlanes* planes = nullptr);
+// The CG direction update inside the in-loop block SpMV (stencil5_direction_block_kernel; slabs without neighbours whose plan has
+// a block map): p_out = direction(r, s->beta, p_in), y = alpha A p_out and the p_out . (A p_out) partials of the plan's slots, in one
+// launch over the block tiles plus one over `slow_list` -- the indices of the range's block tiles whose map byte is 0 (device
+// memory, slow_count of them), which the first launch only writes p_out for. Both launches return on the scalars unless
+// s->iterations == iteration and s->converged == 0. Returns the partial slots written (the plan's).
+struct CgScalars;
+struct DirectionSpmv {
+    const CgScalars* s;
+    int iteration;
+    bool fma_form;
+    const double* r;
+    const double* p_in;
+    double* p_out;
+    const int* slow_list;
+    int slow_count;
+};
+int launch_stencil5_direction_spmv(const SlabCsr& m, const Stencil5Plan& plan, const DirectionSpmv& d, double* y, double alpha,
+                                   double* d_dot_partials, bool reverse, hipStream_t stream, const SymPlanes& planes);
 // The fused Chebyshev step over a row-lds plan (ChebStep): z is read as the SpMV's x, A z is not written. Returns the partial slots
 // a last step writes (the plan's), or -1 without launching when the plan is not a row-lds one.
 int launch_stencil5_cheb_step(const SlabCsr& m, const Stencil5Plan& plan, const double* z, const ChebStep& step, double* d_dot_partials,

@@ -21,6 +21,7 @@
 
 #include <type_traits>
 
+#include "direction_device.hpp"
 #include "reduce_device.hpp"
 #include "stencil_geometry.hpp"
 #include "stencil_row_device.hpp"
@@ -422,6 +423,28 @@ __global__ __launch_bounds__(64) void stencil5_rowlds_kernel(
     if (kMode != 0 && threadIdx.x == 0) dot_partials[tile] = dot;
 }
 
+// A block tile that is not fast (block map byte 0: a tile that streams the planes, the grid's first or last grid row, a short last
+// block): rowlds_tile once per grid row the block holds (block_rows, fewer at the range's end), with that row's own class, one partial per row in the one-row
+// kernel's slot. lds: 5 * 128 + 130 doubles (rowlds_tile's strip and x row). Returns false for a launch enqueued past convergence.
+__device__ __forceinline__ bool rowlds_block_slow_rows(const SlabCsr& m, const double* __restrict__ x, double* __restrict__ y, double alpha,
+                                                       int gi_lo, int gi_hi, int gfirst, int col_tiles, int li0, int block_rows, int col_tile, int j0, int lane, int skip,
+                                                       double* __restrict__ lds, double* __restrict__ dot_partials, const SymPlanes& sp) {
+    double* __restrict__ strip = lds;
+    double* __restrict__ xrow = lds + 5 * kLdsTileCols;
+    const ResidualOut none{nullptr, nullptr, nullptr};
+    const int held = gi_hi - li0 < block_rows ? gi_hi - li0 : block_rows;
+#pragma unroll 1
+    for (int r = 0; r < held; ++r) {
+        const int li = li0 + r;
+        const int uniform = rowlds_tile_class(sp, li, col_tiles, col_tile);
+        double dot = 0.0;
+        if (!rowlds_tile<1, false, true>(m, x, y, alpha, li, gfirst + li, j0, lane, skip, strip, xrow, none, &dot, sp, uniform)) return false;
+        if (lane == 0) dot_partials[(li - gi_lo) * col_tiles + col_tile] = dot;
+        wave_lds_sync();  // the next row rewrites the LDS this row's lanes have just read
+    }
+    return true;
+}
+
 // ---------------------------------------------------------------------------------
 // The in-loop SpMV of a solver slab over BLOCK TILES: one wave evaluates 128 columns of kRows consecutive local grid rows
 // [li0, li0 + kRows). On a uniform tile the one-row kernel moves 16 B/row of unique data (x in, y out) but requests every x value
@@ -505,20 +528,131 @@ __global__ __launch_bounds__(64) void stencil5_rowlds_block_kernel(
             if (lane == 0) dot_partials[(li - gi_lo) * col_tiles + col_tile] = dot;
         }
     } else {
-        double* __restrict__ strip = lds;
-        double* __restrict__ xrow = lds + 5 * kLdsTileCols;
-        const ResidualOut none{nullptr, nullptr, nullptr};
-        const int held = gi_hi - li0 < kRows ? gi_hi - li0 : kRows;
-#pragma unroll 1
-        for (int r = 0; r < held; ++r) {
-            const int li = li0 + r;
-            const int uniform = rowlds_tile_class(sp, li, col_tiles, col_tile);
-            double dot = 0.0;
-            if (!rowlds_tile<1, false, true>(m, x, y, alpha, li, gfirst + li, j0, lane, skip, strip, xrow, none, &dot, sp, uniform)) return;
-            if (lane == 0) dot_partials[(li - gi_lo) * col_tiles + col_tile] = dot;
-            wave_lds_sync();  // the next row rewrites the LDS this row's lanes have just read
+        rowlds_block_slow_rows(m, x, y, alpha, gi_lo, gi_hi, gfirst, col_tiles, li0, kRows, col_tile, j0, lane, skip, lds, dot_partials, sp);
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// The direction update p' = r + beta p INSIDE the in-loop block SpMV (single-rank slabs, cg_slab.hip LoopShape::fused_direction):
+// one launch instead of cg_update_p_ring_kernel followed by stencil5_rowlds_block_kernel. Between the two there is no reduction
+// (beta is known before either starts), and p' was written once and read back (10.3 B/row measured) only because they were two
+// launches. Here a wave reads r and p_in on its kRows + 2 rows, evaluates direction() on all of them -- the two neighbour rows are
+// RE-computed, (kRows + 2) / kRows of the arithmetic, from p_in, which no wave of this launch writes (the ring's new slot is
+// p_out) -- stores its own kRows rows of p' and runs the block kernel's fast path on the values it holds: 16 (kRows + 2) / kRows
+// B/row read, 16 written. Same tile -> XCD relabelling, block map, grid and partial slots as the block kernel.
+// Scalars FIRST, as in cg_update_p_ring_kernel: the launch is enqueued before the host knows whether the iteration converged, and
+// the launch of the converging iteration (or of one past it) reads no vector.
+// A block that is not fast (map byte 0) only writes p' on the rows it holds; its A p' and partials come from
+// stencil5_block_list_kernel behind this launch, which reads p' from memory.
+// ---------------------------------------------------------------------------------
+template <int kRows>
+__global__ __launch_bounds__(64) void stencil5_direction_block_kernel(
+    SlabCsr m, const CgScalars* __restrict__ s, int iteration, int fma_form, const double* __restrict__ rvec, const double* __restrict__ p_in,
+    double* __restrict__ p_out, double* __restrict__ y, double alpha, int gi_lo, int gi_hi, int col_tiles, int total_blocks, int run, int reverse,
+    double* __restrict__ dot_partials, const unsigned char* __restrict__ block_map, SymPlanes sp) {
+    constexpr int kRowDoubles = kLdsTileCols + 2;
+    __shared__ double lds[kRows * kRowDoubles];  // one p' row copy per grid row of the block
+    if (s->iterations != iteration || s->converged != 0) return;
+    const double beta = s->beta;
+    const int block = rowlds_tile_of_block((int)blockIdx.x, run, total_blocks, reverse);
+    if (block < 0) return;
+    const int row_block = block / col_tiles;
+    const int col_tile = block - row_block * col_tiles;
+    const int li0 = gi_lo + row_block * kRows;
+    const int j0 = col_tile * kLdsTileCols, lane = (int)threadIdx.x;
+    const int n = m.grid_size;
+    const int fast = (int)block_map[block];  // a vector load, requested in front of the r / p loads and tested behind them (rowlds_tile_class)
+    // r has no halo rows and this launch runs on slabs without neighbours only: rows outside [0, rows) are not requested
+    const int rows = m.n_local / n;
+    const bool in0 = j0 + lane < n, in1 = j0 + lane + 64 < n;
+    double rv[kRows + 2][2], pv[kRows + 2][2];  // rows li0 - 1 .. li0 + kRows, the lane's two columns
+    double ro[kRows], po[kRows];                // lane 0: the W neighbour left of the tile; lane 63: the E neighbour right of it
+#pragma unroll
+    for (int r = 0; r < kRows + 2; ++r) {
+        const int li = li0 - 1 + r;
+        rv[r][0] = rv[r][1] = pv[r][0] = pv[r][1] = 0.0;
+        if (li >= 0 && li < rows) {
+            const double* __restrict__ rr = rvec + ((long long)li * n + j0);
+            const double* __restrict__ pr = p_in + ((long long)li * n + j0);
+            if (in0) rv[r][0] = rr[lane], pv[r][0] = pr[lane];
+            if (in1) rv[r][1] = rr[lane + 64], pv[r][1] = pr[lane + 64];
         }
     }
+    // one load per vector and row from a per-lane address (lane 0: column j0 - 1, lane 63: column j0 + 128): a vector load like the
+    // rest, returned in order behind them (two branches on the lane number became scalar loads, each waited for on its own)
+    const bool outer = (lane == 0 && j0 > 0) || (lane == 63 && j0 + kLdsTileCols < n);
+    const int outer_col = lane == 0 ? -1 : kLdsTileCols + lane - 63;
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+        const int li = li0 + r;
+        ro[r] = po[r] = 0.0;
+        if (li < rows && outer) {
+            const long long at = (long long)li * n + j0 + outer_col;
+            ro[r] = rvec[at], po[r] = p_in[at];
+        }
+    }
+    if (__builtin_amdgcn_readfirstlane(fast) != 0) {
+        // p' on every row held (columns past n keep 0: what an absent neighbour contributes), then the block kernel's fast path on it
+#pragma unroll
+        for (int r = 0; r < kRows + 2; ++r) {
+            pv[r][0] = in0 ? direction(rv[r][0], beta, pv[r][0], fma_form) : 0.0;
+            pv[r][1] = in1 ? direction(rv[r][1], beta, pv[r][1], fma_form) : 0.0;
+        }
+#pragma unroll
+        for (int r = 0; r < kRows; ++r) {
+            po[r] = outer ? direction(ro[r], beta, po[r], fma_form) : 0.0;
+            double* __restrict__ out = p_out + ((long long)(li0 + r) * n + j0);
+            if (in0) out[lane] = pv[r + 1][0];  // plain: the next launch's loads (and the flush) re-use these lines
+            if (in1) out[lane + 64] = pv[r + 1][1];
+            lds[r * kRowDoubles + 1 + lane] = pv[r + 1][0];
+            lds[r * kRowDoubles + 65 + lane] = pv[r + 1][1];
+        }
+        wave_lds_sync();
+#pragma unroll
+        for (int r = 0; r < kRows; ++r) {
+            const int li = li0 + r;
+            double xw[2], xe[2];
+            tile_west_east(lds + r * kRowDoubles, lane, j0, n, po[r], po[r], xw, xe);
+            double dot = 0.0;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int j = j0 + lane + 64 * h;
+                if (j < n) {
+                    const double xc = pv[r + 1][h], xn = pv[r][h], xs = pv[r + 2][h];
+                    const double sum = stencil5_row(j, n, sp.w, xw[h], sp.c, xc, sp.e, xe[h], sp.n, xn, sp.s5, xs);
+                    dot = fma(xc, sum, dot);
+                    __builtin_nontemporal_store(alpha * sum, y + ((long long)li * n + j));
+                }
+            }
+            dot = wave_sum(dot);
+            if (lane == 0) dot_partials[(li - gi_lo) * col_tiles + col_tile] = dot;
+        }
+    } else {
+        const int held = gi_hi - li0 < kRows ? gi_hi - li0 : kRows;
+#pragma unroll
+        for (int r = 0; r < kRows; ++r) {
+            if (r < held) {
+                double* __restrict__ out = p_out + ((long long)(li0 + r) * n + j0);
+                if (in0) out[lane] = direction(rv[r + 1][0], beta, pv[r + 1][0], fma_form);
+                if (in1) out[lane + 64] = direction(rv[r + 1][1], beta, pv[r + 1][1], fma_form);
+            }
+        }
+    }
+}
+
+// A p' and its partials on the block tiles the launch above left out (`list`: the range's blocks whose map byte is 0, one workgroup
+// each): the block kernel's own path for such a block, on p' in memory. Same scalar test as the launch it follows.
+__global__ __launch_bounds__(64) void stencil5_block_list_kernel(SlabCsr m, const CgScalars* __restrict__ s, int iteration,
+                                                                 const double* __restrict__ x, double* __restrict__ y, double alpha, int gi_lo,
+                                                                 int gi_hi, int gfirst, int col_tiles, int block_rows, const int* __restrict__ list,
+                                                                 double* __restrict__ dot_partials, SymPlanes sp) {
+    __shared__ double lds[5 * kLdsTileCols + kLdsTileCols + 2];
+    if (s->iterations != iteration || s->converged != 0) return;
+    const int block = list[blockIdx.x];
+    const int row_block = block / col_tiles;
+    const int col_tile = block - row_block * col_tiles;
+    const int li0 = gi_lo + row_block * block_rows;
+    rowlds_block_slow_rows(m, x, y, alpha, gi_lo, gi_hi, gfirst, col_tiles, li0, block_rows, col_tile, col_tile * kLdsTileCols, (int)threadIdx.x, 0, lds, dot_partials, sp);
 }
 
 // The block map of one launch range [gi_lo, gi_hi) (stencil5_rowlds_block_kernel): one thread per block tile.
@@ -1280,6 +1414,28 @@ int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& p, const double* 
 #undef SPMV_AMD_LAUNCH_ROWS
     }
     return dot ? p.partials : 0;
+}
+
+int launch_stencil5_direction_spmv(const SlabCsr& m, const Stencil5Plan& p, const DirectionSpmv& d, double* y, double alpha,
+                                   double* d_dot_partials, bool reverse, hipStream_t stream, const SymPlanes& sp) {
+    const int blocks = rowlds_block_tiles(p);
+    if (blocks <= 0 || p.block_map == nullptr || d_dot_partials == nullptr || sp.cls == nullptr || (d.slow_count > 0 && d.slow_list == nullptr)) {
+        fprintf(stderr, "[spmv] the direction update inside the SpMV exists for row-lds plans with a block map only\n");
+        exit(EXIT_FAILURE);
+    }
+    const dim3 grid((unsigned)xcd_padded_grid(blocks, p.xcd_run));
+    const int gfirst = m.row_offset / m.grid_size;
+#define SPMV_AMD_LAUNCH_DIRECTION_BLOCK(ROWS)                                                                                          \
+    hipLaunchKernelGGL((stencil5_direction_block_kernel<ROWS>), grid, dim3(64), 0, stream, m, d.s, d.iteration, d.fma_form ? 1 : 0, d.r, \
+                       d.p_in, d.p_out, y, alpha, p.gi_lo, p.gi_hi, p.row_blocks, blocks, p.xcd_run, reverse ? 1 : 0, d_dot_partials,    \
+                       p.block_map, sp)
+    if (p.block_rows == 4) SPMV_AMD_LAUNCH_DIRECTION_BLOCK(4);
+    else SPMV_AMD_LAUNCH_DIRECTION_BLOCK(8);
+#undef SPMV_AMD_LAUNCH_DIRECTION_BLOCK
+    if (d.slow_count > 0)
+        hipLaunchKernelGGL(stencil5_block_list_kernel, dim3((unsigned)d.slow_count), dim3(64), 0, stream, m, d.s, d.iteration, d.p_out, y, alpha,
+                           p.gi_lo, p.gi_hi, gfirst, p.row_blocks, p.block_rows, d.slow_list, d_dot_partials, sp);
+    return p.partials;
 }
 
 int launch_stencil5_cheb_step(const SlabCsr& m, const Stencil5Plan& p, const double* z, const ChebStep& step, double* d_dot_partials,

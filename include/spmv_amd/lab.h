@@ -40,7 +40,10 @@ SpmvAmdCgSlab* spmv_amd_cg_slab_create_stencil5_as(int n, int as_rank, int as_wo
  * "csr_coefficients"; results are bit-identical), "block_rows" 0 / 4 / 8 (grid rows per block tile of the in-loop SpMV, the
  * product's SPMV_AMD_ROWLDS_BLOCK_ROWS; 0 = the one-row kernel; the block maps are rebuilt; results are bit-identical) and
  * "spmv_with_dot" 0/1 (1 = spmv_amd_cg_slab_spmv runs the SpMV in its in-loop form, p.Ap partials and their sum included, so that
- * it takes the kernel the loop takes). Returns 0, or -1 for an unknown name or value. */
+ * it takes the kernel the loop takes), and "fused_direction" 0 / 1 / 2 (the product's SPMV_AMD_FUSED_DIRECTION: 0 = the direction
+ * update is a launch of its own, 1 = it rides in the next block SpMV's launch where the slab is eligible -- one rank, ring > 1, no
+ * detailed timers, a block map whose slow blocks are at most 1/16 of its blocks --, 2 = the same without the 1/16 cap;
+ * spmv_amd_cg_slab_loop_shape says which ran; results are bit-identical). Returns 0, or -1 for an unknown name or value. */
 int spmv_amd_cg_slab_set_option(SpmvAmdCgSlab* s, const char* name, long long value);
 
 /* The tile class map of a slab in the symmetric form as creation wrote it (spmv_amd_cg_slab_uniform_tiles): one byte per row-lds
@@ -53,6 +56,24 @@ long long spmv_amd_cg_slab_tile_classes(const SpmvAmdCgSlab* s, unsigned char* o
  * column tile], 1 = every tile of the block is uniform and the block holds block_rows rows (the fast path), 0 = the block is
  * evaluated row by row. Copies min(count, cap) bytes to `out` (host) and returns count; 0 = the range has no map. */
 long long spmv_amd_cg_slab_block_map(const SpmvAmdCgSlab* s, int which, unsigned char* out, long long cap);
+
+/* The slow blocks of a launch range (which: as above): the indices of the block tiles whose map byte is 0, ascending -- what the
+ * launch behind the direction update inside the block SpMV evaluates, one workgroup each. Copies min(count, cap) ints to `out`
+ * (host) and returns count. */
+long long spmv_amd_cg_slab_slow_blocks(const SpmvAmdCgSlab* s, int which, int* out, long long cap);
+
+/* What the last spmv_amd_cg_slab_spmv in its in-loop form ("spmv_with_dot" 1) left beside y on a slab without neighbours: *pAp = the
+ * reduced x . (A x), and the whole-slab launch's partials, one per 128 x 1 tile (min(count, cap) doubles to `partials`; returns count). */
+int spmv_amd_cg_slab_spmv_dot(const SpmvAmdCgSlab* s, double* pAp, double* partials, int cap);
+
+/* The direction update inside the block SpMV alone, once, on the caller's r and p_in (host, n_local doubles each): the fused launch,
+ * the launch over the slow blocks and the reduction, as an iteration >= 1 of that loop shape enqueues them, with beta as the
+ * device scalar. iteration_matches = 0: the launches are handed another iteration number than the scalars hold; converged != 0: the
+ * scalars say the solve is over -- in both cases every launch must return on the scalars. p_out, Ap (n_local doubles), partials
+ * (up to cap doubles) and *pAp are NaN wherever a launch did not write. Returns the number of partials the launches write, or -1 on
+ * a slab that cannot take the launch (neighbours, ring 1, no block map). */
+int spmv_amd_cg_slab_direction_spmv(SpmvAmdCgSlab* s, const double* r, const double* p_in, double beta, int iteration_matches, int converged,
+                                    double* p_out, double* Ap, double* pAp, double* partials, int cap);
 
 /* The device scalars of one preconditioned solve (csrc/pcg.hip keeps the same record on the device). */
 typedef struct SpmvAmdPcgScalars {
