@@ -1,10 +1,12 @@
 // cg_solver -- counterpart of reference src/main/cg_solver.cu: b = 1, x0 = 0, 3 warm-up solves,
 // then 10 timed solves from x0 = 0 each.
 //   cg_solver <matrix.mtx | --stencil=N> [--mode=<m1,..>] [--host|--device] [--tol=1e-6]
-//             [--maxiter=1000] [--timers] [--json=<file>] [--csv=<file>] [--precond=none|jacobi|chebyshev[:K]]
+//             [--maxiter=1000] [--timers] [--json=<file>] [--csv=<file>] [--precond=none|jacobi|chebyshev[:K]|multigrid[:NU]]
 // --precond runs the preconditioned solver (spmv_amd_pcg_solve_device, device only); its JSON / CSV carry the mode string
 // <operator>+<kind>. Without it the binary takes cg_solve_device / cg_solve as before. chebyshev = the polynomial preconditioner
 // of degree 4, chebyshev:K of degree K (0..32), both on the automatic interval; the mode string is <operator>+chebyshev<K>.
+// multigrid = the aggregation multigrid V(1, 1) cycle (stencil5-csr only), multigrid:NU the V(NU, NU) cycle (0..8); the mode string is
+// <operator>+multigrid<NU>.
 // (The reference's own main, unmodified, also builds against this library: INTEGRATION.md. Unlike
 // it, this binary restarts every timed solve from x0 = 0 instead of from the warm-up's solution.)
 #include <algorithm>
@@ -70,6 +72,7 @@ int main(int argc, char** argv) {
         return 1;
     }
     int cheb_degree = -1;  // >= 0: --precond=chebyshev[:K]
+    int mg_degree = -1;    // >= 0: --precond=multigrid[:NU]
     if (precond && !strncmp(precond, "chebyshev", 9) && (precond[9] == '\0' || precond[9] == ':')) {
         char* end = nullptr;
         const long k = precond[9] == ':' ? strtol(precond + 10, &end, 10) : 4;
@@ -78,6 +81,14 @@ int main(int argc, char** argv) {
             return 1;
         }
         cheb_degree = (int)k;
+    } else if (precond && !strncmp(precond, "multigrid", 9) && (precond[9] == '\0' || precond[9] == ':')) {
+        char* end = nullptr;
+        const long k = precond[9] == ':' ? strtol(precond + 10, &end, 10) : 1;
+        if (precond[9] == ':' && (end == precond + 10 || *end != '\0' || k < 0 || k > 8)) {
+            fprintf(stderr, "Error: --precond=multigrid:NU takes a smoother degree NU of 0..8, not '%s'\n", precond + 10);
+            return 1;
+        }
+        mg_degree = (int)k;
     } else if (precond && strcmp(precond, "none") != 0 && strcmp(precond, "jacobi") != 0) {
         fprintf(stderr, "Error: unknown preconditioner '%s' (none, jacobi)\n", precond);
         return 1;
@@ -118,14 +129,17 @@ int main(int argc, char** argv) {
         CGStats st;
         if (precond) {
             int bad_row = -1;
-            SpmvAmdPrecond* pm = cheb_degree >= 0 ? spmv_amd_precond_create_chebyshev(op, cheb_degree, 0.0, 0.0, &bad_row)
-                                                  : spmv_amd_precond_create(op, precond, &bad_row);
+            SpmvAmdPrecond* pm = mg_degree >= 0     ? spmv_amd_precond_create_multigrid(op, mg_degree, 0, &bad_row)
+                                 : cheb_degree >= 0 ? spmv_amd_precond_create_chebyshev(op, cheb_degree, 0.0, 0.0, &bad_row)
+                                                    : spmv_amd_precond_create(op, precond, &bad_row);
             if (pm == nullptr) {
                 fprintf(stderr, "Failed to create the '%s' preconditioner (row %d)\n", precond, bad_row);
                 op->free();
                 continue;
             }
-            const std::string kind = cheb_degree >= 0 ? "chebyshev" + std::to_string(cheb_degree) : std::string(precond);
+            const std::string kind = mg_degree >= 0     ? "multigrid" + std::to_string(mg_degree)
+                                     : cheb_degree >= 0 ? "chebyshev" + std::to_string(cheb_degree)
+                                                        : std::string(precond);
             const std::string tag = m + "+" + kind;
             printf("Preconditioner: %s\nWarmup (3 runs)...\n", kind.c_str());
             BenchmarkStats bs;

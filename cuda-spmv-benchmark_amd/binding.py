@@ -87,6 +87,12 @@ class PcgStageArgs(C.Structure):
                 ("hist", C.c_void_p), ("hist_cap", C.c_int)]
 
 
+class MgStageArgs(C.Structure):
+    """SpmvAmdMgStageArgs (include/spmv_amd/lab.h): device pointers of one spmv_amd_mg_stage call; n = the fine grid."""
+    _fields_ = [("n", C.c_int), ("row_ptr", C.c_void_p), ("col_idx", C.c_void_p), ("values", C.c_void_p), ("z", C.c_void_p),
+                ("r", C.c_void_p), ("coarse", C.c_void_p), ("out_row_ptr", C.c_void_p), ("out_col_idx", C.c_void_p), ("out_values", C.c_void_p)]
+
+
 class MultiColumn(C.Structure):
     """SpmvAmdMultiColumn (include/spmv_amd/lab.h): the per-column state of a batched CG solve."""
     _fields_ = [("rr_old", C.c_double), ("pAp", C.c_double), ("alpha", C.c_double), ("beta", C.c_double), ("b_norm", C.c_double),
@@ -132,11 +138,13 @@ DECLARED_SYMBOLS = [
     "spmv_amd_precond_create", "spmv_amd_precond_create_from_diagonal", "spmv_amd_precond_destroy", "spmv_amd_precond_kind",
     "spmv_amd_precond_inverse_diagonal", "spmv_amd_pcg_solve_device", "spmv_amd_pcg_last_history", "spmv_amd_pcg_release_workspace",
     "spmv_amd_precond_create_chebyshev", "spmv_amd_precond_chebyshev_info", "spmv_amd_precond_apply_device",
+    "spmv_amd_precond_create_multigrid", "spmv_amd_precond_multigrid_info",
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
 LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_cg_slab_block_map", "spmv_amd_cg_slab_slow_blocks",
                     "spmv_amd_cg_slab_direction_spmv", "spmv_amd_cg_slab_spmv_dot", "spmv_amd_pcg_stage",
-                    "spmv_amd_pcg_last_step_launches", "spmv_amd_cg_multi_stage"]
+                    "spmv_amd_pcg_last_step_launches", "spmv_amd_cg_multi_stage",
+                    "spmv_amd_pcg_last_multigrid_cycles", "spmv_amd_precond_multigrid_level_csr", "spmv_amd_mg_stage"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
 DECLARED_CXX_SYMBOLS = [
     "SPMV_CSR", "SPMV_STENCIL5_CSR", "SPMV_STENCIL_HALO_MGPU", "SPMV_ELLPACK", "SPMV_STENCIL5_ELLPACK",
@@ -244,6 +252,12 @@ def lib():
         L.spmv_amd_pcg_last_step_launches.restype = C.c_int
         L.spmv_amd_cg_multi_stage.argtypes = [C.c_char_p, C.c_int, C.POINTER(CgMultiStageArgs)]
         L.spmv_amd_cg_multi_stage.restype = C.c_int
+        L.spmv_amd_pcg_last_multigrid_cycles.argtypes = []
+        L.spmv_amd_pcg_last_multigrid_cycles.restype = C.c_int
+        L.spmv_amd_precond_multigrid_level_csr.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.spmv_amd_precond_multigrid_level_csr.restype = C.c_int
+        L.spmv_amd_mg_stage.argtypes = [C.c_char_p, C.POINTER(MgStageArgs)]
+        L.spmv_amd_mg_stage.restype = C.c_int
     L.spmv_amd_cg_slab_create.restype = C.c_void_p
     L.spmv_amd_cg_slab_create.argtypes = [C.POINTER(MatrixData), C.c_void_p]
     L.spmv_amd_cg_slab_create_stencil5.restype = C.c_void_p
@@ -622,6 +636,9 @@ def _pcg_lib():
         L.spmv_amd_precond_chebyshev_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                       C.c_void_p, C.c_int]
         L.spmv_amd_precond_apply_device.argtypes = [C.POINTER(SpmvOperator), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        L.spmv_amd_precond_create_multigrid.argtypes = [C.POINTER(SpmvOperator), C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.spmv_amd_precond_create_multigrid.restype = C.c_void_p
+        L.spmv_amd_precond_multigrid_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int]
         L._pcg_sigs = True
     return L
 
@@ -668,9 +685,41 @@ class Precond:
             raise err
         return cls(_handle=h, _n=op.rows)
 
+    @classmethod
+    def multigrid(cls, op, smoother_degree=1, max_levels=0):
+        """spmv_amd_precond_create_multigrid (stencil5-csr only); max_levels 0 = automatic."""
+        bad = C.c_int(-2)
+        h = _pcg_lib().spmv_amd_precond_create_multigrid(op.op, smoother_degree, max_levels, C.byref(bad))
+        if not h:
+            err = ValueError(f"precond_create_multigrid({op.name}, {smoother_degree}, {max_levels}) refused, bad_row = {bad.value}")
+            err.bad_row = bad.value
+            raise err
+        return cls(_handle=h, _n=op.rows)
+
     @property
     def kind(self):
         return _pcg_lib().spmv_amd_precond_kind(self.handle).decode()
+
+    def multigrid_info(self):
+        """smoother degree, the levels' grids and their lambda_max; None for another kind."""
+        levels, degree = C.c_int(0), C.c_int(-1)
+        grids, lmax = np.zeros(32, dtype=np.int32), np.zeros(32, dtype=np.float64)
+        count = _pcg_lib().spmv_amd_precond_multigrid_info(self.handle, C.byref(levels), C.byref(degree), grids.ctypes.data, lmax.ctypes.data, 32)
+        if count == 0:
+            return None
+        return degree.value, [int(g) for g in grids[:count]], lmax[:count].copy()
+
+    def multigrid_level(self, level):
+        """row_ptr, col_idx, values and dinv of one level (LAB build only; include/spmv_amd/lab.h)."""
+        if not is_lab():
+            raise RuntimeError("the level matrices are read through the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        n = self.multigrid_info()[1][level]
+        rows, nnz = n * n, 5 * n * n - 4 * n
+        rp, ci = np.zeros(rows + 1, dtype=np.int32), np.zeros(nnz, dtype=np.int32)
+        va, dinv = np.zeros(nnz), np.zeros(rows)
+        if lib().spmv_amd_precond_multigrid_level_csr(self.handle, level, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, dinv.ctypes.data) != 0:
+            raise RuntimeError("precond_multigrid_level_csr refused")
+        return rp, ci, va, dinv
 
     def chebyshev_info(self):
         """degree, lambda_min, lambda_max and the coefficients [c0, h_1, g_1, ...]; None for another kind."""
@@ -713,6 +762,13 @@ def pcg_solve_device(op, host_matrix, precond, b, x0, max_iters=1000, tol=1e-6, 
     hist = np.zeros(max_iters + 1, dtype=np.float64)
     count = L.spmv_amd_pcg_last_history(hist.ctypes.data, len(hist))
     return x, hist[:count].copy(), st
+
+
+def mg_stage(stage, args):
+    """spmv_amd_mg_stage (LAB build only; include/spmv_amd/lab.h): one launch of the multigrid cycle on the caller's device data."""
+    if not is_lab():
+        raise RuntimeError("the multigrid stages exist in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+    return lib().spmv_amd_mg_stage(stage if stage is None else stage.encode(), args)
 
 
 def pcg_stage(stage, kind, args, scalars=None):

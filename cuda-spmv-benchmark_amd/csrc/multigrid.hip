@@ -1,0 +1,598 @@
+// multigrid.hip -- kind "multigrid" of the preconditioned solver (pcg.hip): a symmetric V(nu, nu) cycle on a hierarchy of 5-point
+// stencils made by 2 x 2 aggregation of the stencil5-csr operator's grid (include/spmv_amd/api.h states the
+// algebra down to the order of every sum).
+//
+// Levels: level 0 is the operator's own verified CSR on an n0 x n0 grid; level l+1 has the grid ceil(n_l / 2), aggregate (I, J) =
+// the fine points (2I + a, 2J + b), a, b in {0, 1}, that exist; coarsening stops at the first grid of at most 8 (or at max_levels).
+// A_c = P^T A P with P piecewise constant is again a complete 5-point CSR (coarsen_kernel), so every level runs the library's own
+// stencil kernels through a Stencil5Plan of its own: launch_stencil5_cheb_step where the plan is row-lds, launch_stencil5_spmv and
+// pcg.hip's streaming step elsewhere. Per level: dinv by pcg.hip's diagonal pass, lambda_max by its Gershgorin kernel, the smoother =
+// section 14's Chebyshev application of degree nu on [lambda_max / 4, lambda_max]; the coarsest level is solved by degree 8 on
+// [lambda_max / 30, lambda_max] from a zero guess.
+//
+// Cycle on level l (input r, output z):
+//   pre-smooth   term 0 and nu steps of the application
+//   restrict     r_c[I, J] = ((t00 + t01) + t10) + t11 over the members that exist, t = fma(-1.0, (A z)_i, r_i): ONE launch
+//                (residual_restrict_kernel), A z and r - A z never stored
+//   recurse      e_c = cycle(l + 1, r_c)
+//   correct      z = fma(2.0, e_c[agg(i)], z)   (the Galerkin operator of 2 x 2 aggregates is twice the re-discretised one)
+//   post-smooth  nu + 1 step-form updates from the guess z: the first with (g, h) = (c0, 0.0), then steps 1 .. nu
+// Pre- and post-smoother are the same symmetric polynomial: M^-1 is symmetric.
+#include <limits.h>
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <vector>
+
+#include "precond.hpp"
+#include "stencil_geometry.hpp"
+#include "stencil_row_device.hpp"
+#include "stream_device.hpp"
+#ifdef SPMV_AMD_LAB
+#include "spmv_amd/lab.h"
+#endif
+
+using namespace spmv_amd;
+
+namespace {
+
+constexpr hipStream_t kStream = nullptr;  // default stream, shared with the operators and pcg.hip
+constexpr int kWave = 64;
+constexpr int kTileCols = 128;      // fine columns of one residual-restriction tile: lane l owns aggregate column l of the tile
+constexpr int kCoarsestGrid = 8;    // coarsening stops at the first grid of at most this
+constexpr int kCoarsestDegree = 8;  // the coarsest level's Chebyshev degree
+constexpr int kMaxSmoother = 8;
+constexpr int kMaxLevels = 32;
+
+bool fail(const char* what) {
+    fprintf(stderr, "[PCG] multigrid: %s\n", what);
+    return false;
+}
+
+// ---- coarsening: one thread per coarse row; set-up work ----
+// Every coarse entry is a sequential sum from 0.0 with plain additions: the members are walked in the order (0,0), (0,1), (1,0), (1,1),
+// each member's entries in CSR order, and an entry is added to the coarse entry of the aggregate its column lies in. N_c thus sums
+// N(2I, 2J + b) over b ascending, W_c sums W(2I + a, 2J) over a ascending, E_c and S_c likewise, C_c everything that stays inside.
+__global__ __launch_bounds__(256) void coarsen_kernel(SlabCsr fine, int n, int nc, int* __restrict__ row_ptr, int* __restrict__ col_idx,
+                                                      double* __restrict__ values) {
+    const int row = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (row >= nc * nc) return;
+    const int I = row / nc, J = row - I * nc;
+    double vn = 0.0, vw = 0.0, vc = 0.0, ve = 0.0, vs = 0.0;
+    for (int a = 0; a < 2; ++a) {
+        for (int b = 0; b < 2; ++b) {
+            const int i = 2 * I + a, j = 2 * J + b;
+            if (i >= n || j >= n) continue;
+            const int fr = i * n + j;
+            for (int k = fine.row_ptr[fr]; k < fine.row_ptr[fr + 1]; ++k) {
+                const int c = fine.col_idx[k];
+                const int ci = c / n, cj = c - ci * n;
+                const int CI = ci >> 1, CJ = cj >> 1;
+                const double v = fine.values[k];
+                if (CI == I && CJ == J) vc = vc + v;
+                else if (CI < I) vn = vn + v;
+                else if (CI > I) vs = vs + v;
+                else if (CJ < J) vw = vw + v;
+                else ve = ve + v;
+            }
+        }
+    }
+    int at = (int)stencil_row_start(I, J, nc);
+    row_ptr[row] = at;
+    if (I > 0) col_idx[at] = row - nc, values[at] = vn, ++at;
+    if (J > 0) col_idx[at] = row - 1, values[at] = vw, ++at;
+    col_idx[at] = row, values[at] = vc, ++at;
+    if (J < nc - 1) col_idx[at] = row + 1, values[at] = ve, ++at;
+    if (I < nc - 1) col_idx[at] = row + nc, values[at] = vs, ++at;
+    if (row == nc * nc - 1) row_ptr[nc * nc] = at;
+}
+
+// ---- residual + restriction in one launch ----
+// One wave takes 128 fine columns x the 2 fine grid rows of coarse grid row I: 64 coarse values, lane l owns aggregate column l of the
+// tile (fine columns ja = j0 + 2 l and jb = ja + 1). A pair of rows inside the grid (2I >= 1, 2I + 1 <= n - 2) takes the fast path:
+//   * the two rows' coefficients -- 640 consecutive CSR values each, 40 B/row -- by ten coalesced nontemporal 8-byte loads per lane
+//     and row into a wave-private LDS strip (the row-lds kernel's layout: row j of the tile at strip position 5 (j - j0), [N,W,C,E,S];
+//     column 0 holds [N,C,E,S] at positions 1..4), addresses clamped at the array's ends, where the slots feed no row;
+//   * z on the four grid rows 2I-1 .. 2I+2 and r on the two rows, a 16-byte pair per lane and row where the pair is 16-byte aligned
+//     (an odd n leaves the odd grid rows 8-byte aligned only: two 8-byte loads there) -- every load is issued before the first use;
+//   * the W neighbour of ja and the E neighbour of jb from the adjacent lanes (a cross-lane move); only lane 0 and lane 63 load an outer
+//     column;
+//   * the row sums through stencil5_row's chains, t = fma(-1.0, sum, r), r_c = ((t00 + t01) + t10) + t11 over the members that exist;
+//   * one plain 8-byte store per lane: the next level reads it at once.
+// Unique bytes per fine row: 40 + 8 + 8 + 2. A pair that holds grid row 0 or n-1, and a lone last grid row, go one thread per
+// aggregate without the strip (residual_off_tile): grid rows 0 and n-1 walk the CSR in loop order (sum = 0 ; sum = fma(v[k],
+// z[col[k]], sum), ascending k), their interior partner takes its chain -- the bits stencil5-csr's SpMV gives for each row.
+// Tiles are dealt to the XCDs in runs (xcd_run_tile); the launcher pads the grid.
+
+// z or r at (row i, columns ja, ja + 1) of an n x n grid; has_b: column ja + 1 exists
+template <bool kOnce>
+__device__ __forceinline__ d2 load_pair(const double* __restrict__ v, long long at, bool has_b) {
+    d2 out;
+    if (has_b && (at & 1) == 0) {
+        out = kOnce ? __builtin_nontemporal_load(reinterpret_cast<const d2*>(v + at)) : *reinterpret_cast<const d2*>(v + at);
+    } else {
+        out.x = kOnce ? __builtin_nontemporal_load(v + at) : v[at];
+        out.y = 0.0;
+        if (has_b) out.y = kOnce ? __builtin_nontemporal_load(v + at + 1) : v[at + 1];
+    }
+    return out;
+}
+
+// t = fma(-1.0, sum, r) of row (i, j) for the row pairs off the fast path, with the sum stencil5-csr's SpMV gives for that row: grid
+// rows 0 and n-1 walk the CSR in loop order, an interior grid row (the partner of grid row 0 or n-1 in its pair) takes its chain on the
+// row's own CSR entries ([N,W,C,E,S]; column 0: [N,C,E,S]; column n-1: [N,W,C,S]).
+__device__ __forceinline__ double residual_off_tile(const SlabCsr& m, const double* __restrict__ z, const double* __restrict__ r, int i, int j) {
+    const int n = m.grid_size, row = i * n + j;
+    double sum;
+    if (i > 0 && i < n - 1) {
+        const double* __restrict__ v = m.values + m.row_ptr[row];
+        const double* __restrict__ zl = z + row;
+        if (j > 0 && j < n - 1) sum = stencil5_row(j, n, v[1], zl[-1], v[2], zl[0], v[3], zl[1], v[0], zl[-n], v[4], zl[n]);
+        else if (j == 0) sum = stencil5_row(j, n, 0.0, 0.0, v[1], zl[0], v[2], zl[1], v[0], zl[-n], v[3], zl[n]);
+        else sum = stencil5_row(j, n, v[1], zl[-1], v[2], zl[0], 0.0, 0.0, v[0], zl[-n], v[3], zl[n]);
+    } else {
+        sum = 0.0;
+        for (int k = m.row_ptr[row]; k < m.row_ptr[row + 1]; ++k) sum = fma(m.values[k], z[m.col_idx[k]], sum);
+    }
+    return fma(-1.0, sum, r[row]);
+}
+
+// the row sum at column j from the strip slots of that row (v = strip + 5 (j - j0)), through stencil5_row's chains
+__device__ __forceinline__ double strip_row(const double* __restrict__ v, int j, int n, double xw, double xc, double xe, double xn, double xs) {
+    if (j > 0 && j < n - 1) return stencil5_row(j, n, v[1], xw, v[2], xc, v[3], xe, v[0], xn, v[4], xs);  // [N,W,C,E,S]
+    if (j == 0) return stencil5_row(j, n, 0.0, xw, v[2], xc, v[3], xe, v[1], xn, v[4], xs);                // [N,C,E,S] at 1..4
+    return stencil5_row(j, n, v[1], xw, v[2], xc, 0.0, xe, v[0], xn, v[3], xs);                            // [N,W,C,S]
+}
+
+__global__ __launch_bounds__(kWave) void residual_restrict_kernel(SlabCsr m, const double* __restrict__ z, const double* __restrict__ r,
+                                                                  double* __restrict__ rc, int nc, int col_tiles, int total_tiles, int run) {
+    __shared__ double strip[2][5 * kTileCols];
+    const int tile = xcd_run_tile<int>((int)blockIdx.x, run);
+    if (tile >= total_tiles) return;
+    const int n = m.grid_size;
+    const int I = tile / col_tiles;
+    const int j0 = (tile - I * col_tiles) * kTileCols;
+    const int lane = (int)threadIdx.x;
+    const int ja = j0 + 2 * lane, jb = ja + 1;
+    const int i0 = 2 * I, i1 = i0 + 1;
+    const bool has_a = ja < n, has_b = jb < n;
+    if (i0 >= 1 && i1 <= n - 2) {
+        // every load of the tile, then the first use
+        double c[2][10];
+        const long long hi = m.nnz_local - 1;
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const long long e = stencil_gridrow_base(i0 + a, n) + 5LL * j0 - 1 + lane;
+#pragma unroll
+            for (int k = 0; k < 10; ++k) {
+                long long idx = e + 64 * k;
+                idx = idx < 0 ? 0 : (idx > hi ? hi : idx);
+                c[a][k] = __builtin_nontemporal_load(m.values + idx);
+            }
+        }
+        d2 zv[4], rv[2];
+        double west[2] = {0.0, 0.0}, east[2] = {0.0, 0.0};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) zv[q] = d2{0.0, 0.0};
+        rv[0] = rv[1] = d2{0.0, 0.0};
+        if (has_a) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) zv[q] = load_pair<false>(z, (long long)(i0 - 1 + q) * n + ja, has_b);
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                rv[a] = load_pair<true>(r, (long long)(i0 + a) * n + ja, has_b);
+                if (lane == 0 && ja > 0) west[a] = z[(long long)(i0 + a) * n + ja - 1];
+                if (lane == 63 && jb + 1 < n) east[a] = z[(long long)(i0 + a) * n + jb + 1];
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int k = 0; k < 10; ++k) strip[a][64 * k + lane] = c[a][k];
+        wave_lds_sync();
+        double acc = 0.0;
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const d2 zc = zv[1 + a], zn = zv[a], zs = zv[2 + a];
+            const double from_west = __shfl_up(zc.y, 1), from_east = __shfl_down(zc.x, 1);
+            const double xw_a = lane > 0 ? from_west : west[a];
+            const double xe_b = lane < 63 ? from_east : east[a];
+            if (has_a) {
+                const double* __restrict__ v = strip[a] + 5 * (2 * lane);
+                const double ta = fma(-1.0, strip_row(v, ja, n, xw_a, zc.x, zc.y, zn.x, zs.x), rv[a].x);
+                acc = a == 0 ? ta : acc + ta;
+                if (has_b) {
+                    const double tb = fma(-1.0, strip_row(v + 5, jb, n, zc.x, zc.y, xe_b, zn.y, zs.y), rv[a].y);
+                    acc = acc + tb;
+                }
+            }
+        }
+        if (has_a) rc[(long long)I * nc + (ja >> 1)] = acc;
+    } else if (has_a) {
+        // a pair with grid row 0 or n-1 in it, a lone last grid row
+        double acc = residual_off_tile(m, z, r, i0, ja);
+        if (has_b) acc = acc + residual_off_tile(m, z, r, i0, jb);
+        if (i1 < n) {
+            acc = acc + residual_off_tile(m, z, r, i1, ja);
+            if (has_b) acc = acc + residual_off_tile(m, z, r, i1, jb);
+        }
+        rc[(long long)I * nc + (ja >> 1)] = acc;
+    }
+}
+
+// ---- prolongation + correction: z = fma(2.0, e_c[agg(i)], z), z in place; one-wave workgroups, a 16-byte pair per lane ----
+__device__ __forceinline__ double coarse_at(const double* __restrict__ ec, size_t flat, int n, int nc) {
+    const int i = (int)(flat / (size_t)n), j = (int)(flat - (size_t)i * n);
+    return ec[(size_t)(i >> 1) * nc + (j >> 1)];
+}
+
+__global__ __launch_bounds__(kWave) void prolong_correct_kernel(size_t rows, int n, int nc, const double* __restrict__ ec, double* __restrict__ z) {
+    const size_t i = (size_t)blockIdx.x * kWave + threadIdx.x;
+    if (i < (rows >> 1)) {
+        d2 zv = reinterpret_cast<const d2*>(z)[i];
+        zv.x = fma(2.0, coarse_at(ec, 2 * i, n, nc), zv.x);
+        zv.y = fma(2.0, coarse_at(ec, 2 * i + 1, n, nc), zv.y);
+        reinterpret_cast<d2*>(z)[i] = zv;  // plain: the post-smoother's SpMV reads it
+    }
+    if ((rows & 1) && blockIdx.x == 0 && threadIdx.x == 0) z[rows - 1] = fma(2.0, coarse_at(ec, rows - 1, n, nc), z[rows - 1]);
+}
+
+// ---- the launches: the cycle calls these, and so does the LAB build's spmv_amd_mg_stage ----
+int coarse_grid_of(int n) { return (n + 1) / 2; }
+long long stencil_nnz(int n) { return n >= 2 ? stencil_gridrow_base(n, n) : 1; }
+
+void launch_coarsen(const SlabCsr& fine, int nc, int* row_ptr, int* col_idx, double* values) {
+    const int rows = nc * nc;
+    hipLaunchKernelGGL(coarsen_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, kStream, fine, fine.grid_size, nc, row_ptr, col_idx, values);
+}
+
+void launch_residual_restrict(const SlabCsr& m, const double* z, const double* r, double* rc) {
+    const int n = m.grid_size, nc = coarse_grid_of(n);
+    const int col_tiles = (n + kTileCols - 1) / kTileCols;
+    const int tiles = col_tiles * nc;
+    const int run = rowlds_xcd_run_rule(n);
+    hipLaunchKernelGGL(residual_restrict_kernel, dim3((unsigned)xcd_padded_grid(tiles, run)), dim3(kWave), 0, kStream, m, z, r, rc, nc, col_tiles,
+                       tiles, run);
+}
+
+void launch_prolong_correct(int n, const double* ec, double* z) {
+    const size_t rows = (size_t)n * n;
+    hipLaunchKernelGGL(prolong_correct_kernel, dim3(stream_grid(rows)), dim3(kWave), 0, kStream, rows, n, coarse_grid_of(n), ec, z);
+}
+
+// the view of a complete 5-point CSR on an n x n grid in the caller's arrays
+SlabCsr stencil_view(int n, const int* row_ptr, const int* col_idx, const double* values) {
+    SlabCsr v;
+    v.row_ptr = row_ptr, v.col_idx = col_idx, v.values = values;
+    v.n_local = v.n_global = n * n;
+    v.nnz_local = stencil_nnz(n);
+    v.max_row_nnz = n >= 3 ? 5 : (n == 2 ? 3 : 1);
+    v.grid_size = n;
+    return v;
+}
+
+bool verified(SlabCsr& v) {
+    int* d_mismatch = device_try_alloc<int>(1);
+    if (d_mismatch == nullptr) return fail("no device memory for the structure check");
+    HIP_CHECK(hipMemsetAsync(d_mismatch, 0, sizeof(int), kStream));
+    launch_verify_stencil5_csr(v, d_mismatch, kStream);
+    HIP_CHECK(hipGetLastError());
+    int mismatch = 1;
+    download(&mismatch, d_mismatch, 1);  // synchronises
+    device_release(d_mismatch);
+    v.verified_stencil = mismatch == 0;
+    return v.verified_stencil;
+}
+
+}  // namespace
+
+namespace spmv_amd {
+
+struct MgLevel {
+    int n = 0, rows = 0;  // the grid and its rows
+    DeviceCsr A;          // levels above 0 (level 0 reads the operator's own CSR)
+    SlabCsr view;
+    Stencil5Plan plan;
+    double* dinv = nullptr;  // level 0's belongs to the SpmvAmdPrecond
+    bool own_dinv = true;
+    double lambda_max = 0.0;
+    int degree = 0;
+    double coef[1 + 2 * kCoarsestDegree] = {0.0};
+    double *r = nullptr, *d = nullptr, *z = nullptr;  // r: levels above 0
+    double* aux = nullptr;  // a row-lds plan: z' of the fused step; every other plan: w = A z
+    bool fused() const { return plan.variant == Stencil5Variant::RowLds; }
+};
+
+struct MgHierarchy {
+    std::vector<MgLevel> levels;
+    int smoother_degree = 0;
+    double* partials = nullptr;  // the r.z partials of level 0's last update
+    void release() {
+        for (MgLevel& L : levels) {
+            L.A.release();
+            if (L.own_dinv) device_release(L.dinv);
+            device_release(L.r);
+            device_release(L.d);
+            device_release(L.z);
+            device_release(L.aux);
+        }
+        levels.clear();
+        device_release(partials);
+    }
+};
+
+void mg_destroy(MgHierarchy* h) {
+    if (h == nullptr) return;
+    h->release();
+    delete h;
+}
+
+double* mg_result_vector(MgHierarchy* h) { return h->levels[0].z; }
+
+namespace {
+
+struct CycleRun {
+    MgHierarchy* h;
+    StageTimers* T;
+    const double* rz_partials = nullptr;
+    int rz_count = 0;
+
+    template <class F>
+    void spmv(F&& launch) {
+        if (T != nullptr) T->run(&T->t_spmv, launch);
+        else launch();
+    }
+    template <class F>
+    void blas(F&& launch) {
+        if (T != nullptr) T->run(&T->t_blas, launch);
+        else launch();
+    }
+
+    // one step-form update on level L from z in *z: t = fma(-1, A z, r) ; u = dinv t ; d = fma(g, u, h d) ; z = z + d
+    void update(MgLevel& L, const double* r, double** z, double** other, double g, double hh, bool last) {
+        double* const partials = last ? h->partials : nullptr;
+        if (L.fused()) {
+            ChebStep step;
+            step.r = r, step.dinv = L.dinv, step.d = L.d, step.z_out = *other, step.g = g, step.h = hh, step.last = last ? 1 : 0;
+            spmv([&] {
+                const int slots = launch_stencil5_cheb_step(L.view, L.plan, *z, step, partials, nullptr, kStream);
+                if (last) rz_partials = partials, rz_count = slots;
+            });
+            double* const t = *z;
+            *z = *other, *other = t;
+        } else {
+            spmv([&] { (void)launch_stencil5_spmv(L.view, L.plan, *z, L.aux, 1.0, nullptr, nullptr, false, kStream); });
+            blas([&] { launch_cheb_step((size_t)L.rows, L.aux, r, L.dinv, g, hh, L.d, *z, last, partials); });
+            if (last) rz_partials = partials, rz_count = (int)stream_grid((size_t)L.rows);
+        }
+    }
+
+    // returns the vector of level l that holds z
+    double* level(int l, const double* r) {
+        MgLevel& L = h->levels[(size_t)l];
+        const bool coarsest = l + 1 == (int)h->levels.size();
+        const bool top = l == 0;
+        double *z = L.z, *other = L.aux;  // `other` is touched by fused steps only
+        blas([&] { launch_cheb_term0_apply((size_t)L.rows, r, L.dinv, L.coef[0], L.d, z); });
+        for (int k = 1; k <= L.degree; ++k) update(L, r, &z, &other, L.coef[2 * k], L.coef[2 * k - 1], coarsest && top && k == L.degree);
+        if (coarsest) return z;
+        MgLevel& C = h->levels[(size_t)l + 1];
+        spmv([&] { launch_residual_restrict(L.view, z, r, C.r); });
+        const double* const ec = level(l + 1, C.r);
+        blas([&] { launch_prolong_correct(L.n, ec, z); });
+        update(L, r, &z, &other, L.coef[0], 0.0, top && L.degree == 0);
+        for (int k = 1; k <= L.degree; ++k) update(L, r, &z, &other, L.coef[2 * k], L.coef[2 * k - 1], top && k == L.degree);
+        return z;
+    }
+};
+
+}  // namespace
+
+MgCycleResult mg_cycle(MgHierarchy* h, const double* r, StageTimers* T) {
+    CycleRun run{h, T};
+    MgCycleResult out;
+    out.z = run.level(0, r);
+    out.rz_partials = run.rz_partials, out.rz_count = run.rz_count;
+    return out;
+}
+
+}  // namespace spmv_amd
+
+namespace {
+
+// Builds level l (> 0) of the hierarchy from level l - 1, or level 0 from the operator's view; false = refused (said on stderr).
+bool finish_level(MgHierarchy* h, int l, const LaunchShape& shape, int* bad_row) {
+    MgLevel& L = h->levels[(size_t)l];
+    const bool coarsest = l + 1 == (int)h->levels.size();
+    if (l > 0) {
+        const MgLevel& F = h->levels[(size_t)l - 1];
+        L.A.allocate((size_t)L.rows, (size_t)stencil_nnz(L.n));
+        launch_coarsen(F.view, L.n, L.A.row_ptr, L.A.col_idx, L.A.values);
+        HIP_CHECK(hipGetLastError());
+        L.A.view = stencil_view(L.n, L.A.row_ptr, L.A.col_idx, L.A.values);
+        L.view = L.A.view;
+        if (!verified(L.view)) {
+            fprintf(stderr, "[PCG] multigrid: the coarse operator of level %d is not a complete 5-point stencil: refused\n", l);
+            return false;
+        }
+        L.A.view = L.view;
+        int bad = -1;
+        L.dinv = inverse_diagonal_of_csr(L.view, L.rows, &bad);
+        if (L.dinv == nullptr) {
+            if (bad >= 0) {
+                if (bad_row != nullptr) *bad_row = bad;
+                fprintf(stderr, "[PCG] multigrid: level %d: the diagonal entry of row %d is zero, not finite or of the other sign than row 0's: refused\n",
+                        l, bad);
+            }
+            return false;
+        }
+    }
+    L.lambda_max = gershgorin_of_csr(L.view, L.rows, L.dinv);
+    const double lmin = coarsest ? L.lambda_max / 30.0 : L.lambda_max / 4.0;
+    if (!isfinite(L.lambda_max) || !(lmin > 0.0) || !(lmin < L.lambda_max)) {
+        fprintf(stderr, "[PCG] multigrid: level %d: the interval [%g, %g] is not 0 < lambda_min < lambda_max, both finite: refused\n", l, lmin,
+                L.lambda_max);
+        return false;
+    }
+    L.degree = coarsest ? kCoarsestDegree : h->smoother_degree;
+    chebyshev_coefficients(L.degree, lmin, L.lambda_max, L.coef);
+    L.plan = plan_stencil5(L.view, 0, L.rows, Stencil5Variant::Auto, shape);
+    if (l > 0) L.r = device_try_alloc<double>((size_t)L.rows);
+    L.d = device_try_alloc<double>((size_t)L.rows);
+    L.z = device_try_alloc<double>((size_t)L.rows);
+    L.aux = device_try_alloc<double>((size_t)L.rows);
+    if ((l > 0 && L.r == nullptr) || L.d == nullptr || L.z == nullptr || L.aux == nullptr) return fail("the level vectors could not be allocated: refused");
+    return true;
+}
+
+}  // namespace
+
+extern "C" SpmvAmdPrecond* spmv_amd_precond_create_multigrid(SpmvOperator* op, int smoother_degree, int max_levels, int* bad_row) {
+    // argument checks: all before the first HIP call
+    if (bad_row != nullptr) *bad_row = -1;
+    if (op == nullptr) return fail("null operator"), nullptr;
+    if (smoother_degree < 0 || smoother_degree > kMaxSmoother) {
+        fprintf(stderr, "[PCG] multigrid: smoother degree %d is outside 0..%d: refused\n", smoother_degree, kMaxSmoother);
+        return nullptr;
+    }
+    if (max_levels < 0 || max_levels > kMaxLevels) {
+        fprintf(stderr, "[PCG] multigrid: max_levels %d is neither 0 (automatic) nor 1..%d: refused\n", max_levels, kMaxLevels);
+        return nullptr;
+    }
+    const DiagonalSource d = diagonal_source_of(op);
+    if (d.owner == nullptr || d.kind != DiagonalSource::Csr || op->name == nullptr ||
+        (strcmp(op->name, "stencil5-csr") != 0 && strcmp(op->name, "stencil5-halo-mgpu") != 0)) {
+        fprintf(stderr, "[PCG] multigrid: operator '%s' is not stencil5-csr: refused\n", op->name ? op->name : "?");
+        return nullptr;
+    }
+    if (!d.ready) {
+        fprintf(stderr, "[PCG] operator '%s' used before init\n", op->name);
+        return nullptr;
+    }
+    const int n0 = d.csr.grid_size;
+    if (!d.csr.verified_stencil || n0 < 1 || d.rows != d.cols || (long long)n0 * n0 != d.rows) {
+        fprintf(stderr, "[PCG] multigrid: the matrix of operator '%s' is not a verified complete 5-point stencil: refused\n", op->name);
+        return nullptr;
+    }
+
+    MgHierarchy* h = new MgHierarchy();
+    h->smoother_degree = smoother_degree;
+    size_t need = 0;
+    for (int n = n0;; n = coarse_grid_of(n)) {
+        MgLevel L;
+        L.n = n, L.rows = n * n;
+        const bool top = h->levels.empty();
+        h->levels.push_back(L);
+        need += (size_t)L.rows * sizeof(double) * (top ? 3 : 5);
+        if (!top) need += (size_t)stencil_nnz(n) * (sizeof(double) + sizeof(int)) + ((size_t)L.rows + 1) * sizeof(int) + 3 * 4096;
+        if (n <= kCoarsestGrid || (max_levels > 0 && (int)h->levels.size() == max_levels)) break;
+    }
+    SpmvAmdPrecond* pm = nullptr;
+    char what[64];
+    snprintf(what, sizeof what, "%d levels on %d rows (multigrid)", (int)h->levels.size(), d.rows);
+    const LaunchShape shape = current_launch_shape();
+    bool ok = device_has_room(need + (size_t)d.rows * sizeof(double) + ((size_t)64 << 20), "PCG", what);
+    if (ok) {
+        MgLevel& top = h->levels[0];
+        top.view = d.csr;
+        top.own_dinv = false;
+        int bad = -1;
+        top.dinv = inverse_diagonal_of_csr(top.view, top.rows, &bad);
+        if (top.dinv == nullptr) {
+            ok = false;
+            if (bad >= 0) {
+                if (bad_row != nullptr) *bad_row = bad;
+                fprintf(stderr, "[PCG] multigrid: level 0: the diagonal entry of row %d is zero, not finite or of the other sign than row 0's: refused\n",
+                        bad);
+            }
+        } else {
+            pm = new SpmvAmdPrecond();
+            pm->kind = kMultigrid;
+            pm->n = d.rows;
+            pm->dinv = top.dinv;
+            pm->degree = smoother_degree;
+            pm->owner = d.owner;
+            pm->generation = d.generation;
+        }
+    }
+    for (int l = 0; ok && l < (int)h->levels.size(); ++l) ok = finish_level(h, l, shape, bad_row);
+    if (ok) {
+        const MgLevel& top = h->levels[0];
+        const size_t slots = top.fused() ? (size_t)top.plan.partials : (size_t)stream_grid((size_t)top.rows);
+        h->partials = device_try_alloc<double>(slots);
+        if (h->partials == nullptr) ok = fail("the partials could not be allocated: refused");
+    }
+    HIP_CHECK(hipStreamSynchronize(kStream));
+    if (!ok) {
+        mg_destroy(h);
+        if (pm != nullptr) {
+            device_release(pm->dinv);
+            delete pm;
+        }
+        return nullptr;
+    }
+    pm->mg = h;
+    pm->lambda_max = h->levels[0].lambda_max;
+    pm->lambda_min = pm->lambda_max / (h->levels.size() == 1 ? 30.0 : 4.0);
+    return pm;
+}
+
+extern "C" int spmv_amd_precond_multigrid_info(const SpmvAmdPrecond* m, int* levels, int* smoother_degree, int* grids, double* lambda_max, int cap) {
+    if (m == nullptr || m->kind != kMultigrid || m->mg == nullptr) return 0;
+    const int count = (int)m->mg->levels.size();
+    if (levels != nullptr) *levels = count;
+    if (smoother_degree != nullptr) *smoother_degree = m->mg->smoother_degree;
+    for (int l = 0; l < count && l < cap; ++l) {
+        if (grids != nullptr) grids[l] = m->mg->levels[(size_t)l].n;
+        if (lambda_max != nullptr) lambda_max[l] = m->mg->levels[(size_t)l].lambda_max;
+    }
+    return count;
+}
+
+#ifdef SPMV_AMD_LAB
+extern "C" int spmv_amd_precond_multigrid_level_csr(const SpmvAmdPrecond* m, int level, int* row_ptr, int* col_idx, double* values, double* dinv) {
+    if (m == nullptr || m->kind != kMultigrid || m->mg == nullptr) return fail("level_csr: not a multigrid preconditioner"), 1;
+    if (level < 0 || level >= (int)m->mg->levels.size()) return fail("level_csr: no such level"), 1;
+    const MgLevel& L = m->mg->levels[(size_t)level];
+    HIP_CHECK(hipStreamSynchronize(kStream));
+    if (row_ptr != nullptr) download(row_ptr, L.view.row_ptr, (size_t)L.rows + 1);
+    if (col_idx != nullptr) download(col_idx, L.view.col_idx, (size_t)L.view.nnz_local);
+    if (values != nullptr) download(values, L.view.values, (size_t)L.view.nnz_local);
+    if (dinv != nullptr) download(dinv, L.dinv, (size_t)L.rows);
+    return 0;
+}
+
+extern "C" int spmv_amd_mg_stage(const char* stage, SpmvAmdMgStageArgs* a) {
+    // argument checks: all before the first HIP call
+    enum { kCoarsen, kRestrict, kProlong } st;
+    if (stage == nullptr) return fail("stage: none named (coarsen, residual_restrict, prolong)"), 1;
+    if (!strcmp(stage, "coarsen")) st = kCoarsen;
+    else if (!strcmp(stage, "residual_restrict")) st = kRestrict;
+    else if (!strcmp(stage, "prolong")) st = kProlong;
+    else return fail("stage: unknown (coarsen, residual_restrict, prolong)"), 1;
+    if (a == nullptr) return fail("stage: null arguments"), 1;
+    if (a->n < 2 || a->n > 46340) return fail("stage: the fine grid is outside 2..46340"), 1;
+    const auto aligned = [](const void* p, uintptr_t to) { return p != nullptr && ((uintptr_t)p & (to - 1)) == 0; };
+    if (st != kProlong && (!aligned(a->row_ptr, 4) || !aligned(a->col_idx, 4) || !aligned(a->values, 8)))
+        return fail("stage: a null or misaligned CSR array"), 1;
+    if (st == kCoarsen && (!aligned(a->out_row_ptr, 4) || !aligned(a->out_col_idx, 4) || !aligned(a->out_values, 8)))
+        return fail("stage: a null or misaligned coarse CSR array"), 1;
+    if (st == kRestrict && (!aligned(a->z, 16) || !aligned(a->r, 16) || !aligned(a->coarse, 8)))
+        return fail("stage: z and r must be 16-byte aligned, the coarse vector 8-byte aligned"), 1;
+    if (st == kProlong && (!aligned(a->z, 16) || !aligned(a->coarse, 8)))
+        return fail("stage: z must be 16-byte aligned, the coarse vector 8-byte aligned"), 1;
+
+    if (st == kProlong) {
+        launch_prolong_correct(a->n, a->coarse, a->z);
+    } else {
+        SlabCsr fine = stencil_view(a->n, a->row_ptr, a->col_idx, a->values);
+        if (!verified(fine)) return fail("stage: the CSR is not a complete 5-point stencil of that grid: refused"), 1;
+        if (st == kCoarsen) launch_coarsen(fine, coarse_grid_of(a->n), a->out_row_ptr, a->out_col_idx, a->out_values);
+        else launch_residual_restrict(fine, a->z, a->r, a->coarse);
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    return 0;
+}
+#endif  // SPMV_AMD_LAB

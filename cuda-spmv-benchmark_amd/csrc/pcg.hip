@@ -25,6 +25,12 @@
 // On stencil5-csr / row-lds a step is ONE launch (spmv_kernels.hip, kMode 3: A z never leaves the registers, z' goes to a second
 // vector): 144 + 88 k bytes per interior row and iteration. Everywhere else it is the operator's SpMV and one streaming kernel
 // (112 per step). The Jacobi and "none" loops above are untouched by this kind: it has its own loop function.
+//
+// Kind "multigrid" (multigrid.hip; stencil5-csr only): z = M^-1 r is one V-cycle on the preconditioner's own levels.
+// Its iteration:
+//   Ap = A p with the p.Ap partials | sum + alpha | r -= alpha Ap with the r.r partials (the "none" r update) | sum of r.r + verdict |
+//   the host reads the verdict: the converging iteration runs no cycle | V-cycle | sum of r.z + beta | x += alpha p, p = z + beta p
+// The set-up passes and the Chebyshev kernels above reach multigrid.hip through precond.hpp.
 #include <limits.h>
 #include <math.h>
 #include <stddef.h>
@@ -35,6 +41,7 @@
 
 #include "device_runtime.hpp"
 #include "multi_rhs.hpp"
+#include "precond.hpp"
 #include "reduce_device.hpp"
 #include "solve_common.hpp"
 #include "stream_device.hpp"
@@ -43,20 +50,6 @@
 #endif
 
 using namespace spmv_amd;
-
-enum PrecondKind { kNone = 0, kJacobi = 1, kChebyshev = 2 };
-constexpr int kChebMaxDegree = 32;
-
-struct SpmvAmdPrecond {
-    int kind = kNone;
-    int n = 0;
-    const void* owner = nullptr;  // the operator state the diagonal came from (DiagonalSource::owner); null: a caller's diagonal
-    unsigned long long generation = 0;
-    double* dinv = nullptr;       // device, n values ("jacobi", "chebyshev")
-    int degree = 0;               // "chebyshev": steps = SpMVs per application
-    double lambda_min = 0.0, lambda_max = 0.0;
-    double coef[1 + 2 * kChebMaxDegree] = {0.0};  // c0, h_1, g_1, h_2, g_2, ...
-};
 
 namespace {
 
@@ -603,6 +596,7 @@ struct PcgWorkspace {
 };
 PcgWorkspace g_pcg;
 std::vector<double> g_pcg_history;  // of the last preconditioned solve
+int g_mg_cycles = 0;                // V-cycles of the last solve's loop (kind "multigrid"; the LAB build hands it out)
 int g_cheb_step_launches = 0;       // Chebyshev step launches of its loop that did work (the LAB build hands it out)
 
 bool fail(const char* what) {
@@ -663,8 +657,9 @@ int kind_of(const char* kind) {
     return -1;
 }
 
-// The validity pass over a diagonal source; returns the preconditioner or null (*bad_row set when a row is at fault).
-SpmvAmdPrecond* make_jacobi(int src, const SlabCsr& m, const int* idx, const double* val, int width, int n, int* bad_row) {
+// The diagonal pass over a diagonal source: dinv on the device, or null (*bad = the first offending row, -1: no device memory).
+double* inverse_diagonal(int src, const SlabCsr& m, const int* idx, const double* val, int width, int n, int* bad_out) {
+    *bad_out = -1;
     double* dinv = device_try_alloc<double>((size_t)n);
     int* d_bad = device_try_alloc<int>(1);
     if (dinv == nullptr || d_bad == nullptr) {
@@ -682,8 +677,21 @@ SpmvAmdPrecond* make_jacobi(int src, const SlabCsr& m, const int* idx, const dou
     device_release(d_bad);
     if (bad != none) {
         device_release(dinv);
-        if (bad_row != nullptr) *bad_row = bad;
-        fprintf(stderr, "[PCG] jacobi: the diagonal entry of row %d is zero, not finite or of the other sign than row 0's: refused\n", bad);
+        *bad_out = bad;
+        return nullptr;
+    }
+    return dinv;
+}
+
+// The validity pass over a diagonal source; returns the preconditioner or null (*bad_row set when a row is at fault).
+SpmvAmdPrecond* make_jacobi(int src, const SlabCsr& m, const int* idx, const double* val, int width, int n, int* bad_row) {
+    int bad = -1;
+    double* dinv = inverse_diagonal(src, m, idx, val, width, n, &bad);
+    if (dinv == nullptr) {
+        if (bad >= 0) {
+            if (bad_row != nullptr) *bad_row = bad;
+            fprintf(stderr, "[PCG] jacobi: the diagonal entry of row %d is zero, not finite or of the other sign than row 0's: refused\n", bad);
+        }
         return nullptr;
     }
     SpmvAmdPrecond* pm = new SpmvAmdPrecond();
@@ -691,6 +699,21 @@ SpmvAmdPrecond* make_jacobi(int src, const SlabCsr& m, const int* idx, const dou
     pm->n = n;
     pm->dinv = dinv;
     return pm;
+}
+
+// lambda_max of D^-1 A by gershgorin_kernel
+double gershgorin_bound(int src, const SlabCsr& m, const int* idx, const double* val, int width, int rows, const double* dinv) {
+    unsigned long long* d_bits = device_alloc<unsigned long long>(1);
+    const unsigned long long zero = 0;
+    upload(d_bits, &zero, 1);
+    hipLaunchKernelGGL(gershgorin_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, kStream, src, m, idx, val, width, rows, dinv, d_bits);
+    HIP_CHECK(hipGetLastError());
+    unsigned long long bits = 0;
+    download(&bits, d_bits, 1);  // synchronises
+    device_release(d_bits);
+    double bound = 0.0;
+    memcpy(&bound, &bits, sizeof bound);
+    return bound;
 }
 
 }  // namespace
@@ -742,10 +765,9 @@ extern "C" SpmvAmdPrecond* spmv_amd_precond_create_from_diagonal(const double* d
     return make_jacobi(2, SlabCsr{}, nullptr, d_diag, 0, n, bad_row);
 }
 
-namespace {
 // The coefficients of the degree-k Chebyshev polynomial on [lmin, lmax], in the order and with the operations api.h states (the file is
 // compiled with -ffp-contract=off: one rounding per operation).
-void chebyshev_coefficients(int degree, double lmin, double lmax, double* coef) {
+void spmv_amd::chebyshev_coefficients(int degree, double lmin, double lmax, double* coef) {
     const double theta = 0.5 * (lmax + lmin);
     const double delta = 0.5 * (lmax - lmin);
     const double sigma = theta / delta;
@@ -759,6 +781,21 @@ void chebyshev_coefficients(int degree, double lmin, double lmax, double* coef) 
     }
 }
 
+// pcg.hip's set-up passes and Chebyshev kernels for multigrid.hip (precond.hpp)
+namespace spmv_amd {
+double* inverse_diagonal_of_csr(const SlabCsr& m, int n, int* bad_row) { return inverse_diagonal(0, m, nullptr, nullptr, 0, n, bad_row); }
+double gershgorin_of_csr(const SlabCsr& m, int n, const double* dinv) { return gershgorin_bound(0, m, nullptr, nullptr, 0, n, dinv); }
+void launch_cheb_term0_apply(size_t n, const double* r, const double* dinv, double c0, double* d, double* z) {
+    launch_cheb_term0<2>(n, nullptr, nullptr, nullptr, dinv, c0, const_cast<double*>(r), d, z, false, nullptr);
+}
+void launch_cheb_step(size_t n, const double* w, const double* r, const double* dinv, double g, double h, double* d, double* z, bool last,
+                      double* partials) {
+    hipLaunchKernelGGL(cheb_step_kernel, dim3(stream_grid(n)), dim3(kWave), 0, kStream, n, (const int*)nullptr, w, r, dinv, g, h, d, z, last ? 1 : 0,
+                       partials, (int*)nullptr);
+}
+}  // namespace spmv_amd
+
+namespace {
 // What every entry point that takes (op, m) checks of the pair before any HIP call; *d: the operator's storage view.
 bool precond_matches(const SpmvOperator* op, const SpmvAmdPrecond* m, DiagonalSource* d) {
     *d = diagonal_source_of(op);
@@ -806,16 +843,7 @@ extern "C" SpmvAmdPrecond* spmv_amd_precond_create_chebyshev(SpmvOperator* op, i
     pm->generation = d.generation;
     double lmax = lambda_max;
     if (!(lmax > 0.0)) {
-        unsigned long long* d_bits = device_alloc<unsigned long long>(1);
-        const unsigned long long zero = 0;
-        upload(d_bits, &zero, 1);
-        hipLaunchKernelGGL(gershgorin_kernel, dim3((unsigned)((d.rows + 255) / 256)), dim3(256), 0, kStream, src, d.csr, d.idx, d.val, d.width,
-                           d.rows, pm->dinv, d_bits);
-        HIP_CHECK(hipGetLastError());
-        unsigned long long bits = 0;
-        download(&bits, d_bits, 1);  // synchronises
-        device_release(d_bits);
-        memcpy(&lmax, &bits, sizeof lmax);
+        lmax = gershgorin_bound(src, d.csr, d.idx, d.val, d.width, d.rows, pm->dinv);
     }
     const double lmin = lambda_min > 0.0 ? lambda_min : lmax / 30.0;
     if (!isfinite(lmax) || !isfinite(lmin) || !(lmin > 0.0) || !(lmin < lmax)) {
@@ -851,7 +879,8 @@ extern "C" int spmv_amd_precond_apply_device(SpmvOperator* op, const SpmvAmdPrec
     DiagonalSource d;
     if (!precond_matches(op, m, &d)) return 1;
     const bool cheb = m->kind == kChebyshev;
-    if (cheb && (op->run_device == nullptr || d.owner == nullptr || d.rows != m->n || d.cols != m->n))
+    const bool mg = m->kind == kMultigrid;
+    if ((cheb || mg) && (op->run_device == nullptr || d.owner == nullptr || d.rows != m->n || d.cols != m->n))
         return fail("apply: the operator is not the initialised square one the preconditioner was made from: refused"), 1;
 
     CgWorkspaceScope scope;
@@ -878,7 +907,11 @@ extern "C" int spmv_amd_precond_apply_device(SpmvOperator* op, const SpmvAmdPrec
         int rz_count = vec_count;
         const double* rz_partials = partials;
         bool failed = false;
-        if (!cheb) {
+        if (mg) {
+            const MgCycleResult cycle = mg_cycle(m->mg, d_r, nullptr);
+            HIP_CHECK(hipMemcpyAsync(d_z, cycle.z, n * sizeof(double), hipMemcpyDeviceToDevice, kStream));
+            rz_partials = cycle.rz_partials, rz_count = cycle.rz_count;
+        } else if (!cheb) {
             const dim3 grid((unsigned)vec_count), block(kWave);
             if (m->kind == kJacobi) hipLaunchKernelGGL(precond_apply_kernel<true>, grid, block, 0, kStream, n, d_r, m->dinv, d_z, partials);
             else hipLaunchKernelGGL(precond_apply_kernel<false>, grid, block, 0, kStream, n, d_r, nullptr, d_z, partials);
@@ -916,13 +949,14 @@ extern "C" int spmv_amd_precond_apply_device(SpmvOperator* op, const SpmvAmdPrec
 
 extern "C" void spmv_amd_precond_destroy(SpmvAmdPrecond* m) {
     if (m == nullptr) return;
+    mg_destroy(m->mg);
     device_release(m->dinv);
     delete m;
 }
 
 extern "C" const char* spmv_amd_precond_kind(const SpmvAmdPrecond* m) {
     if (m == nullptr) return "invalid";
-    return m->kind == kChebyshev ? "chebyshev" : m->kind == kJacobi ? "jacobi" : "none";
+    return m->kind == kMultigrid ? "multigrid" : m->kind == kChebyshev ? "chebyshev" : m->kind == kJacobi ? "jacobi" : "none";
 }
 
 extern "C" int spmv_amd_precond_inverse_diagonal(const SpmvAmdPrecond* m, double* out, int n) {
@@ -971,6 +1005,7 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
     const CGConfig cfg = *config;
     const bool jac = m->kind == kJacobi;
     const bool cheb = m->kind == kChebyshev;
+    const bool mg = m->kind == kMultigrid;
 
     CgWorkspaceScope scope;
     int device = 0;
@@ -1013,7 +1048,23 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
         if (!op_failed) T.run(&T.t_red, [&] { reduce_at(m->degree == 0 ? w.partials + vec_count : w.partials, rz_count, 1, which); });
         return z;
     };
-    if (cheb) {
+    // kind "multigrid": one V-cycle on r (multigrid.hip times its own launches) and the sum of the r.z partials its last update left
+    int mg_cycles = 0;
+    auto mg_cycle_and_rz = [&](int which) -> double* {
+        const MgCycleResult cycle = mg_cycle(m->mg, w.r, &T);
+        T.run(&T.t_red, [&] { reduce_at(cycle.rz_partials, cycle.rz_count, 1, which); });
+        return cycle.z;
+    };
+    if (mg) {
+        HIP_CHECK(hipMemsetAsync(cs, 0, sizeof(ChebScalars), kStream));
+        T.run(&T.t_spmv, [&] { run_op(w.x, w.Ap); });
+        T.run(&T.t_blas, [&] { launch_pcg_init(false, (size_t)n, w.b, w.Ap, nullptr, w.r, w.p, w.partials); });
+        T.run(&T.t_red, [&] { reduce(vec_count, 1, 0); });
+        if (!op_failed) {
+            const double* const z0 = mg_cycle_and_rz(5);
+            HIP_CHECK(hipMemcpyAsync(w.p, z0, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, kStream));
+        }
+    } else if (cheb) {
         HIP_CHECK(hipMemsetAsync(cs, 0, sizeof(ChebScalars), kStream));
         T.run(&T.t_spmv, [&] { run_op(w.x, w.Ap); });
         T.run(&T.t_blas, [&] { launch_cheb_term0<0>((size_t)n, w.s, w.b, w.Ap, m->dinv, m->coef[0], w.r, w.cd, w.cz, m->degree == 0, w.partials); });
@@ -1040,7 +1091,17 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
         });
         if (op_failed) break;
         T.run(&T.t_red, [&] { reduce(pap_count, 1, 1); });
-        if (cheb) {
+        if (mg) {
+            T.run(&T.t_blas, [&] { launch_pcg_update_r(false, (size_t)n, w.s, w.Ap, nullptr, w.r, w.partials); });
+            T.run(&T.t_red, [&] { reduce(vec_count, 1, 3); });  // r.r and the verdict
+            download(&h, w.s, 1);  // the host reads the verdict first: the converging iteration runs no cycle
+            const double* z = mg_result_vector(m->mg);
+            if (!h.converged && !h.breakdown) {
+                z = mg_cycle_and_rz(4);
+                ++mg_cycles;
+            }
+            T.run(&T.t_blas, [&] { launch_pcg_update_xp(false, (size_t)n, w.s, z, nullptr, w.p, w.x); });
+        } else if (cheb) {
             T.run(&T.t_blas, [&] {
                 launch_cheb_term0<1>((size_t)n, w.s, nullptr, w.Ap, m->dinv, m->coef[0], w.r, w.cd, w.cz, m->degree == 0, w.partials);
             });
@@ -1064,6 +1125,7 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
     const int count = h.iterations + 1 < w.hist_cap ? h.iterations + 1 : w.hist_cap;
     g_pcg_history.assign((size_t)count, 0.0);
     download(g_pcg_history.data(), w.hist, (size_t)count);
+    g_mg_cycles = mg_cycles;
     g_cheb_step_launches = 0;
     if (cheb) download(&g_cheb_step_launches, &cs->steps_done, 1);
     if (op_failed) return 1;
@@ -1092,6 +1154,7 @@ extern "C" void spmv_amd_pcg_release_workspace(void) { spmv_amd::release_cg_work
 
 #ifdef SPMV_AMD_LAB
 extern "C" int spmv_amd_pcg_last_step_launches(void) { return g_cheb_step_launches; }
+extern "C" int spmv_amd_pcg_last_multigrid_cycles(void) { return g_mg_cycles; }
 
 // ---- the loop's kernels one stage at a time on caller data (include/spmv_amd/lab.h; tests/test_pcg_stages_gpu.py) ----
 static_assert(sizeof(SpmvAmdPcgScalars) == sizeof(PcgScalars) && offsetof(SpmvAmdPcgScalars, b_norm) == offsetof(PcgScalars, b_norm) &&

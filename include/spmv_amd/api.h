@@ -318,19 +318,43 @@ SpmvAmdPrecond* spmv_amd_precond_create_chebyshev(SpmvOperator* op, int degree, 
 /* degree, interval, and up to cap coefficients in the order c0, h_1, g_1, h_2, g_2, ...; returns how many exist (1 + 2*degree);
  * 0 for another kind (nothing is written). Any out pointer may be NULL. */
 int spmv_amd_precond_chebyshev_info(const SpmvAmdPrecond* m, int* degree, double* lambda_min, double* lambda_max, double* coefficients, int cap);
+/* Kind "multigrid" (csrc/multigrid.hip), for "stencil5-csr" on a verified complete 5-point stencil: z = M^-1 r is one
+ * symmetric V(nu, nu) cycle, nu = smoother_degree (0..8), on a hierarchy of 5-point stencils made by 2 x 2 aggregation. max_levels: 0 =
+ * automatic, else 1..32 caps the number of levels. Refused before any HIP call: a null operator, an argument out of range, an operator
+ * that is not stencil5-csr or not initialised; after HIP work: a matrix that is not a verified stencil, a diagonal entry on any level
+ * that breaks Jacobi's validity rule (the level is named on stderr, *bad_row = the row of that level). spmv_amd_precond_create(op,
+ * "multigrid") stays refused: this kind has arguments.
+ * Levels: level 0 is the operator's n0 x n0 grid; level l+1 has the grid ceil(n_l / 2); aggregate (I, J) = the fine points (2I + a, 2J + b),
+ * a, b in {0, 1}, that exist. Coarsening stops at the first level with n_l <= 8, or at max_levels.
+ * Coarse operator A_c = P^T A P, P piecewise constant, again a complete 5-point CSR ([N,W,C,E,S]); every entry a sequential sum from
+ * 0.0 with plain additions: the members in the order (0,0), (0,1), (1,0), (1,1), each member's entries in CSR order, every entry added
+ * to the coarse entry of the aggregate its column lies in (N_c = sum_b N(2I, 2J+b), W_c = sum_a W(2I+a, 2J), E_c = sum_a E(2I+a, 2J+1),
+ * S_c = sum_b S(2I+1, 2J+b), C_c = everything that stays inside). A bit-symmetric fine matrix gives a bit-symmetric coarse one.
+ * Per level: dinv by the diagonal pass above, lambda_max by the symmetric Gershgorin bound; the smoother is the Chebyshev application of
+ * degree nu on [lambda_max / 4.0, lambda_max]; the coarsest level is solved by degree 8 on [lambda_max / 30.0, lambda_max] from a
+ * zero guess (term 0 and eight steps).
+ * Cycle on level l, input r, output z:  (1) term 0, then steps 1..nu.  (2) r_c[I,J] = ((t00 + t01) + t10) + t11 over the members that
+ * exist, t_i = fma(-1.0, (A z)_i, r_i), (A z)_i the bits of stencil5-csr's SpMV for row i.  (3) e_c = cycle(l+1, r_c).
+ * (4) z = fma(2.0, e_c[agg(i)], z).  (5) nu + 1 updates t = fma(-1.0, (A z), r); u = dinv t; d = fma(g, u, h d); z = z + d: the first with
+ * g = c0, h = 0.0 and d as step (1) left it, then steps 1..nu with (h_k, g_k).
+ * The solve with this kind reads the iteration's verdict on the host before the cycle: the converging iteration runs none. */
+SpmvAmdPrecond* spmv_amd_precond_create_multigrid(SpmvOperator* op, int smoother_degree, int max_levels, int* bad_row);
+/* The number of levels, nu, and up to cap grids n_l and lambda_max_l; returns the number of levels, 0 for another kind (nothing is
+ * written). Any out pointer may be NULL. */
+int spmv_amd_precond_multigrid_info(const SpmvAmdPrecond* m, int* levels, int* smoother_degree, int* grids, double* lambda_max, int cap);
 /* z = M^-1 r on device vectors of n rows (16-byte aligned), any kind (none: copy, jacobi: dinv*r). d_z must not overlap d_r, which is
  * only read. rz (may be NULL): r.z summed by the solver's own fixed-shape reduction. The pair (op, m) is checked as by
  * spmv_amd_pcg_solve_device, before any HIP call. Work vectors live for the call only. Synchronises. Returns 0, non-zero for a refusal. */
 int spmv_amd_precond_apply_device(SpmvOperator* op, const SpmvAmdPrecond* m, const double* d_r, double* d_z, double* rz);
 void spmv_amd_precond_destroy(SpmvAmdPrecond* m);
-/* "none", "jacobi"; "invalid" for NULL. */
+/* "none", "jacobi", "chebyshev", "multigrid"; "invalid" for NULL. */
 const char* spmv_amd_precond_kind(const SpmvAmdPrecond* m);
 /* Host copy of dinv (n must be the preconditioner's size); non-zero for kind "none". */
 int spmv_amd_precond_inverse_diagonal(const SpmvAmdPrecond* m, double* out, int n);
 /* Preconditioned CG on the device. b, x: host arrays of mat->rows values, x in = x0, out = solution (uploaded before and
  * downloaded after the timed region). Refused: NULL pointers, an uninitialised or non-square operator, n != mat->rows, a
  * preconditioner made from another operator or from an earlier init of this one. The workspace (x, b, r, p, Ap; kind
- * "chebyshev": d, z and a second z as well) is sized against the device's free memory first, kept between calls and released with cg_solve_device's (an operator's free(),
+ * "chebyshev": d, z and a second z as well; kind "multigrid" keeps its level vectors in the preconditioner) is sized against the device's free memory first, kept between calls and released with cg_solve_device's (an operator's free(),
  * spmv_amd_cg_release_workspace(), spmv_amd_pcg_release_workspace()). */
 int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, const double* b, double* x,
                               const CGConfig* config, CGStats* stats);

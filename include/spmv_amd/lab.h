@@ -127,6 +127,31 @@ int spmv_amd_pcg_stage(const char* stage, const char* kind, SpmvAmdPcgStageArgs*
  * degree * (iterations - 1) for a solve that converged. 0 after a solve of another kind. */
 int spmv_amd_pcg_last_step_launches(void);
 
+/* Kind "multigrid" (csrc/multigrid.hip): the V-cycles the last solve's LOOP ran (the one behind the initial residual is not counted):
+ * iterations - 1 for a solve that converged, iterations for one that reached max_iters. 0 after a solve of another kind. */
+int spmv_amd_pcg_last_multigrid_cycles(void);
+/* One level's CSR (rows + 1, nnz, nnz values: a complete 5-point stencil of the level's grid, spmv_amd_precond_multigrid_info) and
+ * dinv (rows) copied to the host; any out pointer may be NULL. Non-zero for another kind or a level that does not exist. */
+int spmv_amd_precond_multigrid_level_csr(const SpmvAmdPrecond* m, int level, int* row_ptr, int* col_idx, double* values, double* dinv);
+/* Device pointers of one spmv_amd_mg_stage call; n = the FINE grid, the coarse grid is (n + 1) / 2. */
+typedef struct SpmvAmdMgStageArgs {
+    int n;
+    const int* row_ptr;      /* coarsen, residual_restrict: the fine level's CSR, a complete 5-point stencil of grid n (checked) */
+    const int* col_idx;
+    const double* values;
+    double* z;               /* residual_restrict: in; prolong: in and out (16-byte aligned) */
+    const double* r;         /* residual_restrict: in (16-byte aligned) */
+    double* coarse;          /* residual_restrict: out, r_c; prolong: in, e_c (8-byte aligned) */
+    int* out_row_ptr;        /* coarsen: the coarse CSR, out */
+    int* out_col_idx;
+    double* out_values;
+} SpmvAmdMgStageArgs;
+/* The multigrid cycle's own launches, one per call on the caller's device data, through the functions the cycle makes them with.
+ * Every call synchronises. stage: "coarsen" (A_c = P^T A P), "residual_restrict" (r_c = P^T (r - A z) in one launch), "prolong"
+ * (z = fma(2.0, e_c[agg(i)], z)). Refused before any HIP call: an unknown stage, null arguments, n outside 2..46340, a null or
+ * misaligned pointer the stage needs; after the structure check: a CSR that is not the complete stencil. Returns 0 otherwise. */
+int spmv_amd_mg_stage(const char* stage, SpmvAmdMgStageArgs* a);
+
 /* Per-column state of a batched CG solve (csrc/multi_rhs.hpp keeps the same record on the device, one per column). */
 typedef struct SpmvAmdMultiColumn {
     double rr_old;    /* r.r of the last iteration that did not converge */
