@@ -162,14 +162,16 @@ struct FusedSpmv {
                   hipStream_t stream) = nullptr;
 };
 FusedSpmv fused_spmv_of(const SpmvOperator* op);
-// What the Chebyshev preconditioner (pcg.hip) may ask of an operator beyond run_device. stencil5-csr on a
-// row-lds plan runs one whole step inside its SpMV launch (kernels.hpp, ChebStep): fused_step returns the partial slots a last step
-// writes. stencil5-csr on any plan has a SpMV that tests a device flag (spmv_if: nothing is read once *d_skip != 0). Every other
-// operator leaves both null and is driven through run_device followed by the streaming step kernel. Defined in operators.hip.
+// How one level runs A z for a step of the Chebyshev application (pcg.hip's cheb_step): this library's
+// stencil5-csr operator and a multigrid level (multigrid.hip) are a verified stencil CSR with its launch plan -- on a row-lds plan one
+// whole step runs inside the SpMV launch (kernels.hpp, ChebStep), on any other plan the SpMV tests a device flag (nothing is read
+// once it is set) --, every other operator is its table, driven through run_device followed by the streaming step kernel. The
+// pointers are the owner's (the operator's state, the level): valid until its next init or free. cheb_spmv_of: operators.hip.
 struct ChebSpmv {
-    int partials = 0;  // slots a fused last step writes
-    int (*fused_step)(const double* d_z, const ChebStep* step, double* d_partials, const int* d_skip, hipStream_t stream) = nullptr;
-    int (*spmv_if)(const double* d_x, double* d_y, const int* d_skip, hipStream_t stream) = nullptr;
+    const SlabCsr* view = nullptr;  // with plan: the stencil forms
+    const Stencil5Plan* plan = nullptr;
+    const SpmvOperator* op = nullptr;  // without them: run_device
+    int partials = 0;                  // slots a fused last step writes; 0: the step is not fused
 };
 ChebSpmv cheb_spmv_of(const SpmvOperator* op);
 // Frees the vectors cg_solve_device keeps between calls (cg_slab.hip); called by every operator's free().

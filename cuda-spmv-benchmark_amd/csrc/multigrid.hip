@@ -302,6 +302,11 @@ struct MgLevel {
     double *r = nullptr, *d = nullptr, *z = nullptr;  // r: levels above 0
     double* aux = nullptr;  // a row-lds plan: z' of the fused step; every other plan: w = A z
     bool fused() const { return plan.variant == Stencil5Variant::RowLds; }
+    ChebSpmv spmv() const {  // how this level runs A z (device_runtime.hpp)
+        ChebSpmv a;
+        a.view = &view, a.plan = &plan, a.partials = fused() ? plan.partials : 0;
+        return a;
+    }
 };
 
 struct MgHierarchy {
@@ -335,66 +340,36 @@ namespace {
 struct CycleRun {
     MgHierarchy* h;
     StageTimers* T;
-    const double* rz_partials = nullptr;
-    int rz_count = 0;
-
-    template <class F>
-    void spmv(F&& launch) {
-        if (T != nullptr) T->run(&T->t_spmv, launch);
-        else launch();
-    }
-    template <class F>
-    void blas(F&& launch) {
-        if (T != nullptr) T->run(&T->t_blas, launch);
-        else launch();
-    }
-
-    // one step-form update on level L from z in *z: t = fma(-1, A z, r) ; u = dinv t ; d = fma(g, u, h d) ; z = z + d
-    void update(MgLevel& L, const double* r, double** z, double** other, double g, double hh, bool last) {
-        double* const partials = last ? h->partials : nullptr;
-        if (L.fused()) {
-            ChebStep step;
-            step.r = r, step.dinv = L.dinv, step.d = L.d, step.z_out = *other, step.g = g, step.h = hh, step.last = last ? 1 : 0;
-            spmv([&] {
-                const int slots = launch_stencil5_cheb_step(L.view, L.plan, *z, step, partials, nullptr, kStream);
-                if (last) rz_partials = partials, rz_count = slots;
-            });
-            double* const t = *z;
-            *z = *other, *other = t;
-        } else {
-            spmv([&] { (void)launch_stencil5_spmv(L.view, L.plan, *z, L.aux, 1.0, nullptr, nullptr, false, kStream); });
-            blas([&] { launch_cheb_step((size_t)L.rows, L.aux, r, L.dinv, g, hh, L.d, *z, last, partials); });
-            if (last) rz_partials = partials, rz_count = (int)stream_grid((size_t)L.rows);
-        }
-    }
+    Applied out;  // level 0's z and the r.z partials of its last step
 
     // returns the vector of level l that holds z
     double* level(int l, const double* r) {
         MgLevel& L = h->levels[(size_t)l];
         const bool coarsest = l + 1 == (int)h->levels.size();
         const bool top = l == 0;
-        double *z = L.z, *other = L.aux;  // `other` is touched by fused steps only
-        blas([&] { launch_cheb_term0_apply((size_t)L.rows, r, L.dinv, L.coef[0], L.d, z); });
-        for (int k = 1; k <= L.degree; ++k) update(L, r, &z, &other, L.coef[2 * k], L.coef[2 * k - 1], coarsest && top && k == L.degree);
-        if (coarsest) return z;
-        MgLevel& C = h->levels[(size_t)l + 1];
-        spmv([&] { launch_residual_restrict(L.view, z, r, C.r); });
-        const double* const ec = level(l + 1, C.r);
-        blas([&] { launch_prolong_correct(L.n, ec, z); });
-        update(L, r, &z, &other, L.coef[0], 0.0, top && L.degree == 0);
-        for (int k = 1; k <= L.degree; ++k) update(L, r, &z, &other, L.coef[2 * k], L.coef[2 * k - 1], top && k == L.degree);
-        return z;
+        ChebRun c;  // section 14's application on this level; only a last step of level 0 writes partials
+        c.a = L.spmv(), c.n = (size_t)L.rows, c.r = r, c.dinv = L.dinv, c.d = L.d, c.z = L.z, c.aux = L.aux, c.partials = h->partials, c.T = T;
+        stage_run(T, &StageTimers::t_blas, [&] { launch_cheb_term0_apply(c.n, r, L.dinv, L.coef[0], L.d, c.z); });
+        (void)cheb_steps(c, L.degree, L.coef, coarsest && top);  // pre-smoothing (the coarsest level: its solve); no run_device here
+        if (!coarsest) {
+            MgLevel& C = h->levels[(size_t)l + 1];
+            stage_run(T, &StageTimers::t_spmv, [&] { launch_residual_restrict(L.view, c.z, r, C.r); });
+            const double* const ec = level(l + 1, C.r);
+            stage_run(T, &StageTimers::t_blas, [&] { launch_prolong_correct(L.n, ec, c.z); });
+            (void)cheb_step(c, L.coef[0], 0.0, top && L.degree == 0);  // post-smoothing from the guess z: term 0 in step form
+            (void)cheb_steps(c, L.degree, L.coef, top);
+        }
+        if (top) out.z = c.z, out.rz_partials = c.rz_partials, out.rz_count = c.rz_count;
+        return c.z;
     }
 };
 
 }  // namespace
 
-MgCycleResult mg_cycle(MgHierarchy* h, const double* r, StageTimers* T) {
-    CycleRun run{h, T};
-    MgCycleResult out;
-    out.z = run.level(0, r);
-    out.rz_partials = run.rz_partials, out.rz_count = run.rz_count;
-    return out;
+Applied mg_cycle(MgHierarchy* h, const double* r, StageTimers* T) {
+    CycleRun run{h, T, Applied{}};
+    (void)run.level(0, r);
+    return run.out;
 }
 
 }  // namespace spmv_amd
@@ -417,16 +392,10 @@ bool finish_level(MgHierarchy* h, int l, const LaunchShape& shape, int* bad_row)
             return false;
         }
         L.A.view = L.view;
-        int bad = -1;
-        L.dinv = inverse_diagonal_of_csr(L.view, L.rows, &bad);
-        if (L.dinv == nullptr) {
-            if (bad >= 0) {
-                if (bad_row != nullptr) *bad_row = bad;
-                fprintf(stderr, "[PCG] multigrid: level %d: the diagonal entry of row %d is zero, not finite or of the other sign than row 0's: refused\n",
-                        l, bad);
-            }
-            return false;
-        }
+        char who[40];
+        snprintf(who, sizeof who, "multigrid: level %d", l);
+        L.dinv = inverse_diagonal_of_csr(L.view, L.rows, who, bad_row);
+        if (L.dinv == nullptr) return false;
     }
     L.lambda_max = gershgorin_of_csr(L.view, L.rows, L.dinv);
     const double lmin = coarsest ? L.lambda_max / 30.0 : L.lambda_max / 4.0;
@@ -460,16 +429,8 @@ extern "C" SpmvAmdPrecond* spmv_amd_precond_create_multigrid(SpmvOperator* op, i
         fprintf(stderr, "[PCG] multigrid: max_levels %d is neither 0 (automatic) nor 1..%d: refused\n", max_levels, kMaxLevels);
         return nullptr;
     }
-    const DiagonalSource d = diagonal_source_of(op);
-    if (d.owner == nullptr || d.kind != DiagonalSource::Csr || op->name == nullptr ||
-        (strcmp(op->name, "stencil5-csr") != 0 && strcmp(op->name, "stencil5-halo-mgpu") != 0)) {
-        fprintf(stderr, "[PCG] multigrid: operator '%s' is not stencil5-csr: refused\n", op->name ? op->name : "?");
-        return nullptr;
-    }
-    if (!d.ready) {
-        fprintf(stderr, "[PCG] operator '%s' used before init\n", op->name);
-        return nullptr;
-    }
+    DiagonalSource d;
+    if (!creation_source(op, "multigrid: ", "stencil5-csr: refused", /*stencil_only=*/true, &d)) return nullptr;
     const int n0 = d.csr.grid_size;
     if (!d.csr.verified_stencil || n0 < 1 || d.rows != d.cols || (long long)n0 * n0 != d.rows) {
         fprintf(stderr, "[PCG] multigrid: the matrix of operator '%s' is not a verified complete 5-point stencil: refused\n", op->name);
@@ -497,15 +458,9 @@ extern "C" SpmvAmdPrecond* spmv_amd_precond_create_multigrid(SpmvOperator* op, i
         MgLevel& top = h->levels[0];
         top.view = d.csr;
         top.own_dinv = false;
-        int bad = -1;
-        top.dinv = inverse_diagonal_of_csr(top.view, top.rows, &bad);
+        top.dinv = inverse_diagonal_of_csr(top.view, top.rows, "multigrid: level 0", bad_row);
         if (top.dinv == nullptr) {
             ok = false;
-            if (bad >= 0) {
-                if (bad_row != nullptr) *bad_row = bad;
-                fprintf(stderr, "[PCG] multigrid: level 0: the diagonal entry of row %d is zero, not finite or of the other sign than row 0's: refused\n",
-                        bad);
-            }
         } else {
             pm = new SpmvAmdPrecond();
             pm->kind = kMultigrid;

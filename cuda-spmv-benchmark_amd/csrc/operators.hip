@@ -189,15 +189,6 @@ int stencil_fused_launch(const double* d_x, double* d_y, double* d_partials, con
     return launch_stencil5_spmv(g_stencil.A.view, g_stencil.plan, d_x, d_y, /*alpha=*/1.0, d_partials, d_skip, reverse, stream, init);
 }
 
-// The Chebyshev preconditioner's launches on this operator (device_runtime.hpp, ChebSpmv).
-int stencil_cheb_step(const double* d_z, const ChebStep* step, double* d_partials, const int* d_skip, hipStream_t stream) {
-    return launch_stencil5_cheb_step(g_stencil.A.view, g_stencil.plan, d_z, *step, d_partials, d_skip, stream);
-}
-int stencil_spmv_if(const double* d_x, double* d_y, const int* d_skip, hipStream_t stream) {
-    (void)launch_stencil5_spmv(g_stencil.A.view, g_stencil.plan, d_x, d_y, /*alpha=*/1.0, nullptr, d_skip, /*reverse=*/false, stream);
-    return 0;
-}
-
 // ---- cusparse-csr ----------------------------------------------------------------
 
 const char* csr_variant_name(CsrVariant v, const SlabCsr& m) {
@@ -504,12 +495,10 @@ FusedSpmv fused_spmv_of(const SpmvOperator* op) {
 
 ChebSpmv cheb_spmv_of(const SpmvOperator* op) {
     ChebSpmv c;
+    c.op = op;
     if (own_operator_of(op).csr == &g_stencil && g_stencil.ready) {
-        c.spmv_if = stencil_spmv_if;
-        if (g_stencil.plan.variant == Stencil5Variant::RowLds && g_stencil.plan.partials > 0) {
-            c.partials = g_stencil.plan.partials;
-            c.fused_step = stencil_cheb_step;
-        }
+        c.view = &g_stencil.A.view, c.plan = &g_stencil.plan;
+        if (g_stencil.plan.variant == Stencil5Variant::RowLds) c.partials = g_stencil.plan.partials;
     }
     return c;
 }

@@ -1,36 +1,41 @@
-// pcg.hip -- preconditioned CG over any SpmvOperator: Jacobi and a Chebyshev polynomial in D^-1 A (section 14).
+// pcg.hip -- preconditioned CG over any SpmvOperator: kinds "none" and "jacobi" (DESIGN.md section 13), a Chebyshev polynomial in
+// D^-1 A (section 14) and one multigrid V-cycle (multigrid.hip, section 15; stencil5-csr only).
 //
-// An entry point with its own loop: the algebra of cg_solve_device with z = M^-1 r, M = diag(A) ("jacobi") or I ("none"),
-// the same stopping rule (true residual ||r_k|| / ||r_0|| < tol, strict, the converging iteration counted), statistics and
-// timer rule (solve_common.hpp has those, stream_device.hpp the kernels' small helpers). One iteration:
+// One loop, spmv_amd_pcg_solve_device: the algebra of cg_solve_device with z = M^-1 r, the same stopping rule (true residual
+// ||r_k|| / ||r_0|| < tol, strict, the converging iteration counted), statistics and timer rule (solve_common.hpp has those,
+// stream_device.hpp the kernels' small helpers). The loop names every stage all kinds share once:
 //   Ap = A p with the p.Ap partials (the operator's fused launch; else run_device + a dot pass) |
 //   sum + step (alpha = rz / pAp) |
-//   r -= alpha Ap, z = dinv r in registers, partials of r.r and r.z |
-//   both sums + step (history, verdict, beta = rz' / rz) |
-//   x += alpha p, p = dinv r + beta p
-// then one small blocking read of the scalars (the stopping test; microseconds against milliseconds of work). Bytes per
-// interior row and iteration on stencil5-csr: 56 (SpMV) + 32 + 48 = 136 ("jacobi"), 120 ("none"); no direction ring, no
-// deferred x update, no run-ahead (that machinery is the slab loop's, cg_slab.hip).
-// Breakdown: a pAp or r.z' that is zero or not finite stops the loop in that iteration with converged = 0 (no sign test:
-// negative-definite systems solve). Sums have a fixed shape (reduce_device.hpp): a solve is bit-reproducible.
+//   the kind's unit: r -= alpha Ap, ||r|| with history and verdict, z = M^-1 r, beta = rz' / rz; it returns where z is |
+//   x += alpha p, p = z + beta p
+// then one small blocking read of the scalars (the stopping test; microseconds against milliseconds of work). A kind is a PcgKind:
+// two plain functions on the solve's PcgLoop -- `first` (everything before the loop: r0, ||r0||, z0, r0.z0, p0) and `next` (the
+// unit above) -- chosen once by pcg_kind_of. No direction ring, no deferred x update, no run-ahead (that is the slab loop's,
+// cg_slab.hip). Breakdown: a pAp or r.z' that is zero or not finite stops the loop in that iteration with converged = 0 (no sign
+// test: negative-definite systems solve). Sums have a fixed shape (reduce_device.hpp): a solve is bit-reproducible.
 //
-// Kind "chebyshev" (degree k, interval [lmin, lmax] of D^-1 A; coefficients c0, h_1, g_1, ... from the host recurrence below):
+// "none" / "jacobi" (plain_first, plain_next): z = dinv r (or r) never leaves the registers:
+//   r -= alpha Ap with the partials of r.r and r.z | both sums + step (history, verdict, beta) | the x / p kernel applies dinv to r
+// Bytes per interior row and iteration on stencil5-csr: 56 (SpMV) + 32 + 48 = 136 ("jacobi"), 120 ("none").
+//
+// "chebyshev" (cheb_first, cheb_next; degree k, interval [lmin, lmax] of D^-1 A; coefficients c0, h_1, g_1, ... from the host
+// recurrence below):
 //   term 0:  u = dinv r ; d = c0 u ; z = d
 //   step j:  w = A z ; t = fma(-1, w, r) ; u = dinv t ; d = fma(g_j, u, h_j d) ; z = z + d
-// Applying it is SpMVs and streaming updates only. Its iteration:
-//   Ap = A p with the p.Ap partials | sum + alpha | r -= alpha Ap with term 0 in registers, partials of r.r |
-//   sum of r.r + verdict (history, stopping test; the verdict also lands in a device flag) |
-//   k steps, each testing that flag before it works: the converging iteration streams nothing |
-//   sum of r.z + beta | x += alpha p, p = z + beta p (the "none" x/p kernel with z where it reads r)
-// On stencil5-csr / row-lds a step is ONE launch (spmv_kernels.hip, kMode 3: A z never leaves the registers, z' goes to a second
-// vector): 144 + 88 k bytes per interior row and iteration. Everywhere else it is the operator's SpMV and one streaming kernel
-// (112 per step). The Jacobi and "none" loops above are untouched by this kind: it has its own loop function.
+//   r -= alpha Ap with term 0 in registers, partials of r.r | sum of r.r + verdict, which also lands in a device flag |
+//   k steps, each testing that flag before it works: the converging iteration streams nothing | sum of r.z + beta
+// A step is cheb_step (declared in precond.hpp), the only place that chooses its form from a ChebSpmv: on a row-lds stencil plan ONE
+// launch (spmv_kernels.hip, kMode 3: A z never leaves the registers, z' goes to a second vector; 144 + 88 k bytes per interior row and
+// iteration), on any other stencil plan the SpMV behind the flag + cheb_step_kernel, else run_device + cheb_step_kernel (112 per
+// step). The loop calls it timed, with the flag and the step counter; spmv_amd_precond_apply_device untimed without a flag; the
+// multigrid cycle on each of its levels.
 //
-// Kind "multigrid" (multigrid.hip; stencil5-csr only): z = M^-1 r is one V-cycle on the preconditioner's own levels.
-// Its iteration:
-//   Ap = A p with the p.Ap partials | sum + alpha | r -= alpha Ap with the r.r partials (the "none" r update) | sum of r.r + verdict |
-//   the host reads the verdict: the converging iteration runs no cycle | V-cycle | sum of r.z + beta | x += alpha p, p = z + beta p
-// The set-up passes and the Chebyshev kernels above reach multigrid.hip through precond.hpp.
+// "multigrid" (mg_first, mg_next): z = M^-1 r is one V-cycle on the preconditioner's own levels:
+//   r -= alpha Ap with the r.r partials (the "none" r update) | sum of r.r + verdict | the host reads the verdict: the converging
+//   iteration runs no cycle | V-cycle | sum of r.z + beta
+//
+// Also here: the set-up passes (diagonal, Gershgorin bound), the creators with their one operator check (creation_source) and the one
+// sentence about a bad diagonal row (inverse_diagonal); multigrid.hip reaches them through precond.hpp.
 #include <limits.h>
 #include <math.h>
 #include <stddef.h>
@@ -525,46 +530,50 @@ void launch_cheb_term0(size_t n, const PcgScalars* s, const double* b, const dou
     hipLaunchKernelGGL(cheb_term0_kernel<kFrom>, grid, block, 0, kStream, n, s, b, Ap, dinv, c0, r, d, z, last ? 1 : 0, partials, (int)grid.x);
 }
 
-// Steps 1 .. degree of one application on top of term 0 (d, and z in *z_a). z_b: the second z vector of the fused step; w: where the
-// unfused step's SpMV writes A z. Returns the vector that holds z afterwards (z_a or z_b) and sets *rz_count to the r.z partials
-// written at `partials` (degree 0: nothing is launched, term 0 wrote them behind its r.r partials). spmv / blas: how the caller
-// runs (and times) a launch of each class. *failed is set when the operator's run_device refuses.
-template <class RunSpmv, class RunBlas>
-double* cheb_run_steps(SpmvOperator* op, const ChebSpmv& c, const SpmvAmdPrecond* m, size_t n, const double* r, double* d, double* z_a,
-                       double* z_b, double* w, double* partials, const int* stop, int* work_count, int* rz_count, bool* failed,
-                       RunSpmv&& spmv, RunBlas&& blas) {
-    double *z = z_a, *z_next = z_b;
-    for (int k = 1; k <= m->degree && !*failed; ++k) {
-        const double h = m->coef[2 * k - 1], g = m->coef[2 * k];
-        const int last = k == m->degree ? 1 : 0;
-        if (c.fused_step != nullptr) {
-            ChebStep step;
-            step.r = r, step.dinv = m->dinv, step.d = d, step.z_out = z_next, step.g = g, step.h = h, step.last = last;
-            step.work_count = work_count;
-            spmv([&] {
-                const int slots = c.fused_step(z, &step, partials, stop, kStream);
-                if (last) *rz_count = slots;
-            });
-            double* const t = z;
-            z = z_next, z_next = t;
-        } else {
-            spmv([&] {
-                if (c.spmv_if != nullptr) {
-                    (void)c.spmv_if(z, w, stop, kStream);
-                } else if (op->run_device(z, w) != 0) {
-                    fprintf(stderr, "[PCG] operator '%s': run_device failed\n", op->name);
-                    *failed = true;
-                }
-            });
-            if (*failed) break;
-            blas([&] {
-                hipLaunchKernelGGL(cheb_step_kernel, dim3(stream_grid(n)), dim3(kWave), 0, kStream, n, stop, w, r, m->dinv, g, h, d, z, last,
-                                   partials, work_count);
-            });
-            if (last) *rz_count = (int)stream_grid(n);
-        }
+}  // namespace
+
+// The runner of a Chebyshev step (precond.hpp, ChebRun): the loop, spmv_amd_precond_apply_device and the multigrid cycle call it.
+bool spmv_amd::cheb_step(ChebRun& c, double g, double h, bool last) {
+    if (c.a.partials > 0) {  // a row-lds plan: the whole step inside the SpMV launch, z' in the other vector
+        ChebStep step;
+        step.r = c.r, step.dinv = c.dinv, step.d = c.d, step.z_out = c.aux, step.g = g, step.h = h, step.last = last ? 1 : 0;
+        step.work_count = c.work_count;
+        stage_run(c.T, &StageTimers::t_spmv, [&] { (void)launch_stencil5_cheb_step(*c.a.view, *c.a.plan, c.z, step, c.partials, c.stop, kStream); });
+        double* const t = c.z;
+        c.z = c.aux, c.aux = t;
+        if (last) c.rz_partials = c.partials, c.rz_count = c.a.partials;
+        return true;
     }
-    return z;
+    bool ok = true;
+    stage_run(c.T, &StageTimers::t_spmv, [&] {
+        if (c.a.plan != nullptr) {
+            (void)launch_stencil5_spmv(*c.a.view, *c.a.plan, c.z, c.aux, 1.0, nullptr, c.stop, false, kStream);
+        } else if (c.a.op->run_device(c.z, c.aux) != 0) {
+            fprintf(stderr, "[PCG] operator '%s': run_device failed\n", c.a.op->name);
+            ok = false;
+        }
+    });
+    if (!ok) return false;
+    stage_run(c.T, &StageTimers::t_blas, [&] {
+        hipLaunchKernelGGL(cheb_step_kernel, dim3(stream_grid(c.n)), dim3(kWave), 0, kStream, c.n, c.stop, c.aux, c.r, c.dinv, g, h, c.d, c.z,
+                           last ? 1 : 0, c.partials, c.work_count);
+    });
+    if (last) c.rz_partials = c.partials, c.rz_count = (int)stream_grid(c.n);
+    return true;
+}
+
+bool spmv_amd::cheb_steps(ChebRun& c, int degree, const double* coef, bool report) {
+    for (int k = 1; k <= degree; ++k)
+        if (!cheb_step(c, coef[2 * k], coef[2 * k - 1], report && k == degree)) return false;
+    return true;
+}
+
+namespace {
+
+// Steps 1 .. degree of m's polynomial behind a term 0 that left d and z in c -- and, at degree 0, the r.z partials behind its r.r ones.
+bool cheb_after_term0(const SpmvAmdPrecond* m, ChebRun& c) {
+    c.rz_partials = c.partials + stream_grid(c.n), c.rz_count = (int)stream_grid(c.n);
+    return cheb_steps(c, m->degree, m->coef, true);
 }
 
 // ---- workspace: kept between calls (like cg_solve_device's), released with it ----
@@ -657,9 +666,9 @@ int kind_of(const char* kind) {
     return -1;
 }
 
-// The diagonal pass over a diagonal source: dinv on the device, or null (*bad = the first offending row, -1: no device memory).
-double* inverse_diagonal(int src, const SlabCsr& m, const int* idx, const double* val, int width, int n, int* bad_out) {
-    *bad_out = -1;
+// The diagonal pass over a diagonal source: dinv on the device, or null -- no device memory, or a row at fault: the first one is named on
+// stderr behind `who` (the only place of that sentence) and stored in *bad_row where that is not null.
+double* inverse_diagonal(int src, const SlabCsr& m, const int* idx, const double* val, int width, int n, const char* who, int* bad_row) {
     double* dinv = device_try_alloc<double>((size_t)n);
     int* d_bad = device_try_alloc<int>(1);
     if (dinv == nullptr || d_bad == nullptr) {
@@ -677,7 +686,8 @@ double* inverse_diagonal(int src, const SlabCsr& m, const int* idx, const double
     device_release(d_bad);
     if (bad != none) {
         device_release(dinv);
-        *bad_out = bad;
+        if (bad_row != nullptr) *bad_row = bad;
+        fprintf(stderr, "[PCG] %s: the diagonal entry of row %d is zero, not finite or of the other sign than row 0's: refused\n", who, bad);
         return nullptr;
     }
     return dinv;
@@ -685,15 +695,8 @@ double* inverse_diagonal(int src, const SlabCsr& m, const int* idx, const double
 
 // The validity pass over a diagonal source; returns the preconditioner or null (*bad_row set when a row is at fault).
 SpmvAmdPrecond* make_jacobi(int src, const SlabCsr& m, const int* idx, const double* val, int width, int n, int* bad_row) {
-    int bad = -1;
-    double* dinv = inverse_diagonal(src, m, idx, val, width, n, &bad);
-    if (dinv == nullptr) {
-        if (bad >= 0) {
-            if (bad_row != nullptr) *bad_row = bad;
-            fprintf(stderr, "[PCG] jacobi: the diagonal entry of row %d is zero, not finite or of the other sign than row 0's: refused\n", bad);
-        }
-        return nullptr;
-    }
+    double* dinv = inverse_diagonal(src, m, idx, val, width, n, "jacobi", bad_row);
+    if (dinv == nullptr) return nullptr;
     SpmvAmdPrecond* pm = new SpmvAmdPrecond();
     pm->kind = kJacobi;
     pm->n = n;
@@ -730,20 +733,8 @@ extern "C" SpmvAmdPrecond* spmv_amd_precond_create(SpmvOperator* op, const char*
         return nullptr;
     }
     if (op == nullptr) return fail("null operator"), nullptr;
-    const DiagonalSource d = diagonal_source_of(op);
-    if (d.owner == nullptr) {
-        fprintf(stderr, "[PCG] operator '%s' is not one of this library's: pass its diagonal to spmv_amd_precond_create_from_diagonal\n",
-                op->name ? op->name : "?");
-        return nullptr;
-    }
-    if (!d.ready) {
-        fprintf(stderr, "[PCG] operator '%s' used before init\n", op->name);
-        return nullptr;
-    }
-    if (d.rows != d.cols) {
-        fprintf(stderr, "[PCG] operator '%s' holds a %d x %d matrix: a square one is required\n", op->name, d.rows, d.cols);
-        return nullptr;
-    }
+    DiagonalSource d;
+    if (!creation_source(op, "", "one of this library's: pass its diagonal to spmv_amd_precond_create_from_diagonal", false, &d)) return nullptr;
     SpmvAmdPrecond* pm = nullptr;
     if (k == kNone) {
         pm = new SpmvAmdPrecond();
@@ -781,29 +772,45 @@ void spmv_amd::chebyshev_coefficients(int degree, double lmin, double lmax, doub
     }
 }
 
-// pcg.hip's set-up passes and Chebyshev kernels for multigrid.hip (precond.hpp)
+// pcg.hip's set-up passes, the creators' operator check and term 0 for multigrid.hip (precond.hpp)
 namespace spmv_amd {
-double* inverse_diagonal_of_csr(const SlabCsr& m, int n, int* bad_row) { return inverse_diagonal(0, m, nullptr, nullptr, 0, n, bad_row); }
+double* inverse_diagonal_of_csr(const SlabCsr& m, int n, const char* who, int* bad_row) {
+    return inverse_diagonal(0, m, nullptr, nullptr, 0, n, who, bad_row);
+}
 double gershgorin_of_csr(const SlabCsr& m, int n, const double* dinv) { return gershgorin_bound(0, m, nullptr, nullptr, 0, n, dinv); }
 void launch_cheb_term0_apply(size_t n, const double* r, const double* dinv, double c0, double* d, double* z) {
     launch_cheb_term0<2>(n, nullptr, nullptr, nullptr, dinv, c0, const_cast<double*>(r), d, z, false, nullptr);
 }
-void launch_cheb_step(size_t n, const double* w, const double* r, const double* dinv, double g, double h, double* d, double* z, bool last,
-                      double* partials) {
-    hipLaunchKernelGGL(cheb_step_kernel, dim3(stream_grid(n)), dim3(kWave), 0, kStream, n, (const int*)nullptr, w, r, dinv, g, h, d, z, last ? 1 : 0,
-                       partials, (int*)nullptr);
+bool creation_source(const SpmvOperator* op, const char* label, const char* not_ours, bool stencil_only, DiagonalSource* d) {
+    *d = diagonal_source_of(op);
+    bool ours = d->owner != nullptr;
+    if (stencil_only)
+        ours = ours && d->kind == DiagonalSource::Csr && op->name != nullptr &&
+               (strcmp(op->name, "stencil5-csr") == 0 || strcmp(op->name, "stencil5-halo-mgpu") == 0);
+    if (!ours) {
+        fprintf(stderr, "[PCG] %soperator '%s' is not %s\n", label, op->name ? op->name : "?", not_ours);
+        return false;
+    }
+    if (!d->ready) {
+        fprintf(stderr, "[PCG] operator '%s' used before init\n", op->name);
+        return false;
+    }
+    if (!stencil_only && d->rows != d->cols) {  // a stencil-only creator has a stricter test of its own behind this
+        fprintf(stderr, "[PCG] operator '%s' holds a %d x %d matrix: a square one is required\n", op->name, d->rows, d->cols);
+        return false;
+    }
+    return true;
 }
 }  // namespace spmv_amd
 
 namespace {
-// What every entry point that takes (op, m) checks of the pair before any HIP call; *d: the operator's storage view.
-bool precond_matches(const SpmvOperator* op, const SpmvAmdPrecond* m, DiagonalSource* d) {
-    *d = diagonal_source_of(op);
+// What every entry point that takes (op, m) checks of the pair before any HIP call; d: the operator's storage view.
+bool precond_matches(const SpmvOperator* op, const SpmvAmdPrecond* m, const DiagonalSource& d) {
     if (m->owner == nullptr) return true;  // made from a caller's diagonal: no operator to belong to
-    if (m->owner != d->owner) return fail("the preconditioner was made from another operator: refused");
-    if (m->generation != d->generation)
+    if (m->owner != d.owner) return fail("the preconditioner was made from another operator: refused");
+    if (m->generation != d.generation)
         return fail("the preconditioner was made before the operator was last initialised or freed: refused");
-    if (!d->ready) {
+    if (!d.ready) {
         fprintf(stderr, "[PCG] operator '%s' used before init\n", op->name);
         return false;
     }
@@ -821,19 +828,8 @@ extern "C" SpmvAmdPrecond* spmv_amd_precond_create_chebyshev(SpmvOperator* op, i
     }
     if (!isfinite(lambda_min) || !isfinite(lambda_max)) return fail("chebyshev: a bound that is not finite: refused"), nullptr;
     if (lambda_min > 0.0 && lambda_max > 0.0 && !(lambda_min < lambda_max)) return fail("chebyshev: lambda_min >= lambda_max: refused"), nullptr;
-    const DiagonalSource d = diagonal_source_of(op);
-    if (d.owner == nullptr) {
-        fprintf(stderr, "[PCG] chebyshev: operator '%s' is not one of this library's: refused\n", op->name ? op->name : "?");
-        return nullptr;
-    }
-    if (!d.ready) {
-        fprintf(stderr, "[PCG] operator '%s' used before init\n", op->name);
-        return nullptr;
-    }
-    if (d.rows != d.cols) {
-        fprintf(stderr, "[PCG] operator '%s' holds a %d x %d matrix: a square one is required\n", op->name, d.rows, d.cols);
-        return nullptr;
-    }
+    DiagonalSource d;
+    if (!creation_source(op, "chebyshev: ", "one of this library's: refused", false, &d)) return nullptr;
     const int src = d.kind == DiagonalSource::Csr ? 0 : 1;
     SpmvAmdPrecond* pm = make_jacobi(src, d.csr, d.idx, d.val, d.width, d.rows, bad_row);
     if (pm == nullptr) return nullptr;
@@ -876,22 +872,22 @@ extern "C" int spmv_amd_precond_apply_device(SpmvOperator* op, const SpmvAmdPrec
         const uintptr_t a = (uintptr_t)d_r, b = (uintptr_t)d_z, bytes = n * sizeof(double);
         if (a < b + bytes && b < a + bytes) return fail("apply: d_z overlaps d_r: refused"), 1;
     }
-    DiagonalSource d;
-    if (!precond_matches(op, m, &d)) return 1;
-    const bool cheb = m->kind == kChebyshev;
-    const bool mg = m->kind == kMultigrid;
+    const DiagonalSource d = diagonal_source_of(op);
+    if (!precond_matches(op, m, d)) return 1;
+    const bool jac = m->kind == kJacobi, cheb = m->kind == kChebyshev, mg = m->kind == kMultigrid;  // which application runs below
     if ((cheb || mg) && (op->run_device == nullptr || d.owner == nullptr || d.rows != m->n || d.cols != m->n))
         return fail("apply: the operator is not the initialised square one the preconditioner was made from: refused"), 1;
 
     CgWorkspaceScope scope;
     const int vec_count = (int)stream_grid(n);
-    const ChebSpmv c = cheb ? cheb_spmv_of(op) : ChebSpmv{};
-    const long long slots = 2LL * vec_count > c.partials ? 2LL * vec_count : (long long)c.partials;
+    ChebRun c;  // kind "chebyshev": the application on temporaries of this call
+    if (cheb) c.a = cheb_spmv_of(op);
+    const long long slots = 2LL * vec_count > c.a.partials ? 2LL * vec_count : (long long)c.a.partials;
     double* partials = device_try_alloc<double>((size_t)slots);
     ChebScalars* cs = device_try_alloc<ChebScalars>(1);
     double* stage = reduce_scratch_alloc();
     double *cd = nullptr, *cz2 = nullptr, *cw = nullptr;
-    const bool fused = cheb && c.fused_step != nullptr;
+    const bool fused = c.a.partials > 0;
     bool ok = partials != nullptr && cs != nullptr;
     if (ok && cheb) {
         cd = device_try_alloc<double>(n);
@@ -904,33 +900,30 @@ extern "C" int spmv_amd_precond_apply_device(SpmvOperator* op, const SpmvAmdPrec
         fail("apply: the work vectors could not be allocated: refused");
     } else {
         HIP_CHECK(hipMemsetAsync(cs, 0, sizeof(ChebScalars), kStream));
-        int rz_count = vec_count;
-        const double* rz_partials = partials;
-        bool failed = false;
+        Applied out;  // null z: refused
         if (mg) {
-            const MgCycleResult cycle = mg_cycle(m->mg, d_r, nullptr);
-            HIP_CHECK(hipMemcpyAsync(d_z, cycle.z, n * sizeof(double), hipMemcpyDeviceToDevice, kStream));
-            rz_partials = cycle.rz_partials, rz_count = cycle.rz_count;
-        } else if (!cheb) {
-            const dim3 grid((unsigned)vec_count), block(kWave);
-            if (m->kind == kJacobi) hipLaunchKernelGGL(precond_apply_kernel<true>, grid, block, 0, kStream, n, d_r, m->dinv, d_z, partials);
-            else hipLaunchKernelGGL(precond_apply_kernel<false>, grid, block, 0, kStream, n, d_r, nullptr, d_z, partials);
-        } else {
+            out = mg_cycle(m->mg, d_r, nullptr);
+            HIP_CHECK(hipMemcpyAsync(d_z, out.z, n * sizeof(double), hipMemcpyDeviceToDevice, kStream));
+        } else if (cheb) {
             // the fused step alternates between two z vectors: start where an application of this degree ends in d_z
-            double* const z0 = fused && (m->degree & 1) ? cz2 : d_z;
-            double* const z1 = z0 == d_z ? cz2 : d_z;
-            launch_cheb_term0<2>(n, &cs->s, nullptr, nullptr, m->dinv, m->coef[0], const_cast<double*>(d_r), cd, z0, m->degree == 0, partials);
-            rz_partials = partials + vec_count;
-            const auto now = [](auto&& launch) { launch(); };
-            int steps_count = 0;
-            double* const z_end = cheb_run_steps(op, c, m, n, d_r, cd, z0, z1, cw, partials, nullptr, nullptr, &steps_count, &failed, now, now);
-            if (m->degree > 0) rz_partials = partials, rz_count = steps_count;
-            if (!failed && z_end != d_z) failed = true, fail("apply: internal error, the result is not in d_z");
+            c.n = n, c.r = d_r, c.dinv = m->dinv, c.d = cd, c.partials = partials;
+            c.z = fused && (m->degree & 1) ? cz2 : d_z;
+            c.aux = !fused ? cw : c.z == d_z ? cz2 : d_z;
+            launch_cheb_term0<2>(n, &cs->s, nullptr, nullptr, m->dinv, m->coef[0], const_cast<double*>(d_r), cd, c.z, m->degree == 0, partials);
+            if (cheb_after_term0(m, c)) {
+                if (c.z == d_z) out.z = d_z, out.rz_partials = c.rz_partials, out.rz_count = c.rz_count;
+                else fail("apply: internal error, the result is not in d_z");
+            }
+        } else {
+            const dim3 grid((unsigned)vec_count), block(kWave);
+            if (jac) hipLaunchKernelGGL(precond_apply_kernel<true>, grid, block, 0, kStream, n, d_r, m->dinv, d_z, partials);
+            else hipLaunchKernelGGL(precond_apply_kernel<false>, grid, block, 0, kStream, n, d_r, nullptr, d_z, partials);
+            out.z = d_z, out.rz_partials = partials, out.rz_count = vec_count;
         }
-        if (failed) {
+        if (out.z == nullptr) {
             rc = 1;
         } else {
-            launch_pcg_reduce(rz_partials, rz_count, 1, 5, stage, &cs->s, 0.0, nullptr, 0);
+            launch_pcg_reduce(out.rz_partials, out.rz_count, 1, 5, stage, &cs->s, 0.0, nullptr, 0);
             HIP_CHECK(hipGetLastError());
             PcgScalars h{};
             download(&h, &cs->s, 1);  // synchronises
@@ -971,6 +964,129 @@ extern "C" int spmv_amd_precond_inverse_diagonal(const SpmvAmdPrecond* m, double
     return 0;
 }
 
+namespace {
+
+// ---- the loop's per-kind units ----
+// What the units of one solve share: the solve's arguments, its workspace and timers, and what the host knows of its state.
+struct PcgLoop {
+    const SpmvOperator* op;
+    const SpmvAmdPrecond* m;
+    size_t n;
+    int vec_count;  // partials of a streaming kernel
+    double tol;
+    ChebSpmv a;     // how the operator runs A z for a Chebyshev step
+    PcgWorkspace& w;
+    StageTimers& T;
+    bool failed = false;          // the operator's run_device refused
+    PcgScalars h{};               // the host's copy of the device scalars
+    int cycles = 0;               // kind "multigrid": V-cycles of the loop
+    int* step_counter = nullptr;  // kind "chebyshev": the device count of its loop's step launches that did work
+
+    ChebScalars* record() const { return reinterpret_cast<ChebScalars*>(w.s); }
+    template <class F>
+    void blas(F&& launch) { T.run(&T.t_blas, launch); }
+    void reduce_at(const double* partials, int count, int nv, int which) {
+        T.run(&T.t_red, [&] { launch_pcg_reduce(partials, count, nv, which, w.stage, w.s, tol, w.hist, w.hist_cap); });
+    }
+    void reduce(int count, int nv, int which) { reduce_at(w.partials, count, nv, which); }
+    template <class F>
+    void spmv(F&& launch) { T.run(&T.t_spmv, launch); }
+    void run_A(const double* in, double* out) {  // out = A in through the vtable
+        if (op->run_device(in, out) != 0) {
+            fprintf(stderr, "[PCG] operator '%s': run_device failed\n", op->name);
+            failed = true;
+        }
+    }
+    // z0 = M^-1 r0 is the first direction
+    void first_direction(const double* z0) { HIP_CHECK(hipMemcpyAsync(w.p, z0, n * sizeof(double), hipMemcpyDeviceToDevice, kStream)); }
+};
+
+// One unit per kind. first: everything before the loop -- r0 = b - A x0, ||r0||, z0 = M^-1 r0, r0.z0, p0 = z0. next: what lies between
+// the sum of p.Ap and the x / p update -- r -= alpha Ap, ||r|| with the verdict, z = M^-1 r, beta -- and returns the vector the x / p
+// update reads (with dinv inside the kernel where jac is set), or null when the operator's run_device refused.
+struct PcgKind {
+    bool jac;
+    bool vectors;  // d, z and z' join the workspace (ensure_cheb_workspace)
+    void (*first)(PcgLoop&);
+    const double* (*next)(PcgLoop&);
+};
+
+// "none" / "jacobi": z stays in the kernels' registers, r.r and r.z are summed in one launch
+template <bool kJac>
+void plain_first(PcgLoop& L) {
+    PcgWorkspace& w = L.w;
+    L.spmv([&] { L.run_A(w.x, w.Ap); });
+    L.blas([&] { launch_pcg_init(kJac, L.n, w.b, w.Ap, L.m->dinv, w.r, w.p, w.partials); });
+    L.reduce(L.vec_count, 2, 0);
+}
+template <bool kJac>
+const double* plain_next(PcgLoop& L) {
+    PcgWorkspace& w = L.w;
+    L.blas([&] { launch_pcg_update_r(kJac, L.n, w.s, w.Ap, L.m->dinv, w.r, w.partials); });
+    L.reduce(L.vec_count, 2, 2);
+    return w.r;
+}
+
+// "chebyshev": term 0 rides on the r update; the steps behind it test the verdict on the device (first: no flag, none is up yet)
+const double* cheb_steps_and_rz(PcgLoop& L, const int* stop, int* work_count, int which) {
+    PcgWorkspace& w = L.w;
+    ChebRun c;
+    c.a = L.a, c.n = L.n, c.r = w.r, c.dinv = L.m->dinv, c.d = w.cd, c.z = w.cz, c.aux = L.a.partials > 0 ? w.cz2 : w.Ap;
+    c.partials = w.partials, c.stop = stop, c.work_count = work_count, c.T = &L.T;
+    if (L.failed || !cheb_after_term0(L.m, c)) return L.failed = true, nullptr;
+    L.reduce_at(c.rz_partials, c.rz_count, 1, which);
+    return c.z;
+}
+void cheb_first(PcgLoop& L) {
+    PcgWorkspace& w = L.w;
+    HIP_CHECK(hipMemsetAsync(L.record(), 0, sizeof(ChebScalars), kStream));
+    L.step_counter = &L.record()->steps_done;
+    L.spmv([&] { L.run_A(w.x, w.Ap); });
+    L.blas([&] { launch_cheb_term0<0>(L.n, w.s, w.b, w.Ap, L.m->dinv, L.m->coef[0], w.r, w.cd, w.cz, L.m->degree == 0, w.partials); });
+    L.reduce(L.vec_count, 1, 0);
+    const double* const z0 = cheb_steps_and_rz(L, nullptr, nullptr, 5);
+    if (z0 != nullptr) L.first_direction(z0);
+}
+const double* cheb_next(PcgLoop& L) {
+    PcgWorkspace& w = L.w;
+    L.blas([&] { launch_cheb_term0<1>(L.n, w.s, nullptr, w.Ap, L.m->dinv, L.m->coef[0], w.r, w.cd, w.cz, L.m->degree == 0, w.partials); });
+    L.reduce(L.vec_count, 1, 3);  // r.r and the verdict: the steps test it on the device
+    return cheb_steps_and_rz(L, &L.record()->stop, L.step_counter, 4);
+}
+
+// "multigrid": the "none" r update, then one V-cycle on r (multigrid.hip) unless the host reads a verdict that ends the solve
+const double* mg_cycle_and_rz(PcgLoop& L, int which) {
+    const Applied cycle = mg_cycle(L.m->mg, L.w.r, &L.T);
+    L.reduce_at(cycle.rz_partials, cycle.rz_count, 1, which);
+    return cycle.z;
+}
+void mg_first(PcgLoop& L) {
+    PcgWorkspace& w = L.w;
+    HIP_CHECK(hipMemsetAsync(L.record(), 0, sizeof(ChebScalars), kStream));
+    L.spmv([&] { L.run_A(w.x, w.Ap); });
+    L.blas([&] { launch_pcg_init(false, L.n, w.b, w.Ap, nullptr, w.r, w.p, w.partials); });
+    L.reduce(L.vec_count, 1, 0);
+    if (!L.failed) L.first_direction(mg_cycle_and_rz(L, 5));
+}
+const double* mg_next(PcgLoop& L) {
+    PcgWorkspace& w = L.w;
+    L.blas([&] { launch_pcg_update_r(false, L.n, w.s, w.Ap, nullptr, w.r, w.partials); });
+    L.reduce(L.vec_count, 1, 3);  // r.r and the verdict
+    download(&L.h, w.s, 1);       // the host reads it first: the converging iteration runs no cycle
+    if (L.h.converged || L.h.breakdown) return mg_result_vector(L.m->mg);
+    ++L.cycles;
+    return mg_cycle_and_rz(L, 4);
+}
+
+PcgKind pcg_kind_of(const SpmvAmdPrecond* m) {
+    if (m->kind == kMultigrid) return {false, false, mg_first, mg_next};
+    if (m->kind == kChebyshev) return {false, true, cheb_first, cheb_next};
+    if (m->kind == kJacobi) return {true, false, plain_first<true>, plain_next<true>};
+    return {false, false, plain_first<false>, plain_next<false>};
+}
+
+}  // namespace
+
 extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, const double* b, double* x,
                                          const CGConfig* config, CGStats* stats) {
     // argument checks: all before the first HIP call
@@ -998,14 +1114,10 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
         fprintf(stderr, "[PCG] the preconditioner is for %d rows, mat->rows = %d\n", m->n, mat->rows);
         return 1;
     }
-    if (m->owner != nullptr && m->owner != d.owner) return fail("the preconditioner was made from another operator: refused"), 1;
-    if (m->owner != nullptr && m->generation != d.generation)
-        return fail("the preconditioner was made before the operator was last initialised or freed: refused"), 1;
+    if (!precond_matches(op, m, d)) return 1;
     const int n = mat->rows;
     const CGConfig cfg = *config;
-    const bool jac = m->kind == kJacobi;
-    const bool cheb = m->kind == kChebyshev;
-    const bool mg = m->kind == kMultigrid;
+    const PcgKind kind = pcg_kind_of(m);
 
     CgWorkspaceScope scope;
     int device = 0;
@@ -1013,107 +1125,39 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
     const FusedSpmv f = fused_spmv_of(op);
     const bool fused = f.launch != nullptr && f.partials > 0;
     const int vec_count = (int)stream_grid((size_t)n);
-    const ChebSpmv c = cheb ? cheb_spmv_of(op) : ChebSpmv{};
+    const ChebSpmv a = kind.vectors ? cheb_spmv_of(op) : ChebSpmv{};
     long long partial_cap = 2LL * vec_count > f.partials ? 2LL * vec_count : (long long)f.partials;
-    if (c.partials > partial_cap) partial_cap = c.partials;
+    if (a.partials > partial_cap) partial_cap = a.partials;
     if (!ensure_workspace(n, device, partial_cap, cfg.max_iters + 1)) return 1;
-    if (cheb && !ensure_cheb_workspace(n)) return 1;
+    if (kind.vectors && !ensure_cheb_workspace(n)) return 1;
     PcgWorkspace& w = g_pcg;
-    ChebScalars* const cs = reinterpret_cast<ChebScalars*>(w.s);
     upload(w.b, b, (size_t)n);
     upload(w.x, x, (size_t)n);
 
     StageTimers T(cfg.enable_detailed_timers != 0, kStream);
-    bool op_failed = false;
-    auto reduce_at = [&](const double* partials, int count, int nv, int which) {
-        launch_pcg_reduce(partials, count, nv, which, w.stage, w.s, cfg.tolerance, w.hist, w.hist_cap);
-    };
-    auto reduce = [&](int count, int nv, int which) { reduce_at(w.partials, count, nv, which); };
-    auto run_op = [&](const double* in, double* out) {
-        if (op->run_device(in, out) != 0) {
-            fprintf(stderr, "[PCG] operator '%s': run_device failed\n", op->name);
-            op_failed = true;
-        }
-    };
-    PcgScalars h{};
+    PcgLoop L{op, m, (size_t)n, vec_count, cfg.tolerance, a, w, T};
+    PcgScalars& h = L.h;
 
     T.total.begin(kStream);
-    // kind "chebyshev": one application behind term 0 (the steps' SpMVs count as SpMV time); returns where z is and reduces r.z
-    const auto as_spmv = [&](auto&& launch) { T.run(&T.t_spmv, launch); };
-    const auto as_blas = [&](auto&& launch) { T.run(&T.t_blas, launch); };
-    auto cheb_steps_and_rz = [&](const int* stop, int* work_count, int which) -> double* {
-        int rz_count = vec_count;
-        double* const z = cheb_run_steps(op, c, m, (size_t)n, w.r, w.cd, w.cz, w.cz2, w.Ap, w.partials, stop, work_count, &rz_count, &op_failed,
-                                         as_spmv, as_blas);
-        if (!op_failed) T.run(&T.t_red, [&] { reduce_at(m->degree == 0 ? w.partials + vec_count : w.partials, rz_count, 1, which); });
-        return z;
-    };
-    // kind "multigrid": one V-cycle on r (multigrid.hip times its own launches) and the sum of the r.z partials its last update left
-    int mg_cycles = 0;
-    auto mg_cycle_and_rz = [&](int which) -> double* {
-        const MgCycleResult cycle = mg_cycle(m->mg, w.r, &T);
-        T.run(&T.t_red, [&] { reduce_at(cycle.rz_partials, cycle.rz_count, 1, which); });
-        return cycle.z;
-    };
-    if (mg) {
-        HIP_CHECK(hipMemsetAsync(cs, 0, sizeof(ChebScalars), kStream));
-        T.run(&T.t_spmv, [&] { run_op(w.x, w.Ap); });
-        T.run(&T.t_blas, [&] { launch_pcg_init(false, (size_t)n, w.b, w.Ap, nullptr, w.r, w.p, w.partials); });
-        T.run(&T.t_red, [&] { reduce(vec_count, 1, 0); });
-        if (!op_failed) {
-            const double* const z0 = mg_cycle_and_rz(5);
-            HIP_CHECK(hipMemcpyAsync(w.p, z0, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, kStream));
-        }
-    } else if (cheb) {
-        HIP_CHECK(hipMemsetAsync(cs, 0, sizeof(ChebScalars), kStream));
-        T.run(&T.t_spmv, [&] { run_op(w.x, w.Ap); });
-        T.run(&T.t_blas, [&] { launch_cheb_term0<0>((size_t)n, w.s, w.b, w.Ap, m->dinv, m->coef[0], w.r, w.cd, w.cz, m->degree == 0, w.partials); });
-        T.run(&T.t_red, [&] { reduce(vec_count, 1, 0); });
-        const double* const z0 = cheb_steps_and_rz(nullptr, nullptr, 5);
-        if (!op_failed) HIP_CHECK(hipMemcpyAsync(w.p, z0, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, kStream));
-    } else {
-        T.run(&T.t_spmv, [&] { run_op(w.x, w.Ap); });
-        T.run(&T.t_blas, [&] { launch_pcg_init(jac, (size_t)n, w.b, w.Ap, m->dinv, w.r, w.p, w.partials); });
-        T.run(&T.t_red, [&] { reduce(vec_count, 2, 0); });
-    }
+    kind.first(L);
     download(&h, w.s, 1);
     if (cfg.verbose >= 1)
         printf("[PCG-DEVICE] Initial residual: %e (preconditioner %s)\n", h.b_norm, spmv_amd_precond_kind(m));
-    for (int it = 0; it < cfg.max_iters && !op_failed && !h.converged && !h.breakdown; ++it) {
+    for (int it = 0; it < cfg.max_iters && !L.failed && !h.converged && !h.breakdown; ++it) {
         int pap_count = vec_count;
-        T.run(&T.t_spmv, [&] {
+        L.spmv([&] {  // Ap = A p with the p.Ap partials
             if (fused) {
                 pap_count = f.launch(w.p, w.Ap, w.partials, nullptr, false, nullptr, kStream);
             } else {
-                run_op(w.p, w.Ap);
+                L.run_A(w.p, w.Ap);
                 launch_dot_partials((size_t)n, w.p, w.Ap, w.partials, kStream);
             }
         });
-        if (op_failed) break;
-        T.run(&T.t_red, [&] { reduce(pap_count, 1, 1); });
-        if (mg) {
-            T.run(&T.t_blas, [&] { launch_pcg_update_r(false, (size_t)n, w.s, w.Ap, nullptr, w.r, w.partials); });
-            T.run(&T.t_red, [&] { reduce(vec_count, 1, 3); });  // r.r and the verdict
-            download(&h, w.s, 1);  // the host reads the verdict first: the converging iteration runs no cycle
-            const double* z = mg_result_vector(m->mg);
-            if (!h.converged && !h.breakdown) {
-                z = mg_cycle_and_rz(4);
-                ++mg_cycles;
-            }
-            T.run(&T.t_blas, [&] { launch_pcg_update_xp(false, (size_t)n, w.s, z, nullptr, w.p, w.x); });
-        } else if (cheb) {
-            T.run(&T.t_blas, [&] {
-                launch_cheb_term0<1>((size_t)n, w.s, nullptr, w.Ap, m->dinv, m->coef[0], w.r, w.cd, w.cz, m->degree == 0, w.partials);
-            });
-            T.run(&T.t_red, [&] { reduce(vec_count, 1, 3); });  // r.r and the verdict: the steps below test it on the device
-            const double* const z = cheb_steps_and_rz(&cs->stop, &cs->steps_done, 4);
-            if (op_failed) break;
-            T.run(&T.t_blas, [&] { launch_pcg_update_xp(false, (size_t)n, w.s, z, nullptr, w.p, w.x); });
-        } else {
-            T.run(&T.t_blas, [&] { launch_pcg_update_r(jac, (size_t)n, w.s, w.Ap, m->dinv, w.r, w.partials); });
-            T.run(&T.t_red, [&] { reduce(vec_count, 2, 2); });
-            T.run(&T.t_blas, [&] { launch_pcg_update_xp(jac, (size_t)n, w.s, w.r, m->dinv, w.p, w.x); });
-        }
+        if (L.failed) break;
+        L.reduce(pap_count, 1, 1);  // alpha = rz / pAp
+        const double* const z = kind.next(L);
+        if (z == nullptr) break;
+        L.blas([&] { launch_pcg_update_xp(kind.jac, (size_t)n, w.s, z, m->dinv, w.p, w.x); });
         download(&h, w.s, 1);  // synchronises: the stopping test
         if (cfg.verbose >= 2)
             printf("[PCG-DEVICE] Iter %3d: residual = %e (rel = %e)\n", h.iterations, h.residual, h.residual / h.b_norm);
@@ -1125,10 +1169,10 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
     const int count = h.iterations + 1 < w.hist_cap ? h.iterations + 1 : w.hist_cap;
     g_pcg_history.assign((size_t)count, 0.0);
     download(g_pcg_history.data(), w.hist, (size_t)count);
-    g_mg_cycles = mg_cycles;
+    g_mg_cycles = L.cycles;
     g_cheb_step_launches = 0;
-    if (cheb) download(&g_cheb_step_launches, &cs->steps_done, 1);
-    if (op_failed) return 1;
+    if (L.step_counter != nullptr) download(&g_cheb_step_launches, L.step_counter, 1);
+    if (L.failed) return 1;
 
     fill_device_stats(stats, h.iterations, h.converged != 0, h.residual, h.b_norm, cfg, total_ms, T.t_spmv, T.t_blas, T.t_red);
     solution_checksums(x, n, &stats->solution_sum, &stats->solution_norm);

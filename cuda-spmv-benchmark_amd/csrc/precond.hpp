@@ -1,6 +1,6 @@
 // precond.hpp -- what pcg.hip (the preconditioned loop, kinds "none", "jacobi", "chebyshev") and multigrid.hip (kind "multigrid",
-// DESIGN.md section 15) share: the preconditioner record, pcg.hip's set-up passes and Chebyshev kernels behind host launchers -- the
-// multigrid smoother IS section 14's application, run by the same kernels --, and the multigrid cycle the loop calls.
+// DESIGN.md section 15) share: the preconditioner record, pcg.hip's set-up passes, the runner of a Chebyshev step -- the multigrid
+// smoother IS section 14's application, run by the same function on a level's operator --, and the multigrid cycle the loop calls.
 #pragma once
 
 #include "device_runtime.hpp"
@@ -27,33 +27,64 @@ struct SpmvAmdPrecond {
 
 namespace spmv_amd {
 
-// ---- pcg.hip ----
-// dinv of a CSR by the diagonal pass (d_i = the sum of row i's entries in column i, CSR order, from 0.0; dinv_i = 1.0 / d_i) with its
-// validity rule. Returns the device array, or null: *bad_row >= 0 names the first offending row, -1 means no device memory (said on
-// stderr; the row sentence is the caller's). Synchronises.
-double* inverse_diagonal_of_csr(const SlabCsr& m, int n, int* bad_row);
-// The symmetric Gershgorin bound of D^-1/2 A D^-1/2 (pcg.hip, gershgorin_kernel). Synchronises.
-double gershgorin_of_csr(const SlabCsr& m, int n, const double* dinv);
-// c0, h_1, g_1, ... of the degree-k Chebyshev polynomial on [lmin, lmax] (api.h states the operations).
-void chebyshev_coefficients(int degree, double lmin, double lmax, double* coef);
-// term 0 from a residual that is only read: u = dinv r ; d = c0 u ; z = d (cheb_term0_kernel<2>, no partials)
-void launch_cheb_term0_apply(size_t n, const double* r, const double* dinv, double c0, double* d, double* z);
-// one step behind a SpMV that wrote w = A z (cheb_step_kernel): d and z in place; last: the partials of r.z at partials[blk],
-// stream_grid(n) of them
-void launch_cheb_step(size_t n, const double* w, const double* r, const double* dinv, double g, double h, double* d, double* z, bool last,
-                      double* partials);
-
-// ---- multigrid.hip ----
-void mg_destroy(MgHierarchy* h);
-// One V-cycle on the hierarchy's own vectors: z = M^-1 r, r (level 0's rows, 16-byte aligned) only read. z: where the result is (a
-// vector the hierarchy owns); rz_partials / rz_count: the partials of r.z the last post-smoothing update left. T (may be null): the
-// solve's timers -- launches that carry a SpMV count as SpMV time, the others as BLAS1 time.
-struct MgCycleResult {
+// Where an application z = M^-1 r left z and the partials of r.z (the Chebyshev runner's and the multigrid cycle's report).
+struct Applied {
     double* z = nullptr;
     const double* rz_partials = nullptr;
     int rz_count = 0;
 };
-MgCycleResult mg_cycle(MgHierarchy* h, const double* r, StageTimers* T);
+
+// One launch under a solve's timers (T null: untimed). A launch that carries a SpMV counts as SpMV time (t_spmv), every other as BLAS1.
+template <class F>
+void stage_run(StageTimers* T, double StageTimers::*acc, F&& launch) {
+    if (T != nullptr) T->run(&(T->*acc), launch);
+    else launch();
+}
+
+// ---- pcg.hip ----
+// dinv of a CSR by the diagonal pass (d_i = the sum of row i's entries in column i, CSR order, from 0.0; dinv_i = 1.0 / d_i) with its
+// validity rule. Returns the device array, or null: a row at fault is named on stderr behind `who` ("jacobi", "multigrid: level 2")
+// and, where bad_row is not null, stored there; no device memory is said too. Synchronises.
+double* inverse_diagonal_of_csr(const SlabCsr& m, int n, const char* who, int* bad_row);
+// The symmetric Gershgorin bound of D^-1/2 A D^-1/2 (pcg.hip, gershgorin_kernel). Synchronises.
+double gershgorin_of_csr(const SlabCsr& m, int n, const double* dinv);
+// c0, h_1, g_1, ... of the degree-k Chebyshev polynomial on [lmin, lmax] (api.h states the operations).
+void chebyshev_coefficients(int degree, double lmin, double lmax, double* coef);
+// What the creators check of their (non-null) operator, in this order, before the first HIP call: not one of this library's -- or,
+// stencil_only, not the stencil operator -- said as "[PCG] <label>operator '<name>' is not <not_ours>"; used before init; not square
+// (left to a stencil_only creator's stricter test behind this). False: refused, said on stderr.
+bool creation_source(const SpmvOperator* op, const char* label, const char* not_ours, bool stencil_only, DiagonalSource* d);
+// term 0 from a residual that is only read: u = dinv r ; d = c0 u ; z = d (cheb_term0_kernel<2>, no partials)
+void launch_cheb_term0_apply(size_t n, const double* r, const double* dinv, double c0, double* d, double* z);
+
+// One Chebyshev application in flight on one operator or level: t = fma(-1, A z, r) ; u = dinv t ; d = fma(g, u, h d) ; z = z + d.
+// cheb_step runs one step in the form `a` allows: on a row-lds plan the fused launch (z' goes to aux, then z and aux change places),
+// on any other stencil plan the SpMV that tests `stop` into aux and cheb_step_kernel, else run_device into aux and cheb_step_kernel.
+// last: the step also writes the partials of r.z to `partials` and records them in rz_partials / rz_count. False: run_device
+// refused (said on stderr). cheb_steps runs steps 1 .. degree from coef (c0, h_1, g_1, ...); report: step `degree` is a last one.
+struct ChebRun {
+    ChebSpmv a;
+    size_t n = 0;
+    const double* r = nullptr;
+    const double* dinv = nullptr;
+    double* d = nullptr;
+    double* z = nullptr;         // where z is: moves between the two vectors of a fused step
+    double* aux = nullptr;       // fused: the other z vector; else w = A z
+    double* partials = nullptr;  // a.partials slots (fused) or stream_grid(n) (cheb_step_kernel)
+    const int* stop = nullptr;   // device flag: nothing is read once it is set (null: no test)
+    int* work_count = nullptr;   // device counter of the step launches that did work (may be null)
+    StageTimers* T = nullptr;    // null: untimed
+    const double* rz_partials = nullptr;
+    int rz_count = 0;
+};
+bool cheb_step(ChebRun& c, double g, double h, bool last);
+bool cheb_steps(ChebRun& c, int degree, const double* coef, bool report);
+
+// ---- multigrid.hip ----
+void mg_destroy(MgHierarchy* h);
+// One V-cycle on the hierarchy's own vectors: z = M^-1 r, r (level 0's rows, 16-byte aligned) only read. z: a vector the hierarchy
+// owns; the r.z partials are the ones the last post-smoothing step left. T (may be null): the solve's timers.
+Applied mg_cycle(MgHierarchy* h, const double* r, StageTimers* T);
 double* mg_result_vector(MgHierarchy* h);  // a level-0 vector of the hierarchy (what a loop hands on when no cycle ran)
 
 }  // namespace spmv_amd

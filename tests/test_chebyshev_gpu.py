@@ -347,6 +347,40 @@ def test_degree_zero_is_jacobi_and_degree_four_cuts_iterations_threefold(B):
         op.free()
 
 
+def timers_change_no_bit(B, op, m, pc, b, x0, label):
+    """enable_detailed_timers = 1 (events between the launches) against the plain solve: x and the history bit for bit and the same
+    iteration count; the timed solve reports each of the three stage times > 0 and their sum <= the total, the plain one reports the
+    three as 0 (tests/test_pcg_gpu.py asserts the same of the Jacobi loop)."""
+    x, h, st = B.pcg_solve_device(op, m, pc, b, x0)
+    xt, ht, stt = B.pcg_solve_device(op, m, pc, b, x0, timers=1)
+    print(f"{label}: {st.iterations} iterations; timed: spmv {stt.time_spmv_ms:.3f} blas1 {stt.time_blas1_ms:.3f} "
+          f"reductions {stt.time_reductions_ms:.3f} of {stt.time_total_ms:.3f} ms")
+    assert np.array_equal(xt, x) and np.array_equal(ht, h) and stt.iterations == st.iterations and stt.converged == 1, label
+    assert st.time_spmv_ms == 0.0 and st.time_blas1_ms == 0.0 and st.time_reductions_ms == 0.0 and st.time_total_ms > 0.0, label
+    assert stt.time_spmv_ms > 0.0 and stt.time_blas1_ms > 0.0 and stt.time_reductions_ms > 0.0, label
+    assert stt.time_spmv_ms + stt.time_blas1_ms + stt.time_reductions_ms <= stt.time_total_ms, label
+
+
+@pytest.mark.parametrize("mode,n,rowlds_from", [("stencil5-csr", 130, 64), ("stencil5-csr", 130, None), ("ellpack", 65, None)])
+def test_detailed_timers_change_no_bit(B, monkeypatch, mode, n, rowlds_from):
+    """Degree 2 on the three forms of a step: the fused row-lds launch (the row-lds threshold lowered to 64), the stencil operator's
+    SpMV behind the device flag + the streaming step (the default threshold: row-direct), and run_device + the streaming step."""
+    if rowlds_from is not None:
+        monkeypatch.setenv("SPMV_AMD_ROWLDS_MIN_GRID", str(rowlds_from))
+    rows = n * n
+    A = P.stencil5(n, center=4.0)
+    m = B.HostMatrix(P.entries_of(A), rows, rows, n)
+    op = B.Operator(mode)
+    assert op.init(m) == 0
+    if mode == "stencil5-csr":
+        assert op.variant() == ("stencil5/row-lds" if rowlds_from is not None else "stencil5/row-direct")
+    pc = B.Precond.chebyshev(op, 2)
+    b = np.random.default_rng(n).standard_normal(rows)
+    timers_change_no_bit(B, op, m, pc, b, np.zeros(rows), f"{mode} {n} row-lds from {rowlds_from}")
+    pc.destroy()
+    op.free()
+
+
 @pytest.mark.parametrize("case", ["81:5.0", "81:-4.0", "512:5.0"])
 def test_golden_anchors_at_degree_zero(B, O, case):
     gold = json.load(open(os.path.join(GOLDEN, "known_answers.json")))["cases"][case]["cg"]

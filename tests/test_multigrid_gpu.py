@@ -12,8 +12,9 @@ import scipy.sparse as sp
 
 import multigrid_restatement as MG
 import pcg_restatement as P
+import reduction_restatement as RR
 from conftest import ROOT
-from test_chebyshev_gpu import GUARD, SUM_TOL, TOL, Guarded, stencil_random_values, ulps
+from test_chebyshev_gpu import GUARD, SUM_TOL, TOL, Guarded, stencil_random_values, timers_change_no_bit, ulps
 
 pytestmark = pytest.mark.gpu
 
@@ -283,6 +284,69 @@ def test_the_converging_iteration_runs_no_cycle(Blab):
     Blab.pcg_solve_device(op, m, jac, b, x0, max_iters=3)
     assert L.spmv_amd_pcg_last_multigrid_cycles() == 0
     jac.destroy()
+    pc.destroy()
+    op.free()
+
+
+@pytest.mark.parametrize("rowlds_from", [64, None])
+def test_detailed_timers_change_no_bit(B, monkeypatch, rowlds_from):
+    """nu = 1 on 130 -> 65 -> 33 -> ...: the cycle's launches under the solve's timers, with the fused step on the levels of 64 and
+    more (the row-lds threshold lowered to 64) and with the SpMV + the streaming step on every level (the default threshold)."""
+    if rowlds_from is not None:
+        monkeypatch.setenv("SPMV_AMD_ROWLDS_MIN_GRID", str(rowlds_from))
+    n = 130
+    rows = n * n
+    A = P.stencil5(n, center=4.0)
+    m = B.HostMatrix(P.entries_of(A), rows, rows, n)
+    op = B.Operator("stencil5-csr")
+    assert op.init(m) == 0
+    assert op.variant() == ("stencil5/row-lds" if rowlds_from is not None else "stencil5/row-direct")
+    pc = B.Precond.multigrid(op, 1)
+    assert pc.multigrid_info()[1] == [130, 65, 33, 17, 9, 5]
+    b = np.random.default_rng(n).standard_normal(rows)
+    timers_change_no_bit(B, op, m, pc, b, np.zeros(rows), f"multigrid 130 row-lds from {rowlds_from}")
+    pc.destroy()
+    op.free()
+
+
+# ---------------------------------------------------------------- the application and the loop
+@pytest.mark.parametrize("rowlds_from", [64, None])
+@pytest.mark.parametrize("kind", ["chebyshev:3", "multigrid:1"])
+def test_the_first_iteration_steps_along_the_application(B, O, monkeypatch, kind, rowlds_from):
+    """spmv_amd_precond_apply_device and the loop run the same application. From x0 = 0 with max_iters = 1 and tol = 0 the solve
+    returns x = alpha p0, p0 = M^-1 b, alpha = r0.z0 / p0.A p0: x / alpha equals apply(b) to 2 ulp per entry (one rounding in the
+    loop's multiply, one in the divide here). alpha itself is exact: both sums are restated bit for bit from the oracle's product
+    (tests/reduction_restatement.py) -- the r.z partials of the last step (the fused launch's slots on a row-lds plan, the streaming
+    step's elsewhere) and the p.Ap partials of the operator's SpMV."""
+    if rowlds_from is not None:
+        monkeypatch.setenv("SPMV_AMD_ROWLDS_MIN_GRID", str(rowlds_from))
+    n = 130
+    rows = n * n
+    e = stencil_random_values(n)
+    rp, ci, va = O.build_csr(e, rows)
+    m = B.HostMatrix(e, rows, rows, n)
+    op = B.Operator("stencil5-csr")
+    assert op.init(m) == 0
+    fused = rowlds_from is not None
+    assert op.variant() == ("stencil5/row-lds" if fused else "stencil5/row-direct")
+    name, arg = kind.split(":")
+    pc = B.Precond.chebyshev(op, int(arg)) if name == "chebyshev" else B.Precond.multigrid(op, int(arg))
+    b = np.random.default_rng(7).standard_normal(rows)
+    db, dz = Guarded(B, b), Guarded(B, np.full(rows, np.nan))
+    pc.apply_device(op, db.ptr, dz.ptr)
+    z = dz.read()
+    x, h, st = B.pcg_solve_device(op, m, pc, b, np.zeros(rows), max_iters=1, tol=0.0)
+    assert st.iterations == 1 and st.converged == 0 and len(h) == 2
+    Az = O.spmv_stencil5(rp, ci, va, z, n)
+    rz_partials = RR.rowlds_partials(b, z, n) if fused else RR.stream_partials(b, z)
+    pap_partials = RR.rowlds_partials(z, Az, n) if fused else RR.rowdirect_partials(z, Az, n)
+    rz = RR.reduce_pcg(rz_partials, len(rz_partials), 1)[0]
+    pap = RR.reduce_pcg(pap_partials, len(pap_partials), 1)[0]
+    alpha = rz / pap
+    err = float(np.max(np.abs(x / alpha - z) / np.spacing(np.abs(z))))
+    print(f"{kind} row-lds from {rowlds_from}: alpha {alpha!r}, x / alpha against apply(b): {err:.2f} ulp")
+    assert err <= 2.0, (kind, rowlds_from, err)
+    db.free(), dz.free()
     pc.destroy()
     op.free()
 
