@@ -1,6 +1,6 @@
 // app_common.hpp -- argv helpers shared by the three harness binaries. The binaries keep the
 // reference's command lines and add --stencil=N: the n x n generator matrix
-// built in memory instead of read from a .mtx file (a 20000^2 file is 48 GB of text).
+// built in memory instead of read from a .mtx file (a 20000^2 file is 48 GB of text), and --stencil3d=N: the n x n x n 7-point one.
 #pragma once
 
 #include <math.h>
@@ -50,6 +50,35 @@ inline bool make_stencil(int n, MatrixData* mat) {
             if (j < n - 1) e[k++] = Entry{id, id + 1, -1.0};
             if (i > 0) e[k++] = Entry{id, id - n, -1.0};
             if (i < n - 1) e[k++] = Entry{id, id + n, -1.0};
+        }
+    }
+    mat->rows = mat->cols = (int)rows;
+    mat->nnz = (int)nnz;
+    mat->grid_size = n;
+    mat->entries = e;
+    return true;
+}
+
+// The n x n x n 7-point generator matrix (centre 7, neighbours -1) as COO in write_matrix_market_stencil7's order
+// (C, W, E, N, S, D, U per grid point); grid_size = n, rows = n^3.
+inline bool make_stencil3d(int n, MatrixData* mat) {
+    if (n < 1 || n > 674) return false;  // rows and nnz inside int32
+    const long long nn = (long long)n * n, rows = nn * n, nnz = 7 * rows - 6 * nn;
+    Entry* e = (Entry*)malloc((size_t)nnz * sizeof(Entry));
+    if (!e) return false;
+    size_t q = 0;
+    for (int k = 0; k < n; ++k) {
+        for (int i = 0; i < n; ++i) {
+            for (int j = 0; j < n; ++j) {
+                const int id = (int)(k * nn + (long long)i * n + j);
+                e[q++] = Entry{id, id, 7.0};
+                if (j > 0) e[q++] = Entry{id, id - 1, -1.0};
+                if (j < n - 1) e[q++] = Entry{id, id + 1, -1.0};
+                if (i > 0) e[q++] = Entry{id, id - n, -1.0};
+                if (i < n - 1) e[q++] = Entry{id, id + n, -1.0};
+                if (k > 0) e[q++] = Entry{id, id - (int)nn, -1.0};
+                if (k < n - 1) e[q++] = Entry{id, id + (int)nn, -1.0};
+            }
         }
     }
     mat->rows = mat->cols = (int)rows;

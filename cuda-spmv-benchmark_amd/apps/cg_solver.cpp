@@ -51,7 +51,7 @@ int pcg_runs(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, const d
 
 int main(int argc, char** argv) {
     const char *matrix = nullptr, *modes_text = "stencil5-csr", *json = nullptr, *csv = nullptr, *precond = nullptr;
-    int stencil = 0, maxiter = 1000, timers = 0;
+    int stencil = 0, stencil3d = 0, maxiter = 1000, timers = 0;
     bool device = true;
     double tol = 1e-6;
     for (int i = 1; i < argc; ++i) {
@@ -59,6 +59,7 @@ int main(int argc, char** argv) {
         else if (const char* v2 = app::value_of(argv[i], "--json=")) json = v2;
         else if (const char* v3 = app::value_of(argv[i], "--csv=")) csv = v3;
         else if (const char* v4 = app::value_of(argv[i], "--stencil=")) stencil = atoi(v4);
+        else if (const char* v8 = app::value_of(argv[i], "--stencil3d=")) stencil3d = atoi(v8);
         else if (const char* v5 = app::value_of(argv[i], "--tol=")) tol = atof(v5);
         else if (const char* v6 = app::value_of(argv[i], "--maxiter=")) maxiter = atoi(v6);
         else if (const char* v7 = app::value_of(argv[i], "--precond=")) precond = v7;
@@ -67,8 +68,8 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--timers")) timers = 1;
         else if (argv[i][0] != '-') matrix = argv[i];
     }
-    if (!matrix && stencil <= 0) {
-        fprintf(stderr, "Usage: %s <matrix.mtx | --stencil=N> [--mode=<modes>] [--host|--device] [--tol=] [--maxiter=] [--timers] [--json=] [--csv=]\n", argv[0]);
+    if (!matrix && stencil <= 0 && stencil3d <= 0) {
+        fprintf(stderr, "Usage: %s <matrix.mtx | --stencil=N | --stencil3d=N> [--mode=<modes>] [--host|--device] [--tol=] [--maxiter=] [--timers] [--json=] [--csv=]\n", argv[0]);
         return 1;
     }
     int cheb_degree = -1;  // >= 0: --precond=chebyshev[:K]
@@ -110,7 +111,13 @@ int main(int argc, char** argv) {
         }
     }
     MatrixData mat;
-    if (stencil > 0 ? !app::make_stencil(stencil, &mat) : load_matrix_market(matrix, &mat) != 0) {
+    if (stencil3d > 674) {
+        fprintf(stderr, "Failed to build the %d^3 stencil (1 <= N <= 674)\n", stencil3d);
+        return 1;
+    }
+    if (stencil3d > 0  ? !app::make_stencil3d(stencil3d, &mat)
+        : stencil > 0 ? !app::make_stencil(stencil, &mat)
+                      : load_matrix_market(matrix, &mat) != 0) {
         fprintf(stderr, "Error loading matrix\n");
         return 1;
     }

@@ -1,33 +1,39 @@
 // spmv_bench -- counterpart of reference src/main/main.cu: x = 1, 5 warm-ups, 10 timed runs with
 // the >2 sigma / median rule, checksums, metrics, one JSON/CSV file per mode.
-//   spmv_bench <matrix.mtx | --stencil=N> --mode=<m1[,m2,...]> [--json=<file>] [--csv=<file>]
+//   spmv_bench <matrix.mtx | --stencil=N | --stencil3d=N> --mode=<m1[,m2,...]> [--json=<file>] [--csv=<file>]
 #include "app_common.hpp"
 
 int main(int argc, char** argv) {
     const char *matrix = nullptr, *modes_text = nullptr, *json = nullptr, *csv = nullptr;
-    int stencil = 0;
+    int stencil = 0, stencil3d = 0;
     for (int i = 1; i < argc; ++i) {
         if (const char* v = app::value_of(argv[i], "--mode=")) modes_text = v;
         else if (const char* v2 = app::value_of(argv[i], "--json=")) json = v2;
         else if (const char* v3 = app::value_of(argv[i], "--csv=")) csv = v3;
         else if (const char* v4 = app::value_of(argv[i], "--stencil=")) stencil = atoi(v4);
+        else if (const char* v5 = app::value_of(argv[i], "--stencil3d=")) stencil3d = atoi(v5);
         else if (argv[i][0] != '-') matrix = argv[i];
     }
-    if ((!matrix && stencil <= 0) || !modes_text) {
-        fprintf(stderr, "Usage: %s <matrix_file.mtx | --stencil=N> --mode=<mode1[,mode2,...]> [--json=<file>] [--csv=<file>]\n", argv[0]);
-        fprintf(stderr, "Available modes: cusparse-csr, stencil5-csr, ellpack, stencil5-ellpack\n");
+    if ((!matrix && stencil <= 0 && stencil3d <= 0) || !modes_text) {
+        fprintf(stderr, "Usage: %s <matrix_file.mtx | --stencil=N | --stencil3d=N> --mode=<mode1[,mode2,...]> [--json=<file>] [--csv=<file>]\n", argv[0]);
+        fprintf(stderr, "Available modes: cusparse-csr, stencil5-csr, stencil7-csr, ellpack, stencil5-ellpack\n");
         return EXIT_FAILURE;
     }
     const std::vector<std::string> modes = app::split_modes(modes_text);
     printf("Validating %zu mode(s): %s\n", modes.size(), modes_text);
     for (const std::string& m : modes) {
         if (get_operator(m.c_str()) == nullptr) {
-            fprintf(stderr, "Error: Unknown mode '%s'\nAvailable modes: cusparse-csr, stencil5-csr, ellpack, stencil5-ellpack\n", m.c_str());
+            fprintf(stderr, "Error: Unknown mode '%s'\nAvailable modes: cusparse-csr, stencil5-csr, stencil7-csr, ellpack, stencil5-ellpack\n", m.c_str());
             return EXIT_FAILURE;
         }
     }
     MatrixData mat;
-    if (stencil > 0) {
+    if (stencil3d > 0) {
+        if (!app::make_stencil3d(stencil3d, &mat)) {
+            fprintf(stderr, "Failed to build the %d^3 stencil (1 <= N <= 674)\n", stencil3d);
+            return EXIT_FAILURE;
+        }
+    } else if (stencil > 0) {
         if (!app::make_stencil(stencil, &mat)) {
             fprintf(stderr, "Failed to build the %dx%d stencil\n", stencil, stencil);
             return EXIT_FAILURE;

@@ -116,13 +116,13 @@ DECLARED_SYMBOLS = [
     "csr_mat", "ellpack_matrix", "build_ellpack_from_csr_local", "ensure_ellpack_structure_built", "get_operator",
     "calculate_spmv_metrics", "get_gpu_properties", "print_benchmark_metrics", "print_metrics_json", "print_metrics_csv",
     "read_matrix_type", "read_matrix_general", "read_matrix_symtogen", "load_matrix_market", "convert_csr_to_ellpack",
-    "write_matrix_market_stencil5", "benchmark_with_stats", "cg_benchmark_with_stats_device",
+    "write_matrix_market_stencil5", "write_matrix_market_stencil7", "benchmark_with_stats", "cg_benchmark_with_stats_device",
     "cg_benchmark_with_stats_mgpu_partitioned", "export_cg_json", "export_cg_mgpu_json", "export_cg_csv",
     "spmv_amd_build_csr_struct", "spmv_amd_build_ellpack_from_csr_struct", "spmv_amd_cg_solve", "spmv_amd_cg_solve_device",
     "spmv_amd_cg_solve_mgpu_partitioned", "spmv_amd_reset_host_matrices", "spmv_amd_interior_csr_offset",
     "spmv_amd_partition_rows", "spmv_amd_device_count", "spmv_amd_set_device", "spmv_amd_current_device", "spmv_amd_stream_ceiling", "spmv_amd_stream_ceiling_mix", "spmv_amd_device_alloc", "spmv_amd_device_free",
     "spmv_amd_copy_to_device", "spmv_amd_copy_to_host", "spmv_amd_device_fill_f64", "spmv_amd_device_synchronize",
-    "spmv_amd_init_stencil5_synthetic", "spmv_amd_ellpack_run_device_scaled", "spmv_amd_download_device_csr", "spmv_amd_time_run_device", "spmv_amd_operator_variant",
+    "spmv_amd_init_stencil5_synthetic", "spmv_amd_init_stencil7_synthetic", "spmv_amd_stencil7_row_start", "spmv_amd_ellpack_run_device_scaled", "spmv_amd_download_device_csr", "spmv_amd_time_run_device", "spmv_amd_operator_variant",
     "spmv_amd_operator_select_variant", "spmv_amd_cg_last_history", "spmv_amd_comm_unique_id", "spmv_amd_comm_create_rccl",
     "spmv_amd_comm_create_staged", "spmv_amd_comm_destroy", "spmv_amd_comm_set_world", "spmv_amd_comm_rank", "spmv_amd_comm_size", "spmv_amd_comm_selftest",
     "spmv_amd_comm_barrier", "spmv_amd_comm_transport", "spmv_amd_comm_transport_ranks",
@@ -147,7 +147,7 @@ LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set
                     "spmv_amd_pcg_last_multigrid_cycles", "spmv_amd_precond_multigrid_level_csr", "spmv_amd_mg_stage"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
 DECLARED_CXX_SYMBOLS = [
-    "SPMV_CSR", "SPMV_STENCIL5_CSR", "SPMV_STENCIL_HALO_MGPU", "SPMV_ELLPACK", "SPMV_STENCIL5_ELLPACK",
+    "SPMV_CSR", "SPMV_STENCIL5_CSR", "SPMV_STENCIL7_CSR", "SPMV_STENCIL_HALO_MGPU", "SPMV_ELLPACK", "SPMV_STENCIL5_ELLPACK",
     "_Z16build_csr_structP10MatrixData",
     "_Z29build_ellpack_from_csr_structPK9CSRMatrixP13ELLPACKMatrixPi",
     "_Z8cg_solveP12SpmvOperatorP10MatrixDataPKdPd8CGConfigP7CGStats",
@@ -203,6 +203,10 @@ def lib():
     L.spmv_amd_copy_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.spmv_amd_device_fill_f64.argtypes = [C.c_void_p, C.c_size_t, C.c_double]
     L.spmv_amd_init_stencil5_synthetic.argtypes = [C.c_char_p, C.c_int]
+    L.spmv_amd_init_stencil7_synthetic.argtypes = [C.c_char_p, C.c_int]
+    L.spmv_amd_stencil7_row_start.argtypes = [C.c_longlong, C.c_int]
+    L.spmv_amd_stencil7_row_start.restype = C.c_longlong
+    L.write_matrix_market_stencil7.argtypes = [C.c_int, C.c_char_p]
     L.spmv_amd_download_device_csr.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.spmv_amd_ellpack_run_device_scaled.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double]
     L.spmv_amd_time_run_device.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float)]
@@ -455,6 +459,13 @@ class Operator:
         require_gpu()
         rc = lib().spmv_amd_init_stencil5_synthetic(self.name.encode(), int(n))
         self.rows = self.cols = n * n
+        return rc
+
+    def init_synthetic3d(self, n):
+        """spmv_amd_init_stencil7_synthetic: the n x n x n 7-point generator matrix built in HBM ("stencil7-csr", "cusparse-csr")."""
+        require_gpu()
+        rc = lib().spmv_amd_init_stencil7_synthetic(self.name.encode(), int(n))
+        self.rows = self.cols = n * n * n
         return rc
 
     def run_timed(self, x):

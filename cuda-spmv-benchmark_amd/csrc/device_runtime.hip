@@ -38,6 +38,7 @@ LaunchShape current_launch_shape() {
     if (shape.knobs.rowlds_group < 0 || shape.knobs.rowlds_group > 64) shape.knobs.rowlds_group = 0;
     const int block_rows = env_int("SPMV_AMD_ROWLDS_BLOCK_ROWS", shape.knobs.rowlds_block_rows);
     if (block_rows == 0 || block_rows == 4 || block_rows == 8) shape.knobs.rowlds_block_rows = block_rows;
+    shape.knobs.stencil7_rowlds_min_grid = env_int("SPMV_AMD_STENCIL7_ROWLDS_MIN_GRID", shape.knobs.stencil7_rowlds_min_grid);
     return shape;
 }
 
@@ -154,6 +155,21 @@ void DeviceCsr::generate_stencil5(int n, int row_offset, int n_local, double cen
     view.grid_size = n;
     view.verified_stencil = false;
     view.max_row_nnz = n >= 3 ? 5 : (n == 2 ? 3 : 1);
+}
+
+void DeviceCsr::generate_stencil7(int n, double center, double off, hipStream_t stream) {
+    release();
+    const long long rows = (long long)n * n * n, nnz = stencil7_nnz(n);
+    allocate((size_t)rows, (size_t)nnz);
+    launch_generate_stencil7_csr(n, center, off, row_ptr, col_idx, values, stream);
+    view = SlabCsr{};
+    view.row_ptr = row_ptr;
+    view.col_idx = col_idx;
+    view.values = values;
+    view.n_local = (int)rows;
+    view.nnz_local = nnz;
+    view.n_global = (int)rows;
+    view.max_row_nnz = n >= 3 ? 7 : (n == 2 ? 4 : 1);
 }
 
 void DeviceCsr::verify_stencil(hipStream_t stream) {

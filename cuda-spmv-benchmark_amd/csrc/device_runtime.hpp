@@ -214,6 +214,9 @@ struct DeviceCsr {
     // Generates the same slab of the synthetic n x n stencil in HBM.
     void generate_stencil5(int n, int row_offset, int n_local, double center, double off,
                            hipStream_t stream);
+    // Generates the whole n x n x n 7-point stencil (stencil_geometry.hpp) in HBM. The view's grid_size stays unset: it means
+    // "2-D 5-point" to the kernels that read it.
+    void generate_stencil7(int n, double center, double off, hipStream_t stream);
     // Runs the structure check and records the verdict in view.verified_stencil.
     void verify_stencil(hipStream_t stream);
     void release();

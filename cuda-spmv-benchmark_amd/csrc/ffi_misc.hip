@@ -12,6 +12,11 @@ extern "C" int spmv_amd_interior_csr_offset(int row, int grid_size) {
     return reference_interior_csr_offset(row, grid_size);
 }
 
+extern "C" long long spmv_amd_stencil7_row_start(long long row, int n) {
+    if (n < 1 || n > (1 << 20) || row < 0 || row > (long long)n * n * n) return -1;  // n <= 2^20: every term stays inside 64 bits
+    return stencil7_row_start_flat(row, n);
+}
+
 extern "C" void spmv_amd_partition_rows(int n, int world, int rank, int* row_offset, int* n_local) {
     int count = n / world;
     const int first = rank * count;

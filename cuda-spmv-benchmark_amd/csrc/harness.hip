@@ -103,7 +103,8 @@ Traffic traffic_model(const BenchmarkMetrics* m) {
     t.flops = 2.0 * m->matrix_nnz;
     t.vector_bytes = (double)m->matrix_cols * sizeof(double) + (double)m->matrix_rows * sizeof(double);
     const bool csr_like = m->operator_name && (!strcmp(m->operator_name, "cusparse-csr") ||
-                                               !strcmp(m->operator_name, "stencil5-csr"));
+                                               !strcmp(m->operator_name, "stencil5-csr") ||
+                                               !strcmp(m->operator_name, "stencil7-csr"));
     if (csr_like) {
         t.values_bytes = (double)csr_mat.nb_nonzeros * sizeof(double);
         t.index_bytes = (double)csr_mat.nb_nonzeros * sizeof(int) + ((double)csr_mat.nb_rows + 1) * sizeof(int);

@@ -39,6 +39,10 @@ struct Tunables {
     // update inside the SpMV (DirectionSpmv) 8 makes that launch 2 % shorter and the whole solve no faster: 4 stays
     // (profiles/r15_fused_direction_ab.txt, section 5).
     int rowlds_block_rows = 4;
+    // SPMV_AMD_STENCIL7_ROWLDS_MIN_GRID: smallest n of an n^3 grid that takes stencil7/row-lds automatically. Measured on MI355X
+    // (profiles/r18_stencil7_bench.txt), row-lds / row-direct medians: 64^3 7.9 / 9.9 us, 96^3 20.3 / 24.0, 128^3 38.4 / 40.9,
+    // 160^3 80.8 / 83.6, 256^3 225 / 287: row-lds is faster from the smallest size measured on
+    int stencil7_rowlds_min_grid = 64;
 };
 
 // How many consecutive logical blocks (each `block_columns` grid columns wide) one XCD takes of every run of
@@ -200,6 +204,33 @@ CsrVariant csr_auto_variant(const SlabCsr& m);
 void launch_csr_spmv(const SlabCsr& m, const double* x, double* y, double alpha,
                      CsrVariant variant, hipStream_t stream, double* d_dot_partials = nullptr);
 int csr_fused_dot_partials(const SlabCsr& m, CsrVariant variant);
+
+// ---- STENCIL7 (n x n x n 7-point stencil in CSR form; stencil7_kernels.hip) ----
+// The 3-D geometry travels beside the view: SlabCsr::grid_size / verified_stencil mean "2-D 5-point" and stay unset here.
+// Fills the CSR of the whole n^3 generator matrix, rows sorted by column ([D,N,W,C,E,S,U] minus the absent ones).
+void launch_generate_stencil7_csr(int n, double center, double off, int* row_ptr, int* col_idx, double* values, hipStream_t stream);
+// Sets *d_mismatch (int, zeroed by the caller) if any row deviates from the complete 7-point pattern of an n^3 grid. The caller has
+// checked m.n_local == n^3 and m.nnz_local == 7 n^3 - 6 n^2 (the analytic offsets then stay inside the arrays).
+void launch_verify_stencil7_csr(const SlabCsr& m, int n, int* d_mismatch, hipStream_t stream);
+enum class Stencil7Variant { Auto, RowLds, RowDirect, CsrLoop };
+// One launch over the whole matrix, computed once per init / variant change. CsrLoop (unverified matrices, n < 2) is the CSR
+// launcher's Auto variant; its partials are csr_fused_dot_partials() (0 = no fused form).
+struct Stencil7Plan {
+    Stencil7Variant variant = Stencil7Variant::CsrLoop;
+    int n = 0;           // the grid (row-lds / row-direct)
+    int col_blocks = 0;  // row-lds: 128-column tiles per grid row; row-direct: 256-column blocks
+    int xcd_run = 1;     // row-lds: consecutive tiles one XCD takes of every run of 8 * xcd_run
+    int partials = 0;    // dot-partial slots a launch with partials writes
+    const char* name = "stencil7/csr-loop";
+};
+int stencil7_xcd_run_rule(int n);
+Stencil7Plan plan_stencil7(const SlabCsr& m, int n, bool verified, Stencil7Variant want, const Tunables& knobs);
+// y = alpha A x. d_dot_partials (may be null): the partials of x . (A x), unscaled, p.partials of them -- row-lds / row-direct in
+// the shapes of tests/reduction_restatement.py's rowlds_partials / rowdirect_partials over n^2 grid rows of n columns.
+// d_skip_flag (may be null; row-lds / row-direct): nothing is read or written once it is set. reverse: tiles walked last to first,
+// same bits, same slots. Returns the partial slots written.
+int launch_stencil7_spmv(const SlabCsr& m, const Stencil7Plan& p, const double* x, double* y, double alpha, double* d_dot_partials,
+                         const int* d_skip_flag, bool reverse, hipStream_t stream);
 
 // ---- ELLPACK SpMV (device layout: slot-major, element (r,k) at [k * rows + r]) ----
 void launch_ell_transpose(int rows, int width, const int* idx_rowmajor, const double* val_rowmajor,

@@ -281,6 +281,41 @@ extern "C" int write_matrix_market_stencil5(int n, const char* filename) {
     return write_stencil5(n, filename, "5.0", "-1.0");
 }
 
+// The n x n x n 7-point stencil (centre 7.0, neighbours -1.0), point (k, i, j) = row k n^2 + i n + j: the 2-D writer's format and
+// STENCIL_GRID_SIZE comment, one point's lines in the order C, W, E, N, S, D, U.
+extern "C" int write_matrix_market_stencil7(int n, const char* filename) {
+    if (n < 1 || n > 674) {
+        fprintf(stderr, "write_matrix_market_stencil7: grid %d^3 is refused (1 <= n <= 674 keeps rows and nnz inside int32)\n", n);
+        return 1;
+    }
+    const long long nn = (long long)n * n, N = nn * n, nnz = 7 * N - 6 * nn;
+    FILE* f = fopen(filename, "w");
+    if (!f) {
+        perror("fopen");
+        return 1;
+    }
+    std::vector<char> big(1 << 20);
+    setvbuf(f, big.data(), _IOFBF, big.size());
+    fprintf(f, "%%%%MatrixMarket matrix coordinate real general\n");
+    fprintf(f, "%% STENCIL_GRID_SIZE %d\n", n);
+    fprintf(f, "%lld %lld %lld\n", N, N, nnz);
+    for (int gk = 0; gk < n; ++gk)
+        for (int gi = 0; gi < n; ++gi)
+            for (int gj = 0; gj < n; ++gj) {
+                const long long id = (long long)gk * nn + (long long)gi * n + gj + 1;  // 1-based
+                fprintf(f, "%lld %lld 7.0\n", id, id);
+                if (gj > 0) fprintf(f, "%lld %lld -1.0\n", id, id - 1);
+                if (gj < n - 1) fprintf(f, "%lld %lld -1.0\n", id, id + 1);
+                if (gi > 0) fprintf(f, "%lld %lld -1.0\n", id, id - n);
+                if (gi < n - 1) fprintf(f, "%lld %lld -1.0\n", id, id + n);
+                if (gk > 0) fprintf(f, "%lld %lld -1.0\n", id, id - nn);
+                if (gk < n - 1) fprintf(f, "%lld %lld -1.0\n", id, id + nn);
+            }
+    fclose(f);
+    printf("Matrix generated: %s (%lldx%lld, %lld nnz)\n", filename, N, N, nnz);
+    return 0;
+}
+
 // Older convention of the shipped matrix/example81x81.mtx (centre -4.0): used to regenerate
 // that fixture, see tests/golden/make_golden.py.
 extern "C" int spmv_amd_write_stencil5_values(int n, const char* filename, const char* center_text,

@@ -4,6 +4,7 @@
 //   "cusparse-csr"     <- reference SPMV_CSR, src/spmv/spmv_cusparse_csr.cu:182-327 (the cuSPARSE
 //                         call is replaced by this build's own CSR kernels; the name is kept so that
 //                         calculate_spmv_metrics and the harness scripts keep working)
+//   "stencil7-csr"     <- no reference counterpart: the n x n x n 7-point stencil (stencil7_kernels.hip)
 //   "ellpack",
 //   "stencil5-ellpack" <- reference include/spmv_ellpack.h, include/spmv_stencil.h:25-42 (headers only)
 //
@@ -39,6 +40,11 @@ struct CsrBackedOperator {
     Stencil5Variant stencil_variant = Stencil5Variant::Auto;
     CsrVariant csr_variant = CsrVariant::Auto;
     const char* variant_name = "uninitialised";
+    // stencil7-csr: the 3-D geometry lives here, not in the view (whose grid_size / verified_stencil mean "2-D 5-point")
+    Stencil7Plan plan7;
+    Stencil7Variant stencil7_variant = Stencil7Variant::Auto;
+    int grid7 = 0;             // n of the verified n^3 grid, 0 otherwise
+    bool verified7 = false;
 
     int tuned_run = 0;         // stencil5-csr: row-lds tiles per XCD and run kept by the set-up trial (0 = not tried yet, -1 = does not apply)
     double tuning[4] = {0, 0, 0, 0};  // {rule, kept, ms with the rule, ms kept}
@@ -70,12 +76,12 @@ struct CsrBackedOperator {
         }, &y_candidates, &y_gain);
         HIP_CHECK(hipStreamSynchronize(kDefaultStream));
     }
-    int init_from_host(MatrixData* mat) {
+    int init_from_host(MatrixData* mat, bool grid_in_view = true) {
         if (build_csr_struct(mat) != EXIT_SUCCESS) return EXIT_FAILURE;
         drop();
         rows = csr_mat.nb_rows;
         cols = csr_mat.nb_cols;
-        A.upload_slab(csr_mat, 0, rows, mat->grid_size);
+        A.upload_slab(csr_mat, 0, rows, grid_in_view ? mat->grid_size : -1);
         A.view.halo_after = cols - rows;  // x is readable on [0, cols)
         alloc_vectors();
         ready = true;
@@ -98,7 +104,22 @@ struct CsrBackedOperator {
         ready = true;
         return 0;
     }
+    // the n^3 generator matrix (centre 7, neighbours -1) built in HBM; the caller has checked stencil7_fits_int32(n)
+    int init_synthetic7(int n) {
+        drop();
+        rows = cols = n * n * n;
+        A.generate_stencil7(n, 7.0, -1.0, kDefaultStream);
+        spmv_amd_reset_host_matrices();
+        csr_mat.nb_rows = rows;
+        csr_mat.nb_cols = cols;
+        csr_mat.nb_nonzeros = (int)A.view.nnz_local;
+        alloc_vectors();
+        ready = true;
+        return 0;
+    }
     void drop() {
+        grid7 = 0;
+        verified7 = false;
         A.release();
         device_release(dX);
         device_release(dY);
@@ -111,6 +132,7 @@ struct CsrBackedOperator {
 
 CsrBackedOperator g_stencil{"stencil5-csr"};
 CsrBackedOperator g_csr{"cusparse-csr"};
+CsrBackedOperator g_stencil7{"stencil7-csr"};
 
 // ---- stencil5-csr ----------------------------------------------------------------
 
@@ -187,6 +209,69 @@ void stencil_free() {
 int stencil_fused_launch(const double* d_x, double* d_y, double* d_partials, const int* d_skip, bool reverse,
                          const ResidualOut* init, hipStream_t stream) {
     return launch_stencil5_spmv(g_stencil.A.view, g_stencil.plan, d_x, d_y, /*alpha=*/1.0, d_partials, d_skip, reverse, stream, init);
+}
+
+// ---- stencil7-csr ----------------------------------------------------------------
+// A matrix is the 3-D operator's own when grid_size = n >= 2, rows == cols == n^3, nnz == 7 n^3 - 6 n^2 and every row has the
+// complete pattern; anything else runs every row through the CSR launcher ("stencil7/csr-loop").
+void stencil7_verify(int n) {
+    CsrBackedOperator& o = g_stencil7;
+    o.grid7 = 0;
+    o.verified7 = false;
+    // the sizes first: the verifier's analytic offsets must not run past the arrays
+    if (n < 2 || !stencil7_fits_int32(n) || o.rows != o.cols || (long long)n * n * n != o.rows || o.A.view.nnz_local != stencil7_nnz(n)) return;
+    int* d_flag = device_alloc<int>(1);
+    HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(int), kDefaultStream));
+    launch_verify_stencil7_csr(o.A.view, n, d_flag, kDefaultStream);
+    int h_flag = 1;
+    HIP_CHECK(hipMemcpyAsync(&h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, kDefaultStream));
+    HIP_CHECK(hipStreamSynchronize(kDefaultStream));
+    device_release(d_flag);
+    o.verified7 = h_flag == 0;
+    if (o.verified7) o.grid7 = n;
+}
+
+void stencil7_pick_variant() {
+    CsrBackedOperator& o = g_stencil7;
+    o.shape = current_launch_shape();
+    o.plan7 = plan_stencil7(o.A.view, o.grid7, o.verified7, o.stencil7_variant, o.shape.knobs);
+    o.variant_name = o.plan7.name;
+    if (o.dY == nullptr)  // once per init, as for the other operators
+        o.place_output([](const double* x, double* y) {
+            (void)launch_stencil7_spmv(g_stencil7.A.view, g_stencil7.plan7, x, y, 1.0, nullptr, nullptr, false, kDefaultStream);
+        });
+}
+
+int stencil7_init(MatrixData* mat) {
+    printf("[stencil7-csr] Initializing (7-point stencil of an n^3 grid: row-lds / row-direct kernels on gfx950)\n");
+    if (g_stencil7.init_from_host(mat, /*grid_in_view=*/false) != 0) return EXIT_FAILURE;
+    stencil7_verify(mat->grid_size);
+    stencil7_pick_variant();
+    printf("[stencil7-csr] %d rows, %d nnz, grid %d^3, variant %s\n", csr_mat.nb_rows, csr_mat.nb_nonzeros, g_stencil7.grid7,
+           g_stencil7.variant_name);
+    return 0;
+}
+
+int stencil7_run_device(const double* d_x, double* d_y) {
+    if (!g_stencil7.ready) {
+        fprintf(stderr, "[stencil7-csr] run before init\n");
+        return EXIT_FAILURE;
+    }
+    (void)launch_stencil7_spmv(g_stencil7.A.view, g_stencil7.plan7, d_x, d_y, /*alpha=*/1.0, nullptr, nullptr, /*reverse=*/false, kDefaultStream);
+    return 0;
+}
+
+void stencil7_free() {
+    printf("[stencil7-csr] Cleaning up\n");
+    release_cg_workspace();
+    g_stencil7.drop();
+}
+
+// cg_solve_device's fused launch: p . Ap partials from inside the SpMV; no fused initial residual (the loop streams it)
+int stencil7_fused_launch(const double* d_x, double* d_y, double* d_partials, const int* d_skip, bool reverse, const ResidualOut* init,
+                          hipStream_t stream) {
+    if (init != nullptr) return -1;
+    return launch_stencil7_spmv(g_stencil7.A.view, g_stencil7.plan7, d_x, d_y, /*alpha=*/1.0, d_partials, d_skip, reverse, stream);
 }
 
 // ---- cusparse-csr ----------------------------------------------------------------
@@ -429,11 +514,12 @@ void ells_free() {
 
 // ---- name table ------------------------------------------------------------------
 
-enum class Which { None, Stencil, Csr, Ell, EllStencil };
+enum class Which { None, Stencil, Csr, Ell, EllStencil, Stencil7 };
 
 Which which_operator(const char* mode) {
     if (!mode) return Which::None;
     if (!strcmp(mode, "stencil5-csr") || !strcmp(mode, "stencil5")) return Which::Stencil;
+    if (!strcmp(mode, "stencil7-csr") || !strcmp(mode, "stencil7")) return Which::Stencil7;
     if (!strcmp(mode, "cusparse-csr") || !strcmp(mode, "csr")) return Which::Csr;
     if (!strcmp(mode, "ellpack")) return Which::Ell;
     if (!strcmp(mode, "stencil5-ellpack")) return Which::EllStencil;
@@ -447,6 +533,8 @@ SpmvOperator SPMV_STENCIL5_CSR = {"stencil5-csr", stencil_init,
                                   stencil_run_device, stencil_free};
 SpmvOperator SPMV_CSR = {"cusparse-csr", csr_init, run_timed_generic<csr_run_device, &g_csr>,
                          csr_run_device, csr_free};
+SpmvOperator SPMV_STENCIL7_CSR = {"stencil7-csr", stencil7_init, run_timed_generic<stencil7_run_device, &g_stencil7>,
+                                  stencil7_run_device, stencil7_free};
 SpmvOperator SPMV_ELLPACK = {"ellpack", ellg_init, ellg_run_timed, ellg_run_device, ellg_free};
 SpmvOperator SPMV_STENCIL5_ELLPACK = {"stencil5-ellpack", ells_init, ells_run_timed,
                                       ells_run_device, ells_free};
@@ -468,6 +556,7 @@ OwnOperator own_operator_of(const SpmvOperator* op) {
     OwnOperator o;
     if (op == &SPMV_STENCIL5_CSR || op == &SPMV_STENCIL_HALO_MGPU) o.csr = &g_stencil;
     else if (op == &SPMV_CSR) o.csr = &g_csr;
+    else if (op == &SPMV_STENCIL7_CSR) o.csr = &g_stencil7;
     else if (op == &SPMV_ELLPACK) o.ell = &g_ell;
     else if (op == &SPMV_STENCIL5_ELLPACK) o.ell = &g_ell_stencil;
     return o;
@@ -483,6 +572,10 @@ FusedSpmv fused_spmv_of(const SpmvOperator* op) {
         f.partials = g_stencil.plan.partials;
         f.can_init = g_stencil.plan.variant == Stencil5Variant::RowLds;
         f.launch = stencil_fused_launch;
+    } else if (o.csr == &g_stencil7 && g_stencil7.ready && g_stencil7.rows == g_stencil7.cols) {
+        // row-lds / row-direct: the kernels' own partials; csr-loop: what cusparse-csr has (0 = run_device, then a dot pass)
+        f.partials = g_stencil7.plan7.partials;
+        f.launch = f.partials > 0 ? stencil7_fused_launch : nullptr;
     } else if (o.csr == &g_csr && g_csr.ready && g_csr.rows == g_csr.cols) {
         f.partials = csr_fused_dot_partials(g_csr.A.view, g_csr.csr_variant);
         f.launch = f.partials > 0 ? csr_fused_launch : nullptr;
@@ -545,6 +638,7 @@ extern "C" SpmvOperator* get_operator(const char* mode) {
     switch (which_operator(mode)) {
         case Which::Stencil: return &SPMV_STENCIL5_CSR;
         case Which::Csr: return &SPMV_CSR;
+        case Which::Stencil7: return &SPMV_STENCIL7_CSR;
         case Which::Ell: return &SPMV_ELLPACK;
         case Which::EllStencil: return &SPMV_STENCIL5_ELLPACK;
         default: break;
@@ -572,6 +666,28 @@ extern "C" int spmv_amd_init_stencil5_synthetic(const char* mode, int n) {
     }
 }
 
+extern "C" int spmv_amd_init_stencil7_synthetic(const char* mode, int n) {
+    // rows = n^3 and nnz = 7 n^3 - 6 n^2 must fit int32 (n <= 674): decided before any HIP call
+    if (!stencil7_fits_int32(n)) {
+        fprintf(stderr, "[stencil7] grid %d^3 is refused: 1 <= n <= 674 keeps rows and nnz inside 32-bit CSR indices\n", n);
+        return EXIT_FAILURE;
+    }
+    switch (which_operator(mode)) {
+        case Which::Stencil7:
+            if (g_stencil7.init_synthetic7(n) != 0) return EXIT_FAILURE;
+            stencil7_verify(n);
+            stencil7_pick_variant();
+            return 0;
+        case Which::Csr:
+            if (g_csr.init_synthetic7(n) != 0) return EXIT_FAILURE;
+            HIP_CHECK(hipStreamSynchronize(kDefaultStream));
+            g_csr.variant_name = csr_variant_name(g_csr.csr_variant, g_csr.A.view);
+            csr_place_output();
+            return 0;
+        default: return EXIT_FAILURE;  // the ELLPACK operators have no 3-D generator
+    }
+}
+
 extern "C" int spmv_amd_ellpack_run_device_scaled(const char* mode, const double* d_x, double* d_y,
                                                   double alpha, double beta) {
     switch (which_operator(mode)) {
@@ -583,9 +699,10 @@ extern "C" int spmv_amd_ellpack_run_device_scaled(const char* mode, const double
 
 extern "C" int spmv_amd_download_device_csr(const char* mode, int* row_ptr, int* col_idx,
                                             double* values) {
-    CsrBackedOperator* op = which_operator(mode) == Which::Stencil ? &g_stencil
-                            : which_operator(mode) == Which::Csr   ? &g_csr
-                                                                   : nullptr;
+    CsrBackedOperator* op = which_operator(mode) == Which::Stencil    ? &g_stencil
+                            : which_operator(mode) == Which::Csr      ? &g_csr
+                            : which_operator(mode) == Which::Stencil7 ? &g_stencil7
+                                                                      : nullptr;
     if (!op || !op->ready) return EXIT_FAILURE;
     HIP_CHECK(hipDeviceSynchronize());
     if (row_ptr) download(row_ptr, op->A.row_ptr, (size_t)op->rows + 1);
@@ -600,6 +717,7 @@ bool own_vectors(const char* mode, double** dX, double** dY, size_t* cols, int* 
     switch (which_operator(mode)) {
         case Which::Stencil: *dX = g_stencil.dX, *dY = g_stencil.dY, *cols = (size_t)g_stencil.cols, *candidates = g_stencil.y_candidates, *gain = g_stencil.y_gain; return g_stencil.ready;
         case Which::Csr: *dX = g_csr.dX, *dY = g_csr.dY, *cols = (size_t)g_csr.cols, *candidates = g_csr.y_candidates, *gain = g_csr.y_gain; return g_csr.ready;
+        case Which::Stencil7: *dX = g_stencil7.dX, *dY = g_stencil7.dY, *cols = (size_t)g_stencil7.cols, *candidates = g_stencil7.y_candidates, *gain = g_stencil7.y_gain; return g_stencil7.ready;
         case Which::Ell: *dX = g_ell.dX, *dY = g_ell.dY, *cols = (size_t)g_ell.cols, *candidates = g_ell.y_candidates, *gain = g_ell.y_gain; return g_ell.ready;
         case Which::EllStencil: *dX = g_ell_stencil.dX, *dY = g_ell_stencil.dY, *cols = (size_t)g_ell_stencil.cols, *candidates = g_ell_stencil.y_candidates, *gain = g_ell_stencil.y_gain; return g_ell_stencil.ready;
         default: return false;
@@ -654,6 +772,7 @@ extern "C" const char* spmv_amd_operator_variant(const char* mode) {
     switch (which_operator(mode)) {
         case Which::Stencil: return g_stencil.variant_name;
         case Which::Csr: return g_csr.variant_name;
+        case Which::Stencil7: return g_stencil7.variant_name;
         case Which::Ell: return g_ell.variant_name;
         case Which::EllStencil: return g_ell_stencil.variant_name;
         default: return "unknown-operator";
@@ -670,6 +789,14 @@ extern "C" int spmv_amd_operator_select_variant(const char* mode, const char* va
             else if (!strcmp(variant, "row-generic")) g_stencil.stencil_variant = Stencil5Variant::RowGeneric;
             else return EXIT_FAILURE;
             if (g_stencil.ready) stencil_pick_variant();
+            return 0;
+        case Which::Stencil7:
+            if (automatic) g_stencil7.stencil7_variant = Stencil7Variant::Auto;
+            else if (!strcmp(variant, "row-lds")) g_stencil7.stencil7_variant = Stencil7Variant::RowLds;
+            else if (!strcmp(variant, "row-direct")) g_stencil7.stencil7_variant = Stencil7Variant::RowDirect;
+            else if (!strcmp(variant, "csr-loop")) g_stencil7.stencil7_variant = Stencil7Variant::CsrLoop;
+            else return EXIT_FAILURE;
+            if (g_stencil7.ready) stencil7_pick_variant();
             return 0;
         case Which::Csr: {
             CsrVariant v;

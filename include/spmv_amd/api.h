@@ -39,8 +39,8 @@ extern ELLPACKMatrix ellpack_matrix;
 int build_ellpack_from_csr_local(CSRMatrix* csr_matrix);
 int ensure_ellpack_structure_built(MatrixData* mat);
 
-/* Operator lookup. Canonical names: "stencil5-csr", "cusparse-csr", "ellpack",
- * "stencil5-ellpack"; accepted aliases: "stencil5", "csr". Unknown -> NULL.
+/* Operator lookup. Canonical names: "stencil5-csr", "cusparse-csr", "stencil7-csr", "ellpack",
+ * "stencil5-ellpack"; accepted aliases: "stencil5", "csr", "stencil7". Unknown -> NULL.
  * reference: include/spmv.h:141-150 ; src/spmv/spmv.cu:11-23 */
 SpmvOperator* get_operator(const char* mode);
 
@@ -63,6 +63,10 @@ int load_matrix_market(const char* filename, MatrixData* mat);
 void convert_csr_to_ellpack(const struct CSRMatrix* csr_matrix,
                             struct ELLPACKMatrix* ellpack_matrix, int* max_width);
 int write_matrix_market_stencil5(int n, const char* filename);
+/* The n x n x n 7-point stencil, point (k, i, j) = row k n^2 + i n + j, neighbours at -+1 (W/E), -+n (N/S), -+n^2 (D/U): centre 7.0,
+ * every neighbour -1.0 (strictly diagonally dominant, SPD; sum(A 1) = n^3 + 6 n^2); write_matrix_market_stencil5's format with the
+ * same "% STENCIL_GRID_SIZE n" comment, entry order C, W, E, N, S, D, U per point; 7 n^3 - 6 n^2 entries. 1 <= n <= 674, else 1. */
+int write_matrix_market_stencil7(int n, const char* filename);
 
 /* N-run statistics with >2 sigma outlier removal and median.
  * reference: include/benchmark_stats.h:23-29 ; include/benchmark_stats_mgpu.h:12-15 ;
@@ -96,6 +100,7 @@ void export_cg_csv(const char* filename, const char* mode, const MatrixData* mat
 /* reference: include/spmv.h:137-139 */
 extern SpmvOperator SPMV_CSR;               /* "cusparse-csr": own CSR kernels, no vendor library */
 extern SpmvOperator SPMV_STENCIL5_CSR;      /* "stencil5-csr" */
+extern SpmvOperator SPMV_STENCIL7_CSR;      /* "stencil7-csr" (new: the n x n x n 7-point stencil, see spmv_amd_init_stencil7_synthetic) */
 extern SpmvOperator SPMV_STENCIL_HALO_MGPU; /* "stencil5-halo-mgpu": declared, never defined upstream */
 extern SpmvOperator SPMV_ELLPACK;           /* "ellpack" (new: upstream ships headers only) */
 extern SpmvOperator SPMV_STENCIL5_ELLPACK;  /* "stencil5-ellpack": ELL values, computed columns */
@@ -153,6 +158,10 @@ void spmv_amd_reset_host_matrices(void);
  * reference: calculate_interior_csr_offset, src/spmv/spmv_stencil_csr_direct.cu:50-67 */
 int spmv_amd_interior_csr_offset(int row, int grid_size);
 
+/* CSR start of row `row` (= k n^2 + i n + j) of the n x n x n 7-point stencil whose rows are sorted by column ([D,N,W,C,E,S,U]
+ * minus the absent ones), in closed form; row == n^3 gives the total, 7 n^3 - 6 n^2. -1 for n < 1, n > 2^20 (the arithmetic is 64-bit) or a row outside [0, n^3]. */
+long long spmv_amd_stencil7_row_start(long long row, int n);
+
 /* Row slab of `rank`: n / world rows each, the last rank takes the remainder.
  * reference: src/solvers/cg_solver_mgpu_partitioned.cu:261-268 */
 void spmv_amd_partition_rows(int n, int world, int rank, int* row_offset, int* n_local);
@@ -187,6 +196,15 @@ double spmv_amd_stream_ceiling_mix(int mix, size_t rows, int warmup, int reps, f
  * load_matrix_market + init would upload, without the host COO/CSR (58 GB at
  * n = 20000). csr_mat gets the dimensions, its host arrays stay NULL. */
 int spmv_amd_init_stencil5_synthetic(const char* mode, int n);
+
+/* The same for the n x n x n 7-point stencil of write_matrix_market_stencil7 (centre 7.0, neighbours -1.0): `mode` is
+ * "stencil7-csr" or "cusparse-csr" (the ELLPACK operators return failure). Rows (n^3) and entries (7 n^3 - 6 n^2) must fit int32:
+ * n < 1 and n > 674 are refused with a message before any HIP call.
+ * "stencil7-csr" contract: a matrix is the operator's own when MatrixData.grid_size = n >= 2, rows == cols == n^3 and every row has the
+ * complete pattern [D,N,W,C,E,S,U] (checked on the device at init); variants "stencil7/row-lds" (n >= SPMV_AMD_STENCIL7_ROWLDS_MIN_GRID,
+ * default 64) and "stencil7/row-direct"; anything else initialises and runs the CSR kernels as "stencil7/csr-loop". Every row, in
+ * every variant, is sum = 0.0 ; sum = fma(v[k], x[col[k]], sum) for ascending k ; y = sum: bit for bit the sequential CSR sum. */
+int spmv_amd_init_stencil7_synthetic(const char* mode, int n);
 
 /* y = alpha*A*x + beta*y on an initialised "ellpack" / "stencil5-ellpack" operator: the full
  * contract of the kernel prototyped in reference include/spmv_stencil.h:25-42 (the operator table
