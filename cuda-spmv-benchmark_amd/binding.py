@@ -142,7 +142,7 @@ DECLARED_SYMBOLS = [
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
 LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_cg_slab_block_map", "spmv_amd_cg_slab_slow_blocks",
-                    "spmv_amd_cg_slab_direction_spmv", "spmv_amd_cg_slab_spmv_dot", "spmv_amd_pcg_stage",
+                    "spmv_amd_cg_slab_direction_spmv", "spmv_amd_cg_slab_spmv_dot", "spmv_amd_cg_slab_initial_stage", "spmv_amd_pcg_stage",
                     "spmv_amd_pcg_last_step_launches", "spmv_amd_cg_multi_stage",
                     "spmv_amd_pcg_last_multigrid_cycles", "spmv_amd_precond_multigrid_level_csr", "spmv_amd_mg_stage"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
@@ -250,6 +250,8 @@ def lib():
         L.spmv_amd_cg_slab_direction_spmv.restype = C.c_int
         L.spmv_amd_cg_slab_spmv_dot.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_int]
         L.spmv_amd_cg_slab_spmv_dot.restype = C.c_int
+        L.spmv_amd_cg_slab_initial_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        L.spmv_amd_cg_slab_initial_stage.restype = C.c_int
         L.spmv_amd_pcg_stage.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PcgStageArgs), C.POINTER(PcgScalars)]
         L.spmv_amd_pcg_stage.restype = C.c_int
         L.spmv_amd_pcg_last_step_launches.argtypes = []
@@ -1046,6 +1048,27 @@ class CgSlab:
         if used < 0:
             raise RuntimeError("this slab cannot take the direction update inside the block SpMV (no block map, neighbours, or ring 1)")
         return p_out, Ap, partials[:used], pAp.value
+
+    def initial_form(self):
+        """The form the initial stage of a solve would take now (LAB build only; include/spmv_amd/lab.h, spmv_amd_cg_slab_initial_stage):
+        bit 0 = no x0 value requested on interior grid rows, bit 1 = r0 stored once, as p0. Nothing is launched."""
+        if not is_lab():
+            raise RuntimeError("the initial stage's form is read through the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        return int(lib().spmv_amd_cg_slab_initial_stage(self.h, None, None, None, 0, None, None))
+
+    def initial_stage(self):
+        """spmv_amd_cg_slab_initial_stage (LAB build only): the first SpMV's launch and the reduction of its partials, once, on the
+        stored b and x0. Returns (form, r0, r_vec, partials, rr); r_vec is NaN where the launch did not write."""
+        if not is_lab():
+            raise RuntimeError("the initial stage alone runs in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        r0, r_vec = np.empty(self.n_local, dtype=np.float64), np.empty(self.n_local, dtype=np.float64)
+        partials = np.empty(self.n_local, dtype=np.float64)  # more than any plan writes (one per 128 x 1 tile)
+        count, rr = C.c_int(0), C.c_double(0.0)
+        form = lib().spmv_amd_cg_slab_initial_stage(self.h, r0.ctypes.data, r_vec.ctypes.data, partials.ctypes.data, len(partials),
+                                                    C.byref(count), C.byref(rr))
+        if form < 0:
+            raise RuntimeError("this slab's first SpMV does not write the residual, or the slab has neighbours")
+        return form, r0, r_vec, partials[:count.value], rr.value
 
     def set_block_rows(self, rows):
         """Grid rows per block tile of the in-loop SpMV (LAB build only): 0 = the one-row kernel, 4 or 8. Rebuilds the block maps."""

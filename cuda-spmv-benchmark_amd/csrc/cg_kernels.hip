@@ -232,6 +232,43 @@ __global__ __launch_bounds__(kStream) void cg_update_r_kernel(size_t n, const Cg
     if (threadIdx.x == 0) partials[block] = acc;
 }
 
+// The same update out of place, r_out = r_in - alpha Ap: the r update of iteration 0 on a slab whose first launch stored r0 once,
+// as p0 (cg_slab.hip, LoopShape::r0_in_ring). A kernel of its own, so that the in-loop kernel above stays the code it was: the
+// loads before the scalars, the same fma per lane, wave_sum and partial slots. r_in is only read (the flush of x reads p0 later).
+__global__ __launch_bounds__(kStream) void cg_update_r_from_kernel(size_t n, const CgScalars* __restrict__ s,
+                                                                  const double* __restrict__ Ap,
+                                                                  const double* __restrict__ r_in,
+                                                                  double* __restrict__ r_out,
+                                                                  double* __restrict__ partials, int reverse) {
+    const unsigned block = reverse ? gridDim.x - 1 - blockIdx.x : blockIdx.x;  // logical workgroup
+    const size_t pairs = n >> 1;
+    const size_t i = (size_t)block * kStream + threadIdx.x;
+    d2 av = {0.0, 0.0}, rv = {0.0, 0.0};
+    if (i < pairs) {
+        av = load_once(Ap, i);
+        rv = load_once(r_in, i);
+    }
+    const int converged = s->converged;
+    const double rr_old = s->rr_old, pAp = s->pAp;
+    if (converged) return;
+    const double alpha = rr_old / pAp;
+    double acc = 0.0;
+    if (i < pairs) {
+        rv.x = fma(-alpha, av.x, rv.x);
+        rv.y = fma(-alpha, av.y, rv.y);
+        store_once(r_out, i, rv);
+        acc = fma(rv.x, rv.x, acc);
+        acc = fma(rv.y, rv.y, acc);
+    }
+    if ((n & 1) && block == 0 && threadIdx.x == 0) {
+        const double rl = fma(-alpha, Ap[n - 1], r_in[n - 1]);
+        r_out[n - 1] = rl;
+        acc = fma(rl, rl, acc);
+    }
+    acc = wave_sum(acc);
+    if (threadIdx.x == 0) partials[block] = acc;
+}
+
 // The direction update p' = r + beta p in its two roundings: direction(), direction_device.hpp.
 
 // x += alpha*p of iteration `iteration` and, unless that iteration converged, p = 1.0*r + beta*p, in
@@ -421,6 +458,8 @@ __device__ __forceinline__ void flush_chunk(d2& xv, const RingSlots& ring, const
 // x <- fma(alpha_j, p_j, x) the per-iteration x updates evaluate (axpy_kernel, mgpu :598), read in one pass
 // with up to eight directions in flight per lane (all fourteen requested before the first fma measured slower in round 3:
 // 8.56-8.59 ms against 8.03-8.36 ms at 4e8 rows, same bits).
+// x_in == nullptr: the initial guess is known to be the zeros the library itself wrote (cg_slab.hip, x0_known_zero): the chain starts
+// from 0.0 in registers, its first term is still fma(alpha, p, 0.0), and 8 B/row of loads are gone.
 __global__ __launch_bounds__(kStream) void cg_flush_x_kernel(size_t n, const double* __restrict__ alphas, RingSlots ring,
                                                              int slots, int first_slot, int count,
                                                              const double* x_in, double* x, const CgScalars* __restrict__ s, int window_start) {
@@ -434,7 +473,8 @@ __global__ __launch_bounds__(kStream) void cg_flush_x_kernel(size_t n, const dou
     const size_t pairs = n >> 1;
     const size_t i = (size_t)blockIdx.x * kStream + threadIdx.x;
     if (i < pairs) {
-        d2 xv = load_once(x_in, i);
+        d2 xv = {0.0, 0.0};
+        if (x_in != nullptr) xv = load_once(x_in, i);
         int slot = first_slot;
         int left = count;
         for (; left >= 8; left -= 8) flush_chunk<8>(xv, ring, alphas, slots, slot, i);
@@ -444,7 +484,7 @@ __global__ __launch_bounds__(kStream) void cg_flush_x_kernel(size_t n, const dou
         store_once(x, i, xv);
     }
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-        double xv = x_in[n - 1];
+        double xv = x_in != nullptr ? x_in[n - 1] : 0.0;
         int slot = first_slot;
         for (int j = 0; j < count; ++j) {
             xv = fma(alphas[slot], ring.p[slot][n - 1], xv);
@@ -525,6 +565,12 @@ void launch_cg_init_residual(size_t n, const double* b, const double* Ap, double
 void launch_cg_update_r(size_t n, const CgScalars* s, const double* Ap, double* r, double* partials,
                         hipStream_t stream, bool reverse) {
     hipLaunchKernelGGL(cg_update_r_kernel, dim3(stream_grid(n)), dim3(kStream), 0, stream, n, s, Ap, r, partials,
+                       reverse ? 1 : 0);
+}
+
+void launch_cg_update_r_from(size_t n, const CgScalars* s, const double* Ap, const double* r_in, double* r_out, double* partials,
+                             hipStream_t stream, bool reverse) {
+    hipLaunchKernelGGL(cg_update_r_from_kernel, dim3(stream_grid(n)), dim3(kStream), 0, stream, n, s, Ap, r_in, r_out, partials,
                        reverse ? 1 : 0);
 }
 

@@ -143,6 +143,22 @@ struct SpmvAmdCgSlab {
     // SPMV_AMD_FUSED_DIRECTION (0 / 1, read at creation): the direction update inside the block SpMV where the slab is eligible
     // (LoopShape::fused_direction). LAB build, set_option("fused_direction", 2): on regardless of the slow blocks' share.
     int fused_direction = 1;
+    // x0 holds the zeros the LIBRARY wrote (the fill at creation, the API's default initial guess) and nothing has written it since:
+    // every other writer of x0 clears this, an uploaded vector of zeros included -- x0 is never scanned. A slab without neighbours
+    // that owns its matrix then requests no x value for r0 = b - A x0 on interior grid rows (LoopShape::zero_start), and every slab
+    // starts the flush of x from 0.0 in registers instead of loading x0 (pointwise: no gate needed).
+    bool x0_known_zero = false;
+    // SPMV_AMD_ZERO_START (0 / 1, read at creation; LAB build: set_option("zero_start", 0 | 1)): 0 = x0 is always loaded and the first
+    // launch stores r0 twice, the launches of before.
+    bool zero_start = true;
+#ifdef SPMV_AMD_LAB
+    // set_option("zero_start_parts", mask), for A/B runs of each part on the same allocations: 1 = the first launch without x loads,
+    // 2 = r0 stored once, 4 = the flush without x_in. The product always takes all three.
+    int zero_start_parts = 7;
+    bool zero_start_part(int bit) const { return zero_start && (zero_start_parts & bit) != 0; }
+#else
+    bool zero_start_part(int) const { return zero_start; }
+#endif
     bool spmv_with_dot = false;  // LAB option: spmv_amd_cg_slab_spmv runs the in-loop form (dot partials wanted)
     const SymPlanes* sym() const { return planes_on ? &planes : nullptr; }
     // place_coefficients: {0, candidates timed, SpMV ms before, SpMV ms kept}
@@ -551,6 +567,7 @@ void make_common(SpmvAmdCgSlab* s) {
     }
     if (const char* v = getenv("SPMV_AMD_NO_OVERLAP")) s->no_overlap = v[0] == '1';
     if (const char* v = getenv("SPMV_AMD_FUSED_DIRECTION")) s->fused_direction = v[0] == '1' ? 1 : 0;
+    if (const char* v = getenv("SPMV_AMD_ZERO_START")) s->zero_start = v[0] != '0';
 #ifdef SPMV_AMD_LAB
     if (const char* v = getenv("SPMV_AMD_TEST_WEDGE_OVERLAPPED_EXCHANGE")) s->test_wedge_overlapped_exchange = atoi(v);
 #endif
@@ -569,6 +586,7 @@ void make_common(SpmvAmdCgSlab* s) {
         adopt_operator(s, s->op);
         launch_fill(s->b, nl, 1.0, s->compute);
         launch_fill(s->x0, nl, 0.0, s->compute);
+        s->x0_known_zero = true;
         HIP_CHECK(hipDeviceSynchronize());
         return;
     }
@@ -604,6 +622,7 @@ void make_common(SpmvAmdCgSlab* s) {
     if (s->setup_trials) tune_tile_runs(s);
     launch_fill(s->b, nl, 1.0, s->compute);   // default right-hand side b = 1
     launch_fill(s->x0, nl, 0.0, s->compute);  // default initial guess x0 = 0
+    s->x0_known_zero = true;
     s->setup_ms[4] = setup_phase_ms(phase);
 }
 
@@ -766,9 +785,10 @@ void reduce_spmv_partials(SpmvAmdCgSlab* s, int used, double* d_out, const int* 
 // overlap = the halo exchange was started on the side stream and ev_halo_done marks its end.
 // spmv_done (optional): recorded behind the last SpMV launch, before the reduction of its partials.
 // init (may be null): the launches write r = b - A x, p = r and r.r partials instead of A x (fused initial residual);
-// the caller reduces the partials. Returns the number of partial slots the launches wrote.
+// the caller reduces the partials. x_zero (with init, on a slab without neighbours that owns its matrix): `input` holds zeros the
+// library wrote, see launch_stencil5_spmv. Returns the number of partial slots the launches wrote.
 int slab_spmv(SpmvAmdCgSlab* s, bool with_dot, bool overlap, const int* skip,
-              const double* input = nullptr, hipEvent_t spmv_done = nullptr, const ResidualOut* init = nullptr) {
+              const double* input = nullptr, hipEvent_t spmv_done = nullptr, const ResidualOut* init = nullptr, bool x_zero = false) {
     const SlabCsr& A = s->A.view;
     const double* in = input ? input : s->p;
     double* part = ((with_dot && s->fused_dot) || init) ? s->partials_spmv : nullptr;
@@ -790,7 +810,7 @@ int slab_spmv(SpmvAmdCgSlab* s, bool with_dot, bool overlap, const int* skip,
     } else if (hi <= lo || (lo == 0 && hi == s->n_local) || (part == nullptr && !overlap)) {
         // one launch: a slab without halo rows, or of one or two grid rows, or a plain y = A x with the halos already in place
         if (overlap) HIP_CHECK(hipStreamWaitEvent(s->compute, s->ev_halo_done, 0));
-        used = launch_stencil5_spmv(A, s->plan_whole, in, s->Ap, 1.0, part, skip, s->shape.reverse, s->compute, init, s->sym());
+        used = launch_stencil5_spmv(A, s->plan_whole, in, s->Ap, 1.0, part, skip, s->shape.reverse, s->compute, init, s->sym(), x_zero);
         if (s->tl_after_interior) HIP_CHECK(hipEventRecord(s->tl_after_interior, s->compute));
     } else {
         // rows whose north and south neighbours are local run under the halo exchange; the first / last grid
@@ -970,6 +990,11 @@ struct LoopShape {
     // neighbours that owns its matrix, the direction ring, no detailed timers, a whole-slab plan on the block kernel whose slow
     // blocks are at most 1 / 16 of its blocks. The direction stage then enqueues no vector launch and late bulk has nothing to split.
     bool fused_direction = false;
+    // The two ends of a solve on a slab without neighbours that owns its matrix and takes the initial residual from the first
+    // SpMV's launch (fuse_init_residual). zero_start: x0 holds the library's own zeros (x0_known_zero), and that launch requests
+    // no x value on interior grid rows. r0_in_ring (any x0): the launch stores r0 once, as p0 into ring slot 0, and the
+    // r update of iteration 0 reads it there and writes r out of place; from iteration 1 on nothing differs.
+    bool zero_start = false, r0_in_ring = false;
     int slots = 1;           // direction ring length; 1 = the in-place x / p update
     EdgeRows edges{0, 0, 0}; // pipeline: [0, count_a) and [second, second + count_b)
     size_t bulk_lo = 0, bulk_hi = 0;  // the rows of the direction update that are not edge rows
@@ -990,6 +1015,10 @@ LoopShape loop_shape(const SpmvAmdCgSlab* s, const CGConfigMultiGPU* config) {
     L.fused_direction = s->fused_direction != 0 && !L.multi && s->op == nullptr && L.slots > 1 && !L.detail &&
                         direction_spmv_available(s, /*cap=*/s->fused_direction != 2);
     L.late = s->late_bulk && !L.detail && L.slots > 1 && !L.fused_direction;
+    // (ring mode only, like fused_direction: the in-place form keeps every launch it had)
+    const bool own_ends = !L.multi && s->op == nullptr && L.slots > 1 && s->fuse_init_residual;
+    L.zero_start = own_ends && s->x0_known_zero && s->zero_start_part(1);
+    L.r0_in_ring = own_ends && s->zero_start_part(2);
     // Early halo (round 3): the two edge ranges are rounded OUTWARDS to 4 KiB (512 doubles), so that the launch over the rest
     // starts on a 4 KiB boundary like every whole-vector launch does: with the ranges cut exactly at the grid row, the rest of a
     // 15 000-column slab started 64 bytes off a 128-byte line and its direction update ran 20-30 % slower (485 vs 386 us at
@@ -1008,6 +1037,13 @@ LoopShape loop_shape(const SpmvAmdCgSlab* s, const CGConfigMultiGPU* config) {
         L.bulk_lo = 0, L.bulk_hi = nl;
     }
     return L;
+}
+
+// The first SpMV of a solve on a slab that takes the initial residual from it (fuse_init_residual): r0 = b - A x0 into ring slot 0
+// (p0) and, unless the shape keeps it there alone, into r; the r0.r0 partials into partials_spmv. Returns the partial slots written.
+int slab_initial_residual(SpmvAmdCgSlab* s, const LoopShape& L, bool halo_in_flight) {
+    const ResidualOut init{s->b, L.r0_in_ring ? nullptr : s->r, s->ring[0]};
+    return slab_spmv(s, /*with_dot=*/false, halo_in_flight, nullptr, s->x0, nullptr, &init, L.zero_start);
 }
 
 // Every halo row of every halo-carrying buffer (x0's, the direction ring's) set to NaN (all bits one). A correct loop receives
@@ -1187,7 +1223,10 @@ extern "C" SpmvAmdCgSlab* spmv_amd_cg_slab_create_stencil5_as(int n, int as_rank
 extern "C" int spmv_amd_cg_slab_set_vectors(SpmvAmdCgSlab* s, const double* b_full,
                                             const double* x0_full) {
     if (b_full) upload(s->b, b_full + s->row_offset, (size_t)s->n_local);
-    if (x0_full) upload(s->x0, x0_full + s->row_offset, (size_t)s->n_local);
+    if (x0_full) {  // the caller's values, whatever they are: never looked at (NULL: x0 keeps its contents, and the flag with them)
+        upload(s->x0, x0_full + s->row_offset, (size_t)s->n_local);
+        s->x0_known_zero = false;
+    }
     return 0;
 }
 
@@ -1256,6 +1295,10 @@ struct SolveRun {
     void mark(int iteration, int k) {
         if (timeline) HIP_CHECK(hipEventRecord(tl_event(s->tl_compute, mark_index(iteration, k)), s->compute));
     }
+
+    // what a flush of x starts from: x itself, the stored x0 for the solve's first window -- or nothing (null: the chain starts from
+    // 0.0 in registers) where x0 holds the library's own zeros
+    const double* flush_from() const { return window_start > 0 ? s->x : (s->x0_known_zero && s->zero_start_part(4) ? nullptr : s->x0); }
 
     void begin();
     void initial_residual();
@@ -1353,9 +1396,8 @@ void SolveRun::initial_residual() {
     if (s->fuse_init_residual) {
         // row-lds slabs: r0 = b - A x0, p0 = r0 and the r0.r0 partials come out of the SpMV launch itself (A x0 is
         // never written out and read back: 16 B/row less, once per solve)
-        const ResidualOut init{s->b, s->r, s->p};
         int used = 0;
-        timed(&stats->time_initial_r_ms, nullptr, [&] { used = slab_spmv(s, /*with_dot=*/false, halo_in_flight, nullptr, s->x0, nullptr, &init); });
+        timed(&stats->time_initial_r_ms, nullptr, [&] { used = slab_initial_residual(s, L, halo_in_flight); });
         timed(&stats->time_dot_rs_initial_ms, nullptr, [&] { reduce_spmv_partials(s, used, &s->d_s->rr_new, nullptr, nullptr, 0, L.mailbox); });
     } else {
         slab_spmv(s, /*with_dot=*/false, halo_in_flight, nullptr, s->x0);
@@ -1435,7 +1477,11 @@ void SolveRun::stage_update_r() {
     s->enqueued_stage = "r update";
     TraceScope range(trace, "BLAS_AXPY");
     timed(&stats->time_blas1_ms, &stats->time_axpy_update_r_ms,
-          [&] { launch_cg_update_r(nl, s->d_s, s->Ap, s->r, s->partials_blas, s->compute, !backward); });
+          [&] {
+              // r0_in_ring: r0 lies in ring slot 0 alone (p0 = r0, stored once): the update of iteration 0 reads it there
+              if (L.r0_in_ring && enqueued == 0) launch_cg_update_r_from(nl, s->d_s, s->Ap, s->ring[0], s->r, s->partials_blas, s->compute, !backward);
+              else launch_cg_update_r(nl, s->d_s, s->Ap, s->r, s->partials_blas, s->compute, !backward);
+          });
     mark(enqueued, 4);
 }
 
@@ -1533,7 +1579,7 @@ void SolveRun::stage_direction_and_halo() {
         // (alpha of this iteration is already on the stream: the step above wrote it)
         if (enqueued - window_start == L.slots) {
             timed(&stats->time_blas1_ms, nullptr, [&] {
-                launch_cg_flush_x(nl, s->d_alpha_ring, ring_view, L.slots, window_start % L.slots, L.slots, window_start == 0 ? s->x0 : s->x, s->x, s->compute,
+                launch_cg_flush_x(nl, s->d_alpha_ring, ring_view, L.slots, window_start % L.slots, L.slots, flush_from(), s->x, s->compute,
                                   s->d_s, window_start);
             });
             window_start = enqueued;
@@ -1665,8 +1711,8 @@ void SolveRun::finish() {
     if (timeline) HIP_CHECK(hipEventRecord(tl_event(s->tl_compute, tl_flush), s->compute));
     if (L.slots > 1 && enqueued > window_start)  // x <- x + the directions of the last window
         timed(&stats->time_blas1_ms, nullptr, [&] {
-            launch_cg_flush_x(nl, s->d_alpha_ring, ring_view, L.slots, window_start % L.slots, enqueued - window_start, window_start == 0 ? s->x0 : s->x,
-                              s->x, s->compute, s->d_s, window_start);
+            launch_cg_flush_x(nl, s->d_alpha_ring, ring_view, L.slots, window_start % L.slots, enqueued - window_start, flush_from(), s->x, s->compute, s->d_s,
+                              window_start);
         });
     s->p = s->ring[0];
     if (enqueued == 0)  // no iteration ran (max_iters == 0): the solution is the initial guess
@@ -1861,6 +1907,8 @@ extern "C" int spmv_amd_cg_slab_set_option(SpmvAmdCgSlab* s, const char* name, l
         if (value < 0 || value > 2) return -1;
         s->fused_direction = (int)value;
     }
+    else if (strcmp(name, "zero_start_parts") == 0) s->zero_start_parts = (int)value & 7;  // which parts "zero_start" 1 switches on: 1 | 2 | 4 (the field says which is which)
+    else if (strcmp(name, "zero_start") == 0) s->zero_start = value != 0;  // 0: x0 always loaded, r0 stored twice (the launches of before)
     else if (strcmp(name, "spmv_with_dot") == 0) s->spmv_with_dot = value != 0;  // spmv() in its in-loop form: p.Ap partials and their sum too
     else return -1;
     return 0;
@@ -1932,6 +1980,38 @@ extern "C" int spmv_amd_cg_slab_direction_spmv(SpmvAmdCgSlab* s, const double* r
     *pAp = sc.pAp;
     s->p = s->ring[0];
     return used;
+}
+
+// (LAB build only.) The initial stage of a solve -- the first SpMV's launch and the reduction of its partials -- once, on the slab's
+// stored b and x0, in the form a solve would take now. Returns the form: bit 0 = no x value requested on interior grid rows
+// (LoopShape::zero_start), bit 1 = r0 stored once, as p0 (LoopShape::r0_in_ring). r0 == NULL: only that, nothing is launched.
+// Otherwise r0 (n_local doubles) = the residual from where it lives (p0 with bit 1, else r), r_vec (n_local doubles, may be null) =
+// the r vector, filled with NaN beforehand (with bit 1 it stays NaN), partials (min(count, cap) doubles; *count = how many the launch
+// writes) and *rr = their reduced sum. -1: a slab with neighbours or one whose first SpMV does not write the residual.
+extern "C" int spmv_amd_cg_slab_initial_stage(SpmvAmdCgSlab* s, double* r0, double* r_vec, double* partials, int cap, int* count, double* rr) {
+    const CGConfigMultiGPU any = {1, 0.0, 0, 0};
+    const LoopShape L = loop_shape(s, &any);
+    const int form = (L.zero_start ? 1 : 0) | (L.r0_in_ring ? 2 : 0);
+    if (r0 == nullptr) return form;
+    if (L.multi || !s->fuse_init_residual) return -1;
+    const size_t nl = (size_t)s->n_local;
+    HIP_CHECK(hipMemsetAsync(s->d_s, 0, sizeof(CgScalars), s->compute));
+    HIP_CHECK(hipMemsetAsync(s->r, 0xFF, nl * sizeof(double), s->compute));
+    HIP_CHECK(hipMemsetAsync(s->ring[0], 0xFF, nl * sizeof(double), s->compute));
+    HIP_CHECK(hipMemsetAsync(s->partials_spmv, 0xFF, (size_t)s->partials_cap * sizeof(double), s->compute));
+    s->shape.reverse = false;
+    s->reduce_mailbox = nullptr;
+    const int used = slab_initial_residual(s, L, /*halo_in_flight=*/false);
+    reduce_spmv_partials(s, used, &s->d_s->rr_new, nullptr, nullptr, 0, nullptr);
+    HIP_CHECK(hipStreamSynchronize(s->compute));
+    HIP_CHECK(hipGetLastError());
+    download(r0, L.r0_in_ring ? s->ring[0] : s->r, nl);
+    if (r_vec != nullptr) download(r_vec, s->r, nl);
+    if (partials != nullptr && cap > 0) download(partials, s->partials_spmv, (size_t)std::min(used, cap));
+    if (count != nullptr) *count = used;
+    HIP_CHECK(hipMemcpy(rr, &s->d_s->rr_new, sizeof(double), hipMemcpyDeviceToHost));
+    s->p = s->ring[0];
+    return form;
 }
 
 // (LAB build only.) The tile class map as creation wrote it: one byte per row-lds tile at [local grid row * tiles per grid row +
@@ -2106,6 +2186,7 @@ int cg_solve_on_operator(SpmvOperator* op, int n, const double* b, double* x, co
     SpmvAmdCgSlab* s = g_workspace;
     upload(s->b, b, (size_t)n);
     upload(s->x0, x, (size_t)n);
+    s->x0_known_zero = false;
     const CGConfigMultiGPU cfg = {config.max_iters, config.tolerance, config.verbose, config.enable_detailed_timers};
     CGStatsMultiGPU st;
     if (spmv_amd_cg_slab_solve(s, &cfg, &st) != 0) return 1;

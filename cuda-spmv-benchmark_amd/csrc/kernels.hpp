@@ -99,6 +99,7 @@ Stencil5Plan plan_stencil5(const SlabCsr& m, int first_row, int last_row, Stenci
 int rowlds_xcd_run_rule(int n);  // the untuned run length of row-lds tiles per XCD for an n x n grid
 // The first SpMV of a CG solve fused with the initial residual (row-lds plans only): instead of storing y = A x the
 // launch writes r = b - A x and p = r and one partial of r.r per wave into d_dot_partials.
+// r == nullptr: the value is stored once, as p (the caller reads r0 from there).
 struct ResidualOut {
     const double* b;
     double* r;
@@ -156,9 +157,12 @@ void launch_verify_sym_planes(const SlabCsr& m, const SymPlanes& planes, int* d_
 // planes (may be null; row-lds plans only): the symmetric coefficient form.
 // A row-lds plan with a block map (Stencil5Plan) takes block tiles -- stencil5_rowlds_block_kernel, the same rows and partial slots --
 // when the launch wants dot partials, has no `init` and `planes` carries a class map; every other launch is the one-row kernel's.
+// x_zero (with `init`, row-lds plans, slabs without halo rows): the caller knows that x holds +0.0 in every element. The launch then
+// requests no x value on grid rows 1 .. n-2 -- the five operands are 0.0 in registers and the same chains run on them, so signed
+// zeros and the NaN of an infinite coefficient come out as they did -- and reads x only on the grid's first and last grid row.
 int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& plan, const double* x, double* y, double alpha,
                          double* d_dot_partials, const int* d_skip_flag, bool reverse, hipStream_t stream,
-                         const ResidualOut* init = nullptr, const SymPlanes* planes = nullptr);
+                         const ResidualOut* init = nullptr, const SymPlanes* planes = nullptr, bool x_zero = false);
 // The CG direction update inside the in-loop block SpMV (stencil5_direction_block_kernel; slabs without neighbours whose plan has
 // a block map): p_out = direction(r, s->beta, p_in), y = alpha A p_out and the p_out . (A p_out) partials of the plan's slots, in one
 // launch over the block tiles plus one over `slow_list` -- the indices of the range's block tiles whose map byte is 0 (device
@@ -334,6 +338,9 @@ void launch_cg_init_residual(size_t n, const double* b, const double* Ap, double
 // reverse: workgroups walk the vectors from the end (same results, same partial slots).
 void launch_cg_update_r(size_t n, const CgScalars* s, const double* Ap, double* r, double* partials,
                         hipStream_t stream, bool reverse = false);
+// The same out of place: r_out = r_in - alpha Ap, same partials (iteration 0 of a solve whose r0 lies in the direction ring alone).
+void launch_cg_update_r_from(size_t n, const CgScalars* s, const double* Ap, const double* r_in, double* r_out, double* partials,
+                             hipStream_t stream, bool reverse = false);
 // x += alpha p (the update of iteration `iteration`), then p = 1.0*r + beta*p unless that iteration
 // converged; one pass over p (axpy + axpby of cg_solver_mgpu_partitioned.cu:598,682 fused).
 // x = x_in + alpha p: x_in is x, or the stored initial guess in the first iteration of a solve.
@@ -354,6 +361,7 @@ struct RingSlots {
 };
 // s (may be null) / window_start: only terms of iterations window_start + 1 ... s->iterations are added (a host that ran one
 // iteration ahead may ask for one term too many: that iteration was never counted and its alpha slot holds an old value).
+// x_in == nullptr: x_in is known to hold +0.0 everywhere and is not loaded; the chain starts from 0.0, same bits.
 void launch_cg_flush_x(size_t n, const double* alphas, const RingSlots& ring, int slots, int first_slot, int count,
                        const double* x_in, double* x, hipStream_t stream, const CgScalars* s = nullptr, int window_start = 0);
 int cg_partial_count(size_t n);  // partial slots written by the two reducing kernels above

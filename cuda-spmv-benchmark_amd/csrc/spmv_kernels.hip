@@ -173,7 +173,11 @@ constexpr int kLdsTileCols = 128;
 // tile_class (kSym only; rowlds_tile_class, the same value in every lane): 1 = every coefficient this tile multiplies equals the
 // slab-wide quintuple in sp bit for bit (checked against the CSR at creation): the tile loads no coefficient, keeps no LDS copy of
 // E and runs the same chains on the quintuple -- 0 B/row of coefficients. 0 = the plane path.
-template <int kMode, bool kFreshHalo = false, bool kSym = false>
+// kZeroX (kMode 2 only; stencil5_rowlds_zero_kernel): the caller knows that x holds +0.0 in every element. An interior grid row
+// requests no x value: centre, W, E, N and S are 0.0 in registers, the LDS copy of the x row and its W / E exchange are gone, and
+// everything behind the loads is the code of the other form -- the chains still multiply every coefficient by its zero, so -0.0
+// and the NaN of an infinite coefficient come out bit for bit. The grid's first and last grid row read x as before.
+template <int kMode, bool kFreshHalo = false, bool kSym = false, bool kZeroX = false>
 __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __restrict__ x, double* __restrict__ y, double alpha,
                                             int li, int gi, int j0, int lane, int skip, double* __restrict__ strip,
                                             double* __restrict__ xrow, const ResidualOut& res, double* dot, const SymPlanes& sp = SymPlanes{},
@@ -216,12 +220,14 @@ __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __re
             xc[h] = xw[h] = xe[h] = xn[h] = xs[h] = bv[h] = 0.0;
             if (j < n) {
                 const double* __restrict__ xl = x + ((long long)li * n + j);
-                xc[h] = xl[0];
-                if (kFreshHalo) {
-                    xn[h] = published_by_any_agent(reinterpret_cast<const unsigned long long*>(xl - n));
-                    xs[h] = published_by_any_agent(reinterpret_cast<const unsigned long long*>(xl + n));
-                } else {
-                    xn[h] = xl[-n], xs[h] = xl[n];
+                if constexpr (!kZeroX) {
+                    xc[h] = xl[0];
+                    if (kFreshHalo) {
+                        xn[h] = published_by_any_agent(reinterpret_cast<const unsigned long long*>(xl - n));
+                        xs[h] = published_by_any_agent(reinterpret_cast<const unsigned long long*>(xl + n));
+                    } else {
+                        xn[h] = xl[-n], xs[h] = xl[n];
+                    }
                 }
                 if (kInit) bv[h] = __builtin_nontemporal_load(res.b + ((long long)li * n + j));
                 if constexpr (kCheb) {  // streams read once per step, requested with the x loads (before the skip flag is tested)
@@ -230,8 +236,10 @@ __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __re
                     cd[h] = __builtin_nontemporal_load(step.d + ((long long)li * n + j));
                 }
                 // only the tile's two outer neighbours come from memory; the rest from the LDS copy below
-                if (h == 0 && lane == 0 && j > 0) xw[0] = xl[-1];
-                if (h == 1 && lane == 63 && j < n - 1) xe[1] = xl[1];
+                if constexpr (!kZeroX) {
+                    if (h == 0 && lane == 0 && j > 0) xw[0] = xl[-1];
+                    if (h == 1 && lane == 63 && j < n - 1) xe[1] = xl[1];
+                }
             }
         }
         // Everything behind the tile's loads, for a tile that streams its coefficients (kUniform false: the CSR strip or the planes)
@@ -249,10 +257,12 @@ __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __re
 #pragma unroll
                 for (int k = 0; k < 10; ++k) strip[64 * k + lane] = c[k];
             }
-            xrow[1 + lane] = xc[0];
-            xrow[65 + lane] = xc[1];
+            if constexpr (!kZeroX) {
+                xrow[1 + lane] = xc[0];
+                xrow[65 + lane] = xc[1];
+            }
             wave_lds_sync();
-            tile_west_east(xrow, lane, j0, n, xw[0], xe[1], xw, xe);
+            if constexpr (!kZeroX) tile_west_east(xrow, lane, j0, n, xw[0], xe[1], xw, xe);  // else: W and E are the zeros they were set to
             double cwv[2] = {0.0, 0.0};  // kSym: W = E[i - 1]
             if constexpr (kSym && !kUniform) {
                 cwv[0] = strip[lane];
@@ -302,7 +312,7 @@ __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __re
                     } else if (kInit) {
                         const long long lr = (long long)li * n + j;
                         const double rv = fma(-1.0, alpha * sum, bv[h]);
-                        __builtin_nontemporal_store(rv, res.r + lr);
+                        if (res.r != nullptr) __builtin_nontemporal_store(rv, res.r + lr);  // null: r0 is stored once, as p0
                         res.p[lr] = rv;  // plain: the next SpMV's neighbour loads re-use these lines
                         dot_acc = fma(rv, rv, dot_acc);
                     } else {
@@ -358,7 +368,7 @@ __device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __re
                     if (step.last) dot_acc = fma(rl, zn, dot_acc);
                 } else if (kInit) {
                     const double rv = fma(-1.0, alpha * sum, res.b[lr]);
-                    res.r[lr] = rv;
+                    if (res.r != nullptr) res.r[lr] = rv;
                     res.p[lr] = rv;
                     dot_acc = fma(rv, rv, dot_acc);
                 } else {
@@ -421,6 +431,29 @@ __global__ __launch_bounds__(64) void stencil5_rowlds_kernel(
                           : rowlds_tile<kMode>(m, x, y, alpha, li, gfirst + li, col_tile * kLdsTileCols, (int)threadIdx.x, skip, strip, xrow, res, &dot);
     if (!live) return;
     if (kMode != 0 && threadIdx.x == 0) dot_partials[tile] = dot;
+}
+
+// The first SpMV of a solve whose initial guess is known to be zero (rowlds_tile, kZeroX): r = b - alpha A 0, p = r and one partial
+// of r.r per tile, in the tiles, XCD runs and partial slots of stencil5_rowlds_kernel<2>. A kernel of its own: the other instances
+// keep their code.
+__global__ __launch_bounds__(64) void stencil5_rowlds_zero_kernel(SlabCsr m, const double* __restrict__ x, double alpha, int gi_lo, int row_step,
+                                                                  int gfirst, int col_tiles, int total_tiles, int run, int reverse,
+                                                                  double* __restrict__ dot_partials, ResidualOut res, SymPlanes sp) {
+    __shared__ double strip[5 * kLdsTileCols];
+    __shared__ double xrow[kLdsTileCols + 2];
+    const int tile = rowlds_tile_of_block((int)blockIdx.x, run, total_tiles, reverse);
+    if (tile < 0) return;
+    const int row_group = tile / col_tiles;
+    const int col_tile = tile - row_group * col_tiles;
+    const int li = gi_lo + row_group * row_step;
+    const int uniform = rowlds_tile_class(sp, li, col_tiles, col_tile);
+    double dot = 0.0;
+    if (sp.ce != nullptr)
+        rowlds_tile<2, false, true, true>(m, x, nullptr, alpha, li, gfirst + li, col_tile * kLdsTileCols, (int)threadIdx.x, 0, strip, xrow, res, &dot, sp,
+                                          uniform);
+    else
+        rowlds_tile<2, false, false, true>(m, x, nullptr, alpha, li, gfirst + li, col_tile * kLdsTileCols, (int)threadIdx.x, 0, strip, xrow, res, &dot);
+    if (threadIdx.x == 0) dot_partials[tile] = dot;
 }
 
 // A block tile that is not fast (block map byte 0: a tile that streams the planes, the grid's first or last grid row, a short last
@@ -1332,11 +1365,16 @@ namespace {
 // the row-lds kernel over `tiles` tiles: `row_step` grid rows between consecutive row groups (1: a contiguous range)
 void launch_rowlds(const SlabCsr& m, const Stencil5Plan& p, const double* x, double* y, double alpha, int gi_lo, int row_step,
                    int tiles, double* d_dot_partials, const int* d_skip_flag, bool reverse, hipStream_t stream, const ResidualOut* init,
-                   const SymPlanes* planes, const ChebStep* step = nullptr) {
+                   const SymPlanes* planes, const ChebStep* step = nullptr, bool x_zero = false) {
     const dim3 grid((unsigned)xcd_padded_grid(tiles, p.xcd_run));
     const int gfirst = m.row_offset / m.grid_size;
     const ResidualOut res = init ? *init : ResidualOut{nullptr, nullptr, nullptr};
     const SymPlanes sp = planes ? *planes : SymPlanes{};
+    if (x_zero && init != nullptr && step == nullptr) {
+        hipLaunchKernelGGL(stencil5_rowlds_zero_kernel, grid, dim3(64), 0, stream, m, x, alpha, gi_lo, row_step, gfirst, p.row_blocks, tiles,
+                           p.xcd_run, reverse ? 1 : 0, d_dot_partials, res, sp);
+        return;
+    }
 #define SPMV_AMD_LAUNCH_ROWLDS(MODE)                                                                                   \
     hipLaunchKernelGGL((stencil5_rowlds_kernel<MODE>), grid, dim3(64), 0, stream, m, x, y, alpha, gi_lo, row_step, gfirst, \
                        p.row_blocks, tiles, p.xcd_run, reverse ? 1 : 0, d_dot_partials, d_skip_flag, res, sp, cs)
@@ -1377,7 +1415,7 @@ void launch_block_map(const unsigned char* cls, const Stencil5Plan& p, unsigned 
 
 int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& p, const double* x, double* y, double alpha,
                          double* d_dot_partials, const int* d_skip_flag, bool reverse, hipStream_t stream,
-                         const ResidualOut* init, const SymPlanes* planes) {
+                         const ResidualOut* init, const SymPlanes* planes, bool x_zero) {
     if (p.last_row <= p.first_row) return 0;
     if (init != nullptr && (p.variant != Stencil5Variant::RowLds || d_dot_partials == nullptr)) {
         fprintf(stderr, "[spmv] the fused initial residual exists for the row-lds kernel only\n");
@@ -1389,7 +1427,7 @@ int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& p, const double* 
         // the in-loop SpMV of a slab with a class map: block tiles (the same rows, the same partial slots)
         launch_rowlds_block(m, p, x, y, alpha, d_dot_partials, d_skip_flag, reverse, stream, *planes);
     } else if (p.variant == Stencil5Variant::RowLds) {
-        launch_rowlds(m, p, x, y, alpha, p.gi_lo, 1, p.partials, d_dot_partials, d_skip_flag, reverse, stream, init, planes);
+        launch_rowlds(m, p, x, y, alpha, p.gi_lo, 1, p.partials, d_dot_partials, d_skip_flag, reverse, stream, init, planes, nullptr, x_zero);
     } else if (p.variant == Stencil5Variant::RowDirect) {
         const dim3 grid((unsigned)p.partials);
         if (dot)

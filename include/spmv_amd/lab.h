@@ -43,7 +43,10 @@ SpmvAmdCgSlab* spmv_amd_cg_slab_create_stencil5_as(int n, int as_rank, int as_wo
  * it takes the kernel the loop takes), and "fused_direction" 0 / 1 / 2 (the product's SPMV_AMD_FUSED_DIRECTION: 0 = the direction
  * update is a launch of its own, 1 = it rides in the next block SpMV's launch where the slab is eligible -- one rank, ring > 1, no
  * detailed timers, a block map whose slow blocks are at most 1/16 of its blocks --, 2 = the same without the 1/16 cap;
- * spmv_amd_cg_slab_loop_shape says which ran; results are bit-identical). Returns 0, or -1 for an unknown name or value. */
+ * spmv_amd_cg_slab_loop_shape says which ran; results are bit-identical) and "zero_start" 0/1 (the product's SPMV_AMD_ZERO_START:
+ * 0 = the first SpMV and the flush of x always load x0 and the first launch stores r0 twice; spmv_amd_cg_slab_initial_stage says
+ * which form a solve takes; results are bit-identical) with "zero_start_parts" 0..7 (a field of the LAB build only: which parts "zero_start" 1 switches on, for A/B
+ * runs of each: 1 = the first launch without x loads, 2 = r0 stored once, 4 = the flush of x without x0; default 7). Returns 0, or -1 for an unknown name or value. */
 int spmv_amd_cg_slab_set_option(SpmvAmdCgSlab* s, const char* name, long long value);
 
 /* The tile class map of a slab in the symmetric form as creation wrote it (spmv_amd_cg_slab_uniform_tiles): one byte per row-lds
@@ -74,6 +77,15 @@ int spmv_amd_cg_slab_spmv_dot(const SpmvAmdCgSlab* s, double* pAp, double* parti
  * a slab that cannot take the launch (neighbours, ring 1, no block map). */
 int spmv_amd_cg_slab_direction_spmv(SpmvAmdCgSlab* s, const double* r, const double* p_in, double beta, int iteration_matches, int converged,
                                     double* p_out, double* Ap, double* pAp, double* partials, int cap);
+
+/* The initial stage of a solve alone, once, on the slab's stored b and x0: the first SpMV's launch (r0 = b - A x0, p0 = r0, one
+ * partial of r0.r0 per 128 x 1 tile) and the reduction of the partials, in the form a solve would take now. Returns the form: bit 0 =
+ * x0 holds the zeros the library wrote and the launch requests no x value on interior grid rows; bit 1 = r0 is stored once, as p0,
+ * and iteration 0's r update reads it there. r0 == NULL: only that, nothing is launched. Otherwise r0 (n_local doubles) = the
+ * residual from where it lives, r_vec (n_local doubles, may be NULL) = the r vector, NaN where the launch did not write (all of it
+ * with bit 1), partials (min(*count, cap) doubles) and *rr = the reduced sum. -1 on a slab with neighbours or one whose first SpMV
+ * does not write the residual. */
+int spmv_amd_cg_slab_initial_stage(SpmvAmdCgSlab* s, double* r0, double* r_vec, double* partials, int cap, int* count, double* rr);
 
 /* The device scalars of one preconditioned solve (csrc/pcg.hip keeps the same record on the device). */
 typedef struct SpmvAmdPcgScalars {
