@@ -5,7 +5,7 @@
 // --precond runs the preconditioned solver (spmv_amd_pcg_solve_device, device only); its JSON / CSV carry the mode string
 // <operator>+<kind>. Without it the binary takes cg_solve_device / cg_solve as before. chebyshev = the polynomial preconditioner
 // of degree 4, chebyshev:K of degree K (0..32), both on the automatic interval; the mode string is <operator>+chebyshev<K>.
-// multigrid = the aggregation multigrid V(1, 1) cycle (stencil5-csr only), multigrid:NU the V(NU, NU) cycle (0..8); the mode string is
+// multigrid = the aggregation multigrid V(1, 1) cycle (stencil5-csr, and stencil7-csr through the 3-D creator), multigrid:NU the V(NU, NU) cycle (0..8); the mode string is
 // <operator>+multigrid<NU>.
 // (The reference's own main, unmodified, also builds against this library: INTEGRATION.md. Unlike
 // it, this binary restarts every timed solve from x0 = 0 instead of from the warm-up's solution.)
@@ -50,7 +50,7 @@ int pcg_runs(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, const d
 }  // namespace
 
 int main(int argc, char** argv) {
-    const char *matrix = nullptr, *modes_text = "stencil5-csr", *json = nullptr, *csv = nullptr, *precond = nullptr;
+    const char *matrix = nullptr, *modes_text = nullptr, *json = nullptr, *csv = nullptr, *precond = nullptr;
     int stencil = 0, stencil3d = 0, maxiter = 1000, timers = 0;
     bool device = true;
     double tol = 1e-6;
@@ -68,6 +68,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--timers")) timers = 1;
         else if (argv[i][0] != '-') matrix = argv[i];
     }
+    if (modes_text == nullptr) modes_text = stencil3d > 0 ? "stencil7-csr" : "stencil5-csr";  // the grid's own operator
     if (!matrix && stencil <= 0 && stencil3d <= 0) {
         fprintf(stderr, "Usage: %s <matrix.mtx | --stencil=N | --stencil3d=N> [--mode=<modes>] [--host|--device] [--tol=] [--maxiter=] [--timers] [--json=] [--csv=]\n", argv[0]);
         return 1;
@@ -136,7 +137,9 @@ int main(int argc, char** argv) {
         CGStats st;
         if (precond) {
             int bad_row = -1;
-            SpmvAmdPrecond* pm = mg_degree >= 0     ? spmv_amd_precond_create_multigrid(op, mg_degree, 0, &bad_row)
+            const bool is3d = op->name != nullptr && !strcmp(op->name, "stencil7-csr");
+            SpmvAmdPrecond* pm = mg_degree >= 0 && is3d ? spmv_amd_precond_create_multigrid3d(op, mg_degree, 0, &bad_row)
+                                 : mg_degree >= 0     ? spmv_amd_precond_create_multigrid(op, mg_degree, 0, &bad_row)
                                  : cheb_degree >= 0 ? spmv_amd_precond_create_chebyshev(op, cheb_degree, 0.0, 0.0, &bad_row)
                                                     : spmv_amd_precond_create(op, precond, &bad_row);
             if (pm == nullptr) {

@@ -122,7 +122,7 @@ DECLARED_SYMBOLS = [
     "spmv_amd_cg_solve_mgpu_partitioned", "spmv_amd_reset_host_matrices", "spmv_amd_interior_csr_offset",
     "spmv_amd_partition_rows", "spmv_amd_device_count", "spmv_amd_set_device", "spmv_amd_current_device", "spmv_amd_stream_ceiling", "spmv_amd_stream_ceiling_mix", "spmv_amd_device_alloc", "spmv_amd_device_free",
     "spmv_amd_copy_to_device", "spmv_amd_copy_to_host", "spmv_amd_device_fill_f64", "spmv_amd_device_synchronize",
-    "spmv_amd_init_stencil5_synthetic", "spmv_amd_init_stencil7_synthetic", "spmv_amd_stencil7_row_start", "spmv_amd_ellpack_run_device_scaled", "spmv_amd_download_device_csr", "spmv_amd_time_run_device", "spmv_amd_operator_variant",
+    "spmv_amd_init_stencil5_synthetic", "spmv_amd_init_stencil7_synthetic", "spmv_amd_init_stencil7_synthetic_values", "spmv_amd_stencil7_row_start", "spmv_amd_ellpack_run_device_scaled", "spmv_amd_download_device_csr", "spmv_amd_time_run_device", "spmv_amd_operator_variant",
     "spmv_amd_operator_select_variant", "spmv_amd_cg_last_history", "spmv_amd_comm_unique_id", "spmv_amd_comm_create_rccl",
     "spmv_amd_comm_create_staged", "spmv_amd_comm_destroy", "spmv_amd_comm_set_world", "spmv_amd_comm_rank", "spmv_amd_comm_size", "spmv_amd_comm_selftest",
     "spmv_amd_comm_barrier", "spmv_amd_comm_transport", "spmv_amd_comm_transport_ranks",
@@ -139,6 +139,7 @@ DECLARED_SYMBOLS = [
     "spmv_amd_precond_inverse_diagonal", "spmv_amd_pcg_solve_device", "spmv_amd_pcg_last_history", "spmv_amd_pcg_release_workspace",
     "spmv_amd_precond_create_chebyshev", "spmv_amd_precond_chebyshev_info", "spmv_amd_precond_apply_device",
     "spmv_amd_precond_create_multigrid", "spmv_amd_precond_multigrid_info",
+    "spmv_amd_precond_create_multigrid3d", "spmv_amd_precond_multigrid_dimension",
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
 LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_cg_slab_block_map", "spmv_amd_cg_slab_slow_blocks",
@@ -204,6 +205,7 @@ def lib():
     L.spmv_amd_device_fill_f64.argtypes = [C.c_void_p, C.c_size_t, C.c_double]
     L.spmv_amd_init_stencil5_synthetic.argtypes = [C.c_char_p, C.c_int]
     L.spmv_amd_init_stencil7_synthetic.argtypes = [C.c_char_p, C.c_int]
+    L.spmv_amd_init_stencil7_synthetic_values.argtypes = [C.c_char_p, C.c_int, C.c_double, C.c_double]
     L.spmv_amd_stencil7_row_start.argtypes = [C.c_longlong, C.c_int]
     L.spmv_amd_stencil7_row_start.restype = C.c_longlong
     L.write_matrix_market_stencil7.argtypes = [C.c_int, C.c_char_p]
@@ -463,10 +465,11 @@ class Operator:
         self.rows = self.cols = n * n
         return rc
 
-    def init_synthetic3d(self, n):
-        """spmv_amd_init_stencil7_synthetic: the n x n x n 7-point generator matrix built in HBM ("stencil7-csr", "cusparse-csr")."""
+    def init_synthetic3d(self, n, center=7.0, off=-1.0):
+        """spmv_amd_init_stencil7_synthetic_values: the n x n x n 7-point matrix (centre 7, neighbours -1 by default: the generator
+        matrix; 6 / -1 is Poisson) built in HBM ("stencil7-csr", "cusparse-csr")."""
         require_gpu()
-        rc = lib().spmv_amd_init_stencil7_synthetic(self.name.encode(), int(n))
+        rc = lib().spmv_amd_init_stencil7_synthetic_values(self.name.encode(), int(n), float(center), float(off))
         self.rows = self.cols = n * n * n
         return rc
 
@@ -652,6 +655,10 @@ def _pcg_lib():
         L.spmv_amd_precond_create_multigrid.argtypes = [C.POINTER(SpmvOperator), C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.spmv_amd_precond_create_multigrid.restype = C.c_void_p
         L.spmv_amd_precond_multigrid_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int]
+        L.spmv_amd_precond_create_multigrid3d.argtypes = [C.POINTER(SpmvOperator), C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.spmv_amd_precond_create_multigrid3d.restype = C.c_void_p
+        L.spmv_amd_precond_multigrid_dimension.argtypes = [C.c_void_p]
+        L.spmv_amd_precond_multigrid_dimension.restype = C.c_int
         L._pcg_sigs = True
     return L
 
@@ -709,6 +716,21 @@ class Precond:
             raise err
         return cls(_handle=h, _n=op.rows)
 
+    @classmethod
+    def multigrid3d(cls, op, smoother_degree=1, max_levels=0):
+        """spmv_amd_precond_create_multigrid3d (stencil7-csr on a verified 7-point stencil only); max_levels 0 = automatic."""
+        bad = C.c_int(-2)
+        h = _pcg_lib().spmv_amd_precond_create_multigrid3d(op.op, smoother_degree, max_levels, C.byref(bad))
+        if not h:
+            err = ValueError(f"precond_create_multigrid3d({op.name}, {smoother_degree}, {max_levels}) refused, bad_row = {bad.value}")
+            err.bad_row = bad.value
+            raise err
+        return cls(_handle=h, _n=op.rows)
+
+    def multigrid_dimension(self):
+        """2 or 3 for a multigrid preconditioner, 0 for another kind."""
+        return _pcg_lib().spmv_amd_precond_multigrid_dimension(self.handle)
+
     @property
     def kind(self):
         return _pcg_lib().spmv_amd_precond_kind(self.handle).decode()
@@ -727,7 +749,7 @@ class Precond:
         if not is_lab():
             raise RuntimeError("the level matrices are read through the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
         n = self.multigrid_info()[1][level]
-        rows, nnz = n * n, 5 * n * n - 4 * n
+        rows, nnz = (n ** 3, 7 * n ** 3 - 6 * n * n) if self.multigrid_dimension() == 3 else (n * n, 5 * n * n - 4 * n)
         rp, ci = np.zeros(rows + 1, dtype=np.int32), np.zeros(nnz, dtype=np.int32)
         va, dinv = np.zeros(nnz), np.zeros(rows)
         if lib().spmv_amd_precond_multigrid_level_csr(self.handle, level, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, dinv.ctypes.data) != 0:

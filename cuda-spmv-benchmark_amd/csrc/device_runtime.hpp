@@ -170,6 +170,7 @@ FusedSpmv fused_spmv_of(const SpmvOperator* op);
 struct ChebSpmv {
     const SlabCsr* view = nullptr;  // with plan: the stencil forms
     const Stencil5Plan* plan = nullptr;
+    const Stencil7Plan* plan7 = nullptr;  // with view: a 3-D multigrid level (never fused: partials stays 0)
     const SpmvOperator* op = nullptr;  // without them: run_device
     int partials = 0;                  // slots a fused last step writes; 0: the step is not fused
 };
@@ -196,6 +197,16 @@ struct DiagonalSource {
     int width = 0;
 };
 DiagonalSource diagonal_source_of(const SpmvOperator* op);
+// What stencil7-csr knows of its matrix beyond the view (whose grid_size / verified_stencil mean "2-D 5-point"): n of the verified
+// n^3 grid (0 otherwise) and whether its launch plan is the CSR loop (an unverified matrix, or the forced variant). Zeros for
+// every other operator. Host state only (no HIP call); operators.hip.
+struct Stencil7Source {
+    int grid = 0;
+    bool verified = false;
+    bool csr_loop = true;
+    const char* plan_name = "none";
+};
+Stencil7Source stencil7_source_of(const SpmvOperator* op);
 
 // Device-resident CSR of one operator or one slab (owning).
 struct DeviceCsr {

@@ -18,6 +18,10 @@
 //   correct      z = fma(2.0, e_c[agg(i)], z)   (the Galerkin operator of 2 x 2 aggregates is twice the re-discretised one)
 //   post-smooth  nu + 1 step-form updates from the guess z: the first with (g, h) = (c0, 0.0), then steps 1 .. nu
 // Pre- and post-smoother are the same symmetric polynomial: M^-1 is symmetric.
+//
+// The same hierarchy, cycle and creator serve the 3-D operator stencil7-csr (spmv_amd_precond_create_multigrid3d, DESIGN.md section
+// 17): a level carries its dimension; a 3-D level is a complete 7-point CSR made by 2 x 2 x 2 aggregation, its three launches are
+// multigrid3d.hip's, and it smooths with launch_stencil7_spmv on a Stencil7Plan of its own + pcg.hip's streaming step.
 #include <limits.h>
 #include <math.h>
 #include <stdint.h>
@@ -25,6 +29,7 @@
 
 #include <vector>
 
+#include "multigrid3d.hpp"
 #include "precond.hpp"
 #include "stencil_geometry.hpp"
 #include "stencil_row_device.hpp"
@@ -272,17 +277,19 @@ SlabCsr stencil_view(int n, const int* row_ptr, const int* col_idx, const double
     return v;
 }
 
-bool verified(SlabCsr& v) {
+// the structure check of a level's view: the complete 5-point pattern of v.grid_size (dim 2), the complete 7-point one of n^3 (dim 3)
+bool verified(SlabCsr& v, int dim = 2, int n = 0) {
     int* d_mismatch = device_try_alloc<int>(1);
     if (d_mismatch == nullptr) return fail("no device memory for the structure check");
     HIP_CHECK(hipMemsetAsync(d_mismatch, 0, sizeof(int), kStream));
-    launch_verify_stencil5_csr(v, d_mismatch, kStream);
+    if (dim == 3) launch_verify_stencil7_csr(v, n, d_mismatch, kStream);
+    else launch_verify_stencil5_csr(v, d_mismatch, kStream);
     HIP_CHECK(hipGetLastError());
     int mismatch = 1;
     download(&mismatch, d_mismatch, 1);  // synchronises
     device_release(d_mismatch);
-    v.verified_stencil = mismatch == 0;
-    return v.verified_stencil;
+    if (dim == 2) v.verified_stencil = mismatch == 0;  // the view's flag means "2-D 5-point"
+    return mismatch == 0;
 }
 
 }  // namespace
@@ -290,26 +297,40 @@ bool verified(SlabCsr& v) {
 namespace spmv_amd {
 
 struct MgLevel {
+    int dim = 2;          // 2: an n x n 5-point stencil; 3: an n x n x n 7-point one
     int n = 0, rows = 0;  // the grid and its rows
     DeviceCsr A;          // levels above 0 (level 0 reads the operator's own CSR)
     SlabCsr view;
-    Stencil5Plan plan;
+    Stencil5Plan plan;    // dim 2
+    Stencil7Plan plan7;   // dim 3
     double* dinv = nullptr;  // level 0's belongs to the SpmvAmdPrecond
     bool own_dinv = true;
     double lambda_max = 0.0;
     int degree = 0;
     double coef[1 + 2 * kCoarsestDegree] = {0.0};
     double *r = nullptr, *d = nullptr, *z = nullptr;  // r: levels above 0
-    double* aux = nullptr;  // a row-lds plan: z' of the fused step; every other plan: w = A z
-    bool fused() const { return plan.variant == Stencil5Variant::RowLds; }
+    double* aux = nullptr;  // a 2-D row-lds plan: z' of the fused step; every other plan: w = A z
+    bool fused() const { return dim == 2 && plan.variant == Stencil5Variant::RowLds; }
     ChebSpmv spmv() const {  // how this level runs A z (device_runtime.hpp)
         ChebSpmv a;
-        a.view = &view, a.plan = &plan, a.partials = fused() ? plan.partials : 0;
+        a.view = &view;
+        if (dim == 3) a.plan7 = &plan7;
+        else a.plan = &plan, a.partials = fused() ? plan.partials : 0;
         return a;
+    }
+    long long nnz() const { return dim == 3 ? stencil7_nnz(n) : stencil_nnz(n); }
+    void residual_restrict(const double* zv, const double* rv, double* rc) const {
+        if (dim == 3) launch_residual_restrict3d(view, n, zv, rv, rc);
+        else launch_residual_restrict(view, zv, rv, rc);
+    }
+    void prolong_correct(const double* ec, double* zv) const {
+        if (dim == 3) launch_prolong_correct3d(n, ec, zv);
+        else launch_prolong_correct(n, ec, zv);
     }
 };
 
 struct MgHierarchy {
+    int dim = 2;
     std::vector<MgLevel> levels;
     int smoother_degree = 0;
     double* partials = nullptr;  // the r.z partials of level 0's last update
@@ -353,9 +374,9 @@ struct CycleRun {
         (void)cheb_steps(c, L.degree, L.coef, coarsest && top);  // pre-smoothing (the coarsest level: its solve); no run_device here
         if (!coarsest) {
             MgLevel& C = h->levels[(size_t)l + 1];
-            stage_run(T, &StageTimers::t_spmv, [&] { launch_residual_restrict(L.view, c.z, r, C.r); });
+            stage_run(T, &StageTimers::t_spmv, [&] { L.residual_restrict(c.z, r, C.r); });
             const double* const ec = level(l + 1, C.r);
-            stage_run(T, &StageTimers::t_blas, [&] { launch_prolong_correct(L.n, ec, c.z); });
+            stage_run(T, &StageTimers::t_blas, [&] { L.prolong_correct(ec, c.z); });
             (void)cheb_step(c, L.coef[0], 0.0, top && L.degree == 0);  // post-smoothing from the guess z: term 0 in step form
             (void)cheb_steps(c, L.degree, L.coef, top);
         }
@@ -382,13 +403,18 @@ bool finish_level(MgHierarchy* h, int l, const LaunchShape& shape, int* bad_row)
     const bool coarsest = l + 1 == (int)h->levels.size();
     if (l > 0) {
         const MgLevel& F = h->levels[(size_t)l - 1];
-        L.A.allocate((size_t)L.rows, (size_t)stencil_nnz(L.n));
-        launch_coarsen(F.view, L.n, L.A.row_ptr, L.A.col_idx, L.A.values);
+        L.A.allocate((size_t)L.rows, (size_t)L.nnz());
+        if (L.dim == 3) {
+            launch_coarsen3d(F.view, F.n, L.A.row_ptr, L.A.col_idx, L.A.values);
+            L.A.view = stencil7_view(L.n, L.A.row_ptr, L.A.col_idx, L.A.values);
+        } else {
+            launch_coarsen(F.view, L.n, L.A.row_ptr, L.A.col_idx, L.A.values);
+            L.A.view = stencil_view(L.n, L.A.row_ptr, L.A.col_idx, L.A.values);
+        }
         HIP_CHECK(hipGetLastError());
-        L.A.view = stencil_view(L.n, L.A.row_ptr, L.A.col_idx, L.A.values);
         L.view = L.A.view;
-        if (!verified(L.view)) {
-            fprintf(stderr, "[PCG] multigrid: the coarse operator of level %d is not a complete 5-point stencil: refused\n", l);
+        if (!verified(L.view, L.dim, L.n)) {
+            fprintf(stderr, "[PCG] multigrid: the coarse operator of level %d is not a complete %d-point stencil: refused\n", l, L.dim == 3 ? 7 : 5);
             return false;
         }
         L.A.view = L.view;
@@ -406,7 +432,8 @@ bool finish_level(MgHierarchy* h, int l, const LaunchShape& shape, int* bad_row)
     }
     L.degree = coarsest ? kCoarsestDegree : h->smoother_degree;
     chebyshev_coefficients(L.degree, lmin, L.lambda_max, L.coef);
-    L.plan = plan_stencil5(L.view, 0, L.rows, Stencil5Variant::Auto, shape);
+    if (L.dim == 3) L.plan7 = plan_stencil7(L.view, L.n, true, Stencil7Variant::Auto, shape.knobs);  // row-lds from the knob's grid, row-direct below
+    else L.plan = plan_stencil5(L.view, 0, L.rows, Stencil5Variant::Auto, shape);
     if (l > 0) L.r = device_try_alloc<double>((size_t)L.rows);
     L.d = device_try_alloc<double>((size_t)L.rows);
     L.z = device_try_alloc<double>((size_t)L.rows);
@@ -415,9 +442,8 @@ bool finish_level(MgHierarchy* h, int l, const LaunchShape& shape, int* bad_row)
     return true;
 }
 
-}  // namespace
-
-extern "C" SpmvAmdPrecond* spmv_amd_precond_create_multigrid(SpmvOperator* op, int smoother_degree, int max_levels, int* bad_row) {
+// The one creator: dim 2 for stencil5-csr (spmv_amd_precond_create_multigrid), dim 3 for stencil7-csr (..._multigrid3d).
+SpmvAmdPrecond* create_multigrid(SpmvOperator* op, int dim, int smoother_degree, int max_levels, int* bad_row) {
     // argument checks: all before the first HIP call
     if (bad_row != nullptr) *bad_row = -1;
     if (op == nullptr) return fail("null operator"), nullptr;
@@ -430,23 +456,35 @@ extern "C" SpmvAmdPrecond* spmv_amd_precond_create_multigrid(SpmvOperator* op, i
         return nullptr;
     }
     DiagonalSource d;
-    if (!creation_source(op, "multigrid: ", "stencil5-csr: refused", /*stencil_only=*/true, &d)) return nullptr;
-    const int n0 = d.csr.grid_size;
-    if (!d.csr.verified_stencil || n0 < 1 || d.rows != d.cols || (long long)n0 * n0 != d.rows) {
-        fprintf(stderr, "[PCG] multigrid: the matrix of operator '%s' is not a verified complete 5-point stencil: refused\n", op->name);
-        return nullptr;
+    if (!creation_source(op, "multigrid: ", dim == 3 ? "stencil7-csr: refused" : "stencil5-csr: refused", /*stencil_dim=*/dim, &d)) return nullptr;
+    int n0 = 0;
+    if (dim == 3) {
+        const Stencil7Source s7 = stencil7_source_of(op);  // the 3-D geometry lives in the operator, not in the view
+        n0 = s7.grid;
+        if (!s7.verified || s7.csr_loop || n0 < 2 || d.rows != d.cols || (long long)n0 * n0 * n0 != d.rows) {
+            fprintf(stderr, "[PCG] multigrid: operator '%s' does not run a verified complete 7-point stencil (its plan is %s): refused\n", op->name,
+                    s7.plan_name);
+            return nullptr;
+        }
+    } else {
+        n0 = d.csr.grid_size;
+        if (!d.csr.verified_stencil || n0 < 1 || d.rows != d.cols || (long long)n0 * n0 != d.rows) {
+            fprintf(stderr, "[PCG] multigrid: the matrix of operator '%s' is not a verified complete 5-point stencil: refused\n", op->name);
+            return nullptr;
+        }
     }
 
     MgHierarchy* h = new MgHierarchy();
+    h->dim = dim;
     h->smoother_degree = smoother_degree;
     size_t need = 0;
     for (int n = n0;; n = coarse_grid_of(n)) {
         MgLevel L;
-        L.n = n, L.rows = n * n;
+        L.dim = dim, L.n = n, L.rows = dim == 3 ? n * n * n : n * n;
         const bool top = h->levels.empty();
         h->levels.push_back(L);
         need += (size_t)L.rows * sizeof(double) * (top ? 3 : 5);
-        if (!top) need += (size_t)stencil_nnz(n) * (sizeof(double) + sizeof(int)) + ((size_t)L.rows + 1) * sizeof(int) + 3 * 4096;
+        if (!top) need += (size_t)L.nnz() * (sizeof(double) + sizeof(int)) + ((size_t)L.rows + 1) * sizeof(int) + 3 * 4096;
         if (n <= kCoarsestGrid || (max_levels > 0 && (int)h->levels.size() == max_levels)) break;
     }
     SpmvAmdPrecond* pm = nullptr;
@@ -493,6 +531,20 @@ extern "C" SpmvAmdPrecond* spmv_amd_precond_create_multigrid(SpmvOperator* op, i
     return pm;
 }
 
+}  // namespace
+
+extern "C" SpmvAmdPrecond* spmv_amd_precond_create_multigrid(SpmvOperator* op, int smoother_degree, int max_levels, int* bad_row) {
+    return create_multigrid(op, 2, smoother_degree, max_levels, bad_row);
+}
+
+extern "C" SpmvAmdPrecond* spmv_amd_precond_create_multigrid3d(SpmvOperator* op, int smoother_degree, int max_levels, int* bad_row) {
+    return create_multigrid(op, 3, smoother_degree, max_levels, bad_row);
+}
+
+extern "C" int spmv_amd_precond_multigrid_dimension(const SpmvAmdPrecond* m) {
+    return m != nullptr && m->kind == kMultigrid && m->mg != nullptr ? m->mg->dim : 0;
+}
+
 extern "C" int spmv_amd_precond_multigrid_info(const SpmvAmdPrecond* m, int* levels, int* smoother_degree, int* grids, double* lambda_max, int cap) {
     if (m == nullptr || m->kind != kMultigrid || m->mg == nullptr) return 0;
     const int count = (int)m->mg->levels.size();
@@ -520,14 +572,22 @@ extern "C" int spmv_amd_precond_multigrid_level_csr(const SpmvAmdPrecond* m, int
 
 extern "C" int spmv_amd_mg_stage(const char* stage, SpmvAmdMgStageArgs* a) {
     // argument checks: all before the first HIP call
-    enum { kCoarsen, kRestrict, kProlong } st;
-    if (stage == nullptr) return fail("stage: none named (coarsen, residual_restrict, prolong)"), 1;
-    if (!strcmp(stage, "coarsen")) st = kCoarsen;
-    else if (!strcmp(stage, "residual_restrict")) st = kRestrict;
-    else if (!strcmp(stage, "prolong")) st = kProlong;
-    else return fail("stage: unknown (coarsen, residual_restrict, prolong)"), 1;
+    enum Stage { kCoarsen, kRestrict, kProlong };
+    static const struct {
+        const char* name;
+        Stage st;
+        int dim;
+    } kStages[] = {{"coarsen", kCoarsen, 2},   {"residual_restrict", kRestrict, 2},   {"prolong", kProlong, 2},
+                   {"coarsen3d", kCoarsen, 3}, {"residual_restrict3d", kRestrict, 3}, {"prolong3d", kProlong, 3}};
+    if (stage == nullptr) return fail("stage: none named (coarsen, residual_restrict, prolong, and each with the suffix 3d)"), 1;
+    Stage st = kCoarsen;
+    int dim = 0;
+    for (const auto& known : kStages)
+        if (!strcmp(stage, known.name)) st = known.st, dim = known.dim;
+    if (dim == 0) return fail("stage: unknown (coarsen, residual_restrict, prolong, and each with the suffix 3d)"), 1;
     if (a == nullptr) return fail("stage: null arguments"), 1;
-    if (a->n < 2 || a->n > 46340) return fail("stage: the fine grid is outside 2..46340"), 1;
+    if (dim == 2 && (a->n < 2 || a->n > 46340)) return fail("stage: the fine grid is outside 2..46340"), 1;
+    if (dim == 3 && (a->n < 2 || a->n > kStencil7MaxGrid)) return fail("stage: the fine grid of a 3-D stage is outside 2..674"), 1;
     const auto aligned = [](const void* p, uintptr_t to) { return p != nullptr && ((uintptr_t)p & (to - 1)) == 0; };
     if (st != kProlong && (!aligned(a->row_ptr, 4) || !aligned(a->col_idx, 4) || !aligned(a->values, 8)))
         return fail("stage: a null or misaligned CSR array"), 1;
@@ -539,7 +599,13 @@ extern "C" int spmv_amd_mg_stage(const char* stage, SpmvAmdMgStageArgs* a) {
         return fail("stage: z must be 16-byte aligned, the coarse vector 8-byte aligned"), 1;
 
     if (st == kProlong) {
-        launch_prolong_correct(a->n, a->coarse, a->z);
+        if (dim == 3) launch_prolong_correct3d(a->n, a->coarse, a->z);
+        else launch_prolong_correct(a->n, a->coarse, a->z);
+    } else if (dim == 3) {
+        SlabCsr fine = stencil7_view(a->n, a->row_ptr, a->col_idx, a->values);
+        if (!verified(fine, 3, a->n)) return fail("stage: the CSR is not a complete 7-point stencil of that grid: refused"), 1;
+        if (st == kCoarsen) launch_coarsen3d(fine, a->n, a->out_row_ptr, a->out_col_idx, a->out_values);
+        else launch_residual_restrict3d(fine, a->n, a->z, a->r, a->coarse);
     } else {
         SlabCsr fine = stencil_view(a->n, a->row_ptr, a->col_idx, a->values);
         if (!verified(fine)) return fail("stage: the CSR is not a complete 5-point stencil of that grid: refused"), 1;

@@ -104,11 +104,11 @@ struct CsrBackedOperator {
         ready = true;
         return 0;
     }
-    // the n^3 generator matrix (centre 7, neighbours -1) built in HBM; the caller has checked stencil7_fits_int32(n)
-    int init_synthetic7(int n) {
+    // the n^3 generator matrix (centre 7, neighbours -1 unless told otherwise) built in HBM; the caller has checked stencil7_fits_int32(n)
+    int init_synthetic7(int n, double center = 7.0, double off = -1.0) {
         drop();
         rows = cols = n * n * n;
-        A.generate_stencil7(n, 7.0, -1.0, kDefaultStream);
+        A.generate_stencil7(n, center, off, kDefaultStream);
         spmv_amd_reset_host_matrices();
         csr_mat.nb_rows = rows;
         csr_mat.nb_cols = cols;
@@ -632,6 +632,16 @@ DiagonalSource diagonal_source_of(const SpmvOperator* op) {
     }
     return d;
 }
+
+Stencil7Source stencil7_source_of(const SpmvOperator* op) {
+    Stencil7Source s;
+    if (own_operator_of(op).csr == &g_stencil7 && g_stencil7.ready) {
+        s.grid = g_stencil7.grid7, s.verified = g_stencil7.verified7;
+        s.csr_loop = g_stencil7.plan7.variant == Stencil7Variant::CsrLoop;
+        s.plan_name = g_stencil7.plan7.name;
+    }
+    return s;
+}
 }  // namespace spmv_amd
 
 extern "C" SpmvOperator* get_operator(const char* mode) {
@@ -666,7 +676,9 @@ extern "C" int spmv_amd_init_stencil5_synthetic(const char* mode, int n) {
     }
 }
 
-extern "C" int spmv_amd_init_stencil7_synthetic(const char* mode, int n) {
+extern "C" int spmv_amd_init_stencil7_synthetic(const char* mode, int n) { return spmv_amd_init_stencil7_synthetic_values(mode, n, 7.0, -1.0); }
+
+extern "C" int spmv_amd_init_stencil7_synthetic_values(const char* mode, int n, double center, double off) {
     // rows = n^3 and nnz = 7 n^3 - 6 n^2 must fit int32 (n <= 674): decided before any HIP call
     if (!stencil7_fits_int32(n)) {
         fprintf(stderr, "[stencil7] grid %d^3 is refused: 1 <= n <= 674 keeps rows and nnz inside 32-bit CSR indices\n", n);
@@ -674,12 +686,12 @@ extern "C" int spmv_amd_init_stencil7_synthetic(const char* mode, int n) {
     }
     switch (which_operator(mode)) {
         case Which::Stencil7:
-            if (g_stencil7.init_synthetic7(n) != 0) return EXIT_FAILURE;
+            if (g_stencil7.init_synthetic7(n, center, off) != 0) return EXIT_FAILURE;
             stencil7_verify(n);
             stencil7_pick_variant();
             return 0;
         case Which::Csr:
-            if (g_csr.init_synthetic7(n) != 0) return EXIT_FAILURE;
+            if (g_csr.init_synthetic7(n, center, off) != 0) return EXIT_FAILURE;
             HIP_CHECK(hipStreamSynchronize(kDefaultStream));
             g_csr.variant_name = csr_variant_name(g_csr.csr_variant, g_csr.A.view);
             csr_place_output();

@@ -1,5 +1,5 @@
 // pcg.hip -- preconditioned CG over any SpmvOperator: kinds "none" and "jacobi" (DESIGN.md section 13), a Chebyshev polynomial in
-// D^-1 A (section 14) and one multigrid V-cycle (multigrid.hip, section 15; stencil5-csr only).
+// D^-1 A (section 14) and one multigrid V-cycle (multigrid.hip, section 15: stencil5-csr; section 17: stencil7-csr).
 //
 // One loop, spmv_amd_pcg_solve_device: the algebra of cg_solve_device with z = M^-1 r, the same stopping rule (true residual
 // ||r_k|| / ||r_0|| < tol, strict, the converging iteration counted), statistics and timer rule (solve_common.hpp has those,
@@ -26,8 +26,8 @@
 //   k steps, each testing that flag before it works: the converging iteration streams nothing | sum of r.z + beta
 // A step is cheb_step (declared in precond.hpp), the only place that chooses its form from a ChebSpmv: on a row-lds stencil plan ONE
 // launch (spmv_kernels.hip, kMode 3: A z never leaves the registers, z' goes to a second vector; 144 + 88 k bytes per interior row and
-// iteration), on any other stencil plan the SpMV behind the flag + cheb_step_kernel, else run_device + cheb_step_kernel (112 per
-// step). The loop calls it timed, with the flag and the step counter; spmv_amd_precond_apply_device untimed without a flag; the
+// iteration), on any other stencil plan -- 2-D, or a 3-D multigrid level's Stencil7Plan -- the SpMV behind the flag +
+// cheb_step_kernel, else run_device + cheb_step_kernel (112 per step). The loop calls it timed, with the flag and the step counter; spmv_amd_precond_apply_device untimed without a flag; the
 // multigrid cycle on each of its levels.
 //
 // "multigrid" (mg_first, mg_next): z = M^-1 r is one V-cycle on the preconditioner's own levels:
@@ -546,7 +546,9 @@ bool spmv_amd::cheb_step(ChebRun& c, double g, double h, bool last) {
     }
     bool ok = true;
     stage_run(c.T, &StageTimers::t_spmv, [&] {
-        if (c.a.plan != nullptr) {
+        if (c.a.plan7 != nullptr) {
+            (void)launch_stencil7_spmv(*c.a.view, *c.a.plan7, c.z, c.aux, 1.0, nullptr, c.stop, false, kStream);
+        } else if (c.a.plan != nullptr) {
             (void)launch_stencil5_spmv(*c.a.view, *c.a.plan, c.z, c.aux, 1.0, nullptr, c.stop, false, kStream);
         } else if (c.a.op->run_device(c.z, c.aux) != 0) {
             fprintf(stderr, "[PCG] operator '%s': run_device failed\n", c.a.op->name);
@@ -734,7 +736,7 @@ extern "C" SpmvAmdPrecond* spmv_amd_precond_create(SpmvOperator* op, const char*
     }
     if (op == nullptr) return fail("null operator"), nullptr;
     DiagonalSource d;
-    if (!creation_source(op, "", "one of this library's: pass its diagonal to spmv_amd_precond_create_from_diagonal", false, &d)) return nullptr;
+    if (!creation_source(op, "", "one of this library's: pass its diagonal to spmv_amd_precond_create_from_diagonal", 0, &d)) return nullptr;
     SpmvAmdPrecond* pm = nullptr;
     if (k == kNone) {
         pm = new SpmvAmdPrecond();
@@ -781,12 +783,14 @@ double gershgorin_of_csr(const SlabCsr& m, int n, const double* dinv) { return g
 void launch_cheb_term0_apply(size_t n, const double* r, const double* dinv, double c0, double* d, double* z) {
     launch_cheb_term0<2>(n, nullptr, nullptr, nullptr, dinv, c0, const_cast<double*>(r), d, z, false, nullptr);
 }
-bool creation_source(const SpmvOperator* op, const char* label, const char* not_ours, bool stencil_only, DiagonalSource* d) {
+bool creation_source(const SpmvOperator* op, const char* label, const char* not_ours, int stencil_dim, DiagonalSource* d) {
     *d = diagonal_source_of(op);
     bool ours = d->owner != nullptr;
-    if (stencil_only)
+    if (stencil_dim == 2)
         ours = ours && d->kind == DiagonalSource::Csr && op->name != nullptr &&
                (strcmp(op->name, "stencil5-csr") == 0 || strcmp(op->name, "stencil5-halo-mgpu") == 0);
+    else if (stencil_dim == 3)
+        ours = ours && d->kind == DiagonalSource::Csr && op->name != nullptr && strcmp(op->name, "stencil7-csr") == 0;
     if (!ours) {
         fprintf(stderr, "[PCG] %soperator '%s' is not %s\n", label, op->name ? op->name : "?", not_ours);
         return false;
@@ -795,7 +799,7 @@ bool creation_source(const SpmvOperator* op, const char* label, const char* not_
         fprintf(stderr, "[PCG] operator '%s' used before init\n", op->name);
         return false;
     }
-    if (!stencil_only && d->rows != d->cols) {  // a stencil-only creator has a stricter test of its own behind this
+    if (stencil_dim == 0 && d->rows != d->cols) {  // a stencil-only creator has a stricter test of its own behind this
         fprintf(stderr, "[PCG] operator '%s' holds a %d x %d matrix: a square one is required\n", op->name, d->rows, d->cols);
         return false;
     }
@@ -829,7 +833,7 @@ extern "C" SpmvAmdPrecond* spmv_amd_precond_create_chebyshev(SpmvOperator* op, i
     if (!isfinite(lambda_min) || !isfinite(lambda_max)) return fail("chebyshev: a bound that is not finite: refused"), nullptr;
     if (lambda_min > 0.0 && lambda_max > 0.0 && !(lambda_min < lambda_max)) return fail("chebyshev: lambda_min >= lambda_max: refused"), nullptr;
     DiagonalSource d;
-    if (!creation_source(op, "chebyshev: ", "one of this library's: refused", false, &d)) return nullptr;
+    if (!creation_source(op, "chebyshev: ", "one of this library's: refused", 0, &d)) return nullptr;
     const int src = d.kind == DiagonalSource::Csr ? 0 : 1;
     SpmvAmdPrecond* pm = make_jacobi(src, d.csr, d.idx, d.val, d.width, d.rows, bad_row);
     if (pm == nullptr) return nullptr;

@@ -51,15 +51,15 @@ double gershgorin_of_csr(const SlabCsr& m, int n, const double* dinv);
 // c0, h_1, g_1, ... of the degree-k Chebyshev polynomial on [lmin, lmax] (api.h states the operations).
 void chebyshev_coefficients(int degree, double lmin, double lmax, double* coef);
 // What the creators check of their (non-null) operator, in this order, before the first HIP call: not one of this library's -- or,
-// stencil_only, not the stencil operator -- said as "[PCG] <label>operator '<name>' is not <not_ours>"; used before init; not square
-// (left to a stencil_only creator's stricter test behind this). False: refused, said on stderr.
-bool creation_source(const SpmvOperator* op, const char* label, const char* not_ours, bool stencil_only, DiagonalSource* d);
+// stencil_dim 2 / 3, not the 2-D / 3-D stencil operator (0: any of ours) -- said as "[PCG] <label>operator '<name>' is not <not_ours>"; used before init; not square
+// (left to a stencil creator's stricter test behind this). False: refused, said on stderr.
+bool creation_source(const SpmvOperator* op, const char* label, const char* not_ours, int stencil_dim, DiagonalSource* d);
 // term 0 from a residual that is only read: u = dinv r ; d = c0 u ; z = d (cheb_term0_kernel<2>, no partials)
 void launch_cheb_term0_apply(size_t n, const double* r, const double* dinv, double c0, double* d, double* z);
 
 // One Chebyshev application in flight on one operator or level: t = fma(-1, A z, r) ; u = dinv t ; d = fma(g, u, h d) ; z = z + d.
 // cheb_step runs one step in the form `a` allows: on a row-lds plan the fused launch (z' goes to aux, then z and aux change places),
-// on any other stencil plan the SpMV that tests `stop` into aux and cheb_step_kernel, else run_device into aux and cheb_step_kernel.
+// on any other stencil plan (2-D, or the Stencil7Plan of a 3-D level) the SpMV that tests `stop` into aux and cheb_step_kernel, else run_device into aux and cheb_step_kernel.
 // last: the step also writes the partials of r.z to `partials` and records them in rz_partials / rz_count. False: run_device
 // refused (said on stderr). cheb_steps runs steps 1 .. degree from coef (c0, h_1, g_1, ...); report: step `degree` is a last one.
 struct ChebRun {

@@ -205,6 +205,9 @@ int spmv_amd_init_stencil5_synthetic(const char* mode, int n);
  * default 64) and "stencil7/row-direct"; anything else initialises and runs the CSR kernels as "stencil7/csr-loop". Every row, in
  * every variant, is sum = 0.0 ; sum = fma(v[k], x[col[k]], sum) for ascending k ; y = sum: bit for bit the sequential CSR sum. */
 int spmv_amd_init_stencil7_synthetic(const char* mode, int n);
+/* The same with the centre and the neighbours' coefficient chosen by the caller (6.0 / -1.0: the Poisson matrix with Dirichlet
+ * boundaries): spmv_amd_init_stencil7_synthetic(mode, n) is this with 7.0 / -1.0. */
+int spmv_amd_init_stencil7_synthetic_values(const char* mode, int n, double center, double off);
 
 /* y = alpha*A*x + beta*y on an initialised "ellpack" / "stencil5-ellpack" operator: the full
  * contract of the kernel prototyped in reference include/spmv_stencil.h:25-42 (the operator table
@@ -357,9 +360,33 @@ int spmv_amd_precond_chebyshev_info(const SpmvAmdPrecond* m, int* degree, double
  * g = c0, h = 0.0 and d as step (1) left it, then steps 1..nu with (h_k, g_k).
  * The solve with this kind reads the iteration's verdict on the host before the cycle: the converging iteration runs none. */
 SpmvAmdPrecond* spmv_amd_precond_create_multigrid(SpmvOperator* op, int smoother_degree, int max_levels, int* bad_row);
-/* The number of levels, nu, and up to cap grids n_l and lambda_max_l; returns the number of levels, 0 for another kind (nothing is
- * written). Any out pointer may be NULL. */
+/* Kind "multigrid" for "stencil7-csr" (csrc/multigrid3d.hip): the cycle above on a hierarchy of 7-point stencils made
+ * by 2 x 2 x 2 aggregation of the operator's n^3 grid. The operator must run a verified complete 7-point stencil (n >= 2): any other
+ * operator ("stencil5-csr" included) and a "stencil7/csr-loop" plan (a matrix that is not the complete pattern, or the forced variant)
+ * are refused, like a null operator, a smoother_degree outside 0..8 and a max_levels outside 0..32, before any HIP call with
+ * *bad_row = -1; a diagonal entry on any level that breaks Jacobi's validity rule is refused after HIP work (the level is named on
+ * stderr, *bad_row = the row of that level). A refusal leaves no device memory behind. spmv_amd_precond_create_multigrid keeps
+ * refusing "stencil7-csr".
+ * Levels: level 0 is the operator's grid n_0; n_{l+1} = ceil(n_l / 2); aggregate (K, I, J) = the fine points (2K + c, 2I + a, 2J + b),
+ * c, a, b in {0, 1}, that exist (point (k, i, j) = row k n^2 + i n + j). Coarsening stops at the first level with n_l <= 8, or at max_levels.
+ * Coarse operator A_c = P^T A P, P piecewise constant, again a complete 7-point CSR ([D,N,W,C,E,S,U] = columns -n^2, -n, -1, 0, +1, +n,
+ * +n^2); every entry a sequential sum from 0.0 with plain additions: the members in the order (c, a, b) = (0,0,0), (0,0,1), (0,1,0),
+ * (0,1,1), (1,0,0), (1,0,1), (1,1,0), (1,1,1), each member's entries in CSR order, every entry added to the coarse entry of the
+ * aggregate its column lies in (D_c = the D entries of the four members with c = 0, in member order; U_c those of c = 1; N_c / S_c
+ * the N / S entries of a = 0 / a = 1; W_c / E_c the W / E entries of b = 0 / b = 1; C_c everything that stays inside, twenty-four
+ * terms in a full aggregate). A bit-symmetric fine matrix gives a bit-symmetric coarse one.
+ * Per level: as above -- dinv by the diagonal pass, lambda_max by the symmetric Gershgorin bound, the smoother of degree nu on
+ * [lambda_max / 4.0, lambda_max], the coarsest level by degree 8 on [lambda_max / 30.0, lambda_max] from a zero guess.
+ * Cycle: steps (1) to (5) above with  (2) r_c[K,I,J] = (((((((t000 + t001) + t010) + t011) + t100) + t101) + t110) + t111) over the
+ * members t_cab that exist, t_i = fma(-1.0, (A z)_i, r_i), (A z)_i the bits of stencil7-csr's SpMV for row i: for EVERY row, interior or
+ * not, sum = 0.0 ; sum = fma(v[k], z[col[k]], sum) for ascending k;  (4) z = fma(2.0, e_c[agg(i)], z): the factor stays 2.0, the Galerkin
+ * face coupling of 2 x 2 x 2 aggregates being twice the re-discretised one as in 2-D. */
+SpmvAmdPrecond* spmv_amd_precond_create_multigrid3d(SpmvOperator* op, int smoother_degree, int max_levels, int* bad_row);
+/* The number of levels, nu, and up to cap grids n_l (the edge of the n_l x n_l or n_l x n_l x n_l grid) and lambda_max_l; returns the
+ * number of levels, 0 for another kind (nothing is written). Any out pointer may be NULL. */
 int spmv_amd_precond_multigrid_info(const SpmvAmdPrecond* m, int* levels, int* smoother_degree, int* grids, double* lambda_max, int cap);
+/* 2 for a multigrid preconditioner of stencil5-csr, 3 for one of stencil7-csr, 0 for NULL or any other kind. */
+int spmv_amd_precond_multigrid_dimension(const SpmvAmdPrecond* m);
 /* z = M^-1 r on device vectors of n rows (16-byte aligned), any kind (none: copy, jacobi: dinv*r). d_z must not overlap d_r, which is
  * only read. rz (may be NULL): r.z summed by the solver's own fixed-shape reduction. The pair (op, m) is checked as by
  * spmv_amd_pcg_solve_device, before any HIP call. Work vectors live for the call only. Synchronises. Returns 0, non-zero for a refusal. */

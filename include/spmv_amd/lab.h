@@ -142,10 +142,11 @@ int spmv_amd_pcg_last_step_launches(void);
 /* Kind "multigrid" (csrc/multigrid.hip): the V-cycles the last solve's LOOP ran (the one behind the initial residual is not counted):
  * iterations - 1 for a solve that converged, iterations for one that reached max_iters. 0 after a solve of another kind. */
 int spmv_amd_pcg_last_multigrid_cycles(void);
-/* One level's CSR (rows + 1, nnz, nnz values: a complete 5-point stencil of the level's grid, spmv_amd_precond_multigrid_info) and
- * dinv (rows) copied to the host; any out pointer may be NULL. Non-zero for another kind or a level that does not exist. */
+/* One level's CSR (rows + 1, nnz, nnz values: a complete 5-point stencil of the level's grid, spmv_amd_precond_multigrid_info; a complete
+ * 7-point one of n_l^3 rows and 7 n_l^3 - 6 n_l^2 entries where spmv_amd_precond_multigrid_dimension is 3) and dinv (rows) copied to the host; any out pointer may be NULL. Non-zero for another kind or a level that does not exist. */
 int spmv_amd_precond_multigrid_level_csr(const SpmvAmdPrecond* m, int level, int* row_ptr, int* col_idx, double* values, double* dinv);
-/* Device pointers of one spmv_amd_mg_stage call; n = the FINE grid, the coarse grid is (n + 1) / 2. */
+/* Device pointers of one spmv_amd_mg_stage call; n = the FINE grid, the coarse grid is (n + 1) / 2. The 3-D stages read the same record:
+ * the CSR is then a complete 7-point stencil of n^3 rows, the vectors hold n^3 and ((n + 1) / 2)^3 values. */
 typedef struct SpmvAmdMgStageArgs {
     int n;
     const int* row_ptr;      /* coarsen, residual_restrict: the fine level's CSR, a complete 5-point stencil of grid n (checked) */
@@ -160,8 +161,10 @@ typedef struct SpmvAmdMgStageArgs {
 } SpmvAmdMgStageArgs;
 /* The multigrid cycle's own launches, one per call on the caller's device data, through the functions the cycle makes them with.
  * Every call synchronises. stage: "coarsen" (A_c = P^T A P), "residual_restrict" (r_c = P^T (r - A z) in one launch), "prolong"
- * (z = fma(2.0, e_c[agg(i)], z)). Refused before any HIP call: an unknown stage, null arguments, n outside 2..46340, a null or
- * misaligned pointer the stage needs; after the structure check: a CSR that is not the complete stencil. Returns 0 otherwise. */
+ * (z = fma(2.0, e_c[agg(i)], z)); "coarsen3d", "residual_restrict3d", "prolong3d": the same three of a 3-D level
+ * (csrc/multigrid3d.hip), with the 7-point structure check. Refused before any HIP call: an unknown stage, null arguments, n outside
+ * 2..46340 (a 3-D stage: 2..674), a null or misaligned pointer the stage needs; after the structure check: a CSR that is not the
+ * complete stencil. Returns 0 otherwise. */
 int spmv_amd_mg_stage(const char* stage, SpmvAmdMgStageArgs* a);
 
 /* Per-column state of a batched CG solve (csrc/multi_rhs.hpp keeps the same record on the device, one per column). */
