@@ -62,7 +62,7 @@ struct SpmvAmdComm {
     bool self_neighbour = false;
     bool exchanges_halos() const { return world > 1 || self_neighbour; }
     // What the first slab created on this communicator found when it solved a few iterations in both loop shapes
-    // (cg_slab.hip, verify_pipeline): 0 = not checked yet, 1 = the overlapped pipeline reproduced the plain order's residual
+    // (cg_slab_create.hip, verify_pipeline): 0 = not checked yet, 1 = the overlapped pipeline reproduced the plain order's residual
     // history bit for bit on every rank, -1 = it did not on some rank: every slab on this communicator runs the plain order.
     int pipeline_verdict = 0;
     virtual ~SpmvAmdComm() {}

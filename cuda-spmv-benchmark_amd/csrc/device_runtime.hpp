@@ -175,7 +175,7 @@ struct ChebSpmv {
     int partials = 0;                  // slots a fused last step writes; 0: the step is not fused
 };
 ChebSpmv cheb_spmv_of(const SpmvOperator* op);
-// Frees the vectors cg_solve_device keeps between calls (cg_slab.hip); called by every operator's free().
+// Frees the vectors cg_solve_device keeps between calls (cg_device.hip); called by every operator's free().
 void release_cg_workspace();
 // The same for the preconditioned solver (pcg.hip); the caller holds the workspace lock (release_cg_workspace does).
 void release_pcg_workspace_locked();

@@ -52,7 +52,7 @@ struct MultiOperand {
 };
 MultiOperand multi_operand_of(const SpmvOperator* op);
 
-// Holds the lock of the CG workspaces (cg_slab.hip) for its lifetime and marks this thread as the one inside a solve: the
+// Holds the lock of the CG workspaces (cg_device.hip) for its lifetime and marks this thread as the one inside a solve: the
 // batched solve obeys the same lock and the same "release asked from inside the solve" rule as cg_solve_device.
 class CgWorkspaceScope {
 public:

@@ -477,14 +477,14 @@ SpmvAmdCgSlab* spmv_amd_cg_slab_create(MatrixData* mat, SpmvAmdComm* comm);
 SpmvAmdCgSlab* spmv_amd_cg_slab_create_stencil5(int n, SpmvAmdComm* comm);
 /* Full-length host vectors as in the reference (each rank uploads its slab);
  * NULL keeps b = 1 / x0 = 0. While no x0 was ever passed, x0 holds the zeros the library wrote itself and most loads of it are
- * skipped (csrc/cg_slab.hip, x0_known_zero): the flush of x in ring mode does not read it, and on a slab without neighbours that
+ * skipped (csrc/cg_slab.hpp, x0_known_zero): the flush of x in ring mode does not read it, and on a slab without neighbours that
  * owns its matrix, in ring mode, the first SpMV reads it on the grid's first and last grid row only. Slabs with neighbours and the
  * in-place form (ring 1) still read it in the first SpMV, and a solve of no iterations copies it into x. SPMV_AMD_ZERO_START=0 at
  * creation: always loaded. A passed x0 is never inspected, zeros included. Results are bit-identical either way. */
 int spmv_amd_cg_slab_set_vectors(SpmvAmdCgSlab* s, const double* b_full, const double* x0_full);
 /* One solve from the stored x0; the timed region is the reference's
  * (cg_solver_mgpu_partitioned.cu:405-413 -> 728-731).
- * The loop has two shapes (csrc/cg_slab.hip, LoopShape), bit-identical in their results. PIPELINE (default on a slab with
+ * The loop has two shapes (csrc/slab_decisions.hpp, LoopShape), bit-identical in their results. PIPELINE (default on a slab with
  * neighbours): the halo exchange runs on a side stream under the interior rows' SpMV; the boundary rows wait inside their
  * launch for a device flag the side stream raises behind the receive, and the side stream's exchange waits for a device
  * flag the direction update's first workgroups raise. CONCURRENCY REQUIREMENT: those two waits spin (bounded: 20 s, or half of
@@ -531,7 +531,7 @@ int spmv_amd_cg_slab_time_spmv(SpmvAmdCgSlab* s, int reps, float* ms_each);
  * The direction-update stage is averaged over the launches that did work ("direction_updates": the converging
  * iteration's update is never needed -- the reference tests convergence before its p update, :652-676). */
 void spmv_amd_cg_slab_set_timeline(SpmvAmdCgSlab* s, int on);
-/* Placement at creation (csrc/cg_slab.hip). Slabs of >= 16 Mi rows place their coefficient stream by timing up to three
+/* Placement at creation (csrc/cg_slab_create.hip). Slabs of >= 16 Mi rows place their coefficient stream by timing up to three
  * allocations one region apart: {0, candidates timed, SpMV ms before, SpMV ms kept}. Returns 4, or 0 if it did not run.
  * Addresses only: results never change; a candidate that does not fit ends the trial, never the process. */
 int spmv_amd_cg_slab_placement(const SpmvAmdCgSlab* s, double* out, int cap);
@@ -542,7 +542,7 @@ int spmv_amd_cg_slab_tile_runs(const SpmvAmdCgSlab* s, double* out, int cap);
  * reference builds and uploads before its own, cg_solver_mgpu_partitioned.cu:303-413): {matrix to HBM (upload or generation),
  * streams + vectors, verification + launch plans, coefficient placement trial, tile-run trial}. Returns 5. */
 int spmv_amd_cg_slab_setup_ms(const SpmvAmdCgSlab* s, double* out, int cap);
-/* The coefficients the slab's SpMV streams (csrc/cg_slab.hip): 0 = its CSR values (40 B/row), 1 = the symmetric planes
+/* The coefficients the slab's SpMV streams (csrc/cg_slab.hpp): 0 = its CSR values (40 B/row), 1 = the symmetric planes
  * (24 B/row: C, E and S per row; W and N are the E of row i-1 and the S of row i-n). A slab takes the planes when it owns its
  * matrix, every launch is a row-lds launch and those W / N entries equal their CSR entries bit for bit (checked at creation);
  * the results are the CSR form's, bit for bit. */

@@ -1,4 +1,4 @@
-"""numpy restatement of the CG slab's block maps (csrc/spmv_kernels.hip block_map_kernel, csrc/cg_slab.hip build_block_maps;
+"""numpy restatement of the CG slab's block maps (csrc/spmv_kernels.hip block_map_kernel, csrc/cg_slab_create.hip build_block_maps;
 kernels.hpp Stencil5Plan). Test infrastructure only.
 
 The in-loop SpMV evaluates BLOCK TILES: 128 columns x R consecutive local grid rows, counted from the first grid row of the launch

@@ -1,4 +1,4 @@
-"""numpy restatement of the CG loop of csrc/cg_slab.hip (the slab solver and, through it, cg_solve_device), every bit specified:
+"""numpy restatement of the CG loop of csrc/cg_slab_solve.hip (the slab solver and, through it, cg_solve_device), every bit specified:
 A p by the oracle's SpMV, the updates of r, p, x by the oracle's element-wise forms (oracle_cg_partitioned's arithmetic), the three
 dot products by tests/reduction_restatement.py and the scalar step of cg_scalars_step (csrc/reduce_device.hpp):
 alpha = rr_old / pAp, beta = rr_new / rr_old, converged when sqrt(rr_new) / b_norm < tol, strictly. Test infrastructure

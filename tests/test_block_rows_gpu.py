@@ -1,4 +1,4 @@
-"""Block tiles of the CG slab's in-loop SpMV (csrc/spmv_kernels.hip stencil5_rowlds_block_kernel; csrc/cg_slab.hip build_block_maps;
+"""Block tiles of the CG slab's in-loop SpMV (csrc/spmv_kernels.hip stencil5_rowlds_block_kernel; csrc/cg_slab_create.hip build_block_maps;
 kernels.hpp Stencil5Plan): one wave evaluates 128 columns x R grid rows, R = 4 or 8. The block maps must equal the numpy restatement
 (tests/block_map.py) exactly, and every result must be what block_rows = 0 -- the one-row kernel -- computes, bit for bit."""
 import numpy as np

@@ -350,7 +350,7 @@ def test_slab_timeline_accounts_for_the_solve(B, O, fresh_host_matrices):
 
 @pytest.mark.parametrize("n,P,r", [(1024, 1, 0), (1000, 1, 0), (1024, 4, 1), (1024, 2, 0), (1024, 2, 1), (1001, 1, 0), (2048, 8, 3)])
 def test_both_loop_shapes_leave_every_bit_alone(Blab, monkeypatch, n, P, r):
-    """The loop has two shapes (csrc/cg_slab.hip, LoopShape): the PIPELINE -- halo exchange on the side stream under the interior
+    """The loop has two shapes (csrc/slab_decisions.hpp, LoopShape): the PIPELINE -- halo exchange on the side stream under the interior
     rows, boundary rows inside the reducing launch behind the arrival flag, the direction update's edge rows + first piece (+ the
     scalar step on the RCCL path) in one launch that releases the exchange by a device flag -- and the PLAIN order (no_overlap:
     everything on the compute stream, the exchange behind the whole direction update: the reference's own, and bench.py's

@@ -1,5 +1,5 @@
 """The CG direction update inside the block SpMV (csrc/spmv_kernels.hip stencil5_direction_block_kernel and stencil5_block_list_kernel;
-csrc/cg_slab.hip LoopShape::fused_direction): on a slab without neighbours the launch of iteration k + 1 evaluates p' = r + beta p on
+csrc/slab_decisions.hpp LoopShape::fused_direction): on a slab without neighbours the launch of iteration k + 1 evaluates p' = r + beta p on
 its block tile and the two grid rows around it, stores its own rows and runs the block kernel's chains on the values it holds. Every
 result must be what the two separate launches compute, bit for bit."""
 import numpy as np

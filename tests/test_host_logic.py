@@ -182,6 +182,21 @@ def test_host_layer_under_sanitizers(tmp_path):
     assert "ERROR: AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr[-3000:]
 
 
+def test_slab_decisions_under_sanitizers(tmp_path):
+    """csrc/slab_decisions.hpp -- the CG slab solver's decisions: the loop's shape, the run-ahead rules with a simulated loop around
+    them, the cut of the direction update, creation's arithmetic -- needs no HIP: tests/abi/slab_decisions_test.cpp includes it and
+    standard headers only, is compiled with g++ -fsanitize=address,undefined and run as it is (the environment passed through)."""
+    import subprocess
+    exe = tmp_path / "slab_decisions_test"
+    build = subprocess.run(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g", "-O1",
+                            "-I", os.path.join(ROOT, "cuda-spmv-benchmark_amd", "csrc"), os.path.join(ROOT, "tests", "abi", "slab_decisions_test.cpp"),
+                            "-o", str(exe)], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-3000:]
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and "slab_decisions: ok" in run.stdout, (run.returncode, run.stdout[-2000:], run.stderr[-3000:])
+    assert "ERROR: AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr[-3000:]
+
+
 def test_only_the_declared_api_leaves_the_library(B):
     """csrc/exports.map: exactly the declared symbols are dynamic exports; no spmv_amd::launch_* or kernel stub leaks."""
     import subprocess

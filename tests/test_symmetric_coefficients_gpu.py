@@ -1,4 +1,4 @@
-"""The symmetric coefficient form of the CG slab (csrc/cg_slab.hip, kernels.hpp SymPlanes): a slab whose W / N entries equal, bit
+"""The symmetric coefficient form of the CG slab (csrc/cg_slab.hpp, kernels.hpp SymPlanes): a slab whose W / N entries equal, bit
 for bit, the E entry of row i-1 / the S entry of row i-n streams [C, E] + S planes (24 B/row) instead of its CSR values (40 B/row).
 Results must be the CSR form's, bit for bit; any matrix that is not bitwise symmetric keeps the CSR form."""
 import numpy as np

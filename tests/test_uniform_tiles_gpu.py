@@ -1,4 +1,4 @@
-"""Uniform tiles of the CG slab's symmetric coefficient form (csrc/cg_slab.hip classify_tiles, csrc/spmv_kernels.hip rowlds_tile;
+"""Uniform tiles of the CG slab's symmetric coefficient form (csrc/cg_slab_create.hip classify_tiles, csrc/spmv_kernels.hip rowlds_tile;
 kernels.hpp SymPlanes): a row-lds tile whose coefficients all equal one slab-wide quintuple bit for bit loads no coefficient.
 The class map must equal the numpy restatement (tests/tile_classes.py) exactly, and every result must be what the planes and the
 CSR form compute, bit for bit."""

@@ -1,4 +1,4 @@
-"""The two ends of a solve on a slab without neighbours that owns its matrix (csrc/cg_slab.hip LoopShape::zero_start, r0_in_ring and
+"""The two ends of a solve on a slab without neighbours that owns its matrix (csrc/slab_decisions.hpp LoopShape::zero_start, r0_in_ring and
 x0_known_zero): while x0 holds the zeros the library wrote, the first SpMV requests no x value on interior grid rows
 (csrc/spmv_kernels.hip stencil5_rowlds_zero_kernel) and the flush of x starts from 0.0 in registers (csrc/cg_kernels.hip
 cg_flush_x_kernel, x_in == nullptr); with any x0 the first launch stores r0 once, as p0, and iteration 0's r update reads it there

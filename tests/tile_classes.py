@@ -1,4 +1,4 @@
-"""numpy restatement of the CG slab's tile classifier (csrc/spmv_kernels.hip classify_tiles_kernel, csrc/cg_slab.hip classify_tiles;
+"""numpy restatement of the CG slab's tile classifier (csrc/spmv_kernels.hip classify_tiles_kernel, csrc/cg_slab_create.hip classify_tiles;
 kernels.hpp SymPlanes). Test infrastructure only.
 
 A row-lds tile is TILE = 128 columns of one grid row. A tile of a global grid row 1 .. n-2 is uniform (class 1) if every coefficient

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Late bulk (csrc/cg_slab.hip): the direction update of an iteration is enqueued as a LEAD piece, then the host reads the status
+"""Late bulk (csrc/cg_slab_solve.hip): the direction update of an iteration is enqueued as a LEAD piece, then the host reads the status
 record and enqueues the rest only if the loop goes on. The lead piece must outlast the host's read + launch; a slow host (a
 throttled container, a noisy neighbour) leaves the GPU idle behind a short one. One slab (LAB build), settings switched between
 solves: late bulk off, the default rule (the protocol only in iterations that may converge, judged by the known residual), and
