@@ -143,7 +143,7 @@ DECLARED_SYMBOLS = [
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
 LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_cg_slab_block_map", "spmv_amd_cg_slab_slow_blocks",
-                    "spmv_amd_cg_slab_direction_spmv", "spmv_amd_cg_slab_spmv_dot", "spmv_amd_cg_slab_initial_stage", "spmv_amd_pcg_stage",
+                    "spmv_amd_cg_slab_direction_spmv", "spmv_amd_cg_slab_spmv_dot", "spmv_amd_cg_slab_initial_stage", "spmv_amd_cg_slab_first_stage", "spmv_amd_cg_slab_stored_b", "spmv_amd_pcg_stage",
                     "spmv_amd_pcg_last_step_launches", "spmv_amd_cg_multi_stage",
                     "spmv_amd_pcg_last_multigrid_cycles", "spmv_amd_precond_multigrid_level_csr", "spmv_amd_mg_stage"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
@@ -254,6 +254,11 @@ def lib():
         L.spmv_amd_cg_slab_spmv_dot.restype = C.c_int
         L.spmv_amd_cg_slab_initial_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]
         L.spmv_amd_cg_slab_initial_stage.restype = C.c_int
+        L.spmv_amd_cg_slab_first_stage.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int),
+                                                   C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.spmv_amd_cg_slab_first_stage.restype = C.c_int
+        L.spmv_amd_cg_slab_stored_b.argtypes = [C.c_void_p, C.c_void_p]
+        L.spmv_amd_cg_slab_stored_b.restype = C.c_int
         L.spmv_amd_pcg_stage.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PcgStageArgs), C.POINTER(PcgScalars)]
         L.spmv_amd_pcg_stage.restype = C.c_int
         L.spmv_amd_pcg_last_step_launches.argtypes = []
@@ -1091,6 +1096,35 @@ class CgSlab:
         if form < 0:
             raise RuntimeError("this slab's first SpMV does not write the residual, or the slab has neighbours")
         return form, r0, r_vec, partials[:count.value], rr.value
+
+    def first_form(self):
+        """1 where a solve of at least one iteration would take b itself as p0 and sum b.b in iteration 0's SpMV (LAB build only;
+        include/spmv_amd/lab.h, spmv_amd_cg_slab_first_stage), else 0. Nothing is launched."""
+        if not is_lab():
+            raise RuntimeError("the first stage's form is read through the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        return int(lib().spmv_amd_cg_slab_first_stage(self.h, 0, None, None, None, 0, None, None, None))
+
+    def first_stage(self, reverse=True):
+        """spmv_amd_cg_slab_first_stage (LAB build only): iteration 0's block SpMV on the stored b with both partial arrays and both
+        reductions, once. Returns (Ap, pAp_partials, bb_partials, rr, pAp); the partial arrays hold the slots the launch writes (one
+        per 128 x 1 tile of the slab), NaN where it did not."""
+        if not is_lab():
+            raise RuntimeError("the first stage alone runs in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        Ap = np.empty(self.n_local, dtype=np.float64)
+        pAp_partials, bb_partials = np.empty(self.n_local, dtype=np.float64), np.empty(self.n_local, dtype=np.float64)
+        count, rr, pAp = C.c_int(-1), C.c_double(0.0), C.c_double(0.0)
+        if lib().spmv_amd_cg_slab_first_stage(self.h, 1 if reverse else 0, Ap.ctypes.data, pAp_partials.ctypes.data, bb_partials.ctypes.data,
+                                              len(bb_partials), C.byref(count), C.byref(rr), C.byref(pAp)) != 1:
+            raise RuntimeError("a solve on this slab would not take b as p0 now (spmv_amd_cg_slab_first_stage returned 0)")
+        return Ap, pAp_partials[:count.value], bb_partials[:count.value], rr.value, pAp.value
+
+    def stored_b(self):
+        """The stored right-hand side as it lies on the device now (LAB build only; spmv_amd_cg_slab_stored_b)."""
+        if not is_lab():
+            raise RuntimeError("the stored right-hand side is read back through the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        b = np.empty(self.n_local, dtype=np.float64)
+        lib().spmv_amd_cg_slab_stored_b(self.h, b.ctypes.data)
+        return b
 
     def set_block_rows(self, rows):
         """Grid rows per block tile of the in-loop SpMV (LAB build only): 0 = the one-row kernel, 4 or 8. Rebuilds the block maps."""

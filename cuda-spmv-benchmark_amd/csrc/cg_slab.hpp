@@ -84,12 +84,19 @@ struct SpmvAmdCgSlab {
     // launch stores r0 twice, the launches of before.
     bool zero_start = true;
 #ifdef SPMV_AMD_LAB
-    // set_option("zero_start_parts", mask), for A/B runs of each part: 1 = first launch without x loads, 2 = r0 stored once, 4 = flush without x_in
-    int zero_start_parts = 7;
+    // set_option("zero_start_parts", mask), for A/B runs of each part: 1 = first launch without x loads, 2 = r0 stored once, 4 = flush without x_in,
+    // 8 = b serves as p0 and iteration 0's SpMV sums b.b (LoopShape::b_is_p0)
+    int zero_start_parts = 15;
 #else
-    static constexpr int zero_start_parts = 7;
+    static constexpr int zero_start_parts = 15;
 #endif
     int zero_start_mask() const { return zero_start ? zero_start_parts : 0; }  // slab_decisions.hpp, ShapeInputs::zero_start_parts
+    // A 0 is +0.0 on every local row (slab_decisions.hpp, sums_to_plus_zero; one pass over the CSR values at creation, next to the class
+    // map; slabs that keep the planes only). No entry point rewrites a slab's coefficients after creation -- the placement trial
+    // copies them bit for bit -- so nothing clears it. partials_first: the b.b partials of LoopShape::b_is_p0's first launch, one per
+    // slot of the whole-slab plan (partials_blas is shorter than that, and partials_spmv takes the launch's p.Ap partials).
+    bool zero_rows_plus_zero = false;
+    double* partials_first = nullptr;
     bool spmv_with_dot = false;  // LAB option: spmv_amd_cg_slab_spmv runs the in-loop form (dot partials wanted)
     const SymPlanes* sym() const { return planes_on ? &planes : nullptr; }
     // place_coefficients: {0, candidates timed, SpMV ms before, SpMV ms kept}
@@ -222,7 +229,9 @@ int slab_spmv(SpmvAmdCgSlab* s, bool with_dot, bool overlap, const int* skip, co
               const ResidualOut* init = nullptr, bool x_zero = false);
 int slab_direction_spmv(SpmvAmdCgSlab* s, const double* p_in, double* p_out, int iteration, hipEvent_t spmv_done = nullptr);
 int slab_initial_residual(SpmvAmdCgSlab* s, const LoopShape& L, bool halo_in_flight);
-void reduce_spmv_partials(SpmvAmdCgSlab* s, int used, double* d_out, const int* skip, int* progress, int progress_value, const PeerMailbox* mailbox);
+int slab_first_spmv(SpmvAmdCgSlab* s, bool reverse, hipEvent_t spmv_done = nullptr);
+void reduce_spmv_partials(SpmvAmdCgSlab* s, int used, double* d_out, const int* skip, int* progress, int progress_value, const PeerMailbox* mailbox,
+                          const double* partials = nullptr);
 void report_slab_state(void* user, FILE* out);
 }  // namespace slab
 }  // namespace spmv_amd

@@ -111,7 +111,7 @@ extern "C" int spmv_amd_cg_slab_set_option(SpmvAmdCgSlab* s, const char* name, l
         if (value < 0 || value > 2) return -1;
         s->fused_direction = (int)value;
     }
-    else if (strcmp(name, "zero_start_parts") == 0) s->zero_start_parts = (int)value & 7;  // which parts "zero_start" 1 switches on: 1 | 2 | 4 (the field says which is which)
+    else if (strcmp(name, "zero_start_parts") == 0) s->zero_start_parts = (int)value & 15;  // which parts "zero_start" 1 switches on: 1 | 2 | 4 | 8 (the field says which is which)
     else if (strcmp(name, "zero_start") == 0) s->zero_start = value != 0;  // 0: x0 always loaded, r0 stored twice (the launches of before)
     else if (strcmp(name, "spmv_with_dot") == 0) s->spmv_with_dot = value != 0;  // spmv() in its in-loop form: p.Ap partials and their sum too
     else return -1;
@@ -205,6 +205,44 @@ extern "C" int spmv_amd_cg_slab_initial_stage(SpmvAmdCgSlab* s, double* r0, doub
     HIP_CHECK(hipMemcpy(rr, &s->d_s->rr_new, sizeof(double), hipMemcpyDeviceToHost));
     s->p = s->ring[0];
     return form;
+}
+
+// The first stage of a solve in the shape LoopShape::b_is_p0 -- iteration 0's block SpMV on the stored b with both partial arrays,
+// the reduction of the b.b partials, the scalars' initialisation and the reduction of the b.Ab partials -- once, as a solve of at
+// least one iteration enqueues them. Returns 1 where a solve would take that shape now, else 0; Ap == NULL, or 0: only that, nothing
+// is launched. Ap and both partial arrays are filled with NaN beforehand.
+extern "C" int spmv_amd_cg_slab_first_stage(SpmvAmdCgSlab* s, int reverse, double* Ap, double* pAp_partials, double* bb_partials, int cap, int* count,
+                                            double* rr, double* pAp) {
+    if (!loop_shape(s).b_is_p0) return 0;
+    if (Ap == nullptr) return 1;
+    const size_t nl = (size_t)s->n_local, slots = (size_t)s->plan_whole.partials;
+    HIP_CHECK(hipMemsetAsync(s->d_s, 0, sizeof(CgScalars), s->compute));
+    HIP_CHECK(hipMemsetAsync(s->Ap, 0xFF, nl * sizeof(double), s->compute));
+    HIP_CHECK(hipMemsetAsync(s->partials_spmv, 0xFF, slots * sizeof(double), s->compute));
+    HIP_CHECK(hipMemsetAsync(s->partials_first, 0xFF, slots * sizeof(double), s->compute));
+    s->reduce_mailbox = nullptr;
+    const int used = slab_first_spmv(s, reverse != 0);
+    reduce_spmv_partials(s, used, &s->d_s->rr_new, nullptr, nullptr, 0, nullptr, s->partials_first);
+    launch_cg_scalars_init(s->d_s, nullptr, s->compute);
+    reduce_spmv_partials(s, used, &s->d_s->pAp, &s->d_s->converged, nullptr, 0, nullptr);
+    HIP_CHECK(hipStreamSynchronize(s->compute));
+    HIP_CHECK(hipGetLastError());
+    download(Ap, s->Ap, nl);
+    const size_t out = std::min(slots, (size_t)(cap > 0 ? cap : 0));
+    if (pAp_partials != nullptr && out > 0) download(pAp_partials, s->partials_spmv, out);
+    if (bb_partials != nullptr && out > 0) download(bb_partials, s->partials_first, out);
+    if (count != nullptr) *count = used;
+    CgScalars sc;
+    HIP_CHECK(hipMemcpy(&sc, s->d_s, sizeof sc, hipMemcpyDeviceToHost));
+    *rr = sc.rr_old, *pAp = sc.pAp;
+    return 1;
+}
+
+// The stored right-hand side as it lies on the device now (n_local doubles): no solve may change a bit of it.
+extern "C" int spmv_amd_cg_slab_stored_b(SpmvAmdCgSlab* s, double* b_local) {
+    HIP_CHECK(hipStreamSynchronize(s->compute));
+    download(b_local, s->b, (size_t)s->n_local);
+    return 0;
 }
 
 // The tile class map as creation wrote it: one byte per row-lds tile, 1 = uniform.

@@ -143,6 +143,10 @@ static void settle_planes(SpmvAmdCgSlab* s) {
         classify_tiles(s);
         s->planes = plane_view(s, s->planes_alloc);
         build_block_maps(s);
+        // the fact LoopShape::b_is_p0 rests on, and the second partial array of its launch; without the array the fact is not recorded
+        if (device_check<int>(s->compute, [&](int* d_bad) { launch_rows_plus_zero(s->A.view, d_bad, s->compute); }) == 0)
+            s->partials_first = device_try_alloc<double>((size_t)s->plan_whole.partials);
+        s->zero_rows_plus_zero = s->partials_first != nullptr;
     }
     s->planes_on = keep;
 }
@@ -575,6 +579,7 @@ extern "C" void spmv_amd_cg_slab_destroy(SpmvAmdCgSlab* s) {
     device_release(s->d_alpha_ring);
     device_release(s->partials_spmv);
     device_release(s->partials_blas);
+    device_release(s->partials_first);
     device_release(s->reduce_stage);
     device_release(s->d_halo_flag);
     device_release(s->d_s);

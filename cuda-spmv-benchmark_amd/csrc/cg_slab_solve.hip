@@ -29,10 +29,12 @@ static int slab_boundary_spmv(SpmvAmdCgSlab* s, const double* in, double* part, 
 }
 
 // Sum of the partials the last slab_spmv wrote (`used` of them): a split SpMV's boundary-row partials as extra values.
-void reduce_spmv_partials(SpmvAmdCgSlab* s, int used, double* d_out, const int* skip, int* progress, int progress_value, const PeerMailbox* mailbox) {
+// partials (null: partials_spmv): the array the launches wrote, where it is another one (slab_first_spmv's b.b partials).
+void reduce_spmv_partials(SpmvAmdCgSlab* s, int used, double* d_out, const int* skip, int* progress, int progress_value, const PeerMailbox* mailbox,
+                          const double* partials) {
+    if (partials == nullptr) partials = s->partials_spmv;
     const int first = s->spmv_split_at >= 0 && s->spmv_split_at < used ? s->spmv_split_at : used;
-    launch_reduce_partials(s->partials_spmv, first, d_out, skip, s->compute, s->scratch(), progress, progress_value, mailbox,
-                           s->partials_spmv + first, used - first);
+    launch_reduce_partials(partials, first, d_out, skip, s->compute, s->scratch(), progress, progress_value, mailbox, partials + first, used - first);
 }
 
 // SpMV of the slab on p (halos must be current or in flight on the side stream).
@@ -223,6 +225,7 @@ ShapeInputs shape_inputs(const SpmvAmdCgSlab* s, bool detailed_timers) {
     in.slow_blocks = s->slow_count_whole, in.block_tiles = in.block_plan ? rowlds_block_tiles(p) : 0;
     in.late_bulk = s->late_bulk, in.fuse_init_residual = s->fuse_init_residual, in.x0_known_zero = s->x0_known_zero;
     in.zero_start_parts = s->zero_start_mask();
+    in.zero_rows_plus_zero = s->zero_rows_plus_zero;
     return in;
 }
 
@@ -231,6 +234,16 @@ ShapeInputs shape_inputs(const SpmvAmdCgSlab* s, bool detailed_timers) {
 int slab_initial_residual(SpmvAmdCgSlab* s, const LoopShape& L, bool halo_in_flight) {
     const ResidualOut init{s->b, L.r0_in_ring ? nullptr : s->r, s->ring[0]};
     return slab_spmv(s, /*with_dot=*/false, halo_in_flight, nullptr, s->x0, nullptr, &init, L.zero_start);
+}
+
+// LoopShape::b_is_p0: iteration 0's SpMV on b -- Ap = A b, the b.Ab partials into partials_spmv and the b.b partials into
+// partials_first, one launch -- with the marks slab_spmv leaves behind a one-launch SpMV. The caller reduces both arrays.
+int slab_first_spmv(SpmvAmdCgSlab* s, bool reverse, hipEvent_t spmv_done) {
+    s->spmv_split_at = -1;
+    const int used = launch_stencil5_first_spmv(s->A.view, s->plan_whole, s->b, s->Ap, 1.0, s->partials_spmv, s->partials_first, reverse, s->compute, *s->sym());
+    if (s->tl_after_interior) HIP_CHECK(hipEventRecord(s->tl_after_interior, s->compute));
+    if (spmv_done) HIP_CHECK(hipEventRecord(spmv_done, s->compute));
+    return used;
 }
 
 // One solve. The loop has TWO shapes, fixed per solve (LoopShape): the pipeline and the plain order; an iteration is the
@@ -244,6 +257,9 @@ struct SolveRun {
     const CGConfigMultiGPU* config;
     CGStatsMultiGPU* stats;
     const LoopShape L;
+    // L.b_is_p0 in a solve that runs iteration 0: b stands for ring slot 0 until the ring wraps, and iteration 0's SpMV is enqueued
+    // by initial_residual (a solve of no iterations keeps the launch that only sums r0.r0)
+    const bool b_is_p0;
     const PeerMailbox* const mailbox;  // non-null: the communicator's peer mailbox completes the sums (L.use_mailbox)
     const EdgeRows edges;              // pipeline: the rows the neighbours wait for, [0, count_a) and [second, second + count_b)
     const TraceRanges trace;
@@ -265,7 +281,8 @@ struct SolveRun {
     std::vector<int> sampled_iteration;  // 0-based loop index of each timed SpMV
 
     SolveRun(SpmvAmdCgSlab* slab, const CGConfigMultiGPU* cfg, CGStatsMultiGPU* st)
-        : s(slab), config(cfg), stats(st), L(loop_shape(slab, cfg->enable_detailed_timers != 0)), mailbox(L.use_mailbox ? slab->comm->d_mailbox : nullptr),
+        : s(slab), config(cfg), stats(st), L(loop_shape(slab, cfg->enable_detailed_timers != 0)), b_is_p0(L.b_is_p0 && cfg->max_iters > 0),
+          mailbox(L.use_mailbox ? slab->comm->d_mailbox : nullptr),
           edges{L.head_rows, L.tail_start, L.pipeline ? (size_t)slab->n_local - L.tail_start : 0}, trace(L.detail || slab->roctx_always), nl((size_t)slab->n_local),
           skip(&slab->d_s->converged), timeline(slab->timeline_on && !L.detail) {
         for (int k = 0; k < kMaxRingSlots; ++k) ring_view.p[k] = s->ring[(size_t)k % s->ring.size()];
@@ -300,6 +317,23 @@ struct SolveRun {
         if (timeline) HIP_CHECK(hipEventRecord(tl_event(s->tl_compute, mark_index(iteration, k)), s->compute));
     }
 
+    // the ring as a flush reads it: in the solve's first window b is slot 0 where it serves as p0 (the real slot 0 is written when
+    // the ring wraps, behind the flush of that window)
+    RingSlots flush_ring() const {
+        RingSlots v = ring_view;
+        if (b_is_p0 && window_start == 0) v.p[0] = s->b;
+        return v;
+    }
+    // the event pair around every spmv_event_stride-th in-loop SpMV: is iteration `index` (0-based) one of them, and its pair
+    bool samples(int index) const { return !timeline && !L.detail && s->spmv_event_stride > 0 && (index + s->spmv_event_phase) % s->spmv_event_stride == 0; }
+    hipEvent_t* sample_pair() {
+        while (s->spmv_ev.size() < 2 * (size_t)(sampled + 1)) {
+            hipEvent_t e;
+            HIP_CHECK(hipEventCreate(&e));
+            s->spmv_ev.push_back(e);
+        }
+        return &s->spmv_ev[2 * (size_t)sampled];
+    }
     // what a flush of x starts from: x itself, the stored x0 for the solve's first window -- or nothing (null: the chain starts from
     // 0.0 in registers) where x0 holds the library's own zeros
     const double* flush_from() const { return window_start > 0 ? s->x : (flush_skips_x0(s->x0_known_zero, s->zero_start_mask()) ? nullptr : s->x0); }
@@ -353,7 +387,7 @@ void SolveRun::begin() {
     // overwritten with x0 first: the initial SpMV reads x0 and the first x update computes x = x0 + alpha p.
     HIP_CHECK(hipStreamSynchronize(s->compute));
     s->timeline_us.clear();
-    s->p = s->ring[0];
+    s->p = b_is_p0 ? s->b : s->ring[0];  // b as p0: what the direction update of iteration 1 reads (never written: p_next is a ring slot)
     sequence0 = s->poll_sequence;
     records_read = 0;
     s->h_poll->converged = 0, s->h_poll->iterations = 0;  // (the stream is idle: nothing of the previous solve can still write here)
@@ -403,7 +437,19 @@ void SolveRun::start_halo(double* v, bool released_by_flag) {
 // p's, so that the point-to-point communicator is driven from one stream only).
 void SolveRun::initial_residual() {
     start_halo(s->x0, /*released_by_flag=*/false);
-    if (s->fuse_init_residual) {
+    int first_used = 0;
+    if (b_is_p0) {
+        // r0 is b and p0 is b: nothing to compute or store. Iteration 0's SpMV goes first, on b, in that iteration's sweep direction
+        // (the r update behind it starts where it ends), and sums b.b on its way; it is that iteration's SpMV for the launch timers.
+        hipEvent_t spmv_done = nullptr;
+        if (samples(0)) {
+            hipEvent_t* pair = sample_pair();
+            HIP_CHECK(hipEventRecord(pair[0], s->compute));
+            spmv_done = pair[1];
+        }
+        first_used = slab_first_spmv(s, sweeps_backward(0), spmv_done);
+        reduce_spmv_partials(s, first_used, &s->d_s->rr_new, nullptr, nullptr, 0, mailbox, s->partials_first);
+    } else if (s->fuse_init_residual) {
         // row-lds slabs: r0 = b - A x0, p0 = r0 and the r0.r0 partials come out of the SpMV launch itself (A x0 is
         // never written out and read back: 16 B/row less, once per solve)
         int used = 0;
@@ -420,6 +466,8 @@ void SolveRun::initial_residual() {
     if (L.separate) allreduce_scalar(s, &s->d_s->rr_new, "all-reduce of the initial r.r");
     s->reduce_mailbox = s->fused_dot ? mailbox : nullptr;  // the in-loop SpMVs' p.Ap reduction
     launch_cg_scalars_init(s->d_s, s->d_hist, s->compute);
+    // b as p0: the b.Ab sum of iteration 0, behind the scalars' initialisation as the in-loop reduction is (it tests the flag that sets)
+    if (b_is_p0) reduce_spmv_partials(s, first_used, &s->d_s->pAp, skip, &s->h_poll->progress, 4 * (s->poll_sequence + 1) + 1, s->reduce_mailbox);
     if (timeline) HIP_CHECK(hipEventRecord(tl_event(s->tl_compute, 1), s->compute));
     if (s->label && config->verbose >= 1) {  // the reference prints ||r0|| before its loop (cg_solver.cu:529-531); verbose runs only
         CgScalars now;
@@ -448,7 +496,12 @@ void SolveRun::stage_spmv() {
         if (L.fused_direction && enqueued > 0) return slab_direction_spmv(s, direction_from, s->p, enqueued, spmv_done);
         return slab_spmv(s, true, halo_in_flight, skip, nullptr, spmv_done);
     };
-    if (timeline) {
+    if (b_is_p0 && enqueued == 0) {
+        // initial_residual enqueued this iteration's launch and the reduction of its partials (with the event pair where this is a
+        // timed iteration): the timeline's SpMV marks of iteration 0 enclose nothing, its launch lies in initial_residual_us
+        if (timeline) mark(0, 1), mark(0, 2);
+        else if (samples(0)) sampled_iteration.push_back(0), ++sampled;
+    } else if (timeline) {
         // [1] is recorded inside slab_spmv behind the interior launch, [2] behind the boundary rows; the reduction of the
         // partials is issued by slab_spmv too, so [3] follows directly
         s->tl_after_interior = tl_event(s->tl_compute, mark_index(enqueued, 1));
@@ -456,14 +509,10 @@ void SolveRun::stage_spmv() {
         s->tl_after_interior = nullptr;
     } else if (L.detail) {
         timed(&stats->time_spmv_ms, nullptr, [&] { spmv(nullptr); });
-    } else if (s->spmv_event_stride > 0 && (enqueued + s->spmv_event_phase) % s->spmv_event_stride == 0) {
-        while (s->spmv_ev.size() < 2 * (size_t)(sampled + 1)) {
-            hipEvent_t e;
-            HIP_CHECK(hipEventCreate(&e));
-            s->spmv_ev.push_back(e);
-        }
-        HIP_CHECK(hipEventRecord(s->spmv_ev[2 * sampled], s->compute));
-        spmv(s->spmv_ev[2 * sampled + 1]);
+    } else if (samples(enqueued)) {
+        hipEvent_t* pair = sample_pair();
+        HIP_CHECK(hipEventRecord(pair[0], s->compute));
+        spmv(pair[1]);
         sampled_iteration.push_back(enqueued);
         ++sampled;
     } else {
@@ -489,7 +538,8 @@ void SolveRun::stage_update_r() {
     timed(&stats->time_blas1_ms, &stats->time_axpy_update_r_ms,
           [&] {
               // r0_in_ring: r0 lies in ring slot 0 alone (p0 = r0, stored once): the update of iteration 0 reads it there
-              if (L.r0_in_ring && enqueued == 0) launch_cg_update_r_from(nl, s->d_s, s->Ap, s->ring[0], s->r, s->partials_blas, s->compute, !backward);
+              // (b_is_p0: r0 is b itself)
+              if (L.r0_in_ring && enqueued == 0) launch_cg_update_r_from(nl, s->d_s, s->Ap, b_is_p0 ? s->b : s->ring[0], s->r, s->partials_blas, s->compute, !backward);
               else launch_cg_update_r(nl, s->d_s, s->Ap, s->r, s->partials_blas, s->compute, !backward);
           });
     mark(enqueued, 4);
@@ -559,7 +609,7 @@ void SolveRun::stage_direction_and_halo() {
         // (alpha of this iteration is already on the stream: the step above wrote it)
         if (flush_due(enqueued, window_start, L.slots)) {
             timed(&stats->time_blas1_ms, nullptr, [&] {
-                launch_cg_flush_x(nl, s->d_alpha_ring, ring_view, L.slots, window_start % L.slots, L.slots, flush_from(), s->x, s->compute,
+                launch_cg_flush_x(nl, s->d_alpha_ring, flush_ring(), L.slots, window_start % L.slots, L.slots, flush_from(), s->x, s->compute,
                                   s->d_s, window_start);
             });
             window_start = enqueued;
@@ -685,7 +735,7 @@ void SolveRun::finish() {
     if (timeline) HIP_CHECK(hipEventRecord(tl_event(s->tl_compute, tl_flush), s->compute));
     if (L.slots > 1 && enqueued > window_start)  // x <- x + the directions of the last window
         timed(&stats->time_blas1_ms, nullptr, [&] {
-            launch_cg_flush_x(nl, s->d_alpha_ring, ring_view, L.slots, window_start % L.slots, enqueued - window_start, flush_from(), s->x, s->compute, s->d_s,
+            launch_cg_flush_x(nl, s->d_alpha_ring, flush_ring(), L.slots, window_start % L.slots, enqueued - window_start, flush_from(), s->x, s->compute, s->d_s,
                               window_start);
         });
     s->p = s->ring[0];

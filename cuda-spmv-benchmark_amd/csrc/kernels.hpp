@@ -181,6 +181,15 @@ struct DirectionSpmv {
 };
 int launch_stencil5_direction_spmv(const SlabCsr& m, const Stencil5Plan& plan, const DirectionSpmv& d, double* y, double alpha,
                                    double* d_dot_partials, bool reverse, hipStream_t stream, const SymPlanes& planes);
+// Iteration 0's SpMV of a solve that starts from x0 = 0 on a matrix whose rows sum to +0.0 over zero operands (slab_decisions.hpp,
+// LoopShape::b_is_p0; stencil5_first_block_kernel): the in-loop block launch on x = b -- y = alpha A b and the b . (A b) partials,
+// as launch_stencil5_spmv writes them -- that also leaves the b . b partials in `self_partials`, same slots, each summed as the
+// launch of the initial residual sums r0 . r0 (r0 is b bit for bit there). Slabs without halo rows whose plan has a block map.
+// Returns the partial slots written to each array (the plan's).
+int launch_stencil5_first_spmv(const SlabCsr& m, const Stencil5Plan& plan, const double* b, double* y, double alpha, double* d_dot_partials,
+                               double* self_partials, bool reverse, hipStream_t stream, const SymPlanes& planes);
+// Sets *d_bad (int, zeroed by the caller) if any local row's stored coefficients fail slab_decisions.hpp's sums_to_plus_zero.
+void launch_rows_plus_zero(const SlabCsr& m, int* d_bad, hipStream_t stream);
 // The fused Chebyshev step over a row-lds plan (ChebStep): z is read as the SpMV's x, A z is not written. Returns the partial slots
 // a last step writes (the plan's), or -1 without launching when the plan is not a row-lds one.
 int launch_stencil5_cheb_step(const SlabCsr& m, const Stencil5Plan& plan, const double* z, const ChebStep& step, double* d_dot_partials,

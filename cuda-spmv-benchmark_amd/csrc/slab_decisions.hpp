@@ -105,6 +105,24 @@ inline bool fused_tail(bool with_dot, bool writes_partials, bool initial_residua
     return with_dot && writes_partials && !initial_residual && head_rows % grid == 0 && tail_rows % grid == 0 && head_rows <= grid && tail_rows <= grid;
 }
 
+// ---- a fact about the matrix, established once at creation ----
+// Does a row with these stored coefficients sum to +0.0, bit for bit, when every operand is +0.0 -- in whatever order the products
+// are added, started from 0.0 or from the first product (the interior fma chain, the CSR loop on edge columns and on the grid's
+// first and last grid row)? Every product of a finite coefficient and +0.0 is a zero with the coefficient's sign, and a sum of
+// zeros is -0.0 only if every addend is: so it is enough that every coefficient is finite and one has its sign bit clear. An
+// infinity or a NaN gives NaN. Conservative (a chain started from 0.0 gives +0.0 for all-negative rows too) and order-independent.
+// constexpr: the creation pass evaluates the same function on the GPU (spmv_kernels.hip, rows_plus_zero_kernel).
+constexpr bool finite_value(double v) { return __builtin_isfinite(v); }
+constexpr bool sign_bit_clear(double v) { return !__builtin_signbit(v); }
+constexpr bool sums_to_plus_zero(const double* coefficients, int count) {
+    bool finite = true, some_plus = false;
+    for (int k = 0; k < count; ++k) {
+        finite = finite && finite_value(coefficients[k]);
+        some_plus = some_plus || sign_bit_clear(coefficients[k]);
+    }
+    return finite && some_plus;
+}
+
 // ---- the loop's shape, chosen once per solve ----
 struct ShapeInputs {
     bool exchanges_halos, collective, mailbox_ready;  // the communicator's answers
@@ -122,7 +140,9 @@ struct ShapeInputs {
     int slow_blocks;                                 // < 0: they could not be listed
     long long block_tiles;
     bool late_bulk, fuse_init_residual, x0_known_zero;
-    int zero_start_parts;  // 0 with zero_start off; else 1 = first launch without x loads, 2 = r0 stored once, 4 = flush without x_in
+    // 0 with zero_start off; else 1 = first launch without x loads, 2 = r0 stored once, 4 = flush without x_in, 8 = b serves as p0
+    int zero_start_parts;
+    bool zero_rows_plus_zero;  // established at creation: every row of A sums to +0.0 over zero operands (sums_to_plus_zero)
 };
 
 struct LoopShape {
@@ -144,6 +164,10 @@ struct LoopShape {
     // SpMV's launch. zero_start: x0 holds the library's own zeros, and that launch requests no x value on interior grid rows.
     // r0_in_ring (any x0): the launch stores r0 once, as p0 into ring slot 0, and the r update of iteration 0 reads it there.
     bool zero_start = false, r0_in_ring = false;
+    // On top of both, where A 0 is +0.0 on every row (ShapeInputs::zero_rows_plus_zero): r0 = b - A 0 is b bit for bit, so nothing
+    // computes or stores it. The first launch of the solve is iteration 0's block SpMV on b, which also sums b.b; b is read wherever
+    // the first window reads ring slot 0, and is never written. Needs the block kernel on the whole slab and no detailed timers.
+    bool b_is_p0 = false;
     int slots = 1;  // direction ring length; 1 = the in-place x / p update
     // pipeline: the edge ranges [0, head_rows) and [tail_start, n_local), rounded OUTWARDS to 4 KiB; the other rows are the bulk
     size_t head_rows = 0, tail_start = 0;
@@ -174,6 +198,8 @@ inline LoopShape loop_shape(const ShapeInputs& in) {
     const bool own_ends = !L.multi && in.owns_matrix && L.slots > 1 && in.fuse_init_residual;
     L.zero_start = own_ends && in.x0_known_zero && (in.zero_start_parts & 1) != 0;
     L.r0_in_ring = own_ends && (in.zero_start_parts & 2) != 0;
+    L.b_is_p0 = L.zero_start && L.r0_in_ring && in.zero_rows_plus_zero && in.fused_dot && in.planes_and_classes && in.block_plan && !L.detail &&
+                (in.zero_start_parts & 8) != 0;
     // Early halo: the two edge ranges are rounded outwards, so that the launch over the rest starts on a 4 KiB boundary like every
     // whole-vector launch does. A few rows beyond the grid row updated early is harmless.
     const size_t head_rows = in.has_prev ? round_up((size_t)in.halo) : 0;

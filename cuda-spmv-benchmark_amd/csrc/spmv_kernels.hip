@@ -23,6 +23,7 @@
 
 #include "direction_device.hpp"
 #include "reduce_device.hpp"
+#include "slab_decisions.hpp"
 #include "stencil_geometry.hpp"
 #include "stencil_row_device.hpp"
 #include "stream_device.hpp"
@@ -688,6 +689,125 @@ __global__ __launch_bounds__(64) void stencil5_block_list_kernel(SlabCsr m, cons
     rowlds_block_slow_rows(m, x, y, alpha, gi_lo, gi_hi, gfirst, col_tiles, li0, block_rows, col_tile, col_tile * kLdsTileCols, (int)threadIdx.x, 0, lds, dot_partials, sp);
 }
 
+// ---------------------------------------------------------------------------------
+// Iteration 0's block SpMV of a solve whose p0 is b itself (cg_slab.hpp, LoopShape::b_is_p0): stencil5_rowlds_block_kernel on
+// x = b, over the same block tiles, tile -> XCD runs, block map and p.Ap partial slots, that also sums b . b -- one partial per
+// 128 x 1 tile in the same slot of `self_partials`, in the form rowlds_tile's kMode 2 sums r0 . r0: fma(v, v, acc) for the lane's
+// column `lane`, then `lane + 64`, then wave_sum. With r0 = b bit for bit both sums keep every bit that the launch of the initial
+// residual followed by the block kernel gives; the values are in registers here anyway. A kernel of its own, first in its solve
+// (no skip flag): the in-loop instances keep their code.
+// ---------------------------------------------------------------------------------
+// rowlds_block_slow_rows with the row's own partial of x . x beside it: the lane's two values are read again (the lines the row
+// has just pulled in) rather than handed out of rowlds_tile, which stays as it is.
+__device__ __forceinline__ void rowlds_first_slow_rows(const SlabCsr& m, const double* __restrict__ x, double* __restrict__ y, double alpha,
+                                                       int gi_lo, int gi_hi, int gfirst, int col_tiles, int li0, int block_rows, int col_tile, int j0, int lane,
+                                                       double* __restrict__ lds, double* __restrict__ dot_partials, double* __restrict__ self_partials,
+                                                       const SymPlanes& sp) {
+    double* __restrict__ strip = lds;
+    double* __restrict__ xrow = lds + 5 * kLdsTileCols;
+    const ResidualOut none{nullptr, nullptr, nullptr};
+    const int n = m.grid_size;
+    const int held = gi_hi - li0 < block_rows ? gi_hi - li0 : block_rows;
+#pragma unroll 1
+    for (int r = 0; r < held; ++r) {
+        const int li = li0 + r;
+        const int uniform = rowlds_tile_class(sp, li, col_tiles, col_tile);
+        double dot = 0.0;
+        rowlds_tile<1, false, true>(m, x, y, alpha, li, gfirst + li, j0, lane, 0, strip, xrow, none, &dot, sp, uniform);
+        double self = 0.0;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int j = j0 + lane + 64 * h;
+            if (j < n) {
+                const double v = x[(long long)li * n + j];
+                self = fma(v, v, self);
+            }
+        }
+        self = wave_sum(self);
+        if (lane == 0) {
+            dot_partials[(li - gi_lo) * col_tiles + col_tile] = dot;
+            self_partials[(li - gi_lo) * col_tiles + col_tile] = self;
+        }
+        wave_lds_sync();  // the next row rewrites the LDS this row's lanes have just read
+    }
+}
+
+template <int kRows>
+__global__ __launch_bounds__(64) void stencil5_first_block_kernel(
+    SlabCsr m, const double* __restrict__ x, double* __restrict__ y, double alpha, int gi_lo, int gi_hi, int gfirst, int col_tiles,
+    int total_blocks, int run, int reverse, double* __restrict__ dot_partials, double* __restrict__ self_partials,
+    const unsigned char* __restrict__ block_map, SymPlanes sp) {
+    constexpr int kRowDoubles = kLdsTileCols + 2;
+    constexpr int kFastDoubles = kRows * kRowDoubles, kOneRowDoubles = 5 * kLdsTileCols + kRowDoubles;
+    __shared__ double lds[kFastDoubles > kOneRowDoubles ? kFastDoubles : kOneRowDoubles];  // the block kernel's, to the byte
+    const int block = rowlds_tile_of_block((int)blockIdx.x, run, total_blocks, reverse);
+    if (block < 0) return;
+    const int row_block = block / col_tiles;
+    const int col_tile = block - row_block * col_tiles;
+    const int li0 = gi_lo + row_block * kRows;
+    const int j0 = col_tile * kLdsTileCols, lane = (int)threadIdx.x;
+    const int n = m.grid_size;
+    const int fast = (int)block_map[block];  // requested in front of the x loads and tested behind them, as in the block kernel
+    // b has no halo rows: the rows of x that exist are the slab's own (the loads are issued before the map byte is known)
+    const int row_lo = -(m.halo_before / n), row_hi = (m.n_local + m.halo_after) / n;
+    double xv[kRows + 2][2];  // rows li0 - 1 .. li0 + kRows, the lane's two columns
+    double xo[kRows];         // lane 0: the W neighbour left of the tile; lane 63: the E neighbour right of it
+#pragma unroll
+    for (int r = 0; r < kRows + 2; ++r) {
+        const int li = li0 - 1 + r;
+        xv[r][0] = xv[r][1] = 0.0;
+        if (li >= row_lo && li < row_hi) {
+            const double* __restrict__ xr = x + ((long long)li * n + j0);
+            if (j0 + lane < n) xv[r][0] = xr[lane];
+            if (j0 + lane + 64 < n) xv[r][1] = xr[lane + 64];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+        const int li = li0 + r;
+        xo[r] = 0.0;
+        if (li < row_hi) {
+            const double* __restrict__ xr = x + ((long long)li * n + j0);
+            if (lane == 0 && j0 > 0) xo[r] = xr[-1];
+            if (lane == 63 && j0 + kLdsTileCols < n) xo[r] = xr[kLdsTileCols];
+        }
+    }
+    if (__builtin_amdgcn_readfirstlane(fast) != 0) {
+#pragma unroll
+        for (int r = 0; r < kRows; ++r) {
+            lds[r * kRowDoubles + 1 + lane] = xv[r + 1][0];
+            lds[r * kRowDoubles + 65 + lane] = xv[r + 1][1];
+        }
+        wave_lds_sync();
+#pragma unroll
+        for (int r = 0; r < kRows; ++r) {
+            const int li = li0 + r;
+            double xw[2], xe[2];
+            tile_west_east(lds + r * kRowDoubles, lane, j0, n, xo[r], xo[r], xw, xe);
+            double dot = 0.0, self = 0.0;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int j = j0 + lane + 64 * h;
+                if (j < n) {
+                    const double xc = xv[r + 1][h], xn = xv[r][h], xs = xv[r + 2][h];
+                    const double sum = stencil5_row(j, n, sp.w, xw[h], sp.c, xc, sp.e, xe[h], sp.n, xn, sp.s5, xs);
+                    dot = fma(xc, sum, dot);
+                    self = fma(xc, xc, self);
+                    __builtin_nontemporal_store(alpha * sum, y + ((long long)li * n + j));
+                }
+            }
+            dot = wave_sum(dot);
+            self = wave_sum(self);
+            if (lane == 0) {
+                dot_partials[(li - gi_lo) * col_tiles + col_tile] = dot;
+                self_partials[(li - gi_lo) * col_tiles + col_tile] = self;
+            }
+        }
+    } else {
+        rowlds_first_slow_rows(m, x, y, alpha, gi_lo, gi_hi, gfirst, col_tiles, li0, kRows, col_tile, j0, lane, lds, dot_partials, self_partials, sp);
+    }
+}
+
 // The block map of one launch range [gi_lo, gi_hi) (stencil5_rowlds_block_kernel): one thread per block tile.
 __global__ __launch_bounds__(kBlock) void block_map_kernel(const unsigned char* __restrict__ cls, int col_tiles, int gi_lo, int gi_hi,
                                                            int block_rows, int total_blocks, unsigned char* __restrict__ out) {
@@ -1259,6 +1379,15 @@ __global__ __launch_bounds__(64) void classify_tiles_kernel(SlabCsr m, double qw
     }
 }
 
+// One thread per local row: does the row keep A 0 = +0.0 (slab_decisions.hpp, sums_to_plus_zero, on the row's stored coefficients)?
+// The CSR values are what every form of the row is evaluated from or was verified against bit for bit (planes, quintuple).
+__global__ __launch_bounds__(kBlock) void rows_plus_zero_kernel(SlabCsr m, int* __restrict__ bad) {
+    const long long lr = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (lr >= m.n_local) return;
+    const int first = m.row_ptr[lr];
+    if (!slab::sums_to_plus_zero(m.values + first, m.row_ptr[lr + 1] - first)) *bad = 1;  // benign race: every writer stores the same value
+}
+
 inline unsigned blocks_for(long long items) { return (unsigned)((items + kBlock - 1) / kBlock); }
 
 }  // namespace
@@ -1474,6 +1603,30 @@ int launch_stencil5_direction_spmv(const SlabCsr& m, const Stencil5Plan& p, cons
         hipLaunchKernelGGL(stencil5_block_list_kernel, dim3((unsigned)d.slow_count), dim3(64), 0, stream, m, d.s, d.iteration, d.p_out, y, alpha,
                            p.gi_lo, p.gi_hi, gfirst, p.row_blocks, p.block_rows, d.slow_list, d_dot_partials, sp);
     return p.partials;
+}
+
+int launch_stencil5_first_spmv(const SlabCsr& m, const Stencil5Plan& p, const double* b, double* y, double alpha, double* d_dot_partials,
+                               double* self_partials, bool reverse, hipStream_t stream, const SymPlanes& sp) {
+    const int blocks = rowlds_block_tiles(p);
+    if (blocks <= 0 || p.block_map == nullptr || d_dot_partials == nullptr || self_partials == nullptr || sp.cls == nullptr || m.halo_before != 0 ||
+        m.halo_after != 0) {
+        fprintf(stderr, "[spmv] the first SpMV on b exists for row-lds plans with a block map on slabs without halo rows only\n");
+        exit(EXIT_FAILURE);
+    }
+    const dim3 grid((unsigned)xcd_padded_grid(blocks, p.xcd_run));
+    const int gfirst = m.row_offset / m.grid_size;
+#define SPMV_AMD_LAUNCH_FIRST_BLOCK(ROWS)                                                                                       \
+    hipLaunchKernelGGL((stencil5_first_block_kernel<ROWS>), grid, dim3(64), 0, stream, m, b, y, alpha, p.gi_lo, p.gi_hi, gfirst, \
+                       p.row_blocks, blocks, p.xcd_run, reverse ? 1 : 0, d_dot_partials, self_partials, p.block_map, sp)
+    if (p.block_rows == 4) SPMV_AMD_LAUNCH_FIRST_BLOCK(4);
+    else SPMV_AMD_LAUNCH_FIRST_BLOCK(8);
+#undef SPMV_AMD_LAUNCH_FIRST_BLOCK
+    return p.partials;
+}
+
+void launch_rows_plus_zero(const SlabCsr& m, int* d_bad, hipStream_t stream) {
+    if (m.n_local == 0) return;
+    hipLaunchKernelGGL(rows_plus_zero_kernel, dim3(blocks_for(m.n_local)), dim3(kBlock), 0, stream, m, d_bad);
 }
 
 int launch_stencil5_cheb_step(const SlabCsr& m, const Stencil5Plan& p, const double* z, const ChebStep& step, double* d_dot_partials,

@@ -478,9 +478,13 @@ SpmvAmdCgSlab* spmv_amd_cg_slab_create_stencil5(int n, SpmvAmdComm* comm);
 /* Full-length host vectors as in the reference (each rank uploads its slab);
  * NULL keeps b = 1 / x0 = 0. While no x0 was ever passed, x0 holds the zeros the library wrote itself and most loads of it are
  * skipped (csrc/cg_slab.hpp, x0_known_zero): the flush of x in ring mode does not read it, and on a slab without neighbours that
- * owns its matrix, in ring mode, the first SpMV reads it on the grid's first and last grid row only. Slabs with neighbours and the
- * in-place form (ring 1) still read it in the first SpMV, and a solve of no iterations copies it into x. SPMV_AMD_ZERO_START=0 at
- * creation: always loaded. A passed x0 is never inspected, zeros included. Results are bit-identical either way. */
+ * owns its matrix, in ring mode, the first SpMV reads it on the grid's first and last grid row only. Where, besides, every row of the
+ * matrix sums to +0.0 over zero operands (every stored coefficient finite and one per row with its sign bit clear: checked once at
+ * creation) and the slab's SpMV runs on block tiles, r0 = b - A x0 is b bit for bit and no launch computes it: the first launch of a
+ * solve is iteration 0's SpMV on b, which also sums b.b, and b stands in for the first direction buffer; b is never written. Slabs
+ * with neighbours and the in-place form (ring 1) still read x0 in the first SpMV, and a solve of no iterations copies it into x.
+ * SPMV_AMD_ZERO_START=0 at creation: always loaded, r0 always computed. A passed x0 is never inspected, zeros included. Results are
+ * bit-identical either way. */
 int spmv_amd_cg_slab_set_vectors(SpmvAmdCgSlab* s, const double* b_full, const double* x0_full);
 /* One solve from the stored x0; the timed region is the reference's
  * (cg_solver_mgpu_partitioned.cu:405-413 -> 728-731).

@@ -45,8 +45,9 @@ SpmvAmdCgSlab* spmv_amd_cg_slab_create_stencil5_as(int n, int as_rank, int as_wo
  * detailed timers, a block map whose slow blocks are at most 1/16 of its blocks --, 2 = the same without the 1/16 cap;
  * spmv_amd_cg_slab_loop_shape says which ran; results are bit-identical) and "zero_start" 0/1 (the product's SPMV_AMD_ZERO_START:
  * 0 = the first SpMV and the flush of x always load x0 and the first launch stores r0 twice; spmv_amd_cg_slab_initial_stage says
- * which form a solve takes; results are bit-identical) with "zero_start_parts" 0..7 (a field of the LAB build only: which parts "zero_start" 1 switches on, for A/B
- * runs of each: 1 = the first launch without x loads, 2 = r0 stored once, 4 = the flush of x without x0; default 7). Returns 0, or -1 for an unknown name or value. */
+ * which form a solve takes; results are bit-identical) with "zero_start_parts" 0..15 (a field of the LAB build only: which parts "zero_start" 1 switches on, for A/B
+ * runs of each: 1 = the first launch without x loads, 2 = r0 stored once, 4 = the flush of x without x0, 8 = b serves as p0 and
+ * iteration 0's SpMV sums b.b, spmv_amd_cg_slab_first_stage; default 15). Returns 0, or -1 for an unknown name or value. */
 int spmv_amd_cg_slab_set_option(SpmvAmdCgSlab* s, const char* name, long long value);
 
 /* The tile class map of a slab in the symmetric form as creation wrote it (spmv_amd_cg_slab_uniform_tiles): one byte per row-lds
@@ -86,6 +87,21 @@ int spmv_amd_cg_slab_direction_spmv(SpmvAmdCgSlab* s, const double* r, const dou
  * with bit 1), partials (min(*count, cap) doubles) and *rr = the reduced sum. -1 on a slab with neighbours or one whose first SpMV
  * does not write the residual. */
 int spmv_amd_cg_slab_initial_stage(SpmvAmdCgSlab* s, double* r0, double* r_vec, double* partials, int cap, int* count, double* rr);
+
+/* The first stage of a solve whose p0 is b itself: x0 holds the library's zeros AND every row of the matrix sums to +0.0 over zero
+ * operands (every stored coefficient finite, one with its sign bit clear; established at creation), so r0 = b - A 0 is b bit for
+ * bit, no launch computes it, and iteration 0's block SpMV on b goes first and also sums b.b. Returns 1 where a solve of at least
+ * one iteration would take that shape now (one rank, ring > 1, the block kernel on the whole slab, no detailed timers,
+ * "zero_start_parts" bit 8), else 0; with Ap == NULL, or 0, only that: nothing is launched. Otherwise runs, once, on the stored b,
+ * what such a solve enqueues -- the launch (tiles walked from the end with reverse != 0), the reduction of the b.b partials, the
+ * scalars' initialisation, the reduction of the b.(A b) partials -- and returns Ap (n_local doubles), both partial arrays (min(slots,
+ * cap) doubles each, one slot per 128 x 1 tile; NaN where the launch did not write), *count = the slots the launch writes, *rr = b.b
+ * and *pAp = b.(A b). The initial stage above keeps launching the kernels it launched before this shape existed. */
+int spmv_amd_cg_slab_first_stage(SpmvAmdCgSlab* s, int reverse, double* Ap, double* pAp_partials, double* bb_partials, int cap, int* count,
+                                 double* rr, double* pAp);
+/* The slab's stored right-hand side as it lies on the device now (n_local doubles): where b serves as p0 the solver reads it in
+ * three more places and must never write it. Returns 0. */
+int spmv_amd_cg_slab_stored_b(SpmvAmdCgSlab* s, double* b_local);
 
 /* The device scalars of one preconditioned solve (csrc/pcg.hip keeps the same record on the device). */
 typedef struct SpmvAmdPcgScalars {
