@@ -143,7 +143,7 @@ DECLARED_SYMBOLS = [
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
 LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_cg_slab_block_map", "spmv_amd_cg_slab_slow_blocks",
-                    "spmv_amd_cg_slab_direction_spmv", "spmv_amd_cg_slab_spmv_dot", "spmv_amd_cg_slab_initial_stage", "spmv_amd_cg_slab_first_stage", "spmv_amd_cg_slab_stored_b", "spmv_amd_pcg_stage",
+                    "spmv_amd_cg_slab_direction_spmv", "spmv_amd_cg_slab_spmv_dot", "spmv_amd_cg_slab_initial_stage", "spmv_amd_cg_slab_first_stage", "spmv_amd_cg_slab_stored_b", "spmv_amd_cg_slab_update_r_stage", "spmv_amd_cg_slab_ap_form", "spmv_amd_pcg_stage",
                     "spmv_amd_pcg_last_step_launches", "spmv_amd_cg_multi_stage",
                     "spmv_amd_pcg_last_multigrid_cycles", "spmv_amd_precond_multigrid_level_csr", "spmv_amd_mg_stage"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
@@ -259,6 +259,11 @@ def lib():
         L.spmv_amd_cg_slab_first_stage.restype = C.c_int
         L.spmv_amd_cg_slab_stored_b.argtypes = [C.c_void_p, C.c_void_p]
         L.spmv_amd_cg_slab_stored_b.restype = C.c_int
+        L.spmv_amd_cg_slab_update_r_stage.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int,
+                                                      C.c_void_p, C.c_void_p, C.c_int]
+        L.spmv_amd_cg_slab_update_r_stage.restype = C.c_int
+        L.spmv_amd_cg_slab_ap_form.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.spmv_amd_cg_slab_ap_form.restype = C.c_int
         L.spmv_amd_pcg_stage.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PcgStageArgs), C.POINTER(PcgScalars)]
         L.spmv_amd_pcg_stage.restype = C.c_int
         L.spmv_amd_pcg_last_step_launches.argtypes = []
@@ -1117,6 +1122,42 @@ class CgSlab:
                                               len(bb_partials), C.byref(count), C.byref(rr), C.byref(pAp)) != 1:
             raise RuntimeError("a solve on this slab would not take b as p0 now (spmv_amd_cg_slab_first_stage returned 0)")
         return Ap, pAp_partials[:count.value], bb_partials[:count.value], rr.value, pAp.value
+
+    def update_r_stage(self, r, Ap, rr_old, pAp, p_new=None, reverse=False, converged=0):
+        """spmv_amd_cg_slab_update_r_stage (LAB build only): the r update of an iteration >= 1, once. p_new None: cg_update_r_kernel on
+        (r, Ap); else the launch that recomputes A p' from p_new on the fast row blocks and reads Ap on the slow ones. Returns
+        (r_out, partials), NaN where the launch did not write."""
+        if not is_lab():
+            raise RuntimeError("the r update alone runs in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        Ap = np.ascontiguousarray(Ap, dtype=np.float64)
+        p_new = None if p_new is None else np.ascontiguousarray(p_new, dtype=np.float64)
+        r_out = np.empty_like(r)
+        partials = np.empty(len(r) // 128 + 2, dtype=np.float64)
+        used = lib().spmv_amd_cg_slab_update_r_stage(self.h, 0 if p_new is None else 1, 1 if reverse else 0, r.ctypes.data,
+                                                     None if p_new is None else p_new.ctypes.data, Ap.ctypes.data, float(rr_old), float(pAp),
+                                                     int(converged), r_out.ctypes.data, partials.ctypes.data, len(partials))
+        if used < 0:
+            raise RuntimeError("this slab cannot take the r update that recomputes A p' (a row block that is neither all-fast nor all-slow, ring 1)")
+        return r_out, partials[:used]
+
+    def ap_form(self):
+        """spmv_amd_cg_slab_ap_form (LAB build only): (a solve would recompute A p' in its r update now, the last solve did, the slab's
+        block map is eligible, the recomputing launches of the last solve)."""
+        if not is_lab():
+            raise RuntimeError("the r update's form is read through the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        launches = C.c_int(0)
+        bits = int(lib().spmv_amd_cg_slab_ap_form(self.h, C.byref(launches)))
+        return bool(bits & 1), bool(bits & 2), bool(bits & 4), launches.value
+
+    @staticmethod
+    def workspace_ap_form():
+        """ap_form() of the workspace slab cg_solve_device keeps (LAB build only); None: there is no workspace."""
+        if not is_lab():
+            raise RuntimeError("the r update's form is read through the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        launches = C.c_int(0)
+        bits = int(lib().spmv_amd_cg_slab_ap_form(None, C.byref(launches)))
+        return None if bits < 0 else (bool(bits & 1), bool(bits & 2), bool(bits & 4), launches.value)
 
     def stored_b(self):
         """The stored right-hand side as it lies on the device now (LAB build only; spmv_amd_cg_slab_stored_b)."""

@@ -39,6 +39,14 @@ void release_cg_workspace() {
     release_cg_workspace_locked();
 }
 
+#ifdef SPMV_AMD_LAB
+// the workspace slab of cg_solve_device as it stands (null: none), for the LAB build's hooks that report on the last solve
+const SpmvAmdCgSlab* cg_workspace_slab() {
+    std::lock_guard<std::mutex> guard(g_workspace_lock);
+    return g_workspace;
+}
+#endif
+
 // The lock and the owner rule of every solve on the workspaces: cg_solve_on_operator below, the batched solve (cg_multi.hip).
 CgWorkspaceScope::CgWorkspaceScope() {
     g_workspace_lock.lock();

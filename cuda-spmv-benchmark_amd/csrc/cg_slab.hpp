@@ -20,6 +20,7 @@
 #include "comm.hpp"
 #include "device_runtime.hpp"
 #include "multi_rhs.hpp"
+#include "skew_geometry.hpp"
 #include "slab_decisions.hpp"
 #include "solve_common.hpp"
 #include "stencil_geometry.hpp"
@@ -76,6 +77,15 @@ struct SpmvAmdCgSlab {
     // SPMV_AMD_FUSED_DIRECTION (0 / 1, read at creation): the direction update inside the block SpMV where the slab is eligible
     // (LoopShape::fused_direction). LAB build, set_option("fused_direction", 2): on regardless of the slow blocks' share.
     int fused_direction = 1;
+    // SPMV_AMD_AP_RECOMPUTE (0 / 1, read at creation; LAB build: set_option("ap_recompute", 0 | 1)): on top of the fused direction
+    // update, A p' is not stored on the fast blocks and the r update recomputes it from p' (LoopShape::ap_recomputed).
+    // row_block_fast (device, with the block maps): one byte per row block of the whole-slab map, 1 = every block tile is fast;
+    // skew_eligible: no row block is mixed (skew_geometry.hpp). last_*: what the last solve did (LAB hook spmv_amd_cg_slab_ap_form).
+    int ap_recompute = 1;
+    unsigned char* row_block_fast = nullptr;
+    bool skew_eligible = false;
+    bool last_ap_recomputed = false;
+    int last_recompute_launches = 0;
     // x0 holds the zeros the LIBRARY wrote (the fill at creation, the API's default initial guess) and nothing has written it since:
     // every other writer of x0 clears this, an uploaded vector of zeros included -- x0 is never scanned. What it buys: DESIGN §4,
     // LoopShape::zero_start (the first launch) and flush_skips_x0 (every slab: the flush is pointwise).
@@ -141,6 +151,7 @@ struct SpmvAmdCgSlab {
     // a stand-in slab's mirrored system does not converge in 14 iterations as the rank of a real job does. Timing only.
     int stop_at = 0;
     int test_wedge_overlapped_exchange = 0;  // SPMV_AMD_TEST_WEDGE_OVERLAPPED_EXCHANGE=1 / 2, see exchange_halo
+    bool lab_direction_store = true;  // set_option("direction_store", 0): spmv_amd_cg_slab_direction_spmv runs the launch that does not store A p'
     bool guess_far_always = false;  // set_option("run_ahead", 2): every iteration is guessed "cannot converge": each solve learns of its convergence one iteration late
 #endif
     // non-null while a solve runs on a communicator with a working peer mailbox: the last stage of every dot
@@ -214,6 +225,9 @@ constexpr const char* kTimelineNames =
 // ---- what the pieces share (internal linkage ends at the library's export map) ----
 namespace spmv_amd {
 std::vector<double>& last_cg_history();
+#ifdef SPMV_AMD_LAB
+const SpmvAmdCgSlab* cg_workspace_slab();  // cg_device.hip
+#endif
 namespace slab {
 // cg_slab_create.hip
 void adopt_operator(SpmvAmdCgSlab* s, SpmvOperator* op);
@@ -227,7 +241,8 @@ ShapeInputs shape_inputs(const SpmvAmdCgSlab* s, bool detailed_timers);
 inline LoopShape loop_shape(const SpmvAmdCgSlab* s, bool detailed_timers = false) { return loop_shape(shape_inputs(s, detailed_timers)); }
 int slab_spmv(SpmvAmdCgSlab* s, bool with_dot, bool overlap, const int* skip, const double* input = nullptr, hipEvent_t spmv_done = nullptr,
               const ResidualOut* init = nullptr, bool x_zero = false);
-int slab_direction_spmv(SpmvAmdCgSlab* s, const double* p_in, double* p_out, int iteration, hipEvent_t spmv_done = nullptr);
+int slab_direction_spmv(SpmvAmdCgSlab* s, const double* p_in, double* p_out, int iteration, hipEvent_t spmv_done = nullptr, bool ap_not_stored = false);
+int slab_update_r_recompute(SpmvAmdCgSlab* s, const double* p_new, bool reverse);
 int slab_initial_residual(SpmvAmdCgSlab* s, const LoopShape& L, bool halo_in_flight);
 int slab_first_spmv(SpmvAmdCgSlab* s, bool reverse, hipEvent_t spmv_done = nullptr);
 void reduce_spmv_partials(SpmvAmdCgSlab* s, int used, double* d_out, const int* skip, int* progress, int progress_value, const PeerMailbox* mailbox,

@@ -112,6 +112,8 @@ extern "C" int spmv_amd_cg_slab_set_option(SpmvAmdCgSlab* s, const char* name, l
         s->fused_direction = (int)value;
     }
     else if (strcmp(name, "zero_start_parts") == 0) s->zero_start_parts = (int)value & 15;  // which parts "zero_start" 1 switches on: 1 | 2 | 4 | 8 (the field says which is which)
+    else if (strcmp(name, "ap_recompute") == 0) s->ap_recompute = value != 0 ? 1 : 0;  // 1: A p' recomputed by the r update where the slab is eligible (LoopShape::ap_recomputed)
+    else if (strcmp(name, "direction_store") == 0) s->lab_direction_store = value != 0;  // 0: spmv_amd_cg_slab_direction_spmv runs the fused launch that does not store A p'
     else if (strcmp(name, "zero_start") == 0) s->zero_start = value != 0;  // 0: x0 always loaded, r0 stored twice (the launches of before)
     else if (strcmp(name, "spmv_with_dot") == 0) s->spmv_with_dot = value != 0;  // spmv() in its in-loop form: p.Ap partials and their sum too
     else return -1;
@@ -167,7 +169,7 @@ extern "C" int spmv_amd_cg_slab_direction_spmv(SpmvAmdCgSlab* s, const double* r
     HIP_CHECK(hipMemsetAsync(s->partials_spmv, 0xFF, (size_t)s->plan_whole.partials * sizeof(double), s->compute));
     s->shape.reverse = false;
     s->reduce_mailbox = nullptr;
-    const int used = slab_direction_spmv(s, s->ring[0], s->ring[1], iteration_matches != 0 ? iteration : iteration + 1);
+    const int used = slab_direction_spmv(s, s->ring[0], s->ring[1], iteration_matches != 0 ? iteration : iteration + 1, nullptr, !s->lab_direction_store);
     HIP_CHECK(hipStreamSynchronize(s->compute));
     HIP_CHECK(hipGetLastError());
     download(p_out, s->ring[1], nl);
@@ -177,6 +179,42 @@ extern "C" int spmv_amd_cg_slab_direction_spmv(SpmvAmdCgSlab* s, const double* r
     *pAp = sc.pAp;
     s->p = s->ring[0];
     return used;
+}
+
+// The r update of an iteration >= 1, once, on the caller's vectors and scalars: recompute == 0, cg_update_r_kernel on (r, Ap);
+// recompute != 0, the launch of LoopShape::ap_recomputed on (r, p_new, Ap) -- Ap is read on the slow row blocks only. r_out and the
+// partials (filled with NaN beforehand) come back; returns the partial count, or -1 where recompute is asked of a slab that is not
+// eligible (spmv_amd_cg_slab_ap_form bit 2).
+extern "C" int spmv_amd_cg_slab_update_r_stage(SpmvAmdCgSlab* s, int recompute, int reverse, const double* r, const double* p_new, const double* Ap,
+                                               double rr_old, double pAp, int converged, double* r_out, double* partials, int cap) {
+    if (recompute != 0 && (s->ring.size() < 2 || !s->skew_eligible || s->sym() == nullptr)) return -1;
+    const size_t nl = (size_t)s->n_local;
+    CgScalars sc;
+    memset(&sc, 0, sizeof sc);
+    sc.rr_old = rr_old, sc.pAp = pAp, sc.converged = converged != 0 ? 1 : 0;
+    HIP_CHECK(hipMemcpy(s->d_s, &sc, sizeof sc, hipMemcpyHostToDevice));
+    upload(s->r, r, nl);
+    upload(s->Ap, Ap, nl);
+    if (recompute != 0) upload(s->ring[1], p_new, nl);
+    const int count = cg_partial_count(nl);
+    HIP_CHECK(hipMemsetAsync(s->partials_blas, 0xFF, (size_t)count * sizeof(double), s->compute));
+    if (recompute != 0) slab_update_r_recompute(s, s->ring[1], reverse != 0);
+    else launch_cg_update_r(nl, s->d_s, s->Ap, s->r, s->partials_blas, s->compute, reverse != 0);
+    HIP_CHECK(hipStreamSynchronize(s->compute));
+    HIP_CHECK(hipGetLastError());
+    download(r_out, s->r, nl);
+    if (partials != nullptr && cap > 0) download(partials, s->partials_blas, (size_t)std::min(count, cap));
+    return count;
+}
+
+// The r update that recomputes A p': bit 0 = a solve would take the form now (LoopShape::ap_recomputed), bit 1 = the last solve took
+// it, bit 2 = the slab's whole-slab block map is eligible (every row block all-fast or all-slow). *launches (may be null): the
+// recomputing launches the last solve enqueued. s == NULL: the workspace slab of cg_solve_device (-1: there is none).
+extern "C" int spmv_amd_cg_slab_ap_form(const SpmvAmdCgSlab* s, int* launches) {
+    if (s == nullptr) s = cg_workspace_slab();
+    if (s == nullptr) return -1;
+    if (launches != nullptr) *launches = s->last_recompute_launches;
+    return (loop_shape(s).ap_recomputed ? 1 : 0) | (s->last_ap_recomputed ? 2 : 0) | (s->skew_eligible ? 4 : 0);
 }
 
 // The initial stage of a solve -- the first SpMV's launch and the reduction of its partials -- once, on the slab's stored b and x0,

@@ -90,7 +90,9 @@ void build_block_maps(SpmvAmdCgSlab* s) {
     device_release(s->block_map_interior);
     device_release(s->slow_list_whole);
     device_release(s->slow_list_interior);
+    device_release(s->row_block_fast);
     s->slow_count_whole = s->slow_count_interior = 0;
+    s->skew_eligible = false;
     if (s->tile_classes != nullptr) {
         const auto map_of = [&](const Stencil5Plan& p) -> unsigned char* {
             const int blocks = rowlds_block_tiles(p);
@@ -122,6 +124,17 @@ void build_block_maps(SpmvAmdCgSlab* s) {
         };
         s->slow_list_whole = list_of(s->plan_whole, s->block_map_whole, &s->slow_count_whole);
         s->slow_list_interior = list_of(s->plan_interior, s->block_map_interior, &s->slow_count_interior);
+        // the whole-slab map by row block, for the r update that recomputes A p' (skew_geometry.hpp): a slab without halo rows only
+        if (s->block_map_whole != nullptr && s->halo == 0 && s->plan_whole.first_row == 0 && s->plan_whole.last_row == s->n_local) {
+            const Stencil5Plan& p = s->plan_whole;
+            const int col_tiles = p.row_blocks, row_blocks = rowlds_block_tiles(p) / col_tiles;
+            std::vector<unsigned char> map((size_t)rowlds_block_tiles(p)), fast((size_t)row_blocks);
+            HIP_CHECK(hipMemcpy(map.data(), s->block_map_whole, map.size(), hipMemcpyDeviceToHost));
+            const bool eligible = skew_eligible(map.data(), row_blocks, col_tiles, fast.data());
+            s->row_block_fast = eligible ? device_try_alloc<unsigned char>(fast.size()) : nullptr;
+            if (s->row_block_fast != nullptr) HIP_CHECK(hipMemcpy(s->row_block_fast, fast.data(), fast.size(), hipMemcpyHostToDevice));
+            s->skew_eligible = s->row_block_fast != nullptr;
+        }
     }
     attach_block_maps(s);
 }
@@ -243,6 +256,7 @@ void make_common(SpmvAmdCgSlab* s) {
     if (const char* v = getenv("SPMV_AMD_NO_OVERLAP")) s->no_overlap = v[0] == '1';
     if (const char* v = getenv("SPMV_AMD_FUSED_DIRECTION")) s->fused_direction = v[0] == '1' ? 1 : 0;
     if (const char* v = getenv("SPMV_AMD_ZERO_START")) s->zero_start = v[0] != '0';
+    if (const char* v = getenv("SPMV_AMD_AP_RECOMPUTE")) s->ap_recompute = v[0] == '1' ? 1 : 0;
 #ifdef SPMV_AMD_LAB
     if (const char* v = getenv("SPMV_AMD_TEST_WEDGE_OVERLAPPED_EXCHANGE")) s->test_wedge_overlapped_exchange = atoi(v);
 #endif
@@ -572,6 +586,7 @@ extern "C" void spmv_amd_cg_slab_destroy(SpmvAmdCgSlab* s) {
     device_release(s->block_map_interior);
     device_release(s->slow_list_whole);
     device_release(s->slow_list_interior);
+    device_release(s->row_block_fast);
     s->planes_on = false;
     s->r = s->Ap = s->p_alloc = s->p = nullptr;
     s->ring_alloc.clear();

@@ -110,14 +110,21 @@ int slab_spmv(SpmvAmdCgSlab* s, bool with_dot, bool overlap, const int* skip, co
 // p_out = r + beta p_in, Ap = A p_out, the partials of p_out . Ap and their sum: the direction update of iteration `iteration`
 // (1-based, as the kernels count) and the SpMV of the next one in one launch (+ one over the slow blocks), on a slab without
 // neighbours. spmv_done as in slab_spmv.
-int slab_direction_spmv(SpmvAmdCgSlab* s, const double* p_in, double* p_out, int iteration, hipEvent_t spmv_done) {
+int slab_direction_spmv(SpmvAmdCgSlab* s, const double* p_in, double* p_out, int iteration, hipEvent_t spmv_done, bool ap_not_stored) {
     s->spmv_split_at = -1;
-    const DirectionSpmv d{s->d_s, iteration, s->device_form, s->r, p_in, p_out, s->slow_list_whole, s->slow_count_whole};
+    const DirectionSpmv d{s->d_s, iteration, s->device_form, s->r, p_in, p_out, s->slow_list_whole, s->slow_count_whole, ap_not_stored};
     const int used = launch_stencil5_direction_spmv(s->A.view, s->plan_whole, d, s->Ap, 1.0, s->partials_spmv, s->shape.reverse, s->compute, *s->sym());
     if (s->tl_after_interior) HIP_CHECK(hipEventRecord(s->tl_after_interior, s->compute));
     if (spmv_done) HIP_CHECK(hipEventRecord(spmv_done, s->compute));
     reduce_spmv_partials(s, used, &s->d_s->pAp, &s->d_s->converged, s->spmv_progress, s->spmv_progress_value, s->reduce_mailbox);
     return used;
+}
+
+// The r update behind a slab_direction_spmv that did not store A p' on its fast blocks (LoopShape::ap_recomputed): r -= alpha A p_new
+// with the r.r partials into partials_blas, cg_update_r_kernel's slots. Returns the partial count.
+int slab_update_r_recompute(SpmvAmdCgSlab* s, const double* p_new, bool reverse) {
+    return launch_cg_update_r_recompute(s->A.view, s->plan_whole, s->d_s, p_new, s->Ap, s->r, s->partials_blas, s->row_block_fast, reverse, s->compute,
+                                        *s->sym());
 }
 
 static const char* query_name(hipError_t e) {
@@ -226,6 +233,7 @@ ShapeInputs shape_inputs(const SpmvAmdCgSlab* s, bool detailed_timers) {
     in.late_bulk = s->late_bulk, in.fuse_init_residual = s->fuse_init_residual, in.x0_known_zero = s->x0_known_zero;
     in.zero_start_parts = s->zero_start_mask();
     in.zero_rows_plus_zero = s->zero_rows_plus_zero;
+    in.ap_recompute = s->ap_recompute, in.skew_eligible = s->skew_eligible && s->row_block_fast != nullptr;
     return in;
 }
 
@@ -363,6 +371,7 @@ struct SolveRun {
 void SolveRun::begin() {
     s->reduce_mailbox = nullptr;  // the initial SpMV has no dot product
     s->op_failed = false;
+    s->last_ap_recomputed = L.ap_recomputed, s->last_recompute_launches = 0;
     memset(stats, 0, sizeof(*stats));
     // residual history: one slot per iteration, capped at 2^20 entries (later iterations go unrecorded)
     const int want_hist = slab::want_hist(config->max_iters);
@@ -493,7 +502,7 @@ void SolveRun::stage_spmv() {
     // fused_direction: the launch of iterations >= 1 writes this iteration's direction (s->p, the slot the direction stage chose)
     // from the previous one on its way; `enqueued` is the number of the iteration that direction belongs to, as the kernels count
     const auto spmv = [&](hipEvent_t spmv_done) {
-        if (L.fused_direction && enqueued > 0) return slab_direction_spmv(s, direction_from, s->p, enqueued, spmv_done);
+        if (L.fused_direction && enqueued > 0) return slab_direction_spmv(s, direction_from, s->p, enqueued, spmv_done, L.ap_recomputed);
         return slab_spmv(s, true, halo_in_flight, skip, nullptr, spmv_done);
     };
     if (b_is_p0 && enqueued == 0) {
@@ -539,7 +548,9 @@ void SolveRun::stage_update_r() {
           [&] {
               // r0_in_ring: r0 lies in ring slot 0 alone (p0 = r0, stored once): the update of iteration 0 reads it there
               // (b_is_p0: r0 is b itself)
-              if (L.r0_in_ring && enqueued == 0) launch_cg_update_r_from(nl, s->d_s, s->Ap, b_is_p0 ? s->b : s->ring[0], s->r, s->partials_blas, s->compute, !backward);
+              // ap_recomputed: the fused launch of iterations >= 1 left A p' unstored on its fast blocks; s->p is the p' it wrote
+              if (L.ap_recomputed && enqueued > 0) slab_update_r_recompute(s, s->p, !backward), ++s->last_recompute_launches;
+              else if (L.r0_in_ring && enqueued == 0) launch_cg_update_r_from(nl, s->d_s, s->Ap, b_is_p0 ? s->b : s->ring[0], s->r, s->partials_blas, s->compute, !backward);
               else launch_cg_update_r(nl, s->d_s, s->Ap, s->r, s->partials_blas, s->compute, !backward);
           });
     mark(enqueued, 4);

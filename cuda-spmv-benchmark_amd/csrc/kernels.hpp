@@ -178,9 +178,16 @@ struct DirectionSpmv {
     double* p_out;
     const int* slow_list;
     int slow_count;
+    bool ap_not_stored = false;  // the first launch leaves y alone on its fast blocks: launch_cg_update_r_recompute follows
 };
 int launch_stencil5_direction_spmv(const SlabCsr& m, const Stencil5Plan& plan, const DirectionSpmv& d, double* y, double alpha,
                                    double* d_dot_partials, bool reverse, hipStream_t stream, const SymPlanes& planes);
+// r -= (s->rr_old / s->pAp) A p_new with the r.r partials of launch_cg_update_r (same slots, same bits; returns their count), behind
+// a launch_stencil5_direction_spmv with ap_not_stored: A p_new is recomputed from p_new on the skewed block tiles of
+// skew_geometry.hpp where the element's row block is fast (row_fast: one byte per row block of the plan's block map, 1 = every
+// block tile fast, 0 = none; slab::skew_eligible) and read from Ap elsewhere. The whole-slab plan of a slab without halo rows.
+int launch_cg_update_r_recompute(const SlabCsr& m, const Stencil5Plan& plan, const CgScalars* s, const double* p_new, const double* Ap, double* r,
+                                 double* partials, const unsigned char* row_fast, bool reverse, hipStream_t stream, const SymPlanes& planes);
 // Iteration 0's SpMV of a solve that starts from x0 = 0 on a matrix whose rows sum to +0.0 over zero operands (slab_decisions.hpp,
 // LoopShape::b_is_p0; stencil5_first_block_kernel): the in-loop block launch on x = b -- y = alpha A b and the b . (A b) partials,
 // as launch_stencil5_spmv writes them -- that also leaves the b . b partials in `self_partials`, same slots, each summed as the

@@ -143,6 +143,10 @@ struct ShapeInputs {
     // 0 with zero_start off; else 1 = first launch without x loads, 2 = r0 stored once, 4 = flush without x_in, 8 = b serves as p0
     int zero_start_parts;
     bool zero_rows_plus_zero;  // established at creation: every row of A sums to +0.0 over zero operands (sums_to_plus_zero)
+    // the r update that recomputes A p' (skew_geometry.hpp): the option (0 off, 1 where eligible) and whether every row block of the
+    // whole-slab launch's block map is all-fast or all-slow (skew_eligible, established with the block maps)
+    int ap_recompute;
+    bool skew_eligible;
 };
 
 struct LoopShape {
@@ -160,6 +164,10 @@ struct LoopShape {
     // matrix, the direction ring, no detailed timers, a whole-slab plan on the block kernel whose slow blocks are at most 1 / 16 of
     // its blocks. The direction stage then enqueues no vector launch and late bulk has nothing to split.
     bool fused_direction = false;
+    // On top of fused_direction, in iterations >= 1: the fused launch does not store A p' on its fast blocks and the r update
+    // recomputes it from p' on skewed block tiles (skew_geometry.hpp; cg_update_r_recompute_kernel): 16 B/row less per iteration.
+    // Iteration 0 and every slab that is not eligible keep the stored A p and cg_update_r_kernel.
+    bool ap_recomputed = false;
     // The two ends of a solve on a slab without neighbours that owns its matrix and takes the initial residual from the first
     // SpMV's launch. zero_start: x0 holds the library's own zeros, and that launch requests no x value on interior grid rows.
     // r0_in_ring (any x0): the launch stores r0 once, as p0 into ring slot 0, and the r update of iteration 0 reads it there.
@@ -193,6 +201,7 @@ inline LoopShape loop_shape(const ShapeInputs& in) {
     // (ring mode only: with the in-place form the x update of the converging iteration rides in that very launch)
     L.fused_direction = in.fused_direction != 0 && !L.multi && in.owns_matrix && L.slots > 1 && !L.detail &&
                         direction_spmv_available(in, /*cap=*/in.fused_direction != 2);
+    L.ap_recomputed = L.fused_direction && in.ap_recompute != 0 && in.skew_eligible;
     L.late = in.late_bulk && !L.detail && L.slots > 1 && !L.fused_direction;
     // (ring mode only, like fused_direction: the in-place form keeps every launch it had)
     const bool own_ends = !L.multi && in.owns_matrix && L.slots > 1 && in.fuse_init_residual;

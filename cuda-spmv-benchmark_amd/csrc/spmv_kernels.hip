@@ -23,6 +23,7 @@
 
 #include "direction_device.hpp"
 #include "reduce_device.hpp"
+#include "skew_geometry.hpp"
 #include "slab_decisions.hpp"
 #include "stencil_geometry.hpp"
 #include "stencil_row_device.hpp"
@@ -578,8 +579,10 @@ __global__ __launch_bounds__(64) void stencil5_rowlds_block_kernel(
 // the launch of the converging iteration (or of one past it) reads no vector.
 // A block that is not fast (map byte 0) only writes p' on the rows it holds; its A p' and partials come from
 // stencil5_block_list_kernel behind this launch, which reads p' from memory.
+// kStoreAp = false (LoopShape::ap_recomputed): the fast path does not store A p' -- the r update behind it recomputes it from p'
+// (cg_update_r_recompute_kernel) -- and is the same code otherwise: p', the LDS copy, the fma chains, the partials and their slots.
 // ---------------------------------------------------------------------------------
-template <int kRows>
+template <int kRows, bool kStoreAp = true>
 __global__ __launch_bounds__(64) void stencil5_direction_block_kernel(
     SlabCsr m, const CgScalars* __restrict__ s, int iteration, int fma_form, const double* __restrict__ rvec, const double* __restrict__ p_in,
     double* __restrict__ p_out, double* __restrict__ y, double alpha, int gi_lo, int gi_hi, int col_tiles, int total_blocks, int run, int reverse,
@@ -655,7 +658,7 @@ __global__ __launch_bounds__(64) void stencil5_direction_block_kernel(
                     const double xc = pv[r + 1][h], xn = pv[r][h], xs = pv[r + 2][h];
                     const double sum = stencil5_row(j, n, sp.w, xw[h], sp.c, xc, sp.e, xe[h], sp.n, xn, sp.s5, xs);
                     dot = fma(xc, sum, dot);
-                    __builtin_nontemporal_store(alpha * sum, y + ((long long)li * n + j));
+                    if constexpr (kStoreAp) __builtin_nontemporal_store(alpha * sum, y + ((long long)li * n + j));
                 }
             }
             dot = wave_sum(dot);
@@ -687,6 +690,127 @@ __global__ __launch_bounds__(64) void stencil5_block_list_kernel(SlabCsr m, cons
     const int col_tile = block - row_block * col_tiles;
     const int li0 = gi_lo + row_block * block_rows;
     rowlds_block_slow_rows(m, x, y, alpha, gi_lo, gi_hi, gfirst, col_tiles, li0, block_rows, col_tile, col_tile * kLdsTileCols, (int)threadIdx.x, 0, lds, dot_partials, sp);
+}
+
+// ---------------------------------------------------------------------------------
+// The r update that RECOMPUTES A p' (single-rank slabs, LoopShape::ap_recomputed): r -= alpha A p' with the r.r partials,
+// where the fused launch above (kStoreAp = false) has not stored A p' on its fast blocks. A p' is a pure function of p', which is in
+// memory anyway: 8 B/row less written there, and here p' with its seam rows is read instead of A p'. The partials must be
+// cg_update_r_kernel's, one per 128 consecutive elements of the LINEAR index, so the block tiles are cut at those boundaries
+// (skew_geometry.hpp): one wave takes kRows chunks, the t-th chunk that starts in each grid row of its row block, lane l the pair
+// 2 l, 2 l + 1 of each as in cg_update_r_kernel. Where the row block is fast and every chunk of the wave lies inside its grid row,
+// all loads -- r and p' of the pair, p' at -n and +n, the two outer neighbours -- are issued before the scalars are looked at, W / E
+// come from the neighbouring lanes, and the sum is stencil5_row on the quintuple: the very chain the fused launch ran, whose store
+// was 1.0 * sum. Every other wave goes chunk by chunk and element by element (ap_at): a slow row block's A p' is read from Ap, where
+// stencil5_block_list_kernel stored it; a chunk that straddles two grid rows decides per element. Same tile -> XCD relabelling as
+// the fused launch, so that the seam rows are found in the L2 that read them. A launch past convergence only reads.
+// ---------------------------------------------------------------------------------
+// A p' at element i: read where its row block is slow, recomputed where it is fast (operands outside the grid are 0.0, and
+// stencil5_row ignores W in column 0 and E in column n - 1, as in the fused launch)
+__device__ __forceinline__ double ap_at(long long i, int n, int rows, int block_rows, const double* __restrict__ p, const double* __restrict__ Ap,
+                                        const unsigned char* __restrict__ row_fast, const SymPlanes& sp) {
+    const int li = (int)(i / n), j = (int)(i - (long long)li * n);
+    if (row_fast[li / block_rows] == 0) return Ap[i];
+    const double xw = j > 0 ? p[i - 1] : 0.0, xe = j < n - 1 ? p[i + 1] : 0.0;
+    const double xn = li > 0 ? p[i - n] : 0.0, xs = li < rows - 1 ? p[i + n] : 0.0;
+    return stencil5_row(j, n, sp.w, xw, sp.c, p[i], sp.e, xe, sp.n, xn, sp.s5, xs);
+}
+
+// two consecutive doubles: one 16-byte load where the address allows it (i +- n with an even n), else two 8-byte loads
+__device__ __forceinline__ d2 load_pair(const double* __restrict__ at, bool aligned) {
+    if (aligned) return *reinterpret_cast<const d2*>(at);
+    d2 v;
+    v.x = at[0], v.y = at[1];
+    return v;
+}
+
+template <int kRows>
+__global__ __launch_bounds__(64) void cg_update_r_recompute_kernel(size_t elements, int n, int rows, const CgScalars* __restrict__ s,
+                                                                   const double* __restrict__ p, const double* __restrict__ Ap,
+                                                                   double* __restrict__ rvec, double* __restrict__ partials, int col_tiles,
+                                                                   int total_blocks, int run, int reverse,
+                                                                   const unsigned char* __restrict__ row_fast, SymPlanes sp) {
+    const int block = rowlds_tile_of_block((int)blockIdx.x, run, total_blocks, reverse);
+    if (block < 0) return;
+    const int row_block = block / col_tiles, t = block - row_block * col_tiles, lane = (int)threadIdx.x;
+    const long long chunks = slab::chunk_count(elements);
+    const size_t pairs = elements >> 1;
+    const int fast = (int)row_fast[row_block];  // a vector load, requested in front of the r / p' loads and tested behind them
+    slab::SkewChunk c[kRows];
+    // the unguarded -n / +n loads need grid rows above and below every row of the block (a fast block never holds the grid's first
+    // or last grid row; the loads are issued before the byte is known)
+    bool whole = row_block * kRows >= 1 && row_block * kRows + kRows <= rows - 1;
+#pragma unroll
+    for (int k = 0; k < kRows; ++k) {
+        c[k] = slab::skew_chunk(row_block, t, k, kRows, n, rows, chunks);
+        whole = whole && c[k].inside_row;
+    }
+    d2 rv[kRows], pc[kRows], pn[kRows], ps[kRows];
+    double po[kRows];  // lane 0: the W neighbour left of the chunk; lane 63: the E neighbour right of it
+    if (whole) {
+        const bool aligned = (n & 1) == 0;
+#pragma unroll
+        for (int k = 0; k < kRows; ++k) {
+            const size_t pair = (size_t)c[k].chunk * 64 + lane;
+            const double* __restrict__ at = p + 2 * pair;
+            rv[k] = load_once(rvec, pair);
+            pc[k] = *reinterpret_cast<const d2*>(at);  // plain: the rows below and above re-use these lines
+            pn[k] = load_pair(at - n, aligned);
+            ps[k] = load_pair(at + n, aligned);
+        }
+#pragma unroll
+        for (int k = 0; k < kRows; ++k) {
+            const bool outer = (lane == 0 && c[k].start_col > 0) || (lane == 63 && c[k].start_col + slab::kChunk < n);
+            const long long at = c[k].chunk * slab::kChunk + (lane == 0 ? -1 : slab::kChunk + lane - 63);
+            po[k] = outer ? p[at] : 0.0;
+        }
+    }
+    const int converged = s->converged;
+    const double rr_old = s->rr_old, pAp = s->pAp;
+    if (converged) return;
+    const double alpha = rr_old / pAp;
+    if (whole && __builtin_amdgcn_readfirstlane(fast) != 0) {
+#pragma unroll
+        for (int k = 0; k < kRows; ++k) {
+            const double from_west = __shfl_up(pc[k].y, 1), from_east = __shfl_down(pc[k].x, 1);
+            const double xw = lane > 0 ? from_west : po[k], xe = lane < 63 ? from_east : po[k];
+            const int j = c[k].start_col + 2 * lane;
+            const double sum_x = stencil5_row(j, n, sp.w, xw, sp.c, pc[k].x, sp.e, pc[k].y, sp.n, pn[k].x, sp.s5, ps[k].x);
+            const double sum_y = stencil5_row(j + 1, n, sp.w, pc[k].x, sp.c, pc[k].y, sp.e, xe, sp.n, pn[k].y, sp.s5, ps[k].y);
+            d2 v = rv[k];
+            v.x = fma(-alpha, sum_x, v.x);
+            v.y = fma(-alpha, sum_y, v.y);
+            store_once(rvec, (size_t)c[k].chunk * 64 + lane, v);
+            double acc = fma(v.x, v.x, 0.0);
+            acc = fma(v.y, v.y, acc);
+            acc = wave_sum(acc);
+            if (lane == 0) partials[c[k].chunk] = acc;
+        }
+        return;
+    }
+#pragma unroll 1
+    for (int k = 0; k < kRows; ++k) {
+        const slab::SkewChunk ck = slab::skew_chunk(row_block, t, k, kRows, n, rows, chunks);
+        if (!ck.exists) continue;
+        const size_t pair = (size_t)ck.chunk * 64 + lane;
+        double acc = 0.0;
+        if (pair < pairs) {
+            const long long i = 2 * (long long)pair;
+            d2 v = load_once(rvec, pair);
+            v.x = fma(-alpha, ap_at(i, n, rows, kRows, p, Ap, row_fast, sp), v.x);
+            v.y = fma(-alpha, ap_at(i + 1, n, rows, kRows, p, Ap, row_fast, sp), v.y);
+            store_once(rvec, pair, v);
+            acc = fma(v.x, v.x, acc);
+            acc = fma(v.y, v.y, acc);
+        }
+        if ((elements & 1) && ck.chunk == 0 && lane == 0) {  // the odd last element, where cg_update_r_kernel adds it
+            const double rl = fma(-alpha, ap_at((long long)elements - 1, n, rows, kRows, p, Ap, row_fast, sp), rvec[elements - 1]);
+            rvec[elements - 1] = rl;
+            acc = fma(rl, rl, acc);
+        }
+        acc = wave_sum(acc);
+        if (lane == 0) partials[ck.chunk] = acc;
+    }
 }
 
 // ---------------------------------------------------------------------------------
@@ -1592,17 +1716,38 @@ int launch_stencil5_direction_spmv(const SlabCsr& m, const Stencil5Plan& p, cons
     }
     const dim3 grid((unsigned)xcd_padded_grid(blocks, p.xcd_run));
     const int gfirst = m.row_offset / m.grid_size;
-#define SPMV_AMD_LAUNCH_DIRECTION_BLOCK(ROWS)                                                                                          \
-    hipLaunchKernelGGL((stencil5_direction_block_kernel<ROWS>), grid, dim3(64), 0, stream, m, d.s, d.iteration, d.fma_form ? 1 : 0, d.r, \
-                       d.p_in, d.p_out, y, alpha, p.gi_lo, p.gi_hi, p.row_blocks, blocks, p.xcd_run, reverse ? 1 : 0, d_dot_partials,    \
+#define SPMV_AMD_LAUNCH_DIRECTION_BLOCK(ROWS, STORE)                                                                                      \
+    hipLaunchKernelGGL((stencil5_direction_block_kernel<ROWS, STORE>), grid, dim3(64), 0, stream, m, d.s, d.iteration, d.fma_form ? 1 : 0, \
+                       d.r, d.p_in, d.p_out, y, alpha, p.gi_lo, p.gi_hi, p.row_blocks, blocks, p.xcd_run, reverse ? 1 : 0, d_dot_partials, \
                        p.block_map, sp)
-    if (p.block_rows == 4) SPMV_AMD_LAUNCH_DIRECTION_BLOCK(4);
-    else SPMV_AMD_LAUNCH_DIRECTION_BLOCK(8);
+    if (p.block_rows == 4 && !d.ap_not_stored) SPMV_AMD_LAUNCH_DIRECTION_BLOCK(4, true);
+    else if (p.block_rows == 4) SPMV_AMD_LAUNCH_DIRECTION_BLOCK(4, false);
+    else if (!d.ap_not_stored) SPMV_AMD_LAUNCH_DIRECTION_BLOCK(8, true);
+    else SPMV_AMD_LAUNCH_DIRECTION_BLOCK(8, false);
 #undef SPMV_AMD_LAUNCH_DIRECTION_BLOCK
     if (d.slow_count > 0)
         hipLaunchKernelGGL(stencil5_block_list_kernel, dim3((unsigned)d.slow_count), dim3(64), 0, stream, m, d.s, d.iteration, d.p_out, y, alpha,
                            p.gi_lo, p.gi_hi, gfirst, p.row_blocks, p.block_rows, d.slow_list, d_dot_partials, sp);
     return p.partials;
+}
+
+int launch_cg_update_r_recompute(const SlabCsr& m, const Stencil5Plan& p, const CgScalars* s, const double* p_new, const double* Ap, double* r,
+                                 double* partials, const unsigned char* row_fast, bool reverse, hipStream_t stream, const SymPlanes& sp) {
+    const int blocks = rowlds_block_tiles(p);
+    if (blocks <= 0 || row_fast == nullptr || partials == nullptr || p.first_row != 0 || p.last_row != m.n_local || m.halo_before != 0 ||
+        m.halo_after != 0) {
+        fprintf(stderr, "[spmv] the recomputing r update exists for whole-slab row-lds plans with a block map on slabs without halo rows only\n");
+        exit(EXIT_FAILURE);
+    }
+    const dim3 grid((unsigned)xcd_padded_grid(blocks, p.xcd_run));
+    const int n = m.grid_size;
+#define SPMV_AMD_LAUNCH_R_RECOMPUTE(ROWS)                                                                                              \
+    hipLaunchKernelGGL((cg_update_r_recompute_kernel<ROWS>), grid, dim3(64), 0, stream, (size_t)m.n_local, n, m.n_local / n, s, p_new, Ap, r, \
+                       partials, p.row_blocks, blocks, p.xcd_run, reverse ? 1 : 0, row_fast, sp)
+    if (p.block_rows == 4) SPMV_AMD_LAUNCH_R_RECOMPUTE(4);
+    else SPMV_AMD_LAUNCH_R_RECOMPUTE(8);
+#undef SPMV_AMD_LAUNCH_R_RECOMPUTE
+    return (int)slab::chunk_count((size_t)m.n_local);
 }
 
 int launch_stencil5_first_spmv(const SlabCsr& m, const Stencil5Plan& p, const double* b, double* y, double alpha, double* d_dot_partials,

@@ -502,7 +502,9 @@ int spmv_amd_cg_slab_solve(SpmvAmdCgSlab* s, const CGConfigMultiGPU* config,
 /* Which shape this slab's loop takes and who decided (a static string): "single rank"; "single rank: direction update inside the
  * block SpMV" (a rank without neighbours that owns its matrix, direction ring > 1, a whole-slab launch on block tiles whose
  * row-by-row blocks are at most 1/16 of its blocks, SPMV_AMD_FUSED_DIRECTION not 0: the direction update p' = r + beta p of
- * iteration k is evaluated inside the SpMV launch of iteration k + 1; a solve with detailed timers keeps the two launches); "pipeline (verified against the plain
+ * iteration k is evaluated inside the SpMV launch of iteration k + 1; a solve with detailed timers keeps the two launches; where
+ * every row of block tiles of that launch is evaluated either all by the fast path or all row by row, and SPMV_AMD_AP_RECOMPUTE is
+ * not 0, that launch does not store A p' on the fast blocks and the r update recomputes it from p', same bits); "pipeline (verified against the plain
  * order at creation)"; "plain: SPMV_AMD_NO_OVERLAP=1"; "plain: the in-place form (ring 1) or a slab too thin to split"; "plain: the
  * pipeline's residual history differed from the plain order's in the creation check". The creation check: the first slab created on a communicator that exchanges halos solves four iterations
  * in each shape (default b = 1, x0 = 0); the shapes are bit-identical by construction, so a difference on any rank -- lost or stale

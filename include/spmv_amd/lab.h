@@ -47,7 +47,12 @@ SpmvAmdCgSlab* spmv_amd_cg_slab_create_stencil5_as(int n, int as_rank, int as_wo
  * 0 = the first SpMV and the flush of x always load x0 and the first launch stores r0 twice; spmv_amd_cg_slab_initial_stage says
  * which form a solve takes; results are bit-identical) with "zero_start_parts" 0..15 (a field of the LAB build only: which parts "zero_start" 1 switches on, for A/B
  * runs of each: 1 = the first launch without x loads, 2 = r0 stored once, 4 = the flush of x without x0, 8 = b serves as p0 and
- * iteration 0's SpMV sums b.b, spmv_amd_cg_slab_first_stage; default 15). Returns 0, or -1 for an unknown name or value. */
+ * iteration 0's SpMV sums b.b, spmv_amd_cg_slab_first_stage; default 15), "ap_recompute" 0/1 (the product's SPMV_AMD_AP_RECOMPUTE: 1 = in
+ * iterations >= 1 of the fused direction loop the fused launch does not store A p' on its fast blocks and the r update recomputes
+ * it from p' on skewed block tiles, where every row block of the whole-slab block map is all-fast or all-slow;
+ * spmv_amd_cg_slab_ap_form says which ran; results are bit-identical) and "direction_store" 0/1 (a field of the LAB build only: 0 =
+ * spmv_amd_cg_slab_direction_spmv runs the fused launch in the form that does not store A p'). Returns 0, or -1 for an unknown
+ * name or value. */
 int spmv_amd_cg_slab_set_option(SpmvAmdCgSlab* s, const char* name, long long value);
 
 /* The tile class map of a slab in the symmetric form as creation wrote it (spmv_amd_cg_slab_uniform_tiles): one byte per row-lds
@@ -78,6 +83,19 @@ int spmv_amd_cg_slab_spmv_dot(const SpmvAmdCgSlab* s, double* pAp, double* parti
  * a slab that cannot take the launch (neighbours, ring 1, no block map). */
 int spmv_amd_cg_slab_direction_spmv(SpmvAmdCgSlab* s, const double* r, const double* p_in, double beta, int iteration_matches, int converged,
                                     double* p_out, double* Ap, double* pAp, double* partials, int cap);
+
+/* The r update of an iteration >= 1 alone, once, on the caller's vectors (host, n_local doubles each) and scalars (alpha = rr_old /
+ * pAp on the device): recompute = 0, cg_update_r_kernel on (r, Ap); recompute != 0, the launch that recomputes A p' from p_new on
+ * the fast row blocks and reads Ap on the slow ones only (csrc/skew_geometry.hpp). reverse != 0: the tiles are walked from the end.
+ * converged != 0: the launch must return on the scalars. r_out (n_local doubles) and partials (min(count, cap) doubles, NaN where
+ * the launch did not write) come back. Returns the number of partials the launch writes (one per 128 consecutive elements), or -1
+ * where recompute is asked of a slab that is not eligible. */
+int spmv_amd_cg_slab_update_r_stage(SpmvAmdCgSlab* s, int recompute, int reverse, const double* r, const double* p_new, const double* Ap,
+                                    double rr_old, double pAp, int converged, double* r_out, double* partials, int cap);
+/* The r update that recomputes A p': bit 0 = a solve would take the form now, bit 1 = the last solve took it, bit 2 = every row block
+ * of the whole-slab block map is all-fast or all-slow. *launches (may be NULL) = the recomputing launches the last solve enqueued.
+ * s == NULL: the workspace slab of cg_solve_device, which borrows the caller's operator (-1: there is none). */
+int spmv_amd_cg_slab_ap_form(const SpmvAmdCgSlab* s, int* launches);
 
 /* The initial stage of a solve alone, once, on the slab's stored b and x0: the first SpMV's launch (r0 = b - A x0, p0 = r0, one
  * partial of r0.r0 per 128 x 1 tile) and the reduction of the partials, in the form a solve would take now. Returns the form: bit 0 =
