@@ -143,7 +143,7 @@ DECLARED_SYMBOLS = [
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
 LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_cg_slab_block_map", "spmv_amd_cg_slab_slow_blocks",
-                    "spmv_amd_cg_slab_direction_spmv", "spmv_amd_cg_slab_spmv_dot", "spmv_amd_cg_slab_initial_stage", "spmv_amd_cg_slab_first_stage", "spmv_amd_cg_slab_stored_b", "spmv_amd_cg_slab_update_r_stage", "spmv_amd_cg_slab_ap_form", "spmv_amd_pcg_stage",
+                    "spmv_amd_cg_slab_direction_spmv", "spmv_amd_cg_slab_spmv_dot", "spmv_amd_cg_slab_initial_stage", "spmv_amd_cg_slab_first_stage", "spmv_amd_cg_slab_stored_b", "spmv_amd_cg_slab_update_r_stage", "spmv_amd_cg_slab_ap_form", "spmv_amd_cg_slab_update_r_from_stage", "spmv_amd_cg_slab_first_recompute_form", "spmv_amd_pcg_stage",
                     "spmv_amd_pcg_last_step_launches", "spmv_amd_cg_multi_stage",
                     "spmv_amd_pcg_last_multigrid_cycles", "spmv_amd_precond_multigrid_level_csr", "spmv_amd_mg_stage"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
@@ -264,6 +264,11 @@ def lib():
         L.spmv_amd_cg_slab_update_r_stage.restype = C.c_int
         L.spmv_amd_cg_slab_ap_form.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.spmv_amd_cg_slab_ap_form.restype = C.c_int
+        L.spmv_amd_cg_slab_update_r_from_stage.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int,
+                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.spmv_amd_cg_slab_update_r_from_stage.restype = C.c_int
+        L.spmv_amd_cg_slab_first_recompute_form.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.spmv_amd_cg_slab_first_recompute_form.restype = C.c_int
         L.spmv_amd_pcg_stage.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PcgStageArgs), C.POINTER(PcgScalars)]
         L.spmv_amd_pcg_stage.restype = C.c_int
         L.spmv_amd_pcg_last_step_launches.argtypes = []
@@ -1140,6 +1145,36 @@ class CgSlab:
         if used < 0:
             raise RuntimeError("this slab cannot take the r update that recomputes A p' (a row block that is neither all-fast nor all-slow, ring 1)")
         return r_out, partials[:used]
+
+    def update_r_from_stage(self, src, Ap, rr_old, pAp, recompute=True, reverse=False, converged=0):
+        """spmv_amd_cg_slab_update_r_from_stage (LAB build only): iteration 0's r update where r0 and p0 are the one vector src, once.
+        recompute False: cg_update_r_from_kernel on (Ap, src); True: the out-of-place instance that recomputes A src on the fast row
+        blocks and reads Ap on the slow ones. Returns (r_out, src as it lies on the device afterwards, partials), NaN where the launch
+        did not write."""
+        if not is_lab():
+            raise RuntimeError("the r update alone runs in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        Ap = np.ascontiguousarray(Ap, dtype=np.float64)
+        r_out, src_back = np.empty_like(src), np.empty_like(src)
+        partials = np.empty(len(src) // 128 + 2, dtype=np.float64)
+        used = lib().spmv_amd_cg_slab_update_r_from_stage(self.h, 1 if recompute else 0, 1 if reverse else 0, src.ctypes.data, Ap.ctypes.data,
+                                                          float(rr_old), float(pAp), int(converged), r_out.ctypes.data, src_back.ctypes.data,
+                                                          partials.ctypes.data, len(partials))
+        if used < 0:
+            raise RuntimeError("this slab cannot take the r update that recomputes A p (a row block that is neither all-fast nor all-slow, ring 1)")
+        return r_out, src_back, partials[:used]
+
+    FIRST_FORMS = ("stored", "from b", "from ring slot 0", "in place")
+
+    def first_recompute_form(self):
+        """spmv_amd_cg_slab_first_recompute_form (LAB build only): (the form iteration 0 of a solve of at least one iteration would
+        take now, the form the last solve's took), each one of FIRST_FORMS: "stored" = A p0 stored and read back, the others = left
+        unstored on the fast blocks and recomputed by the r update from b / ring slot 0 / in place on (r, slot 0)."""
+        if not is_lab():
+            raise RuntimeError("iteration 0's form is read through the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        last = C.c_int(0)
+        now = int(lib().spmv_amd_cg_slab_first_recompute_form(self.h, C.byref(last)))
+        return self.FIRST_FORMS[now], self.FIRST_FORMS[last.value]
 
     def ap_form(self):
         """spmv_amd_cg_slab_ap_form (LAB build only): (a solve would recompute A p' in its r update now, the last solve did, the slab's

@@ -86,6 +86,11 @@ struct SpmvAmdCgSlab {
     bool skew_eligible = false;
     bool last_ap_recomputed = false;
     int last_recompute_launches = 0;
+    // SPMV_AMD_FIRST_RECOMPUTE (0 / 1, read at creation; LAB build: set_option("first_recompute", 0 | 1)): iteration 0 takes the same
+    // form (LoopShape::first_recomputed, slab_decisions.hpp first_form). last_first_form: what the last solve's iteration 0 took, as
+    // a FirstForm; counted apart from last_recompute_launches, which keeps meaning the launches of iterations >= 1.
+    int first_recompute = 1;
+    int last_first_form = 0;
     // x0 holds the zeros the LIBRARY wrote (the fill at creation, the API's default initial guess) and nothing has written it since:
     // every other writer of x0 clears this, an uploaded vector of zeros included -- x0 is never scanned. What it buys: DESIGN §4,
     // LoopShape::zero_start (the first launch) and flush_skips_x0 (every slab: the flush is pointwise).
@@ -151,6 +156,7 @@ struct SpmvAmdCgSlab {
     // a stand-in slab's mirrored system does not converge in 14 iterations as the rank of a real job does. Timing only.
     int stop_at = 0;
     int test_wedge_overlapped_exchange = 0;  // SPMV_AMD_TEST_WEDGE_OVERLAPPED_EXCHANGE=1 / 2, see exchange_halo
+    bool lab_first_store = true;  // set_option("first_store", 0): spmv_amd_cg_slab_first_stage runs the launch that does not store A b
     bool lab_direction_store = true;  // set_option("direction_store", 0): spmv_amd_cg_slab_direction_spmv runs the launch that does not store A p'
     bool guess_far_always = false;  // set_option("run_ahead", 2): every iteration is guessed "cannot converge": each solve learns of its convergence one iteration late
 #endif
@@ -240,11 +246,11 @@ void poison_halos(SpmvAmdCgSlab* s);
 ShapeInputs shape_inputs(const SpmvAmdCgSlab* s, bool detailed_timers);
 inline LoopShape loop_shape(const SpmvAmdCgSlab* s, bool detailed_timers = false) { return loop_shape(shape_inputs(s, detailed_timers)); }
 int slab_spmv(SpmvAmdCgSlab* s, bool with_dot, bool overlap, const int* skip, const double* input = nullptr, hipEvent_t spmv_done = nullptr,
-              const ResidualOut* init = nullptr, bool x_zero = false);
+              const ResidualOut* init = nullptr, bool x_zero = false, bool ap_not_stored = false);
 int slab_direction_spmv(SpmvAmdCgSlab* s, const double* p_in, double* p_out, int iteration, hipEvent_t spmv_done = nullptr, bool ap_not_stored = false);
-int slab_update_r_recompute(SpmvAmdCgSlab* s, const double* p_new, bool reverse);
+int slab_update_r_recompute(SpmvAmdCgSlab* s, const double* p_new, bool reverse, bool r_is_p = false);
 int slab_initial_residual(SpmvAmdCgSlab* s, const LoopShape& L, bool halo_in_flight);
-int slab_first_spmv(SpmvAmdCgSlab* s, bool reverse, hipEvent_t spmv_done = nullptr);
+int slab_first_spmv(SpmvAmdCgSlab* s, bool reverse, hipEvent_t spmv_done = nullptr, bool ap_not_stored = false);
 void reduce_spmv_partials(SpmvAmdCgSlab* s, int used, double* d_out, const int* skip, int* progress, int progress_value, const PeerMailbox* mailbox,
                           const double* partials = nullptr);
 void report_slab_state(void* user, FILE* out);

@@ -33,7 +33,14 @@ extern "C" int spmv_amd_cg_slab_spmv(SpmvAmdCgSlab* s, const double* x_full, dou
     upload(s->p, x_full + s->row_offset, (size_t)s->n_local);
     if (s->has_prev && s->row_offset >= s->halo) upload(s->p - s->halo, x_full + s->row_offset - s->halo, (size_t)s->halo);
     if (s->has_next && s->row_offset + s->n_local + s->halo <= s->n) upload(s->p + s->n_local, x_full + s->row_offset + s->n_local, (size_t)s->halo);
+#ifdef SPMV_AMD_LAB
+    // "first_store" 0 with the in-loop form: the block launch that leaves A x unstored on its fast blocks (y comes back as NaN there)
+    const bool unstored = s->spmv_with_dot && !s->lab_first_store;
+    if (unstored) HIP_CHECK(hipMemsetAsync(s->Ap, 0xFF, (size_t)s->n_local * sizeof(double), s->compute));
+    slab_spmv(s, /*with_dot=*/s->spmv_with_dot, /*overlap=*/false, nullptr, nullptr, nullptr, nullptr, false, unstored);
+#else
     slab_spmv(s, /*with_dot=*/s->spmv_with_dot, /*overlap=*/false, nullptr);
+#endif
     HIP_CHECK(hipStreamSynchronize(s->compute));
     HIP_CHECK(hipGetLastError());
     download(y_local, s->Ap, (size_t)s->n_local);
@@ -113,6 +120,8 @@ extern "C" int spmv_amd_cg_slab_set_option(SpmvAmdCgSlab* s, const char* name, l
     }
     else if (strcmp(name, "zero_start_parts") == 0) s->zero_start_parts = (int)value & 15;  // which parts "zero_start" 1 switches on: 1 | 2 | 4 | 8 (the field says which is which)
     else if (strcmp(name, "ap_recompute") == 0) s->ap_recompute = value != 0 ? 1 : 0;  // 1: A p' recomputed by the r update where the slab is eligible (LoopShape::ap_recomputed)
+    else if (strcmp(name, "first_recompute") == 0) s->first_recompute = value != 0 ? 1 : 0;  // 1: iteration 0 in the store-less form too where ap_recomputed holds (LoopShape::first_recomputed)
+    else if (strcmp(name, "first_store") == 0) s->lab_first_store = value != 0;  // 0: spmv_amd_cg_slab_first_stage, and spmv() in its in-loop form, run the launch that does not store A x
     else if (strcmp(name, "direction_store") == 0) s->lab_direction_store = value != 0;  // 0: spmv_amd_cg_slab_direction_spmv runs the fused launch that does not store A p'
     else if (strcmp(name, "zero_start") == 0) s->zero_start = value != 0;  // 0: x0 always loaded, r0 stored twice (the launches of before)
     else if (strcmp(name, "spmv_with_dot") == 0) s->spmv_with_dot = value != 0;  // spmv() in its in-loop form: p.Ap partials and their sum too
@@ -217,6 +226,40 @@ extern "C" int spmv_amd_cg_slab_ap_form(const SpmvAmdCgSlab* s, int* launches) {
     return (loop_shape(s).ap_recomputed ? 1 : 0) | (s->last_ap_recomputed ? 2 : 0) | (s->skew_eligible ? 4 : 0);
 }
 
+// Iteration 0's r update where r0 and p0 are one vector `src` (b, or ring slot 0), once, on the caller's vectors and scalars:
+// recompute == 0, cg_update_r_from_kernel on (Ap, src); recompute != 0, the out-of-place instance of LoopShape::first_recomputed on
+// (src, Ap) -- Ap is read on the slow row blocks only. r_out and the partials are filled with NaN beforehand; src_back: `src` as it
+// lies on the device behind the launch. Returns the partial count, or -1 where recompute is asked of a slab that is not eligible.
+extern "C" int spmv_amd_cg_slab_update_r_from_stage(SpmvAmdCgSlab* s, int recompute, int reverse, const double* src, const double* Ap, double rr_old,
+                                                    double pAp, int converged, double* r_out, double* src_back, double* partials, int cap) {
+    if (s->ring.size() < 2 || (recompute != 0 && (!s->skew_eligible || s->sym() == nullptr))) return -1;
+    const size_t nl = (size_t)s->n_local;
+    CgScalars sc;
+    memset(&sc, 0, sizeof sc);
+    sc.rr_old = rr_old, sc.pAp = pAp, sc.converged = converged != 0 ? 1 : 0;
+    HIP_CHECK(hipMemcpy(s->d_s, &sc, sizeof sc, hipMemcpyHostToDevice));
+    upload(s->ring[1], src, nl);
+    upload(s->Ap, Ap, nl);
+    const int count = cg_partial_count(nl);
+    HIP_CHECK(hipMemsetAsync(s->r, 0xFF, nl * sizeof(double), s->compute));
+    HIP_CHECK(hipMemsetAsync(s->partials_blas, 0xFF, (size_t)count * sizeof(double), s->compute));
+    if (recompute != 0) slab_update_r_recompute(s, s->ring[1], reverse != 0, /*r_is_p=*/true);
+    else launch_cg_update_r_from(nl, s->d_s, s->Ap, s->ring[1], s->r, s->partials_blas, s->compute, reverse != 0);
+    HIP_CHECK(hipStreamSynchronize(s->compute));
+    HIP_CHECK(hipGetLastError());
+    download(r_out, s->r, nl);
+    if (src_back != nullptr) download(src_back, s->ring[1], nl);
+    if (partials != nullptr && cap > 0) download(partials, s->partials_blas, (size_t)std::min(count, cap));
+    return count;
+}
+
+// Iteration 0's form (slab_decisions.hpp, FirstForm: 0 stored, 1 from b, 2 from ring slot 0, 3 in place) that a solve of at least one
+// iteration would take now; *last (may be null): what the last solve took.
+extern "C" int spmv_amd_cg_slab_first_recompute_form(const SpmvAmdCgSlab* s, int* last) {
+    if (last != nullptr) *last = s->last_first_form;
+    return (int)first_form(loop_shape(s), 1);
+}
+
 // The initial stage of a solve -- the first SpMV's launch and the reduction of its partials -- once, on the slab's stored b and x0,
 // in the form a solve would take now. Returns the form: bit 0 = LoopShape::zero_start, bit 1 = LoopShape::r0_in_ring; r0 == NULL:
 // only that, nothing is launched. -1: a slab with neighbours or one whose first SpMV does not write the residual.
@@ -259,7 +302,7 @@ extern "C" int spmv_amd_cg_slab_first_stage(SpmvAmdCgSlab* s, int reverse, doubl
     HIP_CHECK(hipMemsetAsync(s->partials_spmv, 0xFF, slots * sizeof(double), s->compute));
     HIP_CHECK(hipMemsetAsync(s->partials_first, 0xFF, slots * sizeof(double), s->compute));
     s->reduce_mailbox = nullptr;
-    const int used = slab_first_spmv(s, reverse != 0);
+    const int used = slab_first_spmv(s, reverse != 0, nullptr, !s->lab_first_store);
     reduce_spmv_partials(s, used, &s->d_s->rr_new, nullptr, nullptr, 0, nullptr, s->partials_first);
     launch_cg_scalars_init(s->d_s, nullptr, s->compute);
     reduce_spmv_partials(s, used, &s->d_s->pAp, &s->d_s->converged, nullptr, 0, nullptr);

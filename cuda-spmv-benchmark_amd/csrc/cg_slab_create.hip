@@ -257,6 +257,13 @@ void make_common(SpmvAmdCgSlab* s) {
     if (const char* v = getenv("SPMV_AMD_FUSED_DIRECTION")) s->fused_direction = v[0] == '1' ? 1 : 0;
     if (const char* v = getenv("SPMV_AMD_ZERO_START")) s->zero_start = v[0] != '0';
     if (const char* v = getenv("SPMV_AMD_AP_RECOMPUTE")) s->ap_recompute = v[0] == '1' ? 1 : 0;
+    if (const char* v = getenv("SPMV_AMD_FIRST_RECOMPUTE")) s->first_recompute = v[0] == '1' ? 1 : 0;
+    {
+        // grid rows per block tile: what SPMV_AMD_ROWLDS_BLOCK_ROWS asks, else by the slab's kind (the plans are made further down)
+        const char* v = getenv("SPMV_AMD_ROWLDS_BLOCK_ROWS");
+        s->shape.knobs.rowlds_block_rows =
+            default_block_rows(v && *v ? atoi(v) : -1, s->comm->exchanges_halos(), s->op == nullptr, s->ring_slots, s->fused_direction);
+    }
 #ifdef SPMV_AMD_LAB
     if (const char* v = getenv("SPMV_AMD_TEST_WEDGE_OVERLAPPED_EXCHANGE")) s->test_wedge_overlapped_exchange = atoi(v);
 #endif

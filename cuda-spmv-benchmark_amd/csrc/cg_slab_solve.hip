@@ -42,15 +42,21 @@ void reduce_spmv_partials(SpmvAmdCgSlab* s, int used, double* d_out, const int* 
 // spmv_done (optional): recorded behind the last SpMV launch, before the reduction of its partials.
 // init (may be null): the launches write r = b - A x, p = r and r.r partials instead of A x (fused initial residual);
 // the caller reduces the partials. x_zero (with init, on a slab without neighbours that owns its matrix): `input` holds zeros the
-// library wrote, see launch_stencil5_spmv. Returns the number of partial slots the launches wrote.
+// library wrote, see launch_stencil5_spmv. ap_not_stored (LoopShape::first_recomputed, iteration 0 on a caller's x0): the whole-slab
+// block launch leaves A p unstored on its fast blocks; only a slab whose SpMV is that one launch may ask.
+// Returns the number of partial slots the launches wrote.
 int slab_spmv(SpmvAmdCgSlab* s, bool with_dot, bool overlap, const int* skip, const double* input, hipEvent_t spmv_done,
-              const ResidualOut* init, bool x_zero) {
+              const ResidualOut* init, bool x_zero, bool ap_not_stored) {
     const SlabCsr& A = s->A.view;
     const double* in = input ? input : s->p;
     double* part = ((with_dot && s->fused_dot) || init) ? s->partials_spmv : nullptr;
     const auto [lo, hi] = s->halo_free();
     int used = 0;
     s->spmv_split_at = -1;
+    if (ap_not_stored && (s->op != nullptr || lo != 0 || hi != s->n_local)) {
+        fprintf(stderr, "[cg-slab] only the whole-slab block launch can leave A p unstored\n");
+        exit(EXIT_FAILURE);
+    }
     if (s->op != nullptr) {
         // the caller's operator: its fused launch when it has one (this library's stencil5-csr), else the vtable
         if (part != nullptr) {
@@ -65,7 +71,7 @@ int slab_spmv(SpmvAmdCgSlab* s, bool with_dot, bool overlap, const int* skip, co
     } else if (hi <= lo || (lo == 0 && hi == s->n_local) || (part == nullptr && !overlap)) {
         // one launch: a slab without halo rows, or of one or two grid rows, or a plain y = A x with the halos already in place
         if (overlap) HIP_CHECK(hipStreamWaitEvent(s->compute, s->ev_halo_done, 0));
-        used = launch_stencil5_spmv(A, s->plan_whole, in, s->Ap, 1.0, part, skip, s->shape.reverse, s->compute, init, s->sym(), x_zero);
+        used = launch_stencil5_spmv(A, s->plan_whole, in, s->Ap, 1.0, part, skip, s->shape.reverse, s->compute, init, s->sym(), x_zero, ap_not_stored);
         if (s->tl_after_interior) HIP_CHECK(hipEventRecord(s->tl_after_interior, s->compute));
     } else {
         // rows whose north and south neighbours are local run under the halo exchange; the first / last grid row of the slab once
@@ -121,10 +127,11 @@ int slab_direction_spmv(SpmvAmdCgSlab* s, const double* p_in, double* p_out, int
 }
 
 // The r update behind a slab_direction_spmv that did not store A p' on its fast blocks (LoopShape::ap_recomputed): r -= alpha A p_new
-// with the r.r partials into partials_blas, cg_update_r_kernel's slots. Returns the partial count.
-int slab_update_r_recompute(SpmvAmdCgSlab* s, const double* p_new, bool reverse) {
+// with the r.r partials into partials_blas, cg_update_r_kernel's slots. Returns the partial count. r_is_p (iteration 0 under
+// LoopShape::first_recomputed, p_new = b or ring slot 0): r = p_new - alpha A p_new, out of place.
+int slab_update_r_recompute(SpmvAmdCgSlab* s, const double* p_new, bool reverse, bool r_is_p) {
     return launch_cg_update_r_recompute(s->A.view, s->plan_whole, s->d_s, p_new, s->Ap, s->r, s->partials_blas, s->row_block_fast, reverse, s->compute,
-                                        *s->sym());
+                                        *s->sym(), r_is_p);
 }
 
 static const char* query_name(hipError_t e) {
@@ -234,6 +241,7 @@ ShapeInputs shape_inputs(const SpmvAmdCgSlab* s, bool detailed_timers) {
     in.zero_start_parts = s->zero_start_mask();
     in.zero_rows_plus_zero = s->zero_rows_plus_zero;
     in.ap_recompute = s->ap_recompute, in.skew_eligible = s->skew_eligible && s->row_block_fast != nullptr;
+    in.first_recompute = s->first_recompute;
     return in;
 }
 
@@ -246,9 +254,10 @@ int slab_initial_residual(SpmvAmdCgSlab* s, const LoopShape& L, bool halo_in_fli
 
 // LoopShape::b_is_p0: iteration 0's SpMV on b -- Ap = A b, the b.Ab partials into partials_spmv and the b.b partials into
 // partials_first, one launch -- with the marks slab_spmv leaves behind a one-launch SpMV. The caller reduces both arrays.
-int slab_first_spmv(SpmvAmdCgSlab* s, bool reverse, hipEvent_t spmv_done) {
+int slab_first_spmv(SpmvAmdCgSlab* s, bool reverse, hipEvent_t spmv_done, bool ap_not_stored) {
     s->spmv_split_at = -1;
-    const int used = launch_stencil5_first_spmv(s->A.view, s->plan_whole, s->b, s->Ap, 1.0, s->partials_spmv, s->partials_first, reverse, s->compute, *s->sym());
+    const int used = launch_stencil5_first_spmv(s->A.view, s->plan_whole, s->b, s->Ap, 1.0, s->partials_spmv, s->partials_first, reverse, s->compute, *s->sym(),
+                                                ap_not_stored);
     if (s->tl_after_interior) HIP_CHECK(hipEventRecord(s->tl_after_interior, s->compute));
     if (spmv_done) HIP_CHECK(hipEventRecord(spmv_done, s->compute));
     return used;
@@ -268,6 +277,7 @@ struct SolveRun {
     // L.b_is_p0 in a solve that runs iteration 0: b stands for ring slot 0 until the ring wraps, and iteration 0's SpMV is enqueued
     // by initial_residual (a solve of no iterations keeps the launch that only sums r0.r0)
     const bool b_is_p0;
+    const FirstForm first;  // iteration 0's A p0: stored and read back, or left unstored and recomputed by its r update (first_form)
     const PeerMailbox* const mailbox;  // non-null: the communicator's peer mailbox completes the sums (L.use_mailbox)
     const EdgeRows edges;              // pipeline: the rows the neighbours wait for, [0, count_a) and [second, second + count_b)
     const TraceRanges trace;
@@ -289,7 +299,7 @@ struct SolveRun {
     std::vector<int> sampled_iteration;  // 0-based loop index of each timed SpMV
 
     SolveRun(SpmvAmdCgSlab* slab, const CGConfigMultiGPU* cfg, CGStatsMultiGPU* st)
-        : s(slab), config(cfg), stats(st), L(loop_shape(slab, cfg->enable_detailed_timers != 0)), b_is_p0(L.b_is_p0 && cfg->max_iters > 0),
+        : s(slab), config(cfg), stats(st), L(loop_shape(slab, cfg->enable_detailed_timers != 0)), b_is_p0(L.b_is_p0 && cfg->max_iters > 0), first(first_form(L, cfg->max_iters)),
           mailbox(L.use_mailbox ? slab->comm->d_mailbox : nullptr),
           edges{L.head_rows, L.tail_start, L.pipeline ? (size_t)slab->n_local - L.tail_start : 0}, trace(L.detail || slab->roctx_always), nl((size_t)slab->n_local),
           skip(&slab->d_s->converged), timeline(slab->timeline_on && !L.detail) {
@@ -371,7 +381,7 @@ struct SolveRun {
 void SolveRun::begin() {
     s->reduce_mailbox = nullptr;  // the initial SpMV has no dot product
     s->op_failed = false;
-    s->last_ap_recomputed = L.ap_recomputed, s->last_recompute_launches = 0;
+    s->last_ap_recomputed = L.ap_recomputed, s->last_recompute_launches = 0, s->last_first_form = (int)first;
     memset(stats, 0, sizeof(*stats));
     // residual history: one slot per iteration, capped at 2^20 entries (later iterations go unrecorded)
     const int want_hist = slab::want_hist(config->max_iters);
@@ -456,7 +466,7 @@ void SolveRun::initial_residual() {
             HIP_CHECK(hipEventRecord(pair[0], s->compute));
             spmv_done = pair[1];
         }
-        first_used = slab_first_spmv(s, sweeps_backward(0), spmv_done);
+        first_used = slab_first_spmv(s, sweeps_backward(0), spmv_done, first != FirstForm::Stored);
         reduce_spmv_partials(s, first_used, &s->d_s->rr_new, nullptr, nullptr, 0, mailbox, s->partials_first);
     } else if (s->fuse_init_residual) {
         // row-lds slabs: r0 = b - A x0, p0 = r0 and the r0.r0 partials come out of the SpMV launch itself (A x0 is
@@ -503,7 +513,8 @@ void SolveRun::stage_spmv() {
     // from the previous one on its way; `enqueued` is the number of the iteration that direction belongs to, as the kernels count
     const auto spmv = [&](hipEvent_t spmv_done) {
         if (L.fused_direction && enqueued > 0) return slab_direction_spmv(s, direction_from, s->p, enqueued, spmv_done, L.ap_recomputed);
-        return slab_spmv(s, true, halo_in_flight, skip, nullptr, spmv_done);
+        // (iteration 0 under first_recomputed: the block kernel leaves A p0 to the r update too)
+        return slab_spmv(s, true, halo_in_flight, skip, nullptr, spmv_done, nullptr, false, enqueued == 0 && first != FirstForm::Stored);
     };
     if (b_is_p0 && enqueued == 0) {
         // initial_residual enqueued this iteration's launch and the reduction of its partials (with the event pair where this is a
@@ -549,7 +560,11 @@ void SolveRun::stage_update_r() {
               // r0_in_ring: r0 lies in ring slot 0 alone (p0 = r0, stored once): the update of iteration 0 reads it there
               // (b_is_p0: r0 is b itself)
               // ap_recomputed: the fused launch of iterations >= 1 left A p' unstored on its fast blocks; s->p is the p' it wrote
+              // first_recomputed: iteration 0's launch left A p0 unstored as well; r0 is b, or slot 0, or -- stored twice -- already in r
               if (L.ap_recomputed && enqueued > 0) slab_update_r_recompute(s, s->p, !backward), ++s->last_recompute_launches;
+              else if (enqueued == 0 && first == FirstForm::FromB) slab_update_r_recompute(s, s->b, !backward, /*r_is_p=*/true);
+              else if (enqueued == 0 && first == FirstForm::FromSlot0) slab_update_r_recompute(s, s->ring[0], !backward, /*r_is_p=*/true);
+              else if (enqueued == 0 && first == FirstForm::InPlace) slab_update_r_recompute(s, s->p, !backward);
               else if (L.r0_in_ring && enqueued == 0) launch_cg_update_r_from(nl, s->d_s, s->Ap, b_is_p0 ? s->b : s->ring[0], s->r, s->partials_blas, s->compute, !backward);
               else launch_cg_update_r(nl, s->d_s, s->Ap, s->r, s->partials_blas, s->compute, !backward);
           });

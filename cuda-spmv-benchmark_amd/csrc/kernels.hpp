@@ -36,8 +36,9 @@ struct Tunables {
     int rowlds_group = 0;         // SPMV_AMD_ROWLDS_GROUP: consecutive row-lds tiles per XCD; 0 = derived from the grid (xcd_run_group())
     // SPMV_AMD_ROWLDS_BLOCK_ROWS: grid rows per wave of a solver slab's in-loop SpMV (block tiles): 0 (the one-row kernel), 4 or 8.
     // 20 000^2 on MI355X, one process, alternated: 1.636 ms / 1.064 / 1.086 (profiles/r13_block_rows_ab.txt). With the direction
-    // update inside the SpMV (DirectionSpmv) 8 makes that launch 2 % shorter and the whole solve no faster: 4 stays
-    // (profiles/r15_fused_direction_ab.txt, section 5).
+    // update inside the SpMV (DirectionSpmv) 8 makes that launch 2 % shorter, and with A p' recomputed by the r update a whole solve
+    // 0.5 ms shorter (profiles/r23_ap_recompute_ab.txt, r24_first_recompute_ab.txt): a solver slab on which that loop can run takes 8
+    // where the variable is unset (slab_decisions.hpp, default_block_rows); operators and every other slab keep 4.
     int rowlds_block_rows = 4;
     // SPMV_AMD_STENCIL7_ROWLDS_MIN_GRID: smallest n of an n^3 grid that takes stencil7/row-lds automatically. Measured on MI355X
     // (profiles/r18_stencil7_bench.txt), row-lds / row-direct medians: 64^3 7.9 / 9.9 us, 96^3 20.3 / 24.0, 128^3 38.4 / 40.9,
@@ -160,9 +161,11 @@ void launch_verify_sym_planes(const SlabCsr& m, const SymPlanes& planes, int* d_
 // x_zero (with `init`, row-lds plans, slabs without halo rows): the caller knows that x holds +0.0 in every element. The launch then
 // requests no x value on grid rows 1 .. n-2 -- the five operands are 0.0 in registers and the same chains run on them, so signed
 // zeros and the NaN of an infinite coefficient come out as they did -- and reads x only on the grid's first and last grid row.
+// ap_not_stored (block-tile launches only; anything else is an error): y is left alone on the fast blocks, the partials are written
+// as ever -- launch_cg_update_r_recompute follows (LoopShape::first_recomputed).
 int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& plan, const double* x, double* y, double alpha,
                          double* d_dot_partials, const int* d_skip_flag, bool reverse, hipStream_t stream,
-                         const ResidualOut* init = nullptr, const SymPlanes* planes = nullptr, bool x_zero = false);
+                         const ResidualOut* init = nullptr, const SymPlanes* planes = nullptr, bool x_zero = false, bool ap_not_stored = false);
 // The CG direction update inside the in-loop block SpMV (stencil5_direction_block_kernel; slabs without neighbours whose plan has
 // a block map): p_out = direction(r, s->beta, p_in), y = alpha A p_out and the p_out . (A p_out) partials of the plan's slots, in one
 // launch over the block tiles plus one over `slow_list` -- the indices of the range's block tiles whose map byte is 0 (device
@@ -186,15 +189,18 @@ int launch_stencil5_direction_spmv(const SlabCsr& m, const Stencil5Plan& plan, c
 // a launch_stencil5_direction_spmv with ap_not_stored: A p_new is recomputed from p_new on the skewed block tiles of
 // skew_geometry.hpp where the element's row block is fast (row_fast: one byte per row block of the plan's block map, 1 = every
 // block tile fast, 0 = none; slab::skew_eligible) and read from Ap elsewhere. The whole-slab plan of a slab without halo rows.
+// r_is_p (iteration 0, where r0 and p0 are one vector: b, or ring slot 0): the out-of-place instance, r = p_new - alpha A p_new with
+// launch_cg_update_r_from's bits; r is only written, p_new only read.
 int launch_cg_update_r_recompute(const SlabCsr& m, const Stencil5Plan& plan, const CgScalars* s, const double* p_new, const double* Ap, double* r,
-                                 double* partials, const unsigned char* row_fast, bool reverse, hipStream_t stream, const SymPlanes& planes);
+                                 double* partials, const unsigned char* row_fast, bool reverse, hipStream_t stream, const SymPlanes& planes,
+                                 bool r_is_p = false);
 // Iteration 0's SpMV of a solve that starts from x0 = 0 on a matrix whose rows sum to +0.0 over zero operands (slab_decisions.hpp,
 // LoopShape::b_is_p0; stencil5_first_block_kernel): the in-loop block launch on x = b -- y = alpha A b and the b . (A b) partials,
 // as launch_stencil5_spmv writes them -- that also leaves the b . b partials in `self_partials`, same slots, each summed as the
 // launch of the initial residual sums r0 . r0 (r0 is b bit for bit there). Slabs without halo rows whose plan has a block map.
-// Returns the partial slots written to each array (the plan's).
+// Returns the partial slots written to each array (the plan's). ap_not_stored: as in launch_stencil5_spmv.
 int launch_stencil5_first_spmv(const SlabCsr& m, const Stencil5Plan& plan, const double* b, double* y, double alpha, double* d_dot_partials,
-                               double* self_partials, bool reverse, hipStream_t stream, const SymPlanes& planes);
+                               double* self_partials, bool reverse, hipStream_t stream, const SymPlanes& planes, bool ap_not_stored = false);
 // Sets *d_bad (int, zeroed by the caller) if any local row's stored coefficients fail slab_decisions.hpp's sums_to_plus_zero.
 void launch_rows_plus_zero(const SlabCsr& m, int* d_bad, hipStream_t stream);
 // The fused Chebyshev step over a row-lds plan (ChebStep): z is read as the SpMV's x, A z is not written. Returns the partial slots

@@ -89,6 +89,15 @@ inline Partition partition_check(bool exchanges_halos, int grid, int n_local) {
 }
 
 inline bool late_bulk_default(size_t n_local) { return n_local >= 100000000; }
+// Grid rows per block tile of a slab's in-loop SpMV (Tunables::rowlds_block_rows) where nobody asked (asked < 0; SPMV_AMD_ROWLDS_BLOCK_ROWS
+// of 0, 4 or 8 is taken as it is, any other value counts as not asked): 8 where the loop can take the direction update inside the block SpMV -- a slab
+// without neighbours that owns its matrix, with a direction ring, fused_direction not switched off -- which ran ahead of 4 every time
+// both were measured there; 4 for every other slab: the plain block kernel measured faster with 4, and nothing between
+// devices has been measured with 8.
+inline int default_block_rows(int asked, bool exchanges_halos, bool owns_matrix, int ring_slots, int fused_direction) {
+    if (asked == 0 || asked == 4 || asked == 8) return asked;
+    return !exchanges_halos && owns_matrix && ring_slots > 1 && fused_direction != 0 ? 8 : 4;
+}
 // the coefficient placement trial: slabs of >= 16 Mi rows, where the device offers more than one candidate region
 inline bool wants_coefficient_placement(size_t n_local, int candidates) { return n_local >= ((size_t)16 << 20) && candidates > 1; }
 // In-kernel / side-stream waits for the other stream's flags give up well inside the host's watchdog (limit 0 = none set).
@@ -147,6 +156,7 @@ struct ShapeInputs {
     // whole-slab launch's block map is all-fast or all-slow (skew_eligible, established with the block maps)
     int ap_recompute;
     bool skew_eligible;
+    int first_recompute;  // the option (0 off, 1 where ap_recomputed holds): iteration 0 in the same store-less form
 };
 
 struct LoopShape {
@@ -168,6 +178,10 @@ struct LoopShape {
     // recomputes it from p' on skewed block tiles (skew_geometry.hpp; cg_update_r_recompute_kernel): 16 B/row less per iteration.
     // Iteration 0 and every slab that is not eligible keep the stored A p and cg_update_r_kernel.
     bool ap_recomputed = false;
+    // On top of ap_recomputed, in iteration 0: the SpMV of that iteration (the first launch on b, or the block kernel on p0) does not
+    // store A p0 on its fast blocks either, and the r update recomputes it from the ONE vector that is both r0 and p0 there
+    // (first_form below says which): 14 B/row less, once per solve.
+    bool first_recomputed = false;
     // The two ends of a solve on a slab without neighbours that owns its matrix and takes the initial residual from the first
     // SpMV's launch. zero_start: x0 holds the library's own zeros, and that launch requests no x value on interior grid rows.
     // r0_in_ring (any x0): the launch stores r0 once, as p0 into ring slot 0, and the r update of iteration 0 reads it there.
@@ -202,6 +216,7 @@ inline LoopShape loop_shape(const ShapeInputs& in) {
     L.fused_direction = in.fused_direction != 0 && !L.multi && in.owns_matrix && L.slots > 1 && !L.detail &&
                         direction_spmv_available(in, /*cap=*/in.fused_direction != 2);
     L.ap_recomputed = L.fused_direction && in.ap_recompute != 0 && in.skew_eligible;
+    L.first_recomputed = L.ap_recomputed && in.first_recompute != 0;
     L.late = in.late_bulk && !L.detail && L.slots > 1 && !L.fused_direction;
     // (ring mode only, like fused_direction: the in-place form keeps every launch it had)
     const bool own_ends = !L.multi && in.owns_matrix && L.slots > 1 && in.fuse_init_residual;
@@ -220,6 +235,18 @@ inline LoopShape loop_shape(const ShapeInputs& in) {
     if (L.pipeline) L.head_rows = head_rows, L.tail_start = tail_start;
     L.bulk_lo = L.pipeline ? head_rows : 0, L.bulk_hi = L.pipeline ? tail_start : nl;
     return L;
+}
+
+// Iteration 0 of a solve of `max_iters` iterations under LoopShape::first_recomputed: where r0 lies decides the r update's instance.
+// Stored: A p0 is stored and read back, the launches of before (first_recomputed off; a solve of no iterations launches none of this
+// and keeps the launch that only sums r0.r0). FromB: b is r0 and p0 (b_is_p0), the first launch on b stores nothing on its fast
+// blocks and the out-of-place instance reads b. FromSlot0: r0 lies in ring slot 0 alone (r0_in_ring), the block kernel stores nothing
+// there and the out-of-place instance reads the slot. InPlace: r0 lies in r AND in slot 0 (stored twice), the in-loop instance on
+// (r, p = slot 0) does it.
+enum class FirstForm { Stored, FromB, FromSlot0, InPlace };
+inline FirstForm first_form(const LoopShape& L, int max_iters) {
+    if (!L.first_recomputed || max_iters <= 0) return FirstForm::Stored;
+    return L.b_is_p0 ? FirstForm::FromB : L.r0_in_ring ? FirstForm::FromSlot0 : FirstForm::InPlace;
 }
 
 // what a flush of x starts from in the solve's first window: nothing (0.0 in registers) where x0 holds the library's own zeros

@@ -491,8 +491,10 @@ __device__ __forceinline__ bool rowlds_block_slow_rows(const SlabCsr& m, const d
 // tile, W / E from an LDS copy of each row. 0 = the block calls rowlds_tile once per grid row it holds, with that row's own class.
 // Either way one partial of x . (A x) per 128 x 1 tile in the one-row kernel's slot, (li - gi_lo) * col_tiles + col_tile: the
 // reduction's shape and every bit of the sum stay what they were.
+// kStoreAp = false (LoopShape::first_recomputed, iteration 0 on a caller's x0): the fast path does not store A p0 -- the r update
+// behind it recomputes it (cg_update_r_recompute_kernel) -- and is the same code otherwise; the other path stores as ever.
 // ---------------------------------------------------------------------------------
-template <int kRows>
+template <int kRows, bool kStoreAp = true>
 __global__ __launch_bounds__(64) void stencil5_rowlds_block_kernel(
     SlabCsr m, const double* __restrict__ x, double* __restrict__ y, double alpha, int gi_lo, int gi_hi, int gfirst, int col_tiles,
     int total_blocks, int run, int reverse, double* __restrict__ dot_partials, const int* __restrict__ skip_flag,
@@ -556,7 +558,7 @@ __global__ __launch_bounds__(64) void stencil5_rowlds_block_kernel(
                     const double xc = xv[r + 1][h], xn = xv[r][h], xs = xv[r + 2][h];
                     const double sum = stencil5_row(j, n, sp.w, xw[h], sp.c, xc, sp.e, xe[h], sp.n, xn, sp.s5, xs);
                     dot = fma(xc, sum, dot);
-                    __builtin_nontemporal_store(alpha * sum, y + ((long long)li * n + j));
+                    if constexpr (kStoreAp) __builtin_nontemporal_store(alpha * sum, y + ((long long)li * n + j));
                 }
             }
             dot = wave_sum(dot);
@@ -704,6 +706,10 @@ __global__ __launch_bounds__(64) void stencil5_block_list_kernel(SlabCsr m, cons
 // was 1.0 * sum. Every other wave goes chunk by chunk and element by element (ap_at): a slow row block's A p' is read from Ap, where
 // stencil5_block_list_kernel stored it; a chunk that straddles two grid rows decides per element. Same tile -> XCD relabelling as
 // the fused launch, so that the seam rows are found in the L2 that read them. A launch past convergence only reads.
+// kFrom = true (LoopShape::first_recomputed, iteration 0): the out-of-place instance for r0 == p0 -- `p` is the one vector that is both
+// (b, or ring slot 0), `rvec` is only written: r = p0 - alpha A p0. The centre pair serves as r0 too, so r0 is not loaded a second
+// time; the chain and the fma are cg_update_r_from_kernel's on (the A p0 the first launch would have stored as 1.0 * sum, p0), as
+// are the odd last element and the early return. p0 has no rows outside [0, rows): `whole` keeps the -n / +n loads inside.
 // ---------------------------------------------------------------------------------
 // A p' at element i: read where its row block is slow, recomputed where it is fast (operands outside the grid are 0.0, and
 // stencil5_row ignores W in column 0 and E in column n - 1, as in the fused launch)
@@ -724,7 +730,7 @@ __device__ __forceinline__ d2 load_pair(const double* __restrict__ at, bool alig
     return v;
 }
 
-template <int kRows>
+template <int kRows, bool kFrom = false>
 __global__ __launch_bounds__(64) void cg_update_r_recompute_kernel(size_t elements, int n, int rows, const CgScalars* __restrict__ s,
                                                                    const double* __restrict__ p, const double* __restrict__ Ap,
                                                                    double* __restrict__ rvec, double* __restrict__ partials, int col_tiles,
@@ -753,8 +759,9 @@ __global__ __launch_bounds__(64) void cg_update_r_recompute_kernel(size_t elemen
         for (int k = 0; k < kRows; ++k) {
             const size_t pair = (size_t)c[k].chunk * 64 + lane;
             const double* __restrict__ at = p + 2 * pair;
-            rv[k] = load_once(rvec, pair);
+            if constexpr (!kFrom) rv[k] = load_once(rvec, pair);
             pc[k] = *reinterpret_cast<const d2*>(at);  // plain: the rows below and above re-use these lines
+            if constexpr (kFrom) rv[k] = pc[k];         // r0 is p0: the centre pair serves as both
             pn[k] = load_pair(at - n, aligned);
             ps[k] = load_pair(at + n, aligned);
         }
@@ -796,7 +803,9 @@ __global__ __launch_bounds__(64) void cg_update_r_recompute_kernel(size_t elemen
         double acc = 0.0;
         if (pair < pairs) {
             const long long i = 2 * (long long)pair;
-            d2 v = load_once(rvec, pair);
+            d2 v;
+            if constexpr (kFrom) v = *reinterpret_cast<const d2*>(p + i);
+            else v = load_once(rvec, pair);
             v.x = fma(-alpha, ap_at(i, n, rows, kRows, p, Ap, row_fast, sp), v.x);
             v.y = fma(-alpha, ap_at(i + 1, n, rows, kRows, p, Ap, row_fast, sp), v.y);
             store_once(rvec, pair, v);
@@ -804,7 +813,7 @@ __global__ __launch_bounds__(64) void cg_update_r_recompute_kernel(size_t elemen
             acc = fma(v.y, v.y, acc);
         }
         if ((elements & 1) && ck.chunk == 0 && lane == 0) {  // the odd last element, where cg_update_r_kernel adds it
-            const double rl = fma(-alpha, ap_at((long long)elements - 1, n, rows, kRows, p, Ap, row_fast, sp), rvec[elements - 1]);
+            const double rl = fma(-alpha, ap_at((long long)elements - 1, n, rows, kRows, p, Ap, row_fast, sp), (kFrom ? p : rvec)[elements - 1]);
             rvec[elements - 1] = rl;
             acc = fma(rl, rl, acc);
         }
@@ -819,7 +828,8 @@ __global__ __launch_bounds__(64) void cg_update_r_recompute_kernel(size_t elemen
 // 128 x 1 tile in the same slot of `self_partials`, in the form rowlds_tile's kMode 2 sums r0 . r0: fma(v, v, acc) for the lane's
 // column `lane`, then `lane + 64`, then wave_sum. With r0 = b bit for bit both sums keep every bit that the launch of the initial
 // residual followed by the block kernel gives; the values are in registers here anyway. A kernel of its own, first in its solve
-// (no skip flag): the in-loop instances keep their code.
+// (no skip flag): the in-loop instances keep their code. kStoreAp = false (LoopShape::first_recomputed): as in the block kernel,
+// the fast path leaves y alone and writes only the two partials; rowlds_first_slow_rows stores A b on its rows as ever.
 // ---------------------------------------------------------------------------------
 // rowlds_block_slow_rows with the row's own partial of x . x beside it: the lane's two values are read again (the lines the row
 // has just pulled in) rather than handed out of rowlds_tile, which stays as it is.
@@ -856,7 +866,7 @@ __device__ __forceinline__ void rowlds_first_slow_rows(const SlabCsr& m, const d
     }
 }
 
-template <int kRows>
+template <int kRows, bool kStoreAp = true>
 __global__ __launch_bounds__(64) void stencil5_first_block_kernel(
     SlabCsr m, const double* __restrict__ x, double* __restrict__ y, double alpha, int gi_lo, int gi_hi, int gfirst, int col_tiles,
     int total_blocks, int run, int reverse, double* __restrict__ dot_partials, double* __restrict__ self_partials,
@@ -917,7 +927,7 @@ __global__ __launch_bounds__(64) void stencil5_first_block_kernel(
                     const double sum = stencil5_row(j, n, sp.w, xw[h], sp.c, xc, sp.e, xe[h], sp.n, xn, sp.s5, xs);
                     dot = fma(xc, sum, dot);
                     self = fma(xc, xc, self);
-                    __builtin_nontemporal_store(alpha * sum, y + ((long long)li * n + j));
+                    if constexpr (kStoreAp) __builtin_nontemporal_store(alpha * sum, y + ((long long)li * n + j));
                 }
             }
             dot = wave_sum(dot);
@@ -1641,15 +1651,17 @@ void launch_rowlds(const SlabCsr& m, const Stencil5Plan& p, const double* x, dou
 
 // the block kernel over the plan's block tiles (the in-loop SpMV of a solver slab; launch_stencil5_spmv decides)
 void launch_rowlds_block(const SlabCsr& m, const Stencil5Plan& p, const double* x, double* y, double alpha, double* d_dot_partials,
-                         const int* d_skip_flag, bool reverse, hipStream_t stream, const SymPlanes& sp) {
+                         const int* d_skip_flag, bool reverse, hipStream_t stream, const SymPlanes& sp, bool ap_not_stored) {
     const int blocks = rowlds_block_tiles(p);
     const dim3 grid((unsigned)xcd_padded_grid(blocks, p.xcd_run));
     const int gfirst = m.row_offset / m.grid_size;
-#define SPMV_AMD_LAUNCH_ROWLDS_BLOCK(ROWS)                                                                                      \
-    hipLaunchKernelGGL((stencil5_rowlds_block_kernel<ROWS>), grid, dim3(64), 0, stream, m, x, y, alpha, p.gi_lo, p.gi_hi, gfirst, \
+#define SPMV_AMD_LAUNCH_ROWLDS_BLOCK(ROWS, STORE)                                                                                      \
+    hipLaunchKernelGGL((stencil5_rowlds_block_kernel<ROWS, STORE>), grid, dim3(64), 0, stream, m, x, y, alpha, p.gi_lo, p.gi_hi, gfirst, \
                        p.row_blocks, blocks, p.xcd_run, reverse ? 1 : 0, d_dot_partials, d_skip_flag, p.block_map, sp)
-    if (p.block_rows == 4) SPMV_AMD_LAUNCH_ROWLDS_BLOCK(4);
-    else SPMV_AMD_LAUNCH_ROWLDS_BLOCK(8);
+    if (p.block_rows == 4 && !ap_not_stored) SPMV_AMD_LAUNCH_ROWLDS_BLOCK(4, true);
+    else if (p.block_rows == 4) SPMV_AMD_LAUNCH_ROWLDS_BLOCK(4, false);
+    else if (!ap_not_stored) SPMV_AMD_LAUNCH_ROWLDS_BLOCK(8, true);
+    else SPMV_AMD_LAUNCH_ROWLDS_BLOCK(8, false);
 #undef SPMV_AMD_LAUNCH_ROWLDS_BLOCK
 }
 }  // namespace
@@ -1668,17 +1680,22 @@ void launch_block_map(const unsigned char* cls, const Stencil5Plan& p, unsigned 
 
 int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& p, const double* x, double* y, double alpha,
                          double* d_dot_partials, const int* d_skip_flag, bool reverse, hipStream_t stream,
-                         const ResidualOut* init, const SymPlanes* planes, bool x_zero) {
+                         const ResidualOut* init, const SymPlanes* planes, bool x_zero, bool ap_not_stored) {
     if (p.last_row <= p.first_row) return 0;
     if (init != nullptr && (p.variant != Stencil5Variant::RowLds || d_dot_partials == nullptr)) {
         fprintf(stderr, "[spmv] the fused initial residual exists for the row-lds kernel only\n");
         exit(EXIT_FAILURE);
     }
     const bool dot = d_dot_partials != nullptr;
-    if (p.variant == Stencil5Variant::RowLds && p.block_rows > 0 && p.block_map != nullptr && dot && init == nullptr && planes != nullptr &&
-        planes->ce != nullptr && planes->cls != nullptr) {
+    const bool block_tiles = p.variant == Stencil5Variant::RowLds && p.block_rows > 0 && p.block_map != nullptr && dot && init == nullptr &&
+                             planes != nullptr && planes->ce != nullptr && planes->cls != nullptr;
+    if (ap_not_stored && !block_tiles) {
+        fprintf(stderr, "[spmv] only the block kernel can leave A x unstored\n");
+        exit(EXIT_FAILURE);
+    }
+    if (block_tiles) {
         // the in-loop SpMV of a slab with a class map: block tiles (the same rows, the same partial slots)
-        launch_rowlds_block(m, p, x, y, alpha, d_dot_partials, d_skip_flag, reverse, stream, *planes);
+        launch_rowlds_block(m, p, x, y, alpha, d_dot_partials, d_skip_flag, reverse, stream, *planes, ap_not_stored);
     } else if (p.variant == Stencil5Variant::RowLds) {
         launch_rowlds(m, p, x, y, alpha, p.gi_lo, 1, p.partials, d_dot_partials, d_skip_flag, reverse, stream, init, planes, nullptr, x_zero);
     } else if (p.variant == Stencil5Variant::RowDirect) {
@@ -1732,7 +1749,7 @@ int launch_stencil5_direction_spmv(const SlabCsr& m, const Stencil5Plan& p, cons
 }
 
 int launch_cg_update_r_recompute(const SlabCsr& m, const Stencil5Plan& p, const CgScalars* s, const double* p_new, const double* Ap, double* r,
-                                 double* partials, const unsigned char* row_fast, bool reverse, hipStream_t stream, const SymPlanes& sp) {
+                                 double* partials, const unsigned char* row_fast, bool reverse, hipStream_t stream, const SymPlanes& sp, bool r_is_p) {
     const int blocks = rowlds_block_tiles(p);
     if (blocks <= 0 || row_fast == nullptr || partials == nullptr || p.first_row != 0 || p.last_row != m.n_local || m.halo_before != 0 ||
         m.halo_after != 0) {
@@ -1741,17 +1758,19 @@ int launch_cg_update_r_recompute(const SlabCsr& m, const Stencil5Plan& p, const 
     }
     const dim3 grid((unsigned)xcd_padded_grid(blocks, p.xcd_run));
     const int n = m.grid_size;
-#define SPMV_AMD_LAUNCH_R_RECOMPUTE(ROWS)                                                                                              \
-    hipLaunchKernelGGL((cg_update_r_recompute_kernel<ROWS>), grid, dim3(64), 0, stream, (size_t)m.n_local, n, m.n_local / n, s, p_new, Ap, r, \
+#define SPMV_AMD_LAUNCH_R_RECOMPUTE(ROWS, FROM)                                                                                              \
+    hipLaunchKernelGGL((cg_update_r_recompute_kernel<ROWS, FROM>), grid, dim3(64), 0, stream, (size_t)m.n_local, n, m.n_local / n, s, p_new, Ap, r, \
                        partials, p.row_blocks, blocks, p.xcd_run, reverse ? 1 : 0, row_fast, sp)
-    if (p.block_rows == 4) SPMV_AMD_LAUNCH_R_RECOMPUTE(4);
-    else SPMV_AMD_LAUNCH_R_RECOMPUTE(8);
+    if (p.block_rows == 4 && !r_is_p) SPMV_AMD_LAUNCH_R_RECOMPUTE(4, false);
+    else if (p.block_rows == 4) SPMV_AMD_LAUNCH_R_RECOMPUTE(4, true);
+    else if (!r_is_p) SPMV_AMD_LAUNCH_R_RECOMPUTE(8, false);
+    else SPMV_AMD_LAUNCH_R_RECOMPUTE(8, true);
 #undef SPMV_AMD_LAUNCH_R_RECOMPUTE
     return (int)slab::chunk_count((size_t)m.n_local);
 }
 
 int launch_stencil5_first_spmv(const SlabCsr& m, const Stencil5Plan& p, const double* b, double* y, double alpha, double* d_dot_partials,
-                               double* self_partials, bool reverse, hipStream_t stream, const SymPlanes& sp) {
+                               double* self_partials, bool reverse, hipStream_t stream, const SymPlanes& sp, bool ap_not_stored) {
     const int blocks = rowlds_block_tiles(p);
     if (blocks <= 0 || p.block_map == nullptr || d_dot_partials == nullptr || self_partials == nullptr || sp.cls == nullptr || m.halo_before != 0 ||
         m.halo_after != 0) {
@@ -1760,11 +1779,13 @@ int launch_stencil5_first_spmv(const SlabCsr& m, const Stencil5Plan& p, const do
     }
     const dim3 grid((unsigned)xcd_padded_grid(blocks, p.xcd_run));
     const int gfirst = m.row_offset / m.grid_size;
-#define SPMV_AMD_LAUNCH_FIRST_BLOCK(ROWS)                                                                                       \
-    hipLaunchKernelGGL((stencil5_first_block_kernel<ROWS>), grid, dim3(64), 0, stream, m, b, y, alpha, p.gi_lo, p.gi_hi, gfirst, \
+#define SPMV_AMD_LAUNCH_FIRST_BLOCK(ROWS, STORE)                                                                                       \
+    hipLaunchKernelGGL((stencil5_first_block_kernel<ROWS, STORE>), grid, dim3(64), 0, stream, m, b, y, alpha, p.gi_lo, p.gi_hi, gfirst, \
                        p.row_blocks, blocks, p.xcd_run, reverse ? 1 : 0, d_dot_partials, self_partials, p.block_map, sp)
-    if (p.block_rows == 4) SPMV_AMD_LAUNCH_FIRST_BLOCK(4);
-    else SPMV_AMD_LAUNCH_FIRST_BLOCK(8);
+    if (p.block_rows == 4 && !ap_not_stored) SPMV_AMD_LAUNCH_FIRST_BLOCK(4, true);
+    else if (p.block_rows == 4) SPMV_AMD_LAUNCH_FIRST_BLOCK(4, false);
+    else if (!ap_not_stored) SPMV_AMD_LAUNCH_FIRST_BLOCK(8, true);
+    else SPMV_AMD_LAUNCH_FIRST_BLOCK(8, false);
 #undef SPMV_AMD_LAUNCH_FIRST_BLOCK
     return p.partials;
 }

@@ -504,7 +504,9 @@ int spmv_amd_cg_slab_solve(SpmvAmdCgSlab* s, const CGConfigMultiGPU* config,
  * row-by-row blocks are at most 1/16 of its blocks, SPMV_AMD_FUSED_DIRECTION not 0: the direction update p' = r + beta p of
  * iteration k is evaluated inside the SpMV launch of iteration k + 1; a solve with detailed timers keeps the two launches; where
  * every row of block tiles of that launch is evaluated either all by the fast path or all row by row, and SPMV_AMD_AP_RECOMPUTE is
- * not 0, that launch does not store A p' on the fast blocks and the r update recomputes it from p', same bits); "pipeline (verified against the plain
+ * not 0, that launch does not store A p' on the fast blocks and the r update recomputes it from p', same bits -- and, unless
+ * SPMV_AMD_FIRST_RECOMPUTE is 0, iteration 0 does the same with A p0, recomputed from b or from the stored r0; such a slab's block tiles
+ * hold 8 grid rows unless SPMV_AMD_ROWLDS_BLOCK_ROWS says 0, 4 or 8, every other slab's hold 4); "pipeline (verified against the plain
  * order at creation)"; "plain: SPMV_AMD_NO_OVERLAP=1"; "plain: the in-place form (ring 1) or a slab too thin to split"; "plain: the
  * pipeline's residual history differed from the plain order's in the creation check". The creation check: the first slab created on a communicator that exchanges halos solves four iterations
  * in each shape (default b = 1, x0 = 0); the shapes are bit-identical by construction, so a difference on any rank -- lost or stale

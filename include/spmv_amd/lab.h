@@ -51,8 +51,12 @@ SpmvAmdCgSlab* spmv_amd_cg_slab_create_stencil5_as(int n, int as_rank, int as_wo
  * iterations >= 1 of the fused direction loop the fused launch does not store A p' on its fast blocks and the r update recomputes
  * it from p' on skewed block tiles, where every row block of the whole-slab block map is all-fast or all-slow;
  * spmv_amd_cg_slab_ap_form says which ran; results are bit-identical) and "direction_store" 0/1 (a field of the LAB build only: 0 =
- * spmv_amd_cg_slab_direction_spmv runs the fused launch in the form that does not store A p'). Returns 0, or -1 for an unknown
- * name or value. */
+ * spmv_amd_cg_slab_direction_spmv runs the fused launch in the form that does not store A p'), "first_recompute" 0/1 (the product's
+ * SPMV_AMD_FIRST_RECOMPUTE: 1 = where "ap_recompute" applies, iteration 0 takes the same form -- its SpMV does not store A p0 on the
+ * fast blocks and its r update recomputes it from the one vector that is both r0 and p0; spmv_amd_cg_slab_first_recompute_form says
+ * which ran; results are bit-identical) and "first_store" 0/1 (a field of the LAB build only: 0 = spmv_amd_cg_slab_first_stage, and
+ * spmv_amd_cg_slab_spmv in its in-loop form, run the launch that does not store A x on the fast blocks; y is NaN there). Returns 0,
+ * or -1 for an unknown name or value. */
 int spmv_amd_cg_slab_set_option(SpmvAmdCgSlab* s, const char* name, long long value);
 
 /* The tile class map of a slab in the symmetric form as creation wrote it (spmv_amd_cg_slab_uniform_tiles): one byte per row-lds
@@ -96,6 +100,19 @@ int spmv_amd_cg_slab_update_r_stage(SpmvAmdCgSlab* s, int recompute, int reverse
  * of the whole-slab block map is all-fast or all-slow. *launches (may be NULL) = the recomputing launches the last solve enqueued.
  * s == NULL: the workspace slab of cg_solve_device, which borrows the caller's operator (-1: there is none). */
 int spmv_amd_cg_slab_ap_form(const SpmvAmdCgSlab* s, int* launches);
+
+/* Iteration 0's r update alone, once, where r0 and p0 are the one vector src (host, n_local doubles; b or ring slot 0 in a solve):
+ * recompute = 0, cg_update_r_from_kernel on (Ap, src); recompute != 0, the out-of-place launch that recomputes A src on the fast row
+ * blocks and reads Ap on the slow ones only. reverse, converged, r_out, partials and the return value as in
+ * spmv_amd_cg_slab_update_r_stage; r_out is NaN where the launch did not write. src_back (may be NULL, n_local doubles): src as it
+ * lies on the device behind the launch. */
+int spmv_amd_cg_slab_update_r_from_stage(SpmvAmdCgSlab* s, int recompute, int reverse, const double* src, const double* Ap, double rr_old,
+                                         double pAp, int converged, double* r_out, double* src_back, double* partials, int cap);
+/* Iteration 0's form that a solve of at least one iteration would take now: 0 = A p0 stored and read back; else left unstored on the
+ * fast blocks and recomputed by the r update, 1 = from b (b serves as p0), 2 = from ring slot 0 (r0 stored once), 3 = in place on
+ * (r, ring slot 0). *last (may be NULL) = what the last solve took (0 for a solve of no iterations). Counted apart from
+ * spmv_amd_cg_slab_ap_form's launches, which are those of iterations >= 1. */
+int spmv_amd_cg_slab_first_recompute_form(const SpmvAmdCgSlab* s, int* last);
 
 /* The initial stage of a solve alone, once, on the slab's stored b and x0: the first SpMV's launch (r0 = b - A x0, p0 = r0, one
  * partial of r0.r0 per 128 x 1 tile) and the reduction of the partials, in the form a solve would take now. Returns the form: bit 0 =
