@@ -106,6 +106,21 @@ class CgMultiStageArgs(C.Structure):
                 ("hist", C.c_void_p), ("hist_cap", C.c_int), ("xcd_run", C.c_int)]
 
 
+class PcgMultiColumn(C.Structure):
+    """SpmvAmdPcgMultiColumn (include/spmv_amd/lab.h): the per-column state of a batched preconditioned solve."""
+    _fields_ = [("rz", C.c_double), ("pAp", C.c_double), ("alpha", C.c_double), ("beta", C.c_double), ("b_norm", C.c_double),
+                ("residual", C.c_double), ("active", C.c_int), ("done", C.c_int), ("iterations", C.c_int), ("converged", C.c_int),
+                ("breakdown", C.c_int), ("skip_update", C.c_int), ("pad", C.c_int * 2)]
+
+
+class PcgMultiStageArgs(C.Structure):
+    """SpmvAmdPcgMultiStageArgs (include/spmv_amd/lab.h): device pointers and sizes of one spmv_amd_pcg_multi_stage call."""
+    _fields_ = [("n", C.c_size_t), ("X", C.c_void_p), ("R", C.c_void_p), ("P", C.c_void_p), ("AP", C.c_void_p), ("D", C.c_void_p),
+                ("Z", C.c_void_p), ("dinv", C.c_void_p), ("cols", C.c_void_p), ("partials", C.c_void_p), ("count", C.c_longlong),
+                ("which", C.c_int), ("tol", C.c_double), ("hist", C.c_void_p), ("hist_cap", C.c_int), ("c0", C.c_double), ("g", C.c_double),
+                ("h", C.c_double), ("last", C.c_int)]
+
+
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
 GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int))
@@ -140,12 +155,14 @@ DECLARED_SYMBOLS = [
     "spmv_amd_precond_create_chebyshev", "spmv_amd_precond_chebyshev_info", "spmv_amd_precond_apply_device",
     "spmv_amd_precond_create_multigrid", "spmv_amd_precond_multigrid_info",
     "spmv_amd_precond_create_multigrid3d", "spmv_amd_precond_multigrid_dimension",
+    "spmv_amd_pcg_solve_device_multi", "spmv_amd_pcg_last_history_multi", "spmv_amd_pcg_multi_workspace_bytes",
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
 LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_cg_slab_block_map", "spmv_amd_cg_slab_slow_blocks",
                     "spmv_amd_cg_slab_direction_spmv", "spmv_amd_cg_slab_spmv_dot", "spmv_amd_cg_slab_initial_stage", "spmv_amd_cg_slab_first_stage", "spmv_amd_cg_slab_stored_b", "spmv_amd_cg_slab_update_r_stage", "spmv_amd_cg_slab_ap_form", "spmv_amd_cg_slab_update_r_from_stage", "spmv_amd_cg_slab_first_recompute_form", "spmv_amd_pcg_stage",
                     "spmv_amd_pcg_last_step_launches", "spmv_amd_cg_multi_stage",
-                    "spmv_amd_pcg_last_multigrid_cycles", "spmv_amd_precond_multigrid_level_csr", "spmv_amd_mg_stage"]
+                    "spmv_amd_pcg_last_multigrid_cycles", "spmv_amd_precond_multigrid_level_csr", "spmv_amd_mg_stage",
+                    "spmv_amd_pcg_multi_stage"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
 DECLARED_CXX_SYMBOLS = [
     "SPMV_CSR", "SPMV_STENCIL5_CSR", "SPMV_STENCIL7_CSR", "SPMV_STENCIL_HALO_MGPU", "SPMV_ELLPACK", "SPMV_STENCIL5_ELLPACK",
@@ -281,6 +298,8 @@ def lib():
         L.spmv_amd_precond_multigrid_level_csr.restype = C.c_int
         L.spmv_amd_mg_stage.argtypes = [C.c_char_p, C.POINTER(MgStageArgs)]
         L.spmv_amd_mg_stage.restype = C.c_int
+        L.spmv_amd_pcg_multi_stage.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(PcgMultiStageArgs)]
+        L.spmv_amd_pcg_multi_stage.restype = C.c_int
     L.spmv_amd_cg_slab_create.restype = C.c_void_p
     L.spmv_amd_cg_slab_create.argtypes = [C.POINTER(MatrixData), C.c_void_p]
     L.spmv_amd_cg_slab_create_stencil5.restype = C.c_void_p
@@ -674,6 +693,11 @@ def _pcg_lib():
         L.spmv_amd_precond_create_multigrid3d.restype = C.c_void_p
         L.spmv_amd_precond_multigrid_dimension.argtypes = [C.c_void_p]
         L.spmv_amd_precond_multigrid_dimension.restype = C.c_int
+        L.spmv_amd_pcg_solve_device_multi.argtypes = [C.POINTER(SpmvOperator), C.POINTER(MatrixData), C.c_void_p, C.c_int, C.c_void_p,
+                                                      C.c_void_p, C.POINTER(CGConfig), C.POINTER(CGStats)]
+        L.spmv_amd_pcg_last_history_multi.argtypes = [C.c_int, C.c_void_p, C.c_int]
+        L.spmv_amd_pcg_multi_workspace_bytes.argtypes = []
+        L.spmv_amd_pcg_multi_workspace_bytes.restype = C.c_size_t
         L._pcg_sigs = True
     return L
 
@@ -812,6 +836,36 @@ def pcg_solve_device(op, host_matrix, precond, b, x0, max_iters=1000, tol=1e-6, 
     hist = np.zeros(max_iters + 1, dtype=np.float64)
     count = L.spmv_amd_pcg_last_history(hist.ctypes.data, len(hist))
     return x, hist[:count].copy(), st
+
+
+def pcg_solve_multi(op, host_matrix, precond, Bk, X0k, max_iters=1000, tol=1e-6, verbose=0, timers=0):
+    """spmv_amd_pcg_solve_device_multi: k independent preconditioned solves sharing the SpMM. Bk, X0k: (k, n).
+    Returns X (k, n), a list of k residual histories and a list of k CGStats (raises RuntimeError on a refusal)."""
+    Bk = np.ascontiguousarray(np.atleast_2d(Bk), dtype=np.float64)
+    X = np.ascontiguousarray(np.atleast_2d(X0k), dtype=np.float64).copy()
+    k = Bk.shape[0]
+    assert X.shape == Bk.shape
+    cfg = CGConfig(max_iters, tol, verbose, timers)
+    stats = (CGStats * k)()
+    L = _pcg_lib()
+    rc = L.spmv_amd_pcg_solve_device_multi(op.op, host_matrix.ptr, precond.handle, k, Bk.ctypes.data, X.ctypes.data, C.byref(cfg), stats)
+    if rc != 0:
+        raise RuntimeError(f"pcg_solve_device_multi -> {rc}")
+    hists = []
+    for j in range(k):
+        h = np.zeros(max_iters + 1, dtype=np.float64)
+        count = L.spmv_amd_pcg_last_history_multi(j, h.ctypes.data, len(h))
+        hists.append(h[:count].copy())
+    return X, hists, list(stats)
+
+
+def pcg_multi_stage(stage, kind, k, args):
+    """spmv_amd_pcg_multi_stage (LAB build only; include/spmv_amd/lab.h): one stage of the batched preconditioned solver's own
+    kernels on the device data `args` (PcgMultiStageArgs) points to; returns its return code (0, or non-zero for a refusal)."""
+    if not is_lab():
+        raise RuntimeError("the batched-PCG stages exist in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+    return lib().spmv_amd_pcg_multi_stage(stage if stage is None else stage.encode(), kind if kind is None else kind.encode(), int(k),
+                                          None if args is None else C.byref(args))
 
 
 def mg_stage(stage, args):

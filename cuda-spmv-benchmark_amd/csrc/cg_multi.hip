@@ -23,6 +23,7 @@
 
 #include "device_runtime.hpp"
 #include "multi_rhs.hpp"
+#include "multi_rhs_device.hpp"
 #include "reduce_device.hpp"
 #include "solve_common.hpp"
 #include "stream_device.hpp"
@@ -34,76 +35,8 @@ using namespace spmv_amd;
 namespace {
 
 constexpr hipStream_t kStream = nullptr;  // default stream, shared with the operators
-constexpr int kBlock = kReduceBlock;  // 256: the vector kernels' workgroup and the width of block_tree (reduce_device.hpp)
-constexpr int kSlice = kBlock * 16;  // partials one workgroup of the first reduction stage sums
 
-template <int K>
-__device__ __forceinline__ void load_row(const double* __restrict__ p, double (&o)[K]) {
-    if constexpr (K % 2 == 0) {  // workspace vectors: hipMalloc'd, rows of 8k bytes
-#pragma unroll
-        for (int i = 0; i < K / 2; ++i) {
-            const d2 t = reinterpret_cast<const d2*>(p)[i];
-            o[2 * i] = t.x, o[2 * i + 1] = t.y;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < K; ++i) o[i] = p[i];
-    }
-}
-
-template <int K>
-__device__ __forceinline__ void store_row(double* __restrict__ p, const double (&v)[K]) {
-    if constexpr (K % 2 == 0) {
-#pragma unroll
-        for (int i = 0; i < K / 2; ++i) {
-            d2 t;
-            t.x = v[2 * i], t.y = v[2 * i + 1];
-            reinterpret_cast<d2*>(p)[i] = t;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < K; ++i) p[i] = v[i];
-    }
-}
-
-// One partial per column of the workgroup's 256 rows: wave trees, then the four wave sums in wave order (the shape of the
-// SpMM's partials; independent of k and of the column's slot).
-template <int K>
-__device__ __forceinline__ void block_partials(double (&d)[K], double* __restrict__ partials, long long count, long long blk) {
-    __shared__ double s_wave[kBlock / 64][K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) d[j] += __shfl_down(d[j], off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < K; ++j) s_wave[threadIdx.x >> 6][j] = d[j];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < K) {
-        const int j = (int)threadIdx.x;
-        partials[(long long)j * count + blk] = ((s_wave[0][j] + s_wave[1][j]) + s_wave[2][j]) + s_wave[3][j];
-    }
-}
-
-// The vector kernels walk their workgroup's 256 rows x k columns FLAT (as the row-lds SpMM does, spmm_kernels.hip): unit
-// f = threadIdx.x + 256 i (i < P) is row f / P, columns (f % P) * V ... + V - 1, with V = 2 for even k (16-byte accesses), 1
-// else, P = k / V -- every access of one instruction is one contiguous run. Dot products go through LDS back to thread = row
-// and into block_partials: per column, the same shape whatever k is.
-template <int K>
-struct Flat {
-    static constexpr int V = K % 2 == 0 ? 2 : 1;
-    static constexpr int P = K / V;
-};
-
-// Thread = row again: the k products of the thread's row from LDS (every thread of the workgroup calls it: it has a barrier).
-template <int K>
-__device__ __forceinline__ void products_to_rows(const double* prod, double (&d)[K]) {
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < K; ++q) d[q] = prod[threadIdx.x * K + q];
-}
+// load_row, store_row, block_partials, Flat, products_to_rows, multi_reduce_slices_kernel, slices_for: multi_rhs_device.hpp
 
 // R = b - A x0 (R holds b on entry: axpby_kernel(1.0, b, -1.0, Ap), cg_solver.cu:48-54), P = R, partials of r.r.
 template <int K>
@@ -195,20 +128,6 @@ __global__ __launch_bounds__(kBlock) void multi_update_xp_kernel(long long n, co
     }
 }
 
-// Stage 1: workgroup (s, j) sums partials[j * count + s * kSlice ...] (each thread its strided share in ascending order, then
-// a fixed tree) into slices[j * slice_count + s].
-__global__ __launch_bounds__(kBlock) void multi_reduce_slices_kernel(const double* __restrict__ partials, long long count, int slice_count,
-                                                                    double* __restrict__ slices) {
-    __shared__ double s[kBlock];
-    const int j = (int)blockIdx.y, sl = (int)blockIdx.x;
-    const double* __restrict__ src = partials + (long long)j * count;
-    const long long lo = (long long)sl * kSlice, hi = lo + kSlice < count ? lo + kSlice : count;
-    double acc = 0.0;
-    for (long long i = lo + threadIdx.x; i < hi; i += kBlock) acc += src[i];
-    block_tree(acc, s);
-    if (threadIdx.x == 0) slices[(long long)j * slice_count + sl] = s[0];
-}
-
 // Stage 2 + the scalar step of column j (workgroup j). which: 0 = initial residual, 1 = pAp, 2 = r.r.
 __global__ __launch_bounds__(kBlock) void multi_reduce_step_kernel(const double* __restrict__ slices, int slice_count, int which, double tol,
                                                                   MultiColumn* __restrict__ cols, double* __restrict__ hist, int hist_cap) {
@@ -270,8 +189,6 @@ void launch_vector_step(int k, int which, long long n, const MultiColumn* cols, 
         default: launch_vec<8>(which, n, cols, X, R, P, AP, partials, count); break;
     }
 }
-
-int slices_for(long long count) { return (int)((count + kSlice - 1) / kSlice); }
 
 // The two reduction launches behind every dot product: k x slices_for(count) slice sums, then per column their sum and the
 // scalar step `which`. slices: k x slices_for(count) doubles.

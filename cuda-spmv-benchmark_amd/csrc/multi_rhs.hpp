@@ -1,5 +1,6 @@
-// multi_rhs.hpp -- one matrix, up to 8 right-hand sides: SpMM launchers (spmm_kernels.hip) and the batched CG kernels
-// (cg_multi.hip). Every launcher enqueues on the given stream and returns; none synchronises.
+// multi_rhs.hpp -- one matrix, up to 8 right-hand sides: SpMM launchers (spmm_kernels.hip) and the records of the batched solvers
+// (cg_multi.hip: CG; pcg_multi.hip: preconditioned CG; their shared device helpers: multi_rhs_device.hpp).
+// Every launcher enqueues on the given stream and returns; none synchronises.
 //
 // Block vectors are row-interleaved: element (row, column j) of a block of k columns lives at X[row * k + j]. One lane reads a
 // row's k values as one run of 8k bytes (16-byte loads where k is even and the pointer allows), and the solver streams 4-5
@@ -74,5 +75,25 @@ struct MultiColumn {
     int iterations;  // iterations this column took part in
     int pad;
 };
+
+// Per-column state of a batched preconditioned solve (pcg_multi.hip; device memory, one entry per column): pcg.hip's scalars
+// of one solve, per column, with the batched loop's two flags.
+struct PcgMultiColumn {
+    double rz;        // r.z of the column's current residual
+    double pAp, alpha, beta;
+    double b_norm;    // ||r0||
+    double residual;  // ||r_k||
+    int active;       // the column takes part in the current iteration (set by the pAp step: !done)
+    int done;         // converged or broken down: the column is frozen from the next iteration on
+    int iterations;   // iterations this column took part in
+    int converged;    // stopping test met
+    int breakdown;    // pAp or r.z' zero or not finite: stopped, not converged
+    int skip_update;  // this iteration's pAp broke down: r and x stay as they are
+    int pad[2];
+};
+// The batched preconditioned solver's workspace (pcg_multi.hip), released and counted like the batched CG solver's; the caller
+// holds the workspace lock.
+void release_pcg_multi_workspace_locked();
+size_t pcg_multi_workspace_bytes_locked();
 
 }  // namespace spmv_amd

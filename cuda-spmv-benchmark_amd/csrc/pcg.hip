@@ -807,9 +807,8 @@ bool creation_source(const SpmvOperator* op, const char* label, const char* not_
 }
 }  // namespace spmv_amd
 
-namespace {
-// What every entry point that takes (op, m) checks of the pair before any HIP call; d: the operator's storage view.
-bool precond_matches(const SpmvOperator* op, const SpmvAmdPrecond* m, const DiagonalSource& d) {
+// What every entry point that takes (op, m) checks of the pair before any HIP call; d: the operator's storage view (precond.hpp).
+bool spmv_amd::precond_matches(const SpmvOperator* op, const SpmvAmdPrecond* m, const DiagonalSource& d) {
     if (m->owner == nullptr) return true;  // made from a caller's diagonal: no operator to belong to
     if (m->owner != d.owner) return fail("the preconditioner was made from another operator: refused");
     if (m->generation != d.generation)
@@ -820,7 +819,6 @@ bool precond_matches(const SpmvOperator* op, const SpmvAmdPrecond* m, const Diag
     }
     return true;
 }
-}  // namespace
 
 extern "C" SpmvAmdPrecond* spmv_amd_precond_create_chebyshev(SpmvOperator* op, int degree, double lambda_min, double lambda_max, int* bad_row) {
     // argument checks: all before the first HIP call

@@ -1,0 +1,758 @@
+// pcg_multi.hip -- batched preconditioned CG: up to 8 independent systems A x_j = b_j solved together under one preconditioner of
+// kind "none", "jacobi" or "chebyshev", one matrix pass per product.
+//
+// Each column is its own PCG solve -- own alpha, beta, r.z, verdict, history and iteration count, the algebra of
+// spmv_amd_pcg_solve_device (pcg.hip, sections 13 and 14) element for element. What the columns share is the SpMM (spmm_kernels.hip),
+// which reads the coefficients once for all of them, and one dinv[row] per row. Not block CG: no shared Krylov space.
+//
+// One iteration on the default stream (block vectors interleaved, multi_rhs.hpp), "none" / "jacobi":
+//   AP = A P with the per-column p.Ap partials | sums + step 1 (active = !done, alpha = rz / pAp, an unusable pAp: skip_update) |
+//   R -= alpha AP, z = dinv r in registers, the partials of r.r and r.z | sums + step 2 (history, verdict, beta) |
+//   X += alpha P, then P = z + beta P unless the column stopped in this iteration
+// "chebyshev" of degree K:
+//   AP = A P | step 1 | R -= alpha AP with term 0 (D, Z), the r.r partials | step 3 (history, verdict) |
+//   K x ( W = A Z into the AP buffer ; the step kernel on the columns still running, the last one leaves the r.z partials ) |
+//   step 4 (beta) | X += alpha P, P = Z + beta P
+// then one small blocking read of the k column records (the stopping test). A column that converged or broke down is frozen: no
+// kernel changes a bit of its X, R, P, D, Z, history or count from the next iteration on. In the iteration in which the last column
+// stops the K SpMMs of the Chebyshev steps still run (the step kernels return at once): once per solve, and cheaper than a second
+// host read per iteration.
+//
+// Dot products: the rounded product per row, the workgroup's 256 rows through block_partials (multi_rhs_device.hpp), then the two
+// reduction stages of the batched CG solver per value and column -- the same bits for a column whatever k is and whatever slot it
+// sits in. A kernel with two values sends them through ONE LDS product array, one after the other (16 KiB at k = 8, so LDS never
+// limits the 8 workgroups a CU holds; two arrays would be 32 KiB and 5 workgroups; the price is one more barrier per workgroup).
+#include <limits.h>
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <vector>
+
+#include "device_runtime.hpp"
+#include "multi_rhs.hpp"
+#include "multi_rhs_device.hpp"
+#include "precond.hpp"
+#include "reduce_device.hpp"
+#include "solve_common.hpp"
+#include "stream_device.hpp"
+#ifdef SPMV_AMD_LAB
+#include "spmv_amd/lab.h"
+#endif
+
+using namespace spmv_amd;
+
+namespace {
+
+constexpr hipStream_t kStream = nullptr;  // default stream, shared with the operators
+
+// The kind as the kernels see it: what z is made of decides the loads.
+constexpr int kPlain = 0, kJac = 1, kCheb = 2;
+
+__device__ __forceinline__ bool usable(double v) { return v != 0.0 && isfinite(v); }
+
+// One unit (V = 1 or 2 values) of a stream that is read / written once per pass
+template <int V>
+__device__ __forceinline__ void load_unit_once(const double* __restrict__ p, double (&o)[V]) {
+    if constexpr (V == 2) {
+        const d2 t = __builtin_nontemporal_load(reinterpret_cast<const d2*>(p));
+        o[0] = t.x, o[1] = t.y;
+    } else {
+        o[0] = __builtin_nontemporal_load(p);
+    }
+}
+template <int V>
+__device__ __forceinline__ void store_unit_once(double* __restrict__ p, const double (&v)[V]) {
+    if constexpr (V == 2) {
+        d2 t;
+        t.x = v[0], t.y = v[1];
+        __builtin_nontemporal_store(t, reinterpret_cast<d2*>(p));
+    } else {
+        __builtin_nontemporal_store(v[0], p);
+    }
+}
+
+// The partials of one or two values from the units' products: value 0 (in prod already) at partials[j * count + blk], value 1
+// (second[], this thread's units in walk order) at partials[(K + j) * count + blk] through the same LDS array. Every thread of the
+// workgroup calls it.
+template <int K>
+__device__ __forceinline__ void unit_partials(double* prod, bool first, const double (&second)[K], bool with_second,
+                                              double* __restrict__ partials, long long count) {
+    constexpr int V = Flat<K>::V, U = Flat<K>::P;
+    double d[K];
+    if (first) {
+        products_to_rows<K>(prod, d);
+        block_partials<K>(d, partials, count, blockIdx.x);
+    }
+    if (!with_second) return;
+    __syncthreads();  // every thread has read its row of prod, and threads < K the wave sums
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+        const int f = (int)threadIdx.x + kBlock * i;
+        const int t = f / U, col0 = (f - t * U) * V;
+#pragma unroll
+        for (int q = 0; q < V; ++q) prod[t * K + col0 + q] = second[i * V + q];
+    }
+    products_to_rows<K>(prod, d);
+    block_partials<K>(d, partials + (long long)K * count, count, blockIdx.x);
+}
+
+// R = b - A x0 (R holds b on entry), z0 = M^-1 r0 as far as one pass goes, the partials of r.r (value 0) and r.z (value 1).
+// kPlain / kJac: z = r / dinv r, P = z. kCheb: term 0 in registers -- u = dinv r ; d = c0 u ; z = d -- to D and Z; the r.z partials only
+// when term 0 is the whole polynomial (last).
+template <int K, int kKind>
+__global__ __launch_bounds__(kBlock) void pcg_multi_init_kernel(long long n, const double* __restrict__ AP, const double* __restrict__ dinv,
+                                                               double c0, int last, double* __restrict__ R, double* __restrict__ P,
+                                                               double* __restrict__ D, double* __restrict__ Z, double* __restrict__ partials,
+                                                               long long count) {
+    constexpr int V = Flat<K>::V, U = Flat<K>::P;
+    __shared__ double prod[kBlock * K];
+    double rz[K];
+    const long long row0 = (long long)blockIdx.x * kBlock;
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+        const int f = (int)threadIdx.x + kBlock * i;
+        const int t = f / U, col0 = (f - t * U) * V;
+        double r[V] = {}, z[V] = {};
+        if (row0 + t < n) {
+            const long long at = (row0 + t) * K + col0;
+            double ap[V];
+            load_unit_once<V>(AP + at, ap);
+            load_unit_once<V>(R + at, r);
+            const double dv = kKind == kPlain ? 1.0 : dinv[row0 + t];  // one load per unit: the units of a row read the same 8 bytes
+#pragma unroll
+            for (int q = 0; q < V; ++q) {
+                r[q] = fma(1.0, r[q], -1.0 * ap[q]);
+                z[q] = kKind == kPlain ? r[q] : kKind == kJac ? dv * r[q] : c0 * (dv * r[q]);
+            }
+            store_unit_once<V>(R + at, r);
+            if (kKind == kCheb) {
+                store_unit_once<V>(D + at, z);
+                store_row<V>(Z + at, z);  // plain: the first step's SpMM reads it
+            } else {
+                store_row<V>(P + at, z);  // plain: the first SpMM reads it
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < V; ++q) prod[t * K + col0 + q] = r[q] * r[q], rz[i * V + q] = r[q] * z[q];
+    }
+    unit_partials<K>(prod, true, rz, kKind != kCheb || last != 0, partials, count);
+}
+
+// r = fma(-alpha, Ap, r) for the columns of this iteration whose pAp did not break down; z = M^-1 r as far as one pass goes; the
+// partials of r.r (value 0) and r.z (value 1). kPlain / kJac: z stays in the registers. kCheb: term 0 to D and Z for the active
+// columns (a frozen column's D and Z keep their bits); the r.z partials only when term 0 is the whole polynomial (last).
+template <int K, int kKind>
+__global__ __launch_bounds__(kBlock) void pcg_multi_update_r_kernel(long long n, const PcgMultiColumn* __restrict__ cols,
+                                                                   const double* __restrict__ AP, const double* __restrict__ dinv, double c0,
+                                                                   int last, double* __restrict__ R, double* __restrict__ D,
+                                                                   double* __restrict__ Z, double* __restrict__ partials, long long count) {
+    constexpr int V = Flat<K>::V, U = Flat<K>::P;
+    __shared__ double prod[kBlock * K];
+    double rz[K];
+    const long long row0 = (long long)blockIdx.x * kBlock;
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+        const int f = (int)threadIdx.x + kBlock * i;
+        const int t = f / U, col0 = (f - t * U) * V;
+        double r[V] = {}, z[V] = {};
+        if (row0 + t < n) {
+            const long long at = (row0 + t) * K + col0;
+            double ap[V];
+            load_unit_once<V>(AP + at, ap);
+            load_unit_once<V>(R + at, r);
+            const double dv = kKind == kPlain ? 1.0 : dinv[row0 + t];
+            bool any = false, all = true;
+#pragma unroll
+            for (int q = 0; q < V; ++q) {
+                const PcgMultiColumn& c = cols[col0 + q];
+                if (c.active && !c.skip_update) r[q] = fma(-c.alpha, ap[q], r[q]);
+                z[q] = kKind == kPlain ? r[q] : kKind == kJac ? dv * r[q] : c0 * (dv * r[q]);
+                any = any || c.active, all = all && c.active;
+            }
+            store_unit_once<V>(R + at, r);
+            if (kKind == kCheb && any) {
+                double dz[V], zz[V];
+#pragma unroll
+                for (int q = 0; q < V; ++q) dz[q] = zz[q] = z[q];
+                if (!all) {  // a frozen column beside an active one in a 16-byte pair: its bits go back as they came
+                    double dk[V], zk[V];
+                    load_row<V>(D + at, dk);
+                    load_row<V>(Z + at, zk);
+#pragma unroll
+                    for (int q = 0; q < V; ++q)
+                        if (!cols[col0 + q].active) dz[q] = dk[q], zz[q] = zk[q];
+                }
+                store_unit_once<V>(D + at, dz);
+                store_row<V>(Z + at, zz);  // plain: the first step's SpMM reads it
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < V; ++q) prod[t * K + col0 + q] = r[q] * r[q], rz[i * V + q] = r[q] * z[q];
+    }
+    unit_partials<K>(prod, true, rz, kKind != kCheb || last != 0, partials, count);
+}
+
+// One Chebyshev step behind a SpMM that wrote W = A Z, on the columns still running (done == 0):
+// d = fma(g, dinv * fma(-1, w, r), h * d) ; z = z + d, D and Z in place. last: the partials of r.z as value 1 (value 0, r.r, stays
+// as the r update left it). Nothing is read for a unit without a running column, and nothing at all once every column is done.
+template <int K>
+__global__ __launch_bounds__(kBlock) void pcg_multi_cheb_step_kernel(long long n, const PcgMultiColumn* __restrict__ cols,
+                                                                    const double* __restrict__ W, const double* __restrict__ R,
+                                                                    const double* __restrict__ dinv, double g, double h, double* __restrict__ D,
+                                                                    double* __restrict__ Z, int last, double* __restrict__ partials,
+                                                                    long long count) {
+    constexpr int V = Flat<K>::V, U = Flat<K>::P;
+    __shared__ double prod[kBlock * K];
+    bool running = false;
+#pragma unroll
+    for (int j = 0; j < K; ++j) running = running || cols[j].done == 0;
+    if (!running) return;  // uniform over the launch
+    double rz[K];
+    const long long row0 = (long long)blockIdx.x * kBlock;
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+        const int f = (int)threadIdx.x + kBlock * i;
+        const int t = f / U, col0 = (f - t * U) * V;
+        bool run[V], any = false;
+#pragma unroll
+        for (int q = 0; q < V; ++q) run[q] = cols[col0 + q].done == 0, any = any || run[q], rz[i * V + q] = 0.0;
+        if (any && row0 + t < n) {
+            const long long at = (row0 + t) * K + col0;
+            double w[V], r[V], d[V], z[V];
+            load_unit_once<V>(W + at, w);
+            load_unit_once<V>(R + at, r);
+            load_unit_once<V>(D + at, d);
+            load_row<V>(Z + at, z);
+            const double dv = dinv[row0 + t];
+#pragma unroll
+            for (int q = 0; q < V; ++q) {
+                if (!run[q]) continue;
+                d[q] = fma(g, dv * fma(-1.0, w[q], r[q]), h * d[q]);
+                z[q] = z[q] + d[q];
+                rz[i * V + q] = r[q] * z[q];
+            }
+            store_unit_once<V>(D + at, d);
+            store_row<V>(Z + at, z);  // plain: the next SpMM reads it
+        }
+    }
+    if (last) unit_partials<K>(prod, false, rz, true, partials, count);
+}
+
+// x = fma(alpha, p, x) for the columns of this iteration whose pAp did not break down; then p = fma(beta, p, z) for those that did
+// not stop in it. z: dinv r (kJac), r (kPlain) from ZR = R, or ZR = Z (kCheb). Nothing is read for a unit without such a column.
+template <int K, int kKind>
+__global__ __launch_bounds__(kBlock) void pcg_multi_update_xp_kernel(long long n, const PcgMultiColumn* __restrict__ cols,
+                                                                    const double* __restrict__ ZR, const double* __restrict__ dinv,
+                                                                    double* __restrict__ P, double* __restrict__ X) {
+    constexpr int V = Flat<K>::V, U = Flat<K>::P;
+    const long long row0 = (long long)blockIdx.x * kBlock;
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+        const int f = (int)threadIdx.x + kBlock * i;
+        const int t = f / U, col0 = (f - t * U) * V;
+        if (row0 + t >= n) continue;
+        bool upd[V], dir[V], any_upd = false, any_dir = false;
+        double alpha[V], beta[V];
+#pragma unroll
+        for (int q = 0; q < V; ++q) {
+            const PcgMultiColumn& c = cols[col0 + q];
+            upd[q] = c.active != 0 && c.skip_update == 0;
+            dir[q] = upd[q] && c.done == 0;
+            alpha[q] = c.alpha, beta[q] = c.beta;
+            any_upd = any_upd || upd[q], any_dir = any_dir || dir[q];
+        }
+        if (!any_upd) continue;
+        const long long at = (row0 + t) * K + col0;
+        double x[V], p[V], z[V] = {};
+        double dv = 1.0;
+        load_unit_once<V>(X + at, x);  // every load of the unit before the first use: one wait, not two
+        load_unit_once<V>(P + at, p);
+        if (any_dir) {
+            load_unit_once<V>(ZR + at, z);
+            if (kKind == kJac) dv = dinv[row0 + t];
+        }
+#pragma unroll
+        for (int q = 0; q < V; ++q)
+            if (upd[q]) x[q] = fma(alpha[q], p[q], x[q]);
+        store_unit_once<V>(X + at, x);
+        if (!any_dir) continue;
+#pragma unroll
+        for (int q = 0; q < V; ++q) {
+            if (kKind == kJac) z[q] = dv * z[q];
+            if (dir[q]) p[q] = fma(beta[q], p[q], z[q]);
+        }
+        store_row<V>(P + at, p);  // plain: the next SpMM's neighbour loads re-use these lines
+    }
+}
+
+// pcg.hip's pcg_step, per column and branch for branch. which: 0 = initial r.r / r.z, 1 = pAp, 2 = r.r / r.z', 3 = r.r and the verdict
+// alone, 4 = r.z' and beta alone (the last two: kind "chebyshev").
+__device__ void pcg_multi_step(PcgMultiColumn& c, int which, const double* total, double tol, double* hist, int hist_cap) {
+    if (which == 0) {
+        c.b_norm = sqrt(total[0]);
+        c.residual = c.b_norm;
+        c.rz = total[1];
+        c.pAp = c.alpha = c.beta = 0.0;
+        c.active = c.done = c.iterations = c.converged = c.breakdown = c.skip_update = 0;
+        if (hist_cap > 0) hist[0] = c.b_norm;
+    } else if (which == 1) {
+        c.active = c.done ? 0 : 1;
+        if (!c.active) return;
+        c.pAp = total[0];
+        if (usable(c.pAp)) {
+            c.alpha = c.rz / c.pAp;
+        } else {
+            c.alpha = 0.0;
+            c.skip_update = 1;
+        }
+    } else if (!c.active) {
+        return;
+    } else if (which == 2 || which == 3) {
+        const double res = sqrt(total[0]);
+        c.iterations += 1;
+        c.residual = res;
+        if (c.iterations < hist_cap) hist[c.iterations] = res;
+        if (c.skip_update) {
+            c.breakdown = 1;
+        } else if (res / c.b_norm < tol) {
+            c.converged = 1;
+        } else if (which == 2) {
+            if (!usable(total[1])) {
+                c.breakdown = 1;
+            } else {
+                c.beta = total[1] / c.rz;
+                c.rz = total[1];
+            }
+        }
+        c.done = (c.converged != 0 || c.breakdown != 0) ? 1 : 0;
+    } else if (c.done == 0) {  // which == 4
+        if (!usable(total[0])) {
+            c.breakdown = 1;
+            c.done = 1;
+        } else {
+            c.beta = total[0] / c.rz;
+            c.rz = total[0];
+        }
+    }
+}
+
+// Stage 2 of each value + the scalar step of column j (workgroup j). Value v of column j: slices[(v * k + j) * slice_count ...].
+__global__ __launch_bounds__(kBlock) void pcg_multi_step_kernel(const double* __restrict__ slices, int slice_count, int k, int nv, int which,
+                                                               double tol, PcgMultiColumn* __restrict__ cols, double* __restrict__ hist,
+                                                               int hist_cap) {
+    __shared__ double s[kBlock];
+    const int j = (int)blockIdx.x;
+    double total[2] = {0.0, 0.0};
+    for (int v = 0; v < nv; ++v) {
+        const double* __restrict__ src = slices + ((long long)v * k + j) * slice_count;
+        double acc = 0.0;
+        for (int i = (int)threadIdx.x; i < slice_count; i += kBlock) acc += src[i];
+        block_tree(acc, s);
+        total[v] = s[0];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) pcg_multi_step(cols[j], which, total, tol, hist + (long long)j * hist_cap, hist_cap);
+}
+
+// ---- the loop's launches, one function each: the solve calls these, and so does the LAB build's spmv_amd_pcg_multi_stage ----
+
+struct VecArgs {
+    long long n;
+    const PcgMultiColumn* cols;
+    const double* dinv;
+    double c0, g, h;  // c0: term 0; g, h: one Chebyshev step
+    int last;
+    double *X, *R, *P, *AP, *D, *Z;
+    double* partials;
+    long long count;
+};
+enum { kStageInit, kStageUpdateR, kStageUpdateXp, kStageChebStep };
+
+template <int K, int kKind>
+void launch_vec_kind(int stage, const VecArgs& a) {
+    const dim3 grid((unsigned)((a.n + kBlock - 1) / kBlock)), block(kBlock);
+    if (stage == kStageInit)
+        hipLaunchKernelGGL((pcg_multi_init_kernel<K, kKind>), grid, block, 0, kStream, a.n, a.AP, a.dinv, a.c0, a.last, a.R, a.P, a.D, a.Z,
+                           a.partials, a.count);
+    else if (stage == kStageUpdateR)
+        hipLaunchKernelGGL((pcg_multi_update_r_kernel<K, kKind>), grid, block, 0, kStream, a.n, a.cols, a.AP, a.dinv, a.c0, a.last, a.R, a.D, a.Z,
+                           a.partials, a.count);
+    else
+        hipLaunchKernelGGL((pcg_multi_update_xp_kernel<K, kKind>), grid, block, 0, kStream, a.n, a.cols, kKind == kCheb ? a.Z : a.R, a.dinv, a.P,
+                           a.X);
+}
+
+template <int K>
+void launch_vec(int stage, int kind, const VecArgs& a) {
+    if (stage == kStageChebStep) {
+        const dim3 grid((unsigned)((a.n + kBlock - 1) / kBlock)), block(kBlock);
+        hipLaunchKernelGGL((pcg_multi_cheb_step_kernel<K>), grid, block, 0, kStream, a.n, a.cols, a.AP, a.R, a.dinv, a.g, a.h, a.D, a.Z, a.last,
+                           a.partials, a.count);
+    } else if (kind == kCheb) {
+        launch_vec_kind<K, kCheb>(stage, a);
+    } else if (kind == kJac) {
+        launch_vec_kind<K, kJac>(stage, a);
+    } else {
+        launch_vec_kind<K, kPlain>(stage, a);
+    }
+}
+
+// kind: kPlain, kJac, kCheb. a.count = the workgroups of the launch.
+void launch_vector_stage(int k, int stage, int kind, const VecArgs& a) {
+    switch (k) {
+        case 1: launch_vec<1>(stage, kind, a); break;
+        case 2: launch_vec<2>(stage, kind, a); break;
+        case 3: launch_vec<3>(stage, kind, a); break;
+        case 4: launch_vec<4>(stage, kind, a); break;
+        case 5: launch_vec<5>(stage, kind, a); break;
+        case 6: launch_vec<6>(stage, kind, a); break;
+        case 7: launch_vec<7>(stage, kind, a); break;
+        default: launch_vec<8>(stage, kind, a); break;
+    }
+}
+
+int values_of_step(int which) { return which == 0 || which == 2 ? 2 : 1; }
+
+// The two reduction launches behind a scalar step: nv x k x slices_for(count) slice sums of the values at `partials` (value v of
+// column j at [(v * k + j) * count ...]), then per column their sums and step `which`. slices: 2 k x slices_for(count) doubles.
+void launch_reduce(int k, const double* partials, long long count, double* slices, int which, double tol, PcgMultiColumn* cols, double* hist,
+                   int hist_cap) {
+    const int sc = slices_for(count), nv = values_of_step(which);
+    hipLaunchKernelGGL(multi_reduce_slices_kernel, dim3((unsigned)sc, (unsigned)(nv * k)), dim3(kBlock), 0, kStream, partials, count, sc, slices);
+    hipLaunchKernelGGL(pcg_multi_step_kernel, dim3((unsigned)k), dim3(kBlock), 0, kStream, slices, sc, k, nv, which, tol, cols, hist, hist_cap);
+}
+
+// ---- workspace: kept between calls (like the other CG solvers'), released with them ----
+struct PcgMultiWorkspace {
+    int n = 0, k = 0, device = -1;
+    double *X = nullptr, *R = nullptr, *P = nullptr, *AP = nullptr;
+    double *D = nullptr, *Z = nullptr;  // kind "chebyshev" only
+    double* partials = nullptr;         // max(k x SpMM partials, 2 x k x vector partials)
+    double* slices = nullptr;           // 2 k x slices of max(SpMM partials, vector partials)
+    PcgMultiColumn* cols = nullptr;
+    double* hist = nullptr;  // k x hist_cap
+    int hist_cap = 0;
+    long long partial_cap = 0;  // per value and column
+    void release() {
+        device_release(X);
+        device_release(R);
+        device_release(P);
+        device_release(AP);
+        device_release(D);
+        device_release(Z);
+        device_release(partials);
+        device_release(slices);
+        device_release(cols);
+        device_release(hist);
+        n = k = 0, device = -1, hist_cap = 0, partial_cap = 0;
+    }
+};
+PcgMultiWorkspace g_ws;
+std::vector<std::vector<double>> g_history;  // of the last batched preconditioned solve, per column
+
+bool fail(const char* what) {
+    fprintf(stderr, "[PCG-MULTI] %s\n", what);
+    return false;
+}
+
+bool ensure_workspace(int n, int k, int device, long long partial_cap, int hist_cap, bool cheb) {
+    PcgMultiWorkspace& w = g_ws;
+    if (w.X != nullptr && (w.n != n || w.k != k || w.device != device || w.partial_cap < partial_cap)) w.release();
+    const size_t vec = (size_t)n * k * sizeof(double);
+    char what[64];
+    snprintf(what, sizeof what, "%d systems of %d rows%s", k, n, cheb ? " (chebyshev)" : "");
+    if (w.X == nullptr) {
+        const size_t need = (cheb ? 6 : 4) * vec + 2 * (size_t)k * partial_cap * sizeof(double) +
+                            2 * (size_t)k * slices_for(partial_cap) * sizeof(double) + (size_t)k * hist_cap * sizeof(double) + ((size_t)64 << 20);
+        if (!device_has_room(need, "PCG-MULTI", what)) return false;
+        w.X = device_try_alloc<double>((size_t)n * k);
+        w.R = device_try_alloc<double>((size_t)n * k);
+        w.P = device_try_alloc<double>((size_t)n * k);
+        w.AP = device_try_alloc<double>((size_t)n * k);
+        w.partials = device_try_alloc<double>(2 * (size_t)k * partial_cap);
+        w.slices = device_try_alloc<double>(2 * (size_t)k * slices_for(partial_cap));
+        w.cols = device_try_alloc<PcgMultiColumn>((size_t)k);
+        if (!w.X || !w.R || !w.P || !w.AP || !w.partials || !w.slices || !w.cols) {
+            w.release();
+            return fail("the workspace could not be allocated: refused");
+        }
+        w.n = n, w.k = k, w.device = device, w.partial_cap = partial_cap;
+    }
+    if (cheb && w.D == nullptr) {
+        if (!device_has_room(2 * vec + ((size_t)64 << 20), "PCG-MULTI", what)) return false;
+        w.D = device_try_alloc<double>((size_t)n * k);
+        w.Z = device_try_alloc<double>((size_t)n * k);
+        if (!w.D || !w.Z) {
+            device_release(w.D);
+            device_release(w.Z);
+            return fail("the Chebyshev block vectors could not be allocated: refused");
+        }
+    }
+    if (!grow_history(w.hist, w.hist_cap, hist_cap, (size_t)k)) return fail("the history could not be allocated: refused");
+    return true;
+}
+
+}  // namespace
+
+namespace spmv_amd {
+void release_pcg_multi_workspace_locked() { g_ws.release(); }
+
+size_t pcg_multi_workspace_bytes_locked() {
+    const PcgMultiWorkspace& w = g_ws;
+    if (w.X == nullptr) return 0;
+    return ((w.D != nullptr ? 6 : 4) * (size_t)w.n * w.k + 2 * (size_t)w.k * w.partial_cap + 2 * (size_t)w.k * slices_for(w.partial_cap) +
+            (size_t)w.k * w.hist_cap) *
+               sizeof(double) +
+           (size_t)w.k * sizeof(PcgMultiColumn);
+}
+}  // namespace spmv_amd
+
+extern "C" int spmv_amd_pcg_solve_device_multi(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, int nrhs, const double* B, double* X,
+                                               const CGConfig* config, CGStats* stats) {
+    // argument checks: all before the first HIP call
+    if (nrhs < 1 || nrhs > kMaxRhs) {
+        fprintf(stderr, "[PCG-MULTI] nrhs = %d: 1 to %d right-hand sides are supported\n", nrhs, kMaxRhs);
+        return 1;
+    }
+    if (op == nullptr || mat == nullptr || m == nullptr || B == nullptr || X == nullptr || config == nullptr || stats == nullptr)
+        return fail("null argument"), 1;
+    if (config->max_iters < 0) return fail("max_iters < 0"), 1;
+    const MultiOperand o = multi_operand_of(op);
+    if (!o.has_multi) {
+        fprintf(stderr, "[PCG-MULTI] operator '%s' has no multi-RHS path (stencil5-csr, stencil7-csr and cusparse-csr have one)\n",
+                op->name ? op->name : "?");
+        return 1;
+    }
+    if (!o.ready) {
+        fprintf(stderr, "[PCG-MULTI] operator '%s' used before init\n", op->name);
+        return 1;
+    }
+    if (o.plan.rows != o.plan.cols || mat->rows != o.plan.rows) {
+        fprintf(stderr, "[PCG-MULTI] the operator holds a %d x %d matrix, mat->rows = %d: a square system of that size is required\n",
+                o.plan.rows, o.plan.cols, mat->rows);
+        return 1;
+    }
+    if (m->kind == kMultigrid)
+        return fail("kind 'multigrid' keeps single vectors on every level of its hierarchy: not available for several right-hand sides, refused"), 1;
+    if (m->kind != kNone && m->kind != kJacobi && m->kind != kChebyshev) return fail("unknown preconditioner kind: refused"), 1;
+    if (m->n != mat->rows) {
+        fprintf(stderr, "[PCG-MULTI] the preconditioner is for %d rows, mat->rows = %d\n", m->n, mat->rows);
+        return 1;
+    }
+    if (!precond_matches(op, m, diagonal_source_of(op))) return fail("the preconditioner does not belong to this operator as it stands: refused"), 1;
+    const int n = mat->rows, k = nrhs;
+    const CGConfig cfg = *config;
+    const int kind = m->kind == kChebyshev ? kCheb : m->kind == kJacobi ? kJac : kPlain;
+    const int degree = kind == kCheb ? m->degree : 0;
+
+    CgWorkspaceScope scope;
+    int device = 0;
+    HIP_CHECK(hipGetDevice(&device));
+    const long long vec_count = ((long long)n + kBlock - 1) / kBlock;
+    const long long spmm_count = o.plan.blocks;
+    const long long partial_cap = vec_count > spmm_count ? vec_count : spmm_count;
+    if (!ensure_workspace(n, k, device, partial_cap, cfg.max_iters + 1, kind == kCheb)) return 1;
+    PcgMultiWorkspace& w = g_ws;
+
+    // B and x0 arrive as k columns one after the other: through AP (free until the first SpMM) into interleaved R and X
+    upload(w.AP, B, (size_t)n * k);
+    launch_interleave(k, (size_t)n, w.AP, w.R, kStream);
+    HIP_CHECK(hipStreamSynchronize(kStream));
+    upload(w.AP, X, (size_t)n * k);
+    launch_interleave(k, (size_t)n, w.AP, w.X, kStream);
+    HIP_CHECK(hipMemsetAsync(w.cols, 0, (size_t)k * sizeof(PcgMultiColumn), kStream));  // done = 0: the first application's steps run
+    HIP_CHECK(hipStreamSynchronize(kStream));
+
+    std::vector<PcgMultiColumn> h_cols((size_t)k);
+    StageTimers T(cfg.enable_detailed_timers != 0, kStream);
+    VecArgs a{};
+    a.n = n, a.cols = w.cols, a.dinv = m->dinv, a.c0 = kind == kCheb ? m->coef[0] : 0.0, a.last = degree == 0 ? 1 : 0;
+    a.X = w.X, a.R = w.R, a.P = w.P, a.AP = w.AP, a.D = w.D, a.Z = w.Z, a.partials = w.partials, a.count = vec_count;
+    auto vec = [&](int stage) { T.run(&T.t_blas, [&] { launch_vector_stage(k, stage, kind, a); }); };
+    auto reduce = [&](const double* partials, long long count, int which) {
+        T.run(&T.t_red, [&] { launch_reduce(k, partials, count, w.slices, which, cfg.tolerance, w.cols, w.hist, w.hist_cap); });
+    };
+    auto spmm = [&](const double* in, double* partials) { T.run(&T.t_spmv, [&] { launch_spmm(o.plan, k, in, w.AP, partials, kStream); }); };
+    // steps 1 .. degree behind a term 0 that left D and Z: W = A Z goes to the AP buffer, free between the r update and the next SpMM
+    auto cheb_steps = [&] {
+        for (int s = 1; s <= degree; ++s) {
+            spmm(w.Z, nullptr);
+            VecArgs c = a;
+            c.g = m->coef[2 * s], c.h = m->coef[2 * s - 1], c.last = s == degree ? 1 : 0;
+            T.run(&T.t_blas, [&] { launch_vector_stage(k, kStageChebStep, kind, c); });
+        }
+    };
+    auto read_columns = [&] { download(h_cols.data(), w.cols, (size_t)k); };
+
+    T.total.begin(kStream);
+    spmm(w.X, nullptr);
+    vec(kStageInit);
+    if (kind == kCheb) {
+        cheb_steps();
+        HIP_CHECK(hipMemcpyAsync(w.P, w.Z, (size_t)n * k * sizeof(double), hipMemcpyDeviceToDevice, kStream));  // p0 = z0
+    }
+    reduce(w.partials, vec_count, 0);
+    read_columns();
+    if (cfg.verbose >= 1)
+        for (int j = 0; j < k; ++j)
+            printf("[PCG-MULTI %d] Initial residual: %e (preconditioner %s)\n", j, h_cols[j].b_norm, spmv_amd_precond_kind(m));
+    for (int it = 0; it < cfg.max_iters; ++it) {
+        bool any = false;
+        for (int j = 0; j < k; ++j) any = any || !h_cols[j].done;
+        if (!any) break;
+        spmm(w.P, w.partials);
+        reduce(w.partials, spmm_count, 1);
+        vec(kStageUpdateR);
+        if (kind == kCheb) {
+            reduce(w.partials, vec_count, 3);
+            cheb_steps();
+            reduce(w.partials + (size_t)k * vec_count, vec_count, 4);
+        } else {
+            reduce(w.partials, vec_count, 2);
+        }
+        vec(kStageUpdateXp);
+        read_columns();  // synchronises: the stopping test of every column
+        if (cfg.verbose >= 2)
+            for (int j = 0; j < k; ++j)
+                if (h_cols[j].active)
+                    printf("[PCG-MULTI %d] Iter %3d: residual = %e (rel = %e)\n", j, h_cols[j].iterations, h_cols[j].residual,
+                           h_cols[j].residual / h_cols[j].b_norm);
+    }
+    T.total.end(kStream);
+    const double total_ms = T.total.elapsed_ms();
+    HIP_CHECK(hipGetLastError());
+
+    // the solution back as k columns one after the other (outside the timed region, as the upload)
+    launch_deinterleave(k, (size_t)n, w.X, w.AP, kStream);
+    HIP_CHECK(hipStreamSynchronize(kStream));
+    download(X, w.AP, (size_t)n * k);
+    g_history.assign((size_t)k, std::vector<double>());
+    for (int j = 0; j < k; ++j) {
+        const PcgMultiColumn& c = h_cols[j];
+        const int count = c.iterations + 1 < w.hist_cap ? c.iterations + 1 : w.hist_cap;
+        g_history[j].resize((size_t)count);
+        download(g_history[j].data(), w.hist + (size_t)j * w.hist_cap, (size_t)count);
+        CGStats& st = stats[j];
+        fill_device_stats(&st, c.iterations, c.converged != 0, c.residual, c.b_norm, cfg, total_ms, T.t_spmv, T.t_blas, T.t_red);
+        solution_checksums(X + (size_t)j * n, n, &st.solution_sum, &st.solution_norm);
+        if (cfg.verbose >= 1) {
+            if (c.breakdown) printf("[PCG-MULTI %d] Breakdown in iteration %d (pAp or r.z zero or not finite)\n", j, c.iterations);
+            printf("[PCG-MULTI %d] Converged: %s\n", j, st.converged ? "YES" : "NO");
+            printf("[PCG-MULTI %d] Iterations: %d\n", j, st.iterations);
+            printf("[PCG-MULTI %d] Final residual: %e\n", j, st.residual_norm);
+        }
+    }
+    if (cfg.verbose >= 1) {
+        printf("[PCG-MULTI] %d systems, time breakdown (whole batch):\n", k);
+        printf("     Total:      %.3f ms\n", total_ms);
+        printf("     SpMV:       %.3f ms\n", T.t_spmv);
+        printf("     BLAS1:      %.3f ms\n", T.t_blas);
+        printf("     Reductions: %.3f ms\n", T.t_red);
+    }
+    return 0;
+}
+
+extern "C" size_t spmv_amd_pcg_multi_workspace_bytes(void) {
+    CgWorkspaceScope scope;
+    return pcg_multi_workspace_bytes_locked();
+}
+
+extern "C" int spmv_amd_pcg_last_history_multi(int rhs, double* out, int cap) {
+    if (rhs < 0 || rhs >= (int)g_history.size()) return -1;
+    return copy_history(g_history[(size_t)rhs], out, cap);
+}
+
+#ifdef SPMV_AMD_LAB
+// ---- the loop's kernels one stage at a time on caller data (include/spmv_amd/lab.h; tests/test_pcg_multi_stages_gpu.py) ----
+static_assert(sizeof(SpmvAmdPcgMultiColumn) == sizeof(PcgMultiColumn) && offsetof(SpmvAmdPcgMultiColumn, rz) == offsetof(PcgMultiColumn, rz) &&
+                  offsetof(SpmvAmdPcgMultiColumn, pAp) == offsetof(PcgMultiColumn, pAp) &&
+                  offsetof(SpmvAmdPcgMultiColumn, alpha) == offsetof(PcgMultiColumn, alpha) &&
+                  offsetof(SpmvAmdPcgMultiColumn, beta) == offsetof(PcgMultiColumn, beta) &&
+                  offsetof(SpmvAmdPcgMultiColumn, b_norm) == offsetof(PcgMultiColumn, b_norm) &&
+                  offsetof(SpmvAmdPcgMultiColumn, residual) == offsetof(PcgMultiColumn, residual) &&
+                  offsetof(SpmvAmdPcgMultiColumn, active) == offsetof(PcgMultiColumn, active) &&
+                  offsetof(SpmvAmdPcgMultiColumn, done) == offsetof(PcgMultiColumn, done) &&
+                  offsetof(SpmvAmdPcgMultiColumn, iterations) == offsetof(PcgMultiColumn, iterations) &&
+                  offsetof(SpmvAmdPcgMultiColumn, converged) == offsetof(PcgMultiColumn, converged) &&
+                  offsetof(SpmvAmdPcgMultiColumn, breakdown) == offsetof(PcgMultiColumn, breakdown) &&
+                  offsetof(SpmvAmdPcgMultiColumn, skip_update) == offsetof(PcgMultiColumn, skip_update),
+              "lab.h's column record is the device record, field for field");
+
+namespace {
+bool stage_fail(const char* stage, const char* what) {
+    fprintf(stderr, "[PCG-MULTI] stage '%s': %s: refused\n", stage ? stage : "(null)", what);
+    return false;
+}
+// a pointer the stage needs, aligned to `align` bytes (16: a block vector the vector kernels access in 16-byte pairs)
+bool stage_pointer(const char* stage, const char* name, const void* p, int align) {
+    char what[64];
+    if (p == nullptr) {
+        snprintf(what, sizeof what, "%s is null", name);
+        return stage_fail(stage, what);
+    }
+    if (((uintptr_t)p & (uintptr_t)(align - 1)) != 0) {
+        snprintf(what, sizeof what, "%s is not %d-byte aligned", name, align);
+        return stage_fail(stage, what);
+    }
+    return true;
+}
+}  // namespace
+
+extern "C" int spmv_amd_pcg_multi_stage(const char* stage, const char* kind, int k, SpmvAmdPcgMultiStageArgs* a) {
+    // argument checks: all before the first HIP call
+    int st;
+    if (stage == nullptr) return stage_fail(stage, "no stage named (init, update_r, update_xp, cheb_step, reduce)"), 1;
+    if (!strcmp(stage, "init")) st = kStageInit;
+    else if (!strcmp(stage, "update_r")) st = kStageUpdateR;
+    else if (!strcmp(stage, "update_xp")) st = kStageUpdateXp;
+    else if (!strcmp(stage, "cheb_step")) st = kStageChebStep;
+    else if (!strcmp(stage, "reduce")) st = -1;
+    else return stage_fail(stage, "unknown stage (init, update_r, update_xp, cheb_step, reduce)"), 1;
+    if (k < 1 || k > kMaxRhs) return stage_fail(stage, "k is not 1 to 8"), 1;
+    if (a == nullptr) return stage_fail(stage, "null arguments"), 1;
+    int kd = kPlain;
+    if (st == -1) {
+        if (a->count < 1) return stage_fail(stage, "count < 1"), 1;
+        if (a->which < 0 || a->which > 4) return stage_fail(stage, "which is not 0 to 4"), 1;
+        if (a->hist_cap < 0) return stage_fail(stage, "hist_cap < 0"), 1;
+        if (!stage_pointer(stage, "partials", a->partials, 8) || !stage_pointer(stage, "cols", a->cols, 8)) return 1;
+        if (a->hist_cap > 0 && !stage_pointer(stage, "hist", a->hist, 8)) return 1;
+    } else {
+        if (kind == nullptr) return stage_fail(stage, "no preconditioner kind named (none, jacobi, chebyshev)"), 1;
+        if (!strcmp(kind, "none")) kd = kPlain;
+        else if (!strcmp(kind, "jacobi")) kd = kJac;
+        else if (!strcmp(kind, "chebyshev")) kd = kCheb;
+        else return stage_fail(stage, "unknown preconditioner kind (none, jacobi, chebyshev)"), 1;
+        if (st == kStageChebStep && kd != kCheb) return stage_fail(stage, "the stage belongs to kind chebyshev"), 1;
+        if (a->n < 1 || a->n > (size_t)INT_MAX) return stage_fail(stage, "n < 1 or beyond the solver's int rows"), 1;
+        if (kd != kPlain && !stage_pointer(stage, "dinv", a->dinv, 8)) return 1;
+        if (st != kStageInit && !stage_pointer(stage, "cols", a->cols, 8)) return 1;
+        if (st != kStageUpdateXp && (!stage_pointer(stage, "AP", a->AP, 16) || !stage_pointer(stage, "partials", a->partials, 8))) return 1;
+        if ((st != kStageUpdateXp || kd != kCheb) && !stage_pointer(stage, "R", a->R, 16)) return 1;
+        if ((st == kStageUpdateXp || (st == kStageInit && kd != kCheb)) && !stage_pointer(stage, "P", a->P, 16)) return 1;
+        if (st == kStageUpdateXp && !stage_pointer(stage, "X", a->X, 16)) return 1;
+        if (kd == kCheb && !stage_pointer(stage, "Z", a->Z, 16)) return 1;
+        if (kd == kCheb && st != kStageUpdateXp && !stage_pointer(stage, "D", a->D, 16)) return 1;
+    }
+
+    PcgMultiColumn* cols = reinterpret_cast<PcgMultiColumn*>(a->cols);
+    double* slices = nullptr;
+    if (st == -1) {
+        slices = device_alloc<double>(2 * (size_t)k * slices_for(a->count));
+        launch_reduce(k, a->partials, a->count, slices, a->which, a->tol, cols, a->hist, a->hist_cap);
+    } else {
+        VecArgs v{};
+        v.n = (long long)a->n, v.cols = cols, v.dinv = a->dinv, v.c0 = a->c0, v.g = a->g, v.h = a->h, v.last = a->last;
+        v.X = a->X, v.R = a->R, v.P = a->P, v.AP = a->AP, v.D = a->D, v.Z = a->Z, v.partials = a->partials;
+        v.count = (v.n + kBlock - 1) / kBlock;
+        launch_vector_stage(k, st, kd, v);
+        a->count = v.count;
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    device_release(slices);
+    return 0;
+}
+#endif  // SPMV_AMD_LAB

@@ -54,6 +54,9 @@ void chebyshev_coefficients(int degree, double lmin, double lmax, double* coef);
 // stencil_dim 2 / 3, not the 2-D / 3-D stencil operator (0: any of ours) -- said as "[PCG] <label>operator '<name>' is not <not_ours>"; used before init; not square
 // (left to a stencil creator's stricter test behind this). False: refused, said on stderr.
 bool creation_source(const SpmvOperator* op, const char* label, const char* not_ours, int stencil_dim, DiagonalSource* d);
+// What every entry point that takes (op, m) checks of the pair before any HIP call; d: the operator's storage view. False: refused,
+// said on stderr behind [PCG].
+bool precond_matches(const SpmvOperator* op, const SpmvAmdPrecond* m, const DiagonalSource& d);
 // term 0 from a residual that is only read: u = dinv r ; d = c0 u ; z = d (cheb_term0_kernel<2>, no partials)
 void launch_cheb_term0_apply(size_t n, const double* r, const double* dinv, double c0, double* d, double* z);
 

@@ -408,6 +408,39 @@ int spmv_amd_pcg_last_history(double* out, int cap);
 /* Releases the solver workspaces: the same as spmv_amd_cg_release_workspace(). Safe to call at any time. */
 void spmv_amd_pcg_release_workspace(void);
 
+/* ---- preconditioned CG for several right-hand sides (csrc/pcg_multi.hip) ----
+ * nrhs (1..8) INDEPENDENT preconditioned solves on one operator under one preconditioner of kind "none", "jacobi" (a from-diagonal one
+ * included) or "chebyshev": per column exactly the algebra, stopping rule and breakdown rule of spmv_amd_pcg_solve_device, with the
+ * arguments, statistics, timers and verbose semantics of spmv_amd_cg_solve_device_multi (B, X: host, nrhs vectors of mat->rows values
+ * one after the other, X in = x0; stats: nrhs records; verbose lines tagged [PCG-MULTI j]). Only the SpMM and dinv are shared: the
+ * operator must have the multi-RHS path ("stencil5-csr" in every variant, "stencil7-csr", "cusparse-csr").
+ * Per column j and iteration, element-wise with explicit fma() and one rounding per other operation:
+ *   Ap = A p (the SpMM: the single-vector path's bits); pAp = p.Ap; an unusable pAp (zero or not finite): alpha = 0, nothing is updated
+ *   and the column stops with converged = 0; else alpha = rz / pAp; r = fma(-alpha, Ap, r); ||r|| = sqrt(r.r), counted and recorded; the
+ *   strict test ||r|| / ||r0|| < tol; else z = M^-1 r ("none": r; "jacobi": dinv * r; "chebyshev": u = dinv * r; d = c0 * u; z = d, then
+ *   for s = 1..degree: w = A z; d = fma(g_s, dinv * fma(-1.0, w, r), h_s * d); z = z + d); an unusable r.z stops the column with
+ *   converged = 0; else beta = r.z / rz, rz = r.z; x = fma(alpha, p, x); p = fma(beta, p, z) unless the column stopped in this iteration.
+ * A dot product of column j is the sum of the ROUNDED products per row: 256 consecutive rows per partial (64-lane shuffle trees, then
+ * ((w0 + w1) + w2) + w3; p.Ap: the SpMM's own workgroups), 4096 partials per slice (thread t of 256 adds t, t + 256, ... in ascending
+ * order, then a 256-wide tree), the slice sums the same way. Every value of column j has the same bits whatever nrhs is and whatever
+ * slot the column sits in, and with kind "none" a solve without a breakdown has the bits of spmv_amd_cg_solve_device_multi. (The
+ * single-RHS spmv_amd_pcg_solve_device sums in another shape: the two agree to rounding, not bit for bit.)
+ * A column that has converged or broken down is frozen: from the next iteration on nothing changes a bit of its x, history or count.
+ * Refused before the first HIP call, with a [PCG-MULTI] sentence on stderr and a non-zero return: nrhs outside 1..8, a NULL
+ * argument, max_iters < 0, an operator without the multi-RHS path or used before init, a system that is not square or not of
+ * mat->rows rows, kind "multigrid" (its hierarchy holds single vectors), a preconditioner of another size, of another operator or
+ * from before the operator's last init or free. The workspace (X, R, P, AP; "chebyshev": D and Z too; partials, column records,
+ * histories) is sized against the device's free memory first and refused with a sentence if it does not fit; it is kept between
+ * calls and released with the other CG workspaces (an operator's free(), spmv_amd_cg_release_workspace(),
+ * spmv_amd_pcg_release_workspace()). */
+int spmv_amd_pcg_solve_device_multi(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, int nrhs, const double* B, double* X,
+                                    const CGConfig* config, CGStats* stats);
+/* Residual history of column `rhs` of the last batched preconditioned solve; -1 if there is no such column. */
+int spmv_amd_pcg_last_history_multi(int rhs, double* out, int cap);
+/* Device bytes the batched preconditioned solver's workspace holds now: 0 once it is released or before the first such solve. No
+ * HIP call. */
+size_t spmv_amd_pcg_multi_workspace_bytes(void);
+
 /* ---- multi-GPU communicator ---- */
 typedef struct SpmvAmdComm SpmvAmdComm;
 

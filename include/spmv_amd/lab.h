@@ -273,6 +273,66 @@ typedef struct SpmvAmdCgMultiStageArgs {
  * 8-byte aligned, xcd_run < 0, an operator that is unknown, not initialised or without a multi-RHS path. Returns 0 otherwise. */
 int spmv_amd_cg_multi_stage(const char* stage, int k, SpmvAmdCgMultiStageArgs* a);
 
+/* Per-column state of a batched preconditioned solve (csrc/multi_rhs.hpp keeps the same record on the device, one per column):
+ * SpmvAmdPcgScalars per column, with the batched loop's two flags. */
+typedef struct SpmvAmdPcgMultiColumn {
+    double rz;        /* r.z of the column's current residual */
+    double pAp, alpha, beta;
+    double b_norm;    /* ||r0|| */
+    double residual;  /* ||r_k|| */
+    int active;       /* the column takes part in the current iteration (step 1: !done) */
+    int done;         /* converged or broken down: frozen from the next iteration on */
+    int iterations;
+    int converged;    /* stopping test met */
+    int breakdown;    /* pAp or r.z' zero or not finite: stopped, not converged */
+    int skip_update;  /* this iteration's pAp broke down: r and x stay as they are */
+    int pad[2];
+} SpmvAmdPcgMultiColumn;
+
+/* Device pointers and sizes of one spmv_amd_pcg_multi_stage call; a stage reads only the fields listed for it. Block vectors are
+ * row-interleaved, k columns: element (row, column j) at [row * k + j]. */
+typedef struct SpmvAmdPcgMultiStageArgs {
+    size_t n;                     /* the vector stages: rows */
+    double* X;                    /* update_xp: in and out */
+    double* R;                    /* init: in (b) and out (r0); update_r: in and out; cheb_step: in; update_xp ("none", "jacobi"): in */
+    double* P;                    /* init ("none", "jacobi"): out; update_xp: in and out */
+    double* AP;                   /* init, update_r: in; cheb_step: in, W = A Z */
+    double* D;                    /* kind "chebyshev": init, update_r: out; cheb_step: in and out */
+    double* Z;                    /* kind "chebyshev": init, update_r: out; cheb_step: in and out; update_xp: in */
+    const double* dinv;           /* kinds "jacobi" and "chebyshev": n values */
+    SpmvAmdPcgMultiColumn* cols;  /* update_r, update_xp, cheb_step: in; reduce: in and out -- k records, DEVICE memory */
+    double* partials;             /* init, update_r, cheb_step: out, value v of column j and workgroup g at [(v * k + j) * count + g]
+                                     (value 0 = r.r, value 1 = r.z: the buffer holds 2 * k * count doubles); reduce: in, value v of
+                                     the step's values at the same place */
+    long long count;              /* the vector stages: out, the workgroups of the launch = (n + 255) / 256; reduce: in */
+    int which;                    /* reduce: the scalar step, 0 = initial r.r / r.z (two values), 1 = p.Ap, 2 = r.r / r.z' (two values),
+                                     3 = r.r and the verdict alone, 4 = r.z' and beta alone (ONE value, at value 0's place) */
+    double tol;                   /* reduce, which = 2 or 3 */
+    double* hist;                 /* reduce: k histories of hist_cap doubles one after the other (may be null when hist_cap is 0) */
+    int hist_cap;
+    double c0;                    /* kind "chebyshev": init, update_r: term 0's coefficient */
+    double g, h;                  /* cheb_step: the step's coefficients */
+    int last;                     /* kind "chebyshev": init, update_r: term 0 is the whole polynomial (the r.z partials are written);
+                                     cheb_step: the last step (the r.z partials are written, as value 1) */
+} SpmvAmdPcgMultiStageArgs;
+
+/* The batched preconditioned solver's own kernels (csrc/pcg_multi.hip), one stage per call on the caller's device data -- the
+ * launches spmv_amd_pcg_solve_device_multi makes, through the functions it makes them with, for k = 1..8 columns. The model is
+ * spmv_amd_cg_multi_stage. Every call synchronises. kind: "none", "jacobi" or "chebyshev" ("reduce" does not look at it). stage:
+ *   "init"       R = R - AP (R holds b), z = M^-1 r as far as one pass goes ("none": r, "jacobi": dinv r -> P; "chebyshev": term 0
+ *                -> D and Z), the partials of r.r and (unless "chebyshev" without `last`) r.z; sets a->count
+ *   "update_r"   r = fma(-alpha, AP, r) for the columns with cols[j].active and without skip_update, z as above (kept in registers
+ *                for "none" / "jacobi"; D and Z of the active columns for "chebyshev"), the same partials; sets a->count
+ *   "cheb_step"  d = fma(g, dinv fma(-1, w, r), h d), z = z + d for the columns with cols[j].done == 0; `last`: the partials of r.z
+ *                as value 1; nothing at all once every column is done; sets a->count
+ *   "update_xp"  x = fma(alpha, p, x) for the active columns without skip_update, then p = fma(beta, p, z) for those not done
+ *   "reduce"     the sums of a->count partials of the step's one or two values per column, then the scalar step `which` on cols
+ * Refused before any HIP call, with a sentence on stderr and a non-zero return: an unknown stage or kind, "cheb_step" with another
+ * kind than "chebyshev", k outside 1..8, null arguments, n < 1, count < 1, which outside 0..4, hist_cap < 0, a null pointer the
+ * stage needs, a block vector that is not 16-byte aligned, dinv, cols, partials or hist that are not 8-byte aligned. Returns 0
+ * otherwise. */
+int spmv_amd_pcg_multi_stage(const char* stage, const char* kind, int k, SpmvAmdPcgMultiStageArgs* a);
+
 #ifdef __cplusplus
 }
 #endif
