@@ -13,6 +13,8 @@
 // Bytes per interior row and iteration, per system: (40 + 80 k) / k.
 // No run-ahead, no direction ring, no status protocol: that machinery (cg_slab.hip) buys microseconds per iteration of a
 // single solve; here an iteration is k times longer.
+// This file: the kernels, their launchers, the loop and the LAB build's stage hook. What surrounds the loop -- workspace, argument
+// checks, upload and download, histories, statistics, print-out -- is multi_solve.hpp, shared with pcg_multi.hip.
 #include <limits.h>
 #include <math.h>
 #include <stddef.h>
@@ -24,19 +26,21 @@
 #include "device_runtime.hpp"
 #include "multi_rhs.hpp"
 #include "multi_rhs_device.hpp"
+#include "multi_solve.hpp"
 #include "reduce_device.hpp"
-#include "solve_common.hpp"
 #include "stream_device.hpp"
-
+#ifdef SPMV_AMD_LAB
 #include "spmv_amd/lab.h"
+#endif
 
 using namespace spmv_amd;
 
 namespace {
 
-constexpr hipStream_t kStream = nullptr;  // default stream, shared with the operators
+constexpr const char* kTag = "CG-MULTI";
+constexpr const char* kOperandTag = "multi-rhs";  // nrhs and the operator: refused in the words of the operand entry points (spmm_kernels.hip)
 
-// load_row, store_row, block_partials, Flat, products_to_rows, multi_reduce_slices_kernel, slices_for: multi_rhs_device.hpp
+// load_row, store_row, block_partials, Flat, products_to_rows, multi_reduce_slices_kernel: multi_rhs_device.hpp
 
 // R = b - A x0 (R holds b on entry: axpby_kernel(1.0, b, -1.0, Ap), cg_solver.cu:48-54), P = R, partials of r.r.
 template <int K>
@@ -171,23 +175,15 @@ template <int K>
 void launch_vec(int which, long long n, const MultiColumn* cols, double* X, double* R, double* P, const double* AP, double* partials,
                 long long count) {
     const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
-    if (which == 0) hipLaunchKernelGGL((multi_init_residual_kernel<K>), grid, block, 0, kStream, n, AP, R, P, partials, count);
-    else if (which == 1) hipLaunchKernelGGL((multi_update_r_kernel<K>), grid, block, 0, kStream, n, cols, AP, R, partials, count);
-    else hipLaunchKernelGGL((multi_update_xp_kernel<K>), grid, block, 0, kStream, n, cols, R, P, X);
+    if (which == 0) hipLaunchKernelGGL((multi_init_residual_kernel<K>), grid, block, 0, kBatchStream, n, AP, R, P, partials, count);
+    else if (which == 1) hipLaunchKernelGGL((multi_update_r_kernel<K>), grid, block, 0, kBatchStream, n, cols, AP, R, partials, count);
+    else hipLaunchKernelGGL((multi_update_xp_kernel<K>), grid, block, 0, kBatchStream, n, cols, R, P, X);
 }
 
 void launch_vector_step(int k, int which, long long n, const MultiColumn* cols, double* X, double* R, double* P, const double* AP,
                         double* partials, long long count) {
-    switch (k) {
-        case 1: launch_vec<1>(which, n, cols, X, R, P, AP, partials, count); break;
-        case 2: launch_vec<2>(which, n, cols, X, R, P, AP, partials, count); break;
-        case 3: launch_vec<3>(which, n, cols, X, R, P, AP, partials, count); break;
-        case 4: launch_vec<4>(which, n, cols, X, R, P, AP, partials, count); break;
-        case 5: launch_vec<5>(which, n, cols, X, R, P, AP, partials, count); break;
-        case 6: launch_vec<6>(which, n, cols, X, R, P, AP, partials, count); break;
-        case 7: launch_vec<7>(which, n, cols, X, R, P, AP, partials, count); break;
-        default: launch_vec<8>(which, n, cols, X, R, P, AP, partials, count); break;
-    }
+    auto launch = [&](auto K) { launch_vec<decltype(K)::value>(which, n, cols, X, R, P, AP, partials, count); };
+    if (!dispatch_k(k, launch)) launch(std::integral_constant<int, kMaxRhs>{});
 }
 
 // The two reduction launches behind every dot product: k x slices_for(count) slice sums, then per column their sum and the
@@ -195,174 +191,26 @@ void launch_vector_step(int k, int which, long long n, const MultiColumn* cols, 
 void launch_reduce(int k, const double* partials, long long count, double* slices, int which, double tol, MultiColumn* cols, double* hist,
                    int hist_cap) {
     const int sc = slices_for(count);
-    hipLaunchKernelGGL(multi_reduce_slices_kernel, dim3((unsigned)sc, (unsigned)k), dim3(kBlock), 0, kStream, partials, count, sc, slices);
-    hipLaunchKernelGGL(multi_reduce_step_kernel, dim3((unsigned)k), dim3(kBlock), 0, kStream, slices, sc, which, tol, cols, hist, hist_cap);
+    hipLaunchKernelGGL(multi_reduce_slices_kernel, dim3((unsigned)sc, (unsigned)k), dim3(kBlock), 0, kBatchStream, partials, count, sc, slices);
+    hipLaunchKernelGGL(multi_reduce_step_kernel, dim3((unsigned)k), dim3(kBlock), 0, kBatchStream, slices, sc, which, tol, cols, hist, hist_cap);
 }
 
-// ---- workspace: kept between calls (like cg_solve_device's), released with it ----
-struct MultiWorkspace {
-    int n = 0, k = 0, device = -1;
-    double *X = nullptr, *R = nullptr, *P = nullptr, *AP = nullptr;
-    double* partials = nullptr;  // k x max(SpMM partials, vector partials)
-    double* slices = nullptr;    // k x slices of that
-    MultiColumn* cols = nullptr;
-    double* hist = nullptr;      // k x hist_cap
-    int hist_cap = 0;
-    long long partial_cap = 0;
-    void release() {
-        device_release(X);
-        device_release(R);
-        device_release(P);
-        device_release(AP);
-        device_release(partials);
-        device_release(slices);
-        device_release(cols);
-        device_release(hist);
-        n = k = 0, device = -1, hist_cap = 0, partial_cap = 0;
-    }
-};
-MultiWorkspace g_multi;
+BatchedWorkspace<MultiColumn> g_multi(1);           // one dot-product value per launch
 std::vector<std::vector<double>> g_multi_history;  // of the last batched solve, per column
 
-bool fail(const char* what) {
-    fprintf(stderr, "[CG-MULTI] %s\n", what);
-    return false;
-}
-
-// Allocates the workspace for (n, k, partial slots) if it is not there already (sized against the free memory first).
-bool ensure_workspace(int n, int k, int device, long long partial_cap, int hist_cap) {
-    MultiWorkspace& w = g_multi;
-    if (w.X != nullptr && (w.n != n || w.k != k || w.device != device || w.partial_cap < partial_cap)) w.release();
-    if (w.X == nullptr) {
-        const size_t vec = (size_t)n * k * sizeof(double);
-        const size_t need = 4 * vec + (size_t)k * partial_cap * sizeof(double) + (size_t)k * slices_for(partial_cap) * sizeof(double) +
-                            (size_t)k * hist_cap * sizeof(double) + ((size_t)64 << 20);
-        char what[48];
-        snprintf(what, sizeof what, "%d systems of %d rows", k, n);
-        if (!device_has_room(need, "CG-MULTI", what)) return false;
-        w.X = device_try_alloc<double>((size_t)n * k);
-        w.R = device_try_alloc<double>((size_t)n * k);
-        w.P = device_try_alloc<double>((size_t)n * k);
-        w.AP = device_try_alloc<double>((size_t)n * k);
-        w.partials = device_try_alloc<double>((size_t)k * partial_cap);
-        w.slices = device_try_alloc<double>((size_t)k * slices_for(partial_cap));
-        w.cols = device_try_alloc<MultiColumn>((size_t)k);
-        if (!w.X || !w.R || !w.P || !w.AP || !w.partials || !w.slices || !w.cols) {
-            w.release();
-            return fail("the workspace could not be allocated: refused");
-        }
-        w.n = n, w.k = k, w.device = device, w.partial_cap = partial_cap;
-    }
-    if (!grow_history(w.hist, w.hist_cap, hist_cap, (size_t)k)) return fail("the history could not be allocated: refused");
-    return true;
-}
-
-bool check_rhs(int nrhs) {
-    if (nrhs < 1 || nrhs > kMaxRhs) {
-        fprintf(stderr, "[multi-rhs] nrhs = %d: 1 to %d right-hand sides are supported\n", nrhs, kMaxRhs);
-        return false;
-    }
-    return true;
-}
-
-// The operator behind `op`, if it has a multi-RHS path and is initialised. Host state only (no HIP call).
-bool usable_operator(const SpmvOperator* op, MultiOperand* out) {
-    if (op == nullptr) return fail("null operator");
-    *out = multi_operand_of(op);
-    if (!out->has_multi) {
-        fprintf(stderr, "[multi-rhs] operator '%s' has no multi-RHS path (stencil5-csr and cusparse-csr have one)\n",
-                op->name ? op->name : "?");
-        return false;
-    }
-    if (!out->ready) {
-        fprintf(stderr, "[multi-rhs] operator '%s' used before init\n", op->name);
-        return false;
-    }
-    return true;
-}
+ColumnSummary summary_of(const MultiColumn& c) { return {c.iterations, c.done != 0, false, c.residual, c.b_norm, c.active != 0}; }
 
 }  // namespace
 
 namespace spmv_amd {
 void release_cg_multi_workspace_locked() { g_multi.release(); }
-
-size_t cg_multi_workspace_bytes_locked() {
-    const MultiWorkspace& w = g_multi;
-    if (w.X == nullptr) return 0;
-    return (4 * (size_t)w.n * w.k + (size_t)w.k * w.partial_cap + (size_t)w.k * slices_for(w.partial_cap) + (size_t)w.k * w.hist_cap) *
-               sizeof(double) +
-           (size_t)w.k * sizeof(MultiColumn);
-}
+size_t cg_multi_workspace_bytes_locked() { return g_multi.bytes(); }
 }  // namespace spmv_amd
-
-extern "C" int spmv_amd_spmm_device(const char* mode, int nrhs, const double* d_X, double* d_Y) {
-    if (mode == nullptr || !check_rhs(nrhs)) return 1;
-    if (d_X == nullptr || d_Y == nullptr) return fail("null block vector"), 1;
-    if ((((uintptr_t)d_X | (uintptr_t)d_Y) & 7) != 0) return fail("block vectors must be 8-byte aligned"), 1;
-    SpmvOperator* op = get_operator(mode);
-    if (op == nullptr) {
-        fprintf(stderr, "[multi-rhs] unknown operator '%s'\n", mode);
-        return 1;
-    }
-    MultiOperand o;
-    if (!usable_operator(op, &o)) return 1;
-    launch_spmm(o.plan, nrhs, d_X, d_Y, nullptr, kStream);
-    HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-extern "C" const char* spmv_amd_spmm_variant(const char* mode) {
-    SpmvOperator* op = get_operator(mode);
-    if (op == nullptr) return "unknown-operator";
-    const MultiOperand o = multi_operand_of(op);
-    if (!o.has_multi) return "none";
-    return o.ready ? o.plan.name : "uninitialised";
-}
-
-namespace {
-int move_block(int nrhs, size_t n, const double* src, double* dst, bool to_device) {
-    if (!check_rhs(nrhs)) return 1;
-    if (src == nullptr || dst == nullptr) return fail("null block vector"), 1;
-    if (n == 0) return 0;
-    double* staging = device_try_alloc<double>(n * nrhs);
-    if (staging == nullptr) return fail("no device memory for the staging copy"), 1;
-    if (to_device) {
-        upload(staging, src, n * nrhs);
-        launch_interleave(nrhs, n, staging, dst, kStream);
-    } else {
-        HIP_CHECK(hipStreamSynchronize(kStream));
-        launch_deinterleave(nrhs, n, src, staging, kStream);
-        HIP_CHECK(hipStreamSynchronize(kStream));
-        download(dst, staging, n * nrhs);
-    }
-    HIP_CHECK(hipStreamSynchronize(kStream));
-    device_release(staging);
-    return 0;
-}
-}  // namespace
-
-extern "C" int spmv_amd_block_to_device(int nrhs, size_t n, const double* host_columns, double* d_X) {
-    return move_block(nrhs, n, host_columns, d_X, true);
-}
-
-extern "C" int spmv_amd_block_to_host(int nrhs, size_t n, const double* d_X, double* host_columns) {
-    return move_block(nrhs, n, d_X, host_columns, false);
-}
 
 extern "C" int spmv_amd_cg_solve_device_multi(SpmvOperator* op, MatrixData* mat, int nrhs, const double* B, double* X,
                                               const CGConfig* config, CGStats* stats) {
-    // argument checks: all before the first HIP call
-    if (!check_rhs(nrhs)) return 1;
-    if (mat == nullptr || B == nullptr || X == nullptr || config == nullptr || stats == nullptr)
-        return fail("null argument"), 1;
     MultiOperand o;
-    if (!usable_operator(op, &o)) return 1;
-    if (o.plan.rows != o.plan.cols || mat->rows != o.plan.rows) {
-        fprintf(stderr, "[CG-MULTI] the operator holds a %d x %d matrix, mat->rows = %d: a square system of that size is required\n",
-                o.plan.rows, o.plan.cols, mat->rows);
-        return 1;
-    }
-    if (config->max_iters < 0) return fail("max_iters < 0"), 1;
+    if (!check_batched_system(kTag, kOperandTag, op, mat, nrhs, B, X, config, stats, &o)) return 1;  // before the first HIP call
     const int n = mat->rows, k = nrhs;
     const CGConfig cfg = *config;
 
@@ -371,79 +219,33 @@ extern "C" int spmv_amd_cg_solve_device_multi(SpmvOperator* op, MatrixData* mat,
     HIP_CHECK(hipGetDevice(&device));
     const long long vec_count = ((long long)n + kBlock - 1) / kBlock;
     const long long spmm_count = o.plan.blocks;
-    const long long partial_cap = vec_count > spmm_count ? vec_count : spmm_count;
-    if (!ensure_workspace(n, k, device, partial_cap, cfg.max_iters + 1)) return 1;
-    MultiWorkspace& w = g_multi;
+    BatchedWorkspace<MultiColumn>& w = g_multi;
+    if (!w.ensure(kTag, n, k, device, vec_count > spmm_count ? vec_count : spmm_count, cfg.max_iters + 1, false)) return 1;
+    load_block_system(w, k, n, B, X);
 
-    // B and x0 arrive as k columns one after the other: through AP (free until the first SpMM) into interleaved R and X
-    upload(w.AP, B, (size_t)n * k);
-    launch_interleave(k, (size_t)n, w.AP, w.R, kStream);
-    HIP_CHECK(hipStreamSynchronize(kStream));
-    upload(w.AP, X, (size_t)n * k);
-    launch_interleave(k, (size_t)n, w.AP, w.X, kStream);
-    HIP_CHECK(hipStreamSynchronize(kStream));
-
-    std::vector<MultiColumn> h_cols((size_t)k);
-    StageTimers T(cfg.enable_detailed_timers != 0, kStream);
+    std::vector<ColumnSummary> cols;
+    StageTimers T(cfg.enable_detailed_timers != 0, kBatchStream);
     auto reduce = [&](long long count, int which) {
         launch_reduce(k, w.partials, count, w.slices, which, cfg.tolerance, w.cols, w.hist, w.hist_cap);
     };
-    auto read_columns = [&] { download(h_cols.data(), w.cols, (size_t)k); };
 
-    T.total.begin(kStream);
-    T.run(&T.t_spmv, [&] { launch_spmm(o.plan, k, w.X, w.AP, nullptr, kStream); });
+    T.total.begin(kBatchStream);
+    T.run(&T.t_spmv, [&] { launch_spmm(o.plan, k, w.X, w.AP, nullptr, kBatchStream); });
     T.run(&T.t_blas, [&] { launch_vector_step(k, 0, n, w.cols, w.X, w.R, w.P, w.AP, w.partials, vec_count); });
     T.run(&T.t_red, [&] { reduce(vec_count, 0); });
-    read_columns();
-    if (cfg.verbose >= 1)
-        for (int j = 0; j < k; ++j) printf("[CG-MULTI %d] Initial residual: %e\n", j, h_cols[j].b_norm);
-    for (int it = 0; it < cfg.max_iters; ++it) {
-        bool any = false;
-        for (int j = 0; j < k; ++j) any = any || !h_cols[j].done;
-        if (!any) break;
-        T.run(&T.t_spmv, [&] { launch_spmm(o.plan, k, w.P, w.AP, w.partials, kStream); });
+    read_columns(w, k, summary_of, cols);
+    if (cfg.verbose >= 1) print_initial_residuals(kTag, cols, nullptr);
+    for (int it = 0; it < cfg.max_iters && any_column_running(cols); ++it) {
+        T.run(&T.t_spmv, [&] { launch_spmm(o.plan, k, w.P, w.AP, w.partials, kBatchStream); });
         T.run(&T.t_red, [&] { reduce(spmm_count, 1); });
         T.run(&T.t_blas, [&] { launch_vector_step(k, 1, n, w.cols, w.X, w.R, w.P, w.AP, w.partials, vec_count); });
         T.run(&T.t_red, [&] { reduce(vec_count, 2); });
         T.run(&T.t_blas, [&] { launch_vector_step(k, 2, n, w.cols, w.X, w.R, w.P, w.AP, w.partials, vec_count); });
-        read_columns();  // synchronises: the stopping test of every column
-        if (cfg.verbose >= 2)
-            for (int j = 0; j < k; ++j)
-                if (h_cols[j].active)
-                    printf("[CG-MULTI %d] Iter %3d: residual = %e (rel = %e)\n", j, h_cols[j].iterations, h_cols[j].residual,
-                           h_cols[j].residual / h_cols[j].b_norm);
+        read_columns(w, k, summary_of, cols);  // synchronises: the stopping test of every column
+        if (cfg.verbose >= 2) print_iteration(kTag, cols);
     }
-    T.total.end(kStream);
-    const double total_ms = T.total.elapsed_ms();
-    HIP_CHECK(hipGetLastError());
-
-    // the solution back as k columns one after the other (outside the timed region, as the upload)
-    launch_deinterleave(k, (size_t)n, w.X, w.AP, kStream);
-    HIP_CHECK(hipStreamSynchronize(kStream));
-    download(X, w.AP, (size_t)n * k);
-    // each column's recorded history only (the buffer may be longer: it keeps the largest max_iters seen)
-    g_multi_history.assign((size_t)k, std::vector<double>());
-    for (int j = 0; j < k; ++j) {
-        const MultiColumn& c = h_cols[j];
-        const int count = c.iterations + 1 < w.hist_cap ? c.iterations + 1 : w.hist_cap;
-        g_multi_history[j].resize((size_t)count);
-        download(g_multi_history[j].data(), w.hist + (size_t)j * w.hist_cap, (size_t)count);
-        CGStats& st = stats[j];
-        fill_device_stats(&st, c.iterations, c.done != 0, c.residual, c.b_norm, cfg, total_ms, T.t_spmv, T.t_blas, T.t_red);
-        solution_checksums(X + (size_t)j * n, n, &st.solution_sum, &st.solution_norm);
-        if (cfg.verbose >= 1) {
-            printf("[CG-MULTI %d] Converged: %s\n", j, st.converged ? "YES" : "NO");
-            printf("[CG-MULTI %d] Iterations: %d\n", j, st.iterations);
-            printf("[CG-MULTI %d] Final residual: %e\n", j, st.residual_norm);
-        }
-    }
-    if (cfg.verbose >= 1) {
-        printf("[CG-MULTI] %d systems, time breakdown (whole batch):\n", k);
-        printf("     Total:      %.3f ms\n", total_ms);
-        printf("     SpMV:       %.3f ms\n", T.t_spmv);
-        printf("     BLAS1:      %.3f ms\n", T.t_blas);
-        printf("     Reductions: %.3f ms\n", T.t_red);
-    }
+    T.total.end(kBatchStream);
+    finish_batched_solve(kTag, w, k, n, X, stats, cfg, T, T.total.elapsed_ms(), cols, g_multi_history);
     return 0;
 }
 
@@ -467,61 +269,43 @@ static_assert(sizeof(SpmvAmdMultiColumn) == sizeof(MultiColumn) && offsetof(Spmv
                   offsetof(SpmvAmdMultiColumn, iterations) == offsetof(MultiColumn, iterations),
               "lab.h's column record is the device record, field for field");
 
-namespace {
-bool stage_fail(const char* stage, const char* what) {
-    fprintf(stderr, "[CG-MULTI] stage '%s': %s: refused\n", stage ? stage : "(null)", what);
-    return false;
-}
-// a pointer the stage needs, aligned to `align` bytes (16: a block vector the vector kernels access in 16-byte pairs)
-bool stage_pointer(const char* stage, const char* name, const void* p, int align) {
-    char what[64];
-    if (p == nullptr) {
-        snprintf(what, sizeof what, "%s is null", name);
-        return stage_fail(stage, what);
-    }
-    if (((uintptr_t)p & (uintptr_t)(align - 1)) != 0) {
-        snprintf(what, sizeof what, "%s is not %d-byte aligned", name, align);
-        return stage_fail(stage, what);
-    }
-    return true;
-}
-}  // namespace
-
 extern "C" int spmv_amd_cg_multi_stage(const char* stage, int k, SpmvAmdCgMultiStageArgs* a) {
-    // argument checks: all before the first HIP call
+    // argument checks: all before the first HIP call. 16: a block vector the vector kernels access in 16-byte pairs
+    auto refuse = [&](const char* what) { return stage_fail(kTag, stage, what); };
+    auto pointer = [&](const char* name, const void* ptr, int align) { return stage_pointer(kTag, stage, name, ptr, align); };
     enum { kSpmm, kInit, kUpdateR, kUpdateXp, kReduce } st;
-    if (stage == nullptr) return stage_fail(stage, "no stage named (spmm, init, update_r, update_xp, reduce)"), 1;
+    if (stage == nullptr) return refuse("no stage named (spmm, init, update_r, update_xp, reduce)"), 1;
     if (!strcmp(stage, "spmm")) st = kSpmm;
     else if (!strcmp(stage, "init")) st = kInit;
     else if (!strcmp(stage, "update_r")) st = kUpdateR;
     else if (!strcmp(stage, "update_xp")) st = kUpdateXp;
     else if (!strcmp(stage, "reduce")) st = kReduce;
-    else return stage_fail(stage, "unknown stage (spmm, init, update_r, update_xp, reduce)"), 1;
-    if (k < 1 || k > kMaxRhs) return stage_fail(stage, "k is not 1 to 8"), 1;
-    if (a == nullptr) return stage_fail(stage, "null arguments"), 1;
+    else return refuse("unknown stage (spmm, init, update_r, update_xp, reduce)"), 1;
+    if (k < 1 || k > kMaxRhs) return refuse("k is not 1 to 8"), 1;
+    if (a == nullptr) return refuse("null arguments"), 1;
     MultiOperand o;
     if (st == kSpmm) {
-        if (!stage_pointer(stage, "X", a->X, 8) || !stage_pointer(stage, "AP", a->AP, 8)) return 1;
-        if (a->partials != nullptr && !stage_pointer(stage, "partials", a->partials, 8)) return 1;
-        if (a->xcd_run < 0) return stage_fail(stage, "xcd_run < 0"), 1;
-        if (a->mode == nullptr) return stage_fail(stage, "no operator named"), 1;
+        if (!pointer("X", a->X, 8) || !pointer("AP", a->AP, 8)) return 1;
+        if (a->partials != nullptr && !pointer("partials", a->partials, 8)) return 1;
+        if (a->xcd_run < 0) return refuse("xcd_run < 0"), 1;
+        if (a->mode == nullptr) return refuse("no operator named"), 1;
         SpmvOperator* op = get_operator(a->mode);
-        if (op == nullptr) return stage_fail(stage, "unknown operator"), 1;
-        if (!usable_operator(op, &o)) return stage_fail(stage, "the operator has no usable multi-RHS path"), 1;
+        if (op == nullptr) return refuse("unknown operator"), 1;
+        if (!usable_operator(kOperandTag, op, &o)) return refuse("the operator has no usable multi-RHS path"), 1;
     } else if (st == kReduce) {
-        if (a->count < 1) return stage_fail(stage, "count < 1"), 1;
-        if (a->which < 0 || a->which > 2) return stage_fail(stage, "which is not 0, 1 or 2"), 1;
-        if (a->hist_cap < 0) return stage_fail(stage, "hist_cap < 0"), 1;
-        if (a->which == 0 && a->hist_cap < 1) return stage_fail(stage, "hist_cap < 1 for step 0, which writes the first entry"), 1;
-        if (!stage_pointer(stage, "partials", a->partials, 8) || !stage_pointer(stage, "cols", a->cols, 8)) return 1;
-        if (a->hist_cap > 0 && !stage_pointer(stage, "hist", a->hist, 8)) return 1;
+        if (a->count < 1) return refuse("count < 1"), 1;
+        if (a->which < 0 || a->which > 2) return refuse("which is not 0, 1 or 2"), 1;
+        if (a->hist_cap < 0) return refuse("hist_cap < 0"), 1;
+        if (a->which == 0 && a->hist_cap < 1) return refuse("hist_cap < 1 for step 0, which writes the first entry"), 1;
+        if (!pointer("partials", a->partials, 8) || !pointer("cols", a->cols, 8)) return 1;
+        if (a->hist_cap > 0 && !pointer("hist", a->hist, 8)) return 1;
     } else {
-        if (a->n < 1 || a->n > (size_t)INT_MAX) return stage_fail(stage, "n < 1 or beyond the solver's int rows"), 1;
-        if (st != kInit && !stage_pointer(stage, "cols", a->cols, 8)) return 1;
-        if (st != kUpdateXp && (!stage_pointer(stage, "AP", a->AP, 16) || !stage_pointer(stage, "partials", a->partials, 8))) return 1;
-        if (!stage_pointer(stage, "R", a->R, 16)) return 1;
-        if (st != kUpdateR && !stage_pointer(stage, "P", a->P, 16)) return 1;
-        if (st == kUpdateXp && !stage_pointer(stage, "X", a->X, 16)) return 1;
+        if (a->n < 1 || a->n > (size_t)INT_MAX) return refuse("n < 1 or beyond the solver's int rows"), 1;
+        if (st != kInit && !pointer("cols", a->cols, 8)) return 1;
+        if (st != kUpdateXp && (!pointer("AP", a->AP, 16) || !pointer("partials", a->partials, 8))) return 1;
+        if (!pointer("R", a->R, 16)) return 1;
+        if (st != kUpdateR && !pointer("P", a->P, 16)) return 1;
+        if (st == kUpdateXp && !pointer("X", a->X, 16)) return 1;
     }
 
     MultiColumn* cols = reinterpret_cast<MultiColumn*>(a->cols);
@@ -529,7 +313,7 @@ extern "C" int spmv_amd_cg_multi_stage(const char* stage, int k, SpmvAmdCgMultiS
     if (st == kSpmm) {
         SpmmPlan plan = o.plan;
         if (a->xcd_run > 0) plan.xcd_run = a->xcd_run;
-        launch_spmm(plan, k, a->X, a->AP, a->partials, kStream);
+        launch_spmm(plan, k, a->X, a->AP, a->partials, kBatchStream);
         a->count = plan.blocks;
     } else if (st == kReduce) {
         slices = device_alloc<double>((size_t)k * slices_for(a->count));

@@ -1,5 +1,6 @@
 // multi_rhs.hpp -- one matrix, up to 8 right-hand sides: SpMM launchers (spmm_kernels.hip) and the records of the batched solvers
-// (cg_multi.hip: CG; pcg_multi.hip: preconditioned CG; their shared device helpers: multi_rhs_device.hpp).
+// (cg_multi.hip: CG; pcg_multi.hip: preconditioned CG; their shared device helpers: multi_rhs_device.hpp; their shared host
+// scaffold: multi_solve.hpp).
 // Every launcher enqueues on the given stream and returns; none synchronises.
 //
 // Block vectors are row-interleaved: element (row, column j) of a block of k columns lives at X[row * k + j]. One lane reads a
@@ -19,6 +20,11 @@
 namespace spmv_amd {
 
 constexpr int kMaxRhs = 8;
+
+// Every dot product of the batched solvers is summed in two stages: slices of kReduceSlice workgroup partials first
+// (multi_reduce_slices_kernel, multi_rhs_device.hpp), then the slice sums of each column.
+constexpr int kReduceSlice = 256 * 16;
+inline int slices_for(long long count) { return (int)((count + kReduceSlice - 1) / kReduceSlice); }
 
 // Which kernel family one multi-RHS product of an operator takes. The stencil kinds follow the operator's single-vector
 // variant (Stencil5Plan::variant), so a forced variant is honoured here too.
@@ -47,7 +53,7 @@ void launch_deinterleave(int k, size_t n, const double* src_interleaved, double*
 // The multi-RHS path of one of this library's operators (operators.hip). Host-side state only: no HIP call, so the argument
 // checks of the entry points built on it hold on a machine without a GPU.
 struct MultiOperand {
-    bool has_multi = false;  // "stencil5-csr" (and its alias "stencil5-halo-mgpu") and "cusparse-csr"; not the ELLPACK ones
+    bool has_multi = false;  // "stencil5-csr" (and its alias "stencil5-halo-mgpu"), "stencil7-csr" and "cusparse-csr"; not the ELLPACK ones
     bool ready = false;      // initialised
     SpmmPlan plan;
 };

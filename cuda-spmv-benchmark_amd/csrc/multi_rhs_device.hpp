@@ -1,12 +1,13 @@
 // multi_rhs_device.hpp -- the device helpers the batched solvers share (cg_multi.hip: batched CG; pcg_multi.hip: batched
 // preconditioned CG): a row's k values as 16-byte accesses, the flat row x column walk of a workgroup, the per-column dot
-// partials of a workgroup's 256 rows, and the first stage of the two-stage per-column sum with its geometry.
+// partials of a workgroup's 256 rows, and the first stage of the two-stage per-column sum (its geometry: slices_for, multi_rhs.hpp).
 // Everything sits in an unnamed namespace: each of the two translation units gets its own copy under the names it had when
 // cg_multi.hip held them alone, so moving them here changes no kernel's code or symbol (profiles/r25_pcg_multi_isa_identity.txt).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include "multi_rhs.hpp"
 #include "reduce_device.hpp"
 #include "stream_device.hpp"
 
@@ -15,7 +16,8 @@ namespace {
 using namespace spmv_amd;
 
 constexpr int kBlock = kReduceBlock;  // 256: the vector kernels' workgroup and the width of block_tree (reduce_device.hpp)
-constexpr int kSlice = kBlock * 16;  // partials one workgroup of the first reduction stage sums
+constexpr int kSlice = kReduceSlice;  // partials one workgroup of the first reduction stage sums: 16 per thread
+static_assert(kSlice == kBlock * 16, "slices_for (multi_rhs.hpp) and the first reduction stage agree on the slice");
 
 template <int K>
 __device__ __forceinline__ void load_row(const double* __restrict__ p, double (&o)[K]) {
@@ -98,7 +100,5 @@ __global__ __launch_bounds__(kBlock) void multi_reduce_slices_kernel(const doubl
     block_tree(acc, s);
     if (threadIdx.x == 0) slices[(long long)j * slice_count + sl] = s[0];
 }
-
-inline int slices_for(long long count) { return (int)((count + kSlice - 1) / kSlice); }
 
 }  // namespace

@@ -46,6 +46,7 @@
 
 #include "device_runtime.hpp"
 #include "multi_rhs.hpp"
+#include "multi_solve.hpp"
 #include "precond.hpp"
 #include "reduce_device.hpp"
 #include "solve_common.hpp"
@@ -1208,72 +1209,42 @@ static_assert(sizeof(SpmvAmdPcgScalars) == sizeof(PcgScalars) && offsetof(SpmvAm
                   offsetof(SpmvAmdPcgScalars, skip_update) == offsetof(PcgScalars, skip_update),
               "lab.h's scalar record is the device record, field for field");
 
-namespace {
-bool stage_fail(const char* stage, const char* what) {
-    fprintf(stderr, "[PCG] stage '%s': %s: refused\n", stage ? stage : "(null)", what);
-    return false;
-}
-// a vector the streaming kernels read or write in 16-byte pairs
-bool stage_vector(const char* stage, const char* name, const void* p) {
-    char what[64];
-    if (p == nullptr) {
-        snprintf(what, sizeof what, "%s is null", name);
-        return stage_fail(stage, what);
-    }
-    if (((uintptr_t)p & 15) != 0) {
-        snprintf(what, sizeof what, "%s is not 16-byte aligned", name);
-        return stage_fail(stage, what);
-    }
-    return true;
-}
-// an array of doubles read or written one at a time
-bool stage_array(const char* stage, const char* name, const void* p) {
-    char what[64];
-    if (p == nullptr) {
-        snprintf(what, sizeof what, "%s is null", name);
-        return stage_fail(stage, what);
-    }
-    if (((uintptr_t)p & 7) != 0) {
-        snprintf(what, sizeof what, "%s is not 8-byte aligned", name);
-        return stage_fail(stage, what);
-    }
-    return true;
-}
-}  // namespace
-
 extern "C" int spmv_amd_pcg_stage(const char* stage, const char* kind, SpmvAmdPcgStageArgs* a, SpmvAmdPcgScalars* scalars) {
-    // argument checks: all before the first HIP call
+    // argument checks: all before the first HIP call. 16: a vector the streaming kernels read or write in 16-byte pairs; 8: an array
+    // of doubles read or written one at a time
+    auto refuse = [&](const char* what) { return stage_fail("PCG", stage, what); };
+    auto pointer = [&](const char* name, const void* ptr, int align) { return stage_pointer("PCG", stage, name, ptr, align); };
     enum { kInit, kUpdateR, kUpdateXp, kReduce } st;
-    if (stage == nullptr) return stage_fail(stage, "no stage named (init, update_r, update_xp, reduce)"), 1;
+    if (stage == nullptr) return refuse("no stage named (init, update_r, update_xp, reduce)"), 1;
     if (!strcmp(stage, "init")) st = kInit;
     else if (!strcmp(stage, "update_r")) st = kUpdateR;
     else if (!strcmp(stage, "update_xp")) st = kUpdateXp;
     else if (!strcmp(stage, "reduce")) st = kReduce;
-    else return stage_fail(stage, "unknown stage (init, update_r, update_xp, reduce)"), 1;
-    if (a == nullptr) return stage_fail(stage, "null arguments"), 1;
+    else return refuse("unknown stage (init, update_r, update_xp, reduce)"), 1;
+    if (a == nullptr) return refuse("null arguments"), 1;
     bool jac = false;
     if (st != kReduce) {
         const int k = kind_of(kind);
-        if (k < 0) return stage_fail(stage, "unknown preconditioner kind (none, jacobi)"), 1;
+        if (k < 0) return refuse("unknown preconditioner kind (none, jacobi)"), 1;
         jac = k == kJacobi;
-        if (a->n < 1 || a->n > (size_t)INT_MAX) return stage_fail(stage, "n < 1 or beyond the solver's int rows"), 1;
-        if (jac && !stage_vector(stage, "dinv", a->dinv)) return 1;
+        if (a->n < 1 || a->n > (size_t)INT_MAX) return refuse("n < 1 or beyond the solver's int rows"), 1;
+        if (jac && !pointer("dinv", a->dinv, 16)) return 1;
     }
-    if (st != kInit && scalars == nullptr) return stage_fail(stage, "null scalar record"), 1;
+    if (st != kInit && scalars == nullptr) return refuse("null scalar record"), 1;
     if (st == kInit) {
-        if (!stage_vector(stage, "b", a->b) || !stage_vector(stage, "Ap", a->Ap) || !stage_vector(stage, "r", a->r) ||
-            !stage_vector(stage, "p", a->p) || !stage_array(stage, "partials", a->partials))
+        if (!pointer("b", a->b, 16) || !pointer("Ap", a->Ap, 16) || !pointer("r", a->r, 16) ||
+            !pointer("p", a->p, 16) || !pointer("partials", a->partials, 8))
             return 1;
     } else if (st == kUpdateR) {
-        if (!stage_vector(stage, "Ap", a->Ap) || !stage_vector(stage, "r", a->r) || !stage_array(stage, "partials", a->partials)) return 1;
+        if (!pointer("Ap", a->Ap, 16) || !pointer("r", a->r, 16) || !pointer("partials", a->partials, 8)) return 1;
     } else if (st == kUpdateXp) {
-        if (!stage_vector(stage, "r", a->r) || !stage_vector(stage, "p", a->p) || !stage_vector(stage, "x", a->x)) return 1;
+        if (!pointer("r", a->r, 16) || !pointer("p", a->p, 16) || !pointer("x", a->x, 16)) return 1;
     } else {
-        if (a->count < 1) return stage_fail(stage, "count < 1"), 1;
-        if (a->which < 0 || a->which > 2) return stage_fail(stage, "which is not 0, 1 or 2"), 1;
-        if (a->hist_cap < 0) return stage_fail(stage, "hist_cap < 0"), 1;
-        if (!stage_array(stage, "partials", a->partials)) return 1;
-        if (a->hist_cap > 0 && !stage_array(stage, "hist", a->hist)) return 1;
+        if (a->count < 1) return refuse("count < 1"), 1;
+        if (a->which < 0 || a->which > 2) return refuse("which is not 0, 1 or 2"), 1;
+        if (a->hist_cap < 0) return refuse("hist_cap < 0"), 1;
+        if (!pointer("partials", a->partials, 8)) return 1;
+        if (a->hist_cap > 0 && !pointer("hist", a->hist, 8)) return 1;
     }
 
     PcgScalars h{};

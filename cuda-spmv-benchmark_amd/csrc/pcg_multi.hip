@@ -22,6 +22,10 @@
 // reduction stages of the batched CG solver per value and column -- the same bits for a column whatever k is and whatever slot it
 // sits in. A kernel with two values sends them through ONE LDS product array, one after the other (16 KiB at k = 8, so LDS never
 // limits the 8 workgroups a CU holds; two arrays would be 32 KiB and 5 workgroups; the price is one more barrier per workgroup).
+//
+// This file: the kernels, their launchers, the loop, the preconditioner's checks and the LAB build's stage hook. What surrounds the
+// loop -- workspace, the other argument checks, upload and download, histories, statistics, print-out -- is multi_solve.hpp, shared
+// with cg_multi.hip.
 #include <limits.h>
 #include <math.h>
 #include <stddef.h>
@@ -33,9 +37,9 @@
 #include "device_runtime.hpp"
 #include "multi_rhs.hpp"
 #include "multi_rhs_device.hpp"
+#include "multi_solve.hpp"
 #include "precond.hpp"
 #include "reduce_device.hpp"
-#include "solve_common.hpp"
 #include "stream_device.hpp"
 #ifdef SPMV_AMD_LAB
 #include "spmv_amd/lab.h"
@@ -45,7 +49,7 @@ using namespace spmv_amd;
 
 namespace {
 
-constexpr hipStream_t kStream = nullptr;  // default stream, shared with the operators
+constexpr const char* kTag = "PCG-MULTI";
 
 // The kind as the kernels see it: what z is made of decides the loads.
 constexpr int kPlain = 0, kJac = 1, kCheb = 2;
@@ -374,13 +378,13 @@ template <int K, int kKind>
 void launch_vec_kind(int stage, const VecArgs& a) {
     const dim3 grid((unsigned)((a.n + kBlock - 1) / kBlock)), block(kBlock);
     if (stage == kStageInit)
-        hipLaunchKernelGGL((pcg_multi_init_kernel<K, kKind>), grid, block, 0, kStream, a.n, a.AP, a.dinv, a.c0, a.last, a.R, a.P, a.D, a.Z,
+        hipLaunchKernelGGL((pcg_multi_init_kernel<K, kKind>), grid, block, 0, kBatchStream, a.n, a.AP, a.dinv, a.c0, a.last, a.R, a.P, a.D, a.Z,
                            a.partials, a.count);
     else if (stage == kStageUpdateR)
-        hipLaunchKernelGGL((pcg_multi_update_r_kernel<K, kKind>), grid, block, 0, kStream, a.n, a.cols, a.AP, a.dinv, a.c0, a.last, a.R, a.D, a.Z,
+        hipLaunchKernelGGL((pcg_multi_update_r_kernel<K, kKind>), grid, block, 0, kBatchStream, a.n, a.cols, a.AP, a.dinv, a.c0, a.last, a.R, a.D, a.Z,
                            a.partials, a.count);
     else
-        hipLaunchKernelGGL((pcg_multi_update_xp_kernel<K, kKind>), grid, block, 0, kStream, a.n, a.cols, kKind == kCheb ? a.Z : a.R, a.dinv, a.P,
+        hipLaunchKernelGGL((pcg_multi_update_xp_kernel<K, kKind>), grid, block, 0, kBatchStream, a.n, a.cols, kKind == kCheb ? a.Z : a.R, a.dinv, a.P,
                            a.X);
 }
 
@@ -388,7 +392,7 @@ template <int K>
 void launch_vec(int stage, int kind, const VecArgs& a) {
     if (stage == kStageChebStep) {
         const dim3 grid((unsigned)((a.n + kBlock - 1) / kBlock)), block(kBlock);
-        hipLaunchKernelGGL((pcg_multi_cheb_step_kernel<K>), grid, block, 0, kStream, a.n, a.cols, a.AP, a.R, a.dinv, a.g, a.h, a.D, a.Z, a.last,
+        hipLaunchKernelGGL((pcg_multi_cheb_step_kernel<K>), grid, block, 0, kBatchStream, a.n, a.cols, a.AP, a.R, a.dinv, a.g, a.h, a.D, a.Z, a.last,
                            a.partials, a.count);
     } else if (kind == kCheb) {
         launch_vec_kind<K, kCheb>(stage, a);
@@ -401,16 +405,8 @@ void launch_vec(int stage, int kind, const VecArgs& a) {
 
 // kind: kPlain, kJac, kCheb. a.count = the workgroups of the launch.
 void launch_vector_stage(int k, int stage, int kind, const VecArgs& a) {
-    switch (k) {
-        case 1: launch_vec<1>(stage, kind, a); break;
-        case 2: launch_vec<2>(stage, kind, a); break;
-        case 3: launch_vec<3>(stage, kind, a); break;
-        case 4: launch_vec<4>(stage, kind, a); break;
-        case 5: launch_vec<5>(stage, kind, a); break;
-        case 6: launch_vec<6>(stage, kind, a); break;
-        case 7: launch_vec<7>(stage, kind, a); break;
-        default: launch_vec<8>(stage, kind, a); break;
-    }
+    auto launch = [&](auto K) { launch_vec<decltype(K)::value>(stage, kind, a); };
+    if (!dispatch_k(k, launch)) launch(std::integral_constant<int, kMaxRhs>{});
 }
 
 int values_of_step(int which) { return which == 0 || which == 2 ? 2 : 1; }
@@ -420,125 +416,37 @@ int values_of_step(int which) { return which == 0 || which == 2 ? 2 : 1; }
 void launch_reduce(int k, const double* partials, long long count, double* slices, int which, double tol, PcgMultiColumn* cols, double* hist,
                    int hist_cap) {
     const int sc = slices_for(count), nv = values_of_step(which);
-    hipLaunchKernelGGL(multi_reduce_slices_kernel, dim3((unsigned)sc, (unsigned)(nv * k)), dim3(kBlock), 0, kStream, partials, count, sc, slices);
-    hipLaunchKernelGGL(pcg_multi_step_kernel, dim3((unsigned)k), dim3(kBlock), 0, kStream, slices, sc, k, nv, which, tol, cols, hist, hist_cap);
+    hipLaunchKernelGGL(multi_reduce_slices_kernel, dim3((unsigned)sc, (unsigned)(nv * k)), dim3(kBlock), 0, kBatchStream, partials, count, sc, slices);
+    hipLaunchKernelGGL(pcg_multi_step_kernel, dim3((unsigned)k), dim3(kBlock), 0, kBatchStream, slices, sc, k, nv, which, tol, cols, hist, hist_cap);
 }
 
-// ---- workspace: kept between calls (like the other CG solvers'), released with them ----
-struct PcgMultiWorkspace {
-    int n = 0, k = 0, device = -1;
-    double *X = nullptr, *R = nullptr, *P = nullptr, *AP = nullptr;
-    double *D = nullptr, *Z = nullptr;  // kind "chebyshev" only
-    double* partials = nullptr;         // max(k x SpMM partials, 2 x k x vector partials)
-    double* slices = nullptr;           // 2 k x slices of max(SpMM partials, vector partials)
-    PcgMultiColumn* cols = nullptr;
-    double* hist = nullptr;  // k x hist_cap
-    int hist_cap = 0;
-    long long partial_cap = 0;  // per value and column
-    void release() {
-        device_release(X);
-        device_release(R);
-        device_release(P);
-        device_release(AP);
-        device_release(D);
-        device_release(Z);
-        device_release(partials);
-        device_release(slices);
-        device_release(cols);
-        device_release(hist);
-        n = k = 0, device = -1, hist_cap = 0, partial_cap = 0;
-    }
-};
-PcgMultiWorkspace g_ws;
+BatchedWorkspace<PcgMultiColumn> g_ws(2);    // two dot-product values per launch: r.r and r.z
 std::vector<std::vector<double>> g_history;  // of the last batched preconditioned solve, per column
 
-bool fail(const char* what) {
-    fprintf(stderr, "[PCG-MULTI] %s\n", what);
-    return false;
+ColumnSummary summary_of(const PcgMultiColumn& c) {
+    return {c.iterations, c.converged != 0, c.breakdown != 0, c.residual, c.b_norm, c.active != 0};
 }
 
-bool ensure_workspace(int n, int k, int device, long long partial_cap, int hist_cap, bool cheb) {
-    PcgMultiWorkspace& w = g_ws;
-    if (w.X != nullptr && (w.n != n || w.k != k || w.device != device || w.partial_cap < partial_cap)) w.release();
-    const size_t vec = (size_t)n * k * sizeof(double);
-    char what[64];
-    snprintf(what, sizeof what, "%d systems of %d rows%s", k, n, cheb ? " (chebyshev)" : "");
-    if (w.X == nullptr) {
-        const size_t need = (cheb ? 6 : 4) * vec + 2 * (size_t)k * partial_cap * sizeof(double) +
-                            2 * (size_t)k * slices_for(partial_cap) * sizeof(double) + (size_t)k * hist_cap * sizeof(double) + ((size_t)64 << 20);
-        if (!device_has_room(need, "PCG-MULTI", what)) return false;
-        w.X = device_try_alloc<double>((size_t)n * k);
-        w.R = device_try_alloc<double>((size_t)n * k);
-        w.P = device_try_alloc<double>((size_t)n * k);
-        w.AP = device_try_alloc<double>((size_t)n * k);
-        w.partials = device_try_alloc<double>(2 * (size_t)k * partial_cap);
-        w.slices = device_try_alloc<double>(2 * (size_t)k * slices_for(partial_cap));
-        w.cols = device_try_alloc<PcgMultiColumn>((size_t)k);
-        if (!w.X || !w.R || !w.P || !w.AP || !w.partials || !w.slices || !w.cols) {
-            w.release();
-            return fail("the workspace could not be allocated: refused");
-        }
-        w.n = n, w.k = k, w.device = device, w.partial_cap = partial_cap;
-    }
-    if (cheb && w.D == nullptr) {
-        if (!device_has_room(2 * vec + ((size_t)64 << 20), "PCG-MULTI", what)) return false;
-        w.D = device_try_alloc<double>((size_t)n * k);
-        w.Z = device_try_alloc<double>((size_t)n * k);
-        if (!w.D || !w.Z) {
-            device_release(w.D);
-            device_release(w.Z);
-            return fail("the Chebyshev block vectors could not be allocated: refused");
-        }
-    }
-    if (!grow_history(w.hist, w.hist_cap, hist_cap, (size_t)k)) return fail("the history could not be allocated: refused");
-    return true;
-}
+bool fail(const char* what) { return batched_fail(kTag, what); }
 
 }  // namespace
 
 namespace spmv_amd {
 void release_pcg_multi_workspace_locked() { g_ws.release(); }
-
-size_t pcg_multi_workspace_bytes_locked() {
-    const PcgMultiWorkspace& w = g_ws;
-    if (w.X == nullptr) return 0;
-    return ((w.D != nullptr ? 6 : 4) * (size_t)w.n * w.k + 2 * (size_t)w.k * w.partial_cap + 2 * (size_t)w.k * slices_for(w.partial_cap) +
-            (size_t)w.k * w.hist_cap) *
-               sizeof(double) +
-           (size_t)w.k * sizeof(PcgMultiColumn);
-}
+size_t pcg_multi_workspace_bytes_locked() { return g_ws.bytes(); }
 }  // namespace spmv_amd
 
 extern "C" int spmv_amd_pcg_solve_device_multi(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, int nrhs, const double* B, double* X,
                                                const CGConfig* config, CGStats* stats) {
     // argument checks: all before the first HIP call
-    if (nrhs < 1 || nrhs > kMaxRhs) {
-        fprintf(stderr, "[PCG-MULTI] nrhs = %d: 1 to %d right-hand sides are supported\n", nrhs, kMaxRhs);
-        return 1;
-    }
-    if (op == nullptr || mat == nullptr || m == nullptr || B == nullptr || X == nullptr || config == nullptr || stats == nullptr)
-        return fail("null argument"), 1;
-    if (config->max_iters < 0) return fail("max_iters < 0"), 1;
-    const MultiOperand o = multi_operand_of(op);
-    if (!o.has_multi) {
-        fprintf(stderr, "[PCG-MULTI] operator '%s' has no multi-RHS path (stencil5-csr, stencil7-csr and cusparse-csr have one)\n",
-                op->name ? op->name : "?");
-        return 1;
-    }
-    if (!o.ready) {
-        fprintf(stderr, "[PCG-MULTI] operator '%s' used before init\n", op->name);
-        return 1;
-    }
-    if (o.plan.rows != o.plan.cols || mat->rows != o.plan.rows) {
-        fprintf(stderr, "[PCG-MULTI] the operator holds a %d x %d matrix, mat->rows = %d: a square system of that size is required\n",
-                o.plan.rows, o.plan.cols, mat->rows);
-        return 1;
-    }
+    if (op == nullptr || m == nullptr) return fail("null argument"), 1;  // the two pointers the shared checks do not name so
+    MultiOperand o;
+    if (!check_batched_system(kTag, kTag, op, mat, nrhs, B, X, config, stats, &o)) return 1;
     if (m->kind == kMultigrid)
         return fail("kind 'multigrid' keeps single vectors on every level of its hierarchy: not available for several right-hand sides, refused"), 1;
     if (m->kind != kNone && m->kind != kJacobi && m->kind != kChebyshev) return fail("unknown preconditioner kind: refused"), 1;
     if (m->n != mat->rows) {
-        fprintf(stderr, "[PCG-MULTI] the preconditioner is for %d rows, mat->rows = %d\n", m->n, mat->rows);
+        fprintf(stderr, "[%s] the preconditioner is for %d rows, mat->rows = %d\n", kTag, m->n, mat->rows);
         return 1;
     }
     if (!precond_matches(op, m, diagonal_source_of(op))) return fail("the preconditioner does not belong to this operator as it stands: refused"), 1;
@@ -552,21 +460,12 @@ extern "C" int spmv_amd_pcg_solve_device_multi(SpmvOperator* op, MatrixData* mat
     HIP_CHECK(hipGetDevice(&device));
     const long long vec_count = ((long long)n + kBlock - 1) / kBlock;
     const long long spmm_count = o.plan.blocks;
-    const long long partial_cap = vec_count > spmm_count ? vec_count : spmm_count;
-    if (!ensure_workspace(n, k, device, partial_cap, cfg.max_iters + 1, kind == kCheb)) return 1;
-    PcgMultiWorkspace& w = g_ws;
+    BatchedWorkspace<PcgMultiColumn>& w = g_ws;
+    if (!w.ensure(kTag, n, k, device, vec_count > spmm_count ? vec_count : spmm_count, cfg.max_iters + 1, kind == kCheb)) return 1;
+    load_block_system(w, k, n, B, X, true);  // the records as zeros: done = 0, so the first application's steps run
 
-    // B and x0 arrive as k columns one after the other: through AP (free until the first SpMM) into interleaved R and X
-    upload(w.AP, B, (size_t)n * k);
-    launch_interleave(k, (size_t)n, w.AP, w.R, kStream);
-    HIP_CHECK(hipStreamSynchronize(kStream));
-    upload(w.AP, X, (size_t)n * k);
-    launch_interleave(k, (size_t)n, w.AP, w.X, kStream);
-    HIP_CHECK(hipMemsetAsync(w.cols, 0, (size_t)k * sizeof(PcgMultiColumn), kStream));  // done = 0: the first application's steps run
-    HIP_CHECK(hipStreamSynchronize(kStream));
-
-    std::vector<PcgMultiColumn> h_cols((size_t)k);
-    StageTimers T(cfg.enable_detailed_timers != 0, kStream);
+    std::vector<ColumnSummary> cols;
+    StageTimers T(cfg.enable_detailed_timers != 0, kBatchStream);
     VecArgs a{};
     a.n = n, a.cols = w.cols, a.dinv = m->dinv, a.c0 = kind == kCheb ? m->coef[0] : 0.0, a.last = degree == 0 ? 1 : 0;
     a.X = w.X, a.R = w.R, a.P = w.P, a.AP = w.AP, a.D = w.D, a.Z = w.Z, a.partials = w.partials, a.count = vec_count;
@@ -574,7 +473,7 @@ extern "C" int spmv_amd_pcg_solve_device_multi(SpmvOperator* op, MatrixData* mat
     auto reduce = [&](const double* partials, long long count, int which) {
         T.run(&T.t_red, [&] { launch_reduce(k, partials, count, w.slices, which, cfg.tolerance, w.cols, w.hist, w.hist_cap); });
     };
-    auto spmm = [&](const double* in, double* partials) { T.run(&T.t_spmv, [&] { launch_spmm(o.plan, k, in, w.AP, partials, kStream); }); };
+    auto spmm = [&](const double* in, double* partials) { T.run(&T.t_spmv, [&] { launch_spmm(o.plan, k, in, w.AP, partials, kBatchStream); }); };
     // steps 1 .. degree behind a term 0 that left D and Z: W = A Z goes to the AP buffer, free between the r update and the next SpMM
     auto cheb_steps = [&] {
         for (int s = 1; s <= degree; ++s) {
@@ -584,24 +483,18 @@ extern "C" int spmv_amd_pcg_solve_device_multi(SpmvOperator* op, MatrixData* mat
             T.run(&T.t_blas, [&] { launch_vector_stage(k, kStageChebStep, kind, c); });
         }
     };
-    auto read_columns = [&] { download(h_cols.data(), w.cols, (size_t)k); };
 
-    T.total.begin(kStream);
+    T.total.begin(kBatchStream);
     spmm(w.X, nullptr);
     vec(kStageInit);
     if (kind == kCheb) {
         cheb_steps();
-        HIP_CHECK(hipMemcpyAsync(w.P, w.Z, (size_t)n * k * sizeof(double), hipMemcpyDeviceToDevice, kStream));  // p0 = z0
+        HIP_CHECK(hipMemcpyAsync(w.P, w.Z, (size_t)n * k * sizeof(double), hipMemcpyDeviceToDevice, kBatchStream));  // p0 = z0
     }
     reduce(w.partials, vec_count, 0);
-    read_columns();
-    if (cfg.verbose >= 1)
-        for (int j = 0; j < k; ++j)
-            printf("[PCG-MULTI %d] Initial residual: %e (preconditioner %s)\n", j, h_cols[j].b_norm, spmv_amd_precond_kind(m));
-    for (int it = 0; it < cfg.max_iters; ++it) {
-        bool any = false;
-        for (int j = 0; j < k; ++j) any = any || !h_cols[j].done;
-        if (!any) break;
+    read_columns(w, k, summary_of, cols);
+    if (cfg.verbose >= 1) print_initial_residuals(kTag, cols, spmv_amd_precond_kind(m));
+    for (int it = 0; it < cfg.max_iters && any_column_running(cols); ++it) {
         spmm(w.P, w.partials);
         reduce(w.partials, spmm_count, 1);
         vec(kStageUpdateR);
@@ -613,44 +506,11 @@ extern "C" int spmv_amd_pcg_solve_device_multi(SpmvOperator* op, MatrixData* mat
             reduce(w.partials, vec_count, 2);
         }
         vec(kStageUpdateXp);
-        read_columns();  // synchronises: the stopping test of every column
-        if (cfg.verbose >= 2)
-            for (int j = 0; j < k; ++j)
-                if (h_cols[j].active)
-                    printf("[PCG-MULTI %d] Iter %3d: residual = %e (rel = %e)\n", j, h_cols[j].iterations, h_cols[j].residual,
-                           h_cols[j].residual / h_cols[j].b_norm);
+        read_columns(w, k, summary_of, cols);  // synchronises: the stopping test of every column
+        if (cfg.verbose >= 2) print_iteration(kTag, cols);
     }
-    T.total.end(kStream);
-    const double total_ms = T.total.elapsed_ms();
-    HIP_CHECK(hipGetLastError());
-
-    // the solution back as k columns one after the other (outside the timed region, as the upload)
-    launch_deinterleave(k, (size_t)n, w.X, w.AP, kStream);
-    HIP_CHECK(hipStreamSynchronize(kStream));
-    download(X, w.AP, (size_t)n * k);
-    g_history.assign((size_t)k, std::vector<double>());
-    for (int j = 0; j < k; ++j) {
-        const PcgMultiColumn& c = h_cols[j];
-        const int count = c.iterations + 1 < w.hist_cap ? c.iterations + 1 : w.hist_cap;
-        g_history[j].resize((size_t)count);
-        download(g_history[j].data(), w.hist + (size_t)j * w.hist_cap, (size_t)count);
-        CGStats& st = stats[j];
-        fill_device_stats(&st, c.iterations, c.converged != 0, c.residual, c.b_norm, cfg, total_ms, T.t_spmv, T.t_blas, T.t_red);
-        solution_checksums(X + (size_t)j * n, n, &st.solution_sum, &st.solution_norm);
-        if (cfg.verbose >= 1) {
-            if (c.breakdown) printf("[PCG-MULTI %d] Breakdown in iteration %d (pAp or r.z zero or not finite)\n", j, c.iterations);
-            printf("[PCG-MULTI %d] Converged: %s\n", j, st.converged ? "YES" : "NO");
-            printf("[PCG-MULTI %d] Iterations: %d\n", j, st.iterations);
-            printf("[PCG-MULTI %d] Final residual: %e\n", j, st.residual_norm);
-        }
-    }
-    if (cfg.verbose >= 1) {
-        printf("[PCG-MULTI] %d systems, time breakdown (whole batch):\n", k);
-        printf("     Total:      %.3f ms\n", total_ms);
-        printf("     SpMV:       %.3f ms\n", T.t_spmv);
-        printf("     BLAS1:      %.3f ms\n", T.t_blas);
-        printf("     Reductions: %.3f ms\n", T.t_red);
-    }
+    T.total.end(kBatchStream);
+    finish_batched_solve(kTag, w, k, n, X, stats, cfg, T, T.total.elapsed_ms(), cols, g_history);
     return 0;
 }
 
@@ -680,61 +540,44 @@ static_assert(sizeof(SpmvAmdPcgMultiColumn) == sizeof(PcgMultiColumn) && offseto
                   offsetof(SpmvAmdPcgMultiColumn, skip_update) == offsetof(PcgMultiColumn, skip_update),
               "lab.h's column record is the device record, field for field");
 
-namespace {
-bool stage_fail(const char* stage, const char* what) {
-    fprintf(stderr, "[PCG-MULTI] stage '%s': %s: refused\n", stage ? stage : "(null)", what);
-    return false;
-}
-// a pointer the stage needs, aligned to `align` bytes (16: a block vector the vector kernels access in 16-byte pairs)
-bool stage_pointer(const char* stage, const char* name, const void* p, int align) {
-    char what[64];
-    if (p == nullptr) {
-        snprintf(what, sizeof what, "%s is null", name);
-        return stage_fail(stage, what);
-    }
-    if (((uintptr_t)p & (uintptr_t)(align - 1)) != 0) {
-        snprintf(what, sizeof what, "%s is not %d-byte aligned", name, align);
-        return stage_fail(stage, what);
-    }
-    return true;
-}
-}  // namespace
 
 extern "C" int spmv_amd_pcg_multi_stage(const char* stage, const char* kind, int k, SpmvAmdPcgMultiStageArgs* a) {
-    // argument checks: all before the first HIP call
+    // argument checks: all before the first HIP call. 16: a block vector the vector kernels access in 16-byte pairs
+    auto refuse = [&](const char* what) { return stage_fail(kTag, stage, what); };
+    auto pointer = [&](const char* name, const void* ptr, int align) { return stage_pointer(kTag, stage, name, ptr, align); };
     int st;
-    if (stage == nullptr) return stage_fail(stage, "no stage named (init, update_r, update_xp, cheb_step, reduce)"), 1;
+    if (stage == nullptr) return refuse("no stage named (init, update_r, update_xp, cheb_step, reduce)"), 1;
     if (!strcmp(stage, "init")) st = kStageInit;
     else if (!strcmp(stage, "update_r")) st = kStageUpdateR;
     else if (!strcmp(stage, "update_xp")) st = kStageUpdateXp;
     else if (!strcmp(stage, "cheb_step")) st = kStageChebStep;
     else if (!strcmp(stage, "reduce")) st = -1;
-    else return stage_fail(stage, "unknown stage (init, update_r, update_xp, cheb_step, reduce)"), 1;
-    if (k < 1 || k > kMaxRhs) return stage_fail(stage, "k is not 1 to 8"), 1;
-    if (a == nullptr) return stage_fail(stage, "null arguments"), 1;
+    else return refuse("unknown stage (init, update_r, update_xp, cheb_step, reduce)"), 1;
+    if (k < 1 || k > kMaxRhs) return refuse("k is not 1 to 8"), 1;
+    if (a == nullptr) return refuse("null arguments"), 1;
     int kd = kPlain;
     if (st == -1) {
-        if (a->count < 1) return stage_fail(stage, "count < 1"), 1;
-        if (a->which < 0 || a->which > 4) return stage_fail(stage, "which is not 0 to 4"), 1;
-        if (a->hist_cap < 0) return stage_fail(stage, "hist_cap < 0"), 1;
-        if (!stage_pointer(stage, "partials", a->partials, 8) || !stage_pointer(stage, "cols", a->cols, 8)) return 1;
-        if (a->hist_cap > 0 && !stage_pointer(stage, "hist", a->hist, 8)) return 1;
+        if (a->count < 1) return refuse("count < 1"), 1;
+        if (a->which < 0 || a->which > 4) return refuse("which is not 0 to 4"), 1;
+        if (a->hist_cap < 0) return refuse("hist_cap < 0"), 1;
+        if (!pointer("partials", a->partials, 8) || !pointer("cols", a->cols, 8)) return 1;
+        if (a->hist_cap > 0 && !pointer("hist", a->hist, 8)) return 1;
     } else {
-        if (kind == nullptr) return stage_fail(stage, "no preconditioner kind named (none, jacobi, chebyshev)"), 1;
+        if (kind == nullptr) return refuse("no preconditioner kind named (none, jacobi, chebyshev)"), 1;
         if (!strcmp(kind, "none")) kd = kPlain;
         else if (!strcmp(kind, "jacobi")) kd = kJac;
         else if (!strcmp(kind, "chebyshev")) kd = kCheb;
-        else return stage_fail(stage, "unknown preconditioner kind (none, jacobi, chebyshev)"), 1;
-        if (st == kStageChebStep && kd != kCheb) return stage_fail(stage, "the stage belongs to kind chebyshev"), 1;
-        if (a->n < 1 || a->n > (size_t)INT_MAX) return stage_fail(stage, "n < 1 or beyond the solver's int rows"), 1;
-        if (kd != kPlain && !stage_pointer(stage, "dinv", a->dinv, 8)) return 1;
-        if (st != kStageInit && !stage_pointer(stage, "cols", a->cols, 8)) return 1;
-        if (st != kStageUpdateXp && (!stage_pointer(stage, "AP", a->AP, 16) || !stage_pointer(stage, "partials", a->partials, 8))) return 1;
-        if ((st != kStageUpdateXp || kd != kCheb) && !stage_pointer(stage, "R", a->R, 16)) return 1;
-        if ((st == kStageUpdateXp || (st == kStageInit && kd != kCheb)) && !stage_pointer(stage, "P", a->P, 16)) return 1;
-        if (st == kStageUpdateXp && !stage_pointer(stage, "X", a->X, 16)) return 1;
-        if (kd == kCheb && !stage_pointer(stage, "Z", a->Z, 16)) return 1;
-        if (kd == kCheb && st != kStageUpdateXp && !stage_pointer(stage, "D", a->D, 16)) return 1;
+        else return refuse("unknown preconditioner kind (none, jacobi, chebyshev)"), 1;
+        if (st == kStageChebStep && kd != kCheb) return refuse("the stage belongs to kind chebyshev"), 1;
+        if (a->n < 1 || a->n > (size_t)INT_MAX) return refuse("n < 1 or beyond the solver's int rows"), 1;
+        if (kd != kPlain && !pointer("dinv", a->dinv, 8)) return 1;
+        if (st != kStageInit && !pointer("cols", a->cols, 8)) return 1;
+        if (st != kStageUpdateXp && (!pointer("AP", a->AP, 16) || !pointer("partials", a->partials, 8))) return 1;
+        if ((st != kStageUpdateXp || kd != kCheb) && !pointer("R", a->R, 16)) return 1;
+        if ((st == kStageUpdateXp || (st == kStageInit && kd != kCheb)) && !pointer("P", a->P, 16)) return 1;
+        if (st == kStageUpdateXp && !pointer("X", a->X, 16)) return 1;
+        if (kd == kCheb && !pointer("Z", a->Z, 16)) return 1;
+        if (kd == kCheb && st != kStageUpdateXp && !pointer("D", a->D, 16)) return 1;
     }
 
     PcgMultiColumn* cols = reinterpret_cast<PcgMultiColumn*>(a->cols);

@@ -1,6 +1,7 @@
 // solve_common.hpp -- the host side the CG entry points share around their loops (cg_single.hip, cg_slab_solve.hip, cg_multi.hip,
-// pcg.hip): checksums of the solution, the per-stage timers, the statistics rule of a device solve, the history hand-out and
-// the two halves of a workspace request. The loops, their kernels and their print-outs stay each solver's own.
+// pcg.hip, pcg_multi.hip): checksums of the solution, the per-stage timers, the statistics rule of a device solve, the history
+// hand-out and the two halves of a workspace request. The loops, their kernels and their print-outs stay each solver's own; what the
+// two batched solvers share beyond this (workspace, checks, upload, download, print-out) is multi_solve.hpp, built on this header.
 #pragma once
 
 #include <math.h>

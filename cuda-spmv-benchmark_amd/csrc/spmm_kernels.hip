@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "multi_rhs.hpp"
+#include "multi_solve.hpp"
 #include "stencil_geometry.hpp"
 #include "stencil_row_device.hpp"
 #include "stream_device.hpp"
@@ -401,17 +402,7 @@ SpmmPlan plan_spmm(const SlabCsr& m, Stencil5Variant stencil_variant, bool csr_o
 
 void launch_spmm(const SpmmPlan& p, int k, const double* X, double* Y, double* d_partials, hipStream_t stream) {
     if (p.rows == 0 || p.blocks == 0) return;
-    switch (k) {
-        case 1: launch_k<1>(p, X, Y, d_partials, stream); break;
-        case 2: launch_k<2>(p, X, Y, d_partials, stream); break;
-        case 3: launch_k<3>(p, X, Y, d_partials, stream); break;
-        case 4: launch_k<4>(p, X, Y, d_partials, stream); break;
-        case 5: launch_k<5>(p, X, Y, d_partials, stream); break;
-        case 6: launch_k<6>(p, X, Y, d_partials, stream); break;
-        case 7: launch_k<7>(p, X, Y, d_partials, stream); break;
-        case 8: launch_k<8>(p, X, Y, d_partials, stream); break;
-        default: break;
-    }
+    dispatch_k(k, [&](auto K) { launch_k<decltype(K)::value>(p, X, Y, d_partials, stream); });  // k outside 1..8: nothing
 }
 
 void launch_interleave(int k, size_t n, const double* src_columns, double* dst_interleaved, hipStream_t stream) {
@@ -429,3 +420,65 @@ void launch_deinterleave(int k, size_t n, const double* src_interleaved, double*
 }
 
 }  // namespace spmv_amd
+
+// ---- the operand entry points (include/spmv_amd/api.h): one SpMM on caller data, block vectors to and from the device ----
+using namespace spmv_amd;
+
+namespace {
+constexpr const char* kOperandTag = "multi-rhs";
+bool fail(const char* what) { return batched_fail("CG-MULTI", what); }  // the tag these sentences have had since cg_multi.hip held them
+}  // namespace
+
+extern "C" int spmv_amd_spmm_device(const char* mode, int nrhs, const double* d_X, double* d_Y) {
+    if (mode == nullptr || !check_rhs(kOperandTag, nrhs)) return 1;
+    if (d_X == nullptr || d_Y == nullptr) return fail("null block vector"), 1;
+    if ((((uintptr_t)d_X | (uintptr_t)d_Y) & 7) != 0) return fail("block vectors must be 8-byte aligned"), 1;
+    SpmvOperator* op = get_operator(mode);
+    if (op == nullptr) {
+        fprintf(stderr, "[multi-rhs] unknown operator '%s'\n", mode);
+        return 1;
+    }
+    MultiOperand o;
+    if (!usable_operator(kOperandTag, op, &o)) return 1;
+    launch_spmm(o.plan, nrhs, d_X, d_Y, nullptr, kBatchStream);
+    HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" const char* spmv_amd_spmm_variant(const char* mode) {
+    SpmvOperator* op = get_operator(mode);
+    if (op == nullptr) return "unknown-operator";
+    const MultiOperand o = multi_operand_of(op);
+    if (!o.has_multi) return "none";
+    return o.ready ? o.plan.name : "uninitialised";
+}
+
+namespace {
+int move_block(int nrhs, size_t n, const double* src, double* dst, bool to_device) {
+    if (!check_rhs(kOperandTag, nrhs)) return 1;
+    if (src == nullptr || dst == nullptr) return fail("null block vector"), 1;
+    if (n == 0) return 0;
+    double* staging = device_try_alloc<double>(n * nrhs);
+    if (staging == nullptr) return fail("no device memory for the staging copy"), 1;
+    if (to_device) {
+        upload(staging, src, n * nrhs);
+        launch_interleave(nrhs, n, staging, dst, kBatchStream);
+    } else {
+        HIP_CHECK(hipStreamSynchronize(kBatchStream));
+        launch_deinterleave(nrhs, n, src, staging, kBatchStream);
+        HIP_CHECK(hipStreamSynchronize(kBatchStream));
+        download(dst, staging, n * nrhs);
+    }
+    HIP_CHECK(hipStreamSynchronize(kBatchStream));
+    device_release(staging);
+    return 0;
+}
+}  // namespace
+
+extern "C" int spmv_amd_block_to_device(int nrhs, size_t n, const double* host_columns, double* d_X) {
+    return move_block(nrhs, n, host_columns, d_X, true);
+}
+
+extern "C" int spmv_amd_block_to_host(int nrhs, size_t n, const double* d_X, double* host_columns) {
+    return move_block(nrhs, n, d_X, host_columns, false);
+}

@@ -22,7 +22,7 @@ from oracle import oracle as O
 STAGE_BLOCKS = 256   # kReduceStageBlocks
 SINGLE_MAX = 1024    # partials one workgroup sums alone (4 * kReduceBlock)
 LDS_TILE_COLS = 128  # kLdsTileCols
-MULTI_SLICE = 4096   # kSlice of csrc/cg_multi.hip
+MULTI_SLICE = 4096   # kReduceSlice of csrc/multi_rhs.hpp
 
 
 def _f64(a):

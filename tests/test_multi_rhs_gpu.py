@@ -2,6 +2,7 @@
 bit for bit, through every kernel variant of both operators that have the path; the batched CG (spmv_amd_cg_solve_device_multi)
 against oracle_cg on every column; the columns' independence (permutation, k, scaling: bit for bit); and the coexistence of the
 batched solver with cg_solve_device on one operator."""
+import ctypes
 import os
 
 import numpy as np
@@ -160,6 +161,88 @@ def test_cg_multi_max_iters_some_columns_converge(B, O, fresh_host_matrices):
 
 def stats_tuple(s):
     return (s.iterations, s.residual_norm, s.converged, s.solution_sum, s.solution_norm)
+
+
+def printed(capfd):
+    """What the library's printf calls wrote since the last call, as lines (C's stdout is flushed first: it is not a terminal here)."""
+    ctypes.CDLL(None).fflush(None)
+    return capfd.readouterr().out.splitlines()
+
+
+def expected_print_out(tag, hists, stats, verbose, initial_suffix="", breakdown=()):
+    """The whole print-out of a batched solve at `verbose`, from what the solve returned: the initial residuals, under verbose 2
+    one Iter line per iteration and column that took part in it, each column's verdict, then the time breakdown."""
+    k = len(hists)
+    lines = ["[%s %d] Initial residual: %e%s" % (tag, j, hists[j][0], initial_suffix) for j in range(k)]
+    if verbose >= 2:
+        for it in range(1, max(s.iterations for s in stats) + 1):
+            for j in range(k):
+                if it <= stats[j].iterations:
+                    rel = hists[j][it] / hists[j][0] if hists[j][0] != 0.0 else float("nan")
+                    lines.append("[%s %d] Iter %3d: residual = %e (rel = %e)" % (tag, j, it, hists[j][it], rel))
+    for j in range(k):
+        if j in breakdown:
+            lines.append("[%s %d] Breakdown in iteration %d (pAp or r.z zero or not finite)" % (tag, j, stats[j].iterations))
+        lines += ["[%s %d] Converged: %s" % (tag, j, "YES" if stats[j].converged else "NO"),
+                  "[%s %d] Iterations: %d" % (tag, j, stats[j].iterations),
+                  "[%s %d] Final residual: %e" % (tag, j, stats[j].residual_norm)]
+    t = stats[0]
+    return lines + ["[%s] %d systems, time breakdown (whole batch):" % (tag, k), "     Total:      %.3f ms" % t.time_total_ms,
+                    "     SpMV:       %.3f ms" % t.time_spmv_ms, "     BLAS1:      %.3f ms" % t.time_blas1_ms,
+                    "     Reductions: %.3f ms" % t.time_reductions_ms]
+
+
+def check_print_out(got, want):
+    """Line for line; 0 / 0 of a zero column prints as nan or -nan."""
+    assert [g.replace("-nan", "nan") for g in got] == want, "\n".join(got)
+
+
+def check_verbose_changes_nothing_else(silent, loud, verbose):
+    """x and the histories bit for bit; the statistics too, but for residual_norm of a column that did not converge, which is the
+    last residual under verbose 2 and ||r0|| else (the reference's rule, solve_common.hpp)."""
+    for j in range(len(silent[1])):
+        assert np.array_equal(loud[0][j], silent[0][j]) and np.array_equal(loud[1][j], silent[1][j]), j
+        if verbose < 2 or silent[2][j].converged or silent[2][j].iterations == 0:
+            assert stats_tuple(loud[2][j]) == stats_tuple(silent[2][j]), j
+        else:
+            assert stats_tuple(loud[2][j])[:1] + stats_tuple(loud[2][j])[2:] == stats_tuple(silent[2][j])[:1] + stats_tuple(silent[2][j])[2:], j
+            assert silent[2][j].residual_norm == silent[1][j][0] and loud[2][j].residual_norm == loud[1][j][-1], j
+
+
+def test_cg_multi_print_out_and_late_refusals(B, O, fresh_host_matrices, capfd):
+    """A 32 x 32 system with k = 3 (odd k: 8-byte accesses): the whole print-out of a solve under verbose 1, and under verbose 2
+    with max_iters = 5 (the eigenmode column takes part in one iteration, the others in five), line for line; printing changes no
+    bit of what the solve returns. Then max_iters < 0 on an initialised operator, and the refusal only such an operator reaches: a
+    system that is not of the operator's size."""
+    n = 32
+    N = n * n
+    m = B.HostMatrix(O.stencil5_coo(n), N, N, n)
+    op = B.Operator("stencil5-csr")
+    assert op.init(m) == 0
+    Bk = np.stack([np.ones(N), np.random.default_rng(32).standard_normal(N), eigenmode(n)])
+    X0 = np.zeros((3, N))
+    for verbose, kw in ((1, {}), (2, {"max_iters": 5})):
+        silent = B.cg_solve_multi(op, m, Bk, X0, **kw)
+        printed(capfd)
+        loud = B.cg_solve_multi(op, m, Bk, X0, verbose=verbose, **kw)
+        got = printed(capfd)
+        check_verbose_changes_nothing_else(silent, loud, verbose)
+        check_print_out(got, expected_print_out("CG-MULTI", loud[1], loud[2], verbose))
+        assert len([l for l in got if " Iter " in l]) == (0 if verbose == 1 else 5 + 5 + 1)
+        assert [s.converged for s in loud[2]] == ([1, 1, 1] if verbose == 1 else [0, 0, 1])
+    L = B._multi_lib()
+    stats = (B.CGStats * 3)()
+    X = X0.copy()
+    cfg = B.CGConfig(-1, 1e-6, 0, 0)
+    capfd.readouterr()
+    assert L.spmv_amd_cg_solve_device_multi(op.op, m.ptr, 3, Bk.ctypes.data, X.ctypes.data, ctypes.byref(cfg), stats) != 0
+    assert "[CG-MULTI] max_iters < 0" in capfd.readouterr().err
+    small = B.HostMatrix(np.zeros(0, dtype=B.ENTRY_DTYPE), N - 1, N - 1, -1)
+    with pytest.raises(RuntimeError):
+        B.cg_solve_multi(op, small, Bk, X0)
+    err = capfd.readouterr().err
+    assert "[CG-MULTI] the operator holds a %d x %d matrix, mat->rows = %d: a square system of that size is required" % (N, N, N - 1) in err
+    op.free()
 
 
 @pytest.mark.parametrize("n, mode", [(200, "stencil5-csr"), (512, "stencil5-csr"), (200, "cusparse-csr")])

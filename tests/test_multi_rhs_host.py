@@ -48,34 +48,47 @@ def test_the_stage_hook_is_a_lab_symbol_only(B, Blab):
 def _free_all(B):
     # free() of an operator that was never initialised touches no device memory (nothing to release): safe without a GPU, and
     # it makes "used before init" hold even when GPU tests ran earlier in the same process
-    for mode in ("stencil5-csr", "cusparse-csr", "ellpack"):
+    for mode in ("stencil5-csr", "stencil7-csr", "cusparse-csr", "ellpack"):
         B.Operator(mode).free()
 
 
-def test_spmm_argument_checks_refuse_without_touching_the_gpu(B):
+def test_spmm_argument_checks_refuse_without_touching_the_gpu(B, capfd):
+    """Each refusal of the operand entry points is non-zero and says why on stderr, under the tag it has always had: the number of
+    right-hand sides and the operator under [multi-rhs], the block vectors under [CG-MULTI]."""
     _free_all(B)
     L = B._multi_lib()
     buf = (C.c_double * 16)()
     p = C.cast(buf, C.c_void_p)
+
+    def refused(rc, tag, word):
+        err = capfd.readouterr().err
+        assert rc != 0 and tag in err and word in err, (tag, word, rc, err)
+
     for k in (0, -1, 9, 100):
-        assert L.spmv_amd_spmm_device(b"stencil5-csr", k, p, p) != 0
-    assert L.spmv_amd_spmm_device(b"stencil5-csr", 2, None, p) != 0
-    assert L.spmv_amd_spmm_device(b"stencil5-csr", 2, p, None) != 0
+        refused(L.spmv_amd_spmm_device(b"stencil5-csr", k, p, p), "[multi-rhs]", "right-hand sides")
+    refused(L.spmv_amd_spmm_device(b"stencil5-csr", 2, None, p), "[CG-MULTI]", "null block vector")
+    refused(L.spmv_amd_spmm_device(b"stencil5-csr", 2, p, None), "[CG-MULTI]", "null block vector")
     assert L.spmv_amd_spmm_device(None, 2, p, p) != 0
-    assert L.spmv_amd_spmm_device(b"no-such-operator", 2, p, p) != 0
-    assert L.spmv_amd_spmm_device(b"ellpack", 2, p, p) != 0            # no multi-RHS path
-    assert L.spmv_amd_spmm_device(b"stencil5-ellpack", 2, p, p) != 0
-    assert L.spmv_amd_spmm_device(b"stencil5-csr", 2, p, p) != 0       # used before init
-    assert L.spmv_amd_spmm_device(b"cusparse-csr", 1, p, p) != 0
-    assert L.spmv_amd_spmm_device(b"stencil5-csr", 2, C.c_void_p(p.value + 4), p) != 0  # misaligned
+    refused(L.spmv_amd_spmm_device(b"no-such-operator", 2, p, p), "[multi-rhs]", "unknown operator 'no-such-operator'")
+    refused(L.spmv_amd_spmm_device(b"ellpack", 2, p, p), "[multi-rhs]", "no multi-RHS path")
+    refused(L.spmv_amd_spmm_device(b"stencil5-ellpack", 2, p, p), "[multi-rhs]", "stencil5-csr, stencil7-csr and cusparse-csr have one")
+    refused(L.spmv_amd_spmm_device(b"stencil5-csr", 2, p, p), "[multi-rhs]", "used before init")
+    refused(L.spmv_amd_spmm_device(b"cusparse-csr", 1, p, p), "[multi-rhs]", "used before init")
+    refused(L.spmv_amd_spmm_device(b"stencil5-csr", 2, C.c_void_p(p.value + 4), p), "[CG-MULTI]", "8-byte aligned")
+    refused(L.spmv_amd_spmm_device(b"stencil5-csr", 2, p, C.c_void_p(p.value + 4)), "[CG-MULTI]", "8-byte aligned")
     assert L.spmv_amd_spmm_variant(b"ellpack") == b"none"
     assert L.spmv_amd_spmm_variant(b"stencil5-csr") == b"uninitialised"
     assert L.spmv_amd_spmm_variant(b"nope") == b"unknown-operator"
     assert L.spmv_amd_block_to_device(0, 4, p, p) != 0 and L.spmv_amd_block_to_device(9, 4, p, p) != 0
+    refused(1, "[multi-rhs]", "right-hand sides")
     assert L.spmv_amd_block_to_host(2, 4, None, p) != 0 and L.spmv_amd_block_to_host(2, 4, p, None) != 0
+    refused(1, "[CG-MULTI]", "null block vector")
 
 
-def test_cg_multi_argument_checks_refuse_without_touching_the_gpu(B):
+def test_cg_multi_argument_checks_refuse_without_touching_the_gpu(B, capfd):
+    """Each refusal is non-zero and says why on stderr: the number of right-hand sides and the operator under [multi-rhs], the rest
+    under [CG-MULTI]. max_iters < 0 is refused before the operator is looked at (the order of the batched solvers' shared checks,
+    csrc/multi_solve.hpp); tests/test_multi_rhs_gpu.py holds the same sentence on an initialised operator."""
     _free_all(B)
     L = B._multi_lib()
     n = 9
@@ -85,25 +98,30 @@ def test_cg_multi_argument_checks_refuse_without_touching_the_gpu(B):
     cfg = B.CGConfig(10, 1e-6, 0, 0)
     stats = (B.CGStats * 9)()
 
-    def call(op, k, mat=m.ptr, b=Bk.ctypes.data, x=X.ctypes.data, c=C.byref(cfg), s=stats):
-        return L.spmv_amd_cg_solve_device_multi(op, mat, k, b, x, c, s)
+    def refused(op, k, tag, word, mat=m.ptr, b=Bk.ctypes.data, x=X.ctypes.data, c=C.byref(cfg), s=stats):
+        rc = L.spmv_amd_cg_solve_device_multi(op, mat, k, b, x, c, s)
+        err = capfd.readouterr().err
+        assert rc != 0 and tag in err and word in err, (k, tag, word, rc, err)
 
     stencil = B.Operator("stencil5-csr").op
     for k in (0, 9, -3):
-        assert call(stencil, k) != 0
-    assert call(stencil, 2, mat=None) != 0
-    assert call(stencil, 2, b=None) != 0
-    assert call(stencil, 2, x=None) != 0
-    assert call(stencil, 2, c=None) != 0
-    assert call(stencil, 2, s=None) != 0
-    assert call(None, 2) != 0
+        refused(stencil, k, "[multi-rhs]", "right-hand sides")
+    refused(stencil, 2, "[CG-MULTI]", "null argument", mat=None)
+    refused(stencil, 2, "[CG-MULTI]", "null argument", b=None)
+    refused(stencil, 2, "[CG-MULTI]", "null argument", x=None)
+    refused(stencil, 2, "[CG-MULTI]", "null argument", c=None)
+    refused(stencil, 2, "[CG-MULTI]", "null argument", s=None)
+    refused(None, 2, "[CG-MULTI]", "null operator")
+    refused(stencil, 2, "[CG-MULTI]", "max_iters < 0", c=C.byref(B.CGConfig(-1, 1e-6, 0, 0)))
     for mode in ("ellpack", "stencil5-ellpack"):
-        assert call(B.Operator(mode).op, 2) != 0                         # no multi-RHS path
-    assert call(stencil, 2) != 0                                         # used before init
-    assert call(B.Operator("cusparse-csr").op, 1) != 0
+        refused(B.Operator(mode).op, 2, "[multi-rhs]", "no multi-RHS path")
+        refused(B.Operator(mode).op, 2, "[multi-rhs]", "'" + mode + "' has no multi-RHS path (stencil5-csr, stencil7-csr and cusparse-csr have one)")
+    refused(stencil, 2, "[multi-rhs]", "'stencil5-csr' used before init")
+    refused(B.Operator("stencil7-csr").op, 2, "[multi-rhs]", "'stencil7-csr' used before init")
+    refused(B.Operator("cusparse-csr").op, 1, "[multi-rhs]", "used before init")
     own = B.SpmvOperator()                                               # a caller's own vtable
     own.name = b"mine"
-    assert call(C.pointer(own), 2) != 0
+    refused(C.pointer(own), 2, "[multi-rhs]", "no multi-RHS path")
     with pytest.raises(RuntimeError):
         B.cg_solve_multi(B.Operator("stencil5-csr"), m, np.ones((2, n)), np.zeros((2, n)))
     # columns that no batched solve can have had; no workspace once the operators are freed

@@ -16,7 +16,8 @@ import pcg_restatement as P
 import stencil7 as S7
 from bitwise import same_bits
 from conftest import hist_err
-from test_multi_rhs_gpu import columns, eigenmode, stats_tuple
+from test_multi_rhs_gpu import (check_print_out, check_verbose_changes_nothing_else, columns, eigenmode, expected_print_out, printed,
+                                stats_tuple)
 
 pytestmark = pytest.mark.gpu
 
@@ -304,6 +305,34 @@ def test_a_mixed_batch_and_bad_columns(B, kind, degree):
                     assert len(hists[slot]) == len(hb), (what, k, slot)
                     for j, s in enumerate([s for s in range(k) if s != slot]):
                         assert same_bits(X[s], Xh[j]) and same_bits(hists[s], hh[j]) and stats_tuple(stats[s]) == stats_tuple(sh[j]), (what, k, slot, s)
+    finally:
+        pc.destroy()
+        op.free()
+
+
+# ---------------------------------------------------------------- the print-out
+def test_print_out_under_jacobi(B, O, capfd):
+    """A 32 x 32 system with k = 3 (odd k: 8-byte accesses) whose middle column has a zero right-hand side (p.Ap = r.z = 0: breakdown in
+    iteration 1): the whole print-out of a solve under verbose 1, and under verbose 2 with max_iters = 5, line for line -- the kind on
+    the initial lines, a Breakdown line for the zero column and for no other; printing changes no bit of what the solve returns."""
+    n = 32
+    N = n * n
+    op, m = open_operator(B, "stencil5-csr", None, O.stencil5_coo(n), N, n)
+    pc = B.Precond(op, "jacobi")
+    try:
+        Bk = np.stack([np.ones(N), np.zeros(N), np.random.default_rng(32).standard_normal(N)])
+        X0 = np.zeros((3, N))
+        for verbose, kw in ((1, {}), (2, {"max_iters": 5})):
+            silent = B.pcg_solve_multi(op, m, pc, Bk, X0, **kw)
+            printed(capfd)
+            loud = B.pcg_solve_multi(op, m, pc, Bk, X0, verbose=verbose, **kw)
+            got = printed(capfd)
+            check_verbose_changes_nothing_else(silent, loud, verbose)
+            check_print_out(got, expected_print_out("PCG-MULTI", loud[1], loud[2], verbose, " (preconditioner jacobi)", breakdown=(1,)))
+            assert [l for l in got if "Breakdown" in l] == ["[PCG-MULTI 1] Breakdown in iteration 1 (pAp or r.z zero or not finite)"]
+            assert len([l for l in got if " Iter " in l]) == (0 if verbose == 1 else 5 + 1 + 5)
+            assert [s.converged for s in loud[2]] == ([1, 0, 1] if verbose == 1 else [0, 0, 0])
+            assert [s.iterations for s in loud[2]][1] == 1 and len(loud[1][1]) == 2
     finally:
         pc.destroy()
         op.free()
