@@ -93,6 +93,12 @@ class MgStageArgs(C.Structure):
                 ("r", C.c_void_p), ("coarse", C.c_void_p), ("out_row_ptr", C.c_void_p), ("out_col_idx", C.c_void_p), ("out_values", C.c_void_p)]
 
 
+class MgMultiStageArgs(C.Structure):
+    """SpmvAmdMgMultiStageArgs (include/spmv_amd/lab.h): device pointers of one spmv_amd_mg_multi_stage call; n = the fine grid."""
+    _fields_ = [("n", C.c_int), ("row_ptr", C.c_void_p), ("col_idx", C.c_void_p), ("values", C.c_void_p), ("z", C.c_void_p),
+                ("r", C.c_void_p), ("coarse", C.c_void_p), ("d", C.c_void_p), ("dinv", C.c_void_p), ("c0", C.c_double), ("cols", C.c_void_p)]
+
+
 class MultiColumn(C.Structure):
     """SpmvAmdMultiColumn (include/spmv_amd/lab.h): the per-column state of a batched CG solve."""
     _fields_ = [("rr_old", C.c_double), ("pAp", C.c_double), ("alpha", C.c_double), ("beta", C.c_double), ("b_norm", C.c_double),
@@ -156,13 +162,14 @@ DECLARED_SYMBOLS = [
     "spmv_amd_precond_create_multigrid", "spmv_amd_precond_multigrid_info",
     "spmv_amd_precond_create_multigrid3d", "spmv_amd_precond_multigrid_dimension",
     "spmv_amd_pcg_solve_device_multi", "spmv_amd_pcg_last_history_multi", "spmv_amd_pcg_multi_workspace_bytes",
+    "spmv_amd_precond_create_multigrid_multi", "spmv_amd_precond_multigrid_max_rhs", "spmv_amd_precond_apply_device_multi",
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
 LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_cg_slab_block_map", "spmv_amd_cg_slab_slow_blocks",
                     "spmv_amd_cg_slab_direction_spmv", "spmv_amd_cg_slab_spmv_dot", "spmv_amd_cg_slab_initial_stage", "spmv_amd_cg_slab_first_stage", "spmv_amd_cg_slab_stored_b", "spmv_amd_cg_slab_update_r_stage", "spmv_amd_cg_slab_ap_form", "spmv_amd_cg_slab_update_r_from_stage", "spmv_amd_cg_slab_first_recompute_form", "spmv_amd_pcg_stage",
                     "spmv_amd_pcg_last_step_launches", "spmv_amd_cg_multi_stage",
                     "spmv_amd_pcg_last_multigrid_cycles", "spmv_amd_precond_multigrid_level_csr", "spmv_amd_mg_stage",
-                    "spmv_amd_pcg_multi_stage"]
+                    "spmv_amd_pcg_multi_stage", "spmv_amd_mg_multi_stage"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
 DECLARED_CXX_SYMBOLS = [
     "SPMV_CSR", "SPMV_STENCIL5_CSR", "SPMV_STENCIL7_CSR", "SPMV_STENCIL_HALO_MGPU", "SPMV_ELLPACK", "SPMV_STENCIL5_ELLPACK",
@@ -698,6 +705,11 @@ def _pcg_lib():
         L.spmv_amd_pcg_last_history_multi.argtypes = [C.c_int, C.c_void_p, C.c_int]
         L.spmv_amd_pcg_multi_workspace_bytes.argtypes = []
         L.spmv_amd_pcg_multi_workspace_bytes.restype = C.c_size_t
+        L.spmv_amd_precond_create_multigrid_multi.argtypes = [C.POINTER(SpmvOperator), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.spmv_amd_precond_create_multigrid_multi.restype = C.c_void_p
+        L.spmv_amd_precond_multigrid_max_rhs.argtypes = [C.c_void_p]
+        L.spmv_amd_precond_multigrid_max_rhs.restype = C.c_int
+        L.spmv_amd_precond_apply_device_multi.argtypes = [C.POINTER(SpmvOperator), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L._pcg_sigs = True
     return L
 
@@ -766,6 +778,21 @@ class Precond:
             raise err
         return cls(_handle=h, _n=op.rows)
 
+    @classmethod
+    def multigrid_multi(cls, op, smoother_degree=1, max_levels=0, max_rhs=8):
+        """spmv_amd_precond_create_multigrid_multi (stencil5-csr only): the hierarchy with block vectors of max_rhs columns."""
+        bad = C.c_int(-2)
+        h = _pcg_lib().spmv_amd_precond_create_multigrid_multi(op.op, smoother_degree, max_levels, max_rhs, C.byref(bad))
+        if not h:
+            err = ValueError(f"precond_create_multigrid_multi({op.name}, {smoother_degree}, {max_levels}, {max_rhs}) refused, bad_row = {bad.value}")
+            err.bad_row = bad.value
+            raise err
+        return cls(_handle=h, _n=op.rows)
+
+    def multigrid_max_rhs(self):
+        """The columns a multigrid hierarchy's block vectors hold; 0 for a single-vector hierarchy or another kind."""
+        return _pcg_lib().spmv_amd_precond_multigrid_max_rhs(self.handle)
+
     def multigrid_dimension(self):
         """2 or 3 for a multigrid preconditioner, 0 for another kind."""
         return _pcg_lib().spmv_amd_precond_multigrid_dimension(self.handle)
@@ -810,6 +837,11 @@ class Precond:
         if _pcg_lib().spmv_amd_precond_apply_device(op.op, self.handle, r_ptr, z_ptr, C.byref(rz)) != 0:
             raise RuntimeError("precond_apply_device refused")
         return rz.value
+
+    def apply_device_multi(self, op, k, R_ptr, Z_ptr):
+        """spmv_amd_precond_apply_device_multi on device pointers of k interleaved columns (raises RuntimeError on a refusal)."""
+        if _pcg_lib().spmv_amd_precond_apply_device_multi(op.op, self.handle, int(k), R_ptr, Z_ptr) != 0:
+            raise RuntimeError("precond_apply_device_multi refused")
 
     def inverse_diagonal(self):
         out = np.empty(self.n, dtype=np.float64)
@@ -873,6 +905,14 @@ def mg_stage(stage, args):
     if not is_lab():
         raise RuntimeError("the multigrid stages exist in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
     return lib().spmv_amd_mg_stage(stage if stage is None else stage.encode(), args)
+
+
+def mg_multi_stage(stage, k, args):
+    """spmv_amd_mg_multi_stage (LAB build only; include/spmv_amd/lab.h): one launch of the batched multigrid cycle on the caller's
+    device data `args` (MgMultiStageArgs) points to; returns its return code (0, or non-zero for a refusal)."""
+    if not is_lab():
+        raise RuntimeError("the batched multigrid stages exist in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+    return lib().spmv_amd_mg_multi_stage(stage if stage is None else stage.encode(), int(k), None if args is None else C.byref(args))
 
 
 def pcg_stage(stage, kind, args, scalars=None):

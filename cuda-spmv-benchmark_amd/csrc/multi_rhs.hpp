@@ -97,6 +97,12 @@ struct PcgMultiColumn {
     int skip_update;  // this iteration's pAp broke down: r and x stay as they are
     int pad[2];
 };
+// pcg_multi.hip's Chebyshev step kernel (k = 1..8 columns, on the default stream) behind a SpMM that wrote W = A Z, for the callers
+// outside that file (the batched multigrid cycle and the block application, multigrid_multi.hip): on the columns with done == 0,
+// d = fma(g, dinv * fma(-1, w, r), h * d) ; z = z + d. last: the partials of r.z to partials[(k + j) * count + workgroup]; count =
+// the launch's workgroups, (n + 255) / 256. Nothing is read or written once every column is done.
+void launch_pcg_multi_cheb_step(int k, long long n, const PcgMultiColumn* cols, const double* W, const double* R, const double* dinv, double g,
+                                double h, double* D, double* Z, int last, double* partials, long long count);
 // The batched preconditioned solver's workspace (pcg_multi.hip), released and counted like the batched CG solver's; the caller
 // holds the workspace lock.
 void release_pcg_multi_workspace_locked();

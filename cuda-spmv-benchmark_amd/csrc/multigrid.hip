@@ -29,7 +29,9 @@
 
 #include <vector>
 
+#include "multi_rhs.hpp"
 #include "multigrid3d.hpp"
+#include "multigrid_device.hpp"
 #include "precond.hpp"
 #include "stencil_geometry.hpp"
 #include "stencil_row_device.hpp"
@@ -143,12 +145,7 @@ __device__ __forceinline__ double residual_off_tile(const SlabCsr& m, const doub
     return fma(-1.0, sum, r[row]);
 }
 
-// the row sum at column j from the strip slots of that row (v = strip + 5 (j - j0)), through stencil5_row's chains
-__device__ __forceinline__ double strip_row(const double* __restrict__ v, int j, int n, double xw, double xc, double xe, double xn, double xs) {
-    if (j > 0 && j < n - 1) return stencil5_row(j, n, v[1], xw, v[2], xc, v[3], xe, v[0], xn, v[4], xs);  // [N,W,C,E,S]
-    if (j == 0) return stencil5_row(j, n, 0.0, xw, v[2], xc, v[3], xe, v[1], xn, v[4], xs);                // [N,C,E,S] at 1..4
-    return stencil5_row(j, n, v[1], xw, v[2], xc, 0.0, xe, v[0], xn, v[3], xs);                            // [N,W,C,S]
-}
+// strip_row (multigrid_device.hpp): the row sum at column j from the strip slots of that row, through stencil5_row's chains
 
 __global__ __launch_bounds__(kWave) void residual_restrict_kernel(SlabCsr m, const double* __restrict__ z, const double* __restrict__ r,
                                                                   double* __restrict__ rc, int nc, int col_tiles, int total_tiles, int run) {
@@ -334,7 +331,10 @@ struct MgHierarchy {
     std::vector<MgLevel> levels;
     int smoother_degree = 0;
     double* partials = nullptr;  // the r.z partials of level 0's last update
+    MgMulti* multi = nullptr;    // spmv_amd_precond_create_multigrid_multi: the levels' block vectors and SpMM plans (multigrid_multi.hip)
     void release() {
+        mg_multi_destroy(multi);
+        multi = nullptr;
         for (MgLevel& L : levels) {
             L.A.release();
             if (L.own_dinv) device_release(L.dinv);
@@ -355,6 +355,18 @@ void mg_destroy(MgHierarchy* h) {
 }
 
 double* mg_result_vector(MgHierarchy* h) { return h->levels[0].z; }
+
+// what multigrid_multi.hip reads of the hierarchy (precond.hpp)
+int mg_level_count(const MgHierarchy* h) { return (int)h->levels.size(); }
+MgLevelView mg_level_view(const MgHierarchy* h, int level) {
+    const MgLevel& L = h->levels[(size_t)level];
+    MgLevelView v;
+    v.n = L.n, v.rows = L.rows, v.degree = L.degree, v.view = &L.view, v.variant = L.plan.variant, v.dinv = L.dinv, v.coef = L.coef;
+    return v;
+}
+MgMulti* mg_multi_of(const MgHierarchy* h) { return h != nullptr ? h->multi : nullptr; }
+SlabCsr mg_stencil_view(int n, const int* row_ptr, const int* col_idx, const double* values) { return stencil_view(n, row_ptr, col_idx, values); }
+bool mg_verify_stencil5(SlabCsr& v) { return verified(v); }
 
 namespace {
 
@@ -442,8 +454,9 @@ bool finish_level(MgHierarchy* h, int l, const LaunchShape& shape, int* bad_row)
     return true;
 }
 
-// The one creator: dim 2 for stencil5-csr (spmv_amd_precond_create_multigrid), dim 3 for stencil7-csr (..._multigrid3d).
-SpmvAmdPrecond* create_multigrid(SpmvOperator* op, int dim, int smoother_degree, int max_levels, int* bad_row) {
+// The one creator: dim 2 for stencil5-csr (spmv_amd_precond_create_multigrid), dim 3 for stencil7-csr (..._multigrid3d). max_rhs > 0
+// (dim 2 only, ..._multigrid_multi): the hierarchy also gets block vectors of that many columns and an SpMM plan on every level.
+SpmvAmdPrecond* create_multigrid(SpmvOperator* op, int dim, int smoother_degree, int max_levels, int* bad_row, int max_rhs = 0) {
     // argument checks: all before the first HIP call
     if (bad_row != nullptr) *bad_row = -1;
     if (op == nullptr) return fail("null operator"), nullptr;
@@ -491,6 +504,7 @@ SpmvAmdPrecond* create_multigrid(SpmvOperator* op, int dim, int smoother_degree,
     char what[64];
     snprintf(what, sizeof what, "%d levels on %d rows (multigrid)", (int)h->levels.size(), d.rows);
     const LaunchShape shape = current_launch_shape();
+    if (max_rhs > 0) need += mg_multi_bytes(h, max_rhs);
     bool ok = device_has_room(need + (size_t)d.rows * sizeof(double) + ((size_t)64 << 20), "PCG", what);
     if (ok) {
         MgLevel& top = h->levels[0];
@@ -516,6 +530,10 @@ SpmvAmdPrecond* create_multigrid(SpmvOperator* op, int dim, int smoother_degree,
         h->partials = device_try_alloc<double>(slots);
         if (h->partials == nullptr) ok = fail("the partials could not be allocated: refused");
     }
+    if (ok && max_rhs > 0) {
+        h->multi = mg_multi_create(h, max_rhs);
+        ok = h->multi != nullptr;
+    }
     HIP_CHECK(hipStreamSynchronize(kStream));
     if (!ok) {
         mg_destroy(h);
@@ -539,6 +557,20 @@ extern "C" SpmvAmdPrecond* spmv_amd_precond_create_multigrid(SpmvOperator* op, i
 
 extern "C" SpmvAmdPrecond* spmv_amd_precond_create_multigrid3d(SpmvOperator* op, int smoother_degree, int max_levels, int* bad_row) {
     return create_multigrid(op, 3, smoother_degree, max_levels, bad_row);
+}
+
+extern "C" SpmvAmdPrecond* spmv_amd_precond_create_multigrid_multi(SpmvOperator* op, int smoother_degree, int max_levels, int max_rhs,
+                                                                   int* bad_row) {
+    if (max_rhs < 1 || max_rhs > kMaxRhs) {  // before any HIP call, like the creator's other argument checks
+        if (bad_row != nullptr) *bad_row = -1;
+        fprintf(stderr, "[PCG] multigrid: max_rhs %d is outside 1..%d: refused\n", max_rhs, kMaxRhs);
+        return nullptr;
+    }
+    return create_multigrid(op, 2, smoother_degree, max_levels, bad_row, max_rhs);
+}
+
+extern "C" int spmv_amd_precond_multigrid_max_rhs(const SpmvAmdPrecond* m) {
+    return m != nullptr && m->kind == kMultigrid ? mg_multi_capacity(mg_multi_of(m->mg)) : 0;
 }
 
 extern "C" int spmv_amd_precond_multigrid_dimension(const SpmvAmdPrecond* m) {

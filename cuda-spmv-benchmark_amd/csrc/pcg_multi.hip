@@ -13,6 +13,9 @@
 //   AP = A P | step 1 | R -= alpha AP with term 0 (D, Z), the r.r partials | step 3 (history, verdict) |
 //   K x ( W = A Z into the AP buffer ; the step kernel on the columns still running, the last one leaves the r.z partials ) |
 //   step 4 (beta) | X += alpha P, P = Z + beta P
+// "multigrid" on a hierarchy with block vectors (spmv_amd_precond_create_multigrid_multi): the Chebyshev shape with
+// the rest of a V-cycle (mg_cycle_multi, multigrid_multi.hip) in the place of the K steps -- the r update writes term 0 of level 0 --,
+// level 0 on D, Z and the AP buffer; every launch of the cycle tests the column records.
 // then one small blocking read of the k column records (the stopping test). A column that converged or broke down is frozen: no
 // kernel changes a bit of its X, R, P, D, Z, history or count from the next iteration on. In the iteration in which the last column
 // stops the K SpMMs of the Chebyshev steps still run (the step kernels return at once): once per solve, and cheaper than a second
@@ -432,6 +435,13 @@ bool fail(const char* what) { return batched_fail(kTag, what); }
 }  // namespace
 
 namespace spmv_amd {
+void launch_pcg_multi_cheb_step(int k, long long n, const PcgMultiColumn* cols, const double* W, const double* R, const double* dinv, double g,
+                                double h, double* D, double* Z, int last, double* partials, long long count) {
+    VecArgs a{};
+    a.n = n, a.cols = cols, a.dinv = dinv, a.g = g, a.h = h, a.last = last;
+    a.AP = const_cast<double*>(W), a.R = const_cast<double*>(R), a.D = D, a.Z = Z, a.partials = partials, a.count = count;
+    launch_vector_stage(k, kStageChebStep, kCheb, a);
+}
 void release_pcg_multi_workspace_locked() { g_ws.release(); }
 size_t pcg_multi_workspace_bytes_locked() { return g_ws.bytes(); }
 }  // namespace spmv_amd
@@ -442,9 +452,17 @@ extern "C" int spmv_amd_pcg_solve_device_multi(SpmvOperator* op, MatrixData* mat
     if (op == nullptr || m == nullptr) return fail("null argument"), 1;  // the two pointers the shared checks do not name so
     MultiOperand o;
     if (!check_batched_system(kTag, kTag, op, mat, nrhs, B, X, config, stats, &o)) return 1;
-    if (m->kind == kMultigrid)
+    // kind "multigrid": a hierarchy with block vectors (spmv_amd_precond_create_multigrid_multi) of at least nrhs columns
+    const bool mg = m->kind == kMultigrid;
+    const int capacity = mg ? mg_multi_capacity(mg_multi_of(m->mg)) : 0;
+    if (mg && capacity == 0)
         return fail("kind 'multigrid' keeps single vectors on every level of its hierarchy: not available for several right-hand sides, refused"), 1;
-    if (m->kind != kNone && m->kind != kJacobi && m->kind != kChebyshev) return fail("unknown preconditioner kind: refused"), 1;
+    if (mg && nrhs > capacity) {
+        fprintf(stderr, "[%s] nrhs = %d, the multigrid preconditioner's hierarchy holds block vectors of max_rhs = %d columns: refused\n", kTag, nrhs,
+                capacity);
+        return 1;
+    }
+    if (!mg && m->kind != kNone && m->kind != kJacobi && m->kind != kChebyshev) return fail("unknown preconditioner kind: refused"), 1;
     if (m->n != mat->rows) {
         fprintf(stderr, "[%s] the preconditioner is for %d rows, mat->rows = %d\n", kTag, m->n, mat->rows);
         return 1;
@@ -452,8 +470,10 @@ extern "C" int spmv_amd_pcg_solve_device_multi(SpmvOperator* op, MatrixData* mat
     if (!precond_matches(op, m, diagonal_source_of(op))) return fail("the preconditioner does not belong to this operator as it stands: refused"), 1;
     const int n = mat->rows, k = nrhs;
     const CGConfig cfg = *config;
-    const int kind = m->kind == kChebyshev ? kCheb : m->kind == kJacobi ? kJac : kPlain;
-    const int degree = kind == kCheb ? m->degree : 0;
+    // the kernels' kind: a multigrid cycle begins with term 0 of level 0, so its init and r update are the Chebyshev ones
+    const int kind = (m->kind == kChebyshev || mg) ? kCheb : m->kind == kJacobi ? kJac : kPlain;
+    const int degree = m->kind == kChebyshev ? m->degree : 0;
+    const double c0 = mg ? mg_level_view(m->mg, 0).coef[0] : m->kind == kChebyshev ? m->coef[0] : 0.0;
 
     CgWorkspaceScope scope;
     int device = 0;
@@ -467,15 +487,18 @@ extern "C" int spmv_amd_pcg_solve_device_multi(SpmvOperator* op, MatrixData* mat
     std::vector<ColumnSummary> cols;
     StageTimers T(cfg.enable_detailed_timers != 0, kBatchStream);
     VecArgs a{};
-    a.n = n, a.cols = w.cols, a.dinv = m->dinv, a.c0 = kind == kCheb ? m->coef[0] : 0.0, a.last = degree == 0 ? 1 : 0;
+    a.n = n, a.cols = w.cols, a.dinv = m->dinv, a.c0 = c0, a.last = (degree == 0 && !mg) ? 1 : 0;  // a cycle never ends with term 0
     a.X = w.X, a.R = w.R, a.P = w.P, a.AP = w.AP, a.D = w.D, a.Z = w.Z, a.partials = w.partials, a.count = vec_count;
     auto vec = [&](int stage) { T.run(&T.t_blas, [&] { launch_vector_stage(k, stage, kind, a); }); };
     auto reduce = [&](const double* partials, long long count, int which) {
         T.run(&T.t_red, [&] { launch_reduce(k, partials, count, w.slices, which, cfg.tolerance, w.cols, w.hist, w.hist_cap); });
     };
     auto spmm = [&](const double* in, double* partials) { T.run(&T.t_spmv, [&] { launch_spmm(o.plan, k, in, w.AP, partials, kBatchStream); }); };
-    // steps 1 .. degree behind a term 0 that left D and Z: W = A Z goes to the AP buffer, free between the r update and the next SpMM
-    auto cheb_steps = [&] {
+    // What follows a term 0 that left D and Z. "chebyshev": steps 1 .. degree, W = A Z goes to the AP buffer, free between the r update
+    // and the next SpMM. "multigrid" (degree is 0 here): the rest of the V-cycle, level 0 on D, Z and the AP buffer; every launch of it
+    // tests the column records.
+    auto after_term0 = [&] {
+        if (mg) mg_cycle_multi(m->mg, k, w.cols, w.R, w.D, w.Z, w.AP, w.partials, vec_count, &T);
         for (int s = 1; s <= degree; ++s) {
             spmm(w.Z, nullptr);
             VecArgs c = a;
@@ -488,7 +511,7 @@ extern "C" int spmv_amd_pcg_solve_device_multi(SpmvOperator* op, MatrixData* mat
     spmm(w.X, nullptr);
     vec(kStageInit);
     if (kind == kCheb) {
-        cheb_steps();
+        after_term0();
         HIP_CHECK(hipMemcpyAsync(w.P, w.Z, (size_t)n * k * sizeof(double), hipMemcpyDeviceToDevice, kBatchStream));  // p0 = z0
     }
     reduce(w.partials, vec_count, 0);
@@ -500,7 +523,7 @@ extern "C" int spmv_amd_pcg_solve_device_multi(SpmvOperator* op, MatrixData* mat
         vec(kStageUpdateR);
         if (kind == kCheb) {
             reduce(w.partials, vec_count, 3);
-            cheb_steps();
+            after_term0();
             reduce(w.partials + (size_t)k * vec_count, vec_count, 4);
         } else {
             reduce(w.partials, vec_count, 2);

@@ -90,4 +90,36 @@ void mg_destroy(MgHierarchy* h);
 Applied mg_cycle(MgHierarchy* h, const double* r, StageTimers* T);
 double* mg_result_vector(MgHierarchy* h);  // a level-0 vector of the hierarchy (what a loop hands on when no cycle ran)
 
+// ---- the hierarchy on block vectors (multigrid_multi.hip) ----
+// What the batched cycle reads of one level; the pointers are the hierarchy's.
+struct MgLevelView {
+    int n = 0, rows = 0;     // the grid and its rows
+    int degree = 0;          // Chebyshev steps of the level's smoother (the coarsest level: of its solve)
+    const SlabCsr* view = nullptr;
+    Stencil5Variant variant = Stencil5Variant::RowGeneric;  // of the level's own Stencil5Plan
+    const double* dinv = nullptr;
+    const double* coef = nullptr;  // c0, h_1, g_1, ...
+};
+int mg_level_count(const MgHierarchy* h);
+MgLevelView mg_level_view(const MgHierarchy* h, int level);
+// The block vectors and SpMM plans of a hierarchy made by spmv_amd_precond_create_multigrid_multi (null: a single-vector hierarchy).
+struct MgMulti;
+MgMulti* mg_multi_of(const MgHierarchy* h);
+int mg_multi_capacity(const MgMulti* mm);  // max_rhs; 0 for null
+// Device bytes mg_multi_create will ask for, from the levels' rows alone (the creator sizes everything against free memory first).
+size_t mg_multi_bytes(const MgHierarchy* h, int max_rhs);
+// Allocates them and plans every level's SpMM; null (nothing left behind, said on stderr) when the device cannot provide them.
+MgMulti* mg_multi_create(const MgHierarchy* h, int max_rhs);
+void mg_multi_destroy(MgMulti* mm);
+// One V-cycle on k <= max_rhs interleaved columns, on the batch stream: Z = M^-1 R. Level 0 works on the caller's vectors -- R (only
+// read), D and Z holding term 0 on entry, W (scratch for A Z) -- every other level on the hierarchy's. cols: the device column records
+// (every launch returns at once when no column is running; a stopped column's D, Z and level vectors are scratch). Level 0's last step
+// leaves the r.z partials as value 1 of `partials` (2 k count slots), where pcg_multi.hip's step 4 reads them. T may be null.
+struct PcgMultiColumn;
+void mg_cycle_multi(const MgHierarchy* h, int k, const PcgMultiColumn* cols, const double* R, double* D, double* Z, double* W,
+                    double* partials, long long count, StageTimers* T);
+// A complete 5-point CSR on an n x n grid in the caller's arrays as a view, and its structure check (synchronises; sets the view's flag).
+SlabCsr mg_stencil_view(int n, const int* row_ptr, const int* col_idx, const double* values);
+bool mg_verify_stencil5(SlabCsr& v);
+
 }  // namespace spmv_amd

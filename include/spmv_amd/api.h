@@ -387,6 +387,27 @@ SpmvAmdPrecond* spmv_amd_precond_create_multigrid3d(SpmvOperator* op, int smooth
 int spmv_amd_precond_multigrid_info(const SpmvAmdPrecond* m, int* levels, int* smoother_degree, int* grids, double* lambda_max, int cap);
 /* 2 for a multigrid preconditioner of stencil5-csr, 3 for one of stencil7-csr, 0 for NULL or any other kind. */
 int spmv_amd_precond_multigrid_dimension(const SpmvAmdPrecond* m);
+/* Kind "multigrid" for up to max_rhs (1..8) right-hand sides at once (csrc/multigrid_multi.hip): it is
+ * spmv_amd_precond_create_multigrid in every respect -- levels, coarse operators, dinv, Gershgorin bounds, coefficients, refusals, *bad_row --
+ * and in addition its hierarchy holds block vectors of max_rhs row-interleaved columns (element (row, column j) at [row * k + j]) on every
+ * level above 0 (R, D, Z and W = A Z; level 0 works on the vectors of the solve or of the application) and one SpMM plan per level, on the
+ * level's own view and launch variant. max_rhs outside 1..8 is refused before any HIP call like the other arguments. Everything is sized
+ * against the device's free memory first; a refusal leaves no device memory behind. The handle is also a complete single-vector multigrid
+ * handle: spmv_amd_pcg_solve_device, spmv_amd_precond_apply_device, ..._multigrid_info and ..._multigrid_dimension work on it, bit for
+ * bit as on a handle of spmv_amd_precond_create_multigrid. Only the 2-D hierarchy of "stencil5-csr" has this form: the 3-D hierarchy of
+ * "stencil7-csr" (spmv_amd_precond_create_multigrid3d) has no block vectors, and "stencil7-csr" is refused here as by the 2-D creator. */
+SpmvAmdPrecond* spmv_amd_precond_create_multigrid_multi(SpmvOperator* op, int smoother_degree, int max_levels, int max_rhs, int* bad_row);
+/* The capacity max_rhs of such a handle; 0 for NULL, for another kind and for a handle of spmv_amd_precond_create_multigrid or
+ * ..._multigrid3d. */
+int spmv_amd_precond_multigrid_max_rhs(const SpmvAmdPrecond* m);
+/* Z = M^-1 R on device blocks of nrhs (1..8) row-interleaved columns of n rows (16-byte aligned), for every kind the batched solver
+ * accepts: "none" (copy), "jacobi", "chebyshev", and "multigrid" from spmv_amd_precond_create_multigrid_multi with nrhs <= max_rhs.
+ * The checks are those of spmv_amd_precond_apply_device, plus nrhs and the capacity, all before any HIP call ([PCG-MULTI] sentences;
+ * "chebyshev" and "multigrid" need the operator's multi-RHS path). d_R is only read; d_Z must not overlap it. Work vectors that are not
+ * the hierarchy's live for the call only. Synchronises. Column j of d_Z has exactly the bits spmv_amd_precond_apply_device gives for
+ * column j alone: both run the operator's own product bits and the same element-wise fma forms (the fused row-lds step of the single
+ * path against SpMM + step kernel here). Returns 0, non-zero for a refusal. */
+int spmv_amd_precond_apply_device_multi(SpmvOperator* op, const SpmvAmdPrecond* m, int nrhs, const double* d_R, double* d_Z);
 /* z = M^-1 r on device vectors of n rows (16-byte aligned), any kind (none: copy, jacobi: dinv*r). d_z must not overlap d_r, which is
  * only read. rz (may be NULL): r.z summed by the solver's own fixed-shape reduction. The pair (op, m) is checked as by
  * spmv_amd_pcg_solve_device, before any HIP call. Work vectors live for the call only. Synchronises. Returns 0, non-zero for a refusal. */
@@ -410,7 +431,7 @@ void spmv_amd_pcg_release_workspace(void);
 
 /* ---- preconditioned CG for several right-hand sides (csrc/pcg_multi.hip) ----
  * nrhs (1..8) INDEPENDENT preconditioned solves on one operator under one preconditioner of kind "none", "jacobi" (a from-diagonal one
- * included) or "chebyshev": per column exactly the algebra, stopping rule and breakdown rule of spmv_amd_pcg_solve_device, with the
+ * included), "chebyshev", or "multigrid" from spmv_amd_precond_create_multigrid_multi with nrhs <= max_rhs: per column exactly the algebra, stopping rule and breakdown rule of spmv_amd_pcg_solve_device, with the
  * arguments, statistics, timers and verbose semantics of spmv_amd_cg_solve_device_multi (B, X: host, nrhs vectors of mat->rows values
  * one after the other, X in = x0; stats: nrhs records; verbose lines tagged [PCG-MULTI j]). Only the SpMM and dinv are shared: the
  * operator must have the multi-RHS path ("stencil5-csr" in every variant, "stencil7-csr", "cusparse-csr").
@@ -425,10 +446,19 @@ void spmv_amd_pcg_release_workspace(void);
  * order, then a 256-wide tree), the slice sums the same way. Every value of column j has the same bits whatever nrhs is and whatever
  * slot the column sits in, and with kind "none" a solve without a breakdown has the bits of spmv_amd_cg_solve_device_multi. (The
  * single-RHS spmv_amd_pcg_solve_device sums in another shape: the two agree to rounding, not bit for bit.)
- * A column that has converged or broken down is frozen: from the next iteration on nothing changes a bit of its x, history or count.
+ * Kind "multigrid": z = one V(nu, nu) cycle, steps (1)-(5) of spmv_amd_precond_create_multigrid's text element for element, per column
+ * the algebra of spmv_amd_pcg_solve_device with that kind, the dot products in the shape above. Unlike the single-RHS loop there is no
+ * host read before the cycle; the iteration has the "chebyshev" shape: SpMM, step 1, the r update (which writes term 0 of level 0 into D
+ * and Z), the verdict, the rest of the cycle, beta, the x / p update, the one read of the column records. In the iteration in which the
+ * last column stops the cycle's launches still go out and each returns at once: every kernel of the cycle reads the column records and
+ * does nothing when no column is running. A column's bits depend neither on nrhs nor on its slot. Cycle launches that carry an SpMM (the
+ * smoothing products, the residual restriction) count as SpMV time under detailed timers, the others as BLAS1.
+ * A column that has converged or broken down is frozen: from the next iteration on nothing changes a bit of its x, history or count
+ * (kind "multigrid": of its X, R, P, history, count and record; D, Z and the hierarchy's level vectors are scratch for stopped columns).
  * Refused before the first HIP call, with a [PCG-MULTI] sentence on stderr and a non-zero return: nrhs outside 1..8, a NULL
  * argument, max_iters < 0, an operator without the multi-RHS path or used before init, a system that is not square or not of
- * mat->rows rows, kind "multigrid" (its hierarchy holds single vectors), a preconditioner of another size, of another operator or
+ * mat->rows rows, kind "multigrid" from spmv_amd_precond_create_multigrid or ..._multigrid3d (its hierarchy holds single vectors; the
+ * 3-D hierarchy has no batched form), nrhs above a block hierarchy's max_rhs (the sentence names both), a preconditioner of another size, of another operator or
  * from before the operator's last init or free. The workspace (X, R, P, AP; "chebyshev": D and Z too; partials, column records,
  * histories) is sized against the device's free memory first and refused with a sentence if it does not fit; it is kept between
  * calls and released with the other CG workspaces (an operator's free(), spmv_amd_cg_release_workspace(),

@@ -333,6 +333,31 @@ typedef struct SpmvAmdPcgMultiStageArgs {
  * otherwise. */
 int spmv_amd_pcg_multi_stage(const char* stage, const char* kind, int k, SpmvAmdPcgMultiStageArgs* a);
 
+/* Device pointers of one spmv_amd_mg_multi_stage call; n = the FINE grid, the coarse grid is (n + 1) / 2. Block vectors are
+ * row-interleaved, k columns: element (row, column j) at [row * k + j]. */
+typedef struct SpmvAmdMgMultiStageArgs {
+    int n;
+    const int* row_ptr;      /* residual_restrict: the fine level's CSR, a complete 5-point stencil of grid n (checked) */
+    const int* col_idx;
+    const double* values;
+    double* z;               /* residual_restrict: in; prolong: in and out; term0: out -- n * n rows */
+    const double* r;         /* residual_restrict, term0: in -- n * n rows */
+    double* coarse;          /* residual_restrict: out, r_c; prolong: in, e_c -- ((n + 1) / 2)^2 rows */
+    double* d;               /* term0: out -- n * n rows */
+    const double* dinv;      /* term0: n * n values */
+    double c0;               /* term0 */
+    const SpmvAmdPcgMultiColumn* cols; /* k records, DEVICE memory; null = every column is running. A launch does nothing at all
+                                          when no record has done == 0 */
+} SpmvAmdMgMultiStageArgs;
+/* The batched multigrid cycle's own launches (csrc/multigrid_multi.hip), one per call on the caller's device data
+ * for k = 1..8 columns, through the functions the cycle makes them with. Every call synchronises. stage: "residual_restrict"
+ * (r_c = P^T (r - A z) per column in one launch), "prolong" (z = fma(2.0, e_c[agg(i)], z)), "term0" (d = c0 * (dinv * r); z = d).
+ * Refused before any HIP call, with a [PCG-MULTI] sentence and a non-zero return: an unknown stage, k outside 1..8, null arguments,
+ * n outside 2..46340, a null pointer the stage needs, a block vector that is not 16-byte (even k) or 8-byte (odd k) aligned, a CSR
+ * array, dinv or cols that are not 4- / 8-byte aligned; after the structure check (as spmv_amd_mg_stage makes it): a CSR that is not the
+ * complete stencil. Returns 0 otherwise. */
+int spmv_amd_mg_multi_stage(const char* stage, int k, SpmvAmdMgMultiStageArgs* a);
+
 #ifdef __cplusplus
 }
 #endif
