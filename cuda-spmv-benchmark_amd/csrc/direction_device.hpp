@@ -1,5 +1,5 @@
 // direction_device.hpp -- the CG direction update p' = r + beta p as one expression, for every kernel that evaluates it: the
-// streaming updates of cg_kernels.hip and the block SpMV that recomputes p' in registers (spmv_kernels.hip,
+// streaming updates of cg_kernels.hip and the block SpMV that recomputes p' in registers (stencil5_block_kernels.hip,
 // stencil5_direction_block_kernel). Both translation units must round it the same way, bit for bit.
 #pragma once
 

@@ -166,6 +166,9 @@ void launch_verify_sym_planes(const SlabCsr& m, const SymPlanes& planes, int* d_
 int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& plan, const double* x, double* y, double alpha,
                          double* d_dot_partials, const int* d_skip_flag, bool reverse, hipStream_t stream,
                          const ResidualOut* init = nullptr, const SymPlanes* planes = nullptr, bool x_zero = false, bool ap_not_stored = false);
+// The block-tile launch that launch_stencil5_spmv hands such a plan to (stencil5_block_kernels.hip); callers go through it.
+void launch_rowlds_block(const SlabCsr& m, const Stencil5Plan& plan, const double* x, double* y, double alpha, double* d_dot_partials,
+                         const int* d_skip_flag, bool reverse, hipStream_t stream, const SymPlanes& planes, bool ap_not_stored);
 // The CG direction update inside the in-loop block SpMV (stencil5_direction_block_kernel; slabs without neighbours whose plan has
 // a block map): p_out = direction(r, s->beta, p_in), y = alpha A p_out and the p_out . (A p_out) partials of the plan's slots, in one
 // launch over the block tiles plus one over `slow_list` -- the indices of the range's block tiles whose map byte is 0 (device

@@ -1,4 +1,4 @@
-// skew_geometry.hpp -- the skewed block tiles of the r update that recomputes A p' (spmv_kernels.hip, cg_update_r_recompute_kernel;
+// skew_geometry.hpp -- the skewed block tiles of the r update that recomputes A p' (stencil5_block_kernels.hip, cg_update_r_recompute_kernel;
 // DESIGN §9). cg_update_r_kernel leaves one r.r partial per CHUNK of 128 consecutive elements of the linear index, chunk q =
 // [128 q, 128 q + 128), lane l holding the pair 2 l, 2 l + 1. A kernel that must leave the same partials and still work on blocks
 // of grid rows cuts each grid row at the chunk boundaries instead of at fixed columns: tile t of grid row li is the t-th chunk that

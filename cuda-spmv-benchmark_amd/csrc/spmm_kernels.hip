@@ -9,7 +9,7 @@
 //
 // Memory contract: a STENCIL5 interior row costs 40 B of coefficients + 16 k B of x and y. The coefficients are read ONCE for
 // all k columns -- that is the point of the SpMM.
-//   row-lds     (the stencil operator's "stencil5/row-lds" variant): the shape of spmv_kernels.hip's rowlds_tile. A workgroup
+//   row-lds     (the stencil operator's "stencil5/row-lds" variant): the shape of rowlds_tile_device.hpp's rowlds_tile. A workgroup
 //               is four waves over 256 consecutive columns of one grid row; each wave streams its 64 rows' 320 coefficients
 //               with fully coalesced nontemporal 8-byte loads into a wave-private LDS strip and reads them back as [N,W,C,E,S].
 //               x rows are read per lane as 8k-byte runs (W / E are the neighbouring lanes' runs: cache hits), y leaves with
@@ -65,7 +65,7 @@ __device__ __forceinline__ void store_row_nt(double* __restrict__ p, const doubl
     }
 }
 
-// One row by the CSR loop (spmv_kernels.hip, row_reference with kAnalyticInterior = false): sum = 0, ascending fma; a column
+// One row by the CSR loop (rowlds_tile_device.hpp, row_reference with kAnalyticInterior = false): sum = 0, ascending fma; a column
 // outside the readable range contributes 0 (halo kernel semantics). Columns col0 .. col0 + W - 1 of a block of K.
 template <int K, int W, bool kVec>
 __device__ __forceinline__ void csr_row_part(const SlabCsr& m, const double* __restrict__ X, long long row, int col0, double (&sum)[W]) {

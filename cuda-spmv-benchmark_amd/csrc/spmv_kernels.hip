@@ -15,15 +15,15 @@
 // coefficients) were removed in round 5; their tables are in profiles/ (DESIGN.md section 8 names the files) and their
 // code in the history up to commit 258dcef.
 // blockIdx -> tile mappings are performance choices only, never a correctness input.
+// In this file: the STENCIL5 one-row kernels, the generic CSR and ELL kernels, the creation-time kernels (generate, verify, classify,
+// the planes) and their launchers. The row-lds tile itself is rowlds_tile_device.hpp; the block-tile kernels of a solver slab's loop
+// -- the launch launch_stencil5_spmv hands a plan with a block map to -- are stencil5_block_kernels.hip.
 #include "kernels.hpp"
 
 #include <stdlib.h>
 
-#include <type_traits>
-
-#include "direction_device.hpp"
 #include "reduce_device.hpp"
-#include "skew_geometry.hpp"
+#include "rowlds_tile_device.hpp"
 #include "slab_decisions.hpp"
 #include "stencil_geometry.hpp"
 #include "stencil_row_device.hpp"
@@ -42,34 +42,6 @@ __device__ __forceinline__ long long logical_block(int group, long long total) {
     const long long t = xcd_run_tile<long long>(b, group);
     return t < total ? t : -1;
 }
-
-// x[col - row_offset] if that index is readable, else 0 (halo kernel semantics,
-// reference src/spmv/spmv_stencil_partitioned_halo_kernel.cu:77-94).
-__device__ __forceinline__ double x_at(const double* __restrict__ x, long long local_col,
-                                       int lo, int hi) {
-    return (local_col >= lo && local_col < hi) ? x[local_col] : 0.0;
-}
-
-// One row, evaluated the way the reference kernels do: computed offset and computed
-// columns for interior rows of a verified stencil, the CSR loop otherwise.
-template <bool kAnalyticInterior>
-__device__ __forceinline__ double row_reference(const SlabCsr& m, const double* __restrict__ x,
-                                                int local_row, int i, int j) {
-    const int n = m.grid_size;
-    if (kAnalyticInterior && stencil_is_interior(i, j, n)) {
-        const long long o = stencil_row_start(i, j, n) - m.nnz_base;
-        const double* __restrict__ v = m.values + o;
-        const double* __restrict__ xl = x + local_row;
-        return stencil5_interior(v[1], xl[-1], v[2], xl[0], v[3], xl[1], v[0], xl[-n], v[4], xl[n]);  // [N,W,C,E,S]
-    }
-    const int lo = -m.halo_before, hi = m.n_local + m.halo_after;
-    const int k0 = m.row_ptr[local_row], k1 = m.row_ptr[local_row + 1];
-    double sum = 0.0;
-    for (int k = k0; k < k1; ++k)
-        sum = fma(m.values[k], x_at(x, (long long)m.col_idx[k] - m.row_offset, lo, hi), sum);
-    return sum;
-}
-
 
 // ---------------------------------------------------------------------------------
 // STENCIL5, row-direct variant (slabs made of whole grid rows, grids below 512 columns): one thread per row, a workgroup
@@ -116,289 +88,6 @@ __global__ __launch_bounds__(kBlock) void stencil5_rowdirect_kernel(
         if (threadIdx.x == 0)
             dot_partials[blockIdx.x] = ((wave_part[0] + wave_part[1]) + wave_part[2]) + wave_part[3];
     }
-}
-
-// ---------------------------------------------------------------------------------
-// STENCIL5, row-lds variant (default on slabs made of whole grid rows, n >= 512). Same index space
-// as row-direct -- a workgroup is a run of columns of ONE grid row, so no thread divides -- but the
-// coefficients take the streaming path the probes found fastest on MI355X
-// (tools/stream_probe3.hip, profiles/r01_stream_probe3.txt):
-//   * a workgroup is ONE wavefront that owns 128 consecutive columns, two rows per lane (columns
-//     j0 + lane and j0 + 64 + lane): every x / y access stays an 8-byte-per-lane coalesced access;
-//   * the tile's 640 coefficients are one contiguous run of `values` (five entries per interior
-//     row): ten fully coalesced 8-byte NONTEMPORAL loads per lane -- the run is read once and never
-//     again, so it should not displace x in L2 / Infinity Cache -- parked in a 5 KiB wave-private
-//     LDS strip and read back as [N,W,C,E,S] per row (lane stride 40 B = 10 banks, an even stride
-//     over 64 banks: conflict-free for 8-byte reads);
-//   * y leaves with a nontemporal store;
-//   * x: centre and N/S (the lines the neighbouring grid rows pull through L2 / Infinity Cache) by plain
-//     loads: these are the re-used bytes. W/E come from a 1 KiB LDS copy of the tile's own centre values
-//     (only the tile's two outer neighbours are loaded): four fewer vector-memory instructions per wave,
-//     0.8 % at 20 000^2 and 2.6 % at 10 000^2, bit-identical results;
-//   * tile -> XCD: workgroups are dealt round-robin to the eight XCDs, so tile = blockIdx would
-//     scatter every 1 KiB of x / y over eight L2s. Instead each XCD takes `group` consecutive tiles
-//     of every run of 8 * group (group = 4: 512 columns = 4 KiB of x and y, 20 KiB of values per
-//     XCD and run). Measured at 20 000^2 with the real coefficient layout: group 1 3.89 ms,
-//     group 2 4.04 ms, group 4 / 8 3.63 ms, group 16 3.73 ms -- a plateau, not a spike.
-// Columns 0 and n-1 of an interior grid row (4-entry rows) are evaluated from the same strip in the
-// CSR loop's order (ascending column, sum started at 0: reference :116-119); only the first and
-// last grid row of the whole grid, whose rows have no N or S entry, walk row_ptr / col_idx.
-// No barrier: the strip is private to the wave, and LDS operations of one wave retire in order.
-// Arithmetic per interior row is exactly row-direct's (and the reference's) W,C,E,N,S fma chain.
-// ---------------------------------------------------------------------------------
-constexpr int kLdsTileCols = 128;
-
-// kMode 0: y = alpha A x. kMode 1: also one partial of x . (A x) per wave (the CG loop's p.Ap).
-// kMode 2 (first SpMV of a solve, x = the initial guess): y is NOT stored; instead r = b - A x (one fma, the
-// reference's axpy_kernel(-1, Ap, b), mgpu :475), p = r, and one partial of r.r per wave -- the initial residual
-// without writing A x0 out and reading it back (16 B/row less, once per solve).
-// kMode 3 (one step of the Chebyshev preconditioner, x = z; kernels.hpp ChebStep): y is NOT stored; the row's sum stays in registers
-// and runs t = fma(-1, sum, r), u = dinv t, d = fma(g, u, h d), z_out = z + d. r, dinv and d are read once (nontemporal, requested
-// with the tile's x loads), d is written back in place, z_out -- another vector than x: neighbouring tiles still read x -- with a
-// plain store, because the next step reads it as x. The last step of an application also leaves one partial of r . z_out per wave.
-// 88 B per interior row (40 coefficients; z, r, dinv, d in; d, z_out out) against 56 + 56 for a SpMV followed by a streaming pass.
-//
-// One tile = local grid row li (global gi), columns [j0, j0 + 128), evaluated by one wave on its private LDS (`strip`:
-// 640 doubles, `xrow`: 130). Returns false if the launch was enqueued past convergence (`skip`: the flag's value,
-// REQUESTED by the caller before this call and tested here only after the tile's loads have been issued -- a wave does not
-// sit on a scalar-load round trip before its first vector load; such a launch only reads). *dot: the tile's partial.
-// kFreshHalo (boundary tiles evaluated behind a device-side arrival flag instead of a kernel boundary, see
-// stencil5_rowlds_edges_reduce_kernel): the north / south values -- the halo rows another GPU's data was received into -- are
-// read with SYSTEM-scope loads: the writer is another agent (a peer GPU's stores over xGMI, or the RCCL receive kernel acting
-// for it), and no cache of this device may answer from a line it held before those rows arrived (2 x grid_size
-// values per iteration, nothing on the clock).
-// kSym (the symmetric coefficient form of a solver slab, kernels.hpp SymPlanes): interior grid rows take C and E from the [C, E]
-// plane (one nontemporal 16-byte load per lane and row: read once per SpMV), S from the S plane and N = S[i - n] from the row
-// one grid row up (plain loads: the S line is re-read as N one grid row later, like x's N / S neighbours), and W = E[i - 1]
-// from the LDS copy of the tile's own E values (`strip`; lane 0 loads the one outside the tile). 24 B/row of coefficients
-// instead of 40. The fma chains are the CSR form's, value for value (the planes were verified bit for bit at creation).
-// tile_class (kSym only; rowlds_tile_class, the same value in every lane): 1 = every coefficient this tile multiplies equals the
-// slab-wide quintuple in sp bit for bit (checked against the CSR at creation): the tile loads no coefficient, keeps no LDS copy of
-// E and runs the same chains on the quintuple -- 0 B/row of coefficients. 0 = the plane path.
-// kZeroX (kMode 2 only; stencil5_rowlds_zero_kernel): the caller knows that x holds +0.0 in every element. An interior grid row
-// requests no x value: centre, W, E, N and S are 0.0 in registers, the LDS copy of the x row and its W / E exchange are gone, and
-// everything behind the loads is the code of the other form -- the chains still multiply every coefficient by its zero, so -0.0
-// and the NaN of an infinite coefficient come out bit for bit. The grid's first and last grid row read x as before.
-template <int kMode, bool kFreshHalo = false, bool kSym = false, bool kZeroX = false>
-__device__ __forceinline__ bool rowlds_tile(const SlabCsr& m, const double* __restrict__ x, double* __restrict__ y, double alpha,
-                                            int li, int gi, int j0, int lane, int skip, double* __restrict__ strip,
-                                            double* __restrict__ xrow, const ResidualOut& res, double* dot, const SymPlanes& sp = SymPlanes{},
-                                            int tile_class = 0, const ChebStep& step = ChebStep{}) {
-    constexpr bool kDot = kMode == 1;
-    constexpr bool kInit = kMode == 2;
-    constexpr bool kCheb = kMode == 3;
-    const int n = m.grid_size;
-    double dot_acc = 0.0;
-    if (gi > 0 && gi < n - 1) {
-        // slab-local position of the tile's first coefficient: row (gi, j) starts at base + 5 j - 1
-        // for j >= 1; the run of the first tile starts one entry early so that row j sits at strip
-        // position 5 j there too (row 0 itself holds [N,C,E,S] at positions 1..4)
-        const long long e = stencil_gridrow_base(gi, n) + 5LL * j0 - 1 - m.nnz_base + lane;
-        const double* __restrict__ vals = m.values;
-        double c[10];
-        d2 ce[2];                             // kSym: [C, E] of the lane's two rows
-        double cs[2], cn[2], cw = 0.0;        // kSym: S, N = S[i - n]; lane 0: E[i - 1] of the tile's first row
-        if constexpr (kSym) {
-            // the plane loads are issued behind the x loads below: those do not depend on the tile's class, which is still on its way
-        } else if (j0 == 0 || j0 + kLdsTileCols > n - 1) {
-            // first / last tile of the grid row: part of the run lies outside the row (at the slab's
-            // ends: outside the array): clamp the addresses, those strip slots feed no row
-            const long long hi = m.nnz_local - 1;
-#pragma unroll
-            for (int k = 0; k < 10; ++k) {
-                long long idx = e + 64 * k;
-                idx = idx < 0 ? 0 : (idx > hi ? hi : idx);
-                c[k] = __builtin_nontemporal_load(vals + idx);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 10; ++k) c[k] = __builtin_nontemporal_load(vals + e + 64 * k);
-        }
-        double xc[2], xw[2], xe[2], xn[2], xs[2], bv[2];
-        double cr[2] = {0.0, 0.0}, cdv[2] = {0.0, 0.0}, cd[2] = {0.0, 0.0};  // kCheb: r, dinv and d of the lane's two rows
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int j = j0 + lane + 64 * h;
-            xc[h] = xw[h] = xe[h] = xn[h] = xs[h] = bv[h] = 0.0;
-            if (j < n) {
-                const double* __restrict__ xl = x + ((long long)li * n + j);
-                if constexpr (!kZeroX) {
-                    xc[h] = xl[0];
-                    if (kFreshHalo) {
-                        xn[h] = published_by_any_agent(reinterpret_cast<const unsigned long long*>(xl - n));
-                        xs[h] = published_by_any_agent(reinterpret_cast<const unsigned long long*>(xl + n));
-                    } else {
-                        xn[h] = xl[-n], xs[h] = xl[n];
-                    }
-                }
-                if (kInit) bv[h] = __builtin_nontemporal_load(res.b + ((long long)li * n + j));
-                if constexpr (kCheb) {  // streams read once per step, requested with the x loads (before the skip flag is tested)
-                    cr[h] = __builtin_nontemporal_load(step.r + ((long long)li * n + j));
-                    cdv[h] = __builtin_nontemporal_load(step.dinv + ((long long)li * n + j));
-                    cd[h] = __builtin_nontemporal_load(step.d + ((long long)li * n + j));
-                }
-                // only the tile's two outer neighbours come from memory; the rest from the LDS copy below
-                if constexpr (!kZeroX) {
-                    if (h == 0 && lane == 0 && j > 0) xw[0] = xl[-1];
-                    if (h == 1 && lane == 63 && j < n - 1) xe[1] = xl[1];
-                }
-            }
-        }
-        // Everything behind the tile's loads, for a tile that streams its coefficients (kUniform false: the CSR strip or the planes)
-        // or one that takes the slab-wide quintuple (kUniform true). Two instances rather than one with selects: each keeps the
-        // registers of its own path.
-        const auto finish = [&](auto uniform_tile) {
-            constexpr bool kUniform = decltype(uniform_tile)::value;
-            if constexpr (kSym) {
-                if constexpr (!kUniform) {
-                    strip[1 + lane] = ce[0].y;
-                    strip[65 + lane] = ce[1].y;
-                    if (lane == 0) strip[0] = cw;
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < 10; ++k) strip[64 * k + lane] = c[k];
-            }
-            if constexpr (!kZeroX) {
-                xrow[1 + lane] = xc[0];
-                xrow[65 + lane] = xc[1];
-            }
-            wave_lds_sync();
-            if constexpr (!kZeroX) tile_west_east(xrow, lane, j0, n, xw[0], xe[1], xw, xe);  // else: W and E are the zeros they were set to
-            double cwv[2] = {0.0, 0.0};  // kSym: W = E[i - 1]
-            if constexpr (kSym && !kUniform) {
-                cwv[0] = strip[lane];
-                cwv[1] = strip[64 + lane];
-            }
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int j = j0 + lane + 64 * h;
-                if (j < n) {
-                    const double* __restrict__ v = strip + 5 * (lane + 64 * h);
-                    double sum;
-                    if constexpr (kSym) {
-                        // a uniform tile: the quintuple, bit for bit what every row of the tile holds (checked against the CSR at creation)
-                        const double vw = kUniform ? sp.w : cwv[h], vc = kUniform ? sp.c : ce[h].x, ve = kUniform ? sp.e : ce[h].y,
-                                     vn = kUniform ? sp.n : cn[h], vs = kUniform ? sp.s5 : cs[h];
-                        sum = stencil5_row(j, n, vw, xw[h], vc, xc[h], ve, xe[h], vn, xn[h], vs, xs[h]);
-                    }
-                    // The CSR strip form: its three chains (stencil_row_device.hpp's, on other strip slots per case) stay written out here;
-                    // profiles/r14_stencil_helpers_isa_identity.txt, class C site 2, says why.
-                    else if (j > 0 && j < n - 1) {       // [N,W,C,E,S], evaluated W,C,E,N,S
-                        sum = v[1] * xw[h];
-                        sum = fma(v[2], xc[h], sum);
-                        sum = fma(v[3], xe[h], sum);
-                        sum = fma(v[0], xn[h], sum);
-                        sum = fma(v[4], xs[h], sum);
-                    } else if (j == 0) {                 // [N,C,E,S] at strip positions 1..4, CSR-loop order
-                        sum = fma(v[1], xn[h], 0.0);
-                        sum = fma(v[2], xc[h], sum);
-                        sum = fma(v[3], xe[h], sum);
-                        sum = fma(v[4], xs[h], sum);
-                    } else {                             // j == n-1: [N,W,C,S], CSR-loop order
-                        sum = fma(v[0], xn[h], 0.0);
-                        sum = fma(v[1], xw[h], sum);
-                        sum = fma(v[2], xc[h], sum);
-                        sum = fma(v[3], xs[h], sum);
-                    }
-                    if (kDot) dot_acc = fma(xc[h], sum, dot_acc);
-                    if constexpr (kCheb) {
-                        const long long lr = (long long)li * n + j;
-                        const double t = fma(-1.0, sum, cr[h]);
-                        const double u = cdv[h] * t;
-                        const double dn = fma(step.g, u, step.h * cd[h]);
-                        const double zn = xc[h] + dn;
-                        __builtin_nontemporal_store(dn, step.d + lr);
-                        step.z_out[lr] = zn;  // plain: the next step's neighbour loads re-use these lines
-                        if (step.last) dot_acc = fma(cr[h], zn, dot_acc);
-                    } else if (kInit) {
-                        const long long lr = (long long)li * n + j;
-                        const double rv = fma(-1.0, alpha * sum, bv[h]);
-                        if (res.r != nullptr) __builtin_nontemporal_store(rv, res.r + lr);  // null: r0 is stored once, as p0
-                        res.p[lr] = rv;  // plain: the next SpMV's neighbour loads re-use these lines
-                        dot_acc = fma(rv, rv, dot_acc);
-                    } else {
-                        __builtin_nontemporal_store(alpha * sum, y + ((long long)li * n + j));
-                    }
-                }
-            }
-        };
-        if constexpr (kSym) {
-            // the tile's class (requested by the caller next to the skip flag; the same value in every lane) is looked at here for
-            // the first time: the x loads, which do not depend on it, are out. A uniform tile loads no coefficient and keeps no LDS copy of E.
-            if (__builtin_amdgcn_readfirstlane(tile_class) != 0) {
-                if (skip != 0) return false;
-                finish(std::true_type{});
-            } else {
-                const long long r0 = (long long)li * n + j0 + lane;
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    ce[h] = d2{0.0, 0.0};
-                    cs[h] = cn[h] = 0.0;
-                    if (j0 + lane + 64 * h < n) {
-                        ce[h] = __builtin_nontemporal_load(reinterpret_cast<const d2*>(sp.ce) + r0 + 64 * h);
-                        cs[h] = sp.s[r0 + 64 * h];
-                        cn[h] = sp.s[r0 + 64 * h - n];  // local grid row 0: the halo row in front of the plane
-                    }
-                }
-                if (lane == 0 && j0 > 0) cw = sp.ce[2 * (r0 - 1) + 1];
-                if (skip != 0) return false;
-                finish(std::false_type{});
-            }
-        } else {
-            if (skip != 0) return false;
-            finish(std::false_type{});
-        }
-    } else {
-        // first / last grid row of the whole grid: every row the reference's way
-        if (skip != 0) return false;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int j = j0 + lane + 64 * h;
-            if (j < n) {
-                const long long lr = (long long)li * n + j;
-                const double sum = row_reference<false>(m, x, (int)lr, gi, j);
-                if (kDot) dot_acc = fma(x[lr], sum, dot_acc);
-                if constexpr (kCheb) {
-                    const double rl = step.r[lr];
-                    const double t = fma(-1.0, sum, rl);
-                    const double u = step.dinv[lr] * t;
-                    const double dn = fma(step.g, u, step.h * step.d[lr]);
-                    const double zn = x[lr] + dn;
-                    step.d[lr] = dn;
-                    step.z_out[lr] = zn;
-                    if (step.last) dot_acc = fma(rl, zn, dot_acc);
-                } else if (kInit) {
-                    const double rv = fma(-1.0, alpha * sum, res.b[lr]);
-                    if (res.r != nullptr) res.r[lr] = rv;
-                    res.p[lr] = rv;
-                    dot_acc = fma(rv, rv, dot_acc);
-                } else {
-                    y[lr] = alpha * sum;
-                }
-            }
-        }
-    }
-    if (kDot || kInit || kCheb) dot_acc = wave_sum(dot_acc);
-    *dot = dot_acc;  // lane 0 holds the tile's partial
-    return true;
-}
-
-// The class of the tile at (local grid row li, column tile col_tile): 1 = uniform (kernels.hpp, SymPlanes). One load per wave from
-// a wave-uniform address, indexed by the tile's real position in the slab (not the launch's tile number: launches over separate
-// grid rows and reversed sweeps see the same map). A byte load is a VECTOR-memory load on this part, and that is wanted: vector
-// loads return in order, so the tile's x loads can be issued behind it and the wave waits for this byte alone when it tests the
-// class (rowlds_tile makes the value a scalar there); a scalar load could only be waited for together with everything else the
-// scalar path has in flight, in front of the first x load. No map = every tile streams the planes.
-__device__ __forceinline__ int rowlds_tile_class(const SymPlanes& sp, int li, int col_tiles, int col_tile) {
-    return sp.cls != nullptr ? (int)sp.cls[li * col_tiles + col_tile] : 0;
-}
-
-// Tile of workgroup b in XCD runs of `run` tiles (xcd_run_tile, stencil_row_device.hpp); tiles past `total` do not exist (-1).
-__device__ __forceinline__ int rowlds_tile_of_block(int b, int run, int total, int reverse) {
-    const int tile = xcd_run_tile<int>(b, run);
-    if (tile >= total) return -1;
-    return reverse ? total - 1 - tile : tile;  // same tiles, same partial slots, walked from the end
 }
 
 template <int kMode>
@@ -456,502 +145,6 @@ __global__ __launch_bounds__(64) void stencil5_rowlds_zero_kernel(SlabCsr m, con
     else
         rowlds_tile<2, false, false, true>(m, x, nullptr, alpha, li, gfirst + li, col_tile * kLdsTileCols, (int)threadIdx.x, 0, strip, xrow, res, &dot);
     if (threadIdx.x == 0) dot_partials[tile] = dot;
-}
-
-// A block tile that is not fast (block map byte 0: a tile that streams the planes, the grid's first or last grid row, a short last
-// block): rowlds_tile once per grid row the block holds (block_rows, fewer at the range's end), with that row's own class, one partial per row in the one-row
-// kernel's slot. lds: 5 * 128 + 130 doubles (rowlds_tile's strip and x row). Returns false for a launch enqueued past convergence.
-__device__ __forceinline__ bool rowlds_block_slow_rows(const SlabCsr& m, const double* __restrict__ x, double* __restrict__ y, double alpha,
-                                                       int gi_lo, int gi_hi, int gfirst, int col_tiles, int li0, int block_rows, int col_tile, int j0, int lane, int skip,
-                                                       double* __restrict__ lds, double* __restrict__ dot_partials, const SymPlanes& sp) {
-    double* __restrict__ strip = lds;
-    double* __restrict__ xrow = lds + 5 * kLdsTileCols;
-    const ResidualOut none{nullptr, nullptr, nullptr};
-    const int held = gi_hi - li0 < block_rows ? gi_hi - li0 : block_rows;
-#pragma unroll 1
-    for (int r = 0; r < held; ++r) {
-        const int li = li0 + r;
-        const int uniform = rowlds_tile_class(sp, li, col_tiles, col_tile);
-        double dot = 0.0;
-        if (!rowlds_tile<1, false, true>(m, x, y, alpha, li, gfirst + li, j0, lane, skip, strip, xrow, none, &dot, sp, uniform)) return false;
-        if (lane == 0) dot_partials[(li - gi_lo) * col_tiles + col_tile] = dot;
-        wave_lds_sync();  // the next row rewrites the LDS this row's lanes have just read
-    }
-    return true;
-}
-
-// ---------------------------------------------------------------------------------
-// The in-loop SpMV of a solver slab over BLOCK TILES: one wave evaluates 128 columns of kRows consecutive local grid rows
-// [li0, li0 + kRows). On a uniform tile the one-row kernel moves 16 B/row of unique data (x in, y out) but requests every x value
-// three times (centre, north, south) from workgroups that mostly sit on different XCDs; a block tile reads its kRows + 2 rows of
-// x once each, 8 (kRows + 2) / kRows + 8 B/row. No rotation and no software pipeline: every load of the block is issued before
-// the first value is used, so a wave has 6-10 KB in flight.
-// block_map (one byte per block tile of THIS launch range, launch_block_map): 1 = the block holds kRows grid rows and every one
-// of its tiles is uniform (kernels.hpp, SymPlanes) -- the fast path: the fma chains of rowlds_tile<1, false, true> on a uniform
-// tile, W / E from an LDS copy of each row. 0 = the block calls rowlds_tile once per grid row it holds, with that row's own class.
-// Either way one partial of x . (A x) per 128 x 1 tile in the one-row kernel's slot, (li - gi_lo) * col_tiles + col_tile: the
-// reduction's shape and every bit of the sum stay what they were.
-// kStoreAp = false (LoopShape::first_recomputed, iteration 0 on a caller's x0): the fast path does not store A p0 -- the r update
-// behind it recomputes it (cg_update_r_recompute_kernel) -- and is the same code otherwise; the other path stores as ever.
-// ---------------------------------------------------------------------------------
-template <int kRows, bool kStoreAp = true>
-__global__ __launch_bounds__(64) void stencil5_rowlds_block_kernel(
-    SlabCsr m, const double* __restrict__ x, double* __restrict__ y, double alpha, int gi_lo, int gi_hi, int gfirst, int col_tiles,
-    int total_blocks, int run, int reverse, double* __restrict__ dot_partials, const int* __restrict__ skip_flag,
-    const unsigned char* __restrict__ block_map, SymPlanes sp) {
-    constexpr int kRowDoubles = kLdsTileCols + 2;
-    constexpr int kFastDoubles = kRows * kRowDoubles, kOneRowDoubles = 5 * kLdsTileCols + kRowDoubles;
-    // fast path: one x row copy per grid row of the block; the other path: rowlds_tile's strip and x row
-    __shared__ double lds[kFastDoubles > kOneRowDoubles ? kFastDoubles : kOneRowDoubles];
-    const int skip = skip_flag != nullptr ? __builtin_nontemporal_load(skip_flag) : 0;
-    const int block = rowlds_tile_of_block((int)blockIdx.x, run, total_blocks, reverse);
-    if (block < 0) return;
-    const int row_block = block / col_tiles;
-    const int col_tile = block - row_block * col_tiles;
-    const int li0 = gi_lo + row_block * kRows;
-    const int j0 = col_tile * kLdsTileCols, lane = (int)threadIdx.x;
-    const int n = m.grid_size;
-    const int fast = (int)block_map[block];  // a vector load, requested in front of the x loads and tested behind them (rowlds_tile_class)
-    // local grid rows of x that exist: the slab's own and the halo rows around it (SlabCsr). A fast block reads only such rows (its
-    // rows are global grid rows 1 .. n-2); the loads are issued before the map byte is known, so every block must stay inside.
-    const int row_lo = -(m.halo_before / n), row_hi = (m.n_local + m.halo_after) / n;
-    double xv[kRows + 2][2];  // rows li0 - 1 .. li0 + kRows, the lane's two columns
-    double xo[kRows];         // lane 0: the W neighbour left of the tile; lane 63: the E neighbour right of it
-#pragma unroll
-    for (int r = 0; r < kRows + 2; ++r) {
-        const int li = li0 - 1 + r;
-        xv[r][0] = xv[r][1] = 0.0;
-        if (li >= row_lo && li < row_hi) {
-            const double* __restrict__ xr = x + ((long long)li * n + j0);
-            if (j0 + lane < n) xv[r][0] = xr[lane];
-            if (j0 + lane + 64 < n) xv[r][1] = xr[lane + 64];
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < kRows; ++r) {
-        const int li = li0 + r;
-        xo[r] = 0.0;
-        if (li < row_hi) {
-            const double* __restrict__ xr = x + ((long long)li * n + j0);
-            if (lane == 0 && j0 > 0) xo[r] = xr[-1];
-            if (lane == 63 && j0 + kLdsTileCols < n) xo[r] = xr[kLdsTileCols];
-        }
-    }
-    if (__builtin_amdgcn_readfirstlane(fast) != 0) {
-        if (skip != 0) return;
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) {
-            lds[r * kRowDoubles + 1 + lane] = xv[r + 1][0];
-            lds[r * kRowDoubles + 65 + lane] = xv[r + 1][1];
-        }
-        wave_lds_sync();
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) {
-            const int li = li0 + r;
-            double xw[2], xe[2];
-            tile_west_east(lds + r * kRowDoubles, lane, j0, n, xo[r], xo[r], xw, xe);
-            double dot = 0.0;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int j = j0 + lane + 64 * h;
-                if (j < n) {
-                    const double xc = xv[r + 1][h], xn = xv[r][h], xs = xv[r + 2][h];
-                    const double sum = stencil5_row(j, n, sp.w, xw[h], sp.c, xc, sp.e, xe[h], sp.n, xn, sp.s5, xs);
-                    dot = fma(xc, sum, dot);
-                    if constexpr (kStoreAp) __builtin_nontemporal_store(alpha * sum, y + ((long long)li * n + j));
-                }
-            }
-            dot = wave_sum(dot);
-            if (lane == 0) dot_partials[(li - gi_lo) * col_tiles + col_tile] = dot;
-        }
-    } else {
-        rowlds_block_slow_rows(m, x, y, alpha, gi_lo, gi_hi, gfirst, col_tiles, li0, kRows, col_tile, j0, lane, skip, lds, dot_partials, sp);
-    }
-}
-
-// ---------------------------------------------------------------------------------
-// The direction update p' = r + beta p INSIDE the in-loop block SpMV (single-rank slabs, cg_slab.hip LoopShape::fused_direction):
-// one launch instead of cg_update_p_ring_kernel followed by stencil5_rowlds_block_kernel. Between the two there is no reduction
-// (beta is known before either starts), and p' was written once and read back (10.3 B/row measured) only because they were two
-// launches. Here a wave reads r and p_in on its kRows + 2 rows, evaluates direction() on all of them -- the two neighbour rows are
-// RE-computed, (kRows + 2) / kRows of the arithmetic, from p_in, which no wave of this launch writes (the ring's new slot is
-// p_out) -- stores its own kRows rows of p' and runs the block kernel's fast path on the values it holds: 16 (kRows + 2) / kRows
-// B/row read, 16 written. Same tile -> XCD relabelling, block map, grid and partial slots as the block kernel.
-// Scalars FIRST, as in cg_update_p_ring_kernel: the launch is enqueued before the host knows whether the iteration converged, and
-// the launch of the converging iteration (or of one past it) reads no vector.
-// A block that is not fast (map byte 0) only writes p' on the rows it holds; its A p' and partials come from
-// stencil5_block_list_kernel behind this launch, which reads p' from memory.
-// kStoreAp = false (LoopShape::ap_recomputed): the fast path does not store A p' -- the r update behind it recomputes it from p'
-// (cg_update_r_recompute_kernel) -- and is the same code otherwise: p', the LDS copy, the fma chains, the partials and their slots.
-// ---------------------------------------------------------------------------------
-template <int kRows, bool kStoreAp = true>
-__global__ __launch_bounds__(64) void stencil5_direction_block_kernel(
-    SlabCsr m, const CgScalars* __restrict__ s, int iteration, int fma_form, const double* __restrict__ rvec, const double* __restrict__ p_in,
-    double* __restrict__ p_out, double* __restrict__ y, double alpha, int gi_lo, int gi_hi, int col_tiles, int total_blocks, int run, int reverse,
-    double* __restrict__ dot_partials, const unsigned char* __restrict__ block_map, SymPlanes sp) {
-    constexpr int kRowDoubles = kLdsTileCols + 2;
-    __shared__ double lds[kRows * kRowDoubles];  // one p' row copy per grid row of the block
-    if (s->iterations != iteration || s->converged != 0) return;
-    const double beta = s->beta;
-    const int block = rowlds_tile_of_block((int)blockIdx.x, run, total_blocks, reverse);
-    if (block < 0) return;
-    const int row_block = block / col_tiles;
-    const int col_tile = block - row_block * col_tiles;
-    const int li0 = gi_lo + row_block * kRows;
-    const int j0 = col_tile * kLdsTileCols, lane = (int)threadIdx.x;
-    const int n = m.grid_size;
-    const int fast = (int)block_map[block];  // a vector load, requested in front of the r / p loads and tested behind them (rowlds_tile_class)
-    // r has no halo rows and this launch runs on slabs without neighbours only: rows outside [0, rows) are not requested
-    const int rows = m.n_local / n;
-    const bool in0 = j0 + lane < n, in1 = j0 + lane + 64 < n;
-    double rv[kRows + 2][2], pv[kRows + 2][2];  // rows li0 - 1 .. li0 + kRows, the lane's two columns
-    double ro[kRows], po[kRows];                // lane 0: the W neighbour left of the tile; lane 63: the E neighbour right of it
-#pragma unroll
-    for (int r = 0; r < kRows + 2; ++r) {
-        const int li = li0 - 1 + r;
-        rv[r][0] = rv[r][1] = pv[r][0] = pv[r][1] = 0.0;
-        if (li >= 0 && li < rows) {
-            const double* __restrict__ rr = rvec + ((long long)li * n + j0);
-            const double* __restrict__ pr = p_in + ((long long)li * n + j0);
-            if (in0) rv[r][0] = rr[lane], pv[r][0] = pr[lane];
-            if (in1) rv[r][1] = rr[lane + 64], pv[r][1] = pr[lane + 64];
-        }
-    }
-    // one load per vector and row from a per-lane address (lane 0: column j0 - 1, lane 63: column j0 + 128): a vector load like the
-    // rest, returned in order behind them (two branches on the lane number became scalar loads, each waited for on its own)
-    const bool outer = (lane == 0 && j0 > 0) || (lane == 63 && j0 + kLdsTileCols < n);
-    const int outer_col = lane == 0 ? -1 : kLdsTileCols + lane - 63;
-#pragma unroll
-    for (int r = 0; r < kRows; ++r) {
-        const int li = li0 + r;
-        ro[r] = po[r] = 0.0;
-        if (li < rows && outer) {
-            const long long at = (long long)li * n + j0 + outer_col;
-            ro[r] = rvec[at], po[r] = p_in[at];
-        }
-    }
-    if (__builtin_amdgcn_readfirstlane(fast) != 0) {
-        // p' on every row held (columns past n keep 0: what an absent neighbour contributes), then the block kernel's fast path on it
-#pragma unroll
-        for (int r = 0; r < kRows + 2; ++r) {
-            pv[r][0] = in0 ? direction(rv[r][0], beta, pv[r][0], fma_form) : 0.0;
-            pv[r][1] = in1 ? direction(rv[r][1], beta, pv[r][1], fma_form) : 0.0;
-        }
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) {
-            po[r] = outer ? direction(ro[r], beta, po[r], fma_form) : 0.0;
-            double* __restrict__ out = p_out + ((long long)(li0 + r) * n + j0);
-            if (in0) out[lane] = pv[r + 1][0];  // plain: the next launch's loads (and the flush) re-use these lines
-            if (in1) out[lane + 64] = pv[r + 1][1];
-            lds[r * kRowDoubles + 1 + lane] = pv[r + 1][0];
-            lds[r * kRowDoubles + 65 + lane] = pv[r + 1][1];
-        }
-        wave_lds_sync();
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) {
-            const int li = li0 + r;
-            double xw[2], xe[2];
-            tile_west_east(lds + r * kRowDoubles, lane, j0, n, po[r], po[r], xw, xe);
-            double dot = 0.0;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int j = j0 + lane + 64 * h;
-                if (j < n) {
-                    const double xc = pv[r + 1][h], xn = pv[r][h], xs = pv[r + 2][h];
-                    const double sum = stencil5_row(j, n, sp.w, xw[h], sp.c, xc, sp.e, xe[h], sp.n, xn, sp.s5, xs);
-                    dot = fma(xc, sum, dot);
-                    if constexpr (kStoreAp) __builtin_nontemporal_store(alpha * sum, y + ((long long)li * n + j));
-                }
-            }
-            dot = wave_sum(dot);
-            if (lane == 0) dot_partials[(li - gi_lo) * col_tiles + col_tile] = dot;
-        }
-    } else {
-        const int held = gi_hi - li0 < kRows ? gi_hi - li0 : kRows;
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) {
-            if (r < held) {
-                double* __restrict__ out = p_out + ((long long)(li0 + r) * n + j0);
-                if (in0) out[lane] = direction(rv[r + 1][0], beta, pv[r + 1][0], fma_form);
-                if (in1) out[lane + 64] = direction(rv[r + 1][1], beta, pv[r + 1][1], fma_form);
-            }
-        }
-    }
-}
-
-// A p' and its partials on the block tiles the launch above left out (`list`: the range's blocks whose map byte is 0, one workgroup
-// each): the block kernel's own path for such a block, on p' in memory. Same scalar test as the launch it follows.
-__global__ __launch_bounds__(64) void stencil5_block_list_kernel(SlabCsr m, const CgScalars* __restrict__ s, int iteration,
-                                                                 const double* __restrict__ x, double* __restrict__ y, double alpha, int gi_lo,
-                                                                 int gi_hi, int gfirst, int col_tiles, int block_rows, const int* __restrict__ list,
-                                                                 double* __restrict__ dot_partials, SymPlanes sp) {
-    __shared__ double lds[5 * kLdsTileCols + kLdsTileCols + 2];
-    if (s->iterations != iteration || s->converged != 0) return;
-    const int block = list[blockIdx.x];
-    const int row_block = block / col_tiles;
-    const int col_tile = block - row_block * col_tiles;
-    const int li0 = gi_lo + row_block * block_rows;
-    rowlds_block_slow_rows(m, x, y, alpha, gi_lo, gi_hi, gfirst, col_tiles, li0, block_rows, col_tile, col_tile * kLdsTileCols, (int)threadIdx.x, 0, lds, dot_partials, sp);
-}
-
-// ---------------------------------------------------------------------------------
-// The r update that RECOMPUTES A p' (single-rank slabs, LoopShape::ap_recomputed): r -= alpha A p' with the r.r partials,
-// where the fused launch above (kStoreAp = false) has not stored A p' on its fast blocks. A p' is a pure function of p', which is in
-// memory anyway: 8 B/row less written there, and here p' with its seam rows is read instead of A p'. The partials must be
-// cg_update_r_kernel's, one per 128 consecutive elements of the LINEAR index, so the block tiles are cut at those boundaries
-// (skew_geometry.hpp): one wave takes kRows chunks, the t-th chunk that starts in each grid row of its row block, lane l the pair
-// 2 l, 2 l + 1 of each as in cg_update_r_kernel. Where the row block is fast and every chunk of the wave lies inside its grid row,
-// all loads -- r and p' of the pair, p' at -n and +n, the two outer neighbours -- are issued before the scalars are looked at, W / E
-// come from the neighbouring lanes, and the sum is stencil5_row on the quintuple: the very chain the fused launch ran, whose store
-// was 1.0 * sum. Every other wave goes chunk by chunk and element by element (ap_at): a slow row block's A p' is read from Ap, where
-// stencil5_block_list_kernel stored it; a chunk that straddles two grid rows decides per element. Same tile -> XCD relabelling as
-// the fused launch, so that the seam rows are found in the L2 that read them. A launch past convergence only reads.
-// kFrom = true (LoopShape::first_recomputed, iteration 0): the out-of-place instance for r0 == p0 -- `p` is the one vector that is both
-// (b, or ring slot 0), `rvec` is only written: r = p0 - alpha A p0. The centre pair serves as r0 too, so r0 is not loaded a second
-// time; the chain and the fma are cg_update_r_from_kernel's on (the A p0 the first launch would have stored as 1.0 * sum, p0), as
-// are the odd last element and the early return. p0 has no rows outside [0, rows): `whole` keeps the -n / +n loads inside.
-// ---------------------------------------------------------------------------------
-// A p' at element i: read where its row block is slow, recomputed where it is fast (operands outside the grid are 0.0, and
-// stencil5_row ignores W in column 0 and E in column n - 1, as in the fused launch)
-__device__ __forceinline__ double ap_at(long long i, int n, int rows, int block_rows, const double* __restrict__ p, const double* __restrict__ Ap,
-                                        const unsigned char* __restrict__ row_fast, const SymPlanes& sp) {
-    const int li = (int)(i / n), j = (int)(i - (long long)li * n);
-    if (row_fast[li / block_rows] == 0) return Ap[i];
-    const double xw = j > 0 ? p[i - 1] : 0.0, xe = j < n - 1 ? p[i + 1] : 0.0;
-    const double xn = li > 0 ? p[i - n] : 0.0, xs = li < rows - 1 ? p[i + n] : 0.0;
-    return stencil5_row(j, n, sp.w, xw, sp.c, p[i], sp.e, xe, sp.n, xn, sp.s5, xs);
-}
-
-// two consecutive doubles: one 16-byte load where the address allows it (i +- n with an even n), else two 8-byte loads
-__device__ __forceinline__ d2 load_pair(const double* __restrict__ at, bool aligned) {
-    if (aligned) return *reinterpret_cast<const d2*>(at);
-    d2 v;
-    v.x = at[0], v.y = at[1];
-    return v;
-}
-
-template <int kRows, bool kFrom = false>
-__global__ __launch_bounds__(64) void cg_update_r_recompute_kernel(size_t elements, int n, int rows, const CgScalars* __restrict__ s,
-                                                                   const double* __restrict__ p, const double* __restrict__ Ap,
-                                                                   double* __restrict__ rvec, double* __restrict__ partials, int col_tiles,
-                                                                   int total_blocks, int run, int reverse,
-                                                                   const unsigned char* __restrict__ row_fast, SymPlanes sp) {
-    const int block = rowlds_tile_of_block((int)blockIdx.x, run, total_blocks, reverse);
-    if (block < 0) return;
-    const int row_block = block / col_tiles, t = block - row_block * col_tiles, lane = (int)threadIdx.x;
-    const long long chunks = slab::chunk_count(elements);
-    const size_t pairs = elements >> 1;
-    const int fast = (int)row_fast[row_block];  // a vector load, requested in front of the r / p' loads and tested behind them
-    slab::SkewChunk c[kRows];
-    // the unguarded -n / +n loads need grid rows above and below every row of the block (a fast block never holds the grid's first
-    // or last grid row; the loads are issued before the byte is known)
-    bool whole = row_block * kRows >= 1 && row_block * kRows + kRows <= rows - 1;
-#pragma unroll
-    for (int k = 0; k < kRows; ++k) {
-        c[k] = slab::skew_chunk(row_block, t, k, kRows, n, rows, chunks);
-        whole = whole && c[k].inside_row;
-    }
-    d2 rv[kRows], pc[kRows], pn[kRows], ps[kRows];
-    double po[kRows];  // lane 0: the W neighbour left of the chunk; lane 63: the E neighbour right of it
-    if (whole) {
-        const bool aligned = (n & 1) == 0;
-#pragma unroll
-        for (int k = 0; k < kRows; ++k) {
-            const size_t pair = (size_t)c[k].chunk * 64 + lane;
-            const double* __restrict__ at = p + 2 * pair;
-            if constexpr (!kFrom) rv[k] = load_once(rvec, pair);
-            pc[k] = *reinterpret_cast<const d2*>(at);  // plain: the rows below and above re-use these lines
-            if constexpr (kFrom) rv[k] = pc[k];         // r0 is p0: the centre pair serves as both
-            pn[k] = load_pair(at - n, aligned);
-            ps[k] = load_pair(at + n, aligned);
-        }
-#pragma unroll
-        for (int k = 0; k < kRows; ++k) {
-            const bool outer = (lane == 0 && c[k].start_col > 0) || (lane == 63 && c[k].start_col + slab::kChunk < n);
-            const long long at = c[k].chunk * slab::kChunk + (lane == 0 ? -1 : slab::kChunk + lane - 63);
-            po[k] = outer ? p[at] : 0.0;
-        }
-    }
-    const int converged = s->converged;
-    const double rr_old = s->rr_old, pAp = s->pAp;
-    if (converged) return;
-    const double alpha = rr_old / pAp;
-    if (whole && __builtin_amdgcn_readfirstlane(fast) != 0) {
-#pragma unroll
-        for (int k = 0; k < kRows; ++k) {
-            const double from_west = __shfl_up(pc[k].y, 1), from_east = __shfl_down(pc[k].x, 1);
-            const double xw = lane > 0 ? from_west : po[k], xe = lane < 63 ? from_east : po[k];
-            const int j = c[k].start_col + 2 * lane;
-            const double sum_x = stencil5_row(j, n, sp.w, xw, sp.c, pc[k].x, sp.e, pc[k].y, sp.n, pn[k].x, sp.s5, ps[k].x);
-            const double sum_y = stencil5_row(j + 1, n, sp.w, pc[k].x, sp.c, pc[k].y, sp.e, xe, sp.n, pn[k].y, sp.s5, ps[k].y);
-            d2 v = rv[k];
-            v.x = fma(-alpha, sum_x, v.x);
-            v.y = fma(-alpha, sum_y, v.y);
-            store_once(rvec, (size_t)c[k].chunk * 64 + lane, v);
-            double acc = fma(v.x, v.x, 0.0);
-            acc = fma(v.y, v.y, acc);
-            acc = wave_sum(acc);
-            if (lane == 0) partials[c[k].chunk] = acc;
-        }
-        return;
-    }
-#pragma unroll 1
-    for (int k = 0; k < kRows; ++k) {
-        const slab::SkewChunk ck = slab::skew_chunk(row_block, t, k, kRows, n, rows, chunks);
-        if (!ck.exists) continue;
-        const size_t pair = (size_t)ck.chunk * 64 + lane;
-        double acc = 0.0;
-        if (pair < pairs) {
-            const long long i = 2 * (long long)pair;
-            d2 v;
-            if constexpr (kFrom) v = *reinterpret_cast<const d2*>(p + i);
-            else v = load_once(rvec, pair);
-            v.x = fma(-alpha, ap_at(i, n, rows, kRows, p, Ap, row_fast, sp), v.x);
-            v.y = fma(-alpha, ap_at(i + 1, n, rows, kRows, p, Ap, row_fast, sp), v.y);
-            store_once(rvec, pair, v);
-            acc = fma(v.x, v.x, acc);
-            acc = fma(v.y, v.y, acc);
-        }
-        if ((elements & 1) && ck.chunk == 0 && lane == 0) {  // the odd last element, where cg_update_r_kernel adds it
-            const double rl = fma(-alpha, ap_at((long long)elements - 1, n, rows, kRows, p, Ap, row_fast, sp), (kFrom ? p : rvec)[elements - 1]);
-            rvec[elements - 1] = rl;
-            acc = fma(rl, rl, acc);
-        }
-        acc = wave_sum(acc);
-        if (lane == 0) partials[ck.chunk] = acc;
-    }
-}
-
-// ---------------------------------------------------------------------------------
-// Iteration 0's block SpMV of a solve whose p0 is b itself (cg_slab.hpp, LoopShape::b_is_p0): stencil5_rowlds_block_kernel on
-// x = b, over the same block tiles, tile -> XCD runs, block map and p.Ap partial slots, that also sums b . b -- one partial per
-// 128 x 1 tile in the same slot of `self_partials`, in the form rowlds_tile's kMode 2 sums r0 . r0: fma(v, v, acc) for the lane's
-// column `lane`, then `lane + 64`, then wave_sum. With r0 = b bit for bit both sums keep every bit that the launch of the initial
-// residual followed by the block kernel gives; the values are in registers here anyway. A kernel of its own, first in its solve
-// (no skip flag): the in-loop instances keep their code. kStoreAp = false (LoopShape::first_recomputed): as in the block kernel,
-// the fast path leaves y alone and writes only the two partials; rowlds_first_slow_rows stores A b on its rows as ever.
-// ---------------------------------------------------------------------------------
-// rowlds_block_slow_rows with the row's own partial of x . x beside it: the lane's two values are read again (the lines the row
-// has just pulled in) rather than handed out of rowlds_tile, which stays as it is.
-__device__ __forceinline__ void rowlds_first_slow_rows(const SlabCsr& m, const double* __restrict__ x, double* __restrict__ y, double alpha,
-                                                       int gi_lo, int gi_hi, int gfirst, int col_tiles, int li0, int block_rows, int col_tile, int j0, int lane,
-                                                       double* __restrict__ lds, double* __restrict__ dot_partials, double* __restrict__ self_partials,
-                                                       const SymPlanes& sp) {
-    double* __restrict__ strip = lds;
-    double* __restrict__ xrow = lds + 5 * kLdsTileCols;
-    const ResidualOut none{nullptr, nullptr, nullptr};
-    const int n = m.grid_size;
-    const int held = gi_hi - li0 < block_rows ? gi_hi - li0 : block_rows;
-#pragma unroll 1
-    for (int r = 0; r < held; ++r) {
-        const int li = li0 + r;
-        const int uniform = rowlds_tile_class(sp, li, col_tiles, col_tile);
-        double dot = 0.0;
-        rowlds_tile<1, false, true>(m, x, y, alpha, li, gfirst + li, j0, lane, 0, strip, xrow, none, &dot, sp, uniform);
-        double self = 0.0;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int j = j0 + lane + 64 * h;
-            if (j < n) {
-                const double v = x[(long long)li * n + j];
-                self = fma(v, v, self);
-            }
-        }
-        self = wave_sum(self);
-        if (lane == 0) {
-            dot_partials[(li - gi_lo) * col_tiles + col_tile] = dot;
-            self_partials[(li - gi_lo) * col_tiles + col_tile] = self;
-        }
-        wave_lds_sync();  // the next row rewrites the LDS this row's lanes have just read
-    }
-}
-
-template <int kRows, bool kStoreAp = true>
-__global__ __launch_bounds__(64) void stencil5_first_block_kernel(
-    SlabCsr m, const double* __restrict__ x, double* __restrict__ y, double alpha, int gi_lo, int gi_hi, int gfirst, int col_tiles,
-    int total_blocks, int run, int reverse, double* __restrict__ dot_partials, double* __restrict__ self_partials,
-    const unsigned char* __restrict__ block_map, SymPlanes sp) {
-    constexpr int kRowDoubles = kLdsTileCols + 2;
-    constexpr int kFastDoubles = kRows * kRowDoubles, kOneRowDoubles = 5 * kLdsTileCols + kRowDoubles;
-    __shared__ double lds[kFastDoubles > kOneRowDoubles ? kFastDoubles : kOneRowDoubles];  // the block kernel's, to the byte
-    const int block = rowlds_tile_of_block((int)blockIdx.x, run, total_blocks, reverse);
-    if (block < 0) return;
-    const int row_block = block / col_tiles;
-    const int col_tile = block - row_block * col_tiles;
-    const int li0 = gi_lo + row_block * kRows;
-    const int j0 = col_tile * kLdsTileCols, lane = (int)threadIdx.x;
-    const int n = m.grid_size;
-    const int fast = (int)block_map[block];  // requested in front of the x loads and tested behind them, as in the block kernel
-    // b has no halo rows: the rows of x that exist are the slab's own (the loads are issued before the map byte is known)
-    const int row_lo = -(m.halo_before / n), row_hi = (m.n_local + m.halo_after) / n;
-    double xv[kRows + 2][2];  // rows li0 - 1 .. li0 + kRows, the lane's two columns
-    double xo[kRows];         // lane 0: the W neighbour left of the tile; lane 63: the E neighbour right of it
-#pragma unroll
-    for (int r = 0; r < kRows + 2; ++r) {
-        const int li = li0 - 1 + r;
-        xv[r][0] = xv[r][1] = 0.0;
-        if (li >= row_lo && li < row_hi) {
-            const double* __restrict__ xr = x + ((long long)li * n + j0);
-            if (j0 + lane < n) xv[r][0] = xr[lane];
-            if (j0 + lane + 64 < n) xv[r][1] = xr[lane + 64];
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < kRows; ++r) {
-        const int li = li0 + r;
-        xo[r] = 0.0;
-        if (li < row_hi) {
-            const double* __restrict__ xr = x + ((long long)li * n + j0);
-            if (lane == 0 && j0 > 0) xo[r] = xr[-1];
-            if (lane == 63 && j0 + kLdsTileCols < n) xo[r] = xr[kLdsTileCols];
-        }
-    }
-    if (__builtin_amdgcn_readfirstlane(fast) != 0) {
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) {
-            lds[r * kRowDoubles + 1 + lane] = xv[r + 1][0];
-            lds[r * kRowDoubles + 65 + lane] = xv[r + 1][1];
-        }
-        wave_lds_sync();
-#pragma unroll
-        for (int r = 0; r < kRows; ++r) {
-            const int li = li0 + r;
-            double xw[2], xe[2];
-            tile_west_east(lds + r * kRowDoubles, lane, j0, n, xo[r], xo[r], xw, xe);
-            double dot = 0.0, self = 0.0;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int j = j0 + lane + 64 * h;
-                if (j < n) {
-                    const double xc = xv[r + 1][h], xn = xv[r][h], xs = xv[r + 2][h];
-                    const double sum = stencil5_row(j, n, sp.w, xw[h], sp.c, xc, sp.e, xe[h], sp.n, xn, sp.s5, xs);
-                    dot = fma(xc, sum, dot);
-                    self = fma(xc, xc, self);
-                    if constexpr (kStoreAp) __builtin_nontemporal_store(alpha * sum, y + ((long long)li * n + j));
-                }
-            }
-            dot = wave_sum(dot);
-            self = wave_sum(self);
-            if (lane == 0) {
-                dot_partials[(li - gi_lo) * col_tiles + col_tile] = dot;
-                self_partials[(li - gi_lo) * col_tiles + col_tile] = self;
-            }
-        }
-    } else {
-        rowlds_first_slow_rows(m, x, y, alpha, gi_lo, gi_hi, gfirst, col_tiles, li0, kRows, col_tile, j0, lane, lds, dot_partials, self_partials, sp);
-    }
-}
-
-// The block map of one launch range [gi_lo, gi_hi) (stencil5_rowlds_block_kernel): one thread per block tile.
-__global__ __launch_bounds__(kBlock) void block_map_kernel(const unsigned char* __restrict__ cls, int col_tiles, int gi_lo, int gi_hi,
-                                                           int block_rows, int total_blocks, unsigned char* __restrict__ out) {
-    const int block = (int)(blockIdx.x * (unsigned)kBlock + threadIdx.x);
-    if (block >= total_blocks) return;
-    const int row_block = block / col_tiles, col_tile = block - row_block * col_tiles;
-    const int li0 = gi_lo + row_block * block_rows;
-    bool fast = li0 + block_rows <= gi_hi;
-    for (int r = 0; fast && r < block_rows; ++r) fast = cls[(long long)(li0 + r) * col_tiles + col_tile] == 1;
-    out[block] = fast ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------------
@@ -1648,35 +841,7 @@ void launch_rowlds(const SlabCsr& m, const Stencil5Plan& p, const double* x, dou
     else SPMV_AMD_LAUNCH_ROWLDS(0);
 #undef SPMV_AMD_LAUNCH_ROWLDS
 }
-
-// the block kernel over the plan's block tiles (the in-loop SpMV of a solver slab; launch_stencil5_spmv decides)
-void launch_rowlds_block(const SlabCsr& m, const Stencil5Plan& p, const double* x, double* y, double alpha, double* d_dot_partials,
-                         const int* d_skip_flag, bool reverse, hipStream_t stream, const SymPlanes& sp, bool ap_not_stored) {
-    const int blocks = rowlds_block_tiles(p);
-    const dim3 grid((unsigned)xcd_padded_grid(blocks, p.xcd_run));
-    const int gfirst = m.row_offset / m.grid_size;
-#define SPMV_AMD_LAUNCH_ROWLDS_BLOCK(ROWS, STORE)                                                                                      \
-    hipLaunchKernelGGL((stencil5_rowlds_block_kernel<ROWS, STORE>), grid, dim3(64), 0, stream, m, x, y, alpha, p.gi_lo, p.gi_hi, gfirst, \
-                       p.row_blocks, blocks, p.xcd_run, reverse ? 1 : 0, d_dot_partials, d_skip_flag, p.block_map, sp)
-    if (p.block_rows == 4 && !ap_not_stored) SPMV_AMD_LAUNCH_ROWLDS_BLOCK(4, true);
-    else if (p.block_rows == 4) SPMV_AMD_LAUNCH_ROWLDS_BLOCK(4, false);
-    else if (!ap_not_stored) SPMV_AMD_LAUNCH_ROWLDS_BLOCK(8, true);
-    else SPMV_AMD_LAUNCH_ROWLDS_BLOCK(8, false);
-#undef SPMV_AMD_LAUNCH_ROWLDS_BLOCK
-}
 }  // namespace
-
-int rowlds_block_tiles(const Stencil5Plan& p) {
-    if (p.variant != Stencil5Variant::RowLds || p.block_rows <= 0 || p.gi_hi <= p.gi_lo) return 0;
-    return (p.gi_hi - p.gi_lo + p.block_rows - 1) / p.block_rows * p.row_blocks;
-}
-
-void launch_block_map(const unsigned char* cls, const Stencil5Plan& p, unsigned char* out, hipStream_t stream) {
-    const int blocks = rowlds_block_tiles(p);
-    if (blocks <= 0) return;
-    hipLaunchKernelGGL(block_map_kernel, dim3(blocks_for(blocks)), dim3(kBlock), 0, stream, cls, p.row_blocks, p.gi_lo, p.gi_hi, p.block_rows,
-                       blocks, out);
-}
 
 int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& p, const double* x, double* y, double alpha,
                          double* d_dot_partials, const int* d_skip_flag, bool reverse, hipStream_t stream,
@@ -1722,72 +887,6 @@ int launch_stencil5_spmv(const SlabCsr& m, const Stencil5Plan& p, const double* 
 #undef SPMV_AMD_LAUNCH_ROWS
     }
     return dot ? p.partials : 0;
-}
-
-int launch_stencil5_direction_spmv(const SlabCsr& m, const Stencil5Plan& p, const DirectionSpmv& d, double* y, double alpha,
-                                   double* d_dot_partials, bool reverse, hipStream_t stream, const SymPlanes& sp) {
-    const int blocks = rowlds_block_tiles(p);
-    if (blocks <= 0 || p.block_map == nullptr || d_dot_partials == nullptr || sp.cls == nullptr || (d.slow_count > 0 && d.slow_list == nullptr)) {
-        fprintf(stderr, "[spmv] the direction update inside the SpMV exists for row-lds plans with a block map only\n");
-        exit(EXIT_FAILURE);
-    }
-    const dim3 grid((unsigned)xcd_padded_grid(blocks, p.xcd_run));
-    const int gfirst = m.row_offset / m.grid_size;
-#define SPMV_AMD_LAUNCH_DIRECTION_BLOCK(ROWS, STORE)                                                                                      \
-    hipLaunchKernelGGL((stencil5_direction_block_kernel<ROWS, STORE>), grid, dim3(64), 0, stream, m, d.s, d.iteration, d.fma_form ? 1 : 0, \
-                       d.r, d.p_in, d.p_out, y, alpha, p.gi_lo, p.gi_hi, p.row_blocks, blocks, p.xcd_run, reverse ? 1 : 0, d_dot_partials, \
-                       p.block_map, sp)
-    if (p.block_rows == 4 && !d.ap_not_stored) SPMV_AMD_LAUNCH_DIRECTION_BLOCK(4, true);
-    else if (p.block_rows == 4) SPMV_AMD_LAUNCH_DIRECTION_BLOCK(4, false);
-    else if (!d.ap_not_stored) SPMV_AMD_LAUNCH_DIRECTION_BLOCK(8, true);
-    else SPMV_AMD_LAUNCH_DIRECTION_BLOCK(8, false);
-#undef SPMV_AMD_LAUNCH_DIRECTION_BLOCK
-    if (d.slow_count > 0)
-        hipLaunchKernelGGL(stencil5_block_list_kernel, dim3((unsigned)d.slow_count), dim3(64), 0, stream, m, d.s, d.iteration, d.p_out, y, alpha,
-                           p.gi_lo, p.gi_hi, gfirst, p.row_blocks, p.block_rows, d.slow_list, d_dot_partials, sp);
-    return p.partials;
-}
-
-int launch_cg_update_r_recompute(const SlabCsr& m, const Stencil5Plan& p, const CgScalars* s, const double* p_new, const double* Ap, double* r,
-                                 double* partials, const unsigned char* row_fast, bool reverse, hipStream_t stream, const SymPlanes& sp, bool r_is_p) {
-    const int blocks = rowlds_block_tiles(p);
-    if (blocks <= 0 || row_fast == nullptr || partials == nullptr || p.first_row != 0 || p.last_row != m.n_local || m.halo_before != 0 ||
-        m.halo_after != 0) {
-        fprintf(stderr, "[spmv] the recomputing r update exists for whole-slab row-lds plans with a block map on slabs without halo rows only\n");
-        exit(EXIT_FAILURE);
-    }
-    const dim3 grid((unsigned)xcd_padded_grid(blocks, p.xcd_run));
-    const int n = m.grid_size;
-#define SPMV_AMD_LAUNCH_R_RECOMPUTE(ROWS, FROM)                                                                                              \
-    hipLaunchKernelGGL((cg_update_r_recompute_kernel<ROWS, FROM>), grid, dim3(64), 0, stream, (size_t)m.n_local, n, m.n_local / n, s, p_new, Ap, r, \
-                       partials, p.row_blocks, blocks, p.xcd_run, reverse ? 1 : 0, row_fast, sp)
-    if (p.block_rows == 4 && !r_is_p) SPMV_AMD_LAUNCH_R_RECOMPUTE(4, false);
-    else if (p.block_rows == 4) SPMV_AMD_LAUNCH_R_RECOMPUTE(4, true);
-    else if (!r_is_p) SPMV_AMD_LAUNCH_R_RECOMPUTE(8, false);
-    else SPMV_AMD_LAUNCH_R_RECOMPUTE(8, true);
-#undef SPMV_AMD_LAUNCH_R_RECOMPUTE
-    return (int)slab::chunk_count((size_t)m.n_local);
-}
-
-int launch_stencil5_first_spmv(const SlabCsr& m, const Stencil5Plan& p, const double* b, double* y, double alpha, double* d_dot_partials,
-                               double* self_partials, bool reverse, hipStream_t stream, const SymPlanes& sp, bool ap_not_stored) {
-    const int blocks = rowlds_block_tiles(p);
-    if (blocks <= 0 || p.block_map == nullptr || d_dot_partials == nullptr || self_partials == nullptr || sp.cls == nullptr || m.halo_before != 0 ||
-        m.halo_after != 0) {
-        fprintf(stderr, "[spmv] the first SpMV on b exists for row-lds plans with a block map on slabs without halo rows only\n");
-        exit(EXIT_FAILURE);
-    }
-    const dim3 grid((unsigned)xcd_padded_grid(blocks, p.xcd_run));
-    const int gfirst = m.row_offset / m.grid_size;
-#define SPMV_AMD_LAUNCH_FIRST_BLOCK(ROWS, STORE)                                                                                       \
-    hipLaunchKernelGGL((stencil5_first_block_kernel<ROWS, STORE>), grid, dim3(64), 0, stream, m, b, y, alpha, p.gi_lo, p.gi_hi, gfirst, \
-                       p.row_blocks, blocks, p.xcd_run, reverse ? 1 : 0, d_dot_partials, self_partials, p.block_map, sp)
-    if (p.block_rows == 4 && !ap_not_stored) SPMV_AMD_LAUNCH_FIRST_BLOCK(4, true);
-    else if (p.block_rows == 4) SPMV_AMD_LAUNCH_FIRST_BLOCK(4, false);
-    else if (!ap_not_stored) SPMV_AMD_LAUNCH_FIRST_BLOCK(8, true);
-    else SPMV_AMD_LAUNCH_FIRST_BLOCK(8, false);
-#undef SPMV_AMD_LAUNCH_FIRST_BLOCK
-    return p.partials;
 }
 
 void launch_rows_plus_zero(const SlabCsr& m, int* d_bad, hipStream_t stream) {

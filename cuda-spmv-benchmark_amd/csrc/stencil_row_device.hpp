@@ -1,4 +1,4 @@
-// stencil_row_device.hpp -- what every 5-point-stencil kernel of the library (spmv_kernels.hip, spmm_kernels.hip) must do the
+// stencil_row_device.hpp -- what every 5-point-stencil kernel of the library (spmv_kernels.hip, stencil5_block_kernels.hip, spmm_kernels.hip) must do the
 // same way, bit for bit: the fma chain of one row, the workgroup -> tile relabelling over the XCDs, the ordering of a wave's
 // private LDS, and the W / E neighbour exchange through the LDS copy of a tile's x row.
 //
