@@ -163,13 +163,15 @@ DECLARED_SYMBOLS = [
     "spmv_amd_precond_create_multigrid3d", "spmv_amd_precond_multigrid_dimension",
     "spmv_amd_pcg_solve_device_multi", "spmv_amd_pcg_last_history_multi", "spmv_amd_pcg_multi_workspace_bytes",
     "spmv_amd_precond_create_multigrid_multi", "spmv_amd_precond_multigrid_max_rhs", "spmv_amd_precond_apply_device_multi",
+    "spmv_amd_precond_create_multigrid3d_multi",
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
 LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_cg_slab_block_map", "spmv_amd_cg_slab_slow_blocks",
                     "spmv_amd_cg_slab_direction_spmv", "spmv_amd_cg_slab_spmv_dot", "spmv_amd_cg_slab_initial_stage", "spmv_amd_cg_slab_first_stage", "spmv_amd_cg_slab_stored_b", "spmv_amd_cg_slab_update_r_stage", "spmv_amd_cg_slab_ap_form", "spmv_amd_cg_slab_update_r_from_stage", "spmv_amd_cg_slab_first_recompute_form", "spmv_amd_pcg_stage",
                     "spmv_amd_pcg_last_step_launches", "spmv_amd_cg_multi_stage",
                     "spmv_amd_pcg_last_multigrid_cycles", "spmv_amd_precond_multigrid_level_csr", "spmv_amd_mg_stage",
-                    "spmv_amd_pcg_multi_stage", "spmv_amd_mg_multi_stage"]
+                    "spmv_amd_pcg_multi_stage", "spmv_amd_mg_multi_stage", "spmv_amd_mg_multi_stage3d",
+                    "spmv_amd_mg3d_multi_level_product", "spmv_amd_precond_multigrid_level_spmm"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
 DECLARED_CXX_SYMBOLS = [
     "SPMV_CSR", "SPMV_STENCIL5_CSR", "SPMV_STENCIL7_CSR", "SPMV_STENCIL_HALO_MGPU", "SPMV_ELLPACK", "SPMV_STENCIL5_ELLPACK",
@@ -307,6 +309,12 @@ def lib():
         L.spmv_amd_mg_stage.restype = C.c_int
         L.spmv_amd_pcg_multi_stage.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(PcgMultiStageArgs)]
         L.spmv_amd_pcg_multi_stage.restype = C.c_int
+        L.spmv_amd_mg_multi_stage3d.argtypes = [C.c_char_p, C.c_int, C.POINTER(MgMultiStageArgs)]
+        L.spmv_amd_mg_multi_stage3d.restype = C.c_int
+        L.spmv_amd_mg3d_multi_level_product.argtypes = [C.c_char_p]
+        L.spmv_amd_mg3d_multi_level_product.restype = C.c_int
+        L.spmv_amd_precond_multigrid_level_spmm.argtypes = [C.c_void_p, C.c_int]
+        L.spmv_amd_precond_multigrid_level_spmm.restype = C.c_char_p
     L.spmv_amd_cg_slab_create.restype = C.c_void_p
     L.spmv_amd_cg_slab_create.argtypes = [C.POINTER(MatrixData), C.c_void_p]
     L.spmv_amd_cg_slab_create_stencil5.restype = C.c_void_p
@@ -707,6 +715,8 @@ def _pcg_lib():
         L.spmv_amd_pcg_multi_workspace_bytes.restype = C.c_size_t
         L.spmv_amd_precond_create_multigrid_multi.argtypes = [C.POINTER(SpmvOperator), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
         L.spmv_amd_precond_create_multigrid_multi.restype = C.c_void_p
+        L.spmv_amd_precond_create_multigrid3d_multi.argtypes = [C.POINTER(SpmvOperator), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.spmv_amd_precond_create_multigrid3d_multi.restype = C.c_void_p
         L.spmv_amd_precond_multigrid_max_rhs.argtypes = [C.c_void_p]
         L.spmv_amd_precond_multigrid_max_rhs.restype = C.c_int
         L.spmv_amd_precond_apply_device_multi.argtypes = [C.POINTER(SpmvOperator), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -788,6 +798,24 @@ class Precond:
             err.bad_row = bad.value
             raise err
         return cls(_handle=h, _n=op.rows)
+
+    @classmethod
+    def multigrid3d_multi(cls, op, smoother_degree=1, max_levels=0, max_rhs=8):
+        """spmv_amd_precond_create_multigrid3d_multi (stencil7-csr on a verified 7-point stencil only): the 3-D hierarchy with block
+        vectors of max_rhs columns."""
+        bad = C.c_int(-2)
+        h = _pcg_lib().spmv_amd_precond_create_multigrid3d_multi(op.op, smoother_degree, max_levels, max_rhs, C.byref(bad))
+        if not h:
+            err = ValueError(f"precond_create_multigrid3d_multi({op.name}, {smoother_degree}, {max_levels}, {max_rhs}) refused, bad_row = {bad.value}")
+            err.bad_row = bad.value
+            raise err
+        return cls(_handle=h, _n=op.rows)
+
+    def multigrid_level_spmm(self, level):
+        """The name of one level's SpMM plan in a hierarchy with block vectors (LAB build only; include/spmv_amd/lab.h)."""
+        if not is_lab():
+            raise RuntimeError("the level plans are read through the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        return lib().spmv_amd_precond_multigrid_level_spmm(self.handle, level).decode()
 
     def multigrid_max_rhs(self):
         """The columns a multigrid hierarchy's block vectors hold; 0 for a single-vector hierarchy or another kind."""
@@ -913,6 +941,23 @@ def mg_multi_stage(stage, k, args):
     if not is_lab():
         raise RuntimeError("the batched multigrid stages exist in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
     return lib().spmv_amd_mg_multi_stage(stage if stage is None else stage.encode(), int(k), None if args is None else C.byref(args))
+
+
+def mg_multi_stage3d(stage, k, args):
+    """spmv_amd_mg_multi_stage3d (LAB build only; include/spmv_amd/lab.h): one of the two launches a 3-D level adds to the batched
+    multigrid cycle, on the caller's device data `args` (MgMultiStageArgs, n = the fine grid of n^3 rows) points to; returns its return
+    code (0, or non-zero for a refusal)."""
+    if not is_lab():
+        raise RuntimeError("the batched multigrid stages exist in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+    return lib().spmv_amd_mg_multi_stage3d(stage if stage is None else stage.encode(), int(k), None if args is None else C.byref(args))
+
+
+def mg3d_multi_level_product(kind):
+    """spmv_amd_mg3d_multi_level_product (LAB build only): "auto", "csr" or "stencil7" as the block product of every level of the 3-D
+    block hierarchies made after the call; returns its return code."""
+    if not is_lab():
+        raise RuntimeError("the level product is chosen in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+    return lib().spmv_amd_mg3d_multi_level_product(kind if kind is None else kind.encode())
 
 
 def pcg_stage(stage, kind, args, scalars=None):

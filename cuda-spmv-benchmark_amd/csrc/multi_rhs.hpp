@@ -28,7 +28,8 @@ inline int slices_for(long long count) { return (int)((count + kReduceSlice - 1)
 
 // Which kernel family one multi-RHS product of an operator takes. The stencil kinds follow the operator's single-vector
 // variant (Stencil5Plan::variant), so a forced variant is honoured here too.
-enum class SpmmKind { StencilLds, StencilDirect, StencilGeneric, StencilCsrLoop, Csr };
+// Stencil7Lds: the block product of a complete 7-point level (stencil7_spmm.hip), made by plan_spmm_stencil7 only.
+enum class SpmmKind { StencilLds, StencilDirect, StencilGeneric, StencilCsrLoop, Csr, Stencil7Lds };
 
 struct SpmmPlan {
     SlabCsr m;                 // the operator's whole matrix (single GPU: row_offset 0, no halos)
@@ -37,6 +38,7 @@ struct SpmmPlan {
     int col_blocks = 0;        // StencilLds / StencilDirect: 256-column blocks per grid row
     int xcd_run = 1;           // StencilLds: consecutive blocks one XCD takes of every run of 8 * xcd_run
     long long blocks = 0;      // workgroups of one launch = dot-partial slots per column
+    int grid3 = 0;             // Stencil7Lds: n of the n^3 grid (m.grid_size means "2-D 5-point")
     const char* name = "";     // "spmm/stencil5-row-lds", ...
 };
 SpmmPlan plan_spmm(const SlabCsr& m, Stencil5Variant stencil_variant, bool csr_operator, int rows, int cols);
@@ -45,6 +47,12 @@ SpmmPlan plan_spmm(const SlabCsr& m, Stencil5Variant stencil_variant, bool csr_o
 // sum over the block's rows of X[row][j] * (A X)[row][j]. X and Y must be 8-byte aligned; 16-byte aligned X and Y with an
 // even k take 16-byte loads / stores.
 void launch_spmm(const SpmmPlan& plan, int k, const double* X, double* Y, double* d_partials, hipStream_t stream);
+// The block product of a verified complete 7-point CSR of an n^3 grid (stencil7_spmm.hip; m: a view of
+// stencil7_view): "spmm/stencil7-row-lds", one wave per 128 columns of a grid row, the coefficients read once for all k columns, per
+// column the bits of "spmm/csr". It forms no dot partials: launch_spmm on such a plan ignores d_partials. The level plans of the
+// batched 3-D multigrid hierarchy use it; the operator's own plan on stencil7-csr stays "spmm/csr".
+SpmmPlan plan_spmm_stencil7(const SlabCsr& m, int n);
+void launch_stencil7_spmm(const SpmmPlan& plan, int k, const double* X, double* Y, hipStream_t stream);
 
 // (k, n) column blocks <-> interleaved: dst[row * k + j] = src[j * n + row] and back.
 void launch_interleave(int k, size_t n, const double* src_columns, double* dst_interleaved, hipStream_t stream);

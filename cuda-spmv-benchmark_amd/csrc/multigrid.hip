@@ -331,7 +331,7 @@ struct MgHierarchy {
     std::vector<MgLevel> levels;
     int smoother_degree = 0;
     double* partials = nullptr;  // the r.z partials of level 0's last update
-    MgMulti* multi = nullptr;    // spmv_amd_precond_create_multigrid_multi: the levels' block vectors and SpMM plans (multigrid_multi.hip)
+    MgMulti* multi = nullptr;    // spmv_amd_precond_create_multigrid_multi / ..._multigrid3d_multi: the levels' block vectors and SpMM plans (multigrid_multi.hip)
     void release() {
         mg_multi_destroy(multi);
         multi = nullptr;
@@ -361,12 +361,13 @@ int mg_level_count(const MgHierarchy* h) { return (int)h->levels.size(); }
 MgLevelView mg_level_view(const MgHierarchy* h, int level) {
     const MgLevel& L = h->levels[(size_t)level];
     MgLevelView v;
-    v.n = L.n, v.rows = L.rows, v.degree = L.degree, v.view = &L.view, v.variant = L.plan.variant, v.dinv = L.dinv, v.coef = L.coef;
+    v.dim = L.dim, v.n = L.n, v.rows = L.rows, v.degree = L.degree, v.view = &L.view, v.variant = L.plan.variant, v.dinv = L.dinv, v.coef = L.coef;
     return v;
 }
 MgMulti* mg_multi_of(const MgHierarchy* h) { return h != nullptr ? h->multi : nullptr; }
 SlabCsr mg_stencil_view(int n, const int* row_ptr, const int* col_idx, const double* values) { return stencil_view(n, row_ptr, col_idx, values); }
 bool mg_verify_stencil5(SlabCsr& v) { return verified(v); }
+bool mg_verify_stencil7(SlabCsr& v, int n) { return verified(v, 3, n); }
 
 namespace {
 
@@ -455,7 +456,7 @@ bool finish_level(MgHierarchy* h, int l, const LaunchShape& shape, int* bad_row)
 }
 
 // The one creator: dim 2 for stencil5-csr (spmv_amd_precond_create_multigrid), dim 3 for stencil7-csr (..._multigrid3d). max_rhs > 0
-// (dim 2 only, ..._multigrid_multi): the hierarchy also gets block vectors of that many columns and an SpMM plan on every level.
+// (..._multigrid_multi, ..._multigrid3d_multi): the hierarchy also gets block vectors of that many columns and an SpMM plan on every level.
 SpmvAmdPrecond* create_multigrid(SpmvOperator* op, int dim, int smoother_degree, int max_levels, int* bad_row, int max_rhs = 0) {
     // argument checks: all before the first HIP call
     if (bad_row != nullptr) *bad_row = -1;
@@ -559,14 +560,24 @@ extern "C" SpmvAmdPrecond* spmv_amd_precond_create_multigrid3d(SpmvOperator* op,
     return create_multigrid(op, 3, smoother_degree, max_levels, bad_row);
 }
 
+// what the two block creators check of max_rhs: before any HIP call, like the creator's other argument checks
+static bool max_rhs_in_range(int max_rhs, int* bad_row) {
+    if (max_rhs >= 1 && max_rhs <= kMaxRhs) return true;
+    if (bad_row != nullptr) *bad_row = -1;
+    fprintf(stderr, "[PCG] multigrid: max_rhs %d is outside 1..%d: refused\n", max_rhs, kMaxRhs);
+    return false;
+}
+
 extern "C" SpmvAmdPrecond* spmv_amd_precond_create_multigrid_multi(SpmvOperator* op, int smoother_degree, int max_levels, int max_rhs,
                                                                    int* bad_row) {
-    if (max_rhs < 1 || max_rhs > kMaxRhs) {  // before any HIP call, like the creator's other argument checks
-        if (bad_row != nullptr) *bad_row = -1;
-        fprintf(stderr, "[PCG] multigrid: max_rhs %d is outside 1..%d: refused\n", max_rhs, kMaxRhs);
-        return nullptr;
-    }
+    if (!max_rhs_in_range(max_rhs, bad_row)) return nullptr;
     return create_multigrid(op, 2, smoother_degree, max_levels, bad_row, max_rhs);
+}
+
+extern "C" SpmvAmdPrecond* spmv_amd_precond_create_multigrid3d_multi(SpmvOperator* op, int smoother_degree, int max_levels, int max_rhs,
+                                                                     int* bad_row) {
+    if (!max_rhs_in_range(max_rhs, bad_row)) return nullptr;
+    return create_multigrid(op, 3, smoother_degree, max_levels, bad_row, max_rhs);
 }
 
 extern "C" int spmv_amd_precond_multigrid_max_rhs(const SpmvAmdPrecond* m) {

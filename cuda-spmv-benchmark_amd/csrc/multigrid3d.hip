@@ -12,6 +12,7 @@
 // -ffp-contract=off: the only fused multiply-adds are the explicit ones.
 #include "multigrid3d.hpp"
 
+#include "multigrid3d_device.hpp"
 #include "stencil_geometry.hpp"
 #include "stencil_row_device.hpp"
 #include "stream_device.hpp"
@@ -113,45 +114,7 @@ __device__ __forceinline__ double member_residual(const SlabCsr& m, const double
     return fma(-1.0, sum, r[row]);
 }
 
-// the row at column j of a grid row inside the cube from its strip slots (v = strip + 7 (j - j0)), in the CSR loop's order
-__device__ __forceinline__ double strip_row7(const double* __restrict__ v, int j, int n, double xd, double xn, double xw, double xc, double xe,
-                                             double xs, double xu) {
-    double sum;
-    if (j > 0 && j < n - 1) {  // [D,N,W,C,E,S,U]
-        sum = fma(v[0], xd, 0.0);
-        sum = fma(v[1], xn, sum);
-        sum = fma(v[2], xw, sum);
-        sum = fma(v[3], xc, sum);
-        sum = fma(v[4], xe, sum);
-        sum = fma(v[5], xs, sum);
-        return fma(v[6], xu, sum);
-    }
-    if (j == 0) {  // [D,N,C,E,S,U] at 1..6
-        sum = fma(v[1], xd, 0.0);
-        sum = fma(v[2], xn, sum);
-        sum = fma(v[3], xc, sum);
-        sum = fma(v[4], xe, sum);
-        sum = fma(v[5], xs, sum);
-        return fma(v[6], xu, sum);
-    }
-    sum = fma(v[0], xd, 0.0);  // j == n-1: [D,N,W,C,S,U] at 0..5
-    sum = fma(v[1], xn, sum);
-    sum = fma(v[2], xw, sum);
-    sum = fma(v[3], xc, sum);
-    sum = fma(v[4], xs, sum);
-    return fma(v[5], xu, sum);
-}
-
-// one grid row's tile of coefficients into registers: entries [0, `entries`) of the run that starts at vals
-__device__ __forceinline__ void load_strip(const double* __restrict__ vals, int lane, int entries, double (&c)[14]) {
-    if (entries == 7 * kTileCols) {
-#pragma unroll
-        for (int q = 0; q < 14; ++q) c[q] = __builtin_nontemporal_load(vals + 64 * q);
-    } else {
-#pragma unroll
-        for (int q = 0; q < 14; ++q) c[q] = 64 * q + lane < entries ? __builtin_nontemporal_load(vals + 64 * q) : 0.0;
-    }
-}
+// strip_row7 and load_strip (multigrid3d_device.hpp): a row sum from the strip slots of that row, one grid row's tile of coefficients
 
 __global__ __launch_bounds__(kWave) void residual_restrict3d_kernel(SlabCsr m, int n, const double* __restrict__ z, const double* __restrict__ r,
                                                                     double* __restrict__ rc, int nc, int col_tiles, int total_tiles, int run) {
@@ -247,12 +210,7 @@ __global__ __launch_bounds__(kWave) void residual_restrict3d_kernel(SlabCsr m, i
 }
 
 // ---- prolongation + correction: z = fma(2.0, e_c[agg(i)], z), z in place; one-wave workgroups, a 16-byte pair per lane ----
-__device__ __forceinline__ double coarse_at3d(const double* __restrict__ ec, unsigned flat, unsigned n, unsigned nc) {
-    const unsigned g = flat / n, j = flat - g * n;  // g = k n + i
-    const unsigned k = g / n, i = g - k * n;
-    return ec[((size_t)(k >> 1) * nc + (i >> 1)) * nc + (j >> 1)];
-}
-
+// coarse_at3d (multigrid3d_device.hpp): e_c at the aggregate of a flat fine row
 __global__ __launch_bounds__(kWave) void prolong_correct3d_kernel(unsigned rows, unsigned n, unsigned nc, const double* __restrict__ ec,
                                                                   double* __restrict__ z) {
     const unsigned i = blockIdx.x * kWave + threadIdx.x;

@@ -16,4 +16,12 @@ void launch_residual_restrict3d(const SlabCsr& m, int n, const double* z, const 
 // z = fma(2.0, e_c[agg(i)], z), z (16-byte aligned) in place
 void launch_prolong_correct3d(int n, const double* ec, double* z);
 
+// ---- the same two launches on block vectors of k = 1..8 row-interleaved columns (multigrid3d_multi.hip): the
+// batched cycle of multigrid_multi.hip and the LAB build's spmv_amd_mg_multi_stage3d make them. cols: the device column records (null:
+// every column is running); nothing is read or written once every column is done. Block vectors: 8-byte aligned, 16-byte accesses
+// wherever an address allows. ----
+struct PcgMultiColumn;
+void launch_residual_restrict3d_multi(int k, const SlabCsr& m, int n, const PcgMultiColumn* cols, const double* z, const double* r, double* rc);
+void launch_prolong_correct3d_multi(int k, int n, const PcgMultiColumn* cols, const double* ec, double* z);
+
 }  // namespace spmv_amd

@@ -1,8 +1,9 @@
 // multigrid_multi.hip -- kind "multigrid" of the batched preconditioned solver (pcg_multi.hip): the V(nu, nu) cycle of multigrid.hip on
 // block vectors of up to 8 interleaved columns (multi_rhs.hpp), for the 2-D hierarchy of stencil5-csr (DESIGN.md section 19;
-// include/spmv_amd/api.h states the algebra). The hierarchy, its coarse operators, dinv, bounds and coefficients are multigrid.hip's;
+// include/spmv_amd/api.h states the algebra) and, with the restriction and prolongation of multigrid3d_multi.hip in the place of the two
+// here, for the 3-D hierarchy of stencil7-csr (spmv_amd_precond_create_multigrid3d_multi). The hierarchy, its coarse operators, dinv, bounds and coefficients are multigrid.hip's;
 // spmv_amd_precond_create_multigrid_multi adds what is here: on every level above 0 the block vectors R, D, Z and W of max_rhs columns,
-// and on every level an SpmmPlan on the level's own view and Stencil5Plan variant. Level 0 works on its caller's vectors -- the solve's
+// and on every level an SpmmPlan on the level's own view and Stencil5Plan variant (a 3-D level: "spmm/csr"). Level 0 works on its caller's vectors -- the solve's
 // R, D, Z and AP buffer, or the block application's.
 //
 // A cycle's launch count does not depend on k: the columns share every launch, and the three launches that are multigrid's own read
@@ -24,7 +25,9 @@
 
 #include "multi_rhs.hpp"
 #include "multi_solve.hpp"
+#include "multigrid3d.hpp"
 #include "multigrid_device.hpp"
+#include "multigrid_multi_device.hpp"
 #include "precond.hpp"
 #include "stencil_geometry.hpp"
 #include "stencil_row_device.hpp"
@@ -43,55 +46,7 @@ constexpr int kTileCols = 128;  // fine columns of one residual-restriction tile
 constexpr int kFlat = 256;      // workgroup of the flat kernels
 constexpr int kChunk = 4;       // columns one pass of the restriction holds in registers: 12 * 4 doubles of z and r per lane
 
-template <int K>
-__device__ __forceinline__ bool any_running(const PcgMultiColumn* __restrict__ cols) {
-    if (cols == nullptr) return true;
-    bool running = false;
-#pragma unroll
-    for (int j = 0; j < K; ++j) running = running || cols[j].done == 0;
-    return running;
-}
-
-// A run of C consecutive doubles: 16-byte accesses over the part that is 16-byte aligned (decided by the address: an odd row of an odd n
-// with an odd K, or a block of odd K on an 8-byte pointer, starts 8 bytes off), 8-byte accesses at the ends.
-template <int C, bool kOnce>
-__device__ __forceinline__ void load_run(const double* __restrict__ p, double (&o)[C]) {
-    auto one = [&](int q) { o[q] = kOnce ? __builtin_nontemporal_load(p + q) : p[q]; };
-    auto two = [&](int q) {
-        const d2* at = reinterpret_cast<const d2*>(p + q);
-        const d2 t = kOnce ? __builtin_nontemporal_load(at) : *at;
-        o[q] = t.x, o[q + 1] = t.y;
-    };
-    if ((((uintptr_t)p >> 3) & 1) == 0) {  // uniform over a wave for every caller here; every register index is a constant
-#pragma unroll
-        for (int q = 0; q + 1 < C; q += 2) two(q);
-        if constexpr ((C & 1) != 0) one(C - 1);
-    } else {
-        one(0);
-#pragma unroll
-        for (int q = 1; q + 1 < C; q += 2) two(q);
-        if constexpr ((C & 1) == 0) one(C - 1);
-    }
-}
-
-template <int C>
-__device__ __forceinline__ void store_run(double* __restrict__ p, const double (&v)[C]) {  // plain: the next launch reads it
-    auto two = [&](int q) {
-        d2 t;
-        t.x = v[q], t.y = v[q + 1];
-        *reinterpret_cast<d2*>(p + q) = t;
-    };
-    if ((((uintptr_t)p >> 3) & 1) == 0) {
-#pragma unroll
-        for (int q = 0; q + 1 < C; q += 2) two(q);
-        if constexpr ((C & 1) != 0) p[C - 1] = v[C - 1];
-    } else {
-        p[0] = v[0];
-#pragma unroll
-        for (int q = 1; q + 1 < C; q += 2) two(q);
-        if constexpr ((C & 1) == 0) p[C - 1] = v[C - 1];
-    }
-}
+// any_running, load_run, store_run and the flat walk's FlatWalk, load_unit, store_unit: multigrid_multi_device.hpp
 
 // ---- residual + restriction in one launch, K columns ----
 // The tile, the strip, the fast-path test, the off-tile path and the XCD deal are residual_restrict_kernel's (multigrid.hip). A lane's
@@ -252,32 +207,6 @@ __global__ __launch_bounds__(kWave) void residual_restrict_multi_kernel(SlabCsr 
 
 // ---- the flat kernels: unit f = threadIdx.x + 256 i (i < P) of a workgroup's 256 rows is row f / P, columns (f % P) * V ... + V - 1,
 // V = 2 for even K (16-byte accesses), 1 else, P = K / V -- the walk of the batched solvers' vector kernels (multi_rhs_device.hpp) ----
-template <int K>
-struct FlatWalk {
-    static constexpr int V = K % 2 == 0 ? 2 : 1;
-    static constexpr int P = K / V;
-};
-
-template <int V>
-__device__ __forceinline__ void load_unit(const double* __restrict__ p, double (&o)[V]) {
-    if constexpr (V == 2) {
-        const d2 t = *reinterpret_cast<const d2*>(p);
-        o[0] = t.x, o[1] = t.y;
-    } else {
-        o[0] = p[0];
-    }
-}
-template <int V>
-__device__ __forceinline__ void store_unit(double* __restrict__ p, const double (&v)[V]) {
-    if constexpr (V == 2) {
-        d2 t;
-        t.x = v[0], t.y = v[1];
-        *reinterpret_cast<d2*>(p) = t;
-    } else {
-        p[0] = v[0];
-    }
-}
-
 // z[i][j] = fma(2.0, e_c[agg(i)][j], z[i][j]), z in place; the store is plain: the post-smoother's SpMM reads it
 template <int K>
 __global__ __launch_bounds__(kFlat) void prolong_correct_multi_kernel(long long rows, int n, int nc, const PcgMultiColumn* __restrict__ cols,
@@ -390,6 +319,22 @@ void mg_multi_destroy(MgMulti* mm) {
     delete mm;
 }
 
+// A 3-D level's block product: "spmm/stencil7-row-lds" (stencil7_spmm.hip) from this grid upward, below it the generic CSR gather
+// "spmm/csr" -- the kind of the operator's own multi-RHS plan on stencil7-csr. Both give the same bits. The LAB build can force either
+// kind on every level of the hierarchies made after the call (spmv_amd_mg3d_multi_level_product, lab.h): read here, when a hierarchy
+// is made, never on a launch path. The threshold is measured (tools/mg3d_multi_bench.py --products, k = 4): the
+// smallest measured grid from which the new kernel is faster with the two ranges apart; 96 and 128 are faster in the median only.
+constexpr int kStencil7SpmmMinGrid = 256;
+#ifdef SPMV_AMD_LAB
+static int g_forced_level_product = 0;  // 0: by the threshold; 1: spmm/csr; 2: spmm/stencil7-row-lds
+#endif
+static bool stencil7_level_product(int n) {
+#ifdef SPMV_AMD_LAB
+    if (g_forced_level_product != 0) return g_forced_level_product == 2;
+#endif
+    return n >= kStencil7SpmmMinGrid;
+}
+
 MgMulti* mg_multi_create(const MgHierarchy* h, int max_rhs) {
     MgMulti* mm = new MgMulti();
     mm->max_rhs = max_rhs;
@@ -397,7 +342,8 @@ MgMulti* mg_multi_create(const MgHierarchy* h, int max_rhs) {
     for (int l = 0; l < mg_level_count(h); ++l) {
         const MgLevelView v = mg_level_view(h, l);
         MgMulti::Level& L = mm->levels[(size_t)l];
-        L.plan = plan_spmm(*v.view, v.variant, false, v.rows, v.rows);
+        if (v.dim == 3) L.plan = stencil7_level_product(v.n) ? plan_spmm_stencil7(*v.view, v.n) : plan_spmm(*v.view, Stencil5Variant::Auto, true, v.rows, v.rows);
+        else L.plan = plan_spmm(*v.view, v.variant, false, v.rows, v.rows);
         if (l == 0) continue;
         const size_t count = (size_t)v.rows * (size_t)max_rhs;
         L.R = device_try_alloc<double>(count);
@@ -439,9 +385,15 @@ struct MultiCycle {
         for (int s = 1; s <= v.degree; ++s) step(v.coef[2 * s], v.coef[2 * s - 1], coarsest && top && s == v.degree);  // pre-smoothing / the solve
         if (coarsest) return;
         const MgMulti::Level& C = mm->levels[(size_t)l + 1];
-        stage_run(T, &StageTimers::t_spmv, [&] { launch_residual_restrict_multi(k, *v.view, cols, Z, R, C.R); });
+        stage_run(T, &StageTimers::t_spmv, [&] {
+            if (v.dim == 3) launch_residual_restrict3d_multi(k, *v.view, v.n, cols, Z, R, C.R);
+            else launch_residual_restrict_multi(k, *v.view, cols, Z, R, C.R);
+        });
         level(l + 1, C.R, C.D, C.Z, C.W);
-        stage_run(T, &StageTimers::t_blas, [&] { launch_prolong_correct_multi(k, v.n, cols, C.Z, Z); });
+        stage_run(T, &StageTimers::t_blas, [&] {
+            if (v.dim == 3) launch_prolong_correct3d_multi(k, v.n, cols, C.Z, Z);
+            else launch_prolong_correct_multi(k, v.n, cols, C.Z, Z);
+        });
         step(v.coef[0], 0.0, top && v.degree == 0);  // post-smoothing from the guess z: term 0 in step form
         for (int s = 1; s <= v.degree; ++s) step(v.coef[2 * s], v.coef[2 * s - 1], top && s == v.degree);
     }
@@ -533,6 +485,20 @@ extern "C" int spmv_amd_precond_apply_device_multi(SpmvOperator* op, const SpmvA
 }
 
 #ifdef SPMV_AMD_LAB
+extern "C" int spmv_amd_mg3d_multi_level_product(const char* kind) {
+    if (kind != nullptr && !strcmp(kind, "auto")) spmv_amd::g_forced_level_product = 0;
+    else if (kind != nullptr && !strcmp(kind, "csr")) spmv_amd::g_forced_level_product = 1;
+    else if (kind != nullptr && !strcmp(kind, "stencil7")) spmv_amd::g_forced_level_product = 2;
+    else return fail("level product: not one of auto, csr, stencil7: refused"), 1;
+    return 0;
+}
+
+extern "C" const char* spmv_amd_precond_multigrid_level_spmm(const SpmvAmdPrecond* m, int level) {
+    const MgMulti* mm = m != nullptr && m->kind == kMultigrid ? mg_multi_of(m->mg) : nullptr;
+    if (mm == nullptr || level < 0 || level >= (int)mm->levels.size()) return "none";
+    return mm->levels[(size_t)level].plan.name;
+}
+
 static_assert(sizeof(SpmvAmdPcgMultiColumn) == sizeof(PcgMultiColumn), "lab.h's column record is the device record");
 
 extern "C" int spmv_amd_mg_multi_stage(const char* stage, int k, SpmvAmdMgMultiStageArgs* a) {

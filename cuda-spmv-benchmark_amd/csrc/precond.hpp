@@ -93,6 +93,7 @@ double* mg_result_vector(MgHierarchy* h);  // a level-0 vector of the hierarchy 
 // ---- the hierarchy on block vectors (multigrid_multi.hip) ----
 // What the batched cycle reads of one level; the pointers are the hierarchy's.
 struct MgLevelView {
+    int dim = 2;             // 2: an n x n 5-point stencil; 3: an n x n x n 7-point one
     int n = 0, rows = 0;     // the grid and its rows
     int degree = 0;          // Chebyshev steps of the level's smoother (the coarsest level: of its solve)
     const SlabCsr* view = nullptr;
@@ -102,7 +103,8 @@ struct MgLevelView {
 };
 int mg_level_count(const MgHierarchy* h);
 MgLevelView mg_level_view(const MgHierarchy* h, int level);
-// The block vectors and SpMM plans of a hierarchy made by spmv_amd_precond_create_multigrid_multi (null: a single-vector hierarchy).
+// The block vectors and SpMM plans of a hierarchy made by spmv_amd_precond_create_multigrid_multi or ..._multigrid3d_multi (null: a
+// single-vector hierarchy).
 struct MgMulti;
 MgMulti* mg_multi_of(const MgHierarchy* h);
 int mg_multi_capacity(const MgMulti* mm);  // max_rhs; 0 for null
@@ -121,5 +123,7 @@ void mg_cycle_multi(const MgHierarchy* h, int k, const PcgMultiColumn* cols, con
 // A complete 5-point CSR on an n x n grid in the caller's arrays as a view, and its structure check (synchronises; sets the view's flag).
 SlabCsr mg_stencil_view(int n, const int* row_ptr, const int* col_idx, const double* values);
 bool mg_verify_stencil5(SlabCsr& v);
+// The structure check of a complete 7-point CSR on an n^3 grid (a view of stencil7_view, multigrid3d.hpp); synchronises.
+bool mg_verify_stencil7(SlabCsr& v, int n);
 
 }  // namespace spmv_amd

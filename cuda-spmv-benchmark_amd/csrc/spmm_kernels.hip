@@ -402,6 +402,7 @@ SpmmPlan plan_spmm(const SlabCsr& m, Stencil5Variant stencil_variant, bool csr_o
 
 void launch_spmm(const SpmmPlan& p, int k, const double* X, double* Y, double* d_partials, hipStream_t stream) {
     if (p.rows == 0 || p.blocks == 0) return;
+    if (p.kind == SpmmKind::Stencil7Lds) return launch_stencil7_spmm(p, k, X, Y, stream);  // no partials: the cycle passes none
     dispatch_k(k, [&](auto K) { launch_k<decltype(K)::value>(p, X, Y, d_partials, stream); });  // k outside 1..8: nothing
 }
 

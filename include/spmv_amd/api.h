@@ -394,15 +394,26 @@ int spmv_amd_precond_multigrid_dimension(const SpmvAmdPrecond* m);
  * level's own view and launch variant. max_rhs outside 1..8 is refused before any HIP call like the other arguments. Everything is sized
  * against the device's free memory first; a refusal leaves no device memory behind. The handle is also a complete single-vector multigrid
  * handle: spmv_amd_pcg_solve_device, spmv_amd_precond_apply_device, ..._multigrid_info and ..._multigrid_dimension work on it, bit for
- * bit as on a handle of spmv_amd_precond_create_multigrid. Only the 2-D hierarchy of "stencil5-csr" has this form: the 3-D hierarchy of
- * "stencil7-csr" (spmv_amd_precond_create_multigrid3d) has no block vectors, and "stencil7-csr" is refused here as by the 2-D creator. */
+ * bit as on a handle of spmv_amd_precond_create_multigrid. This creator makes the 2-D hierarchy of "stencil5-csr": "stencil7-csr" is
+ * refused here as by the 2-D creator; the 3-D hierarchy with block vectors is spmv_amd_precond_create_multigrid3d_multi's. */
 SpmvAmdPrecond* spmv_amd_precond_create_multigrid_multi(SpmvOperator* op, int smoother_degree, int max_levels, int max_rhs, int* bad_row);
-/* The capacity max_rhs of such a handle; 0 for NULL, for another kind and for a handle of spmv_amd_precond_create_multigrid or
- * ..._multigrid3d. */
+/* The same for "stencil7-csr" (csrc/multigrid3d_multi.hip): it is spmv_amd_precond_create_multigrid3d in every
+ * respect -- levels, coarse operators, dinv, bounds, coefficients, refusals and their order, *bad_row --, with max_rhs outside 1..8
+ * refused before any HIP call, and in addition its hierarchy holds the block vectors R, D, Z and W of max_rhs row-interleaved columns on
+ * every level above 0 and one SpMM plan per level ("spmm/csr", the kind of the operator's own multi-RHS plan), their bytes sized with
+ * everything else against the device's free memory before anything is allocated. Per column the batched cycle is steps (1) to (5) of
+ * spmv_amd_precond_create_multigrid3d's text element for element: every row of every product is the CSR loop, the coarse sum runs in
+ * the order (((((((t000 + t001) + t010) + t011) + t100) + t101) + t110) + t111) over the members that exist, the correction is
+ * z = fma(2.0, e_c[agg(i)], z). The handle is also a complete single-vector 3-D handle: spmv_amd_pcg_solve_device,
+ * spmv_amd_precond_apply_device, ..._multigrid_info and ..._multigrid_dimension (3) work on it, bit for bit as on a handle of
+ * spmv_amd_precond_create_multigrid3d. */
+SpmvAmdPrecond* spmv_amd_precond_create_multigrid3d_multi(SpmvOperator* op, int smoother_degree, int max_levels, int max_rhs, int* bad_row);
+/* The capacity max_rhs of a handle of the two creators above; 0 for NULL, for another kind and for a handle of
+ * spmv_amd_precond_create_multigrid or ..._multigrid3d. */
 int spmv_amd_precond_multigrid_max_rhs(const SpmvAmdPrecond* m);
 /* Z = M^-1 R on device blocks of nrhs (1..8) row-interleaved columns of n rows (16-byte aligned), for every kind the batched solver
- * accepts: "none" (copy), "jacobi", "chebyshev", and "multigrid" from spmv_amd_precond_create_multigrid_multi with nrhs <= max_rhs.
- * The checks are those of spmv_amd_precond_apply_device, plus nrhs and the capacity, all before any HIP call ([PCG-MULTI] sentences;
+ * accepts: "none" (copy), "jacobi", "chebyshev", and "multigrid" from spmv_amd_precond_create_multigrid_multi or
+ * ..._multigrid3d_multi with nrhs <= max_rhs. The checks are those of spmv_amd_precond_apply_device, plus nrhs and the capacity, all before any HIP call ([PCG-MULTI] sentences;
  * "chebyshev" and "multigrid" need the operator's multi-RHS path). d_R is only read; d_Z must not overlap it. Work vectors that are not
  * the hierarchy's live for the call only. Synchronises. Column j of d_Z has exactly the bits spmv_amd_precond_apply_device gives for
  * column j alone: both run the operator's own product bits and the same element-wise fma forms (the fused row-lds step of the single
@@ -431,7 +442,7 @@ void spmv_amd_pcg_release_workspace(void);
 
 /* ---- preconditioned CG for several right-hand sides (csrc/pcg_multi.hip) ----
  * nrhs (1..8) INDEPENDENT preconditioned solves on one operator under one preconditioner of kind "none", "jacobi" (a from-diagonal one
- * included), "chebyshev", or "multigrid" from spmv_amd_precond_create_multigrid_multi with nrhs <= max_rhs: per column exactly the algebra, stopping rule and breakdown rule of spmv_amd_pcg_solve_device, with the
+ * included), "chebyshev", or "multigrid" from spmv_amd_precond_create_multigrid_multi or ..._multigrid3d_multi with nrhs <= max_rhs: per column exactly the algebra, stopping rule and breakdown rule of spmv_amd_pcg_solve_device, with the
  * arguments, statistics, timers and verbose semantics of spmv_amd_cg_solve_device_multi (B, X: host, nrhs vectors of mat->rows values
  * one after the other, X in = x0; stats: nrhs records; verbose lines tagged [PCG-MULTI j]). Only the SpMM and dinv are shared: the
  * operator must have the multi-RHS path ("stencil5-csr" in every variant, "stencil7-csr", "cusparse-csr").
@@ -446,7 +457,8 @@ void spmv_amd_pcg_release_workspace(void);
  * order, then a 256-wide tree), the slice sums the same way. Every value of column j has the same bits whatever nrhs is and whatever
  * slot the column sits in, and with kind "none" a solve without a breakdown has the bits of spmv_amd_cg_solve_device_multi. (The
  * single-RHS spmv_amd_pcg_solve_device sums in another shape: the two agree to rounding, not bit for bit.)
- * Kind "multigrid": z = one V(nu, nu) cycle, steps (1)-(5) of spmv_amd_precond_create_multigrid's text element for element, per column
+ * Kind "multigrid": z = one V(nu, nu) cycle, steps (1)-(5) of spmv_amd_precond_create_multigrid's text (a 3-D hierarchy: of
+ * ..._multigrid3d's) element for element, per column
  * the algebra of spmv_amd_pcg_solve_device with that kind, the dot products in the shape above. Unlike the single-RHS loop there is no
  * host read before the cycle; the iteration has the "chebyshev" shape: SpMM, step 1, the r update (which writes term 0 of level 0 into D
  * and Z), the verdict, the rest of the cycle, beta, the x / p update, the one read of the column records. In the iteration in which the
@@ -457,8 +469,8 @@ void spmv_amd_pcg_release_workspace(void);
  * (kind "multigrid": of its X, R, P, history, count and record; D, Z and the hierarchy's level vectors are scratch for stopped columns).
  * Refused before the first HIP call, with a [PCG-MULTI] sentence on stderr and a non-zero return: nrhs outside 1..8, a NULL
  * argument, max_iters < 0, an operator without the multi-RHS path or used before init, a system that is not square or not of
- * mat->rows rows, kind "multigrid" from spmv_amd_precond_create_multigrid or ..._multigrid3d (its hierarchy holds single vectors; the
- * 3-D hierarchy has no batched form), nrhs above a block hierarchy's max_rhs (the sentence names both), a preconditioner of another size, of another operator or
+ * mat->rows rows, kind "multigrid" from spmv_amd_precond_create_multigrid or ..._multigrid3d (its hierarchy holds single vectors: the
+ * block creators ..._multigrid_multi and ..._multigrid3d_multi make the batched form), nrhs above a block hierarchy's max_rhs (the sentence names both), a preconditioner of another size, of another operator or
  * from before the operator's last init or free. The workspace (X, R, P, AP; "chebyshev": D and Z too; partials, column records,
  * histories) is sized against the device's free memory first and refused with a sentence if it does not fit; it is kept between
  * calls and released with the other CG workspaces (an operator's free(), spmv_amd_cg_release_workspace(),

@@ -357,6 +357,21 @@ typedef struct SpmvAmdMgMultiStageArgs {
  * array, dinv or cols that are not 4- / 8-byte aligned; after the structure check (as spmv_amd_mg_stage makes it): a CSR that is not the
  * complete stencil. Returns 0 otherwise. */
 int spmv_amd_mg_multi_stage(const char* stage, int k, SpmvAmdMgMultiStageArgs* a);
+/* The two launches a 3-D level adds to the batched cycle (csrc/multigrid3d_multi.hip), on the same arguments: n is
+ * the fine grid of n^3 rows, row_ptr / col_idx / values a complete 7-point stencil of it, coarse has ((n + 1) / 2)^3 rows. stage:
+ * "residual_restrict3d", "prolong3d" (term 0 has no 3-D form: "term0" of spmv_amd_mg_multi_stage is a flat walk over the rows); and a
+ * 3-D level's block product d = A z on the same CSR in its two kinds, "stencil7_spmm" ("spmm/stencil7-row-lds", csrc/stencil7_spmm.hip)
+ * and "spmm_csr" ("spmm/csr"): z in, d out, n^3 rows each, the column records are not read. The checks are spmv_amd_mg_multi_stage's
+ * with n in 2..674, all before any HIP call with a [PCG-MULTI] sentence, and the 7-point structure check as spmv_amd_mg_stage makes it
+ * for its 3d stages behind them. Returns 0 otherwise. */
+int spmv_amd_mg_multi_stage3d(const char* stage, int k, SpmvAmdMgMultiStageArgs* a);
+/* The block product the levels of the 3-D hierarchies made AFTER this call get (spmv_amd_precond_create_multigrid3d_multi): "auto" (the
+ * default: "spmm/stencil7-row-lds" from the threshold grid upward, "spmm/csr" below it), "csr" or "stencil7" on every level. Read when a
+ * hierarchy is made, never on a launch path. Non-zero, with a [PCG-MULTI] sentence, for any other word. */
+int spmv_amd_mg3d_multi_level_product(const char* kind);
+/* The name of one level's SpMM plan in a hierarchy with block vectors ("spmm/csr", "spmm/stencil7-row-lds", "spmm/stencil5-row-lds",
+ * ...); "none" for NULL, another kind, a single-vector hierarchy or a level that does not exist. */
+const char* spmv_amd_precond_multigrid_level_spmm(const SpmvAmdPrecond* m, int level);
 
 #ifdef __cplusplus
 }
