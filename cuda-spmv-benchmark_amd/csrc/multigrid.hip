@@ -10,6 +10,8 @@
 // section 14's Chebyshev application of degree nu on [lambda_max / 4, lambda_max]; the coarsest level is solved by degree 8 on
 // [lambda_max / 30, lambda_max] from a zero guess.
 //
+// The hierarchy (MgLevel, MgHierarchy) and the declarations of every launch are multigrid.hpp's; the order of a cycle's launches is
+// mg_schedule.hpp's mg_vcycle, which CycleOps here and MultiOps in multigrid_multi.hip walk.
 // Cycle on level l (input r, output z):
 //   pre-smooth   term 0 and nu steps of the application
 //   restrict     r_c[I, J] = ((t00 + t01) + t10) + t11 over the members that exist, t = fma(-1.0, (A z)_i, r_i): ONE launch
@@ -29,10 +31,10 @@
 
 #include <vector>
 
+#include "mg_schedule.hpp"
 #include "multi_rhs.hpp"
-#include "multigrid3d.hpp"
+#include "multigrid.hpp"
 #include "multigrid_device.hpp"
-#include "precond.hpp"
 #include "stencil_geometry.hpp"
 #include "stencil_row_device.hpp"
 #include "stream_device.hpp"
@@ -46,15 +48,28 @@ namespace {
 
 constexpr hipStream_t kStream = nullptr;  // default stream, shared with the operators and pcg.hip
 constexpr int kWave = 64;
-constexpr int kTileCols = 128;      // fine columns of one residual-restriction tile: lane l owns aggregate column l of the tile
-constexpr int kCoarsestGrid = 8;    // coarsening stops at the first grid of at most this
-constexpr int kCoarsestDegree = 8;  // the coarsest level's Chebyshev degree
+constexpr int kCoarsestGrid = 8;  // coarsening stops at the first grid of at most this
 constexpr int kMaxSmoother = 8;
 constexpr int kMaxLevels = 32;
 
 bool fail(const char* what) {
     fprintf(stderr, "[PCG] multigrid: %s\n", what);
     return false;
+}
+
+// the structure check of a level's view: the complete 5-point pattern of v.grid_size (dim 2), the complete 7-point one of n^3 (dim 3)
+bool verified(SlabCsr& v, int dim = 2, int n = 0) {
+    int* d_mismatch = device_try_alloc<int>(1);
+    if (d_mismatch == nullptr) return fail("no device memory for the structure check");
+    HIP_CHECK(hipMemsetAsync(d_mismatch, 0, sizeof(int), kStream));
+    if (dim == 3) launch_verify_stencil7_csr(v, n, d_mismatch, kStream);
+    else launch_verify_stencil5_csr(v, d_mismatch, kStream);
+    HIP_CHECK(hipGetLastError());
+    int mismatch = 1;
+    download(&mismatch, d_mismatch, 1);  // synchronises
+    device_release(d_mismatch);
+    if (dim == 2) v.verified_stencil = mismatch == 0;  // the view's flag means "2-D 5-point"
+    return mismatch == 0;
 }
 
 // ---- coarsening: one thread per coarse row; set-up work ----
@@ -112,49 +127,15 @@ __global__ __launch_bounds__(256) void coarsen_kernel(SlabCsr fine, int n, int n
 // z[col[k]], sum), ascending k), their interior partner takes its chain -- the bits stencil5-csr's SpMV gives for each row.
 // Tiles are dealt to the XCDs in runs (xcd_run_tile); the launcher pads the grid.
 
-// z or r at (row i, columns ja, ja + 1) of an n x n grid; has_b: column ja + 1 exists
-template <bool kOnce>
-__device__ __forceinline__ d2 load_pair(const double* __restrict__ v, long long at, bool has_b) {
-    d2 out;
-    if (has_b && (at & 1) == 0) {
-        out = kOnce ? __builtin_nontemporal_load(reinterpret_cast<const d2*>(v + at)) : *reinterpret_cast<const d2*>(v + at);
-    } else {
-        out.x = kOnce ? __builtin_nontemporal_load(v + at) : v[at];
-        out.y = 0.0;
-        if (has_b) out.y = kOnce ? __builtin_nontemporal_load(v + at + 1) : v[at + 1];
-    }
-    return out;
-}
-
-// t = fma(-1.0, sum, r) of row (i, j) for the row pairs off the fast path, with the sum stencil5-csr's SpMV gives for that row: grid
-// rows 0 and n-1 walk the CSR in loop order, an interior grid row (the partner of grid row 0 or n-1 in its pair) takes its chain on the
-// row's own CSR entries ([N,W,C,E,S]; column 0: [N,C,E,S]; column n-1: [N,W,C,S]).
-__device__ __forceinline__ double residual_off_tile(const SlabCsr& m, const double* __restrict__ z, const double* __restrict__ r, int i, int j) {
-    const int n = m.grid_size, row = i * n + j;
-    double sum;
-    if (i > 0 && i < n - 1) {
-        const double* __restrict__ v = m.values + m.row_ptr[row];
-        const double* __restrict__ zl = z + row;
-        if (j > 0 && j < n - 1) sum = stencil5_row(j, n, v[1], zl[-1], v[2], zl[0], v[3], zl[1], v[0], zl[-n], v[4], zl[n]);
-        else if (j == 0) sum = stencil5_row(j, n, 0.0, 0.0, v[1], zl[0], v[2], zl[1], v[0], zl[-n], v[3], zl[n]);
-        else sum = stencil5_row(j, n, v[1], zl[-1], v[2], zl[0], 0.0, 0.0, v[0], zl[-n], v[3], zl[n]);
-    } else {
-        sum = 0.0;
-        for (int k = m.row_ptr[row]; k < m.row_ptr[row + 1]; ++k) sum = fma(m.values[k], z[m.col_idx[k]], sum);
-    }
-    return fma(-1.0, sum, r[row]);
-}
-
-// strip_row (multigrid_device.hpp): the row sum at column j from the strip slots of that row, through stencil5_row's chains
-
+// store_strip5, strip_row, load_pair and residual_off_tile: multigrid_device.hpp
 __global__ __launch_bounds__(kWave) void residual_restrict_kernel(SlabCsr m, const double* __restrict__ z, const double* __restrict__ r,
                                                                   double* __restrict__ rc, int nc, int col_tiles, int total_tiles, int run) {
-    __shared__ double strip[2][5 * kTileCols];
+    __shared__ double strip[2][5 * kStripCols];
     const int tile = xcd_run_tile<int>((int)blockIdx.x, run);
     if (tile >= total_tiles) return;
     const int n = m.grid_size;
     const int I = tile / col_tiles;
-    const int j0 = (tile - I * col_tiles) * kTileCols;
+    const int j0 = (tile - I * col_tiles) * kStripCols;
     const int lane = (int)threadIdx.x;
     const int ja = j0 + 2 * lane, jb = ja + 1;
     const int i0 = 2 * I, i1 = i0 + 1;
@@ -188,11 +169,7 @@ __global__ __launch_bounds__(kWave) void residual_restrict_kernel(SlabCsr m, con
                 if (lane == 63 && jb + 1 < n) east[a] = z[(long long)(i0 + a) * n + jb + 1];
             }
         }
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int k = 0; k < 10; ++k) strip[a][64 * k + lane] = c[a][k];
-        wave_lds_sync();
+        store_strip5(strip, lane, c);
         double acc = 0.0;
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
@@ -224,11 +201,7 @@ __global__ __launch_bounds__(kWave) void residual_restrict_kernel(SlabCsr m, con
 }
 
 // ---- prolongation + correction: z = fma(2.0, e_c[agg(i)], z), z in place; one-wave workgroups, a 16-byte pair per lane ----
-__device__ __forceinline__ double coarse_at(const double* __restrict__ ec, size_t flat, int n, int nc) {
-    const int i = (int)(flat / (size_t)n), j = (int)(flat - (size_t)i * n);
-    return ec[(size_t)(i >> 1) * nc + (j >> 1)];
-}
-
+// coarse_at (multigrid_device.hpp): e_c at the aggregate of a flat fine row
 __global__ __launch_bounds__(kWave) void prolong_correct_kernel(size_t rows, int n, int nc, const double* __restrict__ ec, double* __restrict__ z) {
     const size_t i = (size_t)blockIdx.x * kWave + threadIdx.x;
     if (i < (rows >> 1)) {
@@ -240,9 +213,10 @@ __global__ __launch_bounds__(kWave) void prolong_correct_kernel(size_t rows, int
     if ((rows & 1) && blockIdx.x == 0 && threadIdx.x == 0) z[rows - 1] = fma(2.0, coarse_at(ec, rows - 1, n, nc), z[rows - 1]);
 }
 
-// ---- the launches: the cycle calls these, and so does the LAB build's spmv_amd_mg_stage ----
-int coarse_grid_of(int n) { return (n + 1) / 2; }
-long long stencil_nnz(int n) { return n >= 2 ? stencil_gridrow_base(n, n) : 1; }
+}  // namespace
+
+// ---- the launches (multigrid.hpp) ----
+namespace spmv_amd {
 
 void launch_coarsen(const SlabCsr& fine, int nc, int* row_ptr, int* col_idx, double* values) {
     const int rows = nc * nc;
@@ -250,12 +224,8 @@ void launch_coarsen(const SlabCsr& fine, int nc, int* row_ptr, int* col_idx, dou
 }
 
 void launch_residual_restrict(const SlabCsr& m, const double* z, const double* r, double* rc) {
-    const int n = m.grid_size, nc = coarse_grid_of(n);
-    const int col_tiles = (n + kTileCols - 1) / kTileCols;
-    const int tiles = col_tiles * nc;
-    const int run = rowlds_xcd_run_rule(n);
-    hipLaunchKernelGGL(residual_restrict_kernel, dim3((unsigned)xcd_padded_grid(tiles, run)), dim3(kWave), 0, kStream, m, z, r, rc, nc, col_tiles,
-                       tiles, run);
+    const RestrictTiles t = restrict_tiles5(m.grid_size);
+    hipLaunchKernelGGL(residual_restrict_kernel, dim3(t.grid()), dim3(kWave), 0, kStream, m, z, r, rc, t.nc, t.col_tiles, t.tiles, t.run);
 }
 
 void launch_prolong_correct(int n, const double* ec, double* z) {
@@ -263,8 +233,7 @@ void launch_prolong_correct(int n, const double* ec, double* z) {
     hipLaunchKernelGGL(prolong_correct_kernel, dim3(stream_grid(rows)), dim3(kWave), 0, kStream, rows, n, coarse_grid_of(n), ec, z);
 }
 
-// the view of a complete 5-point CSR on an n x n grid in the caller's arrays
-SlabCsr stencil_view(int n, const int* row_ptr, const int* col_idx, const double* values) {
+SlabCsr mg_stencil_view(int n, const int* row_ptr, const int* col_idx, const double* values) {
     SlabCsr v;
     v.row_ptr = row_ptr, v.col_idx = col_idx, v.values = values;
     v.n_local = v.n_global = n * n;
@@ -274,80 +243,6 @@ SlabCsr stencil_view(int n, const int* row_ptr, const int* col_idx, const double
     return v;
 }
 
-// the structure check of a level's view: the complete 5-point pattern of v.grid_size (dim 2), the complete 7-point one of n^3 (dim 3)
-bool verified(SlabCsr& v, int dim = 2, int n = 0) {
-    int* d_mismatch = device_try_alloc<int>(1);
-    if (d_mismatch == nullptr) return fail("no device memory for the structure check");
-    HIP_CHECK(hipMemsetAsync(d_mismatch, 0, sizeof(int), kStream));
-    if (dim == 3) launch_verify_stencil7_csr(v, n, d_mismatch, kStream);
-    else launch_verify_stencil5_csr(v, d_mismatch, kStream);
-    HIP_CHECK(hipGetLastError());
-    int mismatch = 1;
-    download(&mismatch, d_mismatch, 1);  // synchronises
-    device_release(d_mismatch);
-    if (dim == 2) v.verified_stencil = mismatch == 0;  // the view's flag means "2-D 5-point"
-    return mismatch == 0;
-}
-
-}  // namespace
-
-namespace spmv_amd {
-
-struct MgLevel {
-    int dim = 2;          // 2: an n x n 5-point stencil; 3: an n x n x n 7-point one
-    int n = 0, rows = 0;  // the grid and its rows
-    DeviceCsr A;          // levels above 0 (level 0 reads the operator's own CSR)
-    SlabCsr view;
-    Stencil5Plan plan;    // dim 2
-    Stencil7Plan plan7;   // dim 3
-    double* dinv = nullptr;  // level 0's belongs to the SpmvAmdPrecond
-    bool own_dinv = true;
-    double lambda_max = 0.0;
-    int degree = 0;
-    double coef[1 + 2 * kCoarsestDegree] = {0.0};
-    double *r = nullptr, *d = nullptr, *z = nullptr;  // r: levels above 0
-    double* aux = nullptr;  // a 2-D row-lds plan: z' of the fused step; every other plan: w = A z
-    bool fused() const { return dim == 2 && plan.variant == Stencil5Variant::RowLds; }
-    ChebSpmv spmv() const {  // how this level runs A z (device_runtime.hpp)
-        ChebSpmv a;
-        a.view = &view;
-        if (dim == 3) a.plan7 = &plan7;
-        else a.plan = &plan, a.partials = fused() ? plan.partials : 0;
-        return a;
-    }
-    long long nnz() const { return dim == 3 ? stencil7_nnz(n) : stencil_nnz(n); }
-    void residual_restrict(const double* zv, const double* rv, double* rc) const {
-        if (dim == 3) launch_residual_restrict3d(view, n, zv, rv, rc);
-        else launch_residual_restrict(view, zv, rv, rc);
-    }
-    void prolong_correct(const double* ec, double* zv) const {
-        if (dim == 3) launch_prolong_correct3d(n, ec, zv);
-        else launch_prolong_correct(n, ec, zv);
-    }
-};
-
-struct MgHierarchy {
-    int dim = 2;
-    std::vector<MgLevel> levels;
-    int smoother_degree = 0;
-    double* partials = nullptr;  // the r.z partials of level 0's last update
-    MgMulti* multi = nullptr;    // spmv_amd_precond_create_multigrid_multi / ..._multigrid3d_multi: the levels' block vectors and SpMM plans (multigrid_multi.hip)
-    void release() {
-        mg_multi_destroy(multi);
-        multi = nullptr;
-        for (MgLevel& L : levels) {
-            L.A.release();
-            if (L.own_dinv) device_release(L.dinv);
-            device_release(L.r);
-            device_release(L.d);
-            device_release(L.z);
-            device_release(L.aux);
-        }
-        levels.clear();
-        device_release(partials);
-    }
-};
-
 void mg_destroy(MgHierarchy* h) {
     if (h == nullptr) return;
     h->release();
@@ -355,55 +250,51 @@ void mg_destroy(MgHierarchy* h) {
 }
 
 double* mg_result_vector(MgHierarchy* h) { return h->levels[0].z; }
-
-// what multigrid_multi.hip reads of the hierarchy (precond.hpp)
-int mg_level_count(const MgHierarchy* h) { return (int)h->levels.size(); }
-MgLevelView mg_level_view(const MgHierarchy* h, int level) {
-    const MgLevel& L = h->levels[(size_t)level];
-    MgLevelView v;
-    v.dim = L.dim, v.n = L.n, v.rows = L.rows, v.degree = L.degree, v.view = &L.view, v.variant = L.plan.variant, v.dinv = L.dinv, v.coef = L.coef;
-    return v;
-}
 MgMulti* mg_multi_of(const MgHierarchy* h) { return h != nullptr ? h->multi : nullptr; }
-SlabCsr mg_stencil_view(int n, const int* row_ptr, const int* col_idx, const double* values) { return stencil_view(n, row_ptr, col_idx, values); }
 bool mg_verify_stencil5(SlabCsr& v) { return verified(v); }
 bool mg_verify_stencil7(SlabCsr& v, int n) { return verified(v, 3, n); }
 
 namespace {
 
-struct CycleRun {
+// The single-vector cycle's operations (mg_schedule.hpp): section 14's application per level, a ChebRun whose z and aux change places
+// on fused levels. A launch that carries a product counts as SpMV time, every other as BLAS1.
+struct CycleOps {
     MgHierarchy* h;
+    const double* r;  // level 0's
     StageTimers* T;
-    Applied out;  // level 0's z and the r.z partials of its last step
+    ChebRun run[kMaxLevels];
 
-    // returns the vector of level l that holds z
-    double* level(int l, const double* r) {
+    void term0(int l) {
         MgLevel& L = h->levels[(size_t)l];
-        const bool coarsest = l + 1 == (int)h->levels.size();
-        const bool top = l == 0;
-        ChebRun c;  // section 14's application on this level; only a last step of level 0 writes partials
-        c.a = L.spmv(), c.n = (size_t)L.rows, c.r = r, c.dinv = L.dinv, c.d = L.d, c.z = L.z, c.aux = L.aux, c.partials = h->partials, c.T = T;
-        stage_run(T, &StageTimers::t_blas, [&] { launch_cheb_term0_apply(c.n, r, L.dinv, L.coef[0], L.d, c.z); });
-        (void)cheb_steps(c, L.degree, L.coef, coarsest && top);  // pre-smoothing (the coarsest level: its solve); no run_device here
-        if (!coarsest) {
-            MgLevel& C = h->levels[(size_t)l + 1];
-            stage_run(T, &StageTimers::t_spmv, [&] { L.residual_restrict(c.z, r, C.r); });
-            const double* const ec = level(l + 1, C.r);
-            stage_run(T, &StageTimers::t_blas, [&] { L.prolong_correct(ec, c.z); });
-            (void)cheb_step(c, L.coef[0], 0.0, top && L.degree == 0);  // post-smoothing from the guess z: term 0 in step form
-            (void)cheb_steps(c, L.degree, L.coef, top);
-        }
-        if (top) out.z = c.z, out.rz_partials = c.rz_partials, out.rz_count = c.rz_count;
-        return c.z;
+        ChebRun& c = run[l];  // only a last step of level 0 writes partials
+        c.a = L.spmv(), c.n = (size_t)L.rows, c.r = l == 0 ? r : L.r, c.dinv = L.dinv, c.d = L.d, c.z = L.z, c.aux = L.aux, c.partials = h->partials, c.T = T;
+        stage_run(T, &StageTimers::t_blas, [&] { launch_cheb_term0_apply(c.n, c.r, L.dinv, L.coef[0], L.d, c.z); });
+    }
+    void step(int l, double g, double hh, bool last) { (void)cheb_step(run[l], g, hh, last); }  // no run_device here
+    void restrict_residual(int l) {
+        const MgLevel& L = h->levels[(size_t)l];
+        double* const rc = h->levels[(size_t)l + 1].r;
+        stage_run(T, &StageTimers::t_spmv, [&] {
+            if (L.dim == 3) launch_residual_restrict3d(L.view, L.n, run[l].z, run[l].r, rc);
+            else launch_residual_restrict(L.view, run[l].z, run[l].r, rc);
+        });
+    }
+    void prolong(int l) {
+        const MgLevel& L = h->levels[(size_t)l];
+        stage_run(T, &StageTimers::t_blas, [&] {
+            if (L.dim == 3) launch_prolong_correct3d(L.n, run[l + 1].z, run[l].z);
+            else launch_prolong_correct(L.n, run[l + 1].z, run[l].z);
+        });
     }
 };
 
 }  // namespace
 
 Applied mg_cycle(MgHierarchy* h, const double* r, StageTimers* T) {
-    CycleRun run{h, T, Applied{}};
-    (void)run.level(0, r);
-    return run.out;
+    CycleOps ops{h, r, T, {}};
+    mg_vcycle(ops, h->levels.data(), h->count());
+    const ChebRun& top = ops.run[0];  // level 0's z and the r.z partials of its last step
+    return Applied{top.z, top.rz_partials, top.rz_count};
 }
 
 }  // namespace spmv_amd
@@ -422,7 +313,7 @@ bool finish_level(MgHierarchy* h, int l, const LaunchShape& shape, int* bad_row)
             L.A.view = stencil7_view(L.n, L.A.row_ptr, L.A.col_idx, L.A.values);
         } else {
             launch_coarsen(F.view, L.n, L.A.row_ptr, L.A.col_idx, L.A.values);
-            L.A.view = stencil_view(L.n, L.A.row_ptr, L.A.col_idx, L.A.values);
+            L.A.view = mg_stencil_view(L.n, L.A.row_ptr, L.A.col_idx, L.A.values);
         }
         HIP_CHECK(hipGetLastError());
         L.view = L.A.view;
@@ -443,7 +334,7 @@ bool finish_level(MgHierarchy* h, int l, const LaunchShape& shape, int* bad_row)
                 L.lambda_max);
         return false;
     }
-    L.degree = coarsest ? kCoarsestDegree : h->smoother_degree;
+    L.degree = coarsest ? kMgCoarsestDegree : h->smoother_degree;
     chebyshev_coefficients(L.degree, lmin, L.lambda_max, L.coef);
     if (L.dim == 3) L.plan7 = plan_stencil7(L.view, L.n, true, Stencil7Variant::Auto, shape.knobs);  // row-lds from the knob's grid, row-direct below
     else L.plan = plan_stencil5(L.view, 0, L.rows, Stencil5Variant::Auto, shape);
@@ -650,7 +541,7 @@ extern "C" int spmv_amd_mg_stage(const char* stage, SpmvAmdMgStageArgs* a) {
         if (st == kCoarsen) launch_coarsen3d(fine, a->n, a->out_row_ptr, a->out_col_idx, a->out_values);
         else launch_residual_restrict3d(fine, a->n, a->z, a->r, a->coarse);
     } else {
-        SlabCsr fine = stencil_view(a->n, a->row_ptr, a->col_idx, a->values);
+        SlabCsr fine = mg_stencil_view(a->n, a->row_ptr, a->col_idx, a->values);
         if (!verified(fine)) return fail("stage: the CSR is not a complete 5-point stencil of that grid: refused"), 1;
         if (st == kCoarsen) launch_coarsen(fine, coarse_grid_of(a->n), a->out_row_ptr, a->out_col_idx, a->out_values);
         else launch_residual_restrict(fine, a->z, a->r, a->coarse);

@@ -10,9 +10,8 @@
 // Arithmetic: (A z)_i is stencil7-csr's row -- sum = fma(v[k], z[col[k]], sum) from +0.0 in ascending k, every row --, t = fma(-1.0,
 // (A z)_i, r_i), r_c = (((((((t000 + t001) + t010) + t011) + t100) + t101) + t110) + t111) over the members that exist.
 // -ffp-contract=off: the only fused multiply-adds are the explicit ones.
-#include "multigrid3d.hpp"
-
-#include "multigrid3d_device.hpp"
+#include "multigrid.hpp"
+#include "multigrid_device.hpp"
 #include "stencil_geometry.hpp"
 #include "stencil_row_device.hpp"
 #include "stream_device.hpp"
@@ -22,7 +21,6 @@ namespace {
 
 constexpr hipStream_t kStream = nullptr;  // default stream, shared with the operators and pcg.hip
 constexpr int kWave = 64;
-constexpr int kTileCols = 128;  // fine columns of one residual-restriction tile: lane l owns aggregate column l of the tile
 
 // ---- coarsening ----
 // Every coarse entry is a sequential sum from 0.0 with plain additions: the members in the order (c, a, b) = (0,0,0), (0,0,1), (0,1,0),
@@ -93,36 +91,14 @@ __global__ __launch_bounds__(256) void coarsen3d_kernel(SlabCsr fine, int n, int
 // LDS: 7 168 B per wave. Every other block -- a grid row on a face of the cube in it, the lone last plane or grid row of an odd n --
 // goes one thread per aggregate through row_ptr (member_residual). Tiles are dealt to the XCDs by xcd_run_tile; the launcher pads.
 
-// z or r at (grid row, columns ja, ja + 1); has_b: column ja + 1 exists
-template <bool kOnce>
-__device__ __forceinline__ d2 load_pair3d(const double* __restrict__ v, long long at, bool has_b) {
-    d2 out;
-    if (has_b && (at & 1) == 0) {
-        out = kOnce ? __builtin_nontemporal_load(reinterpret_cast<const d2*>(v + at)) : *reinterpret_cast<const d2*>(v + at);
-    } else {
-        out.x = kOnce ? __builtin_nontemporal_load(v + at) : v[at];
-        out.y = 0.0;
-        if (has_b) out.y = kOnce ? __builtin_nontemporal_load(v + at + 1) : v[at + 1];
-    }
-    return out;
-}
-
-// t = fma(-1.0, (A z)_row, r_row), the row as the CSR loop
-__device__ __forceinline__ double member_residual(const SlabCsr& m, const double* __restrict__ z, const double* __restrict__ r, long long row) {
-    double sum = 0.0;
-    for (int e = m.row_ptr[row]; e < m.row_ptr[row + 1]; ++e) sum = fma(m.values[e], z[m.col_idx[e]], sum);
-    return fma(-1.0, sum, r[row]);
-}
-
-// strip_row7 and load_strip (multigrid3d_device.hpp): a row sum from the strip slots of that row, one grid row's tile of coefficients
-
+// strip_row7, load_strip, load_pair and member_residual: multigrid_device.hpp
 __global__ __launch_bounds__(kWave) void residual_restrict3d_kernel(SlabCsr m, int n, const double* __restrict__ z, const double* __restrict__ r,
                                                                     double* __restrict__ rc, int nc, int col_tiles, int total_tiles, int run) {
-    __shared__ double strip[7 * kTileCols];
+    __shared__ double strip[7 * kStripCols];
     const int tile = xcd_run_tile<int>((int)blockIdx.x, run);
     if (tile >= total_tiles) return;
     const int g = tile / col_tiles;  // the coarse grid row K nc + I
-    const int j0 = (tile - g * col_tiles) * kTileCols;
+    const int j0 = (tile - g * col_tiles) * kStripCols;
     const int K = g / nc, I = g - K * nc;
     const int lane = (int)threadIdx.x;
     const int ja = j0 + 2 * lane, jb = ja + 1;
@@ -131,7 +107,7 @@ __global__ __launch_bounds__(kWave) void residual_restrict3d_kernel(SlabCsr m, i
     const long long nn = (long long)n * n;
     const long long out = (long long)g * nc + (ja >> 1);
     if (k0 >= 1 && k0 + 1 <= n - 2 && i0 >= 1 && i0 + 1 <= n - 2) {
-        const int live = n - j0 < kTileCols ? n - j0 : kTileCols;
+        const int live = n - j0 < kStripCols ? n - j0 : kStripCols;
         const int entries = 7 * live;
         double c[14];
         load_strip(m.values + (stencil7_row_start(k0, i0, 0, n) + 7LL * j0 - 1 + lane), lane, entries, c);
@@ -151,15 +127,15 @@ __global__ __launch_bounds__(kWave) void residual_restrict3d_kernel(SlabCsr m, i
 #pragma unroll
                 for (int a = 0; a < 2; ++a) {
                     const long long p = at + q * nn + a * n;
-                    own[q][a] = load_pair3d<false>(z, p, has_b);
-                    rv[q][a] = load_pair3d<true>(r, p, has_b);
+                    own[q][a] = load_pair<false>(z, p, has_b);
+                    rv[q][a] = load_pair<true>(r, p, has_b);
                     if (lane == 0 && ja > 0) west[q][a] = z[p - 1];
                     if (lane == 63 && jb + 1 < n) east[q][a] = z[p + 2];
                 }
-                zn[q] = load_pair3d<false>(z, at + q * nn - n, has_b);
-                zs[q] = load_pair3d<false>(z, at + q * nn + 2 * n, has_b);
-                zd[q] = load_pair3d<false>(z, at - nn + q * n, has_b);
-                zu[q] = load_pair3d<false>(z, at + 2 * nn + q * n, has_b);
+                zn[q] = load_pair<false>(z, at + q * nn - n, has_b);
+                zs[q] = load_pair<false>(z, at + q * nn + 2 * n, has_b);
+                zd[q] = load_pair<false>(z, at - nn + q * n, has_b);
+                zu[q] = load_pair<false>(z, at + 2 * nn + q * n, has_b);
             }
         }
         double acc = 0.0;
@@ -210,7 +186,7 @@ __global__ __launch_bounds__(kWave) void residual_restrict3d_kernel(SlabCsr m, i
 }
 
 // ---- prolongation + correction: z = fma(2.0, e_c[agg(i)], z), z in place; one-wave workgroups, a 16-byte pair per lane ----
-// coarse_at3d (multigrid3d_device.hpp): e_c at the aggregate of a flat fine row
+// coarse_at3d (multigrid_device.hpp): e_c at the aggregate of a flat fine row
 __global__ __launch_bounds__(kWave) void prolong_correct3d_kernel(unsigned rows, unsigned n, unsigned nc, const double* __restrict__ ec,
                                                                   double* __restrict__ z) {
     const unsigned i = blockIdx.x * kWave + threadIdx.x;
@@ -236,24 +212,20 @@ SlabCsr stencil7_view(int n, const int* row_ptr, const int* col_idx, const doubl
 }
 
 void launch_coarsen3d(const SlabCsr& fine, int n, int* row_ptr, int* col_idx, double* values) {
-    const int nc = (n + 1) / 2;
+    const int nc = coarse_grid_of(n);
     const int rows = nc * nc * nc;
     hipLaunchKernelGGL(coarsen3d_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, kStream, fine, n, nc, row_ptr, col_idx, values);
 }
 
 void launch_residual_restrict3d(const SlabCsr& m, int n, const double* z, const double* r, double* rc) {
-    const int nc = (n + 1) / 2;
-    const int col_tiles = (n + kTileCols - 1) / kTileCols;
-    const int tiles = nc * nc * col_tiles;  // <= 337^2 * 6
-    const int run = stencil7_xcd_run_rule(n);
-    hipLaunchKernelGGL(residual_restrict3d_kernel, dim3((unsigned)xcd_padded_grid(tiles, run)), dim3(kWave), 0, kStream, m, n, z, r, rc, nc,
-                       col_tiles, tiles, run);
+    const RestrictTiles t = restrict_tiles7(n);
+    hipLaunchKernelGGL(residual_restrict3d_kernel, dim3(t.grid()), dim3(kWave), 0, kStream, m, n, z, r, rc, t.nc, t.col_tiles, t.tiles, t.run);
 }
 
 void launch_prolong_correct3d(int n, const double* ec, double* z) {
     const size_t rows = (size_t)n * n * n;  // <= 674^3 < 2^31
     hipLaunchKernelGGL(prolong_correct3d_kernel, dim3(stream_grid(rows)), dim3(kWave), 0, kStream, (unsigned)rows, (unsigned)n,
-                       (unsigned)((n + 1) / 2), ec, z);
+                       (unsigned)coarse_grid_of(n), ec, z);
 }
 
 }  // namespace spmv_amd

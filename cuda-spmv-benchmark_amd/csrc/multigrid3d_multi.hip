@@ -11,15 +11,10 @@
 // the only fused multiply-adds are the explicit ones. Every kernel reads the column records first and returns when no column is running
 // (null records: all are); a stopped column beside running ones is computed like them.
 // Indices: a row index times K is formed in 64 bits everywhere (674^3 rows x 8 columns pass int).
-#include "multigrid3d.hpp"
-
-#include <string.h>
-
 #include "multi_rhs.hpp"
 #include "multi_solve.hpp"
-#include "multigrid3d_device.hpp"
-#include "multigrid_multi_device.hpp"
-#include "precond.hpp"
+#include "multigrid.hpp"
+#include "multigrid_device.hpp"
 #include "stencil_geometry.hpp"
 #include "stencil_row_device.hpp"
 #include "stream_device.hpp"
@@ -31,9 +26,7 @@ namespace spmv_amd {
 namespace {
 
 constexpr int kWave = 64;
-constexpr int kTileCols = kStripCols;  // fine columns of one residual-restriction tile: lane l owns aggregate column l of the tile
-constexpr int kFlat = 256;             // workgroup of the flat kernel
-constexpr int kChunk = 4;              // columns one pass over a grid row holds in registers: 14 * 4 doubles of z and r per lane
+constexpr int kChunk = 4;  // columns one pass over a grid row holds in registers: 14 * 4 doubles of z and r per lane
 
 // ---- residual + restriction in one launch, K columns ----
 // The tile, the strip, the fast-path test, the row_ptr path and the XCD deal are residual_restrict3d_kernel's (multigrid3d.hip). A
@@ -117,26 +110,17 @@ __device__ __forceinline__ void row_chunks(const double* __restrict__ strip, con
     }
 }
 
-// t = fma(-1.0, (A z)_row, r_row) of column q, the row as the CSR loop: member_residual of multigrid3d.hip on interleaved vectors
-template <int K>
-__device__ __forceinline__ double member_residual_multi(const SlabCsr& m, const double* __restrict__ z, const double* __restrict__ r,
-                                                        long long row, int q) {
-    double sum = 0.0;
-    for (int e = m.row_ptr[row]; e < m.row_ptr[row + 1]; ++e) sum = fma(m.values[e], z[(long long)m.col_idx[e] * K + q], sum);
-    return fma(-1.0, sum, r[row * K + q]);
-}
-
 template <int K>
 __global__ __launch_bounds__(kWave) void residual_restrict3d_multi_kernel(SlabCsr m, int n, const PcgMultiColumn* __restrict__ cols,
                                                                           const double* __restrict__ z, const double* __restrict__ r,
                                                                           double* __restrict__ rc, int nc, int col_tiles, int total_tiles,
                                                                           int run) {
-    __shared__ double strip[7 * kTileCols];
+    __shared__ double strip[7 * kStripCols];
     if (!any_running<K>(cols)) return;  // uniform over the launch
     const int tile = xcd_run_tile<int>((int)blockIdx.x, run);
     if (tile >= total_tiles) return;
     const int g = tile / col_tiles;  // the coarse grid row Kc nc + I
-    const int j0 = (tile - g * col_tiles) * kTileCols;
+    const int j0 = (tile - g * col_tiles) * kStripCols;
     const int Kc = g / nc, I = g - Kc * nc;
     const int lane = (int)threadIdx.x;
     const int ja = j0 + 2 * lane, jb = ja + 1;
@@ -145,7 +129,7 @@ __global__ __launch_bounds__(kWave) void residual_restrict3d_multi_kernel(SlabCs
     const long long nn = (long long)n * n;
     const long long out = ((long long)g * nc + (ja >> 1)) * K;
     if (k0 >= 1 && k0 + 1 <= n - 2 && i0 >= 1 && i0 + 1 <= n - 2) {
-        const int live = n - j0 < kTileCols ? n - j0 : kTileCols;
+        const int live = n - j0 < kStripCols ? n - j0 : kStripCols;
         const int entries = 7 * live;
         double c[14];
         load_strip(m.values + (stencil7_row_start(k0, i0, 0, n) + 7LL * j0 - 1 + lane), lane, entries, c);
@@ -178,9 +162,9 @@ __global__ __launch_bounds__(kWave) void residual_restrict3d_multi_kernel(SlabCs
                 for (int a = 0; a < 2; ++a) {
                     if (k0 + q >= n || i0 + a >= n) continue;
                     const long long row = (long long)(k0 + q) * nn + (long long)(i0 + a) * n + ja;
-                    const double ta = member_residual_multi<K>(m, z, r, row, j);
+                    const double ta = member_residual<K>(m, z, r, row, j);
                     acc = (q == 0 && a == 0) ? ta : acc + ta;
-                    if (has_b) acc = acc + member_residual_multi<K>(m, z, r, row + 1, j);
+                    if (has_b) acc = acc + member_residual<K>(m, z, r, row + 1, j);
                 }
             }
             rc[out + j] = acc;
@@ -219,13 +203,10 @@ __global__ __launch_bounds__(kFlat) void prolong_correct3d_multi_kernel(long lon
 
 // ---- the launches: the batched cycle calls these, and so does the LAB build's spmv_amd_mg_multi_stage3d ----
 void launch_residual_restrict3d_multi(int k, const SlabCsr& m, int n, const PcgMultiColumn* cols, const double* z, const double* r, double* rc) {
-    const int nc = (n + 1) / 2;
-    const int col_tiles = (n + kTileCols - 1) / kTileCols;
-    const int tiles = nc * nc * col_tiles;  // <= 337^2 * 6
-    const int run = stencil7_xcd_run_rule(n);
+    const RestrictTiles t = restrict_tiles7(n);
     dispatch_k(k, [&](auto K) {
-        hipLaunchKernelGGL((residual_restrict3d_multi_kernel<decltype(K)::value>), dim3((unsigned)xcd_padded_grid(tiles, run)), dim3(kWave), 0,
-                           kBatchStream, m, n, cols, z, r, rc, nc, col_tiles, tiles, run);
+        hipLaunchKernelGGL((residual_restrict3d_multi_kernel<decltype(K)::value>), dim3(t.grid()), dim3(kWave), 0, kBatchStream, m, n, cols, z, r,
+                           rc, t.nc, t.col_tiles, t.tiles, t.run);
     });
 }
 
@@ -233,51 +214,14 @@ void launch_prolong_correct3d_multi(int k, int n, const PcgMultiColumn* cols, co
     const long long rows = (long long)n * n * n;  // <= 674^3 < 2^31
     dispatch_k(k, [&](auto K) {
         hipLaunchKernelGGL((prolong_correct3d_multi_kernel<decltype(K)::value>), dim3((unsigned)((rows + kFlat - 1) / kFlat)), dim3(kFlat), 0,
-                           kBatchStream, rows, n, (n + 1) / 2, cols, ec, z);
+                           kBatchStream, rows, n, coarse_grid_of(n), cols, ec, z);
     });
 }
 
 }  // namespace spmv_amd
 
 #ifdef SPMV_AMD_LAB
-using namespace spmv_amd;
-
 extern "C" int spmv_amd_mg_multi_stage3d(const char* stage, int k, SpmvAmdMgMultiStageArgs* a) {
-    // argument checks: all but the structure check before the first HIP call
-    constexpr const char* kTag = "PCG-MULTI";
-    auto refuse = [&](const char* what) { return stage_fail(kTag, stage, what); };
-    auto pointer = [&](const char* name, const void* ptr, int align) { return stage_pointer(kTag, stage, name, ptr, align); };
-    enum Stage { kRestrict, kProlong, kSpmm7, kSpmmCsr } st;
-    if (stage == nullptr) return refuse("no stage named (residual_restrict3d, prolong3d, stencil7_spmm, spmm_csr)"), 1;
-    if (!strcmp(stage, "residual_restrict3d")) st = kRestrict;
-    else if (!strcmp(stage, "prolong3d")) st = kProlong;
-    else if (!strcmp(stage, "stencil7_spmm")) st = kSpmm7;
-    else if (!strcmp(stage, "spmm_csr")) st = kSpmmCsr;
-    else return refuse("unknown stage (residual_restrict3d, prolong3d, stencil7_spmm, spmm_csr)"), 1;
-    const bool product = st == kSpmm7 || st == kSpmmCsr;
-    if (k < 1 || k > kMaxRhs) return refuse("k is not 1 to 8"), 1;
-    if (a == nullptr) return refuse("null arguments"), 1;
-    if (a->n < 2 || a->n > kStencil7MaxGrid) return refuse("the fine grid of a 3-D stage is outside 2..674"), 1;
-    const int block = k % 2 == 0 ? 16 : 8;  // a block vector: 16-byte accesses where k is even
-    if (st != kProlong && (!pointer("row_ptr", a->row_ptr, 4) || !pointer("col_idx", a->col_idx, 4) || !pointer("values", a->values, 8))) return 1;
-    if (!pointer("z", a->z, block)) return 1;
-    if (st == kRestrict && !pointer("r", a->r, block)) return 1;
-    if (!product && !pointer("coarse", a->coarse, block)) return 1;
-    if (product && !pointer("d", a->d, block)) return 1;
-    if (a->cols != nullptr && !pointer("cols", a->cols, 8)) return 1;
-
-    const PcgMultiColumn* cols = reinterpret_cast<const PcgMultiColumn*>(a->cols);
-    if (st != kProlong) {
-        SlabCsr fine = stencil7_view(a->n, a->row_ptr, a->col_idx, a->values);
-        if (!mg_verify_stencil7(fine, a->n)) return refuse("the CSR is not a complete 7-point stencil of that grid"), 1;
-        if (st == kRestrict) launch_residual_restrict3d_multi(k, fine, a->n, cols, a->z, a->r, a->coarse);
-        else if (st == kSpmm7) launch_spmm(plan_spmm_stencil7(fine, a->n), k, a->z, a->d, nullptr, kBatchStream);
-        else launch_spmm(plan_spmm(fine, Stencil5Variant::Auto, true, fine.n_local, fine.n_local), k, a->z, a->d, nullptr, kBatchStream);
-    } else {
-        launch_prolong_correct3d_multi(k, a->n, cols, a->coarse, a->z);
-    }
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    return 0;
+    return spmv_amd::mg_multi_stage(3, stage, k, a);  // multigrid_multi.hip: the one body of both stage hooks
 }
 #endif  // SPMV_AMD_LAB

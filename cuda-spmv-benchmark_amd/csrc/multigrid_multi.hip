@@ -6,8 +6,9 @@
 // and on every level an SpmmPlan on the level's own view and Stencil5Plan variant (a 3-D level: "spmm/csr"). Level 0 works on its caller's vectors -- the solve's
 // R, D, Z and AP buffer, or the block application's.
 //
-// A cycle's launch count does not depend on k: the columns share every launch, and the three launches that are multigrid's own read
-// what the columns share once --
+// The cycle is mg_schedule.hpp's mg_vcycle with the operations of MultiOps below; the levels are read straight from multigrid.hpp's
+// MgHierarchy. A cycle's launch count does not depend on k: the columns share every launch, and the three launches that are
+// multigrid's own read what the columns share once --
 //   residual_restrict_multi_kernel<K>  r_c[I, J][j] = ((t00 + t01) + t10) + t11 per column, t = fma(-1.0, (A z)_i, r_i): the two rows'
 //                                      coefficients go through the wave-private LDS strip once for all K columns
 //   prolong_correct_multi_kernel<K>    z[i][j] = fma(2.0, e_c[agg(i)][j], z[i][j]), flat over rows x columns
@@ -23,12 +24,11 @@
 
 #include <vector>
 
+#include "mg_schedule.hpp"
 #include "multi_rhs.hpp"
 #include "multi_solve.hpp"
-#include "multigrid3d.hpp"
+#include "multigrid.hpp"
 #include "multigrid_device.hpp"
-#include "multigrid_multi_device.hpp"
-#include "precond.hpp"
 #include "stencil_geometry.hpp"
 #include "stencil_row_device.hpp"
 #include "stream_device.hpp"
@@ -42,11 +42,9 @@ namespace {
 
 constexpr const char* kTag = "PCG-MULTI";
 constexpr int kWave = 64;
-constexpr int kTileCols = 128;  // fine columns of one residual-restriction tile: lane l owns aggregate column l of the tile
-constexpr int kFlat = 256;      // workgroup of the flat kernels
-constexpr int kChunk = 4;       // columns one pass of the restriction holds in registers: 12 * 4 doubles of z and r per lane
+constexpr int kChunk = 4;  // columns one pass of the restriction holds in registers: 12 * 4 doubles of z and r per lane
 
-// any_running, load_run, store_run and the flat walk's FlatWalk, load_unit, store_unit: multigrid_multi_device.hpp
+// store_strip5, strip_row, residual_off_tile<K>, any_running, load_run, store_run and the flat walk: multigrid_device.hpp
 
 // ---- residual + restriction in one launch, K columns ----
 // The tile, the strip, the fast-path test, the off-tile path and the XCD deal are residual_restrict_kernel's (multigrid.hip). A lane's
@@ -90,7 +88,7 @@ __device__ __forceinline__ void restrict_load(RestrictRegs<C>& t, const double* 
 }
 
 template <int K, int C0, int C>
-__device__ __forceinline__ void restrict_sum(const RestrictRegs<C>& t, const double (*strip)[5 * kTileCols], double* __restrict__ rc, int n,
+__device__ __forceinline__ void restrict_sum(const RestrictRegs<C>& t, const double (*strip)[5 * kStripCols], double* __restrict__ rc, int n,
                                              int nc, int I, int ja, int lane, bool has_a, bool has_b) {
     double acc[C];
 #pragma unroll
@@ -119,7 +117,7 @@ __device__ __forceinline__ void restrict_sum(const RestrictRegs<C>& t, const dou
 
 // the chunks behind the first: columns C0 .. K - 1, the strip already in LDS
 template <int K, int C0>
-__device__ __forceinline__ void restrict_rest(const double (*strip)[5 * kTileCols], const double* __restrict__ z, const double* __restrict__ r,
+__device__ __forceinline__ void restrict_rest(const double (*strip)[5 * kStripCols], const double* __restrict__ z, const double* __restrict__ r,
                                               double* __restrict__ rc, int n, int nc, int I, int i0, int ja, int lane, bool has_a, bool has_b) {
     if constexpr (C0 < K) {
         constexpr int C = K - C0 < kChunk ? K - C0 : kChunk;
@@ -130,38 +128,17 @@ __device__ __forceinline__ void restrict_rest(const double (*strip)[5 * kTileCol
     }
 }
 
-// t = fma(-1.0, sum, r) of row (i, j), column q, off the fast path: residual_off_tile of multigrid.hip on interleaved vectors
-template <int K>
-__device__ __forceinline__ double residual_off_tile_multi(const SlabCsr& m, const double* __restrict__ z, const double* __restrict__ r, int i, int j,
-                                                          int q) {
-    const int n = m.grid_size;
-    const long long row = (long long)i * n + j;
-    double sum;
-    if (i > 0 && i < n - 1) {
-        const double* __restrict__ v = m.values + m.row_ptr[row];
-        const double* __restrict__ zl = z + row * K + q;
-        const long long up = (long long)n * K;
-        if (j > 0 && j < n - 1) sum = stencil5_row(j, n, v[1], zl[-K], v[2], zl[0], v[3], zl[K], v[0], zl[-up], v[4], zl[up]);
-        else if (j == 0) sum = stencil5_row(j, n, 0.0, 0.0, v[1], zl[0], v[2], zl[K], v[0], zl[-up], v[3], zl[up]);
-        else sum = stencil5_row(j, n, v[1], zl[-K], v[2], zl[0], 0.0, 0.0, v[0], zl[-up], v[3], zl[up]);
-    } else {
-        sum = 0.0;
-        for (int e = m.row_ptr[row]; e < m.row_ptr[row + 1]; ++e) sum = fma(m.values[e], z[(long long)m.col_idx[e] * K + q], sum);
-    }
-    return fma(-1.0, sum, r[row * K + q]);
-}
-
 template <int K>
 __global__ __launch_bounds__(kWave) void residual_restrict_multi_kernel(SlabCsr m, const PcgMultiColumn* __restrict__ cols,
                                                                         const double* __restrict__ z, const double* __restrict__ r,
                                                                         double* __restrict__ rc, int nc, int col_tiles, int total_tiles, int run) {
-    __shared__ double strip[2][5 * kTileCols];
+    __shared__ double strip[2][5 * kStripCols];
     if (!any_running<K>(cols)) return;  // uniform over the launch
     const int tile = xcd_run_tile<int>((int)blockIdx.x, run);
     if (tile >= total_tiles) return;
     const int n = m.grid_size;
     const int I = tile / col_tiles;
-    const int j0 = (tile - I * col_tiles) * kTileCols;
+    const int j0 = (tile - I * col_tiles) * kStripCols;
     const int lane = (int)threadIdx.x;
     const int ja = j0 + 2 * lane, jb = ja + 1;
     const int i0 = 2 * I, i1 = i0 + 1;
@@ -183,31 +160,26 @@ __global__ __launch_bounds__(kWave) void residual_restrict_multi_kernel(SlabCsr 
         }
         RestrictRegs<CA> first;
         restrict_load<K, 0, CA>(first, z, r, n, i0, ja, lane, has_a, has_b);
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int s = 0; s < 10; ++s) strip[a][64 * s + lane] = c[a][s];
-        wave_lds_sync();
+        store_strip5(strip, lane, c);
         restrict_sum<K, 0, CA>(first, strip, rc, n, nc, I, ja, lane, has_a, has_b);
         restrict_rest<K, CA>(strip, z, r, rc, n, nc, I, i0, ja, lane, has_a, has_b);
     } else if (has_a) {
         // a pair with grid row 0 or n-1 in it, a lone last grid row
 #pragma unroll
         for (int q = 0; q < K; ++q) {
-            double acc = residual_off_tile_multi<K>(m, z, r, i0, ja, q);
-            if (has_b) acc = acc + residual_off_tile_multi<K>(m, z, r, i0, jb, q);
+            double acc = residual_off_tile<K, long long>(m, z, r, i0, ja, q);
+            if (has_b) acc = acc + residual_off_tile<K, long long>(m, z, r, i0, jb, q);
             if (i1 < n) {
-                acc = acc + residual_off_tile_multi<K>(m, z, r, i1, ja, q);
-                if (has_b) acc = acc + residual_off_tile_multi<K>(m, z, r, i1, jb, q);
+                acc = acc + residual_off_tile<K, long long>(m, z, r, i1, ja, q);
+                if (has_b) acc = acc + residual_off_tile<K, long long>(m, z, r, i1, jb, q);
             }
             rc[((long long)I * nc + (ja >> 1)) * K + q] = acc;
         }
     }
 }
 
-// ---- the flat kernels: unit f = threadIdx.x + 256 i (i < P) of a workgroup's 256 rows is row f / P, columns (f % P) * V ... + V - 1,
-// V = 2 for even K (16-byte accesses), 1 else, P = K / V -- the walk of the batched solvers' vector kernels (multi_rhs_device.hpp) ----
-// z[i][j] = fma(2.0, e_c[agg(i)][j], z[i][j]), z in place; the store is plain: the post-smoother's SpMM reads it
+// ---- the flat kernels (FlatWalk, multigrid_device.hpp) ----
+// z[i][j] = fma(2.0, e_c[agg(i)][j], z[i][j]), z in place
 template <int K>
 __global__ __launch_bounds__(kFlat) void prolong_correct_multi_kernel(long long rows, int n, int nc, const PcgMultiColumn* __restrict__ cols,
                                                                       const double* __restrict__ ec, double* __restrict__ z) {
@@ -255,28 +227,28 @@ __global__ __launch_bounds__(kFlat) void mg_multi_term0_kernel(long long rows, c
     }
 }
 
-// ---- the launches: the cycle calls these, and so does the LAB build's spmv_amd_mg_multi_stage ----
-int coarse_grid_of(int n) { return (n + 1) / 2; }
 unsigned flat_grid(long long rows) { return (unsigned)((rows + kFlat - 1) / kFlat); }
 
-void launch_residual_restrict_multi(int k, const SlabCsr& m, const PcgMultiColumn* cols, const double* z, const double* r, double* rc) {
-    const int n = m.grid_size, nc = coarse_grid_of(n);
-    const int col_tiles = (n + kTileCols - 1) / kTileCols;
-    const int tiles = col_tiles * nc;
-    const int run = rowlds_xcd_run_rule(n);
+}  // namespace
+
+// ---- the launches (multigrid.hpp) ----
+void spmv_amd::launch_residual_restrict_multi(int k, const SlabCsr& m, const PcgMultiColumn* cols, const double* z, const double* r, double* rc) {
+    const RestrictTiles t = restrict_tiles5(m.grid_size);
     dispatch_k(k, [&](auto K) {
-        hipLaunchKernelGGL((residual_restrict_multi_kernel<decltype(K)::value>), dim3((unsigned)xcd_padded_grid(tiles, run)), dim3(kWave), 0,
-                           kBatchStream, m, cols, z, r, rc, nc, col_tiles, tiles, run);
+        hipLaunchKernelGGL((residual_restrict_multi_kernel<decltype(K)::value>), dim3(t.grid()), dim3(kWave), 0, kBatchStream, m, cols, z, r, rc, t.nc,
+                           t.col_tiles, t.tiles, t.run);
     });
 }
 
-void launch_prolong_correct_multi(int k, int n, const PcgMultiColumn* cols, const double* ec, double* z) {
+void spmv_amd::launch_prolong_correct_multi(int k, int n, const PcgMultiColumn* cols, const double* ec, double* z) {
     const long long rows = (long long)n * n;
     dispatch_k(k, [&](auto K) {
         hipLaunchKernelGGL((prolong_correct_multi_kernel<decltype(K)::value>), dim3(flat_grid(rows)), dim3(kFlat), 0, kBatchStream, rows, n,
                            coarse_grid_of(n), cols, ec, z);
     });
 }
+
+namespace {
 
 void launch_mg_multi_term0(int k, long long rows, const PcgMultiColumn* cols, const double* R, const double* dinv, double c0, double* D, double* Z) {
     dispatch_k(k, [&](auto K) {
@@ -304,7 +276,7 @@ int mg_multi_capacity(const MgMulti* mm) { return mm != nullptr ? mm->max_rhs : 
 
 size_t mg_multi_bytes(const MgHierarchy* h, int max_rhs) {
     size_t bytes = 0;
-    for (int l = 1; l < mg_level_count(h); ++l) bytes += 4 * (size_t)mg_level_view(h, l).rows * (size_t)max_rhs * sizeof(double) + 4 * 4096;
+    for (int l = 1; l < h->count(); ++l) bytes += 4 * (size_t)h->levels[(size_t)l].rows * (size_t)max_rhs * sizeof(double) + 4 * 4096;
     return bytes;
 }
 
@@ -338,12 +310,12 @@ static bool stencil7_level_product(int n) {
 MgMulti* mg_multi_create(const MgHierarchy* h, int max_rhs) {
     MgMulti* mm = new MgMulti();
     mm->max_rhs = max_rhs;
-    mm->levels.resize((size_t)mg_level_count(h));
-    for (int l = 0; l < mg_level_count(h); ++l) {
-        const MgLevelView v = mg_level_view(h, l);
+    mm->levels.resize(h->levels.size());
+    for (int l = 0; l < h->count(); ++l) {
+        const MgLevel& v = h->levels[(size_t)l];
         MgMulti::Level& L = mm->levels[(size_t)l];
-        if (v.dim == 3) L.plan = stencil7_level_product(v.n) ? plan_spmm_stencil7(*v.view, v.n) : plan_spmm(*v.view, Stencil5Variant::Auto, true, v.rows, v.rows);
-        else L.plan = plan_spmm(*v.view, v.variant, false, v.rows, v.rows);
+        if (v.dim == 3) L.plan = stencil7_level_product(v.n) ? plan_spmm_stencil7(v.view, v.n) : plan_spmm(v.view, Stencil5Variant::Auto, true, v.rows, v.rows);
+        else L.plan = plan_spmm(v.view, v.plan.variant, false, v.rows, v.rows);
         if (l == 0) continue;
         const size_t count = (size_t)v.rows * (size_t)max_rhs;
         L.R = device_try_alloc<double>(count);
@@ -361,41 +333,53 @@ MgMulti* mg_multi_create(const MgHierarchy* h, int max_rhs) {
 
 namespace {
 
-struct MultiCycle {
+// The batched cycle's operations (mg_schedule.hpp): a level's R, D, Z, W and SpMM plan; level 0 works on the caller's vectors, whose D
+// and Z hold term 0 on entry. A launch that carries an SpMM counts as SpMV time, every other as BLAS1.
+struct MultiOps {
+    struct Vectors {
+        const double* R;
+        double *D, *Z, *W;
+    };
     const MgHierarchy* h;
     const MgMulti* mm;
     int k;
     const PcgMultiColumn* cols;
+    Vectors top;
     double* partials;
     long long count;
     StageTimers* T;
 
-    // level l on (R, D, Z, W); D and Z hold term 0 on entry where l == 0
-    void level(int l, const double* R, double* D, double* Z, double* W) {
-        const MgLevelView v = mg_level_view(h, l);
-        const SpmmPlan& plan = mm->levels[(size_t)l].plan;
-        const bool coarsest = l + 1 == mg_level_count(h);
-        const bool top = l == 0;
-        auto step = [&](double g, double hh, bool last) {  // a launch that carries an SpMM counts as SpMV time, every other as BLAS1
-            stage_run(T, &StageTimers::t_spmv, [&] { launch_spmm(plan, k, Z, W, nullptr, kBatchStream); });
-            stage_run(T, &StageTimers::t_blas,
-                      [&] { launch_pcg_multi_cheb_step(k, v.rows, cols, W, R, v.dinv, g, hh, D, Z, last ? 1 : 0, partials, count); });
-        };
-        if (!top) stage_run(T, &StageTimers::t_blas, [&] { launch_mg_multi_term0(k, v.rows, cols, R, v.dinv, v.coef[0], D, Z); });
-        for (int s = 1; s <= v.degree; ++s) step(v.coef[2 * s], v.coef[2 * s - 1], coarsest && top && s == v.degree);  // pre-smoothing / the solve
-        if (coarsest) return;
-        const MgMulti::Level& C = mm->levels[(size_t)l + 1];
+    Vectors at(int l) const {
+        const MgMulti::Level& M = mm->levels[(size_t)l];
+        return l == 0 ? top : Vectors{M.R, M.D, M.Z, M.W};
+    }
+    void term0(int l) {
+        const MgLevel& L = h->levels[(size_t)l];
+        const Vectors v = at(l);
+        if (l > 0) stage_run(T, &StageTimers::t_blas, [&] { launch_mg_multi_term0(k, L.rows, cols, v.R, L.dinv, L.coef[0], v.D, v.Z); });
+    }
+    void step(int l, double g, double hh, bool last) {
+        const MgLevel& L = h->levels[(size_t)l];
+        const Vectors v = at(l);
+        stage_run(T, &StageTimers::t_spmv, [&] { launch_spmm(mm->levels[(size_t)l].plan, k, v.Z, v.W, nullptr, kBatchStream); });
+        stage_run(T, &StageTimers::t_blas,
+                  [&] { launch_pcg_multi_cheb_step(k, L.rows, cols, v.W, v.R, L.dinv, g, hh, v.D, v.Z, last ? 1 : 0, partials, count); });
+    }
+    void restrict_residual(int l) {
+        const MgLevel& L = h->levels[(size_t)l];
+        const Vectors v = at(l);
+        double* const rc = mm->levels[(size_t)l + 1].R;
         stage_run(T, &StageTimers::t_spmv, [&] {
-            if (v.dim == 3) launch_residual_restrict3d_multi(k, *v.view, v.n, cols, Z, R, C.R);
-            else launch_residual_restrict_multi(k, *v.view, cols, Z, R, C.R);
+            if (L.dim == 3) launch_residual_restrict3d_multi(k, L.view, L.n, cols, v.Z, v.R, rc);
+            else launch_residual_restrict_multi(k, L.view, cols, v.Z, v.R, rc);
         });
-        level(l + 1, C.R, C.D, C.Z, C.W);
+    }
+    void prolong(int l) {
+        const MgLevel& L = h->levels[(size_t)l];
         stage_run(T, &StageTimers::t_blas, [&] {
-            if (v.dim == 3) launch_prolong_correct3d_multi(k, v.n, cols, C.Z, Z);
-            else launch_prolong_correct_multi(k, v.n, cols, C.Z, Z);
+            if (L.dim == 3) launch_prolong_correct3d_multi(k, L.n, cols, at(l + 1).Z, at(l).Z);
+            else launch_prolong_correct_multi(k, L.n, cols, at(l + 1).Z, at(l).Z);
         });
-        step(v.coef[0], 0.0, top && v.degree == 0);  // post-smoothing from the guess z: term 0 in step form
-        for (int s = 1; s <= v.degree; ++s) step(v.coef[2 * s], v.coef[2 * s - 1], top && s == v.degree);
     }
 };
 
@@ -403,8 +387,8 @@ struct MultiCycle {
 
 void mg_cycle_multi(const MgHierarchy* h, int k, const PcgMultiColumn* cols, const double* R, double* D, double* Z, double* W, double* partials,
                     long long count, StageTimers* T) {
-    MultiCycle run{h, mg_multi_of(h), k, cols, partials, count, T};
-    run.level(0, R, D, Z, W);
+    MultiOps ops{h, mg_multi_of(h), k, cols, {R, D, Z, W}, partials, count, T};
+    mg_vcycle(ops, h->levels.data(), h->count());
 }
 
 }  // namespace spmv_amd
@@ -461,7 +445,7 @@ extern "C" int spmv_amd_precond_apply_device_multi(SpmvOperator* op, const SpmvA
     if (ok) {
         if (cols != nullptr) HIP_CHECK(hipMemsetAsync(cols, 0, (size_t)k * sizeof(PcgMultiColumn), kBatchStream));
         if (mg) {
-            launch_mg_multi_term0(k, n, cols, d_R, m->dinv, mg_level_view(m->mg, 0).coef[0], D, d_Z);
+            launch_mg_multi_term0(k, n, cols, d_R, m->dinv, m->mg->levels[0].coef[0], D, d_Z);
             mg_cycle_multi(m->mg, k, cols, d_R, D, d_Z, W, partials, groups, nullptr);
         } else if (cheb) {
             launch_mg_multi_term0(k, n, cols, d_R, m->dinv, m->coef[0], D, d_Z);
@@ -501,34 +485,52 @@ extern "C" const char* spmv_amd_precond_multigrid_level_spmm(const SpmvAmdPrecon
 
 static_assert(sizeof(SpmvAmdPcgMultiColumn) == sizeof(PcgMultiColumn), "lab.h's column record is the device record");
 
-extern "C" int spmv_amd_mg_multi_stage(const char* stage, int k, SpmvAmdMgMultiStageArgs* a) {
-    // argument checks: all before the first HIP call
+// The one body of spmv_amd_mg_multi_stage (dim 2) and spmv_amd_mg_multi_stage3d (dim 3, multigrid3d_multi.hip)
+int spmv_amd::mg_multi_stage(int dim, const char* stage, int k, SpmvAmdMgMultiStageArgs* a) {
+    // argument checks: all but the structure check before the first HIP call
     auto refuse = [&](const char* what) { return stage_fail(kTag, stage, what); };
     auto pointer = [&](const char* name, const void* ptr, int align) { return stage_pointer(kTag, stage, name, ptr, align); };
-    enum Stage { kRestrict, kProlong, kTerm0 } st;
-    if (stage == nullptr) return refuse("no stage named (residual_restrict, prolong, term0)"), 1;
-    if (!strcmp(stage, "residual_restrict")) st = kRestrict;
-    else if (!strcmp(stage, "prolong")) st = kProlong;
-    else if (!strcmp(stage, "term0")) st = kTerm0;
-    else return refuse("unknown stage (residual_restrict, prolong, term0)"), 1;
+    enum Stage { kNoStage, kRestrict, kProlong, kTerm0, kSpmm7, kSpmmCsr } st = kNoStage;
+    static const struct {
+        const char* name;
+        Stage st;
+        int dim;
+    } kStages[] = {{"residual_restrict", kRestrict, 2},   {"prolong", kProlong, 2},   {"term0", kTerm0, 2},
+                   {"residual_restrict3d", kRestrict, 3}, {"prolong3d", kProlong, 3}, {"stencil7_spmm", kSpmm7, 3}, {"spmm_csr", kSpmmCsr, 3}};
+    const bool cube = dim == 3;
+    if (stage == nullptr)
+        return refuse(cube ? "no stage named (residual_restrict3d, prolong3d, stencil7_spmm, spmm_csr)" : "no stage named (residual_restrict, prolong, term0)"), 1;
+    for (const auto& known : kStages)
+        if (known.dim == dim && !strcmp(stage, known.name)) st = known.st;
+    if (st == kNoStage)
+        return refuse(cube ? "unknown stage (residual_restrict3d, prolong3d, stencil7_spmm, spmm_csr)" : "unknown stage (residual_restrict, prolong, term0)"), 1;
+    const bool product = st == kSpmm7 || st == kSpmmCsr;
     if (k < 1 || k > kMaxRhs) return refuse("k is not 1 to 8"), 1;
     if (a == nullptr) return refuse("null arguments"), 1;
-    if (a->n < 2 || a->n > 46340) return refuse("the fine grid is outside 2..46340"), 1;
+    if (!cube && (a->n < 2 || a->n > 46340)) return refuse("the fine grid is outside 2..46340"), 1;
+    if (cube && (a->n < 2 || a->n > kStencil7MaxGrid)) return refuse("the fine grid of a 3-D stage is outside 2..674"), 1;
     const int block = k % 2 == 0 ? 16 : 8;  // a block vector: 16-byte accesses where k is even
-    if (st == kRestrict && (!pointer("row_ptr", a->row_ptr, 4) || !pointer("col_idx", a->col_idx, 4) || !pointer("values", a->values, 8))) return 1;
+    if ((st == kRestrict || product) && (!pointer("row_ptr", a->row_ptr, 4) || !pointer("col_idx", a->col_idx, 4) || !pointer("values", a->values, 8)))
+        return 1;
     if (!pointer("z", a->z, block)) return 1;
-    if (st != kProlong && !pointer("r", a->r, block)) return 1;
-    if (st != kTerm0 && !pointer("coarse", a->coarse, block)) return 1;
-    if (st == kTerm0 && (!pointer("d", a->d, block) || !pointer("dinv", a->dinv, 8))) return 1;
+    if ((st == kRestrict || st == kTerm0) && !pointer("r", a->r, block)) return 1;
+    if ((st == kRestrict || st == kProlong) && !pointer("coarse", a->coarse, block)) return 1;
+    if ((st == kTerm0 || product) && !pointer("d", a->d, block)) return 1;
+    if (st == kTerm0 && !pointer("dinv", a->dinv, 8)) return 1;
     if (a->cols != nullptr && !pointer("cols", a->cols, 8)) return 1;
 
     const PcgMultiColumn* cols = reinterpret_cast<const PcgMultiColumn*>(a->cols);
-    if (st == kRestrict) {
-        SlabCsr fine = mg_stencil_view(a->n, a->row_ptr, a->col_idx, a->values);
-        if (!mg_verify_stencil5(fine)) return refuse("the CSR is not a complete 5-point stencil of that grid"), 1;
-        launch_residual_restrict_multi(k, fine, cols, a->z, a->r, a->coarse);
+    if (st == kRestrict || product) {
+        SlabCsr fine = cube ? stencil7_view(a->n, a->row_ptr, a->col_idx, a->values) : mg_stencil_view(a->n, a->row_ptr, a->col_idx, a->values);
+        if (cube && !mg_verify_stencil7(fine, a->n)) return refuse("the CSR is not a complete 7-point stencil of that grid"), 1;
+        if (!cube && !mg_verify_stencil5(fine)) return refuse("the CSR is not a complete 5-point stencil of that grid"), 1;
+        if (st == kSpmm7) launch_spmm(plan_spmm_stencil7(fine, a->n), k, a->z, a->d, nullptr, kBatchStream);
+        else if (st == kSpmmCsr) launch_spmm(plan_spmm(fine, Stencil5Variant::Auto, true, fine.n_local, fine.n_local), k, a->z, a->d, nullptr, kBatchStream);
+        else if (cube) launch_residual_restrict3d_multi(k, fine, a->n, cols, a->z, a->r, a->coarse);
+        else launch_residual_restrict_multi(k, fine, cols, a->z, a->r, a->coarse);
     } else if (st == kProlong) {
-        launch_prolong_correct_multi(k, a->n, cols, a->coarse, a->z);
+        if (cube) launch_prolong_correct3d_multi(k, a->n, cols, a->coarse, a->z);
+        else launch_prolong_correct_multi(k, a->n, cols, a->coarse, a->z);
     } else {
         launch_mg_multi_term0(k, (long long)a->n * a->n, cols, a->r, a->dinv, a->c0, a->d, a->z);
     }
@@ -536,4 +538,6 @@ extern "C" int spmv_amd_mg_multi_stage(const char* stage, int k, SpmvAmdMgMultiS
     HIP_CHECK(hipDeviceSynchronize());
     return 0;
 }
+
+extern "C" int spmv_amd_mg_multi_stage(const char* stage, int k, SpmvAmdMgMultiStageArgs* a) { return mg_multi_stage(2, stage, k, a); }
 #endif  // SPMV_AMD_LAB

@@ -41,7 +41,7 @@
 #include "multi_rhs.hpp"
 #include "multi_rhs_device.hpp"
 #include "multi_solve.hpp"
-#include "precond.hpp"
+#include "multigrid.hpp"
 #include "reduce_device.hpp"
 #include "stream_device.hpp"
 #ifdef SPMV_AMD_LAB
@@ -473,7 +473,7 @@ extern "C" int spmv_amd_pcg_solve_device_multi(SpmvOperator* op, MatrixData* mat
     // the kernels' kind: a multigrid cycle begins with term 0 of level 0, so its init and r update are the Chebyshev ones
     const int kind = (m->kind == kChebyshev || mg) ? kCheb : m->kind == kJacobi ? kJac : kPlain;
     const int degree = m->kind == kChebyshev ? m->degree : 0;
-    const double c0 = mg ? mg_level_view(m->mg, 0).coef[0] : m->kind == kChebyshev ? m->coef[0] : 0.0;
+    const double c0 = mg ? m->mg->levels[0].coef[0] : m->kind == kChebyshev ? m->coef[0] : 0.0;
 
     CgWorkspaceScope scope;
     int device = 0;

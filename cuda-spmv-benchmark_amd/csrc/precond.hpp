@@ -1,5 +1,5 @@
 // precond.hpp -- what pcg.hip (the preconditioned loop, kinds "none", "jacobi", "chebyshev") and multigrid.hip (kind "multigrid",
-// DESIGN.md section 15) share: the preconditioner record, pcg.hip's set-up passes, the runner of a Chebyshev step -- the multigrid
+// DESIGN.md section 15; its hierarchy and launches: multigrid.hpp) share: the preconditioner record, pcg.hip's set-up passes, the runner of a Chebyshev step -- the multigrid
 // smoother IS section 14's application, run by the same function on a level's operator --, and the multigrid cycle the loop calls.
 #pragma once
 
@@ -7,7 +7,7 @@
 #include "solve_common.hpp"
 
 namespace spmv_amd {
-struct MgHierarchy;  // multigrid.hip
+struct MgHierarchy;  // multigrid.hpp
 }
 
 enum PrecondKind { kNone = 0, kJacobi = 1, kChebyshev = 2, kMultigrid = 3 };
@@ -83,36 +83,17 @@ struct ChebRun {
 bool cheb_step(ChebRun& c, double g, double h, bool last);
 bool cheb_steps(ChebRun& c, int degree, const double* coef, bool report);
 
-// ---- multigrid.hip ----
+// ---- what the PCG loops call of kind "multigrid" (multigrid.hip, multigrid_multi.hip; the hierarchy itself: multigrid.hpp) ----
 void mg_destroy(MgHierarchy* h);
 // One V-cycle on the hierarchy's own vectors: z = M^-1 r, r (level 0's rows, 16-byte aligned) only read. z: a vector the hierarchy
 // owns; the r.z partials are the ones the last post-smoothing step left. T (may be null): the solve's timers.
 Applied mg_cycle(MgHierarchy* h, const double* r, StageTimers* T);
 double* mg_result_vector(MgHierarchy* h);  // a level-0 vector of the hierarchy (what a loop hands on when no cycle ran)
-
-// ---- the hierarchy on block vectors (multigrid_multi.hip) ----
-// What the batched cycle reads of one level; the pointers are the hierarchy's.
-struct MgLevelView {
-    int dim = 2;             // 2: an n x n 5-point stencil; 3: an n x n x n 7-point one
-    int n = 0, rows = 0;     // the grid and its rows
-    int degree = 0;          // Chebyshev steps of the level's smoother (the coarsest level: of its solve)
-    const SlabCsr* view = nullptr;
-    Stencil5Variant variant = Stencil5Variant::RowGeneric;  // of the level's own Stencil5Plan
-    const double* dinv = nullptr;
-    const double* coef = nullptr;  // c0, h_1, g_1, ...
-};
-int mg_level_count(const MgHierarchy* h);
-MgLevelView mg_level_view(const MgHierarchy* h, int level);
 // The block vectors and SpMM plans of a hierarchy made by spmv_amd_precond_create_multigrid_multi or ..._multigrid3d_multi (null: a
 // single-vector hierarchy).
 struct MgMulti;
 MgMulti* mg_multi_of(const MgHierarchy* h);
 int mg_multi_capacity(const MgMulti* mm);  // max_rhs; 0 for null
-// Device bytes mg_multi_create will ask for, from the levels' rows alone (the creator sizes everything against free memory first).
-size_t mg_multi_bytes(const MgHierarchy* h, int max_rhs);
-// Allocates them and plans every level's SpMM; null (nothing left behind, said on stderr) when the device cannot provide them.
-MgMulti* mg_multi_create(const MgHierarchy* h, int max_rhs);
-void mg_multi_destroy(MgMulti* mm);
 // One V-cycle on k <= max_rhs interleaved columns, on the batch stream: Z = M^-1 R. Level 0 works on the caller's vectors -- R (only
 // read), D and Z holding term 0 on entry, W (scratch for A Z) -- every other level on the hierarchy's. cols: the device column records
 // (every launch returns at once when no column is running; a stopped column's D, Z and level vectors are scratch). Level 0's last step
@@ -120,10 +101,5 @@ void mg_multi_destroy(MgMulti* mm);
 struct PcgMultiColumn;
 void mg_cycle_multi(const MgHierarchy* h, int k, const PcgMultiColumn* cols, const double* R, double* D, double* Z, double* W,
                     double* partials, long long count, StageTimers* T);
-// A complete 5-point CSR on an n x n grid in the caller's arrays as a view, and its structure check (synchronises; sets the view's flag).
-SlabCsr mg_stencil_view(int n, const int* row_ptr, const int* col_idx, const double* values);
-bool mg_verify_stencil5(SlabCsr& v);
-// The structure check of a complete 7-point CSR on an n^3 grid (a view of stencil7_view, multigrid3d.hpp); synchronises.
-bool mg_verify_stencil7(SlabCsr& v, int n);
 
 }  // namespace spmv_amd

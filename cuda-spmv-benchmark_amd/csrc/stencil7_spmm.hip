@@ -20,8 +20,7 @@
 
 #include "multi_rhs.hpp"
 #include "multi_solve.hpp"
-#include "multigrid3d_device.hpp"
-#include "multigrid_multi_device.hpp"
+#include "multigrid_device.hpp"
 #include "stencil_geometry.hpp"
 #include "stencil_row_device.hpp"
 #include "stream_device.hpp"

@@ -46,6 +46,9 @@ SPMV_HD bool stencil_is_interior(int i, int j, int n) {
     return i > 0 && i < n - 1 && j > 0 && j < n - 1;
 }
 
+// The grid 2 x 2 (x 2) aggregation makes of an axis of n points: aggregate I holds the fine points 2I and, where it exists, 2I + 1.
+SPMV_HD int coarse_grid_of(int n) { return (n + 1) / 2; }
+
 // ---- n x n x n 7-point stencil, point (k, i, j) = row k n^2 + i n + j, rows sorted by column: [D,N,W,C,E,S,U] minus the absent
 // ones (D/U = -+n^2, N/S = -+n, W/E = -+1). Everything in 64 bits; n <= 674 keeps rows and nnz (7 n^3 - 6 n^2) inside int32.
 

@@ -358,6 +358,7 @@ int spmv_amd_precond_chebyshev_info(const SpmvAmdPrecond* m, int* degree, double
  * exist, t_i = fma(-1.0, (A z)_i, r_i), (A z)_i the bits of stencil5-csr's SpMV for row i.  (3) e_c = cycle(l+1, r_c).
  * (4) z = fma(2.0, e_c[agg(i)], z).  (5) nu + 1 updates t = fma(-1.0, (A z), r); u = dinv t; d = fma(g, u, h d); z = z + d: the first with
  * g = c0, h = 0.0 and d as step (1) left it, then steps 1..nu with (h_k, g_k).
+ * csrc/mg_schedule.hpp states this order once; the single-vector and the batched cycle (..._multigrid_multi below) both walk it.
  * The solve with this kind reads the iteration's verdict on the host before the cycle: the converging iteration runs none. */
 SpmvAmdPrecond* spmv_amd_precond_create_multigrid(SpmvOperator* op, int smoother_degree, int max_levels, int* bad_row);
 /* Kind "multigrid" for "stencil7-csr" (csrc/multigrid3d.hip): the cycle above on a hierarchy of 7-point stencils made

@@ -357,7 +357,8 @@ typedef struct SpmvAmdMgMultiStageArgs {
  * array, dinv or cols that are not 4- / 8-byte aligned; after the structure check (as spmv_amd_mg_stage makes it): a CSR that is not the
  * complete stencil. Returns 0 otherwise. */
 int spmv_amd_mg_multi_stage(const char* stage, int k, SpmvAmdMgMultiStageArgs* a);
-/* The two launches a 3-D level adds to the batched cycle (csrc/multigrid3d_multi.hip), on the same arguments: n is
+/* The two launches a 3-D level adds to the batched cycle (csrc/multigrid3d_multi.hip; the checks are one body with
+ * spmv_amd_mg_multi_stage's, in csrc/multigrid_multi.hip), on the same arguments: n is
  * the fine grid of n^3 rows, row_ptr / col_idx / values a complete 7-point stencil of it, coarse has ((n + 1) / 2)^3 rows. stage:
  * "residual_restrict3d", "prolong3d" (term 0 has no 3-D form: "term0" of spmv_amd_mg_multi_stage is a flat walk over the rows); and a
  * 3-D level's block product d = A z on the same CSR in its two kinds, "stencil7_spmm" ("spmm/stencil7-row-lds", csrc/stencil7_spmm.hip)

@@ -152,3 +152,50 @@ def test_multigrid_cuts_the_poisson_counts_tenfold():
     ours = {name: its for name, nu, tol, its in MG.TABLE if nu == 1 and tol == 1e-6}
     for name in ("poisson127", "poisson255"):
         assert 10 * ours[name] <= jacobi[name], (name, ours[name], jacobi[name])
+
+
+def test_vcycle_schedule_under_sanitizers(tmp_path):
+    """csrc/mg_schedule.hpp -- the one statement of the V-cycle's launch order and of which step writes the r.z partials, walked by the
+    single-vector and the batched cycle alike -- needs no HIP: tests/abi/mg_schedule_test.cpp includes it and standard headers only, is
+    compiled with g++ -fsanitize=address,undefined and run as it is. Its lines are compared with api.h's steps (1)-(5), restated here:
+    levels 1, 2, 3 and 5 x degree 0, 1, 2, the coarsest level solved by degree 8. Exactly one call per cycle carries `last`: the
+    final step of level 0 (one level: the last step of the coarsest solve)."""
+    import subprocess
+
+    def cycle(l, levels, nu):
+        coarsest = l + 1 == levels
+        yield l, "term0"  # (1) term 0, then steps 1..nu; the coarsest level: term 0 and eight steps
+        for k in range(1, (8 if coarsest else nu) + 1):
+            yield l, f"step{k}"
+        if coarsest:
+            return
+        yield l, "restrict"  # (2)
+        yield from cycle(l + 1, levels, nu)  # (3)
+        yield l, "prolong"  # (4)
+        for k in range(0, nu + 1):  # (5) nu + 1 updates: the first with g = c0, h = 0.0, then steps 1..nu
+            yield l, f"step{k}"
+
+    cases = [(levels, nu) for levels in (1, 2, 3, 5) for nu in (0, 1, 2)]
+    exe = tmp_path / "mg_schedule_test"
+    build = subprocess.run(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g", "-O1",
+                            "-I", os.path.join(ROOT, "cuda-spmv-benchmark_amd", "csrc"), os.path.join(ROOT, "tests", "abi", "mg_schedule_test.cpp"),
+                            "-o", str(exe)], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-3000:]
+    run = subprocess.run([str(exe)] + [str(v) for case in cases for v in case], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and "mg_schedule: ok" in run.stdout, (run.returncode, run.stdout[-2000:], run.stderr[-3000:])
+    assert "ERROR: AddressSanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr[-3000:]
+    got = {}
+    for line in run.stdout.splitlines():
+        words = line.split()
+        if words[0] == "case":
+            current = got.setdefault((int(words[1]), int(words[2])), [])
+        elif words[0] != "mg_schedule:":
+            current.append((int(words[0]), words[1], int(words[2])))
+    assert sorted(got) == sorted(cases)
+    for levels, nu in cases:
+        calls = got[(levels, nu)]
+        want = [(l, op, 0) for l, op in cycle(0, levels, nu)]
+        want[-1] = want[-1][:2] + (1,)
+        assert calls == want, (levels, nu, calls, want)
+        assert sum(last for _, _, last in calls) == 1 and calls[-1][0] == 0 and calls[-1][2] == 1, (levels, nu)
+        assert calls[-1][1] == ("step8" if levels == 1 else f"step{nu}"), (levels, nu, calls[-1])
