@@ -2,11 +2,14 @@
 // then 10 timed solves from x0 = 0 each.
 //   cg_solver <matrix.mtx | --stencil=N> [--mode=<m1,..>] [--host|--device] [--tol=1e-6]
 //             [--maxiter=1000] [--timers] [--json=<file>] [--csv=<file>] [--precond=none|jacobi|chebyshev[:K]|multigrid[:NU]]
+//             [--solver=cg|bicgstab]
 // --precond runs the preconditioned solver (spmv_amd_pcg_solve_device, device only); its JSON / CSV carry the mode string
 // <operator>+<kind>. Without it the binary takes cg_solve_device / cg_solve as before. chebyshev = the polynomial preconditioner
 // of degree 4, chebyshev:K of degree K (0..32), both on the automatic interval; the mode string is <operator>+chebyshev<K>.
 // multigrid = the aggregation multigrid V(1, 1) cycle (stencil5-csr, and stencil7-csr through the 3-D creator), multigrid:NU the V(NU, NU) cycle (0..8); the mode string is
 // <operator>+multigrid<NU>.
+// --solver=bicgstab runs spmv_amd_bicgstab_solve_device (nonsymmetric matrices; device only) with --precond=none (the default) or
+// jacobi; the mode string is <operator>+bicgstab or <operator>+jacobi+bicgstab. --solver=cg (the default) is everything above.
 // (The reference's own main, unmodified, also builds against this library: INTEGRATION.md. Unlike
 // it, this binary restarts every timed solve from x0 = 0 instead of from the warm-up's solution.)
 #include <algorithm>
@@ -17,12 +20,13 @@
 namespace {
 // num_runs preconditioned solves from x0 = 0 with the harness's statistics rule (csrc/harness.hip): mean and population sigma,
 // runs further than 2 sigma from the mean dropped, then median / min / max of the survivors; the stats of the last run.
+typedef int (*PrecondSolve)(SpmvOperator*, MatrixData*, const SpmvAmdPrecond*, const double*, double*, const CGConfig*, CGStats*);
 int pcg_runs(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, const double* b, std::vector<double>& x, CGConfig cfg,
-             int num_runs, BenchmarkStats* bs, CGStats* st) {
+             int num_runs, BenchmarkStats* bs, CGStats* st, PrecondSolve solve = spmv_amd_pcg_solve_device) {
     std::vector<double> t;
     for (int k = 0; k < num_runs; ++k) {
         std::fill(x.begin(), x.end(), 0.0);
-        if (spmv_amd_pcg_solve_device(op, mat, m, b, x.data(), &cfg, st) != 0) return 1;
+        if (solve(op, mat, m, b, x.data(), &cfg, st) != 0) return 1;
         t.push_back(st->time_total_ms);
     }
     double mean = 0.0, q = 0.0;
@@ -50,7 +54,7 @@ int pcg_runs(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, const d
 }  // namespace
 
 int main(int argc, char** argv) {
-    const char *matrix = nullptr, *modes_text = nullptr, *json = nullptr, *csv = nullptr, *precond = nullptr;
+    const char *matrix = nullptr, *modes_text = nullptr, *json = nullptr, *csv = nullptr, *precond = nullptr, *solver = "cg";
     int stencil = 0, stencil3d = 0, maxiter = 1000, timers = 0;
     bool device = true;
     double tol = 1e-6;
@@ -63,6 +67,7 @@ int main(int argc, char** argv) {
         else if (const char* v5 = app::value_of(argv[i], "--tol=")) tol = atof(v5);
         else if (const char* v6 = app::value_of(argv[i], "--maxiter=")) maxiter = atoi(v6);
         else if (const char* v7 = app::value_of(argv[i], "--precond=")) precond = v7;
+        else if (const char* v9 = app::value_of(argv[i], "--solver=")) solver = v9;
         else if (!strcmp(argv[i], "--host")) device = false;
         else if (!strcmp(argv[i], "--device")) device = true;
         else if (!strcmp(argv[i], "--timers")) timers = 1;
@@ -72,6 +77,22 @@ int main(int argc, char** argv) {
     if (!matrix && stencil <= 0 && stencil3d <= 0) {
         fprintf(stderr, "Usage: %s <matrix.mtx | --stencil=N | --stencil3d=N> [--mode=<modes>] [--host|--device] [--tol=] [--maxiter=] [--timers] [--json=] [--csv=]\n", argv[0]);
         return 1;
+    }
+    if (strcmp(solver, "cg") != 0 && strcmp(solver, "bicgstab") != 0) {
+        fprintf(stderr, "Error: unknown solver '%s' (cg, bicgstab)\n", solver);
+        return 1;
+    }
+    const bool bicgstab = !strcmp(solver, "bicgstab");
+    if (bicgstab) {
+        if (precond == nullptr) precond = "none";
+        if (strcmp(precond, "none") != 0 && strcmp(precond, "jacobi") != 0) {
+            fprintf(stderr, "Error: --solver=bicgstab takes --precond=none or --precond=jacobi, not '%s' (the other kinds are built for symmetric definite matrices)\n", precond);
+            return 1;
+        }
+        if (!device) {
+            fprintf(stderr, "Error: --solver=bicgstab runs the device solver only (no --host)\n");
+            return 1;
+        }
     }
     int cheb_degree = -1;  // >= 0: --precond=chebyshev[:K]
     int mg_degree = -1;    // >= 0: --precond=multigrid[:NU]
@@ -150,14 +171,16 @@ int main(int argc, char** argv) {
             const std::string kind = mg_degree >= 0     ? "multigrid" + std::to_string(mg_degree)
                                      : cheb_degree >= 0 ? "chebyshev" + std::to_string(cheb_degree)
                                                         : std::string(precond);
-            const std::string tag = m + "+" + kind;
+            const std::string tag = !bicgstab ? m + "+" + kind : kind == "none" ? m + "+bicgstab" : m + "+" + kind + "+bicgstab";
+            const PrecondSolve solve = bicgstab ? spmv_amd_bicgstab_solve_device : spmv_amd_pcg_solve_device;
+            if (bicgstab) printf("Solver: BiCGSTAB\n");
             printf("Preconditioner: %s\nWarmup (3 runs)...\n", kind.c_str());
             BenchmarkStats bs;
             memset(&bs, 0, sizeof bs);
-            bool ok = pcg_runs(op, &mat, pm, b.data(), x, quiet, 3, &bs, &st) == 0;
+            bool ok = pcg_runs(op, &mat, pm, b.data(), x, quiet, 3, &bs, &st, solve) == 0;
             memset(&bs, 0, sizeof bs);
             if (ok) printf("Running benchmark (10 runs)...\n");
-            ok = ok && pcg_runs(op, &mat, pm, b.data(), x, cfg, 10, &bs, &st) == 0;
+            ok = ok && pcg_runs(op, &mat, pm, b.data(), x, cfg, 10, &bs, &st, solve) == 0;
             spmv_amd_precond_destroy(pm);
             if (!ok) {
                 fprintf(stderr, "benchmark failed\n");

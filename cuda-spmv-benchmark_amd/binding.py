@@ -164,6 +164,7 @@ DECLARED_SYMBOLS = [
     "spmv_amd_pcg_solve_device_multi", "spmv_amd_pcg_last_history_multi", "spmv_amd_pcg_multi_workspace_bytes",
     "spmv_amd_precond_create_multigrid_multi", "spmv_amd_precond_multigrid_max_rhs", "spmv_amd_precond_apply_device_multi",
     "spmv_amd_precond_create_multigrid3d_multi",
+    "spmv_amd_bicgstab_solve_device", "spmv_amd_bicgstab_last_history",
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
 LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_cg_slab_block_map", "spmv_amd_cg_slab_slow_blocks",
@@ -171,7 +172,8 @@ LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set
                     "spmv_amd_pcg_last_step_launches", "spmv_amd_cg_multi_stage",
                     "spmv_amd_pcg_last_multigrid_cycles", "spmv_amd_precond_multigrid_level_csr", "spmv_amd_mg_stage",
                     "spmv_amd_pcg_multi_stage", "spmv_amd_mg_multi_stage", "spmv_amd_mg_multi_stage3d",
-                    "spmv_amd_mg3d_multi_level_product", "spmv_amd_precond_multigrid_level_spmm"]
+                    "spmv_amd_mg3d_multi_level_product", "spmv_amd_precond_multigrid_level_spmm",
+                    "spmv_amd_bicgstab_stage"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
 DECLARED_CXX_SYMBOLS = [
     "SPMV_CSR", "SPMV_STENCIL5_CSR", "SPMV_STENCIL7_CSR", "SPMV_STENCIL_HALO_MGPU", "SPMV_ELLPACK", "SPMV_STENCIL5_ELLPACK",
@@ -1407,3 +1409,48 @@ class CgSlab:
         if self.h:
             lib().spmv_amd_cg_slab_destroy(self.h)
             self.h = None
+
+
+# ---------------------------------------------------------------- BiCGSTAB (include/spmv_amd/api.h; csrc/bicgstab.hip)
+class BicgstabScalars(C.Structure):
+    """SpmvAmdBicgstabScalars (include/spmv_amd/lab.h): the device scalars of one BiCGSTAB solve."""
+    _fields_ = [("rho", C.c_double), ("sigma", C.c_double), ("alpha", C.c_double), ("omega", C.c_double), ("beta", C.c_double),
+                ("b_norm", C.c_double), ("residual", C.c_double), ("s_norm", C.c_double), ("iterations", C.c_int), ("converged", C.c_int),
+                ("breakdown", C.c_int), ("x_step", C.c_int), ("stop", C.c_int), ("pad", C.c_int)]
+
+
+class BicgstabStageArgs(C.Structure):
+    """SpmvAmdBicgstabStageArgs (include/spmv_amd/lab.h): device pointers and sizes of one spmv_amd_bicgstab_stage call."""
+    _fields_ = [("n", C.c_size_t), ("b", C.c_void_p), ("dinv", C.c_void_p), ("x", C.c_void_p), ("r", C.c_void_p), ("rhat", C.c_void_p),
+                ("p", C.c_void_p), ("phat", C.c_void_p), ("shat", C.c_void_p), ("v", C.c_void_p), ("t", C.c_void_p),
+                ("partials", C.c_void_p), ("count", C.c_int), ("which", C.c_int), ("tol", C.c_double), ("hist", C.c_void_p),
+                ("hist_cap", C.c_int)]
+
+
+def bicgstab_solve(op, host_matrix, precond, b, x0, tol=1e-6, max_iters=1000, verbose=0, timers=0):
+    """spmv_amd_bicgstab_solve_device; returns x, history, stats like pcg_solve_device (raises RuntimeError on a refusal)."""
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    x = np.ascontiguousarray(x0, dtype=np.float64).copy()
+    cfg = CGConfig(max_iters, tol, verbose, timers)
+    st = CGStats()
+    L = _pcg_lib()
+    L.spmv_amd_bicgstab_solve_device.argtypes = L.spmv_amd_pcg_solve_device.argtypes
+    L.spmv_amd_bicgstab_last_history.argtypes = [C.c_void_p, C.c_int]
+    rc = L.spmv_amd_bicgstab_solve_device(op.op, host_matrix.ptr, precond.handle, b.ctypes.data, x.ctypes.data, C.byref(cfg), C.byref(st))
+    if rc != 0:
+        raise RuntimeError(f"bicgstab_solve_device -> {rc}")
+    hist = np.zeros(max_iters + 1, dtype=np.float64)
+    count = L.spmv_amd_bicgstab_last_history(hist.ctypes.data, len(hist))
+    return x, hist[:count].copy(), st
+
+
+def bicgstab_stage(stage, kind, args, scalars=None):
+    """spmv_amd_bicgstab_stage (LAB build only; include/spmv_amd/lab.h): one stage of the BiCGSTAB solver's own kernels on the
+    device data `args` (BicgstabStageArgs) points to; returns its return code (0, or non-zero for a refusal)."""
+    if not is_lab():
+        raise RuntimeError("the BiCGSTAB stages exist in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+    L = lib()
+    L.spmv_amd_bicgstab_stage.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(BicgstabStageArgs), C.POINTER(BicgstabScalars)]
+    L.spmv_amd_bicgstab_stage.restype = C.c_int
+    return L.spmv_amd_bicgstab_stage(stage if stage is None else stage.encode(), kind if kind is None else kind.encode(),
+                                     None if args is None else C.byref(args), None if scalars is None else C.byref(scalars))

@@ -179,6 +179,8 @@ ChebSpmv cheb_spmv_of(const SpmvOperator* op);
 void release_cg_workspace();
 // The same for the preconditioned solver (pcg.hip); the caller holds the workspace lock (release_cg_workspace does).
 void release_pcg_workspace_locked();
+// The same for the BiCGSTAB solver (bicgstab.hip).
+void release_bicgstab_workspace_locked();
 
 // The device storage an operator of this library keeps its matrix in, for reading its diagonal (pcg.hip): the CSR of
 // stencil5-csr / cusparse-csr, or the slot-major planes of ellpack / stencil5-ellpack (idx[k * rows + r], -1 = padding).

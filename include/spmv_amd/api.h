@@ -441,6 +441,37 @@ int spmv_amd_pcg_last_history(double* out, int cap);
 /* Releases the solver workspaces: the same as spmv_amd_cg_release_workspace(). Safe to call at any time. */
 void spmv_amd_pcg_release_workspace(void);
 
+/* ---- BiCGSTAB: nonsymmetric systems (csrc/bicgstab.hip) ----
+ * Right-preconditioned BiCGSTAB over any operator with run_device: A need not be symmetric or definite. The contract is
+ * spmv_amd_pcg_solve_device's: b, x host arrays (x in = x0, out = solution; upload and download outside the timed region), the
+ * statistics, timer rule and verbose semantics (lines tagged [BICGSTAB-DEVICE]), the stopping rule (strict ||r|| / ||r0|| < tol on
+ * the recurrence residual, which right preconditioning keeps the true one; the converging iteration counted), every argument
+ * check before the first HIP call with a [BICGSTAB] sentence on stderr and a non-zero return, the pair (op, m) checked as there.
+ * m: kind "none" or "jacobi" (a handle of spmv_amd_precond_create_from_diagonal included); kinds "chebyshev" and "multigrid" are
+ * built for symmetric definite matrices and refused. A hat means "times dinv" (kind "none": the same vector); every fma is
+ * explicit, every other operation rounds once; every dot product is a streaming sum of the PCG shape (pair-wise partials per
+ * wave, then pcg_reduce_kernel's geometry), so every operator that gives the same A p bits gives the same solve bits.
+ *   r = fma(1.0, b, -1.0 * (A x0)) ; r^ = r ; p = r ; p^ = dinv p ; rho = r.r ; ||r0|| = sqrt(rho) ; history[0] = ||r0||
+ *   iteration:
+ *   1. v = A p^
+ *   2. sigma = r^.v ; zero or not finite: BREAKDOWN -- the iteration is counted, the unchanged residual recorded, nothing updated
+ *   3. alpha = rho / sigma ; s = fma(-alpha, v, r) ; s^ = dinv s ; ||s|| = sqrt(s.s)
+ *   4. ||s|| / ||r0|| < tol: HALF STEP -- x = fma(alpha, p^, x), the iteration counted, ||s|| recorded, converged
+ *   5. t = A s^ ; omega = (t.s) / (t.t) ; t.t or t.s zero or not finite: BREAKDOWN -- x = fma(alpha, p^, x), r = s, ||s||
+ *      recorded, the iteration counted
+ *   6. x = fma(omega, s^, fma(alpha, p^, x)) ; r = fma(-omega, t, s) ; ||r|| = sqrt(r.r) recorded, the iteration counted, then the
+ *      stopping test
+ *   7. rho' = r^.r ; zero or not finite: BREAKDOWN, x and r keep their update ; else beta = (rho' / rho) * (alpha / omega) ;
+ *      rho = rho' ; p = fma(beta, fma(-omega, v, p), r) ; p^ = dinv p
+ * A breakdown ends the solve with converged = 0 and x finite; there is no sign test. The same solve twice gives bit-identical x
+ * and history. The workspace (x, b, r, r^, p, v, t; "jacobi": p^ and s^ as well) is sized against the device's free memory first,
+ * kept between calls and released with the other CG workspaces (an operator's free(), spmv_amd_cg_release_workspace(),
+ * spmv_amd_pcg_release_workspace()). */
+int spmv_amd_bicgstab_solve_device(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, const double* b, double* x,
+                                   const CGConfig* config, CGStats* stats);
+/* The recorded residual norms, k = 0..iterations, of the last BiCGSTAB solve (the other solvers' histories are not touched by one). */
+int spmv_amd_bicgstab_last_history(double* out, int cap);
+
 /* ---- preconditioned CG for several right-hand sides (csrc/pcg_multi.hip) ----
  * nrhs (1..8) INDEPENDENT preconditioned solves on one operator under one preconditioner of kind "none", "jacobi" (a from-diagonal one
  * included), "chebyshev", or "multigrid" from spmv_amd_precond_create_multigrid_multi or ..._multigrid3d_multi with nrhs <= max_rhs: per column exactly the algebra, stopping rule and breakdown rule of spmv_amd_pcg_solve_device, with the

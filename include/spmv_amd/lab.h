@@ -185,6 +185,64 @@ typedef struct SpmvAmdPcgStageArgs {
  * Returns 0 otherwise. */
 int spmv_amd_pcg_stage(const char* stage, const char* kind, SpmvAmdPcgStageArgs* a, SpmvAmdPcgScalars* scalars);
 
+/* The device scalars of one BiCGSTAB solve (csrc/bicgstab.hip keeps the same record on the device; api.h states the algebra). */
+typedef struct SpmvAmdBicgstabScalars {
+    double rho;       /* r^.r of the current residual */
+    double sigma, alpha, omega, beta;
+    double b_norm;    /* ||r0|| */
+    double residual;  /* the norm recorded last */
+    double s_norm;    /* ||s|| of this iteration */
+    int iterations;
+    int converged;    /* stopping test met (by the half step or by the whole one) */
+    int breakdown;    /* 0, or which scalar stopped the solve: 1 sigma, 2 omega (t.t or t.s), 3 rho' */
+    int x_step;       /* what the x / r kernel applies in this iteration: 0 nothing, 1 the half step, 2 the whole step */
+    int stop;         /* the verdict: set with converged or breakdown; kernels behind it return at once */
+    int pad;
+} SpmvAmdBicgstabScalars;
+
+/* Device pointers and sizes of one spmv_amd_bicgstab_stage call; a stage reads only the fields listed for it. Kind "none" keeps
+ * p^ in p and s^ in r: phat and shat are not looked at. */
+typedef struct SpmvAmdBicgstabStageArgs {
+    size_t n;            /* rows (every stage but reduce) */
+    const double* b;     /* init */
+    const double* dinv;  /* kind "jacobi": init, update_s, direction */
+    double* x;           /* update_xr: in and out */
+    double* r;           /* init: out; update_s: in (r) and out (s); dot_t: in (s); update_xr: in (s) and out (r); direction: in */
+    double* rhat;        /* init: out; dot_rv, update_xr: in */
+    double* p;           /* init: out; direction: in and out; kind "none": update_xr: in */
+    double* phat;        /* kind "jacobi": init, direction: out; update_xr: in */
+    double* shat;        /* kind "jacobi": update_s: out; update_xr: in */
+    double* v;           /* init: in (A x0); dot_rv, update_s, direction: in */
+    const double* t;     /* dot_t, update_xr: in */
+    double* partials;    /* the vector stages: out, value v of workgroup g at [v * count + g]; reduce: in, the same layout */
+    int count;           /* the vector stages: out, the workgroups of the launch = partials per value ((n / 2 + 63) / 64, at least 1:
+                            the buffer holds 2 * count doubles); reduce: in */
+    int which;           /* reduce: the scalar step, 0 = r0.r0, 1 = sigma = r^.v, 2 = s.s, 3 = t.s / t.t (two values), 4 = r.r / r^.r
+                            (two values) */
+    double tol;          /* reduce, which = 2 and 4 */
+    double* hist;        /* reduce: residual history, hist_cap doubles (may be null when hist_cap is 0) */
+    int hist_cap;
+} SpmvAmdBicgstabStageArgs;
+
+/* The BiCGSTAB solver's own kernels (csrc/bicgstab.hip), one stage per call on the caller's device data -- the launches
+ * spmv_amd_bicgstab_solve_device makes, through the functions it makes them with. The model is spmv_amd_pcg_stage;
+ * tests/test_bicgstab_stages_gpu.py holds each stage against the restatement. Every call synchronises. stage (kind = "jacobi" or
+ * "none"; "reduce", "dot_rv" and "dot_t" do not look at it):
+ *   "init"       r = fma(1.0, b, -1.0 * v), r^ = r, p = r, p^ = dinv p, the partials of r.r; sets a->count
+ *   "dot_rv"     the partials of r^.v; sets a->count
+ *   "update_s"   nothing when scalars->stop; else r = fma(-alpha, v, r) (now s), s^ = dinv s, the partials of s.s; sets a->count
+ *   "dot_t"      nothing when scalars->stop; else the partials of t.s (value 0) and t.t (value 1), s read from r; sets a->count
+ *   "update_xr"  scalars->x_step 0: nothing; 1: x = fma(alpha, p^, x); 2: x = fma(omega, s^, fma(alpha, p^, x)), r = fma(-omega, t, r)
+ *                and the partials of r.r (value 0) and r^.r (value 1); sets a->count
+ *   "direction"  nothing when scalars->stop; else p = fma(beta, fma(-omega, v, p), r), p^ = dinv p
+ *   "reduce"     the sums of a->count partials of one (which 0..2) or two values, then the scalar step `which` on *scalars (read and
+ *                written, every field) with a->tol, a->hist and a->hist_cap
+ * Vectors are accessed in 16-byte pairs. Refused before any HIP call, with a sentence on stderr and a non-zero return: an unknown
+ * stage or kind, null arguments, n < 1, count < 1, which outside 0..4, hist_cap < 0, a null pointer the stage needs (scalars: every
+ * stage but "init" and "dot_rv"), a vector that is not 16-byte aligned, partials or hist that are not 8-byte aligned. Returns 0
+ * otherwise. */
+int spmv_amd_bicgstab_stage(const char* stage, const char* kind, SpmvAmdBicgstabStageArgs* a, SpmvAmdBicgstabScalars* scalars);
+
 /* Kind "chebyshev": how many step launches of the last solve's LOOP did work, i.e. were not stopped by the iteration's verdict (the
  * application behind the initial residual is not counted). Every iteration but the converging one runs `degree` of them:
  * degree * (iterations - 1) for a solve that converged. 0 after a solve of another kind. */
