@@ -2,7 +2,7 @@
 // then 10 timed solves from x0 = 0 each.
 //   cg_solver <matrix.mtx | --stencil=N> [--mode=<m1,..>] [--host|--device] [--tol=1e-6]
 //             [--maxiter=1000] [--timers] [--json=<file>] [--csv=<file>] [--precond=none|jacobi|chebyshev[:K]|multigrid[:NU]]
-//             [--solver=cg|bicgstab]
+//             [--solver=cg|bicgstab|gcr[:M]]
 // --precond runs the preconditioned solver (spmv_amd_pcg_solve_device, device only); its JSON / CSV carry the mode string
 // <operator>+<kind>. Without it the binary takes cg_solve_device / cg_solve as before. chebyshev = the polynomial preconditioner
 // of degree 4, chebyshev:K of degree K (0..32), both on the automatic interval; the mode string is <operator>+chebyshev<K>.
@@ -10,6 +10,9 @@
 // <operator>+multigrid<NU>.
 // --solver=bicgstab runs spmv_amd_bicgstab_solve_device (nonsymmetric matrices; device only) with --precond=none (the default) or
 // jacobi; the mode string is <operator>+bicgstab or <operator>+jacobi+bicgstab. --solver=cg (the default) is everything above.
+// --solver=gcr[:M] runs spmv_amd_gcr_solve_device (nonsymmetric matrices; device only), restarted every M = 1..32 iterations (gcr: the
+// default, 16), with every --precond value --solver=cg takes (none is the default); the mode string is <operator>+gcr<M> or
+// <operator>+<kind as above>+gcr<M>.
 // (The reference's own main, unmodified, also builds against this library: INTEGRATION.md. Unlike
 // it, this binary restarts every timed solve from x0 = 0 instead of from the warm-up's solution.)
 #include <algorithm>
@@ -22,11 +25,13 @@ namespace {
 // runs further than 2 sigma from the mean dropped, then median / min / max of the survivors; the stats of the last run.
 typedef int (*PrecondSolve)(SpmvOperator*, MatrixData*, const SpmvAmdPrecond*, const double*, double*, const CGConfig*, CGStats*);
 int pcg_runs(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, const double* b, std::vector<double>& x, CGConfig cfg,
-             int num_runs, BenchmarkStats* bs, CGStats* st, PrecondSolve solve = spmv_amd_pcg_solve_device) {
+             int num_runs, BenchmarkStats* bs, CGStats* st, PrecondSolve solve = spmv_amd_pcg_solve_device, int gcr_restart = 0) {
     std::vector<double> t;
     for (int k = 0; k < num_runs; ++k) {
         std::fill(x.begin(), x.end(), 0.0);
-        if (solve(op, mat, m, b, x.data(), &cfg, st) != 0) return 1;
+        // gcr_restart > 0: the GCR solver, which takes its restart beside the common arguments
+        if ((gcr_restart > 0 ? spmv_amd_gcr_solve_device(op, mat, m, gcr_restart, b, x.data(), &cfg, st) : solve(op, mat, m, b, x.data(), &cfg, st)) != 0)
+            return 1;
         t.push_back(st->time_total_ms);
     }
     double mean = 0.0, q = 0.0;
@@ -78,8 +83,22 @@ int main(int argc, char** argv) {
         fprintf(stderr, "Usage: %s <matrix.mtx | --stencil=N | --stencil3d=N> [--mode=<modes>] [--host|--device] [--tol=] [--maxiter=] [--timers] [--json=] [--csv=]\n", argv[0]);
         return 1;
     }
-    if (strcmp(solver, "cg") != 0 && strcmp(solver, "bicgstab") != 0) {
-        fprintf(stderr, "Error: unknown solver '%s' (cg, bicgstab)\n", solver);
+    int gcr = 0;  // > 0: --solver=gcr[:M], the restart
+    if (!strncmp(solver, "gcr", 3) && (solver[3] == '\0' || solver[3] == ':')) {
+        char* end = nullptr;
+        const long k = solver[3] == ':' ? strtol(solver + 4, &end, 10) : 16;
+        if (solver[3] == ':' && (end == solver + 4 || *end != '\0' || k < 1 || k > 32)) {
+            fprintf(stderr, "Error: --solver=gcr:M takes a restart M of 1..32, not '%s'\n", solver + 4);
+            return 1;
+        }
+        if (!device) {
+            fprintf(stderr, "Error: --solver=gcr runs the device solver only (no --host)\n");
+            return 1;
+        }
+        gcr = (int)k;
+        if (precond == nullptr) precond = "none";
+    } else if (strcmp(solver, "cg") != 0 && strcmp(solver, "bicgstab") != 0) {
+        fprintf(stderr, "Error: unknown solver '%s' (cg, bicgstab, gcr[:M])\n", solver);
         return 1;
     }
     const bool bicgstab = !strcmp(solver, "bicgstab");
@@ -171,16 +190,18 @@ int main(int argc, char** argv) {
             const std::string kind = mg_degree >= 0     ? "multigrid" + std::to_string(mg_degree)
                                      : cheb_degree >= 0 ? "chebyshev" + std::to_string(cheb_degree)
                                                         : std::string(precond);
-            const std::string tag = !bicgstab ? m + "+" + kind : kind == "none" ? m + "+bicgstab" : m + "+" + kind + "+bicgstab";
+            const std::string name = gcr > 0 ? "gcr" + std::to_string(gcr) : std::string("bicgstab");
+            const std::string tag = !bicgstab && gcr == 0 ? m + "+" + kind : kind == "none" ? m + "+" + name : m + "+" + kind + "+" + name;
             const PrecondSolve solve = bicgstab ? spmv_amd_bicgstab_solve_device : spmv_amd_pcg_solve_device;
             if (bicgstab) printf("Solver: BiCGSTAB\n");
+            if (gcr > 0) printf("Solver: GCR(%d)\n", gcr);
             printf("Preconditioner: %s\nWarmup (3 runs)...\n", kind.c_str());
             BenchmarkStats bs;
             memset(&bs, 0, sizeof bs);
-            bool ok = pcg_runs(op, &mat, pm, b.data(), x, quiet, 3, &bs, &st, solve) == 0;
+            bool ok = pcg_runs(op, &mat, pm, b.data(), x, quiet, 3, &bs, &st, solve, gcr) == 0;
             memset(&bs, 0, sizeof bs);
             if (ok) printf("Running benchmark (10 runs)...\n");
-            ok = ok && pcg_runs(op, &mat, pm, b.data(), x, cfg, 10, &bs, &st, solve) == 0;
+            ok = ok && pcg_runs(op, &mat, pm, b.data(), x, cfg, 10, &bs, &st, solve, gcr) == 0;
             spmv_amd_precond_destroy(pm);
             if (!ok) {
                 fprintf(stderr, "benchmark failed\n");

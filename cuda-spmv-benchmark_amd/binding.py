@@ -165,6 +165,7 @@ DECLARED_SYMBOLS = [
     "spmv_amd_precond_create_multigrid_multi", "spmv_amd_precond_multigrid_max_rhs", "spmv_amd_precond_apply_device_multi",
     "spmv_amd_precond_create_multigrid3d_multi",
     "spmv_amd_bicgstab_solve_device", "spmv_amd_bicgstab_last_history",
+    "spmv_amd_gcr_solve_device", "spmv_amd_gcr_last_history", "spmv_amd_gcr_workspace_bytes",
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
 LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_cg_slab_block_map", "spmv_amd_cg_slab_slow_blocks",
@@ -173,7 +174,7 @@ LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set
                     "spmv_amd_pcg_last_multigrid_cycles", "spmv_amd_precond_multigrid_level_csr", "spmv_amd_mg_stage",
                     "spmv_amd_pcg_multi_stage", "spmv_amd_mg_multi_stage", "spmv_amd_mg_multi_stage3d",
                     "spmv_amd_mg3d_multi_level_product", "spmv_amd_precond_multigrid_level_spmm",
-                    "spmv_amd_bicgstab_stage"]
+                    "spmv_amd_bicgstab_stage", "spmv_amd_gcr_stage"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
 DECLARED_CXX_SYMBOLS = [
     "SPMV_CSR", "SPMV_STENCIL5_CSR", "SPMV_STENCIL7_CSR", "SPMV_STENCIL_HALO_MGPU", "SPMV_ELLPACK", "SPMV_STENCIL5_ELLPACK",
@@ -1454,3 +1455,68 @@ def bicgstab_stage(stage, kind, args, scalars=None):
     L.spmv_amd_bicgstab_stage.restype = C.c_int
     return L.spmv_amd_bicgstab_stage(stage if stage is None else stage.encode(), kind if kind is None else kind.encode(),
                                      None if args is None else C.byref(args), None if scalars is None else C.byref(scalars))
+
+
+# ---------------------------------------------------------------- GCR(m) (include/spmv_amd/api.h; csrc/gcr.hip)
+GCR_MAX_RESTART = 32
+GCR_DOT_CHUNK = 8    # SPMV_AMD_GCR_DOT_CHUNK (include/spmv_amd/lab.h)
+GCR_ORTH_CHUNK = 4   # SPMV_AMD_GCR_ORTH_CHUNK
+
+
+class GcrScalars(C.Structure):
+    """SpmvAmdGcrScalars (include/spmv_amd/lab.h): the device scalars of one GCR solve."""
+    _fields_ = [("gamma", C.c_double * GCR_MAX_RESTART), ("beta", C.c_double * GCR_MAX_RESTART), ("alpha", C.c_double), ("rho", C.c_double),
+                ("b_norm", C.c_double), ("residual", C.c_double), ("iterations", C.c_int), ("converged", C.c_int), ("breakdown", C.c_int),
+                ("stop", C.c_int)]
+
+
+class GcrStageArgs(C.Structure):
+    """SpmvAmdGcrStageArgs (include/spmv_amd/lab.h): device pointers and sizes of one spmv_amd_gcr_stage call."""
+    _fields_ = [("n", C.c_size_t), ("b", C.c_void_p), ("v", C.c_void_p), ("dinv", C.c_void_p), ("x", C.c_void_p), ("r", C.c_void_p),
+                ("zs", C.c_void_p), ("z_in", C.c_void_p), ("Q", C.POINTER(C.c_void_p)), ("Z", C.POINTER(C.c_void_p)), ("slot", C.c_int),
+                ("partials", C.c_void_p), ("count", C.c_int), ("which", C.c_int), ("tol", C.c_double), ("hist", C.c_void_p),
+                ("hist_cap", C.c_int)]
+
+
+def _gcr_lib():
+    L = _pcg_lib()
+    if not getattr(L, "_gcr_sigs", False):
+        L.spmv_amd_gcr_solve_device.argtypes = [C.POINTER(SpmvOperator), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.POINTER(CGConfig), C.POINTER(CGStats)]
+        L.spmv_amd_gcr_last_history.argtypes = [C.c_void_p, C.c_int]
+        L.spmv_amd_gcr_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_char_p]
+        L.spmv_amd_gcr_workspace_bytes.restype = C.c_size_t
+        L._gcr_sigs = True
+    return L
+
+
+def gcr_solve(op, host_matrix, precond, b, x0, restart=0, tol=1e-6, max_iters=1000, verbose=0, timers=0):
+    """spmv_amd_gcr_solve_device; returns x, history, stats like bicgstab_solve (raises RuntimeError on a refusal)."""
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    x = np.ascontiguousarray(x0, dtype=np.float64).copy()
+    cfg = CGConfig(max_iters, tol, verbose, timers)
+    st = CGStats()
+    L = _gcr_lib()
+    rc = L.spmv_amd_gcr_solve_device(op.op, host_matrix.ptr, precond.handle, restart, b.ctypes.data, x.ctypes.data, C.byref(cfg), C.byref(st))
+    if rc != 0:
+        raise RuntimeError(f"gcr_solve_device -> {rc}")
+    hist = np.zeros(max_iters + 1, dtype=np.float64)
+    count = L.spmv_amd_gcr_last_history(hist.ctypes.data, len(hist))
+    return x, hist[:count].copy(), st
+
+
+def gcr_workspace_bytes(rows, restart, kind):
+    """spmv_amd_gcr_workspace_bytes: 0 for refused arguments."""
+    return int(_gcr_lib().spmv_amd_gcr_workspace_bytes(rows, restart, kind if kind is None else kind.encode()))
+
+
+def gcr_stage(stage, kind, args, scalars=None):
+    """spmv_amd_gcr_stage (LAB build only; include/spmv_amd/lab.h): one stage of the GCR solver's own kernels on the device data
+    `args` (GcrStageArgs) points to; returns its return code (0, or non-zero for a refusal)."""
+    if not is_lab():
+        raise RuntimeError("the GCR stages exist in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+    L = lib()
+    L.spmv_amd_gcr_stage.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(GcrStageArgs), C.POINTER(GcrScalars)]
+    L.spmv_amd_gcr_stage.restype = C.c_int
+    return L.spmv_amd_gcr_stage(stage if stage is None else stage.encode(), kind if kind is None else kind.encode(),
+                                None if args is None else C.byref(args), None if scalars is None else C.byref(scalars))

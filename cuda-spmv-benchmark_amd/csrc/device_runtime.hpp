@@ -181,6 +181,8 @@ void release_cg_workspace();
 void release_pcg_workspace_locked();
 // The same for the BiCGSTAB solver (bicgstab.hip).
 void release_bicgstab_workspace_locked();
+// The same for the GCR solver (gcr.hip).
+void release_gcr_workspace_locked();
 
 // The device storage an operator of this library keeps its matrix in, for reading its diagonal (pcg.hip): the CSR of
 // stencil5-csr / cusparse-csr, or the slot-major planes of ellpack / stencil5-ellpack (idx[k * rows + r], -1 = padding).

@@ -472,6 +472,47 @@ int spmv_amd_bicgstab_solve_device(SpmvOperator* op, MatrixData* mat, const Spmv
 /* The recorded residual norms, k = 0..iterations, of the last BiCGSTAB solve (the other solvers' histories are not touched by one). */
 int spmv_amd_bicgstab_last_history(double* out, int cap);
 
+/* ---- GCR(m): nonsymmetric systems under ANY preconditioner (csrc/gcr.hip) ----
+ * Restarted GCR (generalised conjugate residuals; mathematically FGMRES) over any operator with run_device: A need not be symmetric
+ * or definite, and m may be of EVERY kind -- "none", "jacobi" (a handle of spmv_amd_precond_create_from_diagonal included),
+ * "chebyshev", "multigrid" of either dimension on its own operator: the loop is flexible, so an application that is a polynomial or
+ * a V-cycle is as good as a matrix, and it minimises the residual over its basis, so the recorded norm never grows. Kind "chebyshev"
+ * is built on the interval of a symmetric definite spectrum: on a convection-dominated matrix the loop does not diverge but MAY
+ * STAGNATE (relative residuals of 0.1 .. 0.9 after 1 500 iterations were seen on the CPU); "multigrid" is the preconditioner this
+ * solver exists for. The contract is spmv_amd_pcg_solve_device's: b, x host arrays (x in = x0, out = solution; upload and download
+ * outside the timed region), the statistics, timer rule and verbose semantics (lines tagged [GCR-DEVICE]), the stopping rule (strict
+ * ||r|| / ||r0|| < tol on the recurrence residual, which right preconditioning keeps the true one; the converging iteration
+ * counted), every argument check before the first HIP call with a [GCR] sentence on stderr and a non-zero return, the pair (op, m)
+ * checked as there. restart = m: 1 .. 32, 0 means the default 16; anything else is refused. Every fma is explicit, every other
+ * operation rounds once; every dot product is a streaming sum of the PCG shape (pair-wise partials per wave, then
+ * pcg_reduce_kernel's geometry), so an operator contributes only the bits of A z.
+ *   r = fma(1.0, b, -1.0 * (A x0)) ; ||r0|| = sqrt(r.r) ; history[0] = ||r0||
+ *   iteration k, slot j = k mod m (j == 0 empties the basis):
+ *   1. z = M^-1 r      "none": z is r ; "jacobi": dinv * r ; "chebyshev": the application stated above (u = dinv r, d = c0 u, z = d,
+ *                      then the steps) ; "multigrid": one V-cycle
+ *   2. q = A z
+ *   3. beta_i = (q.Q_i) / gamma_i, i = 0 .. j-1, ALL from the q of step 2 (classical Gram-Schmidt: one pass over the basis)
+ *   4. for i ascending: q = fma(-beta_i, Q_i, q) ; z = fma(-beta_i, Z_i, z)
+ *   5. gamma = q.q ; rho = r.q ; gamma zero or not finite, or rho zero or not finite: BREAKDOWN -- the iteration counted, the
+ *      unchanged residual recorded, x untouched, converged = 0
+ *   6. alpha = rho / gamma ; x = fma(alpha, z, x) ; r = fma(-alpha, q, r) ; ||r|| = sqrt(r.r) recorded, the iteration counted, then
+ *      the strict stopping test
+ *   7. Z_j = z ; Q_j = q ; gamma_j = gamma
+ * The same solve twice gives bit-identical x and history. The workspace -- x, b, r, 2 m basis vectors, the partials (32 values wide
+ * whatever m, so a unit of restart costs its two vectors and nothing else), "jacobi": one vector, "chebyshev": three; a multigrid
+ * kind keeps its vectors in the handle -- is sized against the device's free memory first (a request that does not fit is refused
+ * with a sentence that names the largest restart that would), kept between calls and released with the other CG workspaces (an
+ * operator's free(), spmv_amd_cg_release_workspace(), spmv_amd_pcg_release_workspace()). */
+int spmv_amd_gcr_solve_device(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, int restart, const double* b, double* x,
+                              const CGConfig* config, CGStats* stats);
+/* The recorded residual norms, k = 0..iterations, of the last GCR solve (the other solvers' histories are not touched by one). */
+int spmv_amd_gcr_last_history(double* out, int cap);
+/* The bytes of the vectors and partials a GCR solve of `rows` rows keeps at this restart (0: the default) under this kind ("none",
+ * "jacobi", "chebyshev", "multigrid"): (3 + 2 m + s) * 8 * rows + 32 * 8 * ((rows / 2 + 63) / 64, at least 1), s = 0, 1, 3, 0. The
+ * history, the scalar record and the reduction scratch (under 100 KB + 8 * max_iters) are not counted. 0: refused arguments (rows
+ * < 1, restart outside 0 .. 32, a null or unknown kind). No HIP call. */
+size_t spmv_amd_gcr_workspace_bytes(int rows, int restart, const char* kind);
+
 /* ---- preconditioned CG for several right-hand sides (csrc/pcg_multi.hip) ----
  * nrhs (1..8) INDEPENDENT preconditioned solves on one operator under one preconditioner of kind "none", "jacobi" (a from-diagonal one
  * included), "chebyshev", or "multigrid" from spmv_amd_precond_create_multigrid_multi or ..._multigrid3d_multi with nrhs <= max_rhs: per column exactly the algebra, stopping rule and breakdown rule of spmv_amd_pcg_solve_device, with the

@@ -243,6 +243,65 @@ typedef struct SpmvAmdBicgstabStageArgs {
  * otherwise. */
 int spmv_amd_bicgstab_stage(const char* stage, const char* kind, SpmvAmdBicgstabStageArgs* a, SpmvAmdBicgstabScalars* scalars);
 
+/* The device scalars of one GCR solve (csrc/gcr.hip keeps the same record on the device; api.h states the algebra). */
+#define SPMV_AMD_GCR_MAX_RESTART 32
+#define SPMV_AMD_GCR_DOT_CHUNK 8   /* basis vectors per chunk of the multidot kernel */
+#define SPMV_AMD_GCR_ORTH_CHUNK 4  /* basis slots per chunk of the orthogonalise kernel */
+typedef struct SpmvAmdGcrScalars {
+    double gamma[SPMV_AMD_GCR_MAX_RESTART]; /* q.q of the basis slots filled since the last restart */
+    double beta[SPMV_AMD_GCR_MAX_RESTART];  /* this iteration's (q.Q_i) / gamma_i, i < slot */
+    double alpha, rho;                      /* this iteration's step length and r.q */
+    double b_norm;                          /* ||r0|| */
+    double residual;                        /* the norm recorded last */
+    int iterations;
+    int converged;
+    int breakdown; /* 0, or which scalar stopped the solve: 1 gamma = q.q, 2 rho = r.q */
+    int stop;      /* the verdict: set with converged or breakdown; kernels behind it return at once */
+} SpmvAmdGcrScalars;
+
+/* Device pointers and sizes of one spmv_amd_gcr_stage call; a stage reads only the fields listed for it. Q and Z are HOST arrays of
+ * device pointers, one 16-byte aligned vector per basis slot; entries past `slot` are not looked at. */
+typedef struct SpmvAmdGcrStageArgs {
+    size_t n;            /* rows (every stage but reduce) */
+    const double* b;     /* init */
+    const double* v;     /* init: A x0 */
+    const double* dinv;  /* kind "jacobi": init, update_xr */
+    double* x;           /* update_xr: in and out */
+    double* r;           /* init: out; orthogonalise: in; update_xr: in and out */
+    double* zs;          /* kind "jacobi": init, update_xr: out, dinv r */
+    const double* z_in;  /* orthogonalise: z = M^-1 r (may be r itself) */
+    double* const* Q;    /* multidot: Q[0 .. slot] in; orthogonalise: Q[0 .. slot-1] in, Q[slot] in and out; update_xr: Q[slot] in */
+    double* const* Z;    /* orthogonalise: Z[0 .. slot-1] in, Z[slot] out; update_xr: Z[slot] in */
+    int slot;            /* j: multidot 1 .. 31, orthogonalise and update_xr 0 .. 31; reduce: which = 1 and 2 */
+    double* partials;    /* the vector stages: out, value v of workgroup g at [v * count + g]; reduce: in, the same layout */
+    int count;           /* the vector stages: out, the workgroups of the launch = partials per value ((n / 2 + 63) / 64, at least 1);
+                            reduce: in */
+    int which;           /* reduce: the scalar step, 0 = r0.r0, 1 = the betas (slot values), 2 = gamma and rho (two values), 3 = r.r */
+    double tol;          /* reduce, which = 3 */
+    double* hist;        /* reduce: residual history, hist_cap doubles (may be null when hist_cap is 0) */
+    int hist_cap;
+} SpmvAmdGcrStageArgs;
+
+/* The GCR solver's own kernels (csrc/gcr.hip), one stage per call on the caller's device data -- the launches
+ * spmv_amd_gcr_solve_device makes, through the functions it makes them with. The model is spmv_amd_bicgstab_stage;
+ * tests/test_gcr_stages_gpu.py holds each stage against the restatement. Every call synchronises. stage (kind = "jacobi" or "none";
+ * "multidot", "orthogonalise" and "reduce" do not look at it):
+ *   "init"           r = fma(1.0, b, -1.0 * v), "jacobi": zs = dinv r, the partials of r.r; sets a->count
+ *   "multidot"       nothing when scalars->stop; else the partials of Q[i].Q[slot], value i = 0 .. slot-1; sets a->count
+ *   "orthogonalise"  nothing when scalars->stop; else for i ascending below slot q = fma(-beta[i], Q[i], q), z = fma(-beta[i], Z[i], z)
+ *                    from q = Q[slot], z = z_in; Q[slot] = q (not written at slot 0), Z[slot] = z, the partials of q.q (value 0) and
+ *                    r.q (value 1); sets a->count
+ *   "update_xr"      nothing when scalars->stop; else x = fma(alpha, Z[slot], x), r = fma(-alpha, Q[slot], r), "jacobi": zs = dinv r,
+ *                    the partials of r.r; sets a->count
+ *   "reduce"         the sums of a->count partials of one (which 0, 3), slot (which 1) or two (which 2) values, then the scalar step
+ *                    `which` on *scalars (read and written, every field) with a->tol, a->hist and a->hist_cap; which >= 1 does nothing
+ *                    when scalars->stop
+ * Vectors are accessed in 16-byte pairs. Refused before any HIP call, with a sentence on stderr and a non-zero return: an unknown
+ * stage or kind, null arguments, n < 1, a slot outside the stage's range, count < 1, which outside 0..3, hist_cap < 0, a null pointer
+ * the stage needs (scalars: every stage but "init"), a vector that is not 16-byte aligned, partials or hist that are not 8-byte
+ * aligned. Returns 0 otherwise. */
+int spmv_amd_gcr_stage(const char* stage, const char* kind, SpmvAmdGcrStageArgs* a, SpmvAmdGcrScalars* scalars);
+
 /* Kind "chebyshev": how many step launches of the last solve's LOOP did work, i.e. were not stopped by the iteration's verdict (the
  * application behind the initial residual is not counted). Every iteration but the converging one runs `degree` of them:
  * degree * (iterations - 1) for a solve that converged. 0 after a solve of another kind. */
