@@ -174,7 +174,7 @@ LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set
                     "spmv_amd_pcg_last_multigrid_cycles", "spmv_amd_precond_multigrid_level_csr", "spmv_amd_mg_stage",
                     "spmv_amd_pcg_multi_stage", "spmv_amd_mg_multi_stage", "spmv_amd_mg_multi_stage3d",
                     "spmv_amd_mg3d_multi_level_product", "spmv_amd_precond_multigrid_level_spmm",
-                    "spmv_amd_bicgstab_stage", "spmv_amd_gcr_stage"]
+                    "spmv_amd_bicgstab_stage", "spmv_amd_gcr_stage", "spmv_amd_operator_fused_spmv"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
 DECLARED_CXX_SYMBOLS = [
     "SPMV_CSR", "SPMV_STENCIL5_CSR", "SPMV_STENCIL7_CSR", "SPMV_STENCIL_HALO_MGPU", "SPMV_ELLPACK", "SPMV_STENCIL5_ELLPACK",
@@ -318,6 +318,8 @@ def lib():
         L.spmv_amd_mg3d_multi_level_product.restype = C.c_int
         L.spmv_amd_precond_multigrid_level_spmm.argtypes = [C.c_void_p, C.c_int]
         L.spmv_amd_precond_multigrid_level_spmm.restype = C.c_char_p
+        L.spmv_amd_operator_fused_spmv.argtypes = [C.POINTER(SpmvOperator), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.spmv_amd_operator_fused_spmv.restype = C.c_int
     L.spmv_amd_cg_slab_create.restype = C.c_void_p
     L.spmv_amd_cg_slab_create.argtypes = [C.POINTER(MatrixData), C.c_void_p]
     L.spmv_amd_cg_slab_create_stencil5.restype = C.c_void_p
@@ -961,6 +963,18 @@ def mg3d_multi_level_product(kind):
     if not is_lab():
         raise RuntimeError("the level product is chosen in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
     return lib().spmv_amd_mg3d_multi_level_product(kind if kind is None else kind.encode())
+
+
+def fused_spmv(op, d_x, d_y, d_partials, cap, count=True):
+    """spmv_amd_operator_fused_spmv (LAB build only; include/spmv_amd/lab.h): one fused launch of `op` (an Operator, a pointer to a
+    table, or None) on device vectors (objects with .ptr, plain addresses, or None): y = A x and the unreduced partials of x . (A x).
+    Returns (return code, number of partials written); count=False passes a null count."""
+    if not is_lab():
+        raise RuntimeError("spmv_amd_operator_fused_spmv exists in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+    used = C.c_int(-1)
+    at = lambda v: getattr(v, "ptr", v)  # noqa: E731
+    rc = lib().spmv_amd_operator_fused_spmv(getattr(op, "op", op), at(d_x), at(d_y), at(d_partials), int(cap), C.byref(used) if count else None)
+    return rc, used.value
 
 
 def pcg_stage(stage, kind, args, scalars=None):

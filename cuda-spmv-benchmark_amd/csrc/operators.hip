@@ -21,6 +21,9 @@
 #include "device_runtime.hpp"
 #include "multi_rhs.hpp"
 #include "stencil_geometry.hpp"
+#ifdef SPMV_AMD_LAB
+#include "spmv_amd/lab.h"
+#endif
 
 using namespace spmv_amd;
 
@@ -585,7 +588,32 @@ FusedSpmv fused_spmv_of(const SpmvOperator* op) {
     }
     return f;
 }
+}  // namespace spmv_amd
 
+#ifdef SPMV_AMD_LAB
+// (LAB build only; include/spmv_amd/lab.h.) One fused launch of an operator -- the SpMV cg_solve_device puts into its loop -- on the
+// caller's device vectors: y = A x and the launch's partials of x . (A x), unreduced. Every refusal comes before any HIP call.
+extern "C" int spmv_amd_operator_fused_spmv(const SpmvOperator* op, const double* d_x, double* d_y, double* d_partials, int cap, int* count) {
+    auto refuse = [](const char* why) {
+        fprintf(stderr, "[fused-spmv] refused: %s\n", why);
+        return EXIT_FAILURE;
+    };
+    if (op == nullptr || d_x == nullptr || d_y == nullptr || d_partials == nullptr || count == nullptr) return refuse("null arguments");
+    const OwnOperator o = own_operator_of(op);
+    if (o.csr == nullptr && o.ell == nullptr) return refuse("the operator is not one of this library's tables");
+    if (!(o.csr != nullptr ? o.csr->ready : o.ell->ready)) return refuse("the operator is used before init");
+    const FusedSpmv f = fused_spmv_of(op);
+    if (f.partials <= 0 || f.launch == nullptr) return refuse("the operator has no fused form (its loop runs run_device, then a dot pass)");
+    if (cap < f.partials) return refuse("cap is below the number of partials the launch writes");
+    const int used = f.launch(d_x, d_y, d_partials, nullptr, false, nullptr, kDefaultStream);
+    HIP_CHECK(hipStreamSynchronize(kDefaultStream));
+    HIP_CHECK(hipGetLastError());
+    *count = used;
+    return used > 0 ? 0 : EXIT_FAILURE;
+}
+#endif  // SPMV_AMD_LAB
+
+namespace spmv_amd {
 ChebSpmv cheb_spmv_of(const SpmvOperator* op) {
     ChebSpmv c;
     c.op = op;

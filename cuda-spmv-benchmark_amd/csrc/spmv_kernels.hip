@@ -294,10 +294,14 @@ __global__ __launch_bounds__(kBlock) void csr_row_scalar_kernel(SlabCsr m, const
 // (Greathouse & Daga, SC'14), without a preprocessing pass: the row count per block is fixed per
 // matrix from its mean row length.
 // kThreads threads fetch kPerThread entries each in phase 1 (LDS: 16 B per entry).
-// kVectorLong ("csr/adaptive", the "vector" half of CSR-adaptive): inside a row that is longer than the strip, a chunk that
-// lies entirely within that row is not staged at all -- every thread folds the entries it fetched into a private partial,
-// and the partials are summed by a fixed tree when the row ends. 20 coalesced passes of 256 threads instead of 20 x 1024
-// sequential fmas by one thread; the price is the summation order of such rows (a tree, like the sub-wavefront kernels).
+// kVectorLong ("csr/adaptive", the "vector" half of CSR-adaptive): in a block whose span leaves the strip, a chunk that lies
+// entirely within ONE row is not staged at all -- every thread folds the entries it fetched into a private partial, and the
+// partials are summed by a fixed tree and added to the row's running sum when the chunks of that row end (the owner changes or
+// the block ends). Any row that covers a whole chunk takes this fold, not only rows longer than the strip: the block's last
+// chunk may be partial, so 16 rows of lengths [64] * 15 + [65] (a span of 1025) send the ONE last product of the 65-entry row
+// through vacc, the trees and sum += t -- one rounding more than fma(v, x, sum). 20 coalesced passes of 256 threads instead of
+// 20 x 1024 sequential fmas by one thread; the price is the summation order of such rows (a tree, like the sub-wavefront
+// kernels). tests/csr_restatement.py states that order and tests/test_csr_gpu.py holds the kernel to it bit for bit.
 template <int kThreads, int kPerThread, bool kVectorLong = false>
 __global__ __launch_bounds__(kThreads) void csr_stream_kernel(SlabCsr m, const double* __restrict__ x,
                                                               double* __restrict__ y, double alpha,

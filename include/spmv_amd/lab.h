@@ -491,6 +491,15 @@ int spmv_amd_mg3d_multi_level_product(const char* kind);
  * ...); "none" for NULL, another kind, a single-vector hierarchy or a level that does not exist. */
 const char* spmv_amd_precond_multigrid_level_spmm(const SpmvAmdPrecond* m, int level);
 
+/* One fused launch of an operator of this library, as cg_solve_device puts it into its loop (csrc/operators.hip, fused_spmv_of), on
+ * the caller's DEVICE vectors: d_y = A d_x and, in d_partials, the launch's partials of x . (A x), unreduced -- one per logical block
+ * of the CSR stream / adaptive kernels, per 256 rows of the ELLPACK kernels, per tile of the stencil kernels. Synchronises; *count
+ * (host) = the number of partials written. Refused before any HIP call, with a [fused-spmv] sentence on stderr and a non-zero return:
+ * null arguments, a table this library does not own, an operator used before init, an operator with no fused form (csr/row-scalar,
+ * csr/wavefront, a rectangular matrix: their loop runs run_device, then a dot pass) and cap below the number of partials. Returns 0
+ * otherwise. */
+int spmv_amd_operator_fused_spmv(const SpmvOperator* op, const double* d_x, double* d_y, double* d_partials, int cap, int* count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,8 @@ A dot product is two steps. The PARTIALS, written by the kernel that touches the
   rowdirect_partials   stencil5_rowdirect_kernel<true> (csrc/spmv_kernels.hip): 256 columns of one grid row
   rowlds_partials      rowlds_tile (row-lds and its block kernel, kMode 1; kMode 2 with a = b = r0): 128 columns of one grid row
   ell_partials         ell_block_dot (the ELLPACK operators' fused p.Ap): 256 rows
+  (csr_restatement.stream_block_partials: the dot_partials tail of csr_stream_kernel, the general CSR operator's fused p.Ap:
+                       per_block rows in the first lanes of 256; it lives with that kernel's row sums in tests/csr_restatement.py)
 and their SUM (csrc/reduce_device.hpp):
   reduce               reduce_single_kernel / reduce_one_launch_kernel / stencil5_rowlds_edges_reduce_kernel
   reduce_pcg           pcg_reduce_kernel, per value

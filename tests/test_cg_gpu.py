@@ -8,7 +8,9 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, rel_err, hist_err
+import csr_restatement as CR
 import matrices as M
+from bitwise import same_bits
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10  # the north_star's bar on fp64 CG residuals
@@ -797,6 +799,7 @@ def test_long_row_matrices_take_the_wavefront_kernel_and_the_unfused_loop(B, O, 
     got, _ = op.run_timed(x)
     scale = np.maximum(np.abs(want), O.spmv_csr(rp, ci, np.abs(va), np.abs(x)))
     assert np.max(np.abs(got - want) / scale) <= 1e-12
+    assert same_bits(got, CR.wavefront_row_sums(rp, ci, va, x))  # the bits of the kernel's own order (tests/csr_restatement.py)
     b = np.random.default_rng(12).standard_normal(r)
     xs, hist, st = B.cg_solve(op, m, b, np.zeros(r), device=True)
     xo, ho, ro = O.cg(rp, ci, va, -1, b, np.zeros(r), device_form=True)

@@ -1,14 +1,17 @@
 """Parity of the HIP SpMV operators with the CPU oracle, through the C-ABI (get_operator ->
 init / run_timed / run_device / free). Bit-exact wherever the summation order is defined by the
 reference (stencil5-csr, ELLPACK, CSR row-scalar), <= 1e-12 relative for the sub-wavefront CSR
-kernels whose shuffle tree re-orders the sum (cuSPARSE's own order is unpinned)."""
+kernels whose shuffle tree re-orders the sum (cuSPARSE's own order is unpinned) -- and, beside that bound, bit for bit
+against the order those kernels have (tests/csr_restatement.py)."""
 import os
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, rel_err
+import csr_restatement as CR
 import matrices as M
+from bitwise import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -124,6 +127,8 @@ def test_csr_operator(B, O, fresh_host_matrices, variant):
         else:
             scale = np.maximum(np.abs(want), O.spmv_csr(rp, ci, np.abs(va), np.abs(x)))
             assert np.max(np.abs(got - want) / np.maximum(scale, 1e-300)) <= 1e-12
+            # ... and the bits of the kernel's own order (tests/csr_restatement.py), whichever kernel the variant is on this matrix
+            assert same_bits(got, CR.row_sums(rp, ci, va, x, CR.variant_of(rp, op.variant()))), op.variant()
         # integer-valued data: exact under any summation order
         xi = np.ones(c)
         ei = e.copy()
@@ -222,6 +227,7 @@ def test_degenerate_inputs(B, O, fresh_host_matrices):
             got, _ = op.run_timed(x)
             if mode == "cusparse-csr" and len(e) == 300:
                 assert np.max(np.abs(got - want)) <= 1e-12 * np.max(np.abs(want))  # long row: sub-wavefront tree
+                assert same_bits(got, CR.row_sums(rp, ci, va, x, CR.variant_of(rp, op.variant()))), op.variant()
             else:
                 assert np.array_equal(got, want), (mode, r, c)
             op.free()
@@ -298,6 +304,7 @@ def test_csr_rows_without_column_zero_never_touch_x0(B, O, fresh_host_matrices, 
     assert np.all(np.isfinite(want)) and np.all(np.isfinite(got))
     scale = np.maximum(np.abs(want), O.spmv_csr(rp, ci, np.abs(va), np.abs(np.where(np.isfinite(x), x, 0.0))))
     assert np.max(np.abs(got - want) / np.maximum(scale, 1e-300)) <= 1e-12
+    assert same_bits(got, CR.row_sums(rp, ci, va, x, CR.variant_of(rp, op.variant()))), op.variant()  # the restatement reads x where A has an entry
     op.free()
     op.select_variant(None)
     # ELLPACK pads with index -1: same property
@@ -340,4 +347,5 @@ def test_structured_non_stencil_fixtures_through_every_operator(B, O, fresh_host
             assert np.array_equal(got, want), (mode, op.variant())
         else:
             assert np.max(np.abs(got - want) / np.maximum(scale, 1e-300)) <= 1e-12, (mode, op.variant())
+            assert same_bits(got, CR.row_sums(rp, ci, va, x, CR.variant_of(rp, op.variant()))), (mode, op.variant())
         op.free()

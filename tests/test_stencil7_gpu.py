@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import cg_restatement as CG
+import csr_restatement as CR
 import matrices as M
 import reduction_restatement as R
 import stencil7 as S7
@@ -223,6 +224,8 @@ def test_the_other_operators_are_not_fooled_by_the_grid_size(B, O, mode):
         got, _ = op.run_timed(x)
         tree = op.variant() in ("csr/wavefront", "csr/adaptive")  # the variants whose sum is a tree: the existing scaled bound
         assert np.array_equal(got, want) or (tree and np.max(np.abs(got - want)) <= 1e-12 * np.max(np.abs(want))), op.variant()
+        if tree:  # ... and the bits of the kernel's own order
+            assert same_bits(got, CR.row_sums(rp, ci, va, x, CR.variant_of(rp, op.variant()))), op.variant()
         assert "stencil5-direct" not in op.variant() and op.variant() not in ("stencil5/row-lds", "stencil5/row-direct")
     finally:
         op.free()
