@@ -165,6 +165,7 @@ DECLARED_SYMBOLS = [
     "spmv_amd_precond_create_multigrid_multi", "spmv_amd_precond_multigrid_max_rhs", "spmv_amd_precond_apply_device_multi",
     "spmv_amd_precond_create_multigrid3d_multi",
     "spmv_amd_bicgstab_solve_device", "spmv_amd_bicgstab_last_history",
+    "spmv_amd_bicgstab_solve_device_multi", "spmv_amd_bicgstab_last_history_multi", "spmv_amd_bicgstab_multi_workspace_bytes",
     "spmv_amd_gcr_solve_device", "spmv_amd_gcr_last_history", "spmv_amd_gcr_workspace_bytes",
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
@@ -174,7 +175,7 @@ LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set
                     "spmv_amd_pcg_last_multigrid_cycles", "spmv_amd_precond_multigrid_level_csr", "spmv_amd_mg_stage",
                     "spmv_amd_pcg_multi_stage", "spmv_amd_mg_multi_stage", "spmv_amd_mg_multi_stage3d",
                     "spmv_amd_mg3d_multi_level_product", "spmv_amd_precond_multigrid_level_spmm",
-                    "spmv_amd_bicgstab_stage", "spmv_amd_gcr_stage", "spmv_amd_operator_fused_spmv"]
+                    "spmv_amd_bicgstab_stage", "spmv_amd_gcr_stage", "spmv_amd_operator_fused_spmv", "spmv_amd_bicgstab_multi_stage"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
 DECLARED_CXX_SYMBOLS = [
     "SPMV_CSR", "SPMV_STENCIL5_CSR", "SPMV_STENCIL7_CSR", "SPMV_STENCIL_HALO_MGPU", "SPMV_ELLPACK", "SPMV_STENCIL5_ELLPACK",
@@ -1469,6 +1470,71 @@ def bicgstab_stage(stage, kind, args, scalars=None):
     L.spmv_amd_bicgstab_stage.restype = C.c_int
     return L.spmv_amd_bicgstab_stage(stage if stage is None else stage.encode(), kind if kind is None else kind.encode(),
                                      None if args is None else C.byref(args), None if scalars is None else C.byref(scalars))
+
+
+# ---------------------------------------------------------------- batched BiCGSTAB (include/spmv_amd/api.h; csrc/bicgstab_multi.hip)
+class BicgstabMultiColumn(C.Structure):
+    """SpmvAmdBicgstabMultiColumn (include/spmv_amd/lab.h): the per-column state of a batched BiCGSTAB solve."""
+    _fields_ = [("rho", C.c_double), ("sigma", C.c_double), ("alpha", C.c_double), ("omega", C.c_double), ("beta", C.c_double),
+                ("b_norm", C.c_double), ("residual", C.c_double), ("s_norm", C.c_double), ("active", C.c_int), ("done", C.c_int),
+                ("iterations", C.c_int), ("converged", C.c_int), ("breakdown", C.c_int), ("x_step", C.c_int), ("pad", C.c_int * 2)]
+
+
+class BicgstabMultiStageArgs(C.Structure):
+    """SpmvAmdBicgstabMultiStageArgs (include/spmv_amd/lab.h): device pointers and sizes of one spmv_amd_bicgstab_multi_stage call."""
+    _fields_ = [("n", C.c_size_t), ("X", C.c_void_p), ("R", C.c_void_p), ("RH", C.c_void_p), ("P", C.c_void_p), ("PH", C.c_void_p),
+                ("SH", C.c_void_p), ("V", C.c_void_p), ("T", C.c_void_p), ("dinv", C.c_void_p), ("cols", C.c_void_p),
+                ("partials", C.c_void_p), ("count", C.c_longlong), ("which", C.c_int), ("tol", C.c_double), ("hist", C.c_void_p),
+                ("hist_cap", C.c_int)]
+
+
+def _bicgstab_multi_lib():
+    L = _pcg_lib()
+    if not getattr(L, "_bicgstab_multi_sigs", False):
+        L.spmv_amd_bicgstab_solve_device_multi.argtypes = L.spmv_amd_pcg_solve_device_multi.argtypes
+        L.spmv_amd_bicgstab_last_history_multi.argtypes = [C.c_int, C.c_void_p, C.c_int]
+        L.spmv_amd_bicgstab_multi_workspace_bytes.argtypes = []
+        L.spmv_amd_bicgstab_multi_workspace_bytes.restype = C.c_size_t
+        L._bicgstab_multi_sigs = True
+    return L
+
+
+def bicgstab_solve_multi(op, host_matrix, precond, Bk, X0k, tol=1e-6, max_iters=1000, verbose=0, timers=0):
+    """spmv_amd_bicgstab_solve_device_multi: k independent BiCGSTAB solves sharing the SpMM. Bk, X0k: (k, n).
+    Returns X (k, n), a list of k residual histories and a list of k CGStats like pcg_solve_multi (raises RuntimeError on a refusal)."""
+    Bk = np.ascontiguousarray(np.atleast_2d(Bk), dtype=np.float64)
+    X = np.ascontiguousarray(np.atleast_2d(X0k), dtype=np.float64).copy()
+    k = Bk.shape[0]
+    assert X.shape == Bk.shape
+    cfg = CGConfig(max_iters, tol, verbose, timers)
+    stats = (CGStats * k)()
+    L = _bicgstab_multi_lib()
+    rc = L.spmv_amd_bicgstab_solve_device_multi(op.op, host_matrix.ptr, precond.handle, k, Bk.ctypes.data, X.ctypes.data, C.byref(cfg), stats)
+    if rc != 0:
+        raise RuntimeError(f"bicgstab_solve_device_multi -> {rc}")
+    hists = []
+    for j in range(k):
+        h = np.zeros(max_iters + 1, dtype=np.float64)
+        count = L.spmv_amd_bicgstab_last_history_multi(j, h.ctypes.data, len(h))
+        hists.append(h[:count].copy())
+    return X, hists, list(stats)
+
+
+def bicgstab_multi_workspace_bytes():
+    """spmv_amd_bicgstab_multi_workspace_bytes: device bytes the batched BiCGSTAB workspace holds now."""
+    return int(_bicgstab_multi_lib().spmv_amd_bicgstab_multi_workspace_bytes())
+
+
+def bicgstab_multi_stage(stage, kind, k, args):
+    """spmv_amd_bicgstab_multi_stage (LAB build only; include/spmv_amd/lab.h): one stage of the batched BiCGSTAB solver's own kernels
+    on the device data `args` (BicgstabMultiStageArgs) points to; returns its return code (0, or non-zero for a refusal)."""
+    if not is_lab():
+        raise RuntimeError("the batched-BiCGSTAB stages exist in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+    L = lib()
+    L.spmv_amd_bicgstab_multi_stage.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(BicgstabMultiStageArgs)]
+    L.spmv_amd_bicgstab_multi_stage.restype = C.c_int
+    return L.spmv_amd_bicgstab_multi_stage(stage if stage is None else stage.encode(), kind if kind is None else kind.encode(), int(k),
+                                           None if args is None else C.byref(args))
 
 
 # ---------------------------------------------------------------- GCR(m) (include/spmv_amd/api.h; csrc/gcr.hip)

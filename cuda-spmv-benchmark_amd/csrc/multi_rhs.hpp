@@ -1,5 +1,5 @@
 // multi_rhs.hpp -- one matrix, up to 8 right-hand sides: SpMM launchers (spmm_kernels.hip) and the records of the batched solvers
-// (cg_multi.hip: CG; pcg_multi.hip: preconditioned CG; their shared device helpers: multi_rhs_device.hpp; their shared host
+// (cg_multi.hip: CG; pcg_multi.hip: preconditioned CG; bicgstab_multi.hip: BiCGSTAB; their shared device helpers: multi_rhs_device.hpp; their shared host
 // scaffold: multi_solve.hpp).
 // Every launcher enqueues on the given stream and returns; none synchronises.
 //
@@ -115,5 +115,26 @@ void launch_pcg_multi_cheb_step(int k, long long n, const PcgMultiColumn* cols, 
 // holds the workspace lock.
 void release_pcg_multi_workspace_locked();
 size_t pcg_multi_workspace_bytes_locked();
+
+// Per-column state of a batched BiCGSTAB solve (bicgstab_multi.hip; device memory, one entry per column): bicgstab.hip's scalars of
+// one solve, per column, with the batched loop's two flags in the place of `stop`.
+struct BicgMultiColumn {
+    double rho;       // r^.r of the column's current residual
+    double sigma, alpha, omega, beta;
+    double b_norm;    // ||r0||
+    double residual;  // the norm recorded last
+    double s_norm;    // ||s|| of this iteration
+    int active;       // the column takes part in the current iteration (set by the sigma step: !done)
+    int done;         // converged or broken down: the column is frozen from the next iteration on
+    int iterations;   // iterations this column took part in
+    int converged;    // stopping test met (by the half step or by the whole one)
+    int breakdown;    // 0, or which scalar stopped the column: 1 sigma, 2 omega (t.t or t.s), 3 rho'
+    int x_step;       // what the x / r kernel applies to the column in this iteration: 0 nothing, 1 the half step, 2 the whole step
+    int pad[2];
+};
+// The batched BiCGSTAB solver's workspace (bicgstab_multi.hip), released and counted like the other batched solvers'; the caller
+// holds the workspace lock.
+void release_bicgstab_multi_workspace_locked();
+size_t bicgstab_multi_workspace_bytes_locked();
 
 }  // namespace spmv_amd

@@ -1,7 +1,8 @@
 // multi_rhs_device.hpp -- the device helpers the batched solvers share (cg_multi.hip: batched CG; pcg_multi.hip: batched
-// preconditioned CG): a row's k values as 16-byte accesses, the flat row x column walk of a workgroup, the per-column dot
-// partials of a workgroup's 256 rows, and the first stage of the two-stage per-column sum (its geometry: slices_for, multi_rhs.hpp).
-// Everything sits in an unnamed namespace: each of the two translation units gets its own copy under the names it had when
+// preconditioned CG; bicgstab_multi.hip: batched BiCGSTAB): a row's k values as 16-byte accesses, the flat row x column walk of a
+// workgroup, one unit of a stream touched once per pass, the per-column dot partials of a workgroup's 256 rows for one or two values,
+// and the first stage of the two-stage per-column sum (its geometry: slices_for, multi_rhs.hpp).
+// Everything sits in an unnamed namespace: each translation unit gets its own copy under the names it had when
 // cg_multi.hip held them alone, so moving them here changes no kernel's code or symbol (profiles/r25_pcg_multi_isa_identity.txt).
 #pragma once
 
@@ -85,6 +86,52 @@ __device__ __forceinline__ void products_to_rows(const double* prod, double (&d)
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < K; ++q) d[q] = prod[threadIdx.x * K + q];
+}
+
+// One unit (V = 1 or 2 values) of a stream that is read / written once per pass
+template <int V>
+__device__ __forceinline__ void load_unit_once(const double* __restrict__ p, double (&o)[V]) {
+    if constexpr (V == 2) {
+        const d2 t = __builtin_nontemporal_load(reinterpret_cast<const d2*>(p));
+        o[0] = t.x, o[1] = t.y;
+    } else {
+        o[0] = __builtin_nontemporal_load(p);
+    }
+}
+template <int V>
+__device__ __forceinline__ void store_unit_once(double* __restrict__ p, const double (&v)[V]) {
+    if constexpr (V == 2) {
+        d2 t;
+        t.x = v[0], t.y = v[1];
+        __builtin_nontemporal_store(t, reinterpret_cast<d2*>(p));
+    } else {
+        __builtin_nontemporal_store(v[0], p);
+    }
+}
+
+// The partials of one or two values from the units' products: value 0 (in prod already) at partials[j * count + blk], value 1
+// (second[], this thread's units in walk order) at partials[(K + j) * count + blk] through the same LDS array. Every thread of the
+// workgroup calls it.
+template <int K>
+__device__ __forceinline__ void unit_partials(double* prod, bool first, const double (&second)[K], bool with_second,
+                                              double* __restrict__ partials, long long count) {
+    constexpr int V = Flat<K>::V, U = Flat<K>::P;
+    double d[K];
+    if (first) {
+        products_to_rows<K>(prod, d);
+        block_partials<K>(d, partials, count, blockIdx.x);
+    }
+    if (!with_second) return;
+    __syncthreads();  // every thread has read its row of prod, and threads < K the wave sums
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+        const int f = (int)threadIdx.x + kBlock * i;
+        const int t = f / U, col0 = (f - t * U) * V;
+#pragma unroll
+        for (int q = 0; q < V; ++q) prod[t * K + col0 + q] = second[i * V + q];
+    }
+    products_to_rows<K>(prod, d);
+    block_partials<K>(d, partials + (long long)K * count, count, blockIdx.x);
 }
 
 // Stage 1: workgroup (s, j) sums partials[j * count + s * kSlice ...] (each thread its strided share in ascending order, then

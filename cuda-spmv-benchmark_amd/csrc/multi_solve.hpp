@@ -1,8 +1,8 @@
-// multi_solve.hpp -- the host side the two batched solvers share around their loops (cg_multi.hip: CG; pcg_multi.hip: preconditioned
-// CG): the workspace, the argument checks, the way in (upload, interleave) and the way out (de-interleave, download, histories,
+// multi_solve.hpp -- the host side the batched solvers share around their loops (cg_multi.hip: CG; pcg_multi.hip: preconditioned
+// CG; bicgstab_multi.hip: BiCGSTAB): the workspace, the argument checks, the way in (upload, interleave) and the way out (de-interleave, download, histories,
 // statistics, print-out), the per-iteration read of the column records, the choice of a kernel template's instance by k, and the
 // refusals of the LAB build's stage hooks. Host code only: no kernel lives here, so spmm_kernels.hip (the operand entry points) and
-// pcg.hip (its stage hook) include it too. Every function that prints takes the tag it prints under ("CG-MULTI", "PCG-MULTI"): each
+// pcg.hip (its stage hook) include it too. Every function that prints takes the tag it prints under ("CG-MULTI", "PCG-MULTI", "BICGSTAB-MULTI"): each
 // solver keeps its sentences. The loops, their launch order, the kernels and the column records stay each solver's own.
 #pragma once
 
@@ -179,9 +179,10 @@ void load_block_system(BatchedWorkspace<Column>& w, int k, int n, const double* 
 struct ColumnSummary {
     int iterations;
     bool converged;  // stopping test met
-    bool breakdown;  // stopped without it (preconditioned CG only)
+    bool breakdown;  // stopped without it (not batched CG)
     double residual, b_norm;
     bool active;  // took part in the last iteration
+    const char* breakdown_scalar = nullptr;  // what the breakdown line names (null: CG's "pAp or r.z")
 };
 
 // One small blocking read of the k column records: the stopping test of every column.
@@ -236,7 +237,9 @@ void finish_batched_solve(const char* tag, BatchedWorkspace<Column>& w, int k, i
         fill_device_stats(&st, c.iterations, c.converged, c.residual, c.b_norm, cfg, total_ms, T.t_spmv, T.t_blas, T.t_red);
         solution_checksums(X + (size_t)j * n, n, &st.solution_sum, &st.solution_norm);
         if (cfg.verbose >= 1) {
-            if (c.breakdown) printf("[%s %d] Breakdown in iteration %d (pAp or r.z zero or not finite)\n", tag, j, c.iterations);
+            if (c.breakdown)
+                printf("[%s %d] Breakdown in iteration %d (%s zero or not finite)\n", tag, j, c.iterations,
+                       c.breakdown_scalar ? c.breakdown_scalar : "pAp or r.z");
             printf("[%s %d] Converged: %s\n", tag, j, st.converged ? "YES" : "NO");
             printf("[%s %d] Iterations: %d\n", tag, j, st.iterations);
             printf("[%s %d] Final residual: %e\n", tag, j, st.residual_norm);

@@ -59,52 +59,6 @@ constexpr int kPlain = 0, kJac = 1, kCheb = 2;
 
 __device__ __forceinline__ bool usable(double v) { return v != 0.0 && isfinite(v); }
 
-// One unit (V = 1 or 2 values) of a stream that is read / written once per pass
-template <int V>
-__device__ __forceinline__ void load_unit_once(const double* __restrict__ p, double (&o)[V]) {
-    if constexpr (V == 2) {
-        const d2 t = __builtin_nontemporal_load(reinterpret_cast<const d2*>(p));
-        o[0] = t.x, o[1] = t.y;
-    } else {
-        o[0] = __builtin_nontemporal_load(p);
-    }
-}
-template <int V>
-__device__ __forceinline__ void store_unit_once(double* __restrict__ p, const double (&v)[V]) {
-    if constexpr (V == 2) {
-        d2 t;
-        t.x = v[0], t.y = v[1];
-        __builtin_nontemporal_store(t, reinterpret_cast<d2*>(p));
-    } else {
-        __builtin_nontemporal_store(v[0], p);
-    }
-}
-
-// The partials of one or two values from the units' products: value 0 (in prod already) at partials[j * count + blk], value 1
-// (second[], this thread's units in walk order) at partials[(K + j) * count + blk] through the same LDS array. Every thread of the
-// workgroup calls it.
-template <int K>
-__device__ __forceinline__ void unit_partials(double* prod, bool first, const double (&second)[K], bool with_second,
-                                              double* __restrict__ partials, long long count) {
-    constexpr int V = Flat<K>::V, U = Flat<K>::P;
-    double d[K];
-    if (first) {
-        products_to_rows<K>(prod, d);
-        block_partials<K>(d, partials, count, blockIdx.x);
-    }
-    if (!with_second) return;
-    __syncthreads();  // every thread has read its row of prod, and threads < K the wave sums
-#pragma unroll
-    for (int i = 0; i < U; ++i) {
-        const int f = (int)threadIdx.x + kBlock * i;
-        const int t = f / U, col0 = (f - t * U) * V;
-#pragma unroll
-        for (int q = 0; q < V; ++q) prod[t * K + col0 + q] = second[i * V + q];
-    }
-    products_to_rows<K>(prod, d);
-    block_partials<K>(d, partials + (long long)K * count, count, blockIdx.x);
-}
-
 // R = b - A x0 (R holds b on entry), z0 = M^-1 r0 as far as one pass goes, the partials of r.r (value 0) and r.z (value 1).
 // kPlain / kJac: z = r / dinv r, P = z. kCheb: term 0 in registers -- u = dinv r ; d = c0 u ; z = d -- to D and Z; the r.z partials only
 // when term 0 is the whole polynomial (last).

@@ -556,6 +556,38 @@ int spmv_amd_pcg_last_history_multi(int rhs, double* out, int cap);
  * HIP call. */
 size_t spmv_amd_pcg_multi_workspace_bytes(void);
 
+/* ---- BiCGSTAB for several right-hand sides (csrc/bicgstab_multi.hip) ----
+ * nrhs (1..8) INDEPENDENT BiCGSTAB solves on one operator under one preconditioner of kind "none" or "jacobi" (a from-diagonal one
+ * included): per column exactly the algebra of spmv_amd_bicgstab_solve_device -- its steps 1-7, the half step, the three breakdowns
+ * (sigma, omega, rho'), the strict stopping test and what each of them records --, with the arguments, statistics, timers and verbose
+ * semantics of spmv_amd_pcg_solve_device_multi (B, X: host, nrhs vectors of mat->rows values one after the other, X in = x0; stats:
+ * nrhs records; verbose lines tagged [BICGSTAB-MULTI j], the breakdown line naming the scalar as the single solver's does). Not a
+ * block Krylov method: every column has its own rho, alpha, omega, beta, verdict, history and iteration count; only the SpMM (two per
+ * iteration, each reading the coefficients once for all columns) and one dinv[row] per row are shared. The operator must have the
+ * multi-RHS path ("stencil5-csr" in every variant, "stencil7-csr", "cusparse-csr").
+ * A dot product of column j is the sum of the ROUNDED products per row in the shape spmv_amd_pcg_solve_device_multi states (256
+ * consecutive rows per partial, 4096 partials per slice, the slice sums the same way), every one of them on the vector kernels' own
+ * 256-row workgroups. Every value of column j therefore has the same bits whatever nrhs is and whatever slot the column sits in. (The
+ * single-RHS spmv_amd_bicgstab_solve_device sums streaming fma chains: the two agree to rounding, not bit for bit.)
+ * A column that has converged or broken down is frozen: in the iteration in which it stops it receives exactly the update the single
+ * solver applies (nothing, the half step, or the whole step) while the others go on, and from the next iteration on nothing changes a
+ * bit of its X, R, r^0, P, P^, history or count; V, T and S^ are scratch for stopped columns. A NaN or inf in one column never reaches
+ * another column.
+ * Refused before the first HIP call, with a [BICGSTAB-MULTI] sentence on stderr and a non-zero return: nrhs outside 1..8, a NULL
+ * argument, max_iters < 0, an operator without the multi-RHS path or used before init, a system that is not square or not of
+ * mat->rows rows, kinds "chebyshev" and "multigrid" (block hierarchies included: built for symmetric definite matrices), a
+ * preconditioner of another size, of another operator or from before the operator's last init or free. The workspace (block vectors X,
+ * R, r^0, P, V, T; "jacobi": P^ and S^ too; partials for two values, slices, column records, histories) is sized against the device's
+ * free memory first and refused with a sentence if it does not fit; it is kept between calls and released with the other CG
+ * workspaces (an operator's free(), spmv_amd_cg_release_workspace(), spmv_amd_pcg_release_workspace()). */
+int spmv_amd_bicgstab_solve_device_multi(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, int nrhs, const double* B, double* X,
+                                         const CGConfig* config, CGStats* stats);
+/* Residual history of column `rhs` of the last batched BiCGSTAB solve; -1 if there is no such column (the other solvers' histories
+ * are not touched by one). */
+int spmv_amd_bicgstab_last_history_multi(int rhs, double* out, int cap);
+/* Device bytes the batched BiCGSTAB solver's workspace holds now: 0 once it is released or before the first such solve. No HIP call. */
+size_t spmv_amd_bicgstab_multi_workspace_bytes(void);
+
 /* ---- multi-GPU communicator ---- */
 typedef struct SpmvAmdComm SpmvAmdComm;
 

@@ -450,6 +450,71 @@ typedef struct SpmvAmdPcgMultiStageArgs {
  * otherwise. */
 int spmv_amd_pcg_multi_stage(const char* stage, const char* kind, int k, SpmvAmdPcgMultiStageArgs* a);
 
+/* Per-column state of a batched BiCGSTAB solve (csrc/multi_rhs.hpp keeps the same record on the device; api.h states the algebra). */
+typedef struct SpmvAmdBicgstabMultiColumn {
+    double rho;       /* r^.r of the column's current residual */
+    double sigma, alpha, omega, beta;
+    double b_norm;    /* ||r0|| */
+    double residual;  /* the norm recorded last */
+    double s_norm;    /* ||s|| of this iteration */
+    int active;       /* the column takes part in the current iteration (step 1: !done) */
+    int done;         /* converged or broken down: frozen from the next iteration on */
+    int iterations;
+    int converged;    /* stopping test met (by the half step or by the whole one) */
+    int breakdown;    /* 0, or which scalar stopped the column: 1 sigma, 2 omega (t.t or t.s), 3 rho' */
+    int x_step;       /* what update_xr applies to the column in this iteration: 0 nothing, 1 the half step, 2 the whole step */
+    int pad[2];
+} SpmvAmdBicgstabMultiColumn;
+
+/* Device pointers and sizes of one spmv_amd_bicgstab_multi_stage call; a stage reads only the fields listed for it. Block vectors are
+ * row-interleaved, k columns: element (row, column j) at [row * k + j]. Kind "none" keeps p^ in P and s^ in R: PH and SH are not
+ * looked at. */
+typedef struct SpmvAmdBicgstabMultiStageArgs {
+    size_t n;                          /* the vector stages: rows */
+    double* X;                         /* update_xr: in and out */
+    double* R;                         /* init: in (b) and out (r0); update_s: in (r) and out (s); dot_t: in (s); update_xr: in (s) and
+                                          out (r); direction: in */
+    double* RH;                        /* r^0. init: out; dot_rv, update_xr: in */
+    double* P;                         /* init: out; direction: in and out; kind "none": update_xr: in */
+    double* PH;                        /* kind "jacobi": init, direction: out; update_xr: in */
+    double* SH;                        /* kind "jacobi": update_s: out; update_xr: in */
+    double* V;                         /* init: in (A x0); dot_rv, update_s, direction: in */
+    double* T;                         /* dot_t, update_xr: in */
+    const double* dinv;                /* kind "jacobi": init, update_s, direction: n values */
+    SpmvAmdBicgstabMultiColumn* cols;  /* every vector stage but init: in; reduce: in and out -- k records, DEVICE memory */
+    double* partials;                  /* the vector stages but direction: out, value v of column j and workgroup g at
+                                          [(v * k + j) * count + g] (the buffer holds 2 * k * count doubles); reduce: in, the same layout */
+    long long count;                   /* the vector stages: out, the workgroups of the launch = (n + 255) / 256; reduce: in */
+    int which;                         /* reduce: the scalar step, 0 = r0.r0, 1 = sigma = r^.v, 2 = s.s, 3 = t.s / t.t (two values),
+                                          4 = r.r / r^.r (two values) */
+    double tol;                        /* reduce, which = 2 and 4 */
+    double* hist;                      /* reduce: k histories of hist_cap doubles one after the other (may be null when hist_cap is 0) */
+    int hist_cap;
+} SpmvAmdBicgstabMultiStageArgs;
+
+/* The batched BiCGSTAB solver's own kernels (csrc/bicgstab_multi.hip), one stage per call on the caller's device data -- the launches
+ * spmv_amd_bicgstab_solve_device_multi makes, through the functions it makes them with, for k = 1..8 columns. The model is
+ * spmv_amd_pcg_multi_stage; tests/test_bicgstab_multi_stages_gpu.py holds each stage against numpy. Every call synchronises. kind:
+ * "none" or "jacobi" ("reduce", "dot_rv" and "dot_t" do not look at it). A column is RUNNING behind step 1 when cols[j].active and not
+ * cols[j].done. stage:
+ *   "init"       R = fma(1.0, R, -1.0 * V) (R holds b, V holds A x0), RH = R, P = R, PH = dinv P, the partials of r.r; sets a->count
+ *   "dot_rv"     the partials of r^.v for the columns with cols[j].done == 0 (0.0 for the others); nothing at all once every column
+ *                is done; sets a->count
+ *   "update_s"   for the running columns r = fma(-alpha, v, r) (now s), s^ = dinv s, the partials of s.s (0.0 for the others); sets
+ *                a->count
+ *   "dot_t"      for the running columns the partials of t.s (value 0) and t.t (value 1), s read from R; sets a->count
+ *   "update_xr"  per active column by its x_step -- 0: nothing; 1: x = fma(alpha, p^, x); 2: x = fma(omega, s^, fma(alpha, p^, x)),
+ *                r = fma(-omega, t, r) and the partials of r.r (value 0) and r^.r (value 1; 0.0 for every other column); nothing at
+ *                all when no column is active; sets a->count
+ *   "direction"  for the running columns p = fma(beta, fma(-omega, v, p), r), p^ = dinv p
+ *   "reduce"     the sums of a->count partials of the step's one or two values per column, then the scalar step `which` on cols
+ * A stage changes no bit of a column it does not name above, also where that column shares a 16-byte pair with one it does; a unit
+ * (one or two neighbouring columns of a row) without such a column is not read. Refused before any HIP call, with a sentence on
+ * stderr and a non-zero return: an unknown stage or kind, k outside 1..8, null arguments, n < 1, count < 1, which outside 0..4,
+ * hist_cap < 0, a null pointer the stage needs, a block vector that is not 16-byte aligned, dinv, cols, partials or hist that are
+ * not 8-byte aligned. Returns 0 otherwise. */
+int spmv_amd_bicgstab_multi_stage(const char* stage, const char* kind, int k, SpmvAmdBicgstabMultiStageArgs* a);
+
 /* Device pointers of one spmv_amd_mg_multi_stage call; n = the FINE grid, the coarse grid is (n + 1) / 2. Block vectors are
  * row-interleaved, k columns: element (row, column j) at [row * k + j]. */
 typedef struct SpmvAmdMgMultiStageArgs {
