@@ -167,6 +167,7 @@ DECLARED_SYMBOLS = [
     "spmv_amd_bicgstab_solve_device", "spmv_amd_bicgstab_last_history",
     "spmv_amd_bicgstab_solve_device_multi", "spmv_amd_bicgstab_last_history_multi", "spmv_amd_bicgstab_multi_workspace_bytes",
     "spmv_amd_gcr_solve_device", "spmv_amd_gcr_last_history", "spmv_amd_gcr_workspace_bytes",
+    "spmv_amd_gcr_solve_device_multi", "spmv_amd_gcr_last_history_multi", "spmv_amd_gcr_multi_workspace_bytes",
 ]
 # What the LAB build exports on top of that (include/spmv_amd/lab.h); the product library must NOT have these.
 LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set_option", "spmv_amd_cg_slab_tile_classes", "spmv_amd_cg_slab_block_map", "spmv_amd_cg_slab_slow_blocks",
@@ -175,7 +176,8 @@ LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set
                     "spmv_amd_pcg_last_multigrid_cycles", "spmv_amd_precond_multigrid_level_csr", "spmv_amd_mg_stage",
                     "spmv_amd_pcg_multi_stage", "spmv_amd_mg_multi_stage", "spmv_amd_mg_multi_stage3d",
                     "spmv_amd_mg3d_multi_level_product", "spmv_amd_precond_multigrid_level_spmm",
-                    "spmv_amd_bicgstab_stage", "spmv_amd_gcr_stage", "spmv_amd_operator_fused_spmv", "spmv_amd_bicgstab_multi_stage"]
+                    "spmv_amd_bicgstab_stage", "spmv_amd_gcr_stage", "spmv_amd_operator_fused_spmv", "spmv_amd_bicgstab_multi_stage",
+                    "spmv_amd_gcr_multi_stage"]
 # C++-linkage entry points kept under the reference's own names (Itanium-mangled).
 DECLARED_CXX_SYMBOLS = [
     "SPMV_CSR", "SPMV_STENCIL5_CSR", "SPMV_STENCIL7_CSR", "SPMV_STENCIL_HALO_MGPU", "SPMV_ELLPACK", "SPMV_STENCIL5_ELLPACK",
@@ -1600,3 +1602,74 @@ def gcr_stage(stage, kind, args, scalars=None):
     L.spmv_amd_gcr_stage.restype = C.c_int
     return L.spmv_amd_gcr_stage(stage if stage is None else stage.encode(), kind if kind is None else kind.encode(),
                                 None if args is None else C.byref(args), None if scalars is None else C.byref(scalars))
+
+
+# ---------------------------------------------------------------- batched GCR(m) (include/spmv_amd/api.h; csrc/gcr_multi.hip)
+GCR_MULTI_DOT_CHUNK = 4    # SPMV_AMD_GCR_MULTI_DOT_CHUNK (include/spmv_amd/lab.h)
+GCR_MULTI_ORTH_CHUNK = 2   # SPMV_AMD_GCR_MULTI_ORTH_CHUNK
+
+
+class GcrMultiColumn(C.Structure):
+    """SpmvAmdGcrMultiColumn (include/spmv_amd/lab.h): the per-column state of a batched GCR solve."""
+    _fields_ = [("gamma", C.c_double * GCR_MAX_RESTART), ("beta", C.c_double * GCR_MAX_RESTART), ("alpha", C.c_double), ("rho", C.c_double),
+                ("b_norm", C.c_double), ("residual", C.c_double), ("done", C.c_int), ("iterations", C.c_int), ("converged", C.c_int),
+                ("breakdown", C.c_int)]
+
+
+class GcrMultiStageArgs(C.Structure):
+    """SpmvAmdGcrMultiStageArgs (include/spmv_amd/lab.h): device pointers and sizes of one spmv_amd_gcr_multi_stage call."""
+    _fields_ = [("n", C.c_size_t), ("X", C.c_void_p), ("R", C.c_void_p), ("AX", C.c_void_p), ("z_in", C.c_void_p), ("ZS", C.c_void_p),
+                ("Q", C.POINTER(C.c_void_p)), ("Z", C.POINTER(C.c_void_p)), ("slot", C.c_int), ("dinv", C.c_void_p), ("cols", C.c_void_p),
+                ("shadow", C.c_void_p), ("partials", C.c_void_p), ("count", C.c_longlong), ("which", C.c_int), ("tol", C.c_double),
+                ("hist", C.c_void_p), ("hist_cap", C.c_int)]
+
+
+def _gcr_multi_lib():
+    L = _pcg_lib()
+    if not getattr(L, "_gcr_multi_sigs", False):
+        L.spmv_amd_gcr_solve_device_multi.argtypes = [C.POINTER(SpmvOperator), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                      C.POINTER(CGConfig), C.POINTER(CGStats)]
+        L.spmv_amd_gcr_last_history_multi.argtypes = [C.c_int, C.c_void_p, C.c_int]
+        L.spmv_amd_gcr_multi_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_char_p]
+        L.spmv_amd_gcr_multi_workspace_bytes.restype = C.c_size_t
+        L._gcr_multi_sigs = True
+    return L
+
+
+def gcr_solve_multi(op, host_matrix, precond, Bk, X0k, restart=0, tol=1e-6, max_iters=1000, verbose=0, timers=0):
+    """spmv_amd_gcr_solve_device_multi: k independent GCR(restart) solves sharing the SpMM and the preconditioner's block application.
+    Bk, X0k: (k, n). Returns X (k, n), a list of k residual histories and a list of k CGStats like bicgstab_solve_multi (raises
+    RuntimeError on a refusal)."""
+    Bk = np.ascontiguousarray(np.atleast_2d(Bk), dtype=np.float64)
+    X = np.ascontiguousarray(np.atleast_2d(X0k), dtype=np.float64).copy()
+    k = Bk.shape[0]
+    assert X.shape == Bk.shape
+    cfg = CGConfig(max_iters, tol, verbose, timers)
+    stats = (CGStats * max(k, 1))()
+    L = _gcr_multi_lib()
+    rc = L.spmv_amd_gcr_solve_device_multi(op.op, host_matrix.ptr, precond.handle, restart, k, Bk.ctypes.data, X.ctypes.data, C.byref(cfg), stats)
+    if rc != 0:
+        raise RuntimeError(f"gcr_solve_device_multi -> {rc}")
+    hists = []
+    for j in range(k):
+        h = np.zeros(max_iters + 1, dtype=np.float64)
+        count = L.spmv_amd_gcr_last_history_multi(j, h.ctypes.data, len(h))
+        hists.append(h[:count].copy())
+    return X, hists, list(stats)[:k]
+
+
+def gcr_multi_workspace_bytes(rows, nrhs, restart, kind):
+    """spmv_amd_gcr_multi_workspace_bytes: 0 for refused arguments."""
+    return int(_gcr_multi_lib().spmv_amd_gcr_multi_workspace_bytes(rows, nrhs, restart, kind if kind is None else kind.encode()))
+
+
+def gcr_multi_stage(stage, kind, k, args):
+    """spmv_amd_gcr_multi_stage (LAB build only; include/spmv_amd/lab.h): one stage of the batched GCR solver's own kernels on the
+    device data `args` (GcrMultiStageArgs) points to; returns its return code (0, or non-zero for a refusal)."""
+    if not is_lab():
+        raise RuntimeError("the batched-GCR stages exist in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+    L = lib()
+    L.spmv_amd_gcr_multi_stage.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(GcrMultiStageArgs)]
+    L.spmv_amd_gcr_multi_stage.restype = C.c_int
+    return L.spmv_amd_gcr_multi_stage(stage if stage is None else stage.encode(), kind if kind is None else kind.encode(), int(k),
+                                      None if args is None else C.byref(args))

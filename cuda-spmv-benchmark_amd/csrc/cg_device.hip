@@ -26,6 +26,7 @@ void release_cg_workspace_locked() {
     spmv_amd::release_bicgstab_workspace_locked();   // and the BiCGSTAB solver's (bicgstab.hip)
     spmv_amd::release_gcr_workspace_locked();        // and the GCR solver's (gcr.hip)
     spmv_amd::release_bicgstab_multi_workspace_locked();  // and the batched BiCGSTAB solver's (bicgstab_multi.hip)
+    spmv_amd::release_gcr_multi_workspace_locked();       // and the batched GCR solver's (gcr_multi.hip)
     if (g_workspace == nullptr) return;
     spmv_amd_cg_slab_destroy(g_workspace);
     g_workspace = nullptr;

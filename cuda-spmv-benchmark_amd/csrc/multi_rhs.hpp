@@ -137,4 +137,27 @@ struct BicgMultiColumn {
 void release_bicgstab_multi_workspace_locked();
 size_t bicgstab_multi_workspace_bytes_locked();
 
+// Per-column state of a batched GCR(m) solve (gcr_multi.hip; device memory, one entry per column): gcr.hip's scalars of one solve,
+// per column, with the batched loop's two flags in the place of `stop`. Beside the k records the solve keeps k PcgMultiColumn records
+// whose `done` every scalar step writes with this one's: the block applications (mg_cycle_multi, launch_pcg_multi_cheb_step,
+// launch_mg_multi_term0) read that field of those records and no other.
+constexpr int kGcrMultiMaxRestart = 32;
+struct GcrMultiColumn {
+    double gamma[kGcrMultiMaxRestart];  // q.q of the basis slots filled since the last restart
+    double beta[kGcrMultiMaxRestart];   // this iteration's (q.Q_i) / gamma_i, i < slot
+    double alpha, rho;                  // this iteration's step length and r.q
+    double b_norm;                      // ||r0||
+    double residual;                    // the norm recorded last
+    int done;        // converged or broken down: the column is frozen from then on -- no launch changes a bit of this record either
+    int iterations;  // iterations this column took part in
+    int converged;   // stopping test met
+    int breakdown;   // 0, or which scalar stopped the column: 1 gamma = q.q, 2 rho = r.q
+};
+// term 0 of an application on k interleaved columns (multigrid_multi.hip's mg_multi_term0_kernel): d = c0 * (dinv * r) ; z = d for
+// every column once one has done == 0 (cols null: all are running). D may be null: the Jacobi product, c0 = 1.0.
+void launch_mg_multi_term0(int k, long long rows, const PcgMultiColumn* cols, const double* R, const double* dinv, double c0, double* D,
+                           double* Z);
+// The batched GCR solver's workspace (gcr_multi.hip), released like the other batched solvers'; the caller holds the workspace lock.
+void release_gcr_multi_workspace_locked();
+
 }  // namespace spmv_amd

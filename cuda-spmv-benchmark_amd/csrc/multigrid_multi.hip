@@ -248,14 +248,16 @@ void spmv_amd::launch_prolong_correct_multi(int k, int n, const PcgMultiColumn* 
     });
 }
 
-namespace {
-
-void launch_mg_multi_term0(int k, long long rows, const PcgMultiColumn* cols, const double* R, const double* dinv, double c0, double* D, double* Z) {
+// multi_rhs.hpp: the batched GCR solver (gcr_multi.hip) launches term 0 of its applications with it too
+void spmv_amd::launch_mg_multi_term0(int k, long long rows, const PcgMultiColumn* cols, const double* R, const double* dinv, double c0, double* D,
+                                     double* Z) {
     dispatch_k(k, [&](auto K) {
         hipLaunchKernelGGL((mg_multi_term0_kernel<decltype(K)::value>), dim3(flat_grid(rows)), dim3(kFlat), 0, kBatchStream, rows, cols, R, dinv, c0,
                            D, Z);
     });
 }
+
+namespace {
 
 bool fail(const char* what) { return batched_fail(kTag, what); }
 

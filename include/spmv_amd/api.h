@@ -588,6 +588,43 @@ int spmv_amd_bicgstab_last_history_multi(int rhs, double* out, int cap);
 /* Device bytes the batched BiCGSTAB solver's workspace holds now: 0 once it is released or before the first such solve. No HIP call. */
 size_t spmv_amd_bicgstab_multi_workspace_bytes(void);
 
+/* ---- GCR(m) for several right-hand sides (csrc/gcr_multi.hip) ----
+ * nrhs (1..8) INDEPENDENT restarted GCR solves on one operator under one preconditioner of ANY kind -- "none", "jacobi" (a
+ * from-diagonal one included), "chebyshev", and "multigrid" on a hierarchy with block vectors (spmv_amd_precond_create_multigrid_multi,
+ * ..._multigrid3d_multi) of at least nrhs columns: per column exactly the algebra of spmv_amd_gcr_solve_device -- its steps 1-7,
+ * classical Gram-Schmidt from the q of the product, i ascending in step 4, the breakdown rule (gamma or rho zero or not finite: x
+ * untouched, the iteration counted, the unchanged residual recorded), the strict stopping test and what each of them records --, with
+ * the arguments, statistics, timers and verbose semantics of spmv_amd_pcg_solve_device_multi (B, X: host, nrhs vectors of mat->rows
+ * values one after the other, X in = x0; stats: nrhs records; verbose lines tagged [GCR-MULTI j], the breakdown line naming the scalar
+ * as the single solver's does). restart: 1..32, or 0 for the default 16. Not a block Krylov method: every column has its own basis,
+ * gammas, betas, alpha, verdict, history and iteration count; the running columns are in the same iteration and so share the slot
+ * j = iteration mod restart. Only the SpMM, one dinv[row] per row and the preconditioner's block application are shared. The
+ * operator must have the multi-RHS path ("stencil5-csr" in every variant, "stencil7-csr", "cusparse-csr").
+ * A dot product of column j is the sum of the ROUNDED products per row in the shape spmv_amd_pcg_solve_device_multi states (256
+ * consecutive rows per partial, 4096 partials per slice, the slice sums the same way). Every value of column j therefore has the same
+ * bits whatever nrhs is and whatever slot the column sits in. (The single-RHS spmv_amd_gcr_solve_device sums streaming fma chains:
+ * the two agree to rounding, not bit for bit.)
+ * A column that has converged or broken down is frozen: from the next iteration on nothing changes a bit of its X, R, history, count
+ * or record; its basis slots and the application's vectors are scratch. A NaN or inf in one column never reaches another column.
+ * Refused before the first HIP call, with a [GCR-MULTI] sentence on stderr and a non-zero return: nrhs outside 1..8, restart outside
+ * 0..32, a NULL argument, max_iters < 0, an operator without the multi-RHS path or used before init, a system that is not square or
+ * not of mat->rows rows, a "multigrid" handle whose hierarchy keeps single vectors or fewer than nrhs columns, a preconditioner of
+ * another size, of another operator or from before the operator's last init or free. The workspace (block vectors X, R, the
+ * transfer vector, "jacobi": dinv r, "chebyshev" and "multigrid": D and Z; 2 x restart basis block vectors, allocated slot by slot;
+ * partials for 32 values, slices, column records, histories) is sized against the device's free memory first and refused with a
+ * sentence that names the largest restart that fits; it is kept between calls and released with the other CG workspaces (an
+ * operator's free(), spmv_amd_cg_release_workspace(), spmv_amd_pcg_release_workspace()). */
+int spmv_amd_gcr_solve_device_multi(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, int restart, int nrhs, const double* B,
+                                    double* X, const CGConfig* config, CGStats* stats);
+/* Residual history of column `column` of the last batched GCR solve; -1 if there is no such column (the other solvers' histories are
+ * not touched by one). */
+int spmv_amd_gcr_last_history_multi(int column, double* out, int cap);
+/* The bytes of the block vectors and partials a batched GCR solve of nrhs systems of `rows` rows keeps at this restart (0: the
+ * default) under this kind ("none", "jacobi", "chebyshev", "multigrid"): (4 + 2 x restart) block vectors, two more for "chebyshev" and
+ * "multigrid", and 32 x nrhs partial rows. One unit of restart costs exactly 16 x rows x nrhs bytes. 0 for refused arguments. No HIP
+ * call. */
+size_t spmv_amd_gcr_multi_workspace_bytes(int rows, int nrhs, int restart, const char* kind);
+
 /* ---- multi-GPU communicator ---- */
 typedef struct SpmvAmdComm SpmvAmdComm;
 

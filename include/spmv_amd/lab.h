@@ -515,6 +515,66 @@ typedef struct SpmvAmdBicgstabMultiStageArgs {
  * not 8-byte aligned. Returns 0 otherwise. */
 int spmv_amd_bicgstab_multi_stage(const char* stage, const char* kind, int k, SpmvAmdBicgstabMultiStageArgs* a);
 
+/* Per-column state of a batched GCR(m) solve (csrc/multi_rhs.hpp keeps the same record on the device; api.h states the algebra). */
+#define SPMV_AMD_GCR_MULTI_DOT_CHUNK 4   /* basis slots per chunk of the batched multidot kernel */
+#define SPMV_AMD_GCR_MULTI_ORTH_CHUNK 2  /* basis slots per chunk of the batched orthogonalise kernel */
+typedef struct SpmvAmdGcrMultiColumn {
+    double gamma[SPMV_AMD_GCR_MAX_RESTART]; /* q.q of the basis slots filled since the last restart */
+    double beta[SPMV_AMD_GCR_MAX_RESTART];  /* this iteration's (q.Q_i) / gamma_i, i < slot */
+    double alpha, rho;
+    double b_norm;    /* ||r0|| */
+    double residual;  /* the norm recorded last */
+    int done;         /* converged or broken down: frozen from then on, this record included */
+    int iterations;
+    int converged;
+    int breakdown;    /* 0, or which scalar stopped the column: 1 gamma = q.q, 2 rho = r.q */
+} SpmvAmdGcrMultiColumn;
+
+/* Device pointers and sizes of one spmv_amd_gcr_multi_stage call; a stage reads only the fields listed for it. Block vectors are
+ * row-interleaved, k columns: element (row, column j) at [row * k + j]. Q and Z are HOST arrays of SPMV_AMD_GCR_MAX_RESTART device
+ * pointers, one block vector per basis slot; slots above `slot` are not looked at. */
+typedef struct SpmvAmdGcrMultiStageArgs {
+    size_t n;                     /* the vector stages: rows */
+    double* X;                    /* update_xr: in and out */
+    double* R;                    /* init: in (b) and out (r0); orthogonalise: in; update_xr: in and out */
+    const double* AX;             /* init: in, A x0 */
+    const double* z_in;           /* orthogonalise: in, where the application left z; may BE R (kind "none") */
+    double* ZS;                   /* kind "jacobi": init, update_xr: out, dinv r */
+    double** Q;                   /* multidot: Q[0 .. slot] in; orthogonalise: Q[0 .. slot - 1] in, Q[slot] in and out; update_xr: Q[slot] in */
+    double** Z;                   /* orthogonalise: Z[0 .. slot - 1] in, Z[slot] out; update_xr: Z[slot] in */
+    int slot;                     /* j: multidot 1 .. 31, orthogonalise and update_xr 0 .. 31; reduce: which = 1 and 2 */
+    const double* dinv;           /* kind "jacobi": init, update_xr: n values */
+    SpmvAmdGcrMultiColumn* cols;  /* every vector stage but init: in; reduce: in and out -- k records, DEVICE memory */
+    SpmvAmdPcgMultiColumn* shadow; /* reduce: out, `done` of each of the k records follows the column's -- DEVICE memory */
+    double* partials;             /* the vector stages: out, value v of column j and workgroup g at [(v * k + j) * count + g] (multidot:
+                                     `slot` values; orthogonalise: two; else one); reduce: in, the same layout */
+    long long count;              /* the vector stages: out, the workgroups of the launch = (n + 255) / 256; reduce: in */
+    int which;                    /* reduce: the scalar step, 0 = r0.r0, 1 = the betas of `slot`, 2 = gamma and rho, 3 = r.r */
+    double tol;                   /* reduce, which = 3 */
+    double* hist;                 /* reduce: k histories of hist_cap doubles one after the other (may be null when hist_cap is 0) */
+    int hist_cap;
+} SpmvAmdGcrMultiStageArgs;
+
+/* The batched GCR solver's own kernels (csrc/gcr_multi.hip), one stage per call on the caller's device data -- the launches
+ * spmv_amd_gcr_solve_device_multi makes, through the functions it makes them with, for k = 1..8 columns. The models are
+ * spmv_amd_gcr_stage and spmv_amd_bicgstab_multi_stage; tests/test_gcr_multi_stages_gpu.py holds each stage against numpy. Every call
+ * synchronises. kind: "none" or "jacobi" (init and update_xr; the others do not look at it). A column is RUNNING when cols[j].done
+ * is 0. stage:
+ *   "init"           R = fma(1.0, R, -1.0 * AX), "jacobi": ZS = dinv R, the partials of r.r; sets a->count
+ *   "multidot"       for the running columns the partials of Q[i].Q[slot], i < slot, as value i (0.0 for the others); sets a->count
+ *   "orthogonalise"  for the running columns, i ascending below slot: Q[slot] = fma(-beta_i, Q[i], Q[slot]) in place and z =
+ *                    fma(-beta_i, Z[i], z) from z_in into Z[slot] (slot 0: z only moves), the partials of q.q (value 0) and r.q
+ *                    (value 1); sets a->count
+ *   "update_xr"      for the running columns x = fma(alpha, Z[slot], x), r = fma(-alpha, Q[slot], r), "jacobi": ZS = dinv r, the
+ *                    partials of r.r; sets a->count
+ *   "reduce"         the sums of a->count partials of the step's values per column, then the scalar step `which` on cols and shadow
+ * A vector stage but init does nothing at all once every column is done, changes no bit of a column that is done, also where it shares
+ * a 16-byte pair with a running one, and does not read a unit (one or two neighbouring columns of a row) without a running column.
+ * Refused before any HIP call, with a sentence on stderr and a non-zero return: an unknown stage or kind, k outside 1..8, null
+ * arguments, n < 1, count < 1, which outside 0..3, a slot outside the stage's range, hist_cap < 0, a null pointer the stage needs, a
+ * block vector that is not 16-byte aligned, dinv, cols, shadow, partials or hist that are not 8-byte aligned. Returns 0 otherwise. */
+int spmv_amd_gcr_multi_stage(const char* stage, const char* kind, int k, SpmvAmdGcrMultiStageArgs* a);
+
 /* Device pointers of one spmv_amd_mg_multi_stage call; n = the FINE grid, the coarse grid is (n + 1) / 2. Block vectors are
  * row-interleaved, k columns: element (row, column j) at [row * k + j]. */
 typedef struct SpmvAmdMgMultiStageArgs {
