@@ -1,13 +1,14 @@
 // cg_solver -- counterpart of reference src/main/cg_solver.cu: b = 1, x0 = 0, 3 warm-up solves,
 // then 10 timed solves from x0 = 0 each.
 //   cg_solver <matrix.mtx | --stencil=N> [--mode=<m1,..>] [--host|--device] [--tol=1e-6]
-//             [--maxiter=1000] [--timers] [--json=<file>] [--csv=<file>] [--precond=none|jacobi|chebyshev[:K]|multigrid[:NU]]
+//             [--maxiter=1000] [--timers] [--json=<file>] [--csv=<file>] [--precond=none|jacobi|chebyshev[:K]|multigrid[:NU]|amg[:NU]]
 //             [--solver=cg|bicgstab|gcr[:M]]
 // --precond runs the preconditioned solver (spmv_amd_pcg_solve_device, device only); its JSON / CSV carry the mode string
 // <operator>+<kind>. Without it the binary takes cg_solve_device / cg_solve as before. chebyshev = the polynomial preconditioner
 // of degree 4, chebyshev:K of degree K (0..32), both on the automatic interval; the mode string is <operator>+chebyshev<K>.
 // multigrid = the aggregation multigrid V(1, 1) cycle (stencil5-csr, and stencil7-csr through the 3-D creator), multigrid:NU the V(NU, NU) cycle (0..8); the mode string is
-// <operator>+multigrid<NU>.
+// <operator>+multigrid<NU>. amg[:NU] = the aggregation AMG V(NU, NU) cycle (default 1, strength 0.08) made from the matrix itself, on
+// --mode=cusparse-csr only: any matrix the general CSR operator holds; the mode string is cusparse-csr+amg<NU>.
 // --solver=bicgstab runs spmv_amd_bicgstab_solve_device (nonsymmetric matrices; device only) with --precond=none (the default) or
 // jacobi; the mode string is <operator>+bicgstab or <operator>+jacobi+bicgstab. --solver=cg (the default) is everything above.
 // --solver=gcr[:M] runs spmv_amd_gcr_solve_device (nonsymmetric matrices; device only), restarted every M = 1..32 iterations (gcr: the
@@ -115,6 +116,7 @@ int main(int argc, char** argv) {
     }
     int cheb_degree = -1;  // >= 0: --precond=chebyshev[:K]
     int mg_degree = -1;    // >= 0: --precond=multigrid[:NU]
+    int amg_degree = -1;   // >= 0: --precond=amg[:NU]
     if (precond && !strncmp(precond, "chebyshev", 9) && (precond[9] == '\0' || precond[9] == ':')) {
         char* end = nullptr;
         const long k = precond[9] == ':' ? strtol(precond + 10, &end, 10) : 4;
@@ -131,6 +133,14 @@ int main(int argc, char** argv) {
             return 1;
         }
         mg_degree = (int)k;
+    } else if (precond && !strncmp(precond, "amg", 3) && (precond[3] == '\0' || precond[3] == ':')) {
+        char* end = nullptr;
+        const long k = precond[3] == ':' ? strtol(precond + 4, &end, 10) : 1;
+        if (precond[3] == ':' && (end == precond + 4 || *end != '\0' || k < 0 || k > 8)) {
+            fprintf(stderr, "Error: --precond=amg:NU takes a smoother degree NU of 0..8, not '%s'\n", precond + 4);
+            return 1;
+        }
+        amg_degree = (int)k;
     } else if (precond && strcmp(precond, "none") != 0 && strcmp(precond, "jacobi") != 0) {
         fprintf(stderr, "Error: unknown preconditioner '%s' (none, jacobi)\n", precond);
         return 1;
@@ -148,6 +158,10 @@ int main(int argc, char** argv) {
         }
         if (device && !op->run_device) {
             fprintf(stderr, "Error: mode '%s' has no device-native interface (use --host)\n", m.c_str());
+            return 1;
+        }
+        if (amg_degree >= 0 && m != "cusparse-csr") {
+            fprintf(stderr, "Error: --precond=amg runs on --mode=cusparse-csr only, not on '%s' (the stencil operators take --precond=multigrid)\n", m.c_str());
             return 1;
         }
     }
@@ -178,7 +192,8 @@ int main(int argc, char** argv) {
         if (precond) {
             int bad_row = -1;
             const bool is3d = op->name != nullptr && !strcmp(op->name, "stencil7-csr");
-            SpmvAmdPrecond* pm = mg_degree >= 0 && is3d ? spmv_amd_precond_create_multigrid3d(op, mg_degree, 0, &bad_row)
+            SpmvAmdPrecond* pm = amg_degree >= 0        ? spmv_amd_precond_create_amg(op, amg_degree, 0, 0.08, &bad_row)
+                                 : mg_degree >= 0 && is3d ? spmv_amd_precond_create_multigrid3d(op, mg_degree, 0, &bad_row)
                                  : mg_degree >= 0     ? spmv_amd_precond_create_multigrid(op, mg_degree, 0, &bad_row)
                                  : cheb_degree >= 0 ? spmv_amd_precond_create_chebyshev(op, cheb_degree, 0.0, 0.0, &bad_row)
                                                     : spmv_amd_precond_create(op, precond, &bad_row);
@@ -187,7 +202,8 @@ int main(int argc, char** argv) {
                 op->free();
                 continue;
             }
-            const std::string kind = mg_degree >= 0     ? "multigrid" + std::to_string(mg_degree)
+            const std::string kind = amg_degree >= 0    ? "amg" + std::to_string(amg_degree)
+                                     : mg_degree >= 0   ? "multigrid" + std::to_string(mg_degree)
                                      : cheb_degree >= 0 ? "chebyshev" + std::to_string(cheb_degree)
                                                         : std::string(precond);
             const std::string name = gcr > 0 ? "gcr" + std::to_string(gcr) : std::string("bicgstab");

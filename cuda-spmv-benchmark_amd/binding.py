@@ -93,6 +93,13 @@ class MgStageArgs(C.Structure):
                 ("r", C.c_void_p), ("coarse", C.c_void_p), ("out_row_ptr", C.c_void_p), ("out_col_idx", C.c_void_p), ("out_values", C.c_void_p)]
 
 
+class AmgStageArgs(C.Structure):
+    """SpmvAmdAmgStageArgs (include/spmv_amd/lab.h): device pointers and sizes of one spmv_amd_amg_stage call."""
+    _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("coarse_rows", C.c_int), ("row_ptr", C.c_void_p), ("col_idx", C.c_void_p),
+                ("values", C.c_void_p), ("agg_ptr", C.c_void_p), ("members", C.c_void_p), ("agg", C.c_void_p), ("z", C.c_void_p),
+                ("r", C.c_void_p), ("coarse", C.c_void_p)]
+
+
 class MgMultiStageArgs(C.Structure):
     """SpmvAmdMgMultiStageArgs (include/spmv_amd/lab.h): device pointers of one spmv_amd_mg_multi_stage call; n = the fine grid."""
     _fields_ = [("n", C.c_int), ("row_ptr", C.c_void_p), ("col_idx", C.c_void_p), ("values", C.c_void_p), ("z", C.c_void_p),
@@ -164,6 +171,7 @@ DECLARED_SYMBOLS = [
     "spmv_amd_pcg_solve_device_multi", "spmv_amd_pcg_last_history_multi", "spmv_amd_pcg_multi_workspace_bytes",
     "spmv_amd_precond_create_multigrid_multi", "spmv_amd_precond_multigrid_max_rhs", "spmv_amd_precond_apply_device_multi",
     "spmv_amd_precond_create_multigrid3d_multi",
+    "spmv_amd_precond_create_amg", "spmv_amd_precond_amg_info",
     "spmv_amd_bicgstab_solve_device", "spmv_amd_bicgstab_last_history",
     "spmv_amd_bicgstab_solve_device_multi", "spmv_amd_bicgstab_last_history_multi", "spmv_amd_bicgstab_multi_workspace_bytes",
     "spmv_amd_gcr_solve_device", "spmv_amd_gcr_last_history", "spmv_amd_gcr_workspace_bytes",
@@ -174,6 +182,7 @@ LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set
                     "spmv_amd_cg_slab_direction_spmv", "spmv_amd_cg_slab_spmv_dot", "spmv_amd_cg_slab_initial_stage", "spmv_amd_cg_slab_first_stage", "spmv_amd_cg_slab_stored_b", "spmv_amd_cg_slab_update_r_stage", "spmv_amd_cg_slab_ap_form", "spmv_amd_cg_slab_update_r_from_stage", "spmv_amd_cg_slab_first_recompute_form", "spmv_amd_pcg_stage",
                     "spmv_amd_pcg_last_step_launches", "spmv_amd_cg_multi_stage",
                     "spmv_amd_pcg_last_multigrid_cycles", "spmv_amd_precond_multigrid_level_csr", "spmv_amd_mg_stage",
+                    "spmv_amd_amg_stage", "spmv_amd_precond_amg_level_aggregates",
                     "spmv_amd_pcg_multi_stage", "spmv_amd_mg_multi_stage", "spmv_amd_mg_multi_stage3d",
                     "spmv_amd_mg3d_multi_level_product", "spmv_amd_precond_multigrid_level_spmm",
                     "spmv_amd_bicgstab_stage", "spmv_amd_gcr_stage", "spmv_amd_operator_fused_spmv", "spmv_amd_bicgstab_multi_stage",
@@ -313,6 +322,10 @@ def lib():
         L.spmv_amd_precond_multigrid_level_csr.restype = C.c_int
         L.spmv_amd_mg_stage.argtypes = [C.c_char_p, C.POINTER(MgStageArgs)]
         L.spmv_amd_mg_stage.restype = C.c_int
+        L.spmv_amd_amg_stage.argtypes = [C.c_char_p, C.POINTER(AmgStageArgs)]
+        L.spmv_amd_amg_stage.restype = C.c_int
+        L.spmv_amd_precond_amg_level_aggregates.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.spmv_amd_precond_amg_level_aggregates.restype = C.c_int
         L.spmv_amd_pcg_multi_stage.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(PcgMultiStageArgs)]
         L.spmv_amd_pcg_multi_stage.restype = C.c_int
         L.spmv_amd_mg_multi_stage3d.argtypes = [C.c_char_p, C.c_int, C.POINTER(MgMultiStageArgs)]
@@ -728,6 +741,10 @@ def _pcg_lib():
         L.spmv_amd_precond_multigrid_max_rhs.argtypes = [C.c_void_p]
         L.spmv_amd_precond_multigrid_max_rhs.restype = C.c_int
         L.spmv_amd_precond_apply_device_multi.argtypes = [C.POINTER(SpmvOperator), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.spmv_amd_precond_create_amg.argtypes = [C.POINTER(SpmvOperator), C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int)]
+        L.spmv_amd_precond_create_amg.restype = C.c_void_p
+        L.spmv_amd_precond_amg_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int]
         L._pcg_sigs = True
     return L
 
@@ -818,6 +835,48 @@ class Precond:
             err.bad_row = bad.value
             raise err
         return cls(_handle=h, _n=op.rows)
+
+    @classmethod
+    def amg(cls, op, smoother_degree=1, max_levels=0, strength=0.08):
+        """spmv_amd_precond_create_amg (cusparse-csr only): aggregation AMG from the matrix; max_levels 0 = automatic."""
+        bad = C.c_int(-2)
+        h = _pcg_lib().spmv_amd_precond_create_amg(op.op, smoother_degree, max_levels, strength, C.byref(bad))
+        if not h:
+            err = ValueError(f"precond_create_amg({op.name}, {smoother_degree}, {max_levels}, {strength}) refused, bad_row = {bad.value}")
+            err.bad_row = bad.value
+            raise err
+        return cls(_handle=h, _n=op.rows)
+
+    def amg_info(self):
+        """A dict of an AMG handle -- smoother_degree, strength, setup_ms and per level rows, nnz, max_aggregate, lambda_max --; None
+        for any other handle."""
+        levels, degree, theta, ms = C.c_int(0), C.c_int(-1), C.c_double(0.0), C.c_double(0.0)
+        rows, agg = np.zeros(32, dtype=np.int32), np.zeros(32, dtype=np.int32)
+        nnz, lmax = np.zeros(32, dtype=np.int64), np.zeros(32, dtype=np.float64)
+        count = _pcg_lib().spmv_amd_precond_amg_info(self.handle, C.byref(levels), C.byref(degree), C.byref(theta), rows.ctypes.data,
+                                                     nnz.ctypes.data, agg.ctypes.data, lmax.ctypes.data, C.byref(ms), 32)
+        if count == 0:
+            return None
+        return {"smoother_degree": degree.value, "strength": theta.value, "setup_ms": ms.value, "rows": [int(v) for v in rows[:count]],
+                "nnz": [int(v) for v in nnz[:count]], "max_aggregate": [int(v) for v in agg[:count]], "lambda_max": lmax[:count].copy()}
+
+    def amg_level(self, level):
+        """row_ptr, col_idx, values, dinv and the aggregate map (None on the coarsest level) of one level of an AMG handle (LAB build
+        only; include/spmv_amd/lab.h)."""
+        if not is_lab():
+            raise RuntimeError("the level matrices are read through the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+        info = self.amg_info()
+        rows, nnz = info["rows"][level], info["nnz"][level]
+        rp, ci = np.zeros(rows + 1, dtype=np.int32), np.zeros(nnz, dtype=np.int32)
+        va, dinv = np.zeros(nnz), np.zeros(rows)
+        if lib().spmv_amd_precond_multigrid_level_csr(self.handle, level, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, dinv.ctypes.data) != 0:
+            raise RuntimeError("precond_multigrid_level_csr refused")
+        agg = None
+        if level + 1 < len(info["rows"]):
+            agg = np.zeros(rows, dtype=np.int32)
+            if lib().spmv_amd_precond_amg_level_aggregates(self.handle, level, agg.ctypes.data) != 0:
+                raise RuntimeError("precond_amg_level_aggregates refused")
+        return rp, ci, va, dinv, agg
 
     def multigrid_level_spmm(self, level):
         """The name of one level's SpMM plan in a hierarchy with block vectors (LAB build only; include/spmv_amd/lab.h)."""
@@ -941,6 +1000,14 @@ def mg_stage(stage, args):
     if not is_lab():
         raise RuntimeError("the multigrid stages exist in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
     return lib().spmv_amd_mg_stage(stage if stage is None else stage.encode(), args)
+
+
+def amg_stage(stage, args):
+    """spmv_amd_amg_stage (LAB build only; include/spmv_amd/lab.h): one of the two launches an AMG level adds to the cycle, on the
+    caller's device data `args` (AmgStageArgs) points to; returns its return code (0, or non-zero for a refusal)."""
+    if not is_lab():
+        raise RuntimeError("the AMG stages exist in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+    return lib().spmv_amd_amg_stage(stage if stage is None else stage.encode(), None if args is None else C.byref(args))
 
 
 def mg_multi_stage(stage, k, args):

@@ -171,6 +171,8 @@ struct ChebSpmv {
     const SlabCsr* view = nullptr;  // with plan: the stencil forms
     const Stencil5Plan* plan = nullptr;
     const Stencil7Plan* plan7 = nullptr;  // with view: a 3-D multigrid level (never fused: partials stays 0)
+    bool csr = false;                     // with view: a general CSR level of an AMG hierarchy, launch_csr_spmv in csr_variant
+    CsrVariant csr_variant = CsrVariant::Auto;
     const SpmvOperator* op = nullptr;  // without them: run_device
     int partials = 0;                  // slots a fused last step writes; 0: the step is not fused
 };

@@ -275,14 +275,16 @@ struct CycleOps {
         const MgLevel& L = h->levels[(size_t)l];
         double* const rc = h->levels[(size_t)l + 1].r;
         stage_run(T, &StageTimers::t_spmv, [&] {
-            if (L.dim == 3) launch_residual_restrict3d(L.view, L.n, run[l].z, run[l].r, rc);
+            if (L.dim == 0) launch_amg_residual_restrict(L.view, L.coarse_rows, L.agg_ptr, L.members, run[l].z, run[l].r, rc);
+            else if (L.dim == 3) launch_residual_restrict3d(L.view, L.n, run[l].z, run[l].r, rc);
             else launch_residual_restrict(L.view, run[l].z, run[l].r, rc);
         });
     }
     void prolong(int l) {
         const MgLevel& L = h->levels[(size_t)l];
         stage_run(T, &StageTimers::t_blas, [&] {
-            if (L.dim == 3) launch_prolong_correct3d(L.n, run[l + 1].z, run[l].z);
+            if (L.dim == 0) launch_amg_prolong_correct((size_t)L.rows, L.agg, run[l + 1].z, run[l].z);
+            else if (L.dim == 3) launch_prolong_correct3d(L.n, run[l + 1].z, run[l].z);
             else launch_prolong_correct(L.n, run[l + 1].z, run[l].z);
         });
     }

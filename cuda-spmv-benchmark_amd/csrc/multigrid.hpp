@@ -57,8 +57,16 @@ void launch_prolong_correct3d_multi(int k, int n, const PcgMultiColumn* cols, co
 int mg_multi_stage(int dim, const char* stage, int k, SpmvAmdMgMultiStageArgs* a);
 #endif
 
+// The two launches of an AMG level (amg.hip): arbitrary aggregates given as member lists (agg_ptr: coarse_rows + 1,
+// members: the fine rows of each aggregate in ascending order) and as the map agg (one aggregate per fine row).
+// r_c[I] = ((t_m0 + t_m1) + ...) over I's members, t_i = fma(-1.0, s_i, r_i), s_i row i's sequential fma chain; one launch, no scratch
+void launch_amg_residual_restrict(const SlabCsr& m, int coarse_rows, const int* agg_ptr, const int* members, const double* z, const double* r,
+                                  double* rc);
+// z = fma(2.0, e_c[agg[i]], z), z in place (16-byte aligned)
+void launch_amg_prolong_correct(size_t rows, const int* agg, const double* ec, double* z);
+
 struct MgLevel {
-    int dim = 2;          // 2: an n x n 5-point stencil; 3: an n x n x n 7-point one
+    int dim = 2;          // 2: an n x n 5-point stencil; 3: an n x n x n 7-point one; 0: a general CSR (an AMG level, no grid: n stays 0)
     int n = 0, rows = 0;  // the grid and its rows
     DeviceCsr A;          // levels above 0 (level 0 reads the operator's own CSR)
     SlabCsr view;
@@ -71,19 +79,31 @@ struct MgLevel {
     double coef[1 + 2 * kMgCoarsestDegree] = {0.0};   // c0, h_1, g_1, ...
     double *r = nullptr, *d = nullptr, *z = nullptr;  // r: levels above 0
     double* aux = nullptr;  // a 2-D row-lds plan: z' of the fused step; every other plan: w = A z
+    // dim 0: level 0 runs the operator's own run_device (op), every other level launch_csr_spmv in csr_variant; a level that is not
+    // the coarsest holds its aggregates on the device
+    const SpmvOperator* op = nullptr;
+    CsrVariant csr_variant = CsrVariant::Auto;
+    int coarse_rows = 0, max_aggregate = 0;
+    int *agg = nullptr, *agg_ptr = nullptr, *members = nullptr;
     bool fused() const { return dim == 2 && plan.variant == Stencil5Variant::RowLds; }
     ChebSpmv spmv() const {  // how this level runs A z (device_runtime.hpp)
         ChebSpmv a;
+        if (dim == 0) {
+            if (op != nullptr) a.op = op;
+            else a.view = &view, a.csr = true, a.csr_variant = csr_variant;
+            return a;
+        }
         a.view = &view;
         if (dim == 3) a.plan7 = &plan7;
         else a.plan = &plan, a.partials = fused() ? plan.partials : 0;
         return a;
     }
-    long long nnz() const { return dim == 3 ? stencil7_nnz(n) : stencil_nnz(n); }
+    long long nnz() const { return dim == 0 ? view.nnz_local : dim == 3 ? stencil7_nnz(n) : stencil_nnz(n); }
 };
 
 struct MgHierarchy {
-    int dim = 2;
+    int dim = 2;  // 0: an AMG hierarchy (spmv_amd_precond_create_amg)
+    double strength = 0.0, setup_ms = 0.0;  // dim 0: theta, and the host wall time of the creation
     std::vector<MgLevel> levels;
     int smoother_degree = 0;
     double* partials = nullptr;  // the r.z partials of level 0's last update
@@ -99,6 +119,9 @@ struct MgHierarchy {
             device_release(L.d);
             device_release(L.z);
             device_release(L.aux);
+            device_release(L.agg);
+            device_release(L.agg_ptr);
+            device_release(L.members);
         }
         levels.clear();
         device_release(partials);

@@ -547,7 +547,9 @@ bool spmv_amd::cheb_step(ChebRun& c, double g, double h, bool last) {
     }
     bool ok = true;
     stage_run(c.T, &StageTimers::t_spmv, [&] {
-        if (c.a.plan7 != nullptr) {
+        if (c.a.csr) {
+            launch_csr_spmv(*c.a.view, c.z, c.aux, 1.0, c.a.csr_variant, kStream);
+        } else if (c.a.plan7 != nullptr) {
             (void)launch_stencil7_spmv(*c.a.view, *c.a.plan7, c.z, c.aux, 1.0, nullptr, c.stop, false, kStream);
         } else if (c.a.plan != nullptr) {
             (void)launch_stencil5_spmv(*c.a.view, *c.a.plan, c.z, c.aux, 1.0, nullptr, c.stop, false, kStream);

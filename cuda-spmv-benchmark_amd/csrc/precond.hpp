@@ -62,7 +62,7 @@ void launch_cheb_term0_apply(size_t n, const double* r, const double* dinv, doub
 
 // One Chebyshev application in flight on one operator or level: t = fma(-1, A z, r) ; u = dinv t ; d = fma(g, u, h d) ; z = z + d.
 // cheb_step runs one step in the form `a` allows: on a row-lds plan the fused launch (z' goes to aux, then z and aux change places),
-// on any other stencil plan (2-D, or the Stencil7Plan of a 3-D level) the SpMV that tests `stop` into aux and cheb_step_kernel, else run_device into aux and cheb_step_kernel.
+// on any other stencil plan (2-D, or the Stencil7Plan of a 3-D level) the SpMV that tests `stop` into aux and cheb_step_kernel, on a general CSR level of an AMG hierarchy launch_csr_spmv into aux and cheb_step_kernel, else run_device into aux and cheb_step_kernel.
 // last: the step also writes the partials of r.z to `partials` and records them in rz_partials / rz_count. False: run_device
 // refused (said on stderr). cheb_steps runs steps 1 .. degree from coef (c0, h_1, g_1, ...); report: step `degree` is a last one.
 struct ChebRun {

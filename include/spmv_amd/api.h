@@ -386,8 +386,50 @@ SpmvAmdPrecond* spmv_amd_precond_create_multigrid3d(SpmvOperator* op, int smooth
 /* The number of levels, nu, and up to cap grids n_l (the edge of the n_l x n_l or n_l x n_l x n_l grid) and lambda_max_l; returns the
  * number of levels, 0 for another kind (nothing is written). Any out pointer may be NULL. */
 int spmv_amd_precond_multigrid_info(const SpmvAmdPrecond* m, int* levels, int* smoother_degree, int* grids, double* lambda_max, int cap);
-/* 2 for a multigrid preconditioner of stencil5-csr, 3 for one of stencil7-csr, 0 for NULL or any other kind. */
+/* 2 for a multigrid preconditioner of stencil5-csr, 3 for one of stencil7-csr, 0 for NULL, any other kind and a handle of
+ * spmv_amd_precond_create_amg (there is no grid). */
 int spmv_amd_precond_multigrid_dimension(const SpmvAmdPrecond* m);
+/* Kind "multigrid" for "cusparse-csr", the general CSR operator (csrc/amg.hip, csrc/amg_setup.hpp): the cycle of
+ * spmv_amd_precond_create_multigrid on a hierarchy made by aggregating the MATRIX -- a 9-point stencil, a rectangular grid, a matrix
+ * read from a file, a permuted stencil, a graph Laplacian. nu = smoother_degree (0..8); max_levels: 0 = automatic (32), else 1..32;
+ * strength = theta, finite and in [0, 1) (the application uses 0.08). Refused before any HIP call, *bad_row = -1: a null operator, an
+ * argument out of range, an operator that is not cusparse-csr (named in the sentence; stencil5-csr and stencil7-csr have creators of
+ * their own and their product bits follow another order: to compare, load the same matrix into cusparse-csr), one used before init, a
+ * matrix that is not square. Refused after HIP work: a diagonal entry on any level that breaks Jacobi's validity rule (the level is
+ * named on stderr, *bad_row = the row of that level). The set-up runs on the host from the operator's CSR read back; everything is
+ * sized against the device's free memory before anything is allocated; a refusal leaves no device memory behind.
+ * The handle is a "multigrid" handle: spmv_amd_pcg_solve_device, spmv_amd_gcr_solve_device and spmv_amd_precond_apply_device accept it;
+ * spmv_amd_bicgstab_solve_device and every batched entry point refuse it with the sentences they have (its hierarchy holds single
+ * vectors); spmv_amd_precond_multigrid_info works on it and writes 0 into every grids entry.
+ * All host arithmetic is fp64 with one rounding per operation.
+ * Diagonal: d_i and dinv_i of a level by the diagonal pass above, with its validity rule.
+ * Strong couplings: t2 = theta theta; entry k of row i with column j != i and value v is strong iff v v > t2 fabs(d_i d_j); strong(i)
+ * lists those columns in CSR order.
+ * Aggregation, sequential in ascending row order, aggregates numbered in order of creation. Pass 1: row i is skipped if it is
+ * aggregated or any j of strong(i) is; otherwise i and all of strong(i) form the next aggregate. Pass 2, from a copy of pass 1's map:
+ * an unaggregated i joins the pass-1 aggregate of the first j of strong(i), in CSR order, that pass 1 aggregated. Pass 3: an i still
+ * unaggregated founds the next aggregate with every j of strong(i) still unaggregated at that moment. The members of an aggregate
+ * are its rows in ascending order.
+ * Coarsest level: level l is the coarsest if rows_l <= 64, or l + 1 = max_levels, or the aggregation of level l gives
+ * 10 n_c > 9 rows_l (that aggregation is discarded).
+ * Coarse operator A_c = P^T A P, P piecewise constant: row I holds one entry per distinct aggregate J = agg(col) met in its members'
+ * rows, sorted by ascending J, stored zeros kept; each value a plain sequential sum that starts from its first term and walks the
+ * members in ascending order, each member's entries in CSR order.
+ * Per level: lambda_max by the symmetric Gershgorin bound; the smoother is the Chebyshev application of degree nu on
+ * [lambda_max / 4.0, lambda_max]; the coarsest level is solved by degree 8 on [lambda_max / 30.0, lambda_max] from a zero guess.
+ * Products: level 0 is the operator's own run_device in whatever variant it currently runs; every other level the general CSR product
+ * in the automatic variant of that level's matrix.
+ * Cycle: steps (1) to (5) of spmv_amd_precond_create_multigrid's text with  (2) r_c[I] = (((t_m0 + t_m1) + t_m2) + ...) over the
+ * members of I in ascending order, t_i = fma(-1.0, s_i, r_i), s_i the chain s = +0.0 ; s = fma(v[k], z[col[k]], s) for ascending k --
+ * for every row, whatever variant the level's product runs;  (4) z_i = fma(2.0, e_c[agg(i)], z_i): the factor stays 2.0.
+ * Limitation: the near-null vector is assumed constant. A symmetric diagonal scaling S A S of a good system coarsens badly from the
+ * second level on (the piecewise-constant P no longer fits); a caller-supplied near-null vector is not available. */
+SpmvAmdPrecond* spmv_amd_precond_create_amg(SpmvOperator* op, int smoother_degree, int max_levels, double strength, int* bad_row);
+/* A handle of spmv_amd_precond_create_amg: the number of levels, nu, theta, the host wall time of the whole creation in ms, and up to
+ * cap entries per level: rows, stored entries, the largest aggregate (0 on the coarsest level) and lambda_max. Returns the number of
+ * levels, 0 for any other handle (nothing is written). Any out pointer may be NULL. */
+int spmv_amd_precond_amg_info(const SpmvAmdPrecond* m, int* levels, int* smoother_degree, double* strength, int* rows, long long* nnz,
+                              int* max_aggregate, double* lambda_max, double* setup_ms, int cap);
 /* Kind "multigrid" for up to max_rhs (1..8) right-hand sides at once (csrc/multigrid_multi.hip): it is
  * spmv_amd_precond_create_multigrid in every respect -- levels, coarse operators, dinv, Gershgorin bounds, coefficients, refusals, *bad_row --
  * and in addition its hierarchy holds block vectors of max_rhs row-interleaved columns (element (row, column j) at [row * k + j]) on every

@@ -335,6 +335,33 @@ typedef struct SpmvAmdMgStageArgs {
  * complete stencil. Returns 0 otherwise. */
 int spmv_amd_mg_stage(const char* stage, SpmvAmdMgStageArgs* a);
 
+/* Device pointers and sizes of one spmv_amd_amg_stage call (csrc/amg.hip). */
+typedef struct SpmvAmdAmgStageArgs {
+    int rows;                /* fine rows */
+    int cols;                /* residual_restrict: the length of z (the columns of the CSR) */
+    int coarse_rows;         /* aggregates: the length of the coarse vector */
+    const int* row_ptr;      /* residual_restrict: the fine level's CSR, rows + 1 / nnz / nnz */
+    const int* col_idx;
+    const double* values;
+    const int* agg_ptr;      /* residual_restrict: coarse_rows + 1 */
+    const int* members;      /* residual_restrict: agg_ptr[coarse_rows] fine rows; a row no aggregate lists is never read */
+    const int* agg;          /* prolong_correct: rows aggregates */
+    double* z;               /* residual_restrict: in (8-byte aligned); prolong_correct: in and out (16-byte aligned) */
+    const double* r;         /* residual_restrict: in */
+    double* coarse;          /* residual_restrict: out, r_c; prolong_correct: in, e_c */
+} SpmvAmdAmgStageArgs;
+/* The two launches an AMG level adds to the cycle, one per call on the caller's device data, through the functions the cycle makes
+ * them with. Every call synchronises. stage: "residual_restrict" (r_c[I] = ((t_m0 + t_m1) + ...) over the members of I, one launch) or
+ * "prolong_correct" (z = fma(2.0, e_c[agg[i]], z)). Refused before any HIP call: an unknown stage, null arguments, sizes below 1, a
+ * null or misaligned pointer the stage needs. The index arrays are then read back and checked on the host -- row_ptr ascending from
+ * 0, columns in [0, cols), agg_ptr ascending from 0, members in [0, rows), agg in [0, coarse_rows) --: an index outside its range is
+ * refused before the launch. Returns 0 otherwise. */
+int spmv_amd_amg_stage(const char* stage, SpmvAmdAmgStageArgs* a);
+/* The aggregate of every row of one level of an AMG hierarchy (spmv_amd_precond_amg_info has the rows) copied to the host; the level's
+ * CSR and dinv come from spmv_amd_precond_multigrid_level_csr. Non-zero for another handle, a level that does not exist or the
+ * coarsest level, which has no aggregates. */
+int spmv_amd_precond_amg_level_aggregates(const SpmvAmdPrecond* m, int level, int* agg);
+
 /* Per-column state of a batched CG solve (csrc/multi_rhs.hpp keeps the same record on the device, one per column). */
 typedef struct SpmvAmdMultiColumn {
     double rr_old;    /* r.r of the last iteration that did not converge */
