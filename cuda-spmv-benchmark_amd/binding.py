@@ -171,7 +171,7 @@ DECLARED_SYMBOLS = [
     "spmv_amd_pcg_solve_device_multi", "spmv_amd_pcg_last_history_multi", "spmv_amd_pcg_multi_workspace_bytes",
     "spmv_amd_precond_create_multigrid_multi", "spmv_amd_precond_multigrid_max_rhs", "spmv_amd_precond_apply_device_multi",
     "spmv_amd_precond_create_multigrid3d_multi",
-    "spmv_amd_precond_create_amg", "spmv_amd_precond_amg_info",
+    "spmv_amd_precond_create_amg", "spmv_amd_precond_amg_info", "spmv_amd_precond_create_amg_multi",
     "spmv_amd_bicgstab_solve_device", "spmv_amd_bicgstab_last_history",
     "spmv_amd_bicgstab_solve_device_multi", "spmv_amd_bicgstab_last_history_multi", "spmv_amd_bicgstab_multi_workspace_bytes",
     "spmv_amd_gcr_solve_device", "spmv_amd_gcr_last_history", "spmv_amd_gcr_workspace_bytes",
@@ -182,7 +182,7 @@ LAB_ONLY_SYMBOLS = ["spmv_amd_cg_slab_create_stencil5_as", "spmv_amd_cg_slab_set
                     "spmv_amd_cg_slab_direction_spmv", "spmv_amd_cg_slab_spmv_dot", "spmv_amd_cg_slab_initial_stage", "spmv_amd_cg_slab_first_stage", "spmv_amd_cg_slab_stored_b", "spmv_amd_cg_slab_update_r_stage", "spmv_amd_cg_slab_ap_form", "spmv_amd_cg_slab_update_r_from_stage", "spmv_amd_cg_slab_first_recompute_form", "spmv_amd_pcg_stage",
                     "spmv_amd_pcg_last_step_launches", "spmv_amd_cg_multi_stage",
                     "spmv_amd_pcg_last_multigrid_cycles", "spmv_amd_precond_multigrid_level_csr", "spmv_amd_mg_stage",
-                    "spmv_amd_amg_stage", "spmv_amd_precond_amg_level_aggregates",
+                    "spmv_amd_amg_stage", "spmv_amd_precond_amg_level_aggregates", "spmv_amd_amg_multi_stage",
                     "spmv_amd_pcg_multi_stage", "spmv_amd_mg_multi_stage", "spmv_amd_mg_multi_stage3d",
                     "spmv_amd_mg3d_multi_level_product", "spmv_amd_precond_multigrid_level_spmm",
                     "spmv_amd_bicgstab_stage", "spmv_amd_gcr_stage", "spmv_amd_operator_fused_spmv", "spmv_amd_bicgstab_multi_stage",
@@ -745,6 +745,8 @@ def _pcg_lib():
         L.spmv_amd_precond_create_amg.restype = C.c_void_p
         L.spmv_amd_precond_amg_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int]
+        L.spmv_amd_precond_create_amg_multi.argtypes = [C.POINTER(SpmvOperator), C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int)]
+        L.spmv_amd_precond_create_amg_multi.restype = C.c_void_p
         L._pcg_sigs = True
     return L
 
@@ -843,6 +845,17 @@ class Precond:
         h = _pcg_lib().spmv_amd_precond_create_amg(op.op, smoother_degree, max_levels, strength, C.byref(bad))
         if not h:
             err = ValueError(f"precond_create_amg({op.name}, {smoother_degree}, {max_levels}, {strength}) refused, bad_row = {bad.value}")
+            err.bad_row = bad.value
+            raise err
+        return cls(_handle=h, _n=op.rows)
+
+    @classmethod
+    def amg_multi(cls, op, smoother_degree=1, max_levels=0, strength=0.08, max_rhs=8):
+        """spmv_amd_precond_create_amg_multi (cusparse-csr only): the AMG hierarchy with block vectors of max_rhs columns."""
+        bad = C.c_int(-2)
+        h = _pcg_lib().spmv_amd_precond_create_amg_multi(op.op, smoother_degree, max_levels, strength, max_rhs, C.byref(bad))
+        if not h:
+            err = ValueError(f"precond_create_amg_multi({op.name}, {smoother_degree}, {max_levels}, {strength}, {max_rhs}) refused, bad_row = {bad.value}")
             err.bad_row = bad.value
             raise err
         return cls(_handle=h, _n=op.rows)
@@ -1008,6 +1021,14 @@ def amg_stage(stage, args):
     if not is_lab():
         raise RuntimeError("the AMG stages exist in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
     return lib().spmv_amd_amg_stage(stage if stage is None else stage.encode(), None if args is None else C.byref(args))
+
+
+def amg_multi_stage(stage, k, args):
+    """spmv_amd_amg_multi_stage (LAB build only; include/spmv_amd/lab.h): one of the two launches an AMG level adds to the batched cycle,
+    on the caller's device blocks of k columns `args` (AmgStageArgs) points to; returns its return code (0, or non-zero for a refusal)."""
+    if not is_lab():
+        raise RuntimeError("the AMG stages exist in the LAB build only (binding.use_lab(), lib/libspmv_amd_lab.so)")
+    return lib().spmv_amd_amg_multi_stage(stage if stage is None else stage.encode(), int(k), None if args is None else C.byref(args))
 
 
 def mg_multi_stage(stage, k, args):

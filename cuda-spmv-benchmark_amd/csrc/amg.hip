@@ -9,6 +9,9 @@
 // Cycle: multigrid.hip's CycleOps on mg_schedule.hpp's mg_vcycle, as for the geometric hierarchies. A level here has dim == 0:
 // level 0 runs the operator's own run_device, every other level launch_csr_spmv in csr_auto_variant of its matrix, both followed
 // by pcg.hip's streaming step; the two transfers are the kernels below.
+//
+// spmv_amd_precond_create_amg_multi is the same creator: its hierarchy also holds multigrid_multi.hip's block
+// vectors and SpMM plans, and the batched cycle's two transfers are amg_multi.hip's.
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -17,6 +20,7 @@
 #include <vector>
 
 #include "amg_setup.hpp"
+#include "multi_rhs.hpp"
 #include "multigrid.hpp"
 #include "stream_device.hpp"
 #ifdef SPMV_AMD_LAB
@@ -169,9 +173,10 @@ bool finish_level(MgHierarchy* h, int l, const amg::HostLevel& H, int* bad_row) 
     return true;
 }
 
-}  // namespace
-
-extern "C" SpmvAmdPrecond* spmv_amd_precond_create_amg(SpmvOperator* op, int smoother_degree, int max_levels, double strength, int* bad_row) {
+// The one creator. multi false: spmv_amd_precond_create_amg (max_rhs is 0 and not looked at); true (..._amg_multi): max_rhs is checked
+// beside the other arguments, and the hierarchy also gets block vectors of that many columns and an SpMM plan on every level
+// (multigrid_multi.hip's mg_multi_create).
+SpmvAmdPrecond* create_amg(SpmvOperator* op, int smoother_degree, int max_levels, double strength, int max_rhs, bool multi, int* bad_row) {
     const auto started = std::chrono::steady_clock::now();
     // argument checks: all before the first HIP call
     if (bad_row != nullptr) *bad_row = -1;
@@ -186,6 +191,10 @@ extern "C" SpmvAmdPrecond* spmv_amd_precond_create_amg(SpmvOperator* op, int smo
     }
     if (!isfinite(strength) || !(strength >= 0.0) || !(strength < 1.0)) {
         fprintf(stderr, "[PCG] amg: strength %g is not a finite number in [0, 1): refused\n", strength);
+        return nullptr;
+    }
+    if (multi && (max_rhs < 1 || max_rhs > kMaxRhs)) {
+        fprintf(stderr, "[PCG] amg: max_rhs %d is outside 1..%d: refused\n", max_rhs, kMaxRhs);
         return nullptr;
     }
     const DiagonalSource d = diagonal_source_of(op);
@@ -231,6 +240,7 @@ extern "C" SpmvAmdPrecond* spmv_amd_precond_create_amg(SpmvOperator* op, int smo
         if (l > 0) need += (size_t)host[l].A.nnz() * (sizeof(double) + sizeof(int)) + ((size_t)L.rows + 1) * sizeof(int) + 3 * 4096;
         if (l + 1 < host.size()) need += (2 * (size_t)L.rows + (size_t)host[l].g.count + 1) * sizeof(int);
     }
+    if (multi) need += mg_multi_bytes(h, max_rhs);
     SpmvAmdPrecond* pm = nullptr;
     char what[64];
     snprintf(what, sizeof what, "%d levels on %d rows (amg)", (int)h->levels.size(), d.rows);
@@ -258,6 +268,10 @@ extern "C" SpmvAmdPrecond* spmv_amd_precond_create_amg(SpmvOperator* op, int smo
         h->partials = device_try_alloc<double>((size_t)stream_grid((size_t)h->levels[0].rows));
         if (h->partials == nullptr) ok = fail("the partials could not be allocated: refused");
     }
+    if (ok && multi) {
+        h->multi = mg_multi_create(h, max_rhs);
+        ok = h->multi != nullptr;
+    }
     HIP_CHECK(hipStreamSynchronize(kStream));
     if (!ok) {
         mg_destroy(h);
@@ -272,6 +286,17 @@ extern "C" SpmvAmdPrecond* spmv_amd_precond_create_amg(SpmvOperator* op, int smo
     pm->lambda_min = pm->lambda_max / (h->levels.size() == 1 ? 30.0 : 4.0);
     h->setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - started).count();
     return pm;
+}
+
+}  // namespace
+
+extern "C" SpmvAmdPrecond* spmv_amd_precond_create_amg(SpmvOperator* op, int smoother_degree, int max_levels, double strength, int* bad_row) {
+    return create_amg(op, smoother_degree, max_levels, strength, 0, false, bad_row);
+}
+
+extern "C" SpmvAmdPrecond* spmv_amd_precond_create_amg_multi(SpmvOperator* op, int smoother_degree, int max_levels, double strength, int max_rhs,
+                                                             int* bad_row) {
+    return create_amg(op, smoother_degree, max_levels, strength, max_rhs, true, bad_row);
 }
 
 extern "C" int spmv_amd_precond_amg_info(const SpmvAmdPrecond* m, int* levels, int* smoother_degree, double* strength, int* rows, long long* nnz,
@@ -303,7 +328,9 @@ extern "C" int spmv_amd_precond_amg_level_aggregates(const SpmvAmdPrecond* m, in
     return 0;
 }
 
-extern "C" int spmv_amd_amg_stage(const char* stage, SpmvAmdAmgStageArgs* a) {
+// The one body of spmv_amd_amg_stage (k = 0: single vectors on the default stream) and spmv_amd_amg_multi_stage (amg_multi.hip; k = 1..8:
+// blocks of k columns, every column running)
+int spmv_amd::amg_stage(const char* stage, int k, SpmvAmdAmgStageArgs* a) {
     // argument checks: all before the first HIP call
     if (stage == nullptr) return fail("stage: none named (residual_restrict, prolong_correct)"), 1;
     const bool restrict_stage = !strcmp(stage, "residual_restrict");
@@ -311,13 +338,17 @@ extern "C" int spmv_amd_amg_stage(const char* stage, SpmvAmdAmgStageArgs* a) {
     if (a == nullptr) return fail("stage: null arguments"), 1;
     if (a->rows < 1 || a->coarse_rows < 1 || (restrict_stage && a->cols < 1)) return fail("stage: a size below 1"), 1;
     const auto aligned = [](const void* p, uintptr_t to) { return p != nullptr && ((uintptr_t)p & (to - 1)) == 0; };
+    const uintptr_t block = k > 0 && k % 2 == 0 ? 16 : 8;  // a block vector: 16-byte accesses where k is even
     if (restrict_stage) {
         if (!aligned(a->row_ptr, 4) || !aligned(a->col_idx, 4) || !aligned(a->values, 8)) return fail("stage: a null or misaligned CSR array"), 1;
         if (!aligned(a->agg_ptr, 4) || !aligned(a->members, 4)) return fail("stage: a null or misaligned member list"), 1;
-        if (!aligned(a->z, 8) || !aligned(a->r, 8) || !aligned(a->coarse, 8)) return fail("stage: z, r and the coarse vector must be 8-byte aligned"), 1;
-    } else if (!aligned(a->agg, 4) || !aligned(a->z, 16) || !aligned(a->coarse, 8)) {
+        if (k == 0 && (!aligned(a->z, 8) || !aligned(a->r, 8) || !aligned(a->coarse, 8)))
+            return fail("stage: z, r and the coarse vector must be 8-byte aligned"), 1;
+    } else if (!aligned(a->agg, 4) || (k == 0 && (!aligned(a->z, 16) || !aligned(a->coarse, 8)))) {
         return fail("stage: agg must be 4-byte, z 16-byte and the coarse vector 8-byte aligned"), 1;
     }
+    if (k > 0 && (!aligned(a->z, block) || (restrict_stage && !aligned(a->r, block)) || !aligned(a->coarse, block)))
+        return fail("stage: a block vector must be 8-byte aligned, 16-byte where k is even"), 1;
 
     // the index arrays, read back: nothing is launched on an index outside its range
     const auto ascending_from_zero = [](const std::vector<int>& p) {
@@ -344,15 +375,19 @@ extern "C" int spmv_amd_amg_stage(const char* stage, SpmvAmdAmgStageArgs* a) {
         v.row_ptr = a->row_ptr, v.col_idx = a->col_idx, v.values = a->values;
         v.n_local = v.n_global = a->rows;
         v.nnz_local = rp.back();
-        launch_amg_residual_restrict(v, a->coarse_rows, a->agg_ptr, a->members, a->z, a->r, a->coarse);
+        if (k == 0) launch_amg_residual_restrict(v, a->coarse_rows, a->agg_ptr, a->members, a->z, a->r, a->coarse);
+        else launch_amg_residual_restrict_multi(k, v, a->coarse_rows, a->agg_ptr, a->members, nullptr, a->z, a->r, a->coarse);
     } else {
         std::vector<int> agg((size_t)a->rows);
         download(agg.data(), a->agg, agg.size());
         if (!all_within(agg, a->coarse_rows)) return fail("stage: an aggregate lies outside the coarse vector: refused"), 1;
-        launch_amg_prolong_correct((size_t)a->rows, a->agg, a->coarse, a->z);
+        if (k == 0) launch_amg_prolong_correct((size_t)a->rows, a->agg, a->coarse, a->z);
+        else launch_amg_prolong_correct_multi(k, (size_t)a->rows, a->agg, nullptr, a->coarse, a->z);
     }
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipDeviceSynchronize());
     return 0;
 }
+
+extern "C" int spmv_amd_amg_stage(const char* stage, SpmvAmdAmgStageArgs* a) { return spmv_amd::amg_stage(stage, 0, a); }
 #endif  // SPMV_AMD_LAB

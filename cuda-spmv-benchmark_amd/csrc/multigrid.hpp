@@ -64,6 +64,16 @@ void launch_amg_residual_restrict(const SlabCsr& m, int coarse_rows, const int* 
                                   double* rc);
 // z = fma(2.0, e_c[agg[i]], z), z in place (16-byte aligned)
 void launch_amg_prolong_correct(size_t rows, const int* agg, const double* ec, double* z);
+// The same two on block vectors of k = 1..8 row-interleaved columns, on the batch stream (amg_multi.hip). cols: the
+// device column records (null: every column is running); nothing is read or written once every column is done. Per column the bits of
+// the two above; the matrix, the member lists and agg are read once for all k columns.
+void launch_amg_residual_restrict_multi(int k, const SlabCsr& m, int coarse_rows, const int* agg_ptr, const int* members,
+                                        const PcgMultiColumn* cols, const double* Z, const double* R, double* Rc);
+void launch_amg_prolong_correct_multi(int k, size_t rows, const int* agg, const PcgMultiColumn* cols, const double* Ec, double* Z);
+#ifdef SPMV_AMD_LAB
+// spmv_amd_amg_stage (k = 0: single vectors) and spmv_amd_amg_multi_stage (k = 1..8): one body, amg.hip
+int amg_stage(const char* stage, int k, SpmvAmdAmgStageArgs* a);
+#endif
 
 struct MgLevel {
     int dim = 2;          // 2: an n x n 5-point stencil; 3: an n x n x n 7-point one; 0: a general CSR (an AMG level, no grid: n stays 0)
@@ -102,12 +112,12 @@ struct MgLevel {
 };
 
 struct MgHierarchy {
-    int dim = 2;  // 0: an AMG hierarchy (spmv_amd_precond_create_amg)
+    int dim = 2;  // 0: an AMG hierarchy (spmv_amd_precond_create_amg, ..._amg_multi)
     double strength = 0.0, setup_ms = 0.0;  // dim 0: theta, and the host wall time of the creation
     std::vector<MgLevel> levels;
     int smoother_degree = 0;
     double* partials = nullptr;  // the r.z partials of level 0's last update
-    MgMulti* multi = nullptr;    // spmv_amd_precond_create_multigrid_multi / ..._multigrid3d_multi; null: single vectors only
+    MgMulti* multi = nullptr;    // spmv_amd_precond_create_multigrid_multi / ..._multigrid3d_multi / ..._amg_multi; null: single vectors only
     int count() const { return (int)levels.size(); }
     void release() {
         mg_multi_destroy(multi);

@@ -4,7 +4,8 @@
 // here, for the 3-D hierarchy of stencil7-csr (spmv_amd_precond_create_multigrid3d_multi). The hierarchy, its coarse operators, dinv, bounds and coefficients are multigrid.hip's;
 // spmv_amd_precond_create_multigrid_multi adds what is here: on every level above 0 the block vectors R, D, Z and W of max_rhs columns,
 // and on every level an SpmmPlan on the level's own view and Stencil5Plan variant (a 3-D level: "spmm/csr"). Level 0 works on its caller's vectors -- the solve's
-// R, D, Z and AP buffer, or the block application's.
+// R, D, Z and AP buffer, or the block application's. An AMG hierarchy (spmv_amd_precond_create_amg_multi) runs the
+// same cycle: its levels have dim == 0, their plan is "spmm/csr" and their two transfers are amg_multi.hip's.
 //
 // The cycle is mg_schedule.hpp's mg_vcycle with the operations of MultiOps below; the levels are read straight from multigrid.hpp's
 // MgHierarchy. A cycle's launch count does not depend on k: the columns share every launch, and the three launches that are
@@ -317,6 +318,7 @@ MgMulti* mg_multi_create(const MgHierarchy* h, int max_rhs) {
         const MgLevel& v = h->levels[(size_t)l];
         MgMulti::Level& L = mm->levels[(size_t)l];
         if (v.dim == 3) L.plan = stencil7_level_product(v.n) ? plan_spmm_stencil7(v.view, v.n) : plan_spmm(v.view, Stencil5Variant::Auto, true, v.rows, v.rows);
+        else if (v.dim == 0) L.plan = plan_spmm(v.view, Stencil5Variant::Auto, true, v.rows, v.rows);  // an AMG level: "spmm/csr", the operator's own kind
         else L.plan = plan_spmm(v.view, v.plan.variant, false, v.rows, v.rows);
         if (l == 0) continue;
         const size_t count = (size_t)v.rows * (size_t)max_rhs;
@@ -372,14 +374,16 @@ struct MultiOps {
         const Vectors v = at(l);
         double* const rc = mm->levels[(size_t)l + 1].R;
         stage_run(T, &StageTimers::t_spmv, [&] {
-            if (L.dim == 3) launch_residual_restrict3d_multi(k, L.view, L.n, cols, v.Z, v.R, rc);
+            if (L.dim == 0) launch_amg_residual_restrict_multi(k, L.view, L.coarse_rows, L.agg_ptr, L.members, cols, v.Z, v.R, rc);
+            else if (L.dim == 3) launch_residual_restrict3d_multi(k, L.view, L.n, cols, v.Z, v.R, rc);
             else launch_residual_restrict_multi(k, L.view, cols, v.Z, v.R, rc);
         });
     }
     void prolong(int l) {
         const MgLevel& L = h->levels[(size_t)l];
         stage_run(T, &StageTimers::t_blas, [&] {
-            if (L.dim == 3) launch_prolong_correct3d_multi(k, L.n, cols, at(l + 1).Z, at(l).Z);
+            if (L.dim == 0) launch_amg_prolong_correct_multi(k, (size_t)L.rows, L.agg, cols, at(l + 1).Z, at(l).Z);
+            else if (L.dim == 3) launch_prolong_correct3d_multi(k, L.n, cols, at(l + 1).Z, at(l).Z);
             else launch_prolong_correct_multi(k, L.n, cols, at(l + 1).Z, at(l).Z);
         });
     }

@@ -89,8 +89,8 @@ void mg_destroy(MgHierarchy* h);
 // owns; the r.z partials are the ones the last post-smoothing step left. T (may be null): the solve's timers.
 Applied mg_cycle(MgHierarchy* h, const double* r, StageTimers* T);
 double* mg_result_vector(MgHierarchy* h);  // a level-0 vector of the hierarchy (what a loop hands on when no cycle ran)
-// The block vectors and SpMM plans of a hierarchy made by spmv_amd_precond_create_multigrid_multi or ..._multigrid3d_multi (null: a
-// single-vector hierarchy).
+// The block vectors and SpMM plans of a hierarchy made by spmv_amd_precond_create_multigrid_multi, ..._multigrid3d_multi or ..._amg_multi
+// (null: a single-vector hierarchy).
 struct MgMulti;
 MgMulti* mg_multi_of(const MgHierarchy* h);
 int mg_multi_capacity(const MgMulti* mm);  // max_rhs; 0 for null

@@ -451,12 +451,31 @@ SpmvAmdPrecond* spmv_amd_precond_create_multigrid_multi(SpmvOperator* op, int sm
  * spmv_amd_precond_apply_device, ..._multigrid_info and ..._multigrid_dimension (3) work on it, bit for bit as on a handle of
  * spmv_amd_precond_create_multigrid3d. */
 SpmvAmdPrecond* spmv_amd_precond_create_multigrid3d_multi(SpmvOperator* op, int smoother_degree, int max_levels, int max_rhs, int* bad_row);
-/* The capacity max_rhs of a handle of the two creators above; 0 for NULL, for another kind and for a handle of
- * spmv_amd_precond_create_multigrid or ..._multigrid3d. */
+/* The same for "cusparse-csr" (csrc/amg_multi.hip): it is spmv_amd_precond_create_amg in every respect -- the
+ * argument checks and their sentences, the order of the refusals, *bad_row, the host set-up and every level's aggregates, CSR, dinv,
+ * lambda_max and coefficients bit for bit --, with max_rhs outside 1..8 refused before any HIP call beside the other argument checks,
+ * and in addition its hierarchy holds the block vectors R, D, Z and W of max_rhs row-interleaved columns on every level above 0 and one
+ * SpMM plan per level ("spmm/csr", the kind of the operator's own multi-RHS plan), their bytes sized with everything else against the
+ * device's free memory before anything is allocated; a refusal leaves no device memory behind.
+ * Per column the batched cycle is steps (1) to (5) of spmv_amd_precond_create_amg's text element for element, with EVERY level's product
+ * the sequential chain s = +0.0 ; s = fma(v[k], z[col[k]], s) for ascending k -- what "spmm/csr" computes; the coarse sum runs
+ * ((t_m0 + t_m1) + ...) over the members in ascending order, t = fma(-1.0, s, r); the correction is z = fma(2.0, e_c[agg(i)], z).
+ * A column's bits therefore do not depend on nrhs, on its slot or on the other columns; a NaN in one column reaches no other. They equal
+ * the bits of the single-vector AMG handle wherever level 0 and every coarse level run "csr/stream" or "csr/row-scalar". On a level that
+ * runs "csr/adaptive" or "csr/wavefront" (long rows) the single handle sums a row as a tree, and the two agree to rounding only -- the
+ * statement the operator's own SpMM makes against its SpMV. The restriction's residual is the sequential chain in both.
+ * The handle is also a complete single-vector AMG handle: spmv_amd_pcg_solve_device, spmv_amd_gcr_solve_device,
+ * spmv_amd_precond_apply_device, ..._amg_info, ..._multigrid_info and ..._multigrid_dimension (0) work on it, bit for bit as on a handle
+ * of spmv_amd_precond_create_amg. The batched PCG, the batched GCR(m) and spmv_amd_precond_apply_device_multi accept it for
+ * nrhs <= max_rhs; spmv_amd_bicgstab_solve_device_multi refuses kind "multigrid" as before. */
+SpmvAmdPrecond* spmv_amd_precond_create_amg_multi(SpmvOperator* op, int smoother_degree, int max_levels, double strength, int max_rhs,
+                                                  int* bad_row);
+/* The capacity max_rhs of a handle of the three creators above; 0 for NULL, for another kind and for a handle of
+ * spmv_amd_precond_create_multigrid, ..._multigrid3d or ..._amg. */
 int spmv_amd_precond_multigrid_max_rhs(const SpmvAmdPrecond* m);
 /* Z = M^-1 R on device blocks of nrhs (1..8) row-interleaved columns of n rows (16-byte aligned), for every kind the batched solver
- * accepts: "none" (copy), "jacobi", "chebyshev", and "multigrid" from spmv_amd_precond_create_multigrid_multi or
- * ..._multigrid3d_multi with nrhs <= max_rhs. The checks are those of spmv_amd_precond_apply_device, plus nrhs and the capacity, all before any HIP call ([PCG-MULTI] sentences;
+ * accepts: "none" (copy), "jacobi", "chebyshev", and "multigrid" from spmv_amd_precond_create_multigrid_multi,
+ * ..._multigrid3d_multi or ..._amg_multi (there per column the bits its own text states) with nrhs <= max_rhs. The checks are those of spmv_amd_precond_apply_device, plus nrhs and the capacity, all before any HIP call ([PCG-MULTI] sentences;
  * "chebyshev" and "multigrid" need the operator's multi-RHS path). d_R is only read; d_Z must not overlap it. Work vectors that are not
  * the hierarchy's live for the call only. Synchronises. Column j of d_Z has exactly the bits spmv_amd_precond_apply_device gives for
  * column j alone: both run the operator's own product bits and the same element-wise fma forms (the fused row-lds step of the single

@@ -357,6 +357,11 @@ typedef struct SpmvAmdAmgStageArgs {
  * 0, columns in [0, cols), agg_ptr ascending from 0, members in [0, rows), agg in [0, coarse_rows) --: an index outside its range is
  * refused before the launch. Returns 0 otherwise. */
 int spmv_amd_amg_stage(const char* stage, SpmvAmdAmgStageArgs* a);
+/* The same two launches on block vectors of k (1..8) row-interleaved columns (csrc/amg_multi.hip), on the same
+ * record: z holds cols x k (residual_restrict) or rows x k (prolong_correct) values, r rows x k, coarse coarse_rows x k, element
+ * (row, column j) at [row * k + j]; every column is running. z, r and coarse are 8-byte aligned, 16-byte where k is even. The checks
+ * and the host-side index validation before the launch are spmv_amd_amg_stage's (one body, csrc/amg.hip), plus k. */
+int spmv_amd_amg_multi_stage(const char* stage, int k, SpmvAmdAmgStageArgs* a);
 /* The aggregate of every row of one level of an AMG hierarchy (spmv_amd_precond_amg_info has the rows) copied to the host; the level's
  * CSR and dinv come from spmv_amd_precond_multigrid_level_csr. Non-zero for another handle, a level that does not exist or the
  * coarsest level, which has no aggregates. */
