@@ -8,7 +8,7 @@
 //
 // Cycle: multigrid.hip's CycleOps on mg_schedule.hpp's mg_vcycle, as for the geometric hierarchies. A level here has dim == 0:
 // level 0 runs the operator's own run_device, every other level launch_csr_spmv in csr_auto_variant of its matrix, both followed
-// by pcg.hip's streaming step; the two transfers are the kernels below.
+// by precond.hip's streaming step; the two transfers are the kernels below.
 //
 // spmv_amd_precond_create_amg_multi is the same creator: its hierarchy also holds multigrid_multi.hip's block
 // vectors and SpMM plans, and the batched cycle's two transfers are amg_multi.hip's.

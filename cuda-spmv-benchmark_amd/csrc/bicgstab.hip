@@ -1,5 +1,5 @@
 // bicgstab.hip -- right-preconditioned BiCGSTAB over any SpmvOperator: the solver for matrices that are not symmetric definite
-// (DESIGN.md section 21). It asks run_device of the operator and nothing else; kinds "none" and "jacobi" (pcg.hip's preconditioner
+// (DESIGN.md section 21). It asks run_device of the operator and nothing else; kinds "none" and "jacobi" (precond.hip's preconditioner
 // record; "chebyshev" and "multigrid" are built for symmetric definite matrices and refused). Contract, statistics, timer rule,
 // verbose semantics and stopping rule are spmv_amd_pcg_solve_device's (solve_common.hpp); right preconditioning keeps the recorded
 // residual the true one.
@@ -41,10 +41,9 @@
 
 #include "device_runtime.hpp"
 #include "multi_rhs.hpp"
-#include "multi_solve.hpp"
 #include "precond.hpp"
 #include "reduce_device.hpp"
-#include "solve_common.hpp"
+#include "single_solve.hpp"
 #include "stream_device.hpp"
 #ifdef SPMV_AMD_LAB
 #include "spmv_amd/lab.h"
@@ -53,9 +52,6 @@
 using namespace spmv_amd;
 
 namespace {
-
-constexpr hipStream_t kStream = nullptr;  // default stream, shared with the operators
-constexpr int kWave = 64;                 // the streaming kernels: one wavefront per workgroup, one 16-byte pair per lane
 
 // Device scalars of one solve.
 struct BicgScalars {
@@ -71,8 +67,6 @@ struct BicgScalars {
     int stop;         // the verdict: set with converged or breakdown; kernels behind it return at once
     int pad;
 };
-
-__device__ __forceinline__ bool usable(double v) { return v != 0.0 && isfinite(v); }
 
 // ---- the streaming kernels. dinv, phat and shat are not looked at by the "none" instantiations (p^ is p, s^ is r). ----
 
@@ -334,39 +328,9 @@ __global__ __launch_bounds__(kReduceBlock) void bicg_reduce_kernel(const double*
     __shared__ int s_last;
     if (which >= 2 && s->stop != 0) return;
     double total[2] = {0.0, 0.0};
-    if (blocks > 1) {
-        const ReduceStage stage = reduce_stage_of(stage_base);
-        unsigned long long* const slot[2] = {stage.sums, stage.extra};
-        const int lo = (int)blockIdx.x * slice, hi = min(lo + slice, count);
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            block_tree(strided_sum(partials + (long long)v * count, lo, hi), sh);
-            if (threadIdx.x == 0) publish(slot[v] + blockIdx.x, sh[0]);
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) {
-            const unsigned drawn = __hip_atomic_fetch_add(stage.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_last = drawn == (unsigned)(blocks - 1) ? 1 : 0;
-            if (s_last) __hip_atomic_store(stage.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        if (s_last == 0) return;
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            double acc = 0.0;
-            for (int i = (int)threadIdx.x; i < blocks; i += kReduceBlock) acc += published(slot[v] + i);
-            block_tree(acc, sh);
-            total[v] = sh[0];
-            __syncthreads();
-        }
-    } else {
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            block_tree(strided_sum(partials + (long long)v * count, 0, count), sh);
-            total[v] = sh[0];
-            __syncthreads();
-        }
-    }
+    const ReduceStage stage = reduce_stage_of(stage_base);
+    const auto slot_of = [&](int v) { return v == 0 ? stage.sums : stage.extra; };
+    if (!sum_values_last_block<NV>(partials, count, NV, slice, blocks, stage.ticket, slot_of, sh, &s_last, total)) return;
     if (threadIdx.x == 0) bicg_step(s, which, total, tol, hist, hist_cap);
 }
 
@@ -384,15 +348,7 @@ struct BicgVectors {
     BicgScalars* s = nullptr;
 };
 
-#define BICG_LAUNCH(kernel, ...)                                                                     \
-    do {                                                                                             \
-        const dim3 grid(stream_grid(a.n)), block(kWave);                                             \
-        const int count = (int)grid.x;                                                               \
-        (void)count;                                                                                 \
-        if (a.jac) hipLaunchKernelGGL(kernel<true>, grid, block, 0, kStream, a.n, __VA_ARGS__);     \
-        else hipLaunchKernelGGL(kernel<false>, grid, block, 0, kStream, a.n, __VA_ARGS__);          \
-    } while (0)
-
+#define BICG_LAUNCH(kernel, ...) SPMV_AMD_STREAM_LAUNCH(kernel, a.jac, a.n, __VA_ARGS__)
 void launch_bicg_init(const BicgVectors& a) { BICG_LAUNCH(bicg_init_kernel, a.b, a.v, a.dinv, a.r, a.rhat, a.p, a.phat, a.partials); }
 void launch_bicg_update_s(const BicgVectors& a) { BICG_LAUNCH(bicg_update_s_kernel, a.s, a.v, a.dinv, a.r, a.shat, a.partials); }
 void launch_bicg_update_xr(const BicgVectors& a) {
@@ -500,13 +456,6 @@ bool ensure_workspace(int n, int device, bool jac, int hist_cap) {
     return true;
 }
 
-int kind_of(const char* kind) {
-    if (kind == nullptr) return -1;
-    if (!strcmp(kind, "none")) return kNone;
-    if (!strcmp(kind, "jacobi")) return kJacobi;
-    return -1;
-}
-
 }  // namespace
 
 namespace spmv_amd {
@@ -516,37 +465,14 @@ void release_bicgstab_workspace_locked() { g_bicg.release(); }
 extern "C" int spmv_amd_bicgstab_solve_device(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, const double* b, double* x,
                                               const CGConfig* config, CGStats* stats) {
     // argument checks: all before the first HIP call
-    if (op == nullptr || mat == nullptr || m == nullptr || b == nullptr || x == nullptr || config == nullptr || stats == nullptr)
-        return fail("null argument"), 1;
-    if (op->run_device == nullptr) {
-        fprintf(stderr, "[BICGSTAB] operator '%s' does not support the device-native interface\n", op->name ? op->name : "?");
-        return 1;
-    }
-    if (config->max_iters < 0) return fail("max_iters < 0"), 1;
+    if (!check_solve_arguments("BICGSTAB", op, mat, m, b, x, config, stats)) return 1;
     if (m->kind != kNone && m->kind != kJacobi) {
         fprintf(stderr,
                 "[BICGSTAB] preconditioner kind '%s' is built for symmetric definite matrices: BiCGSTAB takes 'none' or 'jacobi': refused\n",
                 spmv_amd_precond_kind(m));
         return 1;
     }
-    const DiagonalSource d = diagonal_source_of(op);
-    if (d.owner != nullptr) {
-        if (!d.ready) {
-            fprintf(stderr, "[BICGSTAB] operator '%s' used before init\n", op->name);
-            return 1;
-        }
-        if (d.rows != d.cols || mat->rows != d.rows) {
-            fprintf(stderr, "[BICGSTAB] the operator holds a %d x %d matrix, mat->rows = %d: a square system of that size is required\n",
-                    d.rows, d.cols, mat->rows);
-            return 1;
-        }
-    }
-    if (mat->rows < 1) return fail("mat->rows < 1"), 1;
-    if (m->n != mat->rows) {
-        fprintf(stderr, "[BICGSTAB] the preconditioner is for %d rows, mat->rows = %d\n", m->n, mat->rows);
-        return 1;
-    }
-    if (!precond_matches(op, m, d)) return 1;
+    if (!check_solve_system("BICGSTAB", op, mat, m)) return 1;
     const int n = mat->rows;
     const CGConfig cfg = *config;
     const bool jac = m->kind == kJacobi;
@@ -565,14 +491,7 @@ extern "C" int spmv_amd_bicgstab_solve_device(SpmvOperator* op, MatrixData* mat,
     const int count = (int)stream_grid((size_t)n);
     StageTimers T(cfg.enable_detailed_timers != 0, kStream);
     bool failed = false;
-    auto product = [&](const double* in, double* out) {
-        T.run(&T.t_spmv, [&] {
-            if (op->run_device(in, out) != 0) {
-                fprintf(stderr, "[BICGSTAB] operator '%s': run_device failed\n", op->name);
-                failed = true;
-            }
-        });
-    };
+    auto product = [&](const double* in, double* out) { timed_product("BICGSTAB", op, T, in, out, failed); };
     auto reduce = [&](int which) {
         T.run(&T.t_red, [&] { launch_bicg_reduce(w.partials, count, which, w.stage, w.s, cfg.tolerance, w.hist, w.hist_cap); });
     };
@@ -612,25 +531,11 @@ extern "C" int spmv_amd_bicgstab_solve_device(SpmvOperator* op, MatrixData* mat,
         HIP_CHECK(hipDeviceSynchronize());
         return 1;
     }
-    download(x, w.x, (size_t)n);
-    const int entries = h.iterations + 1 < w.hist_cap ? h.iterations + 1 : w.hist_cap;
-    g_bicg_history.assign((size_t)entries, 0.0);
-    download(g_bicg_history.data(), w.hist, (size_t)entries);
+    download_solution(x, w.x, n, h.iterations, w.hist, w.hist_cap, g_bicg_history);
 
-    fill_device_stats(stats, h.iterations, h.converged != 0, h.residual, h.b_norm, cfg, total_ms, T.t_spmv, T.t_blas, T.t_red);
-    solution_checksums(x, n, &stats->solution_sum, &stats->solution_norm);
-    if (cfg.verbose >= 1) {
-        static const char* const scalar[] = {"", "sigma = r^.v", "t.t or t.s", "rho' = r^.r"};
-        if (h.breakdown) printf("[BICGSTAB-DEVICE] Breakdown in iteration %d (%s zero or not finite)\n", h.iterations, scalar[h.breakdown & 3]);
-        printf("[BICGSTAB-DEVICE] Converged: %s\n", stats->converged ? "YES" : "NO");
-        printf("[BICGSTAB-DEVICE] Iterations: %d\n", stats->iterations);
-        printf("[BICGSTAB-DEVICE] Final residual: %e\n", stats->residual_norm);
-        printf("[BICGSTAB-DEVICE] Time breakdown:\n");
-        printf("     Total:      %.3f ms\n", stats->time_total_ms);
-        printf("     SpMV:       %.3f ms\n", stats->time_spmv_ms);
-        printf("     BLAS1:      %.3f ms\n", stats->time_blas1_ms);
-        printf("     Reductions: %.3f ms\n", stats->time_reductions_ms);
-    }
+    static const char* const scalar[] = {"", "sigma = r^.v", "t.t or t.s", "rho' = r^.r"};
+    const SolveSummary done{h.iterations, h.converged != 0, h.residual, h.b_norm, h.breakdown ? scalar[h.breakdown & 3] : nullptr};
+    report_solve("BICGSTAB", done, x, n, cfg, T, total_ms, stats);
     return 0;
 }
 
@@ -673,7 +578,7 @@ extern "C" int spmv_amd_bicgstab_stage(const char* stage, const char* kind, Spmv
     if (st != kReduce) {
         if (st != kDotRv && st != kDotT) {
             const int k = kind_of(kind);
-            if (k < 0) return refuse("unknown preconditioner kind (none, jacobi)"), 1;
+            if (k != kNone && k != kJacobi) return refuse("unknown preconditioner kind (none, jacobi)"), 1;
             jac = k == kJacobi;
         }
         if (a->n < 1 || a->n > (size_t)INT_MAX) return refuse("n < 1 or beyond the solver's int rows"), 1;

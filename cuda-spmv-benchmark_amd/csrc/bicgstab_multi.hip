@@ -56,7 +56,6 @@ namespace {
 
 constexpr const char* kTag = "BICGSTAB-MULTI";
 
-__device__ __forceinline__ bool usable(double v) { return v != 0.0 && isfinite(v); }
 __device__ __forceinline__ bool running(const BicgMultiColumn& c) { return c.active != 0 && c.done == 0; }
 
 // The walk of one workgroup: unit i of this thread is row t of the workgroup, columns col0 .. col0 + V - 1.

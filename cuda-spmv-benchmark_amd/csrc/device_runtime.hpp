@@ -162,7 +162,7 @@ struct FusedSpmv {
                   hipStream_t stream) = nullptr;
 };
 FusedSpmv fused_spmv_of(const SpmvOperator* op);
-// How one level runs A z for a step of the Chebyshev application (pcg.hip's cheb_step): this library's
+// How one level runs A z for a step of the Chebyshev application (precond.hip's cheb_step): this library's
 // stencil5-csr operator and a multigrid level (multigrid.hip) are a verified stencil CSR with its launch plan -- on a row-lds plan one
 // whole step runs inside the SpMV launch (kernels.hpp, ChebStep), on any other plan the SpMV tests a device flag (nothing is read
 // once it is set) --, every other operator is its table, driven through run_device followed by the streaming step kernel. The
@@ -186,7 +186,7 @@ void release_bicgstab_workspace_locked();
 // The same for the GCR solver (gcr.hip).
 void release_gcr_workspace_locked();
 
-// The device storage an operator of this library keeps its matrix in, for reading its diagonal (pcg.hip): the CSR of
+// The device storage an operator of this library keeps its matrix in, for reading its diagonal (precond.hip): the CSR of
 // stencil5-csr / cusparse-csr, or the slot-major planes of ellpack / stencil5-ellpack (idx[k * rows + r], -1 = padding).
 // Entries of a row appear in CSR order in both (build_csr_struct's stable sort; ELL slots follow it). owner == nullptr: an
 // operator table this library does not own. generation changes with every init and free() of the operator. Defined in

@@ -46,10 +46,9 @@
 
 #include "device_runtime.hpp"
 #include "multi_rhs.hpp"
-#include "multi_solve.hpp"
 #include "precond.hpp"
 #include "reduce_device.hpp"
-#include "solve_common.hpp"
+#include "single_solve.hpp"
 #include "stream_device.hpp"
 #ifdef SPMV_AMD_LAB
 #include "spmv_amd/lab.h"
@@ -59,8 +58,6 @@ using namespace spmv_amd;
 
 namespace {
 
-constexpr hipStream_t kStream = nullptr;  // default stream, shared with the operators
-constexpr int kWave = 64;                 // the streaming kernels: one wavefront per workgroup, one 16-byte pair per lane
 constexpr int kMaxRestart = 32;
 constexpr int kDefaultRestart = 16;
 constexpr int kDotChunk = 8;   // basis vectors whose pairs a lane of the multidot kernel holds in flight
@@ -84,8 +81,6 @@ struct GcrBasis {
     double* q[kMaxRestart];
     double* z[kMaxRestart];
 };
-
-__device__ __forceinline__ bool usable(double v) { return v != 0.0 && isfinite(v); }
 
 // ---- the streaming kernels ----
 
@@ -303,35 +298,8 @@ __global__ __launch_bounds__(kReduceBlock) void gcr_reduce_kernel(const double* 
     __shared__ double total[kMaxRestart];
     __shared__ int s_last;
     if (which >= 1 && s->stop != 0) return;
-    if (blocks > 1) {
-        const ReduceStage stage = reduce_stage_of(stage_base);
-        const int lo = (int)blockIdx.x * slice, hi = min(lo + slice, count);
-        for (int v = 0; v < nv; ++v) {
-            block_tree(strided_sum(partials + (long long)v * count, lo, hi), sh);
-            if (threadIdx.x == 0) publish(slices + (size_t)v * kReduceStageBlocks + blockIdx.x, sh[0]);
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) {
-            const unsigned drawn = __hip_atomic_fetch_add(stage.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_last = drawn == (unsigned)(blocks - 1) ? 1 : 0;
-            if (s_last) __hip_atomic_store(stage.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        if (s_last == 0) return;
-        for (int v = 0; v < nv; ++v) {
-            double acc = 0.0;
-            for (int i = (int)threadIdx.x; i < blocks; i += kReduceBlock) acc += published(slices + (size_t)v * kReduceStageBlocks + i);
-            block_tree(acc, sh);
-            if (threadIdx.x == 0) total[v] = sh[0];
-            __syncthreads();
-        }
-    } else {
-        for (int v = 0; v < nv; ++v) {
-            block_tree(strided_sum(partials + (long long)v * count, 0, count), sh);
-            if (threadIdx.x == 0) total[v] = sh[0];
-            __syncthreads();
-        }
-    }
+    const auto slot_of = [&](int v) { return slices + (size_t)v * kReduceStageBlocks; };
+    if (!sum_values_last_block<0>(partials, count, nv, slice, blocks, reduce_stage_of(stage_base).ticket, slot_of, sh, &s_last, total)) return;
     if (threadIdx.x == 0) gcr_step(s, which, j, total, tol, hist, hist_cap);
 }
 
@@ -352,13 +320,7 @@ struct GcrVectors {
     GcrScalars* s = nullptr;
 };
 
-#define GCR_LAUNCH(kernel, ...)                                                                     \
-    do {                                                                                            \
-        const dim3 grid(stream_grid(a.n)), block(kWave);                                            \
-        if (a.jac) hipLaunchKernelGGL(kernel<true>, grid, block, 0, kStream, a.n, __VA_ARGS__);    \
-        else hipLaunchKernelGGL(kernel<false>, grid, block, 0, kStream, a.n, __VA_ARGS__);         \
-    } while (0)
-
+#define GCR_LAUNCH(kernel, ...) SPMV_AMD_STREAM_LAUNCH(kernel, a.jac, a.n, __VA_ARGS__)
 void launch_gcr_init(const GcrVectors& a) { GCR_LAUNCH(gcr_init_kernel, a.b, a.Ax, a.dinv, a.r, a.zs, a.partials); }
 void launch_gcr_update_xr(const GcrVectors& a, int j) {
     GCR_LAUNCH(gcr_update_xr_kernel, a.s, a.basis.z[j], a.basis.q[j], a.dinv, a.x, a.r, a.zs, a.partials);
@@ -516,15 +478,6 @@ bool ensure_workspace(int n, int device, int restart, int kind, long long cheb_p
     return true;
 }
 
-int kind_of(const char* kind) {
-    if (kind == nullptr) return -1;
-    if (!strcmp(kind, "none")) return kNone;
-    if (!strcmp(kind, "jacobi")) return kJacobi;
-    if (!strcmp(kind, "chebyshev")) return kChebyshev;
-    if (!strcmp(kind, "multigrid")) return kMultigrid;
-    return -1;
-}
-
 }  // namespace
 
 namespace spmv_amd {
@@ -540,37 +493,14 @@ extern "C" size_t spmv_amd_gcr_workspace_bytes(int rows, int restart, const char
 extern "C" int spmv_amd_gcr_solve_device(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, int restart, const double* b, double* x,
                                          const CGConfig* config, CGStats* stats) {
     // argument checks: all before the first HIP call
-    if (op == nullptr || mat == nullptr || m == nullptr || b == nullptr || x == nullptr || config == nullptr || stats == nullptr)
-        return fail("null argument"), 1;
-    if (op->run_device == nullptr) {
-        fprintf(stderr, "[GCR] operator '%s' does not support the device-native interface\n", op->name ? op->name : "?");
-        return 1;
-    }
-    if (config->max_iters < 0) return fail("max_iters < 0"), 1;
+    if (!check_solve_arguments("GCR", op, mat, m, b, x, config, stats)) return 1;
     if (restart < 0 || restart > kMaxRestart) {
         fprintf(stderr, "[GCR] restart = %d: 1 .. %d, or 0 for the default %d: refused\n", restart, kMaxRestart, kDefaultRestart);
         return 1;
     }
     if (m->kind != kNone && m->kind != kJacobi && m->kind != kChebyshev && m->kind != kMultigrid)
         return fail("the preconditioner record is not one of this library's (unknown kind): refused"), 1;
-    const DiagonalSource d = diagonal_source_of(op);
-    if (d.owner != nullptr) {
-        if (!d.ready) {
-            fprintf(stderr, "[GCR] operator '%s' used before init\n", op->name);
-            return 1;
-        }
-        if (d.rows != d.cols || mat->rows != d.rows) {
-            fprintf(stderr, "[GCR] the operator holds a %d x %d matrix, mat->rows = %d: a square system of that size is required\n", d.rows,
-                    d.cols, mat->rows);
-            return 1;
-        }
-    }
-    if (mat->rows < 1) return fail("mat->rows < 1"), 1;
-    if (m->n != mat->rows) {
-        fprintf(stderr, "[GCR] the preconditioner is for %d rows, mat->rows = %d\n", m->n, mat->rows);
-        return 1;
-    }
-    if (!precond_matches(op, m, d)) return 1;
+    if (!check_solve_system("GCR", op, mat, m)) return 1;
     const int n = mat->rows;
     const int mr = restart == 0 ? kDefaultRestart : restart;
     const CGConfig cfg = *config;
@@ -592,14 +522,7 @@ extern "C" int spmv_amd_gcr_solve_device(SpmvOperator* op, MatrixData* mat, cons
     a.zs = jac ? w.zs : nullptr, a.basis = w.basis, a.partials = w.partials, a.s = w.s;
     StageTimers T(cfg.enable_detailed_timers != 0, kStream);
     bool failed = false;
-    auto product = [&](const double* in, double* out) {
-        T.run(&T.t_spmv, [&] {
-            if (op->run_device(in, out) != 0) {
-                fprintf(stderr, "[GCR] operator '%s': run_device failed\n", op->name);
-                failed = true;
-            }
-        });
-    };
+    auto product = [&](const double* in, double* out) { timed_product("GCR", op, T, in, out, failed); };
     auto reduce = [&](int which, int j) {
         T.run(&T.t_red, [&] { launch_gcr_reduce(w.partials, count, which, j, w.stage, w.slices, w.s, cfg.tolerance, w.hist, w.hist_cap); });
     };
@@ -648,25 +571,11 @@ extern "C" int spmv_amd_gcr_solve_device(SpmvOperator* op, MatrixData* mat, cons
         HIP_CHECK(hipDeviceSynchronize());
         return 1;
     }
-    download(x, w.x, (size_t)n);
-    const int entries = h.iterations + 1 < w.hist_cap ? h.iterations + 1 : w.hist_cap;
-    g_gcr_history.assign((size_t)entries, 0.0);
-    download(g_gcr_history.data(), w.hist, (size_t)entries);
+    download_solution(x, w.x, n, h.iterations, w.hist, w.hist_cap, g_gcr_history);
 
-    fill_device_stats(stats, h.iterations, h.converged != 0, h.residual, h.b_norm, cfg, total_ms, T.t_spmv, T.t_blas, T.t_red);
-    solution_checksums(x, n, &stats->solution_sum, &stats->solution_norm);
-    if (cfg.verbose >= 1) {
-        static const char* const scalar[] = {"", "gamma = q.q", "rho = r.q", ""};
-        if (h.breakdown) printf("[GCR-DEVICE] Breakdown in iteration %d (%s zero or not finite)\n", h.iterations, scalar[h.breakdown & 3]);
-        printf("[GCR-DEVICE] Converged: %s\n", stats->converged ? "YES" : "NO");
-        printf("[GCR-DEVICE] Iterations: %d\n", stats->iterations);
-        printf("[GCR-DEVICE] Final residual: %e\n", stats->residual_norm);
-        printf("[GCR-DEVICE] Time breakdown:\n");
-        printf("     Total:      %.3f ms\n", stats->time_total_ms);
-        printf("     SpMV:       %.3f ms\n", stats->time_spmv_ms);
-        printf("     BLAS1:      %.3f ms\n", stats->time_blas1_ms);
-        printf("     Reductions: %.3f ms\n", stats->time_reductions_ms);
-    }
+    static const char* const scalar[] = {"", "gamma = q.q", "rho = r.q", ""};
+    const SolveSummary done{h.iterations, h.converged != 0, h.residual, h.b_norm, h.breakdown ? scalar[h.breakdown & 3] : nullptr};
+    report_solve("GCR", done, x, n, cfg, T, total_ms, stats);
     return 0;
 }
 

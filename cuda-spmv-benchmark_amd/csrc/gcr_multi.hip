@@ -85,8 +85,6 @@ struct GcrMultiBasis {
     double* z[kMaxRestart];
 };
 
-__device__ __forceinline__ bool usable(double v) { return v != 0.0 && isfinite(v); }
-
 template <int K>
 __device__ __forceinline__ bool any_column_runs(const GcrMultiColumn* __restrict__ cols) {
     bool need = false;
@@ -481,15 +479,6 @@ void launch_reduce(int k, const double* partials, long long count, double* slice
 }
 
 bool fail(const char* what) { return batched_fail(kTag, what); }
-
-int kind_of(const char* kind) {
-    if (kind == nullptr) return -1;
-    if (!strcmp(kind, "none")) return kNone;
-    if (!strcmp(kind, "jacobi")) return kJacobi;
-    if (!strcmp(kind, "chebyshev")) return kChebyshev;
-    if (!strcmp(kind, "multigrid")) return kMultigrid;
-    return -1;
-}
 
 // ---- workspace: the batched scaffold's X, R, P ("jacobi": dinv r), AP (the way in and out; the applications' W = A Z), for
 // "chebyshev" and "multigrid" D and Z, partials and slices for 32 values, the column records and histories; next to them the 2 m basis

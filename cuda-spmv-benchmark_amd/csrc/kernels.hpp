@@ -130,7 +130,7 @@ void launch_fill_sym_planes(const SlabCsr& m, double* ce, double* s, hipStream_t
 // ceil(n / 128) of them; the grid's first and last grid row get 0) by comparing the CSR values with `quintuple` = {W, C, E, N, S}
 // bit for bit, and adds the number of uniform tiles to *d_uniform (zeroed by the caller).
 void launch_classify_tiles(const SlabCsr& m, const double quintuple[5], unsigned char* cls, unsigned long long* d_uniform, hipStream_t stream);
-// One Chebyshev step fused into a row-lds launch (kMode 3; pcg.hip): with w = A z kept in registers,
+// One Chebyshev step fused into a row-lds launch (kMode 3; precond.hip): with w = A z kept in registers,
 //   t = fma(-1.0, w, r) ; u = dinv * t ; d = fma(g, u, h * d) ; z_out = z + d
 // d is updated in place (its own lane only), z_out is a SECOND vector (neighbouring tiles still read z). last != 0: the launch also
 // writes one partial of r . z_out per wave, in the slot layout of the p.Ap partials. work_count (may be null): incremented once per

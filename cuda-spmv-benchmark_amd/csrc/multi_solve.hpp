@@ -1,8 +1,7 @@
 // multi_solve.hpp -- the host side the batched solvers share around their loops (cg_multi.hip: CG; pcg_multi.hip: preconditioned
 // CG; bicgstab_multi.hip: BiCGSTAB): the workspace, the argument checks, the way in (upload, interleave) and the way out (de-interleave, download, histories,
-// statistics, print-out), the per-iteration read of the column records, the choice of a kernel template's instance by k, and the
-// refusals of the LAB build's stage hooks. Host code only: no kernel lives here, so spmm_kernels.hip (the operand entry points) and
-// pcg.hip (its stage hook) include it too. Every function that prints takes the tag it prints under ("CG-MULTI", "PCG-MULTI", "BICGSTAB-MULTI"): each
+// statistics, print-out), the per-iteration read of the column records and the choice of a kernel template's instance by k. Host code
+// only: no kernel lives here, so spmm_kernels.hip (the operand entry points) includes it too. Every function that prints takes the tag it prints under ("CG-MULTI", "PCG-MULTI", "BICGSTAB-MULTI"): each
 // solver keeps its sentences. The loops, their launch order, the kernels and the column records stay each solver's own.
 #pragma once
 
@@ -252,26 +251,6 @@ void finish_batched_solve(const char* tag, BatchedWorkspace<Column>& w, int k, i
         printf("     BLAS1:      %.3f ms\n", T.t_blas);
         printf("     Reductions: %.3f ms\n", T.t_red);
     }
-}
-
-// ---- the LAB build's stage hooks (include/spmv_amd/lab.h): their refusals ----
-inline bool stage_fail(const char* tag, const char* stage, const char* what) {
-    fprintf(stderr, "[%s] stage '%s': %s: refused\n", tag, stage ? stage : "(null)", what);
-    return false;
-}
-
-// A pointer the stage needs, aligned to `align` bytes (16: a vector the kernels access in 16-byte pairs; 8: doubles one at a time).
-inline bool stage_pointer(const char* tag, const char* stage, const char* name, const void* p, int align) {
-    char what[64];
-    if (p == nullptr) {
-        snprintf(what, sizeof what, "%s is null", name);
-        return stage_fail(tag, stage, what);
-    }
-    if (((uintptr_t)p & (uintptr_t)(align - 1)) != 0) {
-        snprintf(what, sizeof what, "%s is not %d-byte aligned", name, align);
-        return stage_fail(tag, stage, what);
-    }
-    return true;
 }
 
 }  // namespace spmv_amd

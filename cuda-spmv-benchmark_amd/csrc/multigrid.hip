@@ -6,7 +6,7 @@
 // the fine points (2I + a, 2J + b), a, b in {0, 1}, that exist; coarsening stops at the first grid of at most 8 (or at max_levels).
 // A_c = P^T A P with P piecewise constant is again a complete 5-point CSR (coarsen_kernel), so every level runs the library's own
 // stencil kernels through a Stencil5Plan of its own: launch_stencil5_cheb_step where the plan is row-lds, launch_stencil5_spmv and
-// pcg.hip's streaming step elsewhere. Per level: dinv by pcg.hip's diagonal pass, lambda_max by its Gershgorin kernel, the smoother =
+// precond.hip's streaming step elsewhere. Per level: dinv by precond.hip's diagonal pass, lambda_max by its Gershgorin kernel, the smoother =
 // section 14's Chebyshev application of degree nu on [lambda_max / 4, lambda_max]; the coarsest level is solved by degree 8 on
 // [lambda_max / 30, lambda_max] from a zero guess.
 //
@@ -23,7 +23,7 @@
 //
 // The same hierarchy, cycle and creator serve the 3-D operator stencil7-csr (spmv_amd_precond_create_multigrid3d, DESIGN.md section
 // 17): a level carries its dimension; a 3-D level is a complete 7-point CSR made by 2 x 2 x 2 aggregation, its three launches are
-// multigrid3d.hip's, and it smooths with launch_stencil7_spmv on a Stencil7Plan of its own + pcg.hip's streaming step.
+// multigrid3d.hip's, and it smooths with launch_stencil7_spmv on a Stencil7Plan of its own + precond.hip's streaming step.
 #include <limits.h>
 #include <math.h>
 #include <stdint.h>

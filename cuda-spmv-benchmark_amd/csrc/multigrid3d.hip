@@ -1,6 +1,6 @@
 // multigrid3d.hip -- the device side of kind "multigrid" on the 3-D operator "stencil7-csr" (include/spmv_amd/api.h
 // states the algebra down to the order of every sum): the three launches a 3-D level adds to multigrid.hip's cycle. The hierarchy, the
-// cycle and the creator are multigrid.hip's; smoothing on a level is launch_stencil7_spmv + pcg.hip's streaming step.
+// cycle and the creator are multigrid.hip's; smoothing on a level is launch_stencil7_spmv + precond.hip's streaming step.
 //
 // Levels: n_{l+1} = ceil(n_l / 2); aggregate (K, I, J) = the fine points (2K + c, 2I + a, 2J + b), c, a, b in {0, 1}, that exist;
 // A_c = P^T A P with P piecewise constant is again a complete 7-point CSR [D,N,W,C,E,S,U].

@@ -53,7 +53,7 @@ struct CsrBackedOperator {
     double tuning[4] = {0, 0, 0, 0};  // {rule, kept, ms with the rule, ms kept}
     int y_candidates = 1;      // output placement: candidates timed for dY, and what the choice was worth (device_runtime.hpp)
     double y_gain = 1.0;
-    unsigned long long generation = 0;  // bumped by every init and free (drop()): what a preconditioner was made from (pcg.hip)
+    unsigned long long generation = 0;  // bumped by every init and free (drop()): what a preconditioner was made from (precond.hip)
     void alloc_vectors() {
         dX = device_alloc<double>((size_t)cols);
         dY = nullptr;  // placed by place_output() once the kernel that writes it is known
@@ -637,7 +637,7 @@ MultiOperand multi_operand_of(const SpmvOperator* op) {
     return o;
 }
 
-// Where a Jacobi preconditioner reads the diagonal (pcg.hip): the operator's own device storage, no copy.
+// Where a Jacobi preconditioner reads the diagonal (precond.hip): the operator's own device storage, no copy.
 DiagonalSource diagonal_source_of(const SpmvOperator* op) {
     DiagonalSource d;
     const OwnOperator o = own_operator_of(op);

@@ -1,5 +1,7 @@
 // pcg.hip -- preconditioned CG over any SpmvOperator: kinds "none" and "jacobi" (DESIGN.md section 13), a Chebyshev polynomial in
-// D^-1 A (section 14) and one multigrid V-cycle (multigrid.hip, section 15: stencil5-csr; section 17: stencil7-csr).
+// D^-1 A (section 14) and one multigrid V-cycle (multigrid.hip, section 15: stencil5-csr; section 17: stencil7-csr). The solver only:
+// the preconditioner record, its creators and its application on its own are precond.hip's; the host side this loop shares with
+// bicgstab.hip and gcr.hip is single_solve.hpp's.
 //
 // One loop, spmv_amd_pcg_solve_device: the algebra of cg_solve_device with z = M^-1 r, the same stopping rule (true residual
 // ||r_k|| / ||r_0|| < tol, strict, the converging iteration counted), statistics and timer rule (solve_common.hpp has those,
@@ -24,7 +26,7 @@
 //   step j:  w = A z ; t = fma(-1, w, r) ; u = dinv t ; d = fma(g_j, u, h_j d) ; z = z + d
 //   r -= alpha Ap with term 0 in registers, partials of r.r | sum of r.r + verdict, which also lands in a device flag |
 //   k steps, each testing that flag before it works: the converging iteration streams nothing | sum of r.z + beta
-// A step is cheb_step (declared in precond.hpp), the only place that chooses its form from a ChebSpmv: on a row-lds stencil plan ONE
+// A step is cheb_step (precond.hip, declared in precond.hpp), the only place that chooses its form from a ChebSpmv: on a row-lds stencil plan ONE
 // launch (spmv_kernels.hip, kMode 3: A z never leaves the registers, z' goes to a second vector; 144 + 88 k bytes per interior row and
 // iteration), on any other stencil plan -- 2-D, or a 3-D multigrid level's Stencil7Plan -- the SpMV behind the flag +
 // cheb_step_kernel, else run_device + cheb_step_kernel (112 per step). The loop calls it timed, with the flag and the step counter; spmv_amd_precond_apply_device untimed without a flag; the
@@ -33,9 +35,6 @@
 // "multigrid" (mg_first, mg_next): z = M^-1 r is one V-cycle on the preconditioner's own levels:
 //   r -= alpha Ap with the r.r partials (the "none" r update) | sum of r.r + verdict | the host reads the verdict: the converging
 //   iteration runs no cycle | V-cycle | sum of r.z + beta
-//
-// Also here: the set-up passes (diagonal, Gershgorin bound), the creators with their one operator check (creation_source) and the one
-// sentence about a bad diagonal row (inverse_diagonal); multigrid.hip reaches them through precond.hpp.
 #include <limits.h>
 #include <math.h>
 #include <stddef.h>
@@ -46,10 +45,9 @@
 
 #include "device_runtime.hpp"
 #include "multi_rhs.hpp"
-#include "multi_solve.hpp"
 #include "precond.hpp"
 #include "reduce_device.hpp"
-#include "solve_common.hpp"
+#include "single_solve.hpp"
 #include "stream_device.hpp"
 #ifdef SPMV_AMD_LAB
 #include "spmv_amd/lab.h"
@@ -58,56 +56,6 @@
 using namespace spmv_amd;
 
 namespace {
-
-constexpr hipStream_t kStream = nullptr;  // default stream, shared with the operators
-constexpr int kWave = 64;                 // the streaming kernels: one wavefront per workgroup, one 16-byte pair per lane
-
-// Device scalars of one preconditioned solve.
-struct PcgScalars {
-    double rz;        // r.z of the current residual
-    double pAp, alpha, beta;
-    double b_norm;    // ||r0||
-    double residual;  // ||r_k||
-    int iterations;
-    int converged;    // stopping test met
-    int breakdown;    // pAp or r.z' zero or not finite: stopped, not converged
-    int skip_update;  // this iteration's pAp broke down: r and x stay as they are
-};
-
-__device__ __forceinline__ bool usable(double v) { return v != 0.0 && isfinite(v); }
-
-// ---- diagonal extraction: d_i = sum of row i's entries in column i, CSR order, from 0.0; dinv_i = 1.0 / d_i ----
-// Validity in the same pass: d_i finite, non-zero and of d_0's sign, else atomicMin(bad_row, i).
-
-__device__ __forceinline__ double csr_diagonal(const SlabCsr& m, int r) {
-    double d = 0.0;
-    for (int j = m.row_ptr[r]; j < m.row_ptr[r + 1]; ++j)
-        if (m.col_idx[j] == r) d += m.values[j];
-    return d;
-}
-__device__ __forceinline__ double ell_diagonal(const int* __restrict__ idx, const double* __restrict__ val, int rows, int width, int r) {
-    double d = 0.0;
-    for (int k = 0; k < width; ++k)
-        if (idx[(long long)k * rows + r] == r) d += val[(long long)k * rows + r];
-    return d;
-}
-
-// src: 0 = CSR, 1 = ELL planes, 2 = a plain array of n values
-__device__ __forceinline__ double diagonal_at(int src, const SlabCsr& m, const int* idx, const double* val, int width, int n, int r) {
-    if (src == 0) return csr_diagonal(m, r);
-    if (src == 1) return ell_diagonal(idx, val, n, width, r);
-    return 0.0 + val[r];
-}
-
-__global__ __launch_bounds__(256) void diagonal_inverse_kernel(int src, SlabCsr m, const int* __restrict__ idx, const double* __restrict__ val,
-                                                               int width, int n, double* __restrict__ dinv, int* __restrict__ bad_row) {
-    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (r >= n) return;
-    const double d0 = diagonal_at(src, m, idx, val, width, n, 0);  // row 0: a few entries, the same cached lines for every lane
-    const double d = r == 0 ? d0 : diagonal_at(src, m, idx, val, width, n, r);
-    if (!usable(d) || (d > 0.0) != (d0 > 0.0)) atomicMin(bad_row, r);
-    dinv[r] = 1.0 / d;
-}
 
 // ---- the loop's streaming kernels (16-byte accesses, one pair per lane; the odd last row by lane 0 of workgroup 0) ----
 
@@ -212,40 +160,7 @@ __global__ __launch_bounds__(kWave) void pcg_update_xp_kernel(size_t n, const Pc
     }
 }
 
-// ---- kind "chebyshev": lambda_max, term 0 fused into the r update, the streaming step ----
-
-// max_i sum_j |a_ij| sqrt(|dinv_i| |dinv_j|): Gershgorin's bound on D^-1/2 A D^-1/2, which has the spectrum of D^-1 A and, unlike the
-// plain row sum of D^-1 A, does not move under a symmetric diagonal scaling of A. Row i is summed in storage (CSR) order from 0.0, one
-// rounding per operation. The maximum of non-negative doubles is the maximum of their bit patterns as unsigned integers: a wave tree,
-// then one 64-bit unsigned atomic max per wave -- independent of the order. A NaN row wins and is refused on the host.
-__global__ __launch_bounds__(256) void gershgorin_kernel(int src, SlabCsr m, const int* __restrict__ idx, const double* __restrict__ val,
-                                                         int width, int n, const double* __restrict__ dinv, unsigned long long* __restrict__ out) {
-    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    double sum = 0.0;
-    if (r < n) {
-        const double di = fabs(dinv[r]);
-        if (src == 0) {
-            for (int j = m.row_ptr[r]; j < m.row_ptr[r + 1]; ++j) {
-                const double w = sqrt(di * fabs(dinv[m.col_idx[j]]));
-                sum = sum + fabs(m.values[j]) * w;
-            }
-        } else {
-            for (int k = 0; k < width; ++k) {
-                const int c = idx[(long long)k * n + r];
-                if (c < 0) continue;
-                const double w = sqrt(di * fabs(dinv[c]));
-                sum = sum + fabs(val[(long long)k * n + r]) * w;
-            }
-        }
-    }
-    unsigned long long bits = (unsigned long long)__double_as_longlong(sum);  // sum >= +0.0, or NaN
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long other = (unsigned long long)__shfl_down((long long)bits, off);
-        bits = other > bits ? other : bits;
-    }
-    if ((threadIdx.x & 63) == 0) atomicMax(out, bits);
-}
+// ---- kind "chebyshev": term 0 fused into the r update ----
 
 // The residual of the stage and term 0 of the polynomial from it, in registers. kFrom 0: r = b - Ap (the initial residual, bv = b);
 // 1: r = fma(-alpha, Ap, r) unless this iteration's pAp broke down; 2: r as it is (spmv_amd_precond_apply_device: r is only read).
@@ -308,74 +223,6 @@ __global__ __launch_bounds__(kWave) void cheb_term0_kernel(size_t n, const PcgSc
         if (threadIdx.x == 0) partials[count + blockIdx.x] = rz;
     }
 }
-
-// One step behind a SpMV that wrote w = A z: t = fma(-1, w, r) ; u = dinv t ; d = fma(g, u, h d) ; z = z + d, d and z in place.
-// Nothing is read once *stop != 0 (the iteration's verdict; null: no test). last: the partials of r.z at partials[blk].
-__global__ __launch_bounds__(kWave) void cheb_step_kernel(size_t n, const int* __restrict__ stop, const double* __restrict__ w,
-                                                          const double* __restrict__ r, const double* __restrict__ dinv, double g, double h,
-                                                          double* __restrict__ d, double* __restrict__ z, int last, double* __restrict__ partials,
-                                                          int* __restrict__ work_count) {
-    if (stop != nullptr && *stop != 0) return;
-    const size_t i = (size_t)blockIdx.x * kWave + threadIdx.x;
-    double rz = 0.0;
-    if (i < (n >> 1)) {
-        const d2 wv = load_once(w, i), rv = load_once(r, i), iv = load_once(dinv, i);
-        d2 dd = load_once(d, i), zv = reinterpret_cast<const d2*>(z)[i];
-        dd.x = fma(g, iv.x * fma(-1.0, wv.x, rv.x), h * dd.x);
-        dd.y = fma(g, iv.y * fma(-1.0, wv.y, rv.y), h * dd.y);
-        zv.x = zv.x + dd.x;
-        zv.y = zv.y + dd.y;
-        store_once(d, i, dd);
-        reinterpret_cast<d2*>(z)[i] = zv;  // plain: the next SpMV reads it
-        if (last) rz = fma(rv.x, zv.x, rz), rz = fma(rv.y, zv.y, rz);
-    }
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-        const double rl = r[n - 1];
-        const double dl = fma(g, dinv[n - 1] * fma(-1.0, w[n - 1], rl), h * d[n - 1]);
-        const double zl = z[n - 1] + dl;
-        d[n - 1] = dl, z[n - 1] = zl;
-        if (last) rz = fma(rl, zl, rz);
-    }
-    if (work_count != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *work_count += 1;  // one thread per launch; launches are ordered
-    if (last) {
-        rz = wave_sum(rz);
-        if (threadIdx.x == 0) partials[blockIdx.x] = rz;
-    }
-}
-
-// z = dinv r ("jacobi") or z = r ("none") with the partials of r.z: those kinds through spmv_amd_precond_apply_device.
-template <bool kJac>
-__global__ __launch_bounds__(kWave) void precond_apply_kernel(size_t n, const double* __restrict__ r, const double* __restrict__ dinv,
-                                                              double* __restrict__ z, double* __restrict__ partials) {
-    const size_t i = (size_t)blockIdx.x * kWave + threadIdx.x;
-    double rz = 0.0;
-    if (i < (n >> 1)) {
-        const d2 rv = load_once(r, i);
-        d2 zv = rv;
-        if (kJac) {
-            const d2 dv = load_once(dinv, i);
-            zv.x = dv.x * rv.x, zv.y = dv.y * rv.y;
-        }
-        store_once(z, i, zv);
-        rz = fma(rv.x, zv.x, rz), rz = fma(rv.y, zv.y, rz);
-    }
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-        const double rl = r[n - 1];
-        const double zl = kJac ? dinv[n - 1] * rl : rl;
-        z[n - 1] = zl;
-        rz = fma(rl, zl, rz);
-    }
-    rz = wave_sum(rz);
-    if (threadIdx.x == 0) partials[blockIdx.x] = rz;
-}
-
-// The device record of a Chebyshev solve: the scalars every kind keeps, then what only this kind needs. pcg_step's steps 3 to 5 are
-// handed the record's first member and reach the rest through it.
-struct ChebScalars {
-    PcgScalars s;
-    int stop;        // the iteration's verdict (converged or broken down): the steps' skip flag
-    int steps_done;  // step launches that did work
-};
 
 // ---- reductions: NV sums of `count` partials each (value v at partials[v * count ...]) in ONE launch, then the scalar step ----
 // The shape of reduce_device.hpp extended to two values: slice workgroups publish their slice sums of value 0 into the stage's
@@ -444,39 +291,9 @@ __global__ __launch_bounds__(kReduceBlock) void pcg_reduce_kernel(const double* 
     __shared__ double sh[kReduceBlock];
     __shared__ int s_last;
     double total[2] = {0.0, 0.0};
-    if (blocks > 1) {
-        const ReduceStage stage = reduce_stage_of(stage_base);
-        unsigned long long* const slot[2] = {stage.sums, stage.extra};
-        const int lo = (int)blockIdx.x * slice, hi = min(lo + slice, count);
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            block_tree(strided_sum(partials + (long long)v * count, lo, hi), sh);
-            if (threadIdx.x == 0) publish(slot[v] + blockIdx.x, sh[0]);
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) {
-            const unsigned drawn = __hip_atomic_fetch_add(stage.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_last = drawn == (unsigned)(blocks - 1) ? 1 : 0;
-            if (s_last) __hip_atomic_store(stage.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        if (s_last == 0) return;
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            double acc = 0.0;
-            for (int i = (int)threadIdx.x; i < blocks; i += kReduceBlock) acc += published(slot[v] + i);
-            block_tree(acc, sh);
-            total[v] = sh[0];
-            __syncthreads();
-        }
-    } else {
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            block_tree(strided_sum(partials + (long long)v * count, 0, count), sh);
-            total[v] = sh[0];
-            __syncthreads();
-        }
-    }
+    const ReduceStage stage = reduce_stage_of(stage_base);
+    const auto slot_of = [&](int v) { return v == 0 ? stage.sums : stage.extra; };
+    if (!sum_values_last_block<NV>(partials, count, NV, slice, blocks, stage.ticket, slot_of, sh, &s_last, total)) return;
     if (threadIdx.x == 0) pcg_step(s, which, total, tol, hist, hist_cap);
 }
 
@@ -484,34 +301,20 @@ __global__ __launch_bounds__(kReduceBlock) void pcg_reduce_kernel(const double* 
 // kernels on caller data, tests/test_pcg_stages_gpu.py). dinv is not read by the "none" instantiations. ----
 
 void launch_pcg_init(bool jac, size_t n, const double* b, const double* Ap, const double* dinv, double* r, double* p, double* partials) {
-    const dim3 grid(stream_grid(n)), block(kWave);
-    const int count = (int)grid.x;
-    if (jac)
-        hipLaunchKernelGGL(pcg_init_kernel<true>, grid, block, 0, kStream, n, b, Ap, dinv, r, p, partials, count);
-    else
-        hipLaunchKernelGGL(pcg_init_kernel<false>, grid, block, 0, kStream, n, b, Ap, nullptr, r, p, partials, count);
+    SPMV_AMD_STREAM_LAUNCH(pcg_init_kernel, jac, n, b, Ap, dinv, r, p, partials, count);
 }
-
 void launch_pcg_update_r(bool jac, size_t n, const PcgScalars* s, const double* Ap, const double* dinv, double* r, double* partials) {
-    const dim3 grid(stream_grid(n)), block(kWave);
-    const int count = (int)grid.x;
-    if (jac)
-        hipLaunchKernelGGL(pcg_update_r_kernel<true>, grid, block, 0, kStream, n, s, Ap, dinv, r, partials, count);
-    else
-        hipLaunchKernelGGL(pcg_update_r_kernel<false>, grid, block, 0, kStream, n, s, Ap, nullptr, r, partials, count);
+    SPMV_AMD_STREAM_LAUNCH(pcg_update_r_kernel, jac, n, s, Ap, dinv, r, partials, count);
+}
+void launch_pcg_update_xp(bool jac, size_t n, const PcgScalars* s, const double* r, const double* dinv, double* p, double* x) {
+    SPMV_AMD_STREAM_LAUNCH(pcg_update_xp_kernel, jac, n, s, r, dinv, p, x);
 }
 
-void launch_pcg_update_xp(bool jac, size_t n, const PcgScalars* s, const double* r, const double* dinv, double* p, double* x) {
-    const dim3 grid(stream_grid(n)), block(kWave);
-    if (jac)
-        hipLaunchKernelGGL(pcg_update_xp_kernel<true>, grid, block, 0, kStream, n, s, r, dinv, p, x);
-    else
-        hipLaunchKernelGGL(pcg_update_xp_kernel<false>, grid, block, 0, kStream, n, s, r, nullptr, p, x);
-}
+}  // namespace
 
 // nv sums of `count` partials each and the scalar step `which` (0: two sums, 1: one, 2: two)
-void launch_pcg_reduce(const double* partials, int count, int nv, int which, double* stage, PcgScalars* s, double tol, double* hist,
-                       int hist_cap) {
+void spmv_amd::launch_pcg_reduce(const double* partials, int count, int nv, int which, double* stage, PcgScalars* s, double tol,
+                                 double* hist, int hist_cap) {
     int slice = 0, blocks = 0;
     reduce_geometry(count, &slice, &blocks);
     if (nv == 1)
@@ -522,6 +325,8 @@ void launch_pcg_reduce(const double* partials, int count, int nv, int which, dou
                            s, which, tol, hist, hist_cap);
 }
 
+namespace {
+
 // ---- kind "chebyshev": the launches ----
 
 template <int kFrom>
@@ -529,56 +334,6 @@ void launch_cheb_term0(size_t n, const PcgScalars* s, const double* b, const dou
                        double* z, bool last, double* partials) {
     const dim3 grid(stream_grid(n)), block(kWave);
     hipLaunchKernelGGL(cheb_term0_kernel<kFrom>, grid, block, 0, kStream, n, s, b, Ap, dinv, c0, r, d, z, last ? 1 : 0, partials, (int)grid.x);
-}
-
-}  // namespace
-
-// The runner of a Chebyshev step (precond.hpp, ChebRun): the loop, spmv_amd_precond_apply_device and the multigrid cycle call it.
-bool spmv_amd::cheb_step(ChebRun& c, double g, double h, bool last) {
-    if (c.a.partials > 0) {  // a row-lds plan: the whole step inside the SpMV launch, z' in the other vector
-        ChebStep step;
-        step.r = c.r, step.dinv = c.dinv, step.d = c.d, step.z_out = c.aux, step.g = g, step.h = h, step.last = last ? 1 : 0;
-        step.work_count = c.work_count;
-        stage_run(c.T, &StageTimers::t_spmv, [&] { (void)launch_stencil5_cheb_step(*c.a.view, *c.a.plan, c.z, step, c.partials, c.stop, kStream); });
-        double* const t = c.z;
-        c.z = c.aux, c.aux = t;
-        if (last) c.rz_partials = c.partials, c.rz_count = c.a.partials;
-        return true;
-    }
-    bool ok = true;
-    stage_run(c.T, &StageTimers::t_spmv, [&] {
-        if (c.a.csr) {
-            launch_csr_spmv(*c.a.view, c.z, c.aux, 1.0, c.a.csr_variant, kStream);
-        } else if (c.a.plan7 != nullptr) {
-            (void)launch_stencil7_spmv(*c.a.view, *c.a.plan7, c.z, c.aux, 1.0, nullptr, c.stop, false, kStream);
-        } else if (c.a.plan != nullptr) {
-            (void)launch_stencil5_spmv(*c.a.view, *c.a.plan, c.z, c.aux, 1.0, nullptr, c.stop, false, kStream);
-        } else if (c.a.op->run_device(c.z, c.aux) != 0) {
-            fprintf(stderr, "[PCG] operator '%s': run_device failed\n", c.a.op->name);
-            ok = false;
-        }
-    });
-    if (!ok) return false;
-    stage_run(c.T, &StageTimers::t_blas, [&] {
-        hipLaunchKernelGGL(cheb_step_kernel, dim3(stream_grid(c.n)), dim3(kWave), 0, kStream, c.n, c.stop, c.aux, c.r, c.dinv, g, h, c.d, c.z,
-                           last ? 1 : 0, c.partials, c.work_count);
-    });
-    if (last) c.rz_partials = c.partials, c.rz_count = (int)stream_grid(c.n);
-    return true;
-}
-
-bool spmv_amd::cheb_steps(ChebRun& c, int degree, const double* coef, bool report) {
-    for (int k = 1; k <= degree; ++k)
-        if (!cheb_step(c, coef[2 * k], coef[2 * k - 1], report && k == degree)) return false;
-    return true;
-}
-
-namespace {
-
-// Steps 1 .. degree of m's polynomial behind a term 0 that left d and z in c -- and, at degree 0, the r.z partials behind its r.r ones.
-bool cheb_after_term0(const SpmvAmdPrecond* m, ChebRun& c) {
-    c.rz_partials = c.partials + stream_grid(c.n), c.rz_count = (int)stream_grid(c.n);
-    return cheb_steps(c, m->degree, m->coef, true);
 }
 
 // ---- workspace: kept between calls (like cg_solve_device's), released with it ----
@@ -664,309 +419,16 @@ bool ensure_cheb_workspace(int n) {
     return true;
 }
 
-int kind_of(const char* kind) {
-    if (kind == nullptr) return -1;
-    if (!strcmp(kind, "none")) return kNone;
-    if (!strcmp(kind, "jacobi")) return kJacobi;
-    return -1;
-}
-
-// The diagonal pass over a diagonal source: dinv on the device, or null -- no device memory, or a row at fault: the first one is named on
-// stderr behind `who` (the only place of that sentence) and stored in *bad_row where that is not null.
-double* inverse_diagonal(int src, const SlabCsr& m, const int* idx, const double* val, int width, int n, const char* who, int* bad_row) {
-    double* dinv = device_try_alloc<double>((size_t)n);
-    int* d_bad = device_try_alloc<int>(1);
-    if (dinv == nullptr || d_bad == nullptr) {
-        device_release(dinv);
-        device_release(d_bad);
-        fail("no device memory for the inverse diagonal");
-        return nullptr;
-    }
-    const int none = INT_MAX;
-    upload(d_bad, &none, 1);
-    hipLaunchKernelGGL(diagonal_inverse_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, kStream, src, m, idx, val, width, n, dinv, d_bad);
-    HIP_CHECK(hipGetLastError());
-    int bad = none;
-    download(&bad, d_bad, 1);  // synchronises
-    device_release(d_bad);
-    if (bad != none) {
-        device_release(dinv);
-        if (bad_row != nullptr) *bad_row = bad;
-        fprintf(stderr, "[PCG] %s: the diagonal entry of row %d is zero, not finite or of the other sign than row 0's: refused\n", who, bad);
-        return nullptr;
-    }
-    return dinv;
-}
-
-// The validity pass over a diagonal source; returns the preconditioner or null (*bad_row set when a row is at fault).
-SpmvAmdPrecond* make_jacobi(int src, const SlabCsr& m, const int* idx, const double* val, int width, int n, int* bad_row) {
-    double* dinv = inverse_diagonal(src, m, idx, val, width, n, "jacobi", bad_row);
-    if (dinv == nullptr) return nullptr;
-    SpmvAmdPrecond* pm = new SpmvAmdPrecond();
-    pm->kind = kJacobi;
-    pm->n = n;
-    pm->dinv = dinv;
-    return pm;
-}
-
-// lambda_max of D^-1 A by gershgorin_kernel
-double gershgorin_bound(int src, const SlabCsr& m, const int* idx, const double* val, int width, int rows, const double* dinv) {
-    unsigned long long* d_bits = device_alloc<unsigned long long>(1);
-    const unsigned long long zero = 0;
-    upload(d_bits, &zero, 1);
-    hipLaunchKernelGGL(gershgorin_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, kStream, src, m, idx, val, width, rows, dinv, d_bits);
-    HIP_CHECK(hipGetLastError());
-    unsigned long long bits = 0;
-    download(&bits, d_bits, 1);  // synchronises
-    device_release(d_bits);
-    double bound = 0.0;
-    memcpy(&bound, &bits, sizeof bound);
-    return bound;
-}
-
 }  // namespace
 
 namespace spmv_amd {
 void release_pcg_workspace_locked() { g_pcg.release(); }
 }  // namespace spmv_amd
 
-extern "C" SpmvAmdPrecond* spmv_amd_precond_create(SpmvOperator* op, const char* kind, int* bad_row) {
-    if (bad_row != nullptr) *bad_row = -1;
-    const int k = kind_of(kind);
-    if (k < 0) {
-        fprintf(stderr, "[PCG] unknown preconditioner kind '%s' (none, jacobi)\n", kind ? kind : "(null)");
-        return nullptr;
-    }
-    if (op == nullptr) return fail("null operator"), nullptr;
-    DiagonalSource d;
-    if (!creation_source(op, "", "one of this library's: pass its diagonal to spmv_amd_precond_create_from_diagonal", 0, &d)) return nullptr;
-    SpmvAmdPrecond* pm = nullptr;
-    if (k == kNone) {
-        pm = new SpmvAmdPrecond();
-        pm->kind = kNone;
-        pm->n = d.rows;
-    } else {
-        pm = make_jacobi(d.kind == DiagonalSource::Csr ? 0 : 1, d.csr, d.idx, d.val, d.width, d.rows, bad_row);
-        if (pm == nullptr) return nullptr;
-    }
-    pm->owner = d.owner;
-    pm->generation = d.generation;
-    return pm;
-}
-
-extern "C" SpmvAmdPrecond* spmv_amd_precond_create_from_diagonal(const double* d_diag, int n, int* bad_row) {
-    if (bad_row != nullptr) *bad_row = -1;
-    if (d_diag == nullptr) return fail("null diagonal"), nullptr;
-    if (n < 1) return fail("n < 1"), nullptr;
-    return make_jacobi(2, SlabCsr{}, nullptr, d_diag, 0, n, bad_row);
-}
-
-// The coefficients of the degree-k Chebyshev polynomial on [lmin, lmax], in the order and with the operations api.h states (the file is
-// compiled with -ffp-contract=off: one rounding per operation).
-void spmv_amd::chebyshev_coefficients(int degree, double lmin, double lmax, double* coef) {
-    const double theta = 0.5 * (lmax + lmin);
-    const double delta = 0.5 * (lmax - lmin);
-    const double sigma = theta / delta;
-    coef[0] = 1.0 / theta;
-    double rho = 1.0 / sigma;
-    for (int k = 1; k <= degree; ++k) {
-        const double rho_next = 1.0 / (2.0 * sigma - rho);
-        coef[2 * k - 1] = rho_next * rho;
-        coef[2 * k] = 2.0 * rho_next / delta;
-        rho = rho_next;
-    }
-}
-
-// pcg.hip's set-up passes, the creators' operator check and term 0 for multigrid.hip (precond.hpp)
-namespace spmv_amd {
-double* inverse_diagonal_of_csr(const SlabCsr& m, int n, const char* who, int* bad_row) {
-    return inverse_diagonal(0, m, nullptr, nullptr, 0, n, who, bad_row);
-}
-double gershgorin_of_csr(const SlabCsr& m, int n, const double* dinv) { return gershgorin_bound(0, m, nullptr, nullptr, 0, n, dinv); }
-void launch_cheb_term0_apply(size_t n, const double* r, const double* dinv, double c0, double* d, double* z) {
-    launch_cheb_term0<2>(n, nullptr, nullptr, nullptr, dinv, c0, const_cast<double*>(r), d, z, false, nullptr);
-}
-bool creation_source(const SpmvOperator* op, const char* label, const char* not_ours, int stencil_dim, DiagonalSource* d) {
-    *d = diagonal_source_of(op);
-    bool ours = d->owner != nullptr;
-    if (stencil_dim == 2)
-        ours = ours && d->kind == DiagonalSource::Csr && op->name != nullptr &&
-               (strcmp(op->name, "stencil5-csr") == 0 || strcmp(op->name, "stencil5-halo-mgpu") == 0);
-    else if (stencil_dim == 3)
-        ours = ours && d->kind == DiagonalSource::Csr && op->name != nullptr && strcmp(op->name, "stencil7-csr") == 0;
-    if (!ours) {
-        fprintf(stderr, "[PCG] %soperator '%s' is not %s\n", label, op->name ? op->name : "?", not_ours);
-        return false;
-    }
-    if (!d->ready) {
-        fprintf(stderr, "[PCG] operator '%s' used before init\n", op->name);
-        return false;
-    }
-    if (stencil_dim == 0 && d->rows != d->cols) {  // a stencil-only creator has a stricter test of its own behind this
-        fprintf(stderr, "[PCG] operator '%s' holds a %d x %d matrix: a square one is required\n", op->name, d->rows, d->cols);
-        return false;
-    }
-    return true;
-}
-}  // namespace spmv_amd
-
-// What every entry point that takes (op, m) checks of the pair before any HIP call; d: the operator's storage view (precond.hpp).
-bool spmv_amd::precond_matches(const SpmvOperator* op, const SpmvAmdPrecond* m, const DiagonalSource& d) {
-    if (m->owner == nullptr) return true;  // made from a caller's diagonal: no operator to belong to
-    if (m->owner != d.owner) return fail("the preconditioner was made from another operator: refused");
-    if (m->generation != d.generation)
-        return fail("the preconditioner was made before the operator was last initialised or freed: refused");
-    if (!d.ready) {
-        fprintf(stderr, "[PCG] operator '%s' used before init\n", op->name);
-        return false;
-    }
-    return true;
-}
-
-extern "C" SpmvAmdPrecond* spmv_amd_precond_create_chebyshev(SpmvOperator* op, int degree, double lambda_min, double lambda_max, int* bad_row) {
-    // argument checks: all before the first HIP call
-    if (bad_row != nullptr) *bad_row = -1;
-    if (op == nullptr) return fail("null operator"), nullptr;
-    if (degree < 0 || degree > kChebMaxDegree) {
-        fprintf(stderr, "[PCG] chebyshev: degree %d is outside 0..%d: refused\n", degree, kChebMaxDegree);
-        return nullptr;
-    }
-    if (!isfinite(lambda_min) || !isfinite(lambda_max)) return fail("chebyshev: a bound that is not finite: refused"), nullptr;
-    if (lambda_min > 0.0 && lambda_max > 0.0 && !(lambda_min < lambda_max)) return fail("chebyshev: lambda_min >= lambda_max: refused"), nullptr;
-    DiagonalSource d;
-    if (!creation_source(op, "chebyshev: ", "one of this library's: refused", 0, &d)) return nullptr;
-    const int src = d.kind == DiagonalSource::Csr ? 0 : 1;
-    SpmvAmdPrecond* pm = make_jacobi(src, d.csr, d.idx, d.val, d.width, d.rows, bad_row);
-    if (pm == nullptr) return nullptr;
-    pm->kind = kChebyshev;
-    pm->degree = degree;
-    pm->owner = d.owner;
-    pm->generation = d.generation;
-    double lmax = lambda_max;
-    if (!(lmax > 0.0)) {
-        lmax = gershgorin_bound(src, d.csr, d.idx, d.val, d.width, d.rows, pm->dinv);
-    }
-    const double lmin = lambda_min > 0.0 ? lambda_min : lmax / 30.0;
-    if (!isfinite(lmax) || !isfinite(lmin) || !(lmin > 0.0) || !(lmin < lmax)) {
-        fprintf(stderr, "[PCG] chebyshev: the interval [%g, %g] is not 0 < lambda_min < lambda_max, both finite: refused\n", lmin, lmax);
-        spmv_amd_precond_destroy(pm);
-        return nullptr;
-    }
-    pm->lambda_min = lmin, pm->lambda_max = lmax;
-    chebyshev_coefficients(degree, lmin, lmax, pm->coef);
-    return pm;
-}
-
-extern "C" int spmv_amd_precond_chebyshev_info(const SpmvAmdPrecond* m, int* degree, double* lambda_min, double* lambda_max,
-                                               double* coefficients, int cap) {
-    if (m == nullptr || m->kind != kChebyshev) return 0;
-    if (degree != nullptr) *degree = m->degree;
-    if (lambda_min != nullptr) *lambda_min = m->lambda_min;
-    if (lambda_max != nullptr) *lambda_max = m->lambda_max;
-    const int count = 1 + 2 * m->degree;
-    for (int i = 0; i < count && i < cap && coefficients != nullptr; ++i) coefficients[i] = m->coef[i];
-    return count;
-}
-
-extern "C" int spmv_amd_precond_apply_device(SpmvOperator* op, const SpmvAmdPrecond* m, const double* d_r, double* d_z, double* rz) {
-    // argument checks: all before the first HIP call
-    if (op == nullptr || m == nullptr || d_r == nullptr || d_z == nullptr) return fail("null argument"), 1;
-    if ((((uintptr_t)d_r) & 15) != 0 || (((uintptr_t)d_z) & 15) != 0) return fail("apply: a vector is not 16-byte aligned: refused"), 1;
-    const size_t n = (size_t)m->n;
-    {
-        const uintptr_t a = (uintptr_t)d_r, b = (uintptr_t)d_z, bytes = n * sizeof(double);
-        if (a < b + bytes && b < a + bytes) return fail("apply: d_z overlaps d_r: refused"), 1;
-    }
-    const DiagonalSource d = diagonal_source_of(op);
-    if (!precond_matches(op, m, d)) return 1;
-    const bool jac = m->kind == kJacobi, cheb = m->kind == kChebyshev, mg = m->kind == kMultigrid;  // which application runs below
-    if ((cheb || mg) && (op->run_device == nullptr || d.owner == nullptr || d.rows != m->n || d.cols != m->n))
-        return fail("apply: the operator is not the initialised square one the preconditioner was made from: refused"), 1;
-
-    CgWorkspaceScope scope;
-    const int vec_count = (int)stream_grid(n);
-    ChebRun c;  // kind "chebyshev": the application on temporaries of this call
-    if (cheb) c.a = cheb_spmv_of(op);
-    const long long slots = 2LL * vec_count > c.a.partials ? 2LL * vec_count : (long long)c.a.partials;
-    double* partials = device_try_alloc<double>((size_t)slots);
-    ChebScalars* cs = device_try_alloc<ChebScalars>(1);
-    double* stage = reduce_scratch_alloc();
-    double *cd = nullptr, *cz2 = nullptr, *cw = nullptr;
-    const bool fused = c.a.partials > 0;
-    bool ok = partials != nullptr && cs != nullptr;
-    if (ok && cheb) {
-        cd = device_try_alloc<double>(n);
-        if (m->degree > 0) (fused ? cz2 : cw) = device_try_alloc<double>(n);
-        ok = cd != nullptr && (m->degree == 0 || cz2 != nullptr || cw != nullptr);
-    }
-    int rc = 0;
-    if (!ok) {
-        rc = 1;
-        fail("apply: the work vectors could not be allocated: refused");
-    } else {
-        HIP_CHECK(hipMemsetAsync(cs, 0, sizeof(ChebScalars), kStream));
-        Applied out;  // null z: refused
-        if (mg) {
-            out = mg_cycle(m->mg, d_r, nullptr);
-            HIP_CHECK(hipMemcpyAsync(d_z, out.z, n * sizeof(double), hipMemcpyDeviceToDevice, kStream));
-        } else if (cheb) {
-            // the fused step alternates between two z vectors: start where an application of this degree ends in d_z
-            c.n = n, c.r = d_r, c.dinv = m->dinv, c.d = cd, c.partials = partials;
-            c.z = fused && (m->degree & 1) ? cz2 : d_z;
-            c.aux = !fused ? cw : c.z == d_z ? cz2 : d_z;
-            launch_cheb_term0<2>(n, &cs->s, nullptr, nullptr, m->dinv, m->coef[0], const_cast<double*>(d_r), cd, c.z, m->degree == 0, partials);
-            if (cheb_after_term0(m, c)) {
-                if (c.z == d_z) out.z = d_z, out.rz_partials = c.rz_partials, out.rz_count = c.rz_count;
-                else fail("apply: internal error, the result is not in d_z");
-            }
-        } else {
-            const dim3 grid((unsigned)vec_count), block(kWave);
-            if (jac) hipLaunchKernelGGL(precond_apply_kernel<true>, grid, block, 0, kStream, n, d_r, m->dinv, d_z, partials);
-            else hipLaunchKernelGGL(precond_apply_kernel<false>, grid, block, 0, kStream, n, d_r, nullptr, d_z, partials);
-            out.z = d_z, out.rz_partials = partials, out.rz_count = vec_count;
-        }
-        if (out.z == nullptr) {
-            rc = 1;
-        } else {
-            launch_pcg_reduce(out.rz_partials, out.rz_count, 1, 5, stage, &cs->s, 0.0, nullptr, 0);
-            HIP_CHECK(hipGetLastError());
-            PcgScalars h{};
-            download(&h, &cs->s, 1);  // synchronises
-            if (rz != nullptr) *rz = h.rz;
-        }
-    }
-    HIP_CHECK(hipDeviceSynchronize());
-    device_release(partials);
-    device_release(cs);
-    device_release(stage);
-    device_release(cd);
-    device_release(cz2);
-    device_release(cw);
-    return rc;
-}
-
-extern "C" void spmv_amd_precond_destroy(SpmvAmdPrecond* m) {
-    if (m == nullptr) return;
-    mg_destroy(m->mg);
-    device_release(m->dinv);
-    delete m;
-}
-
-extern "C" const char* spmv_amd_precond_kind(const SpmvAmdPrecond* m) {
-    if (m == nullptr) return "invalid";
-    return m->kind == kMultigrid ? "multigrid" : m->kind == kChebyshev ? "chebyshev" : m->kind == kJacobi ? "jacobi" : "none";
-}
-
-extern "C" int spmv_amd_precond_inverse_diagonal(const SpmvAmdPrecond* m, double* out, int n) {
-    if (m == nullptr || out == nullptr) return fail("null argument"), 1;
-    if (m->kind == kNone) return fail("kind 'none' has no inverse diagonal"), 1;
-    if (n != m->n) {
-        fprintf(stderr, "[PCG] the preconditioner has %d values, %d asked for\n", m->n, n);
-        return 1;
-    }
-    HIP_CHECK(hipStreamSynchronize(kStream));
-    download(out, m->dinv, (size_t)n);
-    return 0;
+// term 0 for an application on its own (precond.hpp: precond.hip, gcr.hip)
+void spmv_amd::launch_cheb_term0_apply(size_t n, const double* r, const double* dinv, double c0, double* d, double* z, bool last,
+                                       double* partials) {
+    launch_cheb_term0<2>(n, nullptr, nullptr, nullptr, dinv, c0, const_cast<double*>(r), d, z, last, partials);
 }
 
 namespace {
@@ -996,12 +458,7 @@ struct PcgLoop {
     void reduce(int count, int nv, int which) { reduce_at(w.partials, count, nv, which); }
     template <class F>
     void spmv(F&& launch) { T.run(&T.t_spmv, launch); }
-    void run_A(const double* in, double* out) {  // out = A in through the vtable
-        if (op->run_device(in, out) != 0) {
-            fprintf(stderr, "[PCG] operator '%s': run_device failed\n", op->name);
-            failed = true;
-        }
-    }
+    void product(const double* in, double* out) { timed_product("PCG", op, T, in, out, failed); }  // out = A in through the vtable
     // z0 = M^-1 r0 is the first direction
     void first_direction(const double* z0) { HIP_CHECK(hipMemcpyAsync(w.p, z0, n * sizeof(double), hipMemcpyDeviceToDevice, kStream)); }
 };
@@ -1020,7 +477,7 @@ struct PcgKind {
 template <bool kJac>
 void plain_first(PcgLoop& L) {
     PcgWorkspace& w = L.w;
-    L.spmv([&] { L.run_A(w.x, w.Ap); });
+    L.product(w.x, w.Ap);
     L.blas([&] { launch_pcg_init(kJac, L.n, w.b, w.Ap, L.m->dinv, w.r, w.p, w.partials); });
     L.reduce(L.vec_count, 2, 0);
 }
@@ -1046,7 +503,7 @@ void cheb_first(PcgLoop& L) {
     PcgWorkspace& w = L.w;
     HIP_CHECK(hipMemsetAsync(L.record(), 0, sizeof(ChebScalars), kStream));
     L.step_counter = &L.record()->steps_done;
-    L.spmv([&] { L.run_A(w.x, w.Ap); });
+    L.product(w.x, w.Ap);
     L.blas([&] { launch_cheb_term0<0>(L.n, w.s, w.b, w.Ap, L.m->dinv, L.m->coef[0], w.r, w.cd, w.cz, L.m->degree == 0, w.partials); });
     L.reduce(L.vec_count, 1, 0);
     const double* const z0 = cheb_steps_and_rz(L, nullptr, nullptr, 5);
@@ -1068,7 +525,7 @@ const double* mg_cycle_and_rz(PcgLoop& L, int which) {
 void mg_first(PcgLoop& L) {
     PcgWorkspace& w = L.w;
     HIP_CHECK(hipMemsetAsync(L.record(), 0, sizeof(ChebScalars), kStream));
-    L.spmv([&] { L.run_A(w.x, w.Ap); });
+    L.product(w.x, w.Ap);
     L.blas([&] { launch_pcg_init(false, L.n, w.b, w.Ap, nullptr, w.r, w.p, w.partials); });
     L.reduce(L.vec_count, 1, 0);
     if (!L.failed) L.first_direction(mg_cycle_and_rz(L, 5));
@@ -1095,31 +552,7 @@ PcgKind pcg_kind_of(const SpmvAmdPrecond* m) {
 extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, const SpmvAmdPrecond* m, const double* b, double* x,
                                          const CGConfig* config, CGStats* stats) {
     // argument checks: all before the first HIP call
-    if (op == nullptr || mat == nullptr || m == nullptr || b == nullptr || x == nullptr || config == nullptr || stats == nullptr)
-        return fail("null argument"), 1;
-    if (op->run_device == nullptr) {
-        fprintf(stderr, "[PCG] operator '%s' does not support the device-native interface\n", op->name ? op->name : "?");
-        return 1;
-    }
-    if (config->max_iters < 0) return fail("max_iters < 0"), 1;
-    const DiagonalSource d = diagonal_source_of(op);
-    if (d.owner != nullptr) {
-        if (!d.ready) {
-            fprintf(stderr, "[PCG] operator '%s' used before init\n", op->name);
-            return 1;
-        }
-        if (d.rows != d.cols || mat->rows != d.rows) {
-            fprintf(stderr, "[PCG] the operator holds a %d x %d matrix, mat->rows = %d: a square system of that size is required\n", d.rows,
-                    d.cols, mat->rows);
-            return 1;
-        }
-    }
-    if (mat->rows < 1) return fail("mat->rows < 1"), 1;
-    if (m->n != mat->rows) {
-        fprintf(stderr, "[PCG] the preconditioner is for %d rows, mat->rows = %d\n", m->n, mat->rows);
-        return 1;
-    }
-    if (!precond_matches(op, m, d)) return 1;
+    if (!check_solve_arguments("PCG", op, mat, m, b, x, config, stats) || !check_solve_system("PCG", op, mat, m)) return 1;
     const int n = mat->rows;
     const CGConfig cfg = *config;
     const PcgKind kind = pcg_kind_of(m);
@@ -1154,7 +587,7 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
             if (fused) {
                 pap_count = f.launch(w.p, w.Ap, w.partials, nullptr, false, nullptr, kStream);
             } else {
-                L.run_A(w.p, w.Ap);
+                operator_product("PCG", op, w.p, w.Ap, L.failed);
                 launch_dot_partials((size_t)n, w.p, w.Ap, w.partials, kStream);
             }
         });
@@ -1170,28 +603,14 @@ extern "C" int spmv_amd_pcg_solve_device(SpmvOperator* op, MatrixData* mat, cons
     T.total.end(kStream);
     const double total_ms = T.total.elapsed_ms();
     HIP_CHECK(hipGetLastError());
-    download(x, w.x, (size_t)n);
-    const int count = h.iterations + 1 < w.hist_cap ? h.iterations + 1 : w.hist_cap;
-    g_pcg_history.assign((size_t)count, 0.0);
-    download(g_pcg_history.data(), w.hist, (size_t)count);
+    download_solution(x, w.x, n, h.iterations, w.hist, w.hist_cap, g_pcg_history);
     g_mg_cycles = L.cycles;
     g_cheb_step_launches = 0;
     if (L.step_counter != nullptr) download(&g_cheb_step_launches, L.step_counter, 1);
     if (L.failed) return 1;
 
-    fill_device_stats(stats, h.iterations, h.converged != 0, h.residual, h.b_norm, cfg, total_ms, T.t_spmv, T.t_blas, T.t_red);
-    solution_checksums(x, n, &stats->solution_sum, &stats->solution_norm);
-    if (cfg.verbose >= 1) {
-        if (h.breakdown) printf("[PCG-DEVICE] Breakdown in iteration %d (pAp or r.z zero or not finite)\n", h.iterations);
-        printf("[PCG-DEVICE] Converged: %s\n", stats->converged ? "YES" : "NO");
-        printf("[PCG-DEVICE] Iterations: %d\n", stats->iterations);
-        printf("[PCG-DEVICE] Final residual: %e\n", stats->residual_norm);
-        printf("[PCG-DEVICE] Time breakdown:\n");
-        printf("     Total:      %.3f ms\n", stats->time_total_ms);
-        printf("     SpMV:       %.3f ms\n", stats->time_spmv_ms);
-        printf("     BLAS1:      %.3f ms\n", stats->time_blas1_ms);
-        printf("     Reductions: %.3f ms\n", stats->time_reductions_ms);
-    }
+    const SolveSummary done{h.iterations, h.converged != 0, h.residual, h.b_norm, h.breakdown ? "pAp or r.z" : nullptr};
+    report_solve("PCG", done, x, n, cfg, T, total_ms, stats);
     return 0;
 }
 
@@ -1227,7 +646,7 @@ extern "C" int spmv_amd_pcg_stage(const char* stage, const char* kind, SpmvAmdPc
     bool jac = false;
     if (st != kReduce) {
         const int k = kind_of(kind);
-        if (k < 0) return refuse("unknown preconditioner kind (none, jacobi)"), 1;
+        if (k != kNone && k != kJacobi) return refuse("unknown preconditioner kind (none, jacobi)"), 1;
         jac = k == kJacobi;
         if (a->n < 1 || a->n > (size_t)INT_MAX) return refuse("n < 1 or beyond the solver's int rows"), 1;
         if (jac && !pointer("dinv", a->dinv, 16)) return 1;

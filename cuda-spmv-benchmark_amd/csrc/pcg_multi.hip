@@ -57,8 +57,6 @@ constexpr const char* kTag = "PCG-MULTI";
 // The kind as the kernels see it: what z is made of decides the loads.
 constexpr int kPlain = 0, kJac = 1, kCheb = 2;
 
-__device__ __forceinline__ bool usable(double v) { return v != 0.0 && isfinite(v); }
-
 // R = b - A x0 (R holds b on entry), z0 = M^-1 r0 as far as one pass goes, the partials of r.r (value 0) and r.z (value 1).
 // kPlain / kJac: z = r / dinv r, P = z. kCheb: term 0 in registers -- u = dinv r ; d = c0 u ; z = d -- to D and Z; the r.z partials only
 // when term 0 is the whole polynomial (last).

@@ -1,7 +1,11 @@
-// precond.hpp -- what pcg.hip (the preconditioned loop, kinds "none", "jacobi", "chebyshev") and multigrid.hip (kind "multigrid",
-// DESIGN.md section 15; its hierarchy and launches: multigrid.hpp) share: the preconditioner record, pcg.hip's set-up passes, the runner of a Chebyshev step -- the multigrid
-// smoother IS section 14's application, run by the same function on a level's operator --, and the multigrid cycle the loop calls.
+// precond.hpp -- the preconditioner record and what its users share. precond.hip owns the record: the creators with their set-up passes
+// (diagonal, Gershgorin bound, Chebyshev coefficients), the runner of a Chebyshev step, spmv_amd_precond_apply_device, info and destroy.
+// pcg.hip (the preconditioned loop), bicgstab.hip, gcr.hip, the batched solvers and multigrid.hip (kind "multigrid", DESIGN.md section
+// 15; its hierarchy and launches: multigrid.hpp) reach those through this header -- the multigrid smoother IS section 14's application,
+// run by the same function on a level's operator -- and precond.hip reaches pcg.hip's term-0 kernel and reduce launch through it.
 #pragma once
+
+#include <string.h>
 
 #include "device_runtime.hpp"
 #include "solve_common.hpp"
@@ -12,6 +16,16 @@ struct MgHierarchy;  // multigrid.hpp
 
 enum PrecondKind { kNone = 0, kJacobi = 1, kChebyshev = 2, kMultigrid = 3 };
 constexpr int kChebMaxDegree = 32;
+
+// The kind a caller names, or -1. An entry point that takes "none" and "jacobi" alone refuses the other two itself.
+inline int kind_of(const char* kind) {
+    if (kind == nullptr) return -1;
+    if (!strcmp(kind, "none")) return kNone;
+    if (!strcmp(kind, "jacobi")) return kJacobi;
+    if (!strcmp(kind, "chebyshev")) return kChebyshev;
+    if (!strcmp(kind, "multigrid")) return kMultigrid;
+    return -1;
+}
 
 struct SpmvAmdPrecond {
     int kind = kNone;
@@ -41,12 +55,12 @@ void stage_run(StageTimers* T, double StageTimers::*acc, F&& launch) {
     else launch();
 }
 
-// ---- pcg.hip ----
+// ---- precond.hip ----
 // dinv of a CSR by the diagonal pass (d_i = the sum of row i's entries in column i, CSR order, from 0.0; dinv_i = 1.0 / d_i) with its
 // validity rule. Returns the device array, or null: a row at fault is named on stderr behind `who` ("jacobi", "multigrid: level 2")
 // and, where bad_row is not null, stored there; no device memory is said too. Synchronises.
 double* inverse_diagonal_of_csr(const SlabCsr& m, int n, const char* who, int* bad_row);
-// The symmetric Gershgorin bound of D^-1/2 A D^-1/2 (pcg.hip, gershgorin_kernel). Synchronises.
+// The symmetric Gershgorin bound of D^-1/2 A D^-1/2 (precond.hip, gershgorin_kernel). Synchronises.
 double gershgorin_of_csr(const SlabCsr& m, int n, const double* dinv);
 // c0, h_1, g_1, ... of the degree-k Chebyshev polynomial on [lmin, lmax] (api.h states the operations).
 void chebyshev_coefficients(int degree, double lmin, double lmax, double* coef);
@@ -57,8 +71,33 @@ bool creation_source(const SpmvOperator* op, const char* label, const char* not_
 // What every entry point that takes (op, m) checks of the pair before any HIP call; d: the operator's storage view. False: refused,
 // said on stderr behind [PCG].
 bool precond_matches(const SpmvOperator* op, const SpmvAmdPrecond* m, const DiagonalSource& d);
-// term 0 from a residual that is only read: u = dinv r ; d = c0 u ; z = d (cheb_term0_kernel<2>, no partials)
-void launch_cheb_term0_apply(size_t n, const double* r, const double* dinv, double c0, double* d, double* z);
+
+// ---- pcg.hip: what an application on its own (spmv_amd_precond_apply_device, gcr.hip) takes from the preconditioned loop ----
+// Device scalars of one preconditioned solve.
+struct PcgScalars {
+    double rz;        // r.z of the current residual
+    double pAp, alpha, beta;
+    double b_norm;    // ||r0||
+    double residual;  // ||r_k||
+    int iterations;
+    int converged;    // stopping test met
+    int breakdown;    // pAp or r.z' zero or not finite: stopped, not converged
+    int skip_update;  // this iteration's pAp broke down: r and x stay as they are
+};
+// The device record of a Chebyshev solve: the scalars every kind keeps, then what only this kind needs. pcg_step's steps 3 to 5 are
+// handed the record's first member and reach the rest through it.
+struct ChebScalars {
+    PcgScalars s;
+    int stop;        // the iteration's verdict (converged or broken down): the steps' skip flag
+    int steps_done;  // step launches that did work
+};
+// term 0 from a residual that is only read: u = dinv r ; d = c0 u ; z = d (cheb_term0_kernel<2>). last (term 0 is the whole
+// polynomial): the partials of r.z at partials[stream_grid(n) + blk]; else no partials.
+void launch_cheb_term0_apply(size_t n, const double* r, const double* dinv, double c0, double* d, double* z, bool last = false,
+                             double* partials = nullptr);
+// nv sums of `count` partials each and the scalar step `which` (pcg.hip has the steps; 5: rz = the sum, an application on its own)
+void launch_pcg_reduce(const double* partials, int count, int nv, int which, double* stage, PcgScalars* s, double tol, double* hist,
+                       int hist_cap);
 
 // One Chebyshev application in flight on one operator or level: t = fma(-1, A z, r) ; u = dinv t ; d = fma(g, u, h d) ; z = z + d.
 // cheb_step runs one step in the form `a` allows: on a row-lds plan the fused launch (z' goes to aux, then z and aux change places),
@@ -82,6 +121,8 @@ struct ChebRun {
 };
 bool cheb_step(ChebRun& c, double g, double h, bool last);
 bool cheb_steps(ChebRun& c, int degree, const double* coef, bool report);
+// Steps 1 .. degree of m's polynomial behind a term 0 that left d and z in c -- and, at degree 0, the r.z partials behind its r.r ones.
+bool cheb_after_term0(const SpmvAmdPrecond* m, ChebRun& c);
 
 // ---- what the PCG loops call of kind "multigrid" (multigrid.hip, multigrid_multi.hip; the hierarchy itself: multigrid.hpp) ----
 void mg_destroy(MgHierarchy* h);

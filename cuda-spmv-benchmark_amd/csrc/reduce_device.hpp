@@ -229,4 +229,51 @@ __device__ __forceinline__ void reduce_slice_block(const double* __restrict__ pa
     draw_ticket_and_finish_if_last(stage, blocks, extra, extra_count, tickets, tail, s, s_last);
 }
 
+// The reduction of the single-vector preconditioned solvers (pcg.hip, bicgstab.hip, gcr.hip), called by ALL threads of every workgroup
+// of the launch: nv sums of `count` partials each, value v at partials[v * count ...], on reduce_geometry()'s slice and blocks. One
+// workgroup sums directly. More: each sums its slice of every value and publishes it at slot_of(v)[blockIdx.x] -- kReduceStageBlocks
+// slots per value, the caller's choice of where --, then draws a ticket; the workgroup that draws the last one sums the published
+// slice sums. The hand-over is the header's: publish() waits for the store's acknowledgement, the ticket is relaxed and agent scope,
+// no fence. True: this workgroup holds the totals and its thread 0 has written total[v] (registers or LDS: only thread 0 takes the
+// scalar step); false: another workgroup does. NV > 0: nv is NV at compile time; 0: a run-time nv. sh: kReduceBlock doubles of LDS.
+template <int NV, class SlotOf>
+__device__ __forceinline__ bool sum_values_last_block(const double* __restrict__ partials, int count, int nv, int slice, int blocks,
+                                                      unsigned* ticket, SlotOf&& slot_of, double* __restrict__ sh, int* __restrict__ s_last,
+                                                      double* total) {
+    constexpr int kUnroll = NV > 0 ? NV : 1;  // a run-time nv: the loops stay loops
+    if (NV > 0) nv = NV;
+    if (blocks > 1) {
+        const int lo = (int)blockIdx.x * slice, hi = min(lo + slice, count);
+#pragma unroll kUnroll
+        for (int v = 0; v < nv; ++v) {
+            block_tree(strided_sum(partials + (long long)v * count, lo, hi), sh);
+            if (threadIdx.x == 0) publish(slot_of(v) + blockIdx.x, sh[0]);
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            const unsigned drawn = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            *s_last = drawn == (unsigned)(blocks - 1) ? 1 : 0;
+            if (*s_last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next reduction on this stream
+        }
+        __syncthreads();
+        if (*s_last == 0) return false;
+#pragma unroll kUnroll
+        for (int v = 0; v < nv; ++v) {
+            double acc = 0.0;
+            for (int i = (int)threadIdx.x; i < blocks; i += kReduceBlock) acc += published(slot_of(v) + i);
+            block_tree(acc, sh);
+            if (threadIdx.x == 0) total[v] = sh[0];
+            __syncthreads();
+        }
+    } else {
+#pragma unroll kUnroll
+        for (int v = 0; v < nv; ++v) {
+            block_tree(strided_sum(partials + (long long)v * count, 0, count), sh);
+            if (threadIdx.x == 0) total[v] = sh[0];
+            __syncthreads();
+        }
+    }
+    return true;
+}
+
 }  // namespace spmv_amd

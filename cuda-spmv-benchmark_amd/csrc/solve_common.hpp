@@ -1,10 +1,13 @@
-// solve_common.hpp -- the host side the CG entry points share around their loops (cg_single.hip, cg_slab_solve.hip, cg_multi.hip,
-// pcg.hip, pcg_multi.hip): checksums of the solution, the per-stage timers, the statistics rule of a device solve, the history
-// hand-out and the two halves of a workspace request. The loops, their kernels and their print-outs stay each solver's own; what the
-// two batched solvers share beyond this (workspace, checks, upload, download, print-out) is multi_solve.hpp, built on this header.
+// solve_common.hpp -- the host side every solve entry point shares around its loop (cg_single.hip, cg_slab_solve.hip, pcg.hip,
+// bicgstab.hip, gcr.hip and the batched solvers): checksums of the solution, the per-stage timers, the statistics rule of a device
+// solve, the history hand-out, the two halves of a workspace request and the refusals of the LAB build's stage hooks. The loops and
+// their kernels stay each solver's own. Two scaffolds are built on this header: multi_solve.hpp, what the batched solvers share beyond
+// it (workspace, checks, upload, download, print-out), and single_solve.hpp, what pcg.hip, bicgstab.hip and gcr.hip share (checks,
+// the product, download, print-out).
 #pragma once
 
 #include <math.h>
+#include <stdint.h>
 #include <stdio.h>
 
 #include <vector>
@@ -87,6 +90,26 @@ inline bool grow_history(double*& hist, int& cap, int want, size_t columns = 1) 
     hist = device_try_alloc<double>(columns * (size_t)want);
     if (hist == nullptr) return false;
     cap = want;
+    return true;
+}
+
+// ---- the LAB build's stage hooks (include/spmv_amd/lab.h): their refusals ----
+inline bool stage_fail(const char* tag, const char* stage, const char* what) {
+    fprintf(stderr, "[%s] stage '%s': %s: refused\n", tag, stage ? stage : "(null)", what);
+    return false;
+}
+
+// A pointer the stage needs, aligned to `align` bytes (16: a vector the kernels access in 16-byte pairs; 8: doubles one at a time).
+inline bool stage_pointer(const char* tag, const char* stage, const char* name, const void* p, int align) {
+    char what[64];
+    if (p == nullptr) {
+        snprintf(what, sizeof what, "%s is null", name);
+        return stage_fail(tag, stage, what);
+    }
+    if (((uintptr_t)p & (uintptr_t)(align - 1)) != 0) {
+        snprintf(what, sizeof what, "%s is not %d-byte aligned", name, align);
+        return stage_fail(tag, stage, what);
+    }
     return true;
 }
 

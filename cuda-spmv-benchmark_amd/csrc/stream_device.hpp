@@ -14,6 +14,9 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// A scalar a solver may divide by: not zero and finite (else the iteration is a breakdown).
+__device__ __forceinline__ bool usable(double v) { return v != 0.0 && isfinite(v); }
+
 // 16-byte accesses of streams that are read / written once per pass
 __device__ __forceinline__ d2 load_once(const double* __restrict__ base, size_t pair) {
     return __builtin_nontemporal_load(reinterpret_cast<const d2*>(base) + pair);

@@ -303,7 +303,7 @@ int spmv_amd_cg_last_history_multi(int rhs, double* out, int cap);
  * spmv_amd_cg_release_workspace()) or before the first batched solve. No HIP call. */
 size_t spmv_amd_cg_multi_workspace_bytes(void);
 
-/* ---- preconditioned CG (csrc/pcg.hip) ----
+/* ---- preconditioned CG (csrc/pcg.hip, the preconditioner record csrc/precond.hip) ----
  * z = M^-1 r with M = diag(A) ("jacobi") or I ("none"); otherwise the algebra, stopping rule (true residual, strict <, the
  * converging iteration counted), statistics, timer rule and verbose semantics of cg_solve_device (verbose lines tagged
  * [PCG-DEVICE]). A pAp or r.z that is zero or not finite stops the solve in that iteration with converged = 0 and x finite;

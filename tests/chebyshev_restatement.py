@@ -1,4 +1,4 @@
-"""numpy restatement of the Chebyshev polynomial preconditioner of csrc/pcg.hip: the coefficient recurrence
+"""numpy restatement of the Chebyshev polynomial preconditioner of csrc/precond.hip: the coefficient recurrence
 in Python floats, the symmetric Gershgorin bound, the application z = M^-1 r -- bit for bit when it is given the operator's own
 product and a fused multiply-add (the oracle's spmv_* and axpy), to rounding with plain numpy --, the preconditioned loop of
 pcg_restatement._loop with a preconditioner callable, and the table of systems the whole-solve tests use."""

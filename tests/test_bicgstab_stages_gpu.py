@@ -218,7 +218,7 @@ def reduce_stage(Blab, partials_ptr, count, which, incoming, tol=0.0, hist_ptr=N
 
 @pytest.mark.parametrize("count", COUNTS)
 def test_reduction_alone(Blab, count):
-    """One value (step 0 leaves the total in rho) and two (step 3: omega = total 0 / total 1; step 4 with rho = alpha = omega = 1
+    """One value (step 0 leaves the total in rho, step 1 in sigma, step 2 its root in s_norm) and two (step 3: omega = total 0 / total 1; step 4 with rho = alpha = omega = 1
     leaves sqrt(total 0) in residual and total 1 in rho and beta): reduce_pcg's bits, twice the same, what follows a single value
     is not read, and a sum behind a verdict changes no field."""
     rng = np.random.default_rng(count)
@@ -228,6 +228,10 @@ def test_reduction_alone(Blab, count):
     for _ in range(2):
         sc = reduce_stage(Blab, one.ptr, count, 0, scalars(Blab))
         assert bits(sc.rho) == bits(want0) and bits(sc.b_norm) == bits(np.sqrt(want0))
+        sc = reduce_stage(Blab, one.ptr, count, 1, scalars(Blab, rho=1.0))
+        assert bits(sc.sigma) == bits(want0) and bits(sc.alpha) == bits(np.float64(1.0) / np.float64(want0)) and sc.stop == 0
+        sc = reduce_stage(Blab, one.ptr, count, 2, scalars(Blab, b_norm=1.0))
+        assert bits(sc.s_norm) == bits(np.sqrt(want0)) and sc.stop == 0
     two = Guarded(Blab, np.concatenate([v0, v1]))
     t0, t1 = R.reduce_pcg(np.concatenate([v0, v1]), count, 2)
     assert bits(t0) == bits(want0)

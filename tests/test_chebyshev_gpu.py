@@ -1,4 +1,4 @@
-"""The Chebyshev polynomial preconditioner (csrc/pcg.hip) on the GPU: the coefficients and the automatic interval
+"""The Chebyshev polynomial preconditioner (csrc/precond.hip, its loop in csrc/pcg.hip) on the GPU: the coefficients and the automatic interval
 the library reports, the application z = M^-1 r bit for bit against tests/chebyshev_restatement.py on the fused row-lds step and on
 the unfused step of every operator, the verdict flag that keeps the converging iteration from streaming, whole solves against the
 restatement run with the library's reported interval, and refusals, lifetime and the application's --precond=chebyshev."""

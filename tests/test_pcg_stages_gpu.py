@@ -9,6 +9,8 @@ import math
 import numpy as np
 import pytest
 
+import reduction_restatement as R
+
 pytestmark = pytest.mark.gpu
 
 # one workgroup covers 128 elements; 131 073 is the largest n of the one-workgroup reduction (1024 partials, odd tail),
@@ -62,6 +64,10 @@ def vectors(n, kind, salt):
 
 def z_of(kind, dinv, r):
     return r.copy() if kind == "none" else dinv * r  # one product per element
+
+
+def bits(x):
+    return np.float64(x).view(np.uint64)
 
 
 def reduce_stage(Blab, partials_ptr, count, which, incoming=None, tol=0.0, hist_ptr=None, hist_cap=0):
@@ -171,7 +177,8 @@ def test_update_xp_stage(Blab, O, n, kind):
 @pytest.mark.parametrize("count", COUNTS)
 def test_reduction_alone(Blab, count):
     """Caller partials, value 1 another random array than value 0: one value (step 1 leaves the total in pAp) and two (step 0:
-    b_norm = sqrt(total 0), so value 0 is non-negative there; step 2 with rz = 1 leaves total 1 in beta and rz)."""
+    b_norm = sqrt(total 0), so value 0 is non-negative there; step 2 with rz = 1 leaves total 1 in beta and rz). Every total has
+    reduction_restatement.reduce_pcg's bits: one workgroup, two with a short last slice, 256 with one."""
     rng = np.random.default_rng(count)
     v0, v1, vs = rng.standard_normal(count) ** 2, rng.standard_normal(count), rng.standard_normal(count)
     one = Guarded(Blab, np.concatenate([vs, np.full(count, np.nan)]))  # what follows value 0 is not read
@@ -179,6 +186,7 @@ def test_reduction_alone(Blab, count):
     err = abs(got - math.fsum(vs))
     print(f"count={count}: one value err {err / float(np.sum(np.abs(vs))):.2e} of sum|terms|")
     assert err <= SUM_TOL * float(np.sum(np.abs(vs)))
+    assert bits(got) == bits(R.reduce_pcg(vs, count, 1)[0])
     assert reduce_stage(Blab, one.ptr, count, 1, Blab.PcgScalars(rz=1.0)).pAp == got
     two = Guarded(Blab, np.concatenate([v0, v1]))
     b_norm, rz = two_sums(Blab, two.ptr, count)
@@ -186,6 +194,8 @@ def test_reduction_alone(Blab, count):
     print(f"count={count}: two values err {e0 / math.fsum(v0):.2e}, {e1 / float(np.sum(np.abs(v1))):.2e} of sum|terms|")
     assert e0 <= SUM_TOL * math.fsum(v0) and e1 <= SUM_TOL * float(np.sum(np.abs(v1)))
     assert two_sums(Blab, two.ptr, count) == (b_norm, rz)
+    t0, t1 = R.reduce_pcg(np.concatenate([v0, v1]), count, 2)
+    assert bits(b_norm) == bits(np.sqrt(np.float64(t0))) and bits(rz) == bits(t1)
     sc = reduce_stage(Blab, two.ptr, count, 2, Blab.PcgScalars(rz=1.0, b_norm=1.0), tol=0.0)
     assert sc.residual == b_norm and sc.beta == rz and sc.rz == rz and sc.converged == 0 and sc.breakdown == 0
     assert np.array_equal(two.read(), np.concatenate([v0, v1]))
