@@ -365,6 +365,14 @@ def arrow(n=3000):
     return Csr(a.rp, a.ci, a.va)
 
 
+def as_a_file_gives_it(name):
+    """split33 / oneway33 of tests/poison.py: the 33 x 33 Poisson matrix with duplicate entries, stored zeros and (oneway33) partly
+    cancelling pairs and one-way entries, rows sorted, equal columns adjacent in input order. Not through csr_of: scipy would be free
+    to reorder or merge the duplicates."""
+    import poison
+    return Csr(*getattr(poison, name)())
+
+
 SYSTEMS = {
     "poisson33": lambda: poisson2d(33), "poisson64": lambda: poisson2d(64), "poisson127": lambda: poisson2d(127),
     "permuted33": lambda: permuted(poisson2d(33), 33), "permuted64": lambda: permuted(poisson2d(64), 64),
@@ -373,6 +381,7 @@ SYSTEMS = {
     "nine24": lambda: ninepoint(24), "nine64": lambda: ninepoint(64),
     "graph1500": lambda: knn_laplacian(1500, seed=1500), "graph6000": lambda: knn_laplacian(6000, seed=6000),
     "arrow3000": arrow,
+    "split33": lambda: as_a_file_gives_it("split33"),
 }
 
 
@@ -396,6 +405,13 @@ def upwind33():
     return csr_of(A), b, x0
 
 
+def oneway33():
+    """The second nonsymmetric row: oneway33 of tests/poison.py, b ~ N(0, 1) seeded by its rows, x0 = 0."""
+    M = as_a_file_gives_it("oneway33")
+    n = rows_of(M)
+    return M, np.random.default_rng(n).standard_normal(n), np.zeros(n)
+
+
 # (system, nu, iterations of AMG-PCG in both CPU roundings at tol 1e-6 from x0 = 0, b ~ N(0, 1)); JACOBI: the Jacobi-PCG counts of the
 # same restatement. tests/test_amg_host.py re-runs every row in both roundings.
 TABLE = [
@@ -411,13 +427,15 @@ TABLE = [
     ("nine64", 0, 18), ("nine64", 1, 13), ("nine64", 2, 10),
     ("graph1500", 0, 25), ("graph1500", 1, 18), ("graph1500", 2, 15),
     ("graph6000", 0, 29), ("graph6000", 1, 19), ("graph6000", 2, 16),
+    ("split33", 1, 12),
 ]
 JACOBI = {"poisson33": 87, "poisson64": 152, "poisson127": 320, "permuted64": 166, "aniso64": 275, "cube9": 31, "cube16": 52,
-          "cube24": 74, "nine24": 46, "nine64": 107, "graph1500": 193, "graph6000": 338}
+          "cube24": 74, "nine24": 46, "nine64": 107, "graph1500": 193, "graph6000": 338, "split33": 87}
 # the level rows of the automatic hierarchies (theta = 0.08)
 LEVEL_ROWS = {"poisson33": [1089, 195, 28], "poisson64": [4096, 704, 88, 17], "poisson127": [16129, 2720, 319, 54],
               "permuted64": [4096, 588, 78, 8], "aniso64": [4096, 1408, 512, 192, 64], "cube9": [729, 96, 14],
               "cube16": [4096, 514, 74, 11], "cube24": [13824, 1685, 215, 31], "nine24": [576, 64], "nine64": [4096, 484, 88, 14],
-              "graph1500": [1500, 137, 20], "graph6000": [6000, 523, 75, 11]}
+              "graph1500": [1500, 137, 20], "graph6000": [6000, 523, 75, 11], "split33": [1089, 195, 28]}
 # GCR(16) on upwind33 at nu = 1, tol 1e-6: iterations in both CPU roundings
 GCR_ROW = ("upwind33", 1, 16, 10)
+GCR_ROW_ONEWAY = ("oneway33", 1, 16, 16)  # the same on oneway33 (levels 1089, 198, 30)

@@ -1,4 +1,6 @@
-"""Poisoned inputs for the stencil kernels (tests/test_poison_host.py, tests/test_poison_gpu.py). Test infrastructure only.
+"""Poisoned inputs for the stencil kernels (tests/test_poison_host.py, tests/test_poison_gpu.py) and, in the section "general CSR" at
+the end, for the AMG transfers and the CSR family (tests/test_poison_csr_host.py, tests/test_poison_csr_gpu.py). Test infrastructure
+only.
 
 A kernel that reads a value its row does not hold and cancels it -- multiplies it by 0.0, adds it to a sum -- changes no bit on finite
 data. With +inf at such a place the product is NaN, with -0.0 over a whole neighbourhood a sum started at +0.0 differs from a bare
@@ -350,3 +352,296 @@ def chebyshev_system(n, case):
     for a in (s.va, s.x, s.x_at, s.coef_at):
         a.setflags(write=False)
     return s
+
+
+# ================================================================ general CSR: the AMG transfers and the CSR family
+# (tests/test_poison_csr_host.py, tests/test_poison_csr_gpu.py)
+#
+# amg_residual_restrict_kernel and its batched form (csrc/amg.hip, csrc/amg_multi.hip) give eight lanes to an aggregate and eight
+# aggregates to a wave; the round count is the wave's maximum, so a group that is done keeps shuffling with `have <= 0`. The seams are
+# between the members of one round, between rounds, between the eight groups of a wave and between waves. Aggregate I is group I % 8
+# of wave I // 8.
+AGG_WAVES = (
+    [100, 1, 1, 1, 1, 1, 1, 1],       # 13 rounds in group 0; the seven singles sit at have <= 0 for twelve of them
+    [1, 7, 8, 9, 16, 17, 2, 100],     # the long aggregate in the last group; sizes around one and two rounds
+    [8] * 8,                          # a full wave of full single rounds
+    [9, 1, 17, 3, 8],                 # a last wave with three dead groups (live == false)
+)
+AGG_TARGETS = ((0, 0), (0, 1), (1, 7), (2, 0), (3, 4), (1, 3))  # (wave, group)
+AGG_PLANTERS = ("r_inf", "z_inf", "coef_inf", "negzero_sum", "negzero_chain")
+AGG_POOL = 2000      # the common columns [0, 2000); the reserved band lies behind them
+AGG_SEED = 2900
+
+AggLevel = collections.namedtuple("AggLevel", "rp ci va count agg agg_ptr members z r cols reserved free_rows")
+AggCase = collections.namedtuple("AggCase", "planter target slot rp ci va z r rows_at planted touched")
+# rows_at: the fine rows the poison was planted at; planted: the coarse rows that may be non-finite; touched: the coarse rows whose
+# inputs differ from the clean level's (every other coarse row must come out with the clean run's bits)
+
+
+def coarse_of(target):
+    return 8 * target[0] + target[1]
+
+
+@functools.lru_cache(maxsize=1)
+def aggregate_level():
+    """One level for the restriction: 29 aggregates of AGG_WAVES' sizes, members dealt at random and ascending inside each aggregate,
+    five more rows owned by nobody. Rows hold 0, 1, 5 or 70 entries with values in U(0.25, 3); the members at slots 0, 7, 8 and last
+    of every target aggregate hold 5, 70, 1 and 5 (a later slot wins where two coincide), so a poison can be planted there. Columns
+    come from the pool [0, 2000); every non-empty member row of a target aggregate also holds, as its last entry, a reserved column of
+    its own behind the pool that no other row refers to (reserved[row], else -1): poison in z there reaches that row alone. z and r are
+    standard normal, z nowhere zero. Built once, never written."""
+    rng = np.random.default_rng(AGG_SEED)
+    sizes = np.array([s for wave in AGG_WAVES for s in wave], dtype=np.int64)
+    count, owned = len(sizes), int(sizes.sum())
+    rows = owned + 5
+    deal = rng.permutation(rows)
+    free_rows, deal = np.sort(deal[:5]), deal[5:]
+    agg_ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    members = np.concatenate([np.sort(deal[agg_ptr[I]:agg_ptr[I + 1]]) for I in range(count)]).astype(np.int32)
+    agg = np.full(rows, -1, dtype=np.int32)
+    agg[members] = np.repeat(np.arange(count), sizes)
+    lengths = rng.choice([0, 1, 5, 70], size=rows, p=[0.15, 0.15, 0.6, 0.1])
+    reserved = np.full(rows, -1, dtype=np.int64)
+    band = AGG_POOL
+    for target in AGG_TARGETS:
+        m = members[agg_ptr[coarse_of(target)]:agg_ptr[coarse_of(target) + 1]]
+        for slot, n in ((0, 5), (7, 70), (8, 1), (len(m) - 1, 5)):
+            if slot < len(m):
+                lengths[m[slot]] = n
+        for row in m[lengths[m] > 0]:
+            reserved[row], band = band, band + 1
+    cols = band
+    body = []
+    for row in range(rows):
+        n = int(lengths[row])
+        own = [reserved[row]] if reserved[row] >= 0 else []
+        body.append(np.concatenate([np.sort(rng.choice(AGG_POOL, size=n - len(own), replace=False)), own]))
+    rp = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+    ci = np.concatenate(body).astype(np.int32)
+    va = rng.uniform(0.25, 3.0, len(ci))
+    z, r = rng.standard_normal(cols), rng.standard_normal(rows)
+    z[z == 0.0] = 1.0
+    for a in (rp, ci, va, agg, agg_ptr, members, z, r, reserved, free_rows):
+        a.setflags(write=False)
+    return AggLevel(rp, ci, va, count, agg, agg_ptr, members, z, r, cols, reserved, free_rows)
+
+
+def target_members(target, level=None):
+    L = aggregate_level() if level is None else level
+    I = coarse_of(target)
+    return L.members[L.agg_ptr[I]:L.agg_ptr[I + 1]].astype(np.int64)
+
+
+def target_slots(target):
+    """The positions inside a target: "all" (the whole aggregate), and one member at slot 0, 7, 8 or last, each once."""
+    size = len(target_members(target))
+    singles = sorted({s for s in (0, 7, 8, size - 1) if s < size})
+    return (["all"] if size > 1 else []) + singles
+
+
+def planted_coarse(rp, ci, va, z, r, agg_ptr, members):
+    """The coarse rows that may be non-finite, by plain indexing: aggregate I is in iff one of its member rows holds a non-finite r, a
+    non-finite stored value, or a column at which z is not finite."""
+    entry_hit = ~np.isfinite(va) | ~np.isfinite(z[ci])
+    row_hit = ~np.isfinite(r)
+    row_hit[row_of_entry(rp)[entry_hit]] = True
+    return np.array([I for I in range(len(agg_ptr) - 1) if row_hit[members[agg_ptr[I]:agg_ptr[I + 1]]].any()], dtype=np.int64)
+
+
+def _emptied(L, rows):
+    """The level's CSR with `rows` left without entries."""
+    keep = ~np.isin(row_of_entry(L.rp), rows)
+    lengths = np.diff(L.rp).astype(np.int64)
+    lengths[rows] = 0
+    return np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32), L.ci[keep].copy(), L.va[keep].copy()
+
+
+@functools.lru_cache(maxsize=None)
+def aggregate_case(planter, target, slot):
+    """One poisoned form of aggregate_level(), built once, never written.
+    r_inf          +inf in r at the chosen member rows: r_c = +inf at the target
+    z_inf          +inf in z at the chosen rows' reserved columns: the coefficients are positive, so r_c = -inf
+    coef_inf       +inf in one stored value of each chosen row: a non-finite r_c
+    negzero_sum    every member of the target has an empty row and r = -0.0: r_c is -0.0, a sum started at +0.0 gives +0.0
+    negzero_chain  the member at `slot` keeps its row, z = -0.0 at its columns and r = -0.0 there: its chain starts at +0.0, so its
+                   t = fma(-1.0, +0.0, -0.0) is -0.0, where a chain started from its first product gives +0.0; every other member is
+                   as in negzero_sum, so that one t decides the sign of r_c
+    "all" chooses every member (z_inf and coef_inf: every member that has an entry)."""
+    L = aggregate_level()
+    m = target_members(target)
+    I = coarse_of(target)
+    rp, ci, va, z, r = L.rp, L.ci, L.va.copy(), L.z.copy(), L.r.copy()
+    chosen = m if slot == "all" else m[[slot]]
+    touched = {I}
+    if planter == "r_inf":
+        r[chosen] = np.inf
+    elif planter in ("z_inf", "coef_inf"):
+        chosen = chosen[np.diff(rp)[chosen] > 0]
+        assert len(chosen) > 0 and (L.reserved[chosen] >= 0).all(), (target, slot)
+        if planter == "z_inf":
+            z[L.reserved[chosen]] = np.inf
+        else:
+            va[rp[chosen] + chosen % np.diff(rp)[chosen]] = np.inf
+    elif planter == "negzero_sum":
+        assert slot == "all"
+        rp, ci, va = _emptied(L, m)
+        r[m] = -0.0
+    elif planter == "negzero_chain":
+        assert slot != "all" and rp[chosen[0] + 1] > rp[chosen[0]]
+        rp, ci, va = _emptied(L, m[m != chosen[0]])
+        r[m] = -0.0
+        at = ci[rp[chosen[0]]:rp[chosen[0] + 1]]
+        z[at] = -0.0
+        holders = np.unique(row_of_entry(rp)[np.isin(ci, at)])
+        touched |= {int(a) for a in L.agg[holders] if a >= 0}
+    else:
+        raise KeyError(planter)
+    planted = planted_coarse(rp, ci, va, z, r, L.agg_ptr, L.members)
+    for a in (rp, ci, va, z, r, planted):
+        a.setflags(write=False)
+    return AggCase(planter, target, slot, rp, ci, va, z, r, chosen, planted, np.array(sorted(touched), dtype=np.int64))
+
+
+def aggregate_cases(planter):
+    """Every (planter, target, slot) of the table: the inf planters at every slot of every target, negzero_sum on whole targets,
+    negzero_chain at the single slots."""
+    out = []
+    for target in AGG_TARGETS:
+        slots = target_slots(target)
+        if planter == "negzero_sum":
+            slots = ["all"]
+        elif planter == "negzero_chain":
+            slots = [s for s in slots if s != "all"]
+        out += [(planter, target, s) for s in slots]
+    return out
+
+
+AGG_TABLE = [c for planter in AGG_PLANTERS for c in aggregate_cases(planter)]
+
+
+@functools.lru_cache(maxsize=None)
+def aggregate_reference(planter=None, target=None, slot=None):
+    """r_c = restrict(r - A z) of a case (no planter: of the clean level): the oracle's sequential chain, its fma for the residual,
+    amg_restatement.restrict for the sum over the members from the first member's t. Computed once, shared, never written."""
+    import amg_restatement as AMG
+    from oracle import oracle as O
+
+    L = aggregate_level()
+    c = L if planter is None else aggregate_case(planter, target, slot)
+    with np.errstate(invalid="ignore"):
+        t = O.axpy(-1.0, O.spmv_csr(c.rp, c.ci, c.va, c.z), c.r)
+        out = AMG.restrict(t, AMG.Aggregates(L.count, L.agg, L.agg_ptr, L.members))
+    out.setflags(write=False)
+    return out
+
+
+# ---- the prolongation
+PROLONG_ROWS = (1, 2, 3, 129, 4225)
+ProlongLevel = collections.namedtuple("ProlongLevel", "rows coarse_rows agg z ec")
+
+
+@functools.lru_cache(maxsize=None)
+def prolong_level(rows):
+    """agg deals the rows to max(1, min(rows, max(2, rows // 4))) aggregates at random, none empty; rows 0 and 1 -- one 16-byte pair
+    -- lie in different aggregates wherever there are two rows (at 129 and 4 225 most pairs do); an odd `rows` leaves the last row
+    outside every pair. z and e_c standard normal."""
+    rng = np.random.default_rng(7100 + rows)
+    coarse_rows = max(1, min(rows, max(2, rows // 4)))
+    agg = rng.permutation(np.arange(rows) % coarse_rows).astype(np.int32)
+    if rows > 1 and agg[0] == agg[1]:
+        other = int(np.flatnonzero(agg != agg[0])[0])
+        agg[1], agg[other] = agg[other], agg[1]
+    z, ec = rng.standard_normal(rows), rng.standard_normal(coarse_rows)
+    for a in (agg, z, ec):
+        a.setflags(write=False)
+    return ProlongLevel(rows, coarse_rows, agg, z, ec)
+
+
+def prolong_cases(rows):
+    """(label, e_c, z, I): +inf in e_c at aggregate I = 0, a middle one and the last one (each once), and the -0.0 case (I None):
+    e_c = -0.0 and z = -0.0 everywhere give -0.0 everywhere."""
+    L = prolong_level(rows)
+    out = []
+    for I in sorted({0, L.coarse_rows // 2, L.coarse_rows - 1}):
+        ec = L.ec.copy()
+        ec[I] = np.inf
+        out.append((f"inf@{I}", ec, L.z, I))
+    out.append(("negzero", np.full(L.coarse_rows, -0.0), np.full(rows, -0.0), None))
+    return out
+
+
+# ---- two CSR matrices as a file gives them: sorted rows in which equal columns stay adjacent in input order
+def _poisson(n):
+    rp, ci, _ = stencil_csr(n, 2, np.random.default_rng(0))
+    return rp, ci, np.where(row_of_entry(rp) == ci, 4.0, -1.0)
+
+
+def _with_twins(rp, ci, va, first, second):
+    """Entry k stays alone where second[k] is NaN, else becomes the adjacent pair (first[k], second[k]) in its column."""
+    pair = ~np.isnan(second)
+    copies = np.where(pair, 2, 1)
+    src = np.repeat(np.arange(len(ci)), copies)
+    is_second = np.concatenate([[False], src[1:] == src[:-1]])
+    values = np.where(is_second, second[src], first[src])
+    lengths = np.bincount(row_of_entry(rp)[src], minlength=len(rp) - 1)
+    return np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32), ci[src].astype(np.int32), values
+
+
+@functools.lru_cache(maxsize=1)
+def split33():
+    """The 33 x 33 Poisson matrix with each entry v in one of three forms chosen at random: kept; split into v / 4 and 3 v / 4 (both
+    exact in fp64, as is their sum); given a stored 0.0 twin, in front of it or behind it. The summed matrix is Poisson: symmetric
+    positive definite. Returns (rp, ci, va), built once, never written."""
+    rng = np.random.default_rng(3301)
+    rp, ci, va = _poisson(33)
+    form = rng.integers(0, 3, len(ci))
+    zero_first = rng.random(len(ci)) < 0.5
+    first = np.where(form == 1, va / 4.0, np.where((form == 2) & zero_first, 0.0, va))
+    second = np.where(form == 1, 3.0 * va / 4.0, np.where(form == 2, np.where(zero_first, va, 0.0), np.nan))
+    out = _with_twins(rp, ci, va, first, second)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=1)
+def oneway33():
+    """split33 with about a tenth of its lone entries v turned into the partly cancelling pair (3 v, -2 v), and about 7 % of the
+    edges i < j left with one direction only (every stored part of the other goes). The pattern is not symmetric; every row stays
+    weakly diagonally dominant with its diagonal 4. Returns (rp, ci, va), built once, never written."""
+    rng = np.random.default_rng(3302)
+    rp, ci, va = split33()
+    rows = row_of_entry(rp)
+    n = len(rp) - 1
+    key = rows * n + ci
+    lone = np.ones(len(ci), dtype=bool)
+    lone[1:] &= key[1:] != key[:-1]
+    lone[:-1] &= key[1:] != key[:-1]
+    cancel = lone & (rng.random(len(ci)) < 0.1)
+    first, second = np.where(cancel, 3.0 * va, va), np.where(cancel, -2.0 * va, np.nan)
+    rp, ci, va = _with_twins(rp, ci, va, first, second)
+    rows = row_of_entry(rp)
+    lo, hi = np.minimum(rows, ci), np.maximum(rows, ci)
+    edges = np.unique((lo * n + hi)[rows != ci])
+    gone = edges[rng.random(len(edges)) < 0.07]
+    upper = rng.random(len(gone)) < 0.5            # which direction of the edge goes
+    gone_key = np.where(upper, (gone // n) * n + gone % n, (gone % n) * n + gone // n)
+    keep = ~np.isin(rows * n + ci, gone_key)
+    lengths = np.bincount(rows[keep], minlength=n)
+    out = (np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32), ci[keep].copy(), va[keep].copy())
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def shuffled_entries(rp, ci, va, seed):
+    """The CSR as COO entries in a random order: what a file with its lines shuffled gives."""
+    e = entries_of(rp, ci, va)
+    return e[np.random.default_rng(seed).permutation(len(e))]
+
+
+def csr_of_entries(e, rows):
+    """What build_csr_struct makes of COO entries: rows ascending, columns ascending inside a row, equal columns in input order."""
+    order = np.lexsort((e["col"], e["row"]))  # stable: ties keep the input order
+    rp = np.concatenate([[0], np.cumsum(np.bincount(e["row"], minlength=rows))]).astype(np.int32)
+    return rp, e["col"][order].astype(np.int32), np.ascontiguousarray(e["value"][order], dtype=np.float64)

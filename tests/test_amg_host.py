@@ -140,6 +140,9 @@ SETUP_CASES = [
     ("poisson33-tie", lambda: AMG.poisson2d(33), 0.25, 0),
     ("poisson33-two-levels", lambda: AMG.poisson2d(33), AMG.THETA, 2),
     ("rectangle", lambda: AMG.poisson2d(40, 13), AMG.THETA, 0),
+    # as a file gives them (tests/poison.py): duplicate entries, stored zeros, partly cancelling pairs, one-way entries
+    ("split33", lambda: AMG.as_a_file_gives_it("split33"), AMG.THETA, 0),
+    ("oneway33", lambda: AMG.as_a_file_gives_it("oneway33"), AMG.THETA, 0),
 ]
 
 
@@ -326,6 +329,21 @@ def test_gcr_on_the_upwind_stencil_in_two_roundings(O):
     name, nu, restart, iterations = AMG.GCR_ROW
     M, b, x0 = AMG.upwind33()
     levels = AMG.hierarchy(M, nu)
+    A = AMG.scipy_of(M)
+    r1 = GR.gcr(A, b, x0, AMG.make_cycle(levels), restart)
+    r2 = GR.gcr_other_rounding(A, b, x0, AMG.other_cycle(levels), restart)
+    r3 = GR.gcr_exact(lambda v: O.spmv_csr(M.rp, M.ci, M.va, v), b, x0, AMG.exact_cycle(O, levels), restart)
+    assert all(r[2] == iterations and r[3] for r in (r1, r2, r3)), [r[2:4] for r in (r1, r2, r3)]
+    assert GR.hist_err(r1[1], r2[1]) < 1e-12 and GR.hist_err(r3[1], r1[1]) < 1e-10
+
+
+def test_gcr_on_oneway33_in_two_roundings(O):
+    """The same on oneway33 -- duplicates, stored zeros, cancelling pairs and a pattern that is not symmetric --: the stored count in
+    both CPU roundings and in the exact form."""
+    name, nu, restart, iterations = AMG.GCR_ROW_ONEWAY
+    M, b, x0 = AMG.oneway33()
+    levels = AMG.hierarchy(M, nu)
+    assert [L.rows for L in levels] == [1089, 198, 30]
     A = AMG.scipy_of(M)
     r1 = GR.gcr(A, b, x0, AMG.make_cycle(levels), restart)
     r2 = GR.gcr_other_rounding(A, b, x0, AMG.other_cycle(levels), restart)

@@ -1,7 +1,8 @@
 """The two launches an AMG level adds to the batched cycle (csrc/amg_multi.hip), each on caller data through the
 LAB hook spmv_amd_amg_multi_stage, bit for bit per column against tests/amg_restatement.py for every k = 1..8: aggregates of every size
 around the eight lanes of a group and far beyond, rows of no, one, five and 1 100 entries, a last wave that is not full, every array
-between NaN paddings that keep their bits, an inf in a row no aggregate owns, and a NaN in one column that reaches no other."""
+between NaN paddings that keep their bits, an inf in a row no aggregate owns, and a NaN in one column that reaches no other. (Poison in
+the rows that ARE owned, in one column of the block, is tests/test_poison_csr_gpu.py's.)"""
 import functools
 
 import numpy as np

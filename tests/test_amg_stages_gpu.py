@@ -1,7 +1,8 @@
 """The two launches an AMG level adds to the cycle (csrc/amg.hip), each on caller data through the LAB hook
 spmv_amd_amg_stage, bit for bit against tests/amg_restatement.py: aggregates of every size around the eight lanes of a group and
 far beyond, rows of no, one, five and 1 100 entries, a last wave that is not full, every array between NaN paddings that keep their
-bits, and an inf in a row no aggregate owns."""
+bits, and an inf in a row no aggregate owns. (Poison in the rows that ARE owned -- between the members of a round, between rounds, groups
+and waves, and the signed zeros of the two sums -- is tests/test_poison_csr_gpu.py's.)"""
 import numpy as np
 import pytest
 

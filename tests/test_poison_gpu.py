@@ -1,4 +1,5 @@
-"""Poisoned inputs on the GPU: each stencil kernel reads only what its rows hold. Every test runs a kernel family on a poisoned system
+"""Poisoned inputs on the GPU: each stencil kernel reads only what its rows hold (the AMG transfers and the CSR family: the "general CSR"
+section of tests/poison.py, run by tests/test_poison_csr_gpu.py). Every test runs a kernel family on a poisoned system
 of tests/poison.py -- +inf in x at the seam positions of the 128-column tile, -0.0 over a whole neighbourhood, +inf in stored
 coefficients (the first and last entry of the matrix, where every clamped coefficient run lands, among them) -- and compares with the
 oracle through same_bits_nan_as_class: a value that is read and then cancelled (multiplied by 0.0, added to a sum) shows as a
